@@ -8,7 +8,10 @@ One "step" = one mini-batch of the hot path on ONE GPU, inputs resident in HBM:
 Default workload = the largest single-GPU configuration of BASELINE.json: papers100M-shaped
 synthetic power-law CSR (N 111,059,956, E ~1.62e9, f32 dim 128 = 56.9 GB of features), 3-hop GCN
 fanout [5,10,15] (sgnn/train_gcn.py:84), batch 8000, graph + features in HBM (cache_ratio 1.0).
-The same line carries, as sub-records measured after the timed region:
+A plain run sets up, warms up, times --steps steps once, writes the last step's outputs (--dump-outputs)
+and prints the headline.  With --full the timed steps are repeated (--repeats, median block), the gathered
+rows are checked against the generator, the box's copy rates and the gather alone are measured, and the
+same line carries, as sub-records measured after the timed region:
     host_tier     BASELINE configs[2]: the same workload with every feature row in pinned host DRAM
                   (cache_ratio 0), read zero-copy by the gather kernel, next to the box's pinned-copy rate;
     cpu_baseline  the reference's CPU sampler / extractor objects on the host cores, same graph.
@@ -40,9 +43,18 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=3,
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the timed steps repeated (--repeats 3), the row self-check, the "
+                         "box's copy rates, the gather alone and every sub-record (sampler roofline, engine, configs, host "
+                         "tier, CPU baseline; N > 1: the other stores, XGNN mode).  Default: the headline alone")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / "
+                         "float64, at most 64 MB in all; an array above its share is a fixed, seeded sample of rows): "
+                         "input_nodes, layer<i>_row / layer<i>_col (/ layer<i>_data), labels, features, counts")
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the K timed steps are run this many times (each block bracketed by barrier + synchronize); "
-                         "the line reports the MEDIAN block (a block is a few ms: one hiccup must not move the headline)")
+                         "the line reports the MEDIAN block (a block is a few ms: one hiccup must not move the headline).  "
+                         "Default: 1, with --full 3")
     ap.add_argument("--preset", default="papers100M")
     ap.add_argument("--batch", type=int, default=8000)
     ap.add_argument("--fanout", default=None, help="default: 5,10,15 (papers100M / friendster), 25,10 (products)")
@@ -130,7 +142,41 @@ def parse():
     ap.add_argument("--cache-ratio", type=float, default=1.0,
                     help="fraction of feature rows (by degree rank) resident in HBM; the rest is gathered from "
                          "pinned host memory by the same kernel (GGMS host tier)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
+    if not args.full:  # a plain run: the headline alone -- every sub-record beside it is --full's
+        args.no_cpu_baseline = args.no_host_tier = args.no_engine = args.no_configs = True
+        args.no_staged_host = args.no_sampler_roofline = args.no_xgnn_mode = True
+        args.other_stores = ""
+    return args
+
+
+DUMP_BYTES = 64_000_000  # --dump-outputs: all files together
+DUMP_FEATURE_BYTES = 24_000_000  # of which the feature rows
+
+
+def dump_positions(n, cap, salt):
+    """Positions of an n-long output that are written: all of them up to `cap`, else a fixed, seeded sample (sorted)."""
+    if n <= cap:
+        return np.arange(n)
+    return np.sort(np.random.default_rng([0x5EED, salt, n]).choice(n, cap, replace=False))
+
+
+def dump_outputs(path, arrays, features):
+    """arrays: name -> 1-D host array of ids / counts (written as float64, exact below 2**53); features: 2-D float32
+    device or host rows.  Every array above its share of DUMP_BYTES is a seeded sample of its positions."""
+    os.makedirs(path, exist_ok=True)
+    header = 1024  # an upper bound of an .npy header
+    cap = max(1, (DUMP_BYTES - DUMP_FEATURE_BYTES - header * (len(arrays) + 1)) // 8 // max(1, len(arrays)))
+    for salt, (name, a) in enumerate(sorted(arrays.items())):
+        a = np.asarray(a).reshape(-1)
+        np.save(os.path.join(path, name + ".npy"), a[dump_positions(a.size, cap, salt)].astype(np.float64))
+    rows = dump_positions(features.shape[0], max(1, DUMP_FEATURE_BYTES // max(1, 4 * features.shape[1])), len(arrays))
+    import torch
+    f = features[torch.from_numpy(rows).to(features.device)] if isinstance(features, torch.Tensor) else features[rows]
+    f = f.cpu().numpy() if isinstance(f, torch.Tensor) else f
+    np.save(os.path.join(path, "features.npy"), np.ascontiguousarray(f, dtype=np.float32))
 
 
 def usable_cores():
@@ -935,6 +981,22 @@ def main():
         log(f"pipelines trial: {per} -> {K} x {n_xs}")
     blocks, next_step = measure(extract_main, args.steps, args.warmup, repeats, first_step=first_main)
     log("main region done")
+    if args.dump_outputs and rank == 0:
+        # what a caller of the step receives from its last timed batch (the device is drained: measure() ends in a barrier)
+        last = next_step - 1
+        slot_d = last % NSLOT
+        c = sampler.counts_slots[slot_d].cpu().tolist()
+        as_ids = lambda t: t.cpu().numpy().view(np.uint32)  # noqa: E731
+        arrays = {"input_nodes": as_ids(sampler.input_nodes[slot_d][:c[3 * L]]),
+                  "labels": out_label[slot_d][:batch_seeds(last).numel()].cpu().numpy(),
+                  "counts": np.array(c, dtype=np.int64)}
+        for i in range(L):
+            arrays[f"layer{i}_row"] = as_ids(sampler.rows[slot_d][i][:c[3 * i]])
+            arrays[f"layer{i}_col"] = as_ids(sampler.cols[slot_d][i][:c[3 * i]])
+            if sampler.datas is not None:
+                arrays[f"layer{i}_data"] = as_ids(sampler.datas[slot_d][i][:c[3 * i]])
+        dump_outputs(args.dump_outputs, arrays, out[slot_d][:c[3 * L]])
+        log(f"outputs of step {last} written to {args.dump_outputs}")
     blk = median_block(blocks)
     elapsed, edges_all = blk["elapsed"], blk["edges_all"]
     edges, rows = blk["edges"], blk["rows"]
@@ -943,12 +1005,12 @@ def main():
         n_all = args.warmup + args.steps * repeats
         print("host enqueue ms/step:", {n: round(1e3 * t / n_all, 4) for n, t in zip(names, host_t)}, file=sys.stderr)
 
-    # self-check outside the timed region: the rows of the last batch in EVERY slot (with two extract streams the last two
-    # gathers ran side by side) against the generator's closed form
+    # self-check outside the timed region (--full): the rows of the last batch in EVERY slot (with two extract streams the
+    # last two gathers ran side by side) against the generator's closed form
     total_steps = args.warmup + args.steps * repeats
     last_slot = (total_steps - 1) % NSLOT
-    rows_ok = True
-    for back in range(min(NSLOT, total_steps)):
+    rows_ok = True if args.full else None
+    for back in range(min(NSLOT, total_steps) if args.full else 0):
         slot_c = (total_steps - 1 - back) % NSLOT
         n_c = int(sampler.counts_slots[slot_c][3 * L].item())
         ids = sampler.input_nodes[slot_c][:n_c].to(torch.int64)
@@ -956,13 +1018,13 @@ def main():
         want = torch.empty((ids[::stride].numel(), dim), dtype=torch.float32, device=dev)
         feat_rows(ids[::stride], want)
         rows_ok = rows_ok and n_c > 0 and bool(torch.equal(out[slot_c][:n_c][::stride], want))
-    n_last = int(sampler.counts_slots[last_slot][3 * L].item())
-    if not rows_ok:
+    if rows_ok is False:
         raise SystemExit("bench self-check failed: gathered rows differ from the feature generator")
 
-    # the same gather with nothing beside it (one stream), for reference next to the in-pipeline figure
+    # the same gather with nothing beside it (one stream), for reference next to the in-pipeline figure (--full)
     serial_us = serial_rows = None
-    if not args.no_overlap:
+    if args.full and not args.no_overlap:
+        n_last = int(sampler.counts_slots[last_slot][3 * L].item())
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         reps = 10
         counts = sampler.counts_slots[last_slot]
@@ -1004,9 +1066,9 @@ def main():
         "a2a": "k_gather_rows<16-B chunks, PlainRows> at the owner + RCCL all-to-all of ids and rows",
     }[main_store]
     # ---- what THIS box sustains (boxes of one pool differ by a few per cent; the line carries its own yardstick):
-    # a device-to-device copy (read + write bytes per second, the guide's 6.29 TB/s figure) and a pinned H2D copy
+    # a device-to-device copy (read + write bytes per second, the guide's 6.29 TB/s figure) and a pinned H2D copy (--full)
     box = None
-    if rank == 0:
+    if rank == 0 and args.full:
         import ctypes as C
         from xgnn_amd import lib as _lib
         n_copy = 1 << 30
@@ -1149,7 +1211,9 @@ def main():
         # N > 1: the headline goes to stdout NOW and the enriched line follows (the last line wins) -- the multi-GPU
         # run is the one whose sub-records (stores, engine child with a minute of start-up) can be slow or stuck under a
         # limit somebody else set.  N = 1 keeps the contract's ONE line on stdout; its early headline goes to stderr.
-        print(json.dumps(res), flush=True, file=(sys.stdout if world > 1 else sys.stderr))
+        # (A plain run has no sub-records: its one line is the final one.)
+        if args.full:
+            print(json.dumps(res), flush=True, file=(sys.stdout if world > 1 else sys.stderr))
 
     # ---- sub-records: one wall-clock budget for all of them; what no longer fits is skipped and says so -------------
     size_factor = max(0.02, meta["num_edge"] / 1.6e9)  # the default workload = 1
@@ -1386,7 +1450,7 @@ def main():
 
     # ---- N = 1: the other single-GPU configurations BASELINE.json names, one block of this script each (child process) ---
     if default_workload and not args.no_configs:
-        me = [sys.executable, os.path.abspath(__file__), "--no-host-tier", "--no-cpu-baseline",
+        me = [sys.executable, os.path.abspath(__file__), "--full", "--no-host-tier", "--no-cpu-baseline",
               "--no-sampler-roofline", "--no-configs", "--steps", str(args.steps), "--warmup", str(args.warmup),
               "--repeats", str(repeats)]
         res["configs"] = {}

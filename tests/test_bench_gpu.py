@@ -6,6 +6,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -27,7 +28,7 @@ def _last_json(stdout):
 
 
 def test_single_gpu_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--preset", "tiny", "--steps", "4", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--preset", "tiny", "--steps", "4", "--warmup", "1",
                         "--batch", "512", "--cpu-seconds", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
@@ -60,6 +61,38 @@ def test_single_gpu_line():
     assert 0 < en["log_items"]["kLogEpochCopyTime"] <= 1.05 * en["wall_s"], en
 
 
+def test_plain_run_is_the_headline_alone_and_dumps_its_last_step(tmp_path):
+    """No --full: --steps timed steps once, ONE line (stdout, no early headline), no sub-record and no check beside it;
+    --dump-outputs writes what the last timed step computed (float32 / float64 .npy, at most 64 MB), the same from run
+    to run with the same arguments, and the feature rows are the generator's rows of the dumped input nodes."""
+    runs = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--preset", "tiny", "--steps", "5", "--warmup", "2",
+                            "--batch", "512", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1 and not [l for l in r.stderr.splitlines() if l.startswith("{")]
+        d = json.loads(lines[0])
+        assert KEYS <= set(d) and d["steps"] == 5 and d["warmup"] == 2 and d["repeats"]["blocks"] == 1
+        assert d["ms_per_step"] > 0 and d["rows_verified"] is None
+        assert abs(d["value"] - d["per_gpu"]["edges_per_step"] / (d["ms_per_step"] / 1e3)) <= 1e-9 * d["value"]
+        assert d["box"] is None and not {"engine", "configs", "host_tier", "cpu_baseline", "roofline_sampler"} & set(d)
+        files = {p.name[:-4]: np.load(p) for p in out.glob("*.npy")}
+        assert set(files) == {"input_nodes", "labels", "counts", "features", "layer0_row", "layer0_col", "layer1_row",
+                              "layer1_col"}
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        assert sum(p.stat().st_size for p in out.glob("*.npy")) <= 64_000_000
+        runs.append(files)
+    a, b = runs
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    c, ids = a["counts"], a["input_nodes"].astype(np.int64)
+    assert c[3 * 2 + 1] == 0 and ids.size == c[3 * 2] > 0 and a["layer0_row"].size == c[0] and a["layer1_col"].size == c[3]
+    assert 0 < a["labels"].size <= 640 and 0 <= a["labels"].min() and a["labels"].max() < 47  # label = node id % num_class
+    dim = a["features"].shape[1]
+    assert np.array_equal(a["features"], ((ids[:, None] * dim + np.arange(dim)) & 0xFFFF).astype(np.float32))
+
+
 def test_single_gpu_line_carries_its_box_the_other_configs_and_the_staged_host_tier():
     """the N = 1 line carries `box` (what this box sustains: the yardstick between boxes) and
     `value_over_box`, the north_star read-fraction target next to the ceiling a copy can reach, a `configs` sub-record
@@ -67,7 +100,7 @@ def test_single_gpu_line_carries_its_box_the_other_configs_and_the_staged_host_t
     `host_tier.staged` (the engine's host-staged path, cache 0 and 0.64: per-phase rates of the serial sequence, effective
     rate of the chunked pipeline)."""
     env = dict(os.environ, GGMS_BENCH_TEST_CONFIGS="tiny")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--preset", "tiny", "--steps", "4", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--preset", "tiny", "--steps", "4", "--warmup", "1",
                         "--batch", "512", "--no-cpu-baseline", "--no-engine"], capture_output=True, text=True, timeout=900,
                        cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -108,7 +141,7 @@ def test_headline_is_out_before_the_sub_records_and_the_budget_bounds_them():
     import time
     env = dict(os.environ, GGMS_BENCH_TEST_ENGINE_SLEEP="600")
     t0 = time.time()
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--preset", "tiny", "--steps", "4", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--preset", "tiny", "--steps", "4", "--warmup", "1",
                         "--batch", "512", "--cpu-seconds", "20", "--budget-s", "45"], capture_output=True, text=True,
                        timeout=300, cwd=ROOT, env=env)
     wall = time.time() - t0
@@ -130,7 +163,7 @@ def test_sampling_through_logical_topology_shards_one_gpu():
     """--dist-graph 0.5 --topology-shards 2 (N = 1): the timed sampler runs through DeviceDistGraph -- two logical
     shards in HBM, the other half of the nodes read from the whole CSR in registered host memory; the rows gathered
     for the sampled input nodes still check against the generator, and the line says what it measured."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--preset", "tiny", "--steps", "4", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--preset", "tiny", "--steps", "4", "--warmup", "1",
                         "--batch", "512", "--no-cpu-baseline", "--no-host-tier", "--no-engine", "--dist-graph", "0.5",
                         "--topology-shards", "2"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -148,7 +181,7 @@ def test_two_ranks_xgnn_mode_topology_shards_in_the_main_region():
     env.update(GGMS_BENCH_DEVICE="0", GGMS_BENCH_BACKEND="gloo")
     lines = []
     for extra in ([], ["--dist-graph", "0.5"]):
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--preset", "tiny", "--steps", "4",
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--preset", "tiny", "--steps", "4",
                             "--warmup", "1", "--batch", "512", "--other-stores", "", "--no-engine", "--no-sampler-roofline",
                             "--repeats", "1", "--no-xgnn-mode"]  # one block: the line reports exactly these batches
                            + extra, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
@@ -168,7 +201,7 @@ def test_two_ranks_default_is_the_planned_placement():
     env = dict(os.environ, GGMS_BENCH_DEVICE="0", GGMS_BENCH_BACKEND="gloo")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-                        "--gpus", "2", "--preset", "tiny", "--steps", "4", "--warmup", "1", "--batch", "512"],
+                        "--full", "--gpus", "2", "--preset", "tiny", "--steps", "4", "--warmup", "1", "--batch", "512"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _last_json(r.stdout)
@@ -231,7 +264,7 @@ def test_two_ranks_whose_shards_cannot_be_mapped_report_replicas_and_say_so(tmp_
     script.write_text(_BROKEN_IPC.format(root=os.path.abspath(ROOT), bench=os.path.abspath(bench)))
     env = dict(os.environ, GGMS_BENCH_DEVICE="0", GGMS_BENCH_BACKEND="gloo")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-                        "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), str(script),
+                        "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), str(script), "--full",
                         "--gpus", "2", "--preset", "tiny", "--steps", "3", "--warmup", "1", "--batch", "512", "--no-engine"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -248,7 +281,7 @@ def test_gpus_flag_alone_starts_the_ranks():
     starts its two ranks itself and the line says n_gpus: 2 -- here both pinned to the box's one GPU by the hooks."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(GGMS_BENCH_DEVICE="0", GGMS_BENCH_BACKEND="gloo")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--preset", "tiny", "--steps", "4",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--preset", "tiny", "--steps", "4",
                         "--warmup", "1", "--batch", "512", "--other-stores", ""],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -267,7 +300,7 @@ def test_five_ranks_one_gpu_peer_and_hybrid():
     through hipIpc; main region on the sharded store, the hybrid one (hot prefix replicated) measured beside it."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(GGMS_BENCH_DEVICE="0", GGMS_BENCH_BACKEND="gloo")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "5", "--preset", "tiny", "--steps", "3",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "5", "--preset", "tiny", "--steps", "3",
                         "--warmup", "1", "--batch", "128", "--repeats", "1", "--store", "peer", "--other-stores", "hybrid",
                         "--replicate-frac", "0.25", "--no-engine"],
                        capture_output=True, text=True, timeout=1200, cwd=ROOT, env=env)
@@ -357,7 +390,7 @@ def test_two_ranks_sharing_the_gpu_at_full_size_never_stall_each_other():
     6 runs, profiles/r03_two_ranks_one_gpu_before_selfserve_lookback.txt).  A look-back now computes a predecessor
     that does not show up itself, so both ranks always finish."""
     env = dict(os.environ, GGMS_BENCH_DEVICE="0", GGMS_BENCH_BACKEND="gloo")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--store", "replica",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--store", "replica",
                         "--other-stores", "", "--no-engine", "--steps", "30"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -369,7 +402,8 @@ def _two_ranks_full_size(flags, timeout=900):
     env = dict(os.environ, GGMS_BENCH_DEVICE="0", GGMS_BENCH_BACKEND="gloo")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-                        "--gpus", "2", "--steps", "5", "--warmup", "1", "--repeats", "1", "--other-stores", ""] + flags,
+                        "--full", "--gpus", "2", "--steps", "5", "--warmup", "1", "--repeats", "1", "--other-stores", ""]
+                       + flags,
                        capture_output=True, text=True, timeout=timeout, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     return _last_json(r.stdout)

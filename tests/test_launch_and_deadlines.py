@@ -383,3 +383,56 @@ def test_streams_trial_verdict_and_slot_counts():
         for x in (1, 2):
             n = bench.slots_for(k, x)
             assert n >= k + x + 1 and n % k == 0
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)  # (imports numpy only: torch is imported inside main())
+    return bench
+
+
+def test_plain_run_is_the_headline_alone_and_full_keeps_everything(monkeypatch):
+    """bench.py's options (no GPU): a plain run times --steps steps once and turns every sub-record off; --full keeps
+    the three repeats and every sub-record unless its own --no-* flag says otherwise."""
+    bench = _bench_module()
+    off = ("no_cpu_baseline", "no_host_tier", "no_engine", "no_configs", "no_staged_host", "no_sampler_roofline",
+           "no_xgnn_mode")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert not a.full and a.steps == 7 and a.warmup == 2 and a.repeats == 1 and a.dump_outputs is None
+    assert all(getattr(a, k) for k in off) and a.other_stores == ""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-engine"])
+    a = bench.parse()
+    assert a.full and a.repeats == 3 and a.no_engine and a.other_stores == "peer,replica"
+    assert not any(getattr(a, k) for k in off if k != "no_engine")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--repeats", "2", "--dump-outputs", "somewhere"])
+    a = bench.parse()
+    assert a.repeats == 2 and a.dump_outputs == "somewhere"
+
+
+def test_dumped_outputs_are_bounded_float_arrays_and_a_fixed_sample(tmp_path):
+    """--dump-outputs (no GPU): small arrays are written whole, large ones as the same seeded sample of their positions
+    every time; ids as float64 (exact), rows as float32; all files together at most 64 MB."""
+    import numpy as np
+    bench = _bench_module()
+    rng = np.random.default_rng(1)
+    big = rng.integers(0, 2 ** 32, 6_000_000, dtype=np.uint64).astype(np.uint32)
+    arrays = {"input_nodes": big, "layer0_row": big[::-1].copy(), "labels": np.arange(100, dtype=np.int64)}
+    feat = rng.standard_normal((40_000, 256), dtype=np.float32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays, feat)
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["features.npy", "input_nodes.npy", "labels.npy", "layer0_row.npy"]
+    assert sum((tmp_path / "a" / f).stat().st_size for f in files) <= 64_000_000
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert np.array_equal(x, y) and x.dtype == (np.float32 if f == "features.npy" else np.float64)
+    assert np.array_equal(np.load(tmp_path / "a" / "labels.npy"), np.arange(100))
+    ids = np.load(tmp_path / "a" / "input_nodes.npy")
+    pos = bench.dump_positions(big.size, ids.size, 0)
+    assert 0 < ids.size < big.size and np.all(np.diff(pos) > 0) and np.array_equal(ids, big[pos].astype(np.float64))
+    rows = np.load(tmp_path / "a" / "features.npy")
+    assert rows.shape[1] == 256 and 0 < rows.shape[0] < feat.shape[0]
+    assert np.array_equal(rows, feat[bench.dump_positions(feat.shape[0], rows.shape[0], len(arrays))])

@@ -9,7 +9,7 @@ F="--no-engine --no-configs --no-staged-host --no-host-tier --no-cpu-baseline --
 pick='import sys,json; d=json.loads([l for l in sys.stdin if l.startswith("{")][-1]); print("%-7s" % sys.argv[1], "ms/step %.4f" % d["ms_per_step"], "edges/s %.4g" % d["value"], "gather us %.1f" % d["roofline"]["avg_launch_us"], "alone %.1f" % (d["roofline"]["avg_launch_us_alone"] or 0), "sample ms %.3f" % d["per_gpu"]["sample_ms_per_step"])'
 for rep in 1 2 3; do
   [ -f bench_prev.py ] && python bench_prev.py $F 2>/dev/null | python -c "$pick" prev
-  GGMS_BENCH_GATHER_TIMING=events python bench.py $F 2>/dev/null | python -c "$pick" events
-  python bench.py $F 2>/dev/null | python -c "$pick" timer
-  GGMS_BENCH_STEP_EVENTS=0 python bench.py $F 2>/dev/null | python -c "$pick" lean
+  GGMS_BENCH_GATHER_TIMING=events python bench.py --full $F 2>/dev/null | python -c "$pick" events
+  python bench.py --full $F 2>/dev/null | python -c "$pick" timer
+  GGMS_BENCH_STEP_EVENTS=0 python bench.py --full $F 2>/dev/null | python -c "$pick" lean
 done

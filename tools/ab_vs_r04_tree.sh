@@ -8,11 +8,11 @@ run() { # label, dir, flags...
 }
 for rep in 1 2; do
   run "r04 papers100M khop0" build/_r04 --sample-type khop0
-  run "r05 papers100M khop0" . --no-configs --sample-type khop0
+  run "r05 papers100M khop0" . --full --no-configs --sample-type khop0
   run "r04 papers100M khop0 hub-skewed" build/_r04 --sample-type khop0 --neighbour-skew 1.0
-  run "r05 papers100M khop0 hub-skewed" . --no-configs --sample-type khop0 --neighbour-skew 1.0
+  run "r05 papers100M khop0 hub-skewed" . --full --no-configs --sample-type khop0 --neighbour-skew 1.0
   run "r04 products khop0" build/_r04 --preset products --sample-type khop0
-  run "r05 products khop0" . --no-configs --preset products --sample-type khop0
+  run "r05 products khop0" . --full --no-configs --preset products --sample-type khop0
   run "r04 products khop0 hub-skewed" build/_r04 --preset products --sample-type khop0 --neighbour-skew 1.0
-  run "r05 products khop0 hub-skewed" . --no-configs --preset products --sample-type khop0 --neighbour-skew 1.0
+  run "r05 products khop0 hub-skewed" . --full --no-configs --preset products --sample-type khop0 --neighbour-skew 1.0
 done

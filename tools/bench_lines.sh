@@ -6,7 +6,7 @@ OUT=gpurun_out/lines_$TAG
 mkdir -p $OUT
 run() { # name, flags...
   local name=$1; shift
-  python bench.py --no-host-tier "$@" > $OUT/$name.json 2> $OUT/$name.err || echo "FAILED $name"
+  python bench.py --full --no-host-tier "$@" > $OUT/$name.json 2> $OUT/$name.err || echo "FAILED $name"
   python tools/brief.py "$name" < $OUT/$name.json
 }
 run bench_products_sage_25_10 --preset products

@@ -7,7 +7,7 @@ OUT=gpurun_out/sharded_$TAG
 mkdir -p $OUT
 run() {
   name=$1; shift
-  python bench.py --no-engine --no-host-tier --no-cpu-baseline "$@" > $OUT/$name.json 2> $OUT/$name.err || { echo "$name FAILED"; tail -3 $OUT/$name.err; return; }
+  python bench.py --full --no-engine --no-host-tier --no-cpu-baseline "$@" > $OUT/$name.json 2> $OUT/$name.err || { echo "$name FAILED"; tail -3 $OUT/$name.err; return; }
   python - "$OUT/$name.json" "$name" <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
