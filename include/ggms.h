@@ -493,7 +493,8 @@ int ggms_extract_tiered(void *out, const ggms_id_t *nodes, size_t num_nodes,
  * MI355X, all of it dead time on the stream that bounds the step (profiles/r05_ab_extract_stream.txt).  A timer's
  * two events ride ON the dispatch packet of the next row-gather launch (hipExtLaunchKernel): the kernel's own
  * start and end timestamps, and its end event is what another stream waits for ("the slot's rows are out").
- *   arm(t):      the next launch of ggms_extract* / ggms_gather_scatter* / ggms_mock_extract issued by THIS thread
+ *   arm(t):      the next launch of ggms_extract* / ggms_gather_scatter* / ggms_mock_extract / ggms_batch_handoff
+ *                issued by THIS thread
  *                carries the timer (thread-local, consumed by that one launch; a call that launches nothing --
  *                zero rows -- leaves it armed)
  *   wait(t, s):  stream s waits for the timed launch (no-op if the timer never rode a launch)
@@ -510,6 +511,28 @@ int ggms_launch_timer_elapsed_us(ggms_launch_timer_t *timer, double *us);
 /* from the start of `first`'s launch to the end of `last`'s (both finished: blocks for them): with launches that may
  * overlap on two streams, sum of durations / span = how many are in flight on average */
 int ggms_launch_timer_span_us(ggms_launch_timer_t *first, ggms_launch_timer_t *last, double *us);
+
+/* ---------------------------------------------------------------------------
+ * Batch hand-off (arch3: one GPU samples, another trains) -- DoGraphCopy + DoIdCopy (cuda/cuda_loops.cc:600-655)
+ * in ONE launch, with no size on the host: every array of a sampled batch (COO per layer, input / output nodes, the
+ * counts words) is one segment, copied from `src` to `dst`.  A segment's length in elements is *count_dev when
+ * count_dev is not NULL (read on the device, at the launch), else count_host; either is clamped to max_count, which
+ * also sizes the grid.  Run it on a stream of the DESTINATION device: it reads `src` in place (peer memory over xGMI
+ * with peer access enabled, or local memory).  src and dst of a segment with max_count > 0 are 16-byte aligned;
+ * lengths are arbitrary, 0 included.  Segments must not overlap.  A launch timer armed on the calling thread rides
+ * on the launch (see above).
+ * ------------------------------------------------------------------------- */
+#define GGMS_HANDOFF_MAX_SEGS 64
+typedef struct {
+  const void *src;
+  void *dst;
+  const uint64_t *count_dev; /* device word holding the length in elements, or NULL */
+  uint64_t count_host;       /* the length when count_dev is NULL */
+  uint64_t max_count;        /* upper bound of the length (elements that dst can hold) */
+  uint32_t elem_bytes;
+  uint32_t _pad;
+} ggms_copy_seg_t;
+int ggms_batch_handoff(const ggms_copy_seg_t *segs, uint32_t num_segs, ggms_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * GGMS shards across processes (one process per GPU).

@@ -34,6 +34,12 @@ class FeatureTiers(C.Structure):
                 ("host_feat", C.c_void_p), ("host_row_mask", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+class CopySeg(C.Structure):
+    """ggms_copy_seg_t"""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("count_dev", C.c_void_p), ("count_host", C.c_uint64),
+                ("max_count", C.c_uint64), ("elem_bytes", C.c_uint32), ("_pad", C.c_uint32)]
+
+
 class Topology(C.Structure):
     """ggms_topology_t"""
     _fields_ = [("num_device", C.c_int32), ("_pad", C.c_int32), ("can_access", (C.c_int32 * 16) * 16),
@@ -123,6 +129,7 @@ SYMBOLS = {
     "ggms_launch_timer_wait": (_i, [_vp, _vp]),
     "ggms_launch_timer_elapsed_us": (_i, [_vp, C.POINTER(C.c_double)]),
     "ggms_launch_timer_span_us": (_i, [_vp, _vp, C.POINTER(C.c_double)]),
+    "ggms_batch_handoff": (_i, [C.POINTER(CopySeg), _u32, _vp]),
 }
 
 ABI_VERSION = 3  # include/ggms.h as this binding declares it (struct layouts, host / device pointer conventions)

@@ -65,6 +65,11 @@ static int parse_device(const std::string &ctx) {
   return id;
 }
 
+static std::string ctx_id_as_written(const std::string &ctx) { // the device id of "cuda:N", SAMGRAPH_FORCE_DEVICE not applied
+  auto p = ctx.find(':');
+  return std::to_string(p == std::string::npos ? 0 : std::atoi(ctx.c_str() + p + 1));
+}
+
 // ------------------------------------------------------------------ configuration
 void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in) {
   auto kv = kv_in;
@@ -99,13 +104,37 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
       cfg.trainer_device = parse_device(kv["trainer_ctx"]);
       cfg.num_worker = 1;
       break;
+    case kArch3: { // GPUEngine::ArchCheck (cuda/cuda_engine.cc:410-435): one GPU samples, a different GPU trains
+      SAM_CHECK(kv.count("sampler_ctx") && kv.count("trainer_ctx"), "arch3 needs sampler_ctx/trainer_ctx");
+      const std::string sc = kv["sampler_ctx"], tc = kv["trainer_ctx"];
+      if (sc.rfind("cuda", 0) != 0 || tc.rfind("cuda", 0) != 0)
+        fatal(__FILE__, __LINE__, "arch3: sampler_ctx and trainer_ctx must both be GPU contexts (cuda:N), got " + sc +
+                                      " and " + tc);
+      if (ctx_id_as_written(sc) == ctx_id_as_written(tc))
+        fatal(__FILE__, __LINE__, "arch3: sampler_ctx and trainer_ctx are the same GPU (" + sc + "): arch3 samples on one "
+                                      "GPU and trains on another; one GPU for both is arch1");
+      const bool log_access = getenv("SAMGRAPH_LOG_NODE_ACCESS") || getenv("SAMGRAPH_LOG_NODE_ACCESS_SIMPLE");
+      if (cfg.cache_percentage > 0 && log_access)
+        fatal(__FILE__, __LINE__, "arch3: a GPU cache (cache_percentage > 0) cannot be combined with node access logging "
+                                  "(SAMGRAPH_LOG_NODE_ACCESS*)");
+      const bool dist_graph = kv.count("use_dist_graph") && std::stod(kv["use_dist_graph"]) > 0.0;
+      for (const char *k : {"part_cache", "gpu_extract"})
+        if (kv.count(k) && kv[k] == "True")
+          fatal(__FILE__, __LINE__, std::string("arch3: ") + k + " is an arch6 key (GGMS shards across workers)");
+      if (dist_graph) fatal(__FILE__, __LINE__, "arch3: use_dist_graph is an arch6 key (GGMS shards across workers)");
+      cfg.sampler_device = parse_device(sc);
+      cfg.trainer_device = parse_device(tc);
+      cfg.num_worker = 1;
+      break;
+    }
     case kArch6:
       SAM_CHECK(kv.count("num_worker"), "arch6 needs num_worker");
       cfg.num_worker = std::stoull(kv["num_worker"]);
       SAM_CHECK(cfg.num_worker >= 1, "num_worker >= 1");
       break;
     default:
-      fatal(__FILE__, __LINE__, "only arch0 (CPU), arch1 (standalone) and arch6 (SGNN/XGNN) are built; see DESIGN.md");
+      fatal(__FILE__, __LINE__, "only arch0 (CPU), arch1 (standalone), arch3 (dedicated) and arch6 (SGNN/XGNN) are built; "
+                                "see DESIGN.md");
   }
   if (cfg.sample_type != GGMS_RANDOM_WALK) { // operation.cc:150-163
     SAM_CHECK(kv.count("num_fanout") && kv.count("fanout"), "khop sampling needs num_fanout/fanout");
@@ -558,8 +587,8 @@ bool Engine::ShufflerNext(Batch *b, hipStream_t copy_stream) {
   b->num_seeds = size;
   b->key = BatchKey(cur_epoch_, global_step_offset_ + cur_step_);
   static const bool sanity = getenv("SAMGRAPH_SANITY_CHECK") != nullptr; // run_config.cc:126-128
-  if (sanity && cfg.arch == kArch1) SanityCheckBatch(shuf_host_.data() + global_data_offset_ + offset, size);
-  SAM_HIP(hipMemcpyAsync(b->output_nodes, shuf_dev_ + offset, size * 4, hipMemcpyDeviceToDevice, copy_stream)); // Copy1D
+  if (sanity && (cfg.arch == kArch1 || cfg.arch == kArch3)) SanityCheckBatch(shuf_host_.data() + global_data_offset_ + offset, size);
+  SAM_HIP(hipMemcpyAsync(b->s_output_nodes, shuf_dev_ + offset, size * 4, hipMemcpyDeviceToDevice, copy_stream)); // Copy1D
   return true;
 }
 
@@ -651,10 +680,15 @@ void Engine::SampleInit(int worker_id, const std::string &ctx) {
   SAM_CHECK(data_ready_, "samgraph_data_init first");
   worker_id_ = worker_id;
   device_ = parse_device(ctx);
+  trainer_device_ = cfg.arch == kArch3 ? cfg.trainer_device : device_;
+  if (trainer_device_ != device_) EnablePeerAccess();
   SAM_HIP(hipSetDevice(device_));
   SAM_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+  // the extract streams belong to the trainer GPU (the same device except under arch3): no stream is added for arch3
+  SAM_HIP(hipSetDevice(trainer_device_));
   SAM_HIP(hipStreamCreateWithFlags(&stream_extract_, hipStreamNonBlocking));
   if (cfg.extract_streams > 1) SAM_HIP(hipStreamCreateWithFlags(&stream_extract2_, hipStreamNonBlocking));
+  SAM_HIP(hipSetDevice(device_));
   UploadGraph();
   ShufflerInit();
   const uint32_t L = (uint32_t)cfg.fanout.size();
@@ -730,6 +764,23 @@ void Engine::SampleInit(int worker_id, const std::string &ctx) {
   sample_ready_ = true;
 }
 
+// arch3 with two distinct GPUs: the hand-off kernel runs on the trainer GPU T and reads the sampler GPU S's memory in
+// place (ggms_batch_handoff), so T must reach S.  A pair that cannot is refused here, named -- there is no fallback.
+void Engine::EnablePeerAccess() {
+  int can = 0;
+  SAM_HIP(hipDeviceCanAccessPeer(&can, trainer_device_, device_));
+  if (!can)
+    fatal(__FILE__, __LINE__, "arch3: GPU " + std::to_string(trainer_device_) + " (trainer_ctx) cannot access GPU " +
+                                  std::to_string(device_) + " (sampler_ctx) (hipDeviceCanAccessPeer): the trainer GPU "
+                                  "reads each sampled batch from the sampler GPU's memory, which needs peer access");
+  SAM_HIP(hipSetDevice(trainer_device_));
+  const hipError_t e = hipDeviceEnablePeerAccess(device_, 0);
+  if (e == hipErrorPeerAccessAlreadyEnabled) (void)hipGetLastError();
+  else SAM_HIP(e);
+  SAM_HIP(hipSetDevice(device_));
+  log_info("arch3: peer access GPU " + std::to_string(trainer_device_) + " -> GPU " + std::to_string(device_) + " enabled");
+}
+
 // PreSampler (dist/pre_sampler.cc:39-139): sample `presample_epoch` epochs of the WHOLE train set with a
 // GPUShuffler of its own, count how often each node is an input node, rank by (freq << 32 | id) descending.
 // Counting happens on the device (one atomicAdd per input node) instead of D2H copy + OpenMP loop.
@@ -785,9 +836,12 @@ void Engine::Presample() {
 void Engine::BuildCache() {
   const size_t row_bytes = ds.feat_dim * ggms_dtype_bytes(ds.feat_dtype);
   const char *feat = (const char *)ds.feat.ptr;
+  // the cache and the label table live on the trainer GPU: uploaded through a stream of that device (arch3: the
+  // extract stream; the other deployments have one device, and the sampling stream as before)
+  hipStream_t bs = cfg.arch == kArch3 ? stream_extract_ : stream_;
   // labels are 8 B x N: always resident on the device (the reference keeps them on the host and
   // gathers through zero-copy in gpu_extract mode, dist_loops.cc:938-974)
-  label_src_ = dev_upload(ds.label.ptr, ds.label.bytes, stream_);
+  label_src_ = dev_upload(ds.label.ptr, ds.label.bytes, bs);
   if (!cfg.UseGPUCache()) {
     if (cfg.arch == kArch6 && !cfg.gpu_extract) {
       // cache 0 without gpu_extract: the table stays in host memory and every row takes the host-staged path
@@ -795,12 +849,12 @@ void Engine::BuildCache() {
       feat_src_ = nullptr;
     } else if (cfg.arch == kArch1) {
       // arch1: the whole table lives in HBM and is gathered directly (cuda_loops_arch1.cc:61)
-      d_feat_ = dev_upload(feat, ds.feat.bytes, stream_);
+      d_feat_ = dev_upload(feat, ds.feat.bytes, bs);
       feat_src_ = d_feat_;
     } else {
       feat_src_ = map_host(ds.feat.ptr, ds.feat.bytes); // cache 0 %: DoGPUFeatureExtract from host, dist_loops.cc:585-634
     }
-    SAM_HIP(hipStreamSynchronize(stream_));
+    SAM_HIP(hipStreamSynchronize(bs));
     return;
   }
   // GPUCacheManager ctor: cuda_cache_manager_host.cc:61-130 (replicated) / :133-254 (partition)
@@ -826,7 +880,7 @@ void Engine::BuildCache() {
   } else {
     std::vector<uint32_t> table(ds.num_node, GGMS_EMPTY_KEY);
     for (size_t i = 0; i < num_cached_nodes_; ++i) table[rank[i]] = (uint32_t)i; // :197-229
-    cache_table_ = (uint32_t *)dev_upload(table.data(), ds.num_node * 4, stream_);
+    cache_table_ = (uint32_t *)dev_upload(table.data(), ds.num_node * 4, bs);
   }
   // Rows are staged through a bounded host buffer (64 MB at a time), never through a host copy of the whole replica
   // or shard: at papers100M size a replica is 46 GB, and eight workers of one node would hold eight of them at once.
@@ -847,8 +901,8 @@ void Engine::BuildCache() {
     if (ds.feat_is_zero) {
       // rows of a table that is known to be all zero need no gather: touching them in rank order would fault in every
       // page of the untouched anonymous mapping once per worker (two minutes of page faults at papers100M size)
-      SAM_HIP(hipMemsetAsync(d, 0, count * row_bytes, stream_));
-      SAM_HIP(hipStreamSynchronize(stream_));
+      SAM_HIP(hipMemsetAsync(d, 0, count * row_bytes, bs));
+      SAM_HIP(hipStreamSynchronize(bs));
       return d;
     }
     size_t k = 0;
@@ -860,10 +914,10 @@ void Engine::BuildCache() {
         for (size_t i = a; i < b; ++i)
           std::memcpy(buf + i * row_bytes, feat + (size_t)(rank[first + (lo + i) * stride] & ds.feat_mask) * row_bytes, row_bytes);
       });
-      SAM_HIP(hipMemcpyAsync((char *)d + lo * row_bytes, buf, m * row_bytes, hipMemcpyHostToDevice, stream_));
-      SAM_HIP(hipEventRecord(drained[k & 1], stream_));
+      SAM_HIP(hipMemcpyAsync((char *)d + lo * row_bytes, buf, m * row_bytes, hipMemcpyHostToDevice, bs));
+      SAM_HIP(hipEventRecord(drained[k & 1], bs));
     }
-    SAM_HIP(hipStreamSynchronize(stream_));
+    SAM_HIP(hipStreamSynchronize(bs));
     return d;
   };
   if (R) d_replica_ = upload_rows(0, 1, R); // this GPU's copy of the hottest rows
@@ -872,7 +926,7 @@ void Engine::BuildCache() {
   const size_t my_rows = sharded / P + (p < sharded % P ? 1 : 0);
   cache_parts_.assign(P, nullptr);
   cache_parts_[p] = upload_rows(R + p, P, my_rows);
-  SAM_HIP(hipStreamSynchronize(stream_));
+  SAM_HIP(hipStreamSynchronize(bs));
   if (P > 1) { // _DataIpcShare
     SAM_HIP(hipIpcGetMemHandle(&shared_->feat_part[p], cache_parts_[p]));
     shared_->feat_rows[p] = my_rows;
@@ -889,15 +943,20 @@ void Engine::BuildCache() {
   }
   // miss tier: pinned host memory read by the gather kernel itself (GPUExtractMissData, :573-625); the host-staged
   // path (`gpu_extract` off) reads the table with the host cores instead and needs no device mapping of it
-  feat_src_ = cfg.gpu_extract ? map_host(ds.feat.ptr, ds.feat.bytes) : nullptr;
-  SAM_HIP(hipStreamSynchronize(stream_));
+  // (arch3 gathers its misses the gpu_extract way: zero-copy by the trainer GPU, no CPU-staged path)
+  const bool host_tier = cfg.gpu_extract || (cfg.arch == kArch3 && (num_cached_nodes_ < ds.num_node || ds.feat_mask != 0xffffffffu));
+  feat_src_ = host_tier ? map_host(ds.feat.ptr, ds.feat.bytes) : nullptr;
+  SAM_HIP(hipStreamSynchronize(bs));
 }
 
 void Engine::TrainInit(int worker_id, const std::string &ctx) {
   SAM_CHECK(sample_ready_, "samgraph_sample_init first");
-  SAM_CHECK(parse_device(ctx) == device_, "arch6: sampler and trainer share the GPU (cuda_cache_manager_host.cc:152-155)");
+  if (cfg.arch == kArch3)
+    SAM_CHECK(parse_device(ctx) == trainer_device_, "arch3: train_init on the config's trainer_ctx");
+  else
+    SAM_CHECK(parse_device(ctx) == device_, "arch6: sampler and trainer share the GPU (cuda_cache_manager_host.cc:152-155)");
   (void)worker_id;
-  SAM_HIP(hipSetDevice(device_));
+  SAM_HIP(hipSetDevice(trainer_device_));
   auto t0 = std::chrono::steady_clock::now();
   BuildCache();
   prof.LogInit(/*kLogInitL2BuildCache*/ 10, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
@@ -940,11 +999,31 @@ void Engine::TrainInit(int worker_id, const std::string &ctx) {
     std::memset(b->counts, 0, (3 * L + 8) * 8);
     SAM_HIP(hipEventCreateWithFlags(&b->ev_seeds, hipEventDisableTiming));
     SAM_HIP(hipEventCreateWithFlags(&b->ev_label, hipEventDisableTiming));
-    SAM_HIP(hipEventCreate(&b->ev_start));
-    SAM_HIP(hipEventCreate(&b->ev_sampled));
     SAM_HIP(hipEventCreate(&b->ev_xstart));
     SAM_HIP(hipEventCreate(&b->ev_done));
     SAM_GGMS(ggms_launch_timer_create(&b->gather_timer));
+    if (cfg.arch == kArch3) { // the sampler's side of the slot, on the sampler GPU (GetGraphFileCtx, cuda_engine.cc:437-481)
+      SAM_GGMS(ggms_launch_timer_create(&b->handoff_timer));
+      SAM_HIP(hipSetDevice(device_));
+      b->s_row.resize(L); b->s_col.resize(L); b->s_data.resize(L, nullptr);
+      for (uint32_t i = 0; i < L; ++i) {
+        SAM_HIP(hipMalloc((void **)&b->s_row[i], std::max<size_t>(max_edges_[i], 4) * 4));
+        SAM_HIP(hipMalloc((void **)&b->s_col[i], std::max<size_t>(max_edges_[i], 4) * 4));
+        if (cfg.sample_type == GGMS_RANDOM_WALK) SAM_HIP(hipMalloc((void **)&b->s_data[i], std::max<size_t>(max_edges_[i], 4) * 4));
+      }
+      SAM_HIP(hipMalloc((void **)&b->s_input_nodes, max_unique_ * 4));
+      SAM_HIP(hipMalloc((void **)&b->s_output_nodes, max_seeds_ * 4));
+      SAM_HIP(hipMalloc((void **)&b->s_counts_dev, (3 * L + 8) * 8));
+      SAM_HIP(hipMemset(b->s_counts_dev, 0, (3 * L + 8) * 8));
+    } else {
+      b->s_row = b->row; b->s_col = b->col; b->s_data = b->data;
+      b->s_input_nodes = b->input_nodes;
+      b->s_output_nodes = b->output_nodes;
+      b->s_counts_dev = b->counts_dev;
+    }
+    SAM_HIP(hipEventCreate(&b->ev_start)); // both recorded on the sampling stream
+    SAM_HIP(hipEventCreate(&b->ev_sampled));
+    SAM_HIP(hipSetDevice(trainer_device_));
     slots_.push_back(std::move(b));
   }
   train_ready_ = true;
@@ -961,7 +1040,11 @@ void Engine::Init() { // samgraph_init, single process
   TrainInit(0, "cuda:" + std::to_string(cfg.trainer_device));
 }
 
-void Engine::Start() {}
+// GPUEngine::Start (cuda/cuda_engine.cc:292-317): arch3 starts its background sample + hand-off + extract loop, and the
+// caller only asks for batches (get_next_batch).  The other deployments start theirs with extract_start, or not at all.
+void Engine::Start() {
+  if (cfg.arch == kArch3) ExtractStart(0);
+}
 
 void Engine::Shutdown() {
   shutdown_ = true;
@@ -1012,6 +1095,13 @@ void Engine::RunSampleOnce(bool background) {
 bool Engine::EnqueueOne(bool background) {
   if (cfg.arch == kArch0) return CpuEnqueueOne(background);
   SAM_CHECK(train_ready_, "engine not initialised");
+  // arch3: sample_once() runs on the caller's training thread, whose current device is the trainer GPU (torch's
+  // streams, events and allocations follow it) -- it is left as the caller had it, on every way out of here
+  struct RestoreDevice {
+    int dev = -1;
+    ~RestoreDevice() { if (dev >= 0) (void)hipSetDevice(dev); }
+  } restore;
+  if (cfg.arch == kArch3) SAM_HIP(hipGetDevice(&restore.dev));
   SAM_HIP(hipSetDevice(device_));
   Batch *b = AcquireSlot(background);
   if (!b) return false;
@@ -1030,7 +1120,7 @@ bool Engine::EnqueueOne(bool background) {
   ++enq_count_;
   SAM_HIP(hipEventRecord(b->ev_start, ss));
   ggms_sample_extra_t extra = extra_;
-  extra.data = b->data.data();
+  extra.data = b->s_data.data();
   extra.seeds_distinct = BatchSeedsDistinct(cur_step_ * cfg.batch_size, b->num_seeds) ? 1u : 0u;
   if (pipes_.size() > 1 && cfg.sample_type != GGMS_KHOP0) {
     extra.rng_wait = last_rng_done_;
@@ -1040,19 +1130,22 @@ bool Engine::EnqueueOne(bool background) {
   // input nodes = the table's unique list (task->input_nodes, dist_loops.cc:357).  The table struct is plain data and
   // its n2o buffer the caller's: the batch builds the list directly in its slot (a later batch uses another slot)
   ggms_hashtable_t ht = P.ht;
-  ht.n2o = b->input_nodes;
+  ht.n2o = b->s_input_nodes;
   ht.n2o_size = max_unique_;
-  SAM_GGMS(ggms_sample_batch(cfg.sample_type, &graph_, b->output_nodes, b->num_seeds, cfg.fanout.data(), L, &ht,
-                             states_, num_states_, b->row.data(), b->col.data(), b->counts_dev, &extra, P.ws, ws_bytes_,
-                             ss));
+  SAM_GGMS(ggms_sample_batch(cfg.sample_type, &graph_, b->s_output_nodes, b->num_seeds, cfg.fanout.data(), L, &ht,
+                             states_, num_states_, b->s_row.data(), b->s_col.data(), b->s_counts_dev, &extra, P.ws,
+                             ws_bytes_, ss));
   P.ht.version = ht.version; // the batch bumped the table's version stamp
   uint64_t *n_in = b->counts_dev + 3 * L, *n_miss = b->counts_dev + 3 * L + 2; // [3L + 1] = the batch's status word
-  SAM_HIP(hipMemsetAsync(n_miss, 0, 8, ss));
+  SAM_HIP(hipMemsetAsync(b->s_counts_dev + 3 * L + 2, 0, 8, ss));
   SAM_HIP(hipEventRecord(b->ev_sampled, ss));
+  // arch3: everything from here on runs on the trainer GPU, on the batch's extract stream -- hand-off, labels, rows,
+  // counts -- and the sampling stream is left to the sampler
+  const bool arch3 = cfg.arch == kArch3;
   // DoGPULabelExtract (dist_loops.cc:938-974) needs the seeds only: it rides behind the batch on its sampling stream, not
   // between two gathers on the extract stream, which bounds the step.  (Not on a stream of its own: HIP streams share 4
   // hardware queues, and a fifth stream serialises streams that have nothing to do with each other.)
-  SAM_GGMS(ggms_extract(b->label, label_src_, b->output_nodes, b->num_seeds, 1, GGMS_I64, ss));
+  if (!arch3) SAM_GGMS(ggms_extract(b->label, label_src_, b->output_nodes, b->num_seeds, 1, GGMS_I64, ss));
   const bool mock = ds.feat_mask != 0xffffffffu; // SAMGRAPH_EMPTY_FEAT: host rows are node & mask
   // The extract stream bounds the step, and every event record / wait / small copy on it is a packet the command
   // processor works through between two gathers -- 28 us of dead time per 0.7-ms step with six of them
@@ -1066,16 +1159,21 @@ bool Engine::EnqueueOne(bool background) {
   const bool gather_counts = cfg.UseGPUCache() && (mock || ((num_replica_ || cache_table_) && can_miss));
   static const bool lean_off = [] { const char *e = getenv("SAMGRAPH_LEAN_EXTRACT"); return e && e[0] == '0'; }(); // A/B hook
   b->lean = !lean_off && !StagedHostTier() && !gather_counts && !node_access_dev_;
-  if (b->lean) {
+  if (!arch3 && b->lean) {
     SAM_HIP(hipMemcpyAsync(b->counts, b->counts_dev, (3 * L + 8) * 8, hipMemcpyDeviceToHost, ss));
     SAM_HIP(hipEventRecord(b->ev_done, ss)); // labels and counts are out; the rows: gather_timer
-  } else {
+  } else if (!arch3) {
     SAM_HIP(hipEventRecord(b->ev_label, ss));
   }
   // The gather is HBM-bound, the sampler latency-bound: they run on separate streams so that batch k's
   // extract overlaps batch k+1's sampling (the reference serialises them, dist_loops_arch6.cc:248-251)
   hipStream_t xs = (b->lean && stream_extract2_ && (enq_count_ & 1)) ? stream_extract2_ : stream_extract_;
+  if (arch3) SAM_HIP(hipSetDevice(trainer_device_));
   SAM_HIP(hipStreamWaitEvent(xs, b->ev_sampled, 0));
+  if (arch3) {
+    Handoff(b, xs); // the batch's arrays, S -> T; the gather below reads the input nodes and their count on T
+    SAM_GGMS(ggms_extract(b->label, label_src_, b->output_nodes, b->num_seeds, 1, GGMS_I64, xs));
+  }
   if (b->lean) SAM_GGMS(ggms_launch_timer_arm(b->gather_timer));
   else SAM_HIP(hipEventRecord(b->ev_xstart, xs)); // the extract's own start: behind the previous batch's extract on xs
   if (StagedHostTier()) {
@@ -1110,7 +1208,10 @@ bool Engine::EnqueueOne(bool background) {
   if (!b->lean) {
     if (node_access_dev_) // Profiler::LogNodeAccess (profiler.cc:570-575): visits per node, counted on the device
       SAM_GGMS(ggms_count_nodes(node_access_dev_, b->input_nodes, max_unique_, n_in, xs));
-    SAM_HIP(hipStreamWaitEvent(xs, b->ev_label, 0)); // the batch is complete when its labels are, too
+    if (!arch3) SAM_HIP(hipStreamWaitEvent(xs, b->ev_label, 0)); // the batch is complete when its labels are, too
+    SAM_HIP(hipMemcpyAsync(b->counts, b->counts_dev, (3 * L + 8) * 8, hipMemcpyDeviceToHost, xs));
+    SAM_HIP(hipEventRecord(b->ev_done, xs));
+  } else if (arch3) { // counts of T (the gather may have added to them) to the host behind the rows
     SAM_HIP(hipMemcpyAsync(b->counts, b->counts_dev, (3 * L + 8) * 8, hipMemcpyDeviceToHost, xs));
     SAM_HIP(hipEventRecord(b->ev_done, xs));
   }
@@ -1120,6 +1221,31 @@ bool Engine::EnqueueOne(bool background) {
   }
   pool_cv_.notify_all();
   return true;
+}
+
+// arch3: DoGraphCopy + DoIdCopy (cuda/cuda_loops.cc:600-655) as one launch on the trainer GPU's extract stream.  Every
+// length is read by the kernel from the sampler's counts words (the output nodes' from the host: the shuffler knows
+// it), so the batch is still enqueued without a host round trip.  The counts words themselves are the last segment:
+// the status word [3L + 1] and the zeroed miss count travel with them.
+void Engine::Handoff(Batch *b, hipStream_t xs) {
+  const uint32_t L = (uint32_t)cfg.fanout.size();
+  ggms_copy_seg_t segs[GGMS_HANDOFF_MAX_SEGS];
+  uint32_t n = 0;
+  auto add = [&](const void *src, void *dst, const uint64_t *count_dev, uint64_t count_host, uint64_t max_count,
+                 uint32_t elem_bytes) {
+    SAM_CHECK(n < GGMS_HANDOFF_MAX_SEGS, "arch3: too many hand-off segments");
+    segs[n++] = ggms_copy_seg_t{src, dst, count_dev, count_host, max_count, elem_bytes, 0};
+  };
+  for (uint32_t i = 0; i < L; ++i) {
+    add(b->s_row[i], b->row[i], b->s_counts_dev + 3 * i, 0, max_edges_[i], 4);
+    add(b->s_col[i], b->col[i], b->s_counts_dev + 3 * i, 0, max_edges_[i], 4);
+    if (b->s_data[i]) add(b->s_data[i], b->data[i], b->s_counts_dev + 3 * i, 0, max_edges_[i], 4);
+  }
+  add(b->s_input_nodes, b->input_nodes, b->s_counts_dev + 3 * L, 0, max_unique_, 4);
+  add(b->s_output_nodes, b->output_nodes, nullptr, b->num_seeds, max_seeds_, 4);
+  add(b->s_counts_dev, b->counts_dev, nullptr, 3 * L + 8, 3 * L + 8, 8);
+  SAM_GGMS(ggms_launch_timer_arm(b->handoff_timer)); // kLogL2GraphCopyTime: the hand-off's own time
+  SAM_GGMS(ggms_batch_handoff(segs, n, xs));
 }
 
 // ---- the host-staged feature path: arch6 without `gpu_extract` (the reference's SGNN mode) --------------------------
@@ -1367,6 +1493,14 @@ void Engine::Finish(Batch *b, Batch *prev) {
   prof.LogEpochAdd(b->key, 12 /*kLogEpochFeatureBytes*/, b->num_input * row_bytes);
   prof.LogEpochAdd(b->key, 13 /*kLogEpochMissBytes*/, b->num_miss * row_bytes);
   prof.LogEpochAdd(b->key, 15 /*kLogEpochNumSample*/, (double)edges);
+  if (cfg.arch == kArch3) { // what the hand-off moved (DoGraphCopy / DoIdCopy, cuda/cuda_loops.cc:629,653) and its time
+    double us_handoff = 0;
+    SAM_GGMS(ggms_launch_timer_elapsed_us(b->handoff_timer, &us_handoff));
+    const double per_edge = cfg.sample_type == GGMS_RANDOM_WALK ? 12.0 : 8.0; // row + col (+ data)
+    prof.LogStep(b->key, 12 /*kLogL1GraphBytes*/, edges * per_edge);
+    prof.LogStep(b->key, 11 /*kLogL1IdBytes*/, (b->num_input + b->num_seeds) * 4.0);
+    prof.LogStep(b->key, 22 /*kLogL2GraphCopyTime*/, us_handoff * 1e-6);
+  }
 }
 
 uint64_t Engine::GetNextBatch() { // operation.cc:366-378 + GraphPool::GetGraphBatch graph_pool.cc:31-49

@@ -2,8 +2,8 @@
 //
 // Counterpart of the reference's Engine / GPUEngine / DistEngine
 // (samgraph/common/engine.{h,cc}, cuda/cuda_engine.cc, dist/dist_engine.cc) for the
-// deployments on the hot path: arch1 (one process, one GPU) and arch6 (one process
-// per GPU, GGMS shards).  It owns device memory (hipMalloc, no framework allocator),
+// deployments on the hot path: arch1 (one process, one GPU), arch3 (one process, a
+// sampler GPU and a trainer GPU) and arch6 (one process per GPU, GGMS shards).  It owns device memory (hipMalloc, no framework allocator),
 // streams, the shuffler, the sampler state and the feature cache, and drives the
 // leaf operators of include/ggms.h.  Everything below is plain C++17 + HIP runtime.
 #pragma once
@@ -159,6 +159,13 @@ struct Batch {
   // lean: this batch's extract stream carried the gather and nothing else (EnqueueOne)
   ggms_launch_timer_t *gather_timer = nullptr;
   bool lean = false;
+  // arch3: the sampler writes its own copies of row / col / data / input / output nodes / counts on the SAMPLER GPU,
+  // and ggms_batch_handoff copies them into the buffers above, on the trainer GPU (handoff_timer rides on that
+  // launch).  Every other deployment samples straight into the buffers above: these alias them.
+  std::vector<uint32_t *> s_row, s_col, s_data;
+  uint32_t *s_input_nodes = nullptr, *s_output_nodes = nullptr;
+  uint64_t *s_counts_dev = nullptr;
+  ggms_launch_timer_t *handoff_timer = nullptr;
 };
 
 class Engine {
@@ -189,7 +196,7 @@ class Engine {
   size_t NumStep() const { return num_global_step_; }
   size_t NumLocalStep() const { return num_local_step_; }
   uint64_t BatchKey(uint64_t epoch, uint64_t step) const { return epoch * num_global_step_ + step; }
-  int trainer_device() const { return device_; }
+  int trainer_device() const { return cfg.arch == kArch3 ? trainer_device_ : device_; }
   int batch_device_type() const { return (cfg.arch == kArch0 && cfg.trainer_on_host) ? 0 : 2; } // DeviceType, common.h:48
   void Barrier(const char *what = "step");
   void *OpenPeer(const hipIpcMemHandle_t &handle, uint32_t peer, size_t bytes, const char *what);
@@ -230,11 +237,15 @@ class Engine {
   bool CpuEnqueueOne(bool background);
   void CpuShutdown();
   void Finish(Batch *b, Batch *prev);
+  void EnablePeerAccess(); // arch3: the trainer GPU reads the sampler GPU's batch buffers in place
+  void Handoff(Batch *b, hipStream_t xs);
 
   bool data_ready_ = false, sample_ready_ = false, train_ready_ = false, shutdown_ = false;
   int worker_id_ = 0, device_ = 0;
+  int trainer_device_ = 0; // arch3: the trainer GPU (label table, feature cache, the batch as handed out); else device_
   hipStream_t stream_ = nullptr;         // shuffle + sampling (latency-bound)
   hipStream_t stream_extract_ = nullptr; // feature gather (HBM-bound): overlaps the next batch's sampling
+                                         // (arch3: on the trainer GPU, with the hand-off and the label gather)
   // a second one: consecutive lean batches' gathers alternate and may overlap -- no wait packet between two gathers, and
   // one gather's head fills the other's tail (default workload -5 %, profiles/r05_ab_extract_streams.txt)
   hipStream_t stream_extract2_ = nullptr;

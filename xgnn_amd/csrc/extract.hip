@@ -321,18 +321,26 @@ namespace ggms {
 
 static thread_local ggms_launch_timer *tl_armed_timer = nullptr;
 
+bool take_armed_timer(hipEvent_t *start, hipEvent_t *stop) {
+  ggms_launch_timer *t = tl_armed_timer;
+  if (!t) return false;
+  tl_armed_timer = nullptr;
+  t->launched = true;
+  *start = t->start;
+  *stop = t->stop;
+  return true;
+}
+
 // One row-gather launch: with a timer armed on this thread the kernel goes out through hipExtLaunchKernel carrying
 // the timer's events (start = the dispatch's own begin timestamp, stop = its completion signal) -- no marker packet
 // before or behind it; otherwise the plain launch.
 template <typename F, typename... Args>
 static inline void launch_rows(F kernel, int grid, hipStream_t stream, Args... args) {
-  if (ggms_launch_timer *t = tl_armed_timer) {
-    tl_armed_timer = nullptr;
-    t->launched = true;
-    hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, stream, t->start, t->stop, 0, args...);
-  } else {
+  hipEvent_t start, stop;
+  if (take_armed_timer(&start, &stop))
+    hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, stream, start, stop, 0, args...);
+  else
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, stream, args...);
-  }
 }
 
 template <typename Rows>

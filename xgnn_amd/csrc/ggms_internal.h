@@ -121,4 +121,8 @@ int ht_fill_impl(const ggms_hashtable_t *ht, const uint32_t *input, size_t n_max
                  bool inserted, ScanArea scan, uint64_t *mirror_a, uint64_t *mirror_b, hipStream_t s, uint32_t *mapped,
                  const BatchPrologue *prologue, int rest, const uint64_t *n_dev_for_rest);
 
+// extract.hip: hands the launch timer armed on this thread (include/ggms.h) to the launch about to be issued -- its
+// start / stop events for hipExtLaunchKernel -- and disarms it; false if none is armed
+bool take_armed_timer(hipEvent_t *start, hipEvent_t *stop);
+
 } // namespace ggms

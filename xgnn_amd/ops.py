@@ -422,6 +422,31 @@ class LaunchTimer:
             pass
 
 
+def batch_handoff(segments):
+    """ggms_batch_handoff (include/ggms.h): every segment copied in ONE launch on the current stream, which belongs to
+    the destination's device.  segments: (src, dst, count) with src / dst contiguous tensors of one element size and
+    count an int (elements, on the host) or a one-element int64 device tensor read by the kernel at the launch; at
+    most dst.numel() (and src.numel()) elements are copied."""
+    n = len(segments)
+    arr = (_lib.CopySeg * max(n, 1))()
+    for k, (src, dst, count) in enumerate(segments):
+        _require_gpu(dst)
+        if dst.device.index != torch.cuda.current_device():
+            raise _lib.GgmsError(f"batch_handoff: dst is on {dst.device}, the current stream on "
+                                 f"cuda:{torch.cuda.current_device()}: launch it on the destination's device")
+        assert src.is_contiguous() and dst.is_contiguous() and src.element_size() == dst.element_size()
+        c = arr[k]
+        c.src, c.dst = src.data_ptr(), dst.data_ptr()
+        if isinstance(count, torch.Tensor):
+            assert count.dtype == torch.int64 and count.is_cuda
+            c.count_dev, c.count_host = count.data_ptr(), 0
+        else:
+            c.count_dev, c.count_host = None, int(count)
+        c.max_count = min(src.numel(), dst.numel())
+        c.elem_bytes = dst.element_size()
+    check(lib().ggms_batch_handoff(arr, n, _stream()), "ggms_batch_handoff")
+
+
 def owner_histogram(table, nodes, num_part, slots_out, counts, num=None, num_dev=None):
     """slots_out[i] = table[nodes[i]]; counts[p] += rows of the batch owned by shard p (p = num_part: host tier)."""
     _require_gpu(nodes)
