@@ -40,6 +40,26 @@ class CopySeg(C.Structure):
                 ("max_count", C.c_uint64), ("elem_bytes", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+_QL = 16  # GGMS_QUEUE_MAX_LAYERS
+
+
+class QueueLayout(C.Structure):
+    """ggms_queue_layout_t"""
+    _fields_ = [("num_layer", C.c_uint32), ("has_data", C.c_uint32), ("max_edges", C.c_uint64 * _QL),
+                ("max_input", C.c_uint64), ("max_output", C.c_uint64), ("off_row", C.c_uint64 * _QL),
+                ("off_col", C.c_uint64 * _QL), ("off_data", C.c_uint64 * _QL), ("off_input", C.c_uint64),
+                ("off_output", C.c_uint64), ("slot_bytes", C.c_uint64)]
+
+
+class QueueBatch(C.Structure):
+    """ggms_queue_batch_t"""
+    _fields_ = [("row", C.c_void_p * _QL), ("col", C.c_void_p * _QL), ("data", C.c_void_p * _QL),
+                ("input_nodes", C.c_void_p), ("output_nodes", C.c_void_p), ("counts", C.c_void_p)]
+
+
+QUEUE_HEADER_BYTES = 512  # ggms_queue_header_t: seq, key, num_output, num_layer, 4 reserved, counts[56]
+
+
 class Topology(C.Structure):
     """ggms_topology_t"""
     _fields_ = [("num_device", C.c_int32), ("_pad", C.c_int32), ("can_access", (C.c_int32 * 16) * 16),
@@ -130,6 +150,9 @@ SYMBOLS = {
     "ggms_launch_timer_elapsed_us": (_i, [_vp, C.POINTER(C.c_double)]),
     "ggms_launch_timer_span_us": (_i, [_vp, _vp, C.POINTER(C.c_double)]),
     "ggms_batch_handoff": (_i, [C.POINTER(CopySeg), _u32, _vp]),
+    "ggms_queue_layout": (_i, [C.POINTER(QueueLayout), _u32, C.POINTER(_sz), _sz, _sz, _i]),
+    "ggms_queue_pack": (_i, [_vp, C.POINTER(QueueLayout), C.POINTER(QueueBatch), _u64, _u64, _vp]),
+    "ggms_queue_unpack": (_i, [C.POINTER(QueueBatch), _vp, C.POINTER(QueueLayout), _vp]),
 }
 
 ABI_VERSION = 3  # include/ggms.h as this binding declares it (struct layouts, host / device pointer conventions)

@@ -51,6 +51,13 @@ struct Engine::Shared {
   size_t indptr_words[kMaxWorker], indices_words[kMaxWorker], feat_rows[kMaxWorker];
 };
 
+// arch5's batch queue: the first page of its mapping, zeroed by the anonymous mapping (see QueueInit)
+struct Engine::QueueCtl {
+  alignas(64) uint64_t enqueue_pos; // next producer ticket
+  alignas(64) uint64_t dequeue_pos; // next consumer ticket
+  alignas(64) uint64_t ranking_ready; // pre_sample: sampler 0 has written ds.ranking_nodes
+};
+
 Engine &Engine::Get() {
   static Engine e;
   return e;
@@ -127,14 +134,45 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
       cfg.num_worker = 1;
       break;
     }
+    case kArch5: { // DistEngine (dist/dist_engine.cc, operation.cc:112-121): S sampler processes, T trainer processes
+      SAM_CHECK(kv.count("num_sample_worker") && kv.count("num_train_worker"), "arch5 needs num_sample_worker/num_train_worker");
+      cfg.num_sample_worker = std::stoull(kv["num_sample_worker"]);
+      cfg.num_train_worker = std::stoull(kv["num_train_worker"]);
+      if (cfg.num_sample_worker < 1 || cfg.num_train_worker < 1)
+        fatal(__FILE__, __LINE__, "arch5: num_sample_worker and num_train_worker must both be >= 1, got " +
+                                      kv["num_sample_worker"] + " and " + kv["num_train_worker"]);
+      if (cfg.num_sample_worker + cfg.num_train_worker > 16)
+        fatal(__FILE__, __LINE__, "arch5: num_sample_worker + num_train_worker = " +
+                                      std::to_string(cfg.num_sample_worker + cfg.num_train_worker) + ": at most 16 workers");
+      if (kv.count("have_switcher") && kv["have_switcher"] != "0" && kv["have_switcher"] != "False")
+        fatal(__FILE__, __LINE__, "arch5: have_switcher = " + kv["have_switcher"] + ": the switcher is not built "
+                                  "(samgraph_switch_init); set have_switcher = 0");
+      const bool dist_graph = kv.count("use_dist_graph") && std::stod(kv["use_dist_graph"]) > 0.0;
+      for (const char *k : {"part_cache", "gpu_extract"})
+        if (kv.count(k) && kv[k] == "True")
+          fatal(__FILE__, __LINE__, std::string("arch5: ") + k + " is an arch6 key (GGMS shards across workers)");
+      if (dist_graph) fatal(__FILE__, __LINE__, "arch5: use_dist_graph is an arch6 key (GGMS shards across workers)");
+      if (kv.count("unified_memory") && (kv["unified_memory"] == "True" || kv["unified_memory"] == "1"))
+        fatal(__FILE__, __LINE__, "arch5: unified_memory is not built (arch9, unified-memory sampling)");
+      // the queue: 2 slots per trainer (one being unpacked, one filled meanwhile), at least 4
+      cfg.queue_depth = std::max<size_t>(4, 2 * cfg.num_train_worker);
+      if (kv.count("queue_depth")) cfg.queue_depth = std::stoull(kv["queue_depth"]);
+      if (cfg.queue_depth < 1 || cfg.queue_depth > 1024)
+        fatal(__FILE__, __LINE__, "arch5: queue_depth = " + kv["queue_depth"] + ": 1 .. 1024 slots");
+      if (kv.count("queue_timeout_s")) cfg.queue_timeout_s = std::stod(kv["queue_timeout_s"]);
+      if (!(cfg.queue_timeout_s > 0))
+        fatal(__FILE__, __LINE__, "arch5: queue_timeout_s = " + kv["queue_timeout_s"] + ": a positive number of seconds");
+      cfg.num_worker = cfg.num_sample_worker + cfg.num_train_worker;
+      break;
+    }
     case kArch6:
       SAM_CHECK(kv.count("num_worker"), "arch6 needs num_worker");
       cfg.num_worker = std::stoull(kv["num_worker"]);
       SAM_CHECK(cfg.num_worker >= 1, "num_worker >= 1");
       break;
     default:
-      fatal(__FILE__, __LINE__, "only arch0 (CPU), arch1 (standalone), arch3 (dedicated) and arch6 (SGNN/XGNN) are built; "
-                                "see DESIGN.md");
+      fatal(__FILE__, __LINE__, "only arch0 (CPU), arch1 (standalone), arch3 (dedicated), arch5 (factored) and arch6 "
+                                "(SGNN/XGNN) are built; see DESIGN.md");
   }
   if (cfg.sample_type != GGMS_RANDOM_WALK) { // operation.cc:150-163
     SAM_CHECK(kv.count("num_fanout") && kv.count("fanout"), "khop sampling needs num_fanout/fanout");
@@ -177,6 +215,10 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
   if (const char *e = getenv("SAMGRAPH_EXTRACT_STREAMS")) cfg.extract_streams = (e[0] == '1') ? 1 : 2; // A/B hook
   if (kv.count("pipelines")) cfg.pipelines = std::max<size_t>(1, std::min<size_t>(4, std::stoull(kv["pipelines"])));
   if (cfg.lookahead + 1 < cfg.pipelines) cfg.pipelines = cfg.lookahead + 1; // nothing to overlap without batches ahead
+  if (cfg.arch == kArch5) { // a trainer's sample_once() handles exactly one message; a sampler packs each batch it samples
+    cfg.lookahead = 0;
+    cfg.pipelines = 1;
+  }
   SAM_CHECK(cfg.sample_type >= GGMS_KHOP0 && cfg.sample_type <= GGMS_KHOP3, "unknown sample type");
   if (cfg.sample_type == GGMS_WEIGHTED_KHOP || cfg.sample_type == GGMS_KHOP2 || cfg.sample_type == GGMS_KHOP1 ||
       cfg.sample_type == GGMS_WEIGHTED_KHOP_PREFIX ||
@@ -342,6 +384,11 @@ void Engine::DataInit() {
     // DistGraph::DistGraph -> PartitionSolver (dist_graph.cu:592-594): which GPUs reach which, before anything is placed
     if (cfg.num_worker > 1 && (cfg.use_dist_graph || cfg.part_cache)) DetectTopo();
   }
+  if (cfg.arch == kArch5) {
+    num_global_step_ = (ds.num_train + cfg.batch_size - 1) / cfg.batch_size; // dist_engine.cc:139-142, drop_last false
+    ComputeBounds();
+    QueueInit();
+  }
   prof.LogInit(/*kLogInitL2LoadDataset*/ 6, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
   data_ready_ = true;
 }
@@ -490,20 +537,37 @@ void *Engine::OpenPeer(const hipIpcMemHandle_t &handle, uint32_t peer, size_t by
 
 // ------------------------------------------------------------------ shuffler
 // GPUShuffler (cuda/cuda_shuffler.cc:38-160) for one worker, DistAlignedShuffler
-// (dist/dist_shuffler_aligned.cc:37-146) for arch6: same Fisher-Yates with
-// std::default_random_engine(seed) + uniform_int_distribution<size_t>(i, n-1).
+// (dist/dist_shuffler_aligned.cc:37-146) for arch6, DistShuffler (dist/dist_shuffler.cc:37-90) for arch5's samplers:
+// same Fisher-Yates with std::default_random_engine(seed) + uniform_int_distribution<size_t>(i, n-1).
 void Engine::ShufflerInit() {
   const uint32_t *train = (const uint32_t *)ds.train_set.ptr;
-  const size_t nw = cfg.arch == kArch6 ? cfg.num_worker : 1;
+  if (cfg.arch == kArch5) {
+    // the epoch's ceil(num_train / batch_size) steps in consecutive ranges: the first (steps % S) samplers take one step
+    // more ("large"), e.g. 15 steps over 4 samplers = 4, 4, 4, 3.  No padding, the last batch may be short.  (The
+    // reference sizes a large sampler's slice as whole batches even where the train set ends inside it -- more
+    // samplers than steps; here every slice ends at the train set.)
+    const size_t S = cfg.num_sample_worker, w = (size_t)worker_id_, steps = num_global_step_;
+    const size_t large = steps % S, small = steps / S;
+    num_data_ = ds.num_train;
+    shuf_host_.assign(train, train + num_data_);
+    num_local_step_ = w < large ? small + 1 : small;
+    global_step_offset_ = w < large ? (small + 1) * w : small * w + large;
+    global_data_offset_ = global_step_offset_ * cfg.batch_size;
+    num_local_data_ = std::min(num_local_step_ * cfg.batch_size,
+                               num_data_ > global_data_offset_ ? num_data_ - global_data_offset_ : 0);
+  } else {
+    const size_t nw = cfg.arch == kArch6 ? cfg.num_worker : 1;
+    const size_t origin = ds.num_train;
+    num_data_ = (origin + nw - 1) / nw * nw; // aligned to num_worker (:46)
+    shuf_host_.assign(train, train + origin);
+    for (size_t i = 0; i < num_data_ - origin; ++i) shuf_host_.push_back(train[i]); // :52-54
+    num_local_data_ = num_data_ / nw;
+    num_local_step_ = (num_local_data_ + cfg.batch_size - 1) / cfg.batch_size;
+    num_global_step_ = num_local_step_ * nw;
+    global_step_offset_ = num_local_step_ * worker_id_;
+    global_data_offset_ = num_local_data_ * worker_id_;
+  }
   const size_t origin = ds.num_train;
-  num_data_ = (origin + nw - 1) / nw * nw; // aligned to num_worker (:46)
-  shuf_host_.assign(train, train + origin);
-  for (size_t i = 0; i < num_data_ - origin; ++i) shuf_host_.push_back(train[i]); // :52-54
-  num_local_data_ = num_data_ / nw;
-  num_local_step_ = (num_local_data_ + cfg.batch_size - 1) / cfg.batch_size;
-  num_global_step_ = num_local_step_ * nw;
-  global_step_offset_ = num_local_step_ * worker_id_;
-  global_data_offset_ = num_local_data_ * worker_id_;
   cur_epoch_ = 0;
   cur_step_ = num_local_step_;
   shuf_initialized_ = false;
@@ -531,7 +595,7 @@ void Engine::Reshuffle() {
   cur_step_ = 0;
   if (cur_epoch_ >= cfg.num_epoch) return;
   uint64_t seed;
-  if (cfg.arch == kArch6) seed = cur_epoch_;   // all samplers share the permutation (:92-94)
+  if (cfg.arch == kArch6 || cfg.arch == kArch5) seed = cur_epoch_; // all samplers share the permutation (:92-94)
   else if (cfg.has_seed) seed = cfg.seed + cur_epoch_;
   else seed = std::chrono::system_clock::now().time_since_epoch().count(); // cuda_shuffler.cc:89
   auto g = std::default_random_engine(seed);
@@ -557,7 +621,8 @@ void Engine::Reshuffle() {
   // the previous epoch's batches may still be copying their seeds out of shuf_dev_ on the pipeline streams
   for (auto &P : pipes_)
     if (P.stream) SAM_HIP(hipStreamSynchronize(P.stream));
-  SAM_HIP(hipMemcpyAsync(shuf_dev_, data + global_data_offset_, num_local_data_ * 4, hipMemcpyHostToDevice, stream_));
+  if (num_local_data_)
+    SAM_HIP(hipMemcpyAsync(shuf_dev_, data + global_data_offset_, num_local_data_ * 4, hipMemcpyHostToDevice, stream_));
   SAM_HIP(hipStreamSynchronize(stream_));
 }
 
@@ -574,6 +639,7 @@ void Engine::SanityCheckBatch(const uint32_t *seeds, size_t n) {
 }
 
 bool Engine::ShufflerNext(Batch *b, hipStream_t copy_stream) {
+  if (num_local_step_ == 0) return false; // arch5: a sampler with no step (more samplers than steps)
   cur_step_++;
   if (cur_step_ >= num_local_step_) Reshuffle();
   if (cur_epoch_ >= cfg.num_epoch) return false;
@@ -678,6 +744,12 @@ void Engine::UploadGraph() {
 // ------------------------------------------------------------------ init
 void Engine::SampleInit(int worker_id, const std::string &ctx) {
   SAM_CHECK(data_ready_, "samgraph_data_init first");
+  if (cfg.arch == kArch5) {
+    SAM_CHECK(role_ == kRoleNone, "arch5: a process is one sampler or one trainer (one sample_init or one train_init)");
+    SAM_CHECK(worker_id >= 0 && (size_t)worker_id < cfg.num_sample_worker, "arch5: sample_init(worker_id) with 0 <= "
+              "worker_id < num_sample_worker = " + std::to_string(cfg.num_sample_worker));
+    role_ = kRoleSampler;
+  }
   worker_id_ = worker_id;
   device_ = parse_device(ctx);
   trainer_device_ = cfg.arch == kArch3 ? cfg.trainer_device : device_;
@@ -685,18 +757,17 @@ void Engine::SampleInit(int worker_id, const std::string &ctx) {
   SAM_HIP(hipSetDevice(device_));
   SAM_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
   // the extract streams belong to the trainer GPU (the same device except under arch3): no stream is added for arch3
-  SAM_HIP(hipSetDevice(trainer_device_));
-  SAM_HIP(hipStreamCreateWithFlags(&stream_extract_, hipStreamNonBlocking));
-  if (cfg.extract_streams > 1) SAM_HIP(hipStreamCreateWithFlags(&stream_extract2_, hipStreamNonBlocking));
-  SAM_HIP(hipSetDevice(device_));
+  // (an arch5 sampler gathers nothing: it has none)
+  if (cfg.arch != kArch5) {
+    SAM_HIP(hipSetDevice(trainer_device_));
+    SAM_HIP(hipStreamCreateWithFlags(&stream_extract_, hipStreamNonBlocking));
+    if (cfg.extract_streams > 1) SAM_HIP(hipStreamCreateWithFlags(&stream_extract2_, hipStreamNonBlocking));
+    SAM_HIP(hipSetDevice(device_));
+  }
   UploadGraph();
   ShufflerInit();
   const uint32_t L = (uint32_t)cfg.fanout.size();
-  // first batch of arch6 is x1.25 (dist_shuffler_aligned.cc:137-140): size every buffer for it
-  max_seeds_ = (size_t)(cfg.batch_size * 1.25) + 1;
-  max_input_.resize(L);
-  max_edges_.resize(L);
-  SAM_GGMS(ggms_sample_batch_capacity(max_seeds_, cfg.fanout.data(), L, max_input_.data(), max_edges_.data(), &max_unique_));
+  ComputeBounds();
   // OrderedHashTable(PredictNumNodes(...)) dist_engine.cc:423-424; direct layout by default
   std::memset(&ht_, 0, sizeof(ht_));
   ht_.direct = cfg.direct_table ? 1 : 0;
@@ -758,8 +829,30 @@ void Engine::SampleInit(int worker_id, const std::string &ctx) {
   if (cfg.UsePresample()) { // dist_engine.cc:455-466: worker 0 ranks the nodes, everybody waits
     auto t0 = std::chrono::steady_clock::now();
     if (worker_id_ == 0) Presample();
-    Barrier("presample ranking");
+    if (cfg.arch == kArch5) { // sampler 0 publishes the ranking (shared pages); the other samplers wait for it
+      if (worker_id_ == 0) __atomic_store_n(&queue_->ranking_ready, (uint64_t)1, __ATOMIC_RELEASE);
+      else WaitRankingReady();
+    } else {
+      Barrier("presample ranking");
+    }
     prof.LogInit(/*kLogInitL2Presample*/ 8, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+  }
+  if (cfg.arch == kArch5) { // the sampler's own batch buffers: it samples into them and packs them into a queue slot
+    sbatch_ = std::make_unique<Batch>();
+    Batch *b = sbatch_.get();
+    b->s_row.resize(L); b->s_col.resize(L); b->s_data.resize(L, nullptr);
+    for (uint32_t i = 0; i < L; ++i) {
+      SAM_HIP(hipMalloc((void **)&b->s_row[i], std::max<size_t>(max_edges_[i], 4) * 4));
+      SAM_HIP(hipMalloc((void **)&b->s_col[i], std::max<size_t>(max_edges_[i], 4) * 4));
+      if (cfg.sample_type == GGMS_RANDOM_WALK) SAM_HIP(hipMalloc((void **)&b->s_data[i], std::max<size_t>(max_edges_[i], 4) * 4));
+    }
+    SAM_HIP(hipMalloc((void **)&b->s_input_nodes, max_unique_ * 4));
+    SAM_HIP(hipMalloc((void **)&b->s_output_nodes, max_seeds_ * 4));
+    SAM_HIP(hipMalloc((void **)&b->s_counts_dev, (3 * L + 8) * 8));
+    SAM_HIP(hipMemset(b->s_counts_dev, 0, (3 * L + 8) * 8));
+    SAM_HIP(hipEventCreateWithFlags(&b->ev_sampled, hipEventDisableTiming));
+    SAM_HIP(hipEventCreateWithFlags(&b->ev_done, hipEventDisableTiming));
+    QueueMap();
   }
   sample_ready_ = true;
 }
@@ -838,7 +931,7 @@ void Engine::BuildCache() {
   const char *feat = (const char *)ds.feat.ptr;
   // the cache and the label table live on the trainer GPU: uploaded through a stream of that device (arch3: the
   // extract stream; the other deployments have one device, and the sampling stream as before)
-  hipStream_t bs = cfg.arch == kArch3 ? stream_extract_ : stream_;
+  hipStream_t bs = (cfg.arch == kArch3 || cfg.arch == kArch5) ? stream_extract_ : stream_;
   // labels are 8 B x N: always resident on the device (the reference keeps them on the host and
   // gathers through zero-copy in gpu_extract mode, dist_loops.cc:938-974)
   label_src_ = dev_upload(ds.label.ptr, ds.label.bytes, bs);
@@ -943,19 +1036,22 @@ void Engine::BuildCache() {
   }
   // miss tier: pinned host memory read by the gather kernel itself (GPUExtractMissData, :573-625); the host-staged
   // path (`gpu_extract` off) reads the table with the host cores instead and needs no device mapping of it
-  // (arch3 gathers its misses the gpu_extract way: zero-copy by the trainer GPU, no CPU-staged path)
-  const bool host_tier = cfg.gpu_extract || (cfg.arch == kArch3 && (num_cached_nodes_ < ds.num_node || ds.feat_mask != 0xffffffffu));
+  // (arch3 and arch5 gather their misses the gpu_extract way: zero-copy by the trainer GPU, no CPU-staged path)
+  const bool host_tier = cfg.gpu_extract || ((cfg.arch == kArch3 || cfg.arch == kArch5) &&
+                                             (num_cached_nodes_ < ds.num_node || ds.feat_mask != 0xffffffffu));
   feat_src_ = host_tier ? map_host(ds.feat.ptr, ds.feat.bytes) : nullptr;
   SAM_HIP(hipStreamSynchronize(bs));
 }
 
 void Engine::TrainInit(int worker_id, const std::string &ctx) {
-  SAM_CHECK(sample_ready_, "samgraph_sample_init first");
+  if (cfg.arch == kArch5)
+    Arch5TrainerInit(worker_id, ctx);
+  else
+    SAM_CHECK(sample_ready_, "samgraph_sample_init first");
   if (cfg.arch == kArch3)
     SAM_CHECK(parse_device(ctx) == trainer_device_, "arch3: train_init on the config's trainer_ctx");
   else
     SAM_CHECK(parse_device(ctx) == device_, "arch6: sampler and trainer share the GPU (cuda_cache_manager_host.cc:152-155)");
-  (void)worker_id;
   SAM_HIP(hipSetDevice(trainer_device_));
   auto t0 = std::chrono::steady_clock::now();
   BuildCache();
@@ -1002,6 +1098,7 @@ void Engine::TrainInit(int worker_id, const std::string &ctx) {
     SAM_HIP(hipEventCreate(&b->ev_xstart));
     SAM_HIP(hipEventCreate(&b->ev_done));
     SAM_GGMS(ggms_launch_timer_create(&b->gather_timer));
+    if (cfg.arch == kArch5) SAM_GGMS(ggms_launch_timer_create(&b->handoff_timer)); // rides on the unpack
     if (cfg.arch == kArch3) { // the sampler's side of the slot, on the sampler GPU (GetGraphFileCtx, cuda_engine.cc:437-481)
       SAM_GGMS(ggms_launch_timer_create(&b->handoff_timer));
       SAM_HIP(hipSetDevice(device_));
@@ -1079,6 +1176,10 @@ Batch *Engine::AcquireSlot(bool background) {
 // `lookahead` more of them enqueued than it was asked for -- batch k+1 samples while batch k's rows are gathered and
 // while the caller trains on batch k.  The pool hands them out in the same order (GetNextBatch).
 void Engine::RunSampleOnce(bool background) {
+  if (IsArch5Sampler()) { // dist_loops_arch5.cc RunSampleSubLoopOnce: sample one batch and send it
+    SendOne();
+    return;
+  }
   // the role is an argument, never inferred from the std::thread member (the new thread would read it while
   // ExtractStart is still assigning it)
   if (background) { // background loop: one per iteration
@@ -1105,6 +1206,16 @@ bool Engine::EnqueueOne(bool background) {
   SAM_HIP(hipSetDevice(device_));
   Batch *b = AcquireSlot(background);
   if (!b) return false;
+  if (cfg.arch == kArch5) { // a trainer: the next message from the queue instead of a batch of its own
+    if (!Receive(b)) {
+      std::lock_guard<std::mutex> lk(pool_mu_);
+      b->in_use = false;
+      return false;
+    }
+    ++enq_count_;
+    EnqueueGather(b, nullptr);
+    return true;
+  }
   // Consecutive batches go to the sampling pipelines round-robin; a batch's seeds are copied on ITS pipeline's
   // stream (not behind another pipeline's queued sampling).
   Pipe &P = pipes_[enq_count_ % pipes_.size()];
@@ -1136,16 +1247,24 @@ bool Engine::EnqueueOne(bool background) {
                              states_, num_states_, b->s_row.data(), b->s_col.data(), b->s_counts_dev, &extra, P.ws,
                              ws_bytes_, ss));
   P.ht.version = ht.version; // the batch bumped the table's version stamp
-  uint64_t *n_in = b->counts_dev + 3 * L, *n_miss = b->counts_dev + 3 * L + 2; // [3L + 1] = the batch's status word
   SAM_HIP(hipMemsetAsync(b->s_counts_dev + 3 * L + 2, 0, 8, ss));
   SAM_HIP(hipEventRecord(b->ev_sampled, ss));
+  EnqueueGather(b, ss);
+  return true;
+}
+
+// the labels and the feature rows of batch b, sampled on stream ss; then b goes to the pool
+void Engine::EnqueueGather(Batch *b, hipStream_t ss) {
+  const uint32_t L = (uint32_t)cfg.fanout.size();
+  uint64_t *n_in = b->counts_dev + 3 * L, *n_miss = b->counts_dev + 3 * L + 2; // [3L + 1] = the batch's status word
   // arch3: everything from here on runs on the trainer GPU, on the batch's extract stream -- hand-off, labels, rows,
-  // counts -- and the sampling stream is left to the sampler
-  const bool arch3 = cfg.arch == kArch3;
+  // counts -- and the sampling stream is left to the sampler.  arch5: the same on the trainer's GPU, starting with the
+  // unpack of the batch's queue slot (there is no sampling stream)
+  const bool remote = cfg.arch == kArch3 || cfg.arch == kArch5; // the batch was sampled in another place
   // DoGPULabelExtract (dist_loops.cc:938-974) needs the seeds only: it rides behind the batch on its sampling stream, not
   // between two gathers on the extract stream, which bounds the step.  (Not on a stream of its own: HIP streams share 4
   // hardware queues, and a fifth stream serialises streams that have nothing to do with each other.)
-  if (!arch3) SAM_GGMS(ggms_extract(b->label, label_src_, b->output_nodes, b->num_seeds, 1, GGMS_I64, ss));
+  if (!remote) SAM_GGMS(ggms_extract(b->label, label_src_, b->output_nodes, b->num_seeds, 1, GGMS_I64, ss));
   const bool mock = ds.feat_mask != 0xffffffffu; // SAMGRAPH_EMPTY_FEAT: host rows are node & mask
   // The extract stream bounds the step, and every event record / wait / small copy on it is a packet the command
   // processor works through between two gathers -- 28 us of dead time per 0.7-ms step with six of them
@@ -1159,19 +1278,20 @@ bool Engine::EnqueueOne(bool background) {
   const bool gather_counts = cfg.UseGPUCache() && (mock || ((num_replica_ || cache_table_) && can_miss));
   static const bool lean_off = [] { const char *e = getenv("SAMGRAPH_LEAN_EXTRACT"); return e && e[0] == '0'; }(); // A/B hook
   b->lean = !lean_off && !StagedHostTier() && !gather_counts && !node_access_dev_;
-  if (!arch3 && b->lean) {
+  if (!remote && b->lean) {
     SAM_HIP(hipMemcpyAsync(b->counts, b->counts_dev, (3 * L + 8) * 8, hipMemcpyDeviceToHost, ss));
     SAM_HIP(hipEventRecord(b->ev_done, ss)); // labels and counts are out; the rows: gather_timer
-  } else if (!arch3) {
+  } else if (!remote) {
     SAM_HIP(hipEventRecord(b->ev_label, ss));
   }
   // The gather is HBM-bound, the sampler latency-bound: they run on separate streams so that batch k's
   // extract overlaps batch k+1's sampling (the reference serialises them, dist_loops_arch6.cc:248-251)
   hipStream_t xs = (b->lean && stream_extract2_ && (enq_count_ & 1)) ? stream_extract2_ : stream_extract_;
-  if (arch3) SAM_HIP(hipSetDevice(trainer_device_));
-  SAM_HIP(hipStreamWaitEvent(xs, b->ev_sampled, 0));
-  if (arch3) {
-    Handoff(b, xs); // the batch's arrays, S -> T; the gather below reads the input nodes and their count on T
+  if (remote) SAM_HIP(hipSetDevice(trainer_device_));
+  if (cfg.arch == kArch5) Unpack(b, xs); // the batch's arrays, queue slot -> T (the slot is free again when it returns)
+  else SAM_HIP(hipStreamWaitEvent(xs, b->ev_sampled, 0));
+  if (remote) {
+    if (cfg.arch == kArch3) Handoff(b, xs); // the batch's arrays, S -> T; the gather below reads the input nodes and their count on T
     SAM_GGMS(ggms_extract(b->label, label_src_, b->output_nodes, b->num_seeds, 1, GGMS_I64, xs));
   }
   if (b->lean) SAM_GGMS(ggms_launch_timer_arm(b->gather_timer));
@@ -1208,10 +1328,10 @@ bool Engine::EnqueueOne(bool background) {
   if (!b->lean) {
     if (node_access_dev_) // Profiler::LogNodeAccess (profiler.cc:570-575): visits per node, counted on the device
       SAM_GGMS(ggms_count_nodes(node_access_dev_, b->input_nodes, max_unique_, n_in, xs));
-    if (!arch3) SAM_HIP(hipStreamWaitEvent(xs, b->ev_label, 0)); // the batch is complete when its labels are, too
+    if (!remote) SAM_HIP(hipStreamWaitEvent(xs, b->ev_label, 0)); // the batch is complete when its labels are, too
     SAM_HIP(hipMemcpyAsync(b->counts, b->counts_dev, (3 * L + 8) * 8, hipMemcpyDeviceToHost, xs));
     SAM_HIP(hipEventRecord(b->ev_done, xs));
-  } else if (arch3) { // counts of T (the gather may have added to them) to the host behind the rows
+  } else if (remote) { // counts of T (the gather may have added to them) to the host behind the rows
     SAM_HIP(hipMemcpyAsync(b->counts, b->counts_dev, (3 * L + 8) * 8, hipMemcpyDeviceToHost, xs));
     SAM_HIP(hipEventRecord(b->ev_done, xs));
   }
@@ -1220,7 +1340,6 @@ bool Engine::EnqueueOne(bool background) {
     pool_.push_back(b); // graph_pool->Submit
   }
   pool_cv_.notify_all();
-  return true;
 }
 
 // arch3: DoGraphCopy + DoIdCopy (cuda/cuda_loops.cc:600-655) as one launch on the trainer GPU's extract stream.  Every
@@ -1246,6 +1365,206 @@ void Engine::Handoff(Batch *b, hipStream_t xs) {
   add(b->s_counts_dev, b->counts_dev, nullptr, 3 * L + 8, 3 * L + 8, 8);
   SAM_GGMS(ggms_launch_timer_arm(b->handoff_timer)); // kLogL2GraphCopyTime: the hand-off's own time
   SAM_GGMS(ggms_batch_handoff(segs, n, xs));
+}
+
+// ---- arch5: the batch queue ----------------------------------------------------------------------------------------
+// MemoryQueue (dist/memory_queue.cc) + DistEngine's queue set-up (dist_engine.cc:395-397).  The reference serialises a
+// Task into a queue slot with host copies and a mutex-guarded ring; here the sampler's GPU writes the batch into the
+// slot itself (ggms_queue_pack: one launch, every length read on the device) and the trainer's GPU reads it out
+// (ggms_queue_unpack), and the ring is lock-free: tickets from two counters, one sequence word per slot.
+
+void Engine::ComputeBounds() {
+  const uint32_t L = (uint32_t)cfg.fanout.size();
+  // first batch of arch6 is x1.25 (dist_shuffler_aligned.cc:137-140): size every buffer for it
+  max_seeds_ = (size_t)(cfg.batch_size * 1.25) + 1;
+  max_input_.resize(L);
+  max_edges_.resize(L);
+  SAM_GGMS(ggms_sample_batch_capacity(max_seeds_, cfg.fanout.data(), L, max_input_.data(), max_edges_.data(), &max_unique_));
+}
+
+// the parent, before the fork: no GPU is touched (every process registers the slots itself, QueueMap)
+void Engine::QueueInit() {
+  static_assert(sizeof(QueueCtl) <= 4096, "the control block fits its page");
+  const auto t0 = std::chrono::steady_clock::now();
+  const uint32_t L = (uint32_t)cfg.fanout.size();
+  SAM_CHECK(L <= GGMS_QUEUE_MAX_LAYERS, "arch5: at most GGMS_QUEUE_MAX_LAYERS layers");
+  SAM_GGMS(ggms_queue_layout(&qlay_, L, max_edges_.data(), max_unique_, max_seeds_, cfg.sample_type == GGMS_RANDOM_WALK));
+  queue_depth_ = cfg.queue_depth;
+  const size_t bytes = 4096 + queue_depth_ * qlay_.slot_bytes;
+  void *m = mmap(nullptr, bytes, PROT_READ | PROT_WRITE, MAP_SHARED | MAP_ANONYMOUS, -1, 0);
+  SAM_CHECK(m != MAP_FAILED, "arch5: batch queue mmap of " + std::to_string(bytes) + " bytes failed");
+  queue_ = (QueueCtl *)m;
+  queue_slots_ = (char *)m + 4096;
+  for (size_t i = 0; i < queue_depth_; ++i) __atomic_store_n(&QueueHeader(i)->seq, (uint64_t)i, __ATOMIC_RELAXED);
+  __atomic_thread_fence(__ATOMIC_SEQ_CST);
+  prof.LogInit(/*kLogInitL2DistQueue*/ 7, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+  log_info("arch5: batch queue of " + std::to_string(queue_depth_) + " slots x " + std::to_string(qlay_.slot_bytes) + " bytes");
+}
+
+// this process's device reads / writes the slots in place: pinned and mapped (cudaHostRegister, dist_engine.cc:217-241)
+void Engine::QueueMap() {
+  SAM_HIP(hipHostRegister(queue_slots_, queue_depth_ * qlay_.slot_bytes, hipHostRegisterMapped));
+  void *d = nullptr;
+  SAM_HIP(hipHostGetDevicePointer(&d, queue_slots_, 0));
+  queue_slots_dev_ = (char *)d;
+}
+
+ggms_queue_header_t *Engine::QueueHeader(uint64_t pos) const {
+  return (ggms_queue_header_t *)(queue_slots_ + (pos % queue_depth_) * qlay_.slot_bytes);
+}
+
+// Every wait on another process has a deadline (queue_timeout_s): a sampler or trainer that died, or that stopped
+// early, must not hold the others.  The process then ends with status 1 -- nothing in it is at fault, there is nothing
+// to dump.  false: the engine is shutting down (a background loop waiting for a message that will not come).
+bool Engine::QueueWait(const uint64_t *word, uint64_t want, const char *what, bool stoppable) {
+  const auto t0 = std::chrono::steady_clock::now();
+  for (uint64_t spin = 0;; ++spin) {
+    if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == want) return true;
+    if (spin < 4096) continue;
+    if (stoppable && bg_stop_.load()) return false;
+    if ((spin & 63) == 0) {
+      const double waited = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+      if (waited > cfg.queue_timeout_s) {
+        std::fprintf(stderr, "[samgraph-amd FATAL] %s:%d: arch5: %s %d (device %d) waited %d s for %s -- queue_timeout_s "
+                             "= %g s passed; a process on the other side died, stopped early or is stuck\n",
+                     __FILE__, __LINE__, role_ == kRoleSampler ? "sampler" : "trainer", worker_id_, device_, (int)waited,
+                     what, cfg.queue_timeout_s);
+        std::fflush(stderr);
+        _exit(1);
+      }
+    }
+    spin < 65536 ? (void)sched_yield() : (void)usleep(100);
+  }
+}
+
+// pre_sample: the other samplers and the trainers wait for sampler 0's ranking (dist_engine.cc:451-466)
+void Engine::WaitRankingReady() { QueueWait(&queue_->ranking_ready, 1, "sampler 0's presample ranking", false); }
+
+// train_init of an arch5 trainer: its GPU, its extract streams, its share of each epoch's messages, the slots
+void Engine::Arch5TrainerInit(int worker_id, const std::string &ctx) {
+  SAM_CHECK(data_ready_, "samgraph_data_init first");
+  SAM_CHECK(role_ == kRoleNone, "arch5: a process is one sampler or one trainer (one sample_init or one train_init)");
+  SAM_CHECK(worker_id >= 0 && (size_t)worker_id < cfg.num_train_worker, "arch5: train_init(worker_id) with 0 <= "
+            "worker_id < num_train_worker = " + std::to_string(cfg.num_train_worker));
+  role_ = kRoleTrainer;
+  worker_id_ = worker_id;
+  device_ = trainer_device_ = parse_device(ctx);
+  SAM_HIP(hipSetDevice(device_));
+  SAM_HIP(hipStreamCreateWithFlags(&stream_extract_, hipStreamNonBlocking));
+  if (cfg.extract_streams > 1) SAM_HIP(hipStreamCreateWithFlags(&stream_extract2_, hipStreamNonBlocking));
+  // the scripts' split of an epoch's steps over the trainers (multi_gpu/train_graphsage.py: steps w, w + T, ...)
+  const size_t T = cfg.num_train_worker;
+  num_local_step_ = num_global_step_ / T + ((size_t)worker_id < num_global_step_ % T ? 1 : 0);
+  prof.Resize(cfg.num_epoch, num_global_step_);
+  if (cfg.UsePresample()) WaitRankingReady(); // the cache is built from sampler 0's ranking
+  QueueMap();
+  sample_ready_ = true; // (the bounds are the parent's, ComputeBounds in DataInit)
+}
+
+// RunSampleSubLoopOnce (dist_loops_arch5.cc): shuffle, sample, send.  The reference's DoGetCacheMissIndex is not run:
+// the trainer's gather resolves hits itself, and a hit / miss split would only add bytes to the message.
+void Engine::SendOne() {
+  using clk = std::chrono::steady_clock;
+  auto since = [](clk::time_point t) { return std::chrono::duration<double>(clk::now() - t).count(); };
+  SAM_HIP(hipSetDevice(device_));
+  const uint32_t L = (uint32_t)cfg.fanout.size();
+  Batch *b = sbatch_.get();
+  hipStream_t ss = stream_;
+  const auto t0 = clk::now();
+  if (!ShufflerNext(b, ss))
+    fatal(__FILE__, __LINE__, "arch5: sample_once() on sampler " + std::to_string(worker_id_) + " after its last batch (" +
+                                  std::to_string(cfg.num_epoch) + " epochs x " + std::to_string(num_local_step_) +
+                                  " steps, num_local_step())");
+  const double t_shuffle = since(t0);
+  Pipe &P = pipes_[0];
+  ggms_sample_extra_t extra = extra_;
+  extra.data = b->s_data.data();
+  extra.seeds_distinct = BatchSeedsDistinct(cur_step_ * cfg.batch_size, b->num_seeds) ? 1u : 0u;
+  ggms_hashtable_t ht = P.ht;
+  ht.n2o = b->s_input_nodes;
+  ht.n2o_size = max_unique_;
+  SAM_GGMS(ggms_sample_batch(cfg.sample_type, &graph_, b->s_output_nodes, b->num_seeds, cfg.fanout.data(), L, &ht,
+                             states_, num_states_, b->s_row.data(), b->s_col.data(), b->s_counts_dev, &extra, P.ws,
+                             ws_bytes_, ss));
+  P.ht.version = ht.version;
+  SAM_HIP(hipMemsetAsync(b->s_counts_dev + 3 * L + 2, 0, 8, ss)); // the trainer's miss count starts at 0
+  SAM_HIP(hipEventRecord(b->ev_sampled, ss));
+  SAM_HIP(hipEventSynchronize(b->ev_sampled)); // DoGPUSample ends with a stream sync too
+  const double t_sample = since(t0);
+  // send: a free slot (the ticket's), the pack, its completion, then the slot is published
+  const auto t1 = clk::now();
+  const uint64_t pos = __atomic_fetch_add(&queue_->enqueue_pos, 1, __ATOMIC_ACQ_REL);
+  ggms_queue_header_t *h = QueueHeader(pos);
+  const std::string what = "a free queue slot from the trainers (ticket " + std::to_string(pos) + ")";
+  QueueWait(&h->seq, pos, what.c_str(), false);
+  ggms_queue_batch_t src{};
+  for (uint32_t i = 0; i < L; ++i) {
+    src.row[i] = b->s_row[i];
+    src.col[i] = b->s_col[i];
+    src.data[i] = b->s_data[i];
+  }
+  src.input_nodes = b->s_input_nodes;
+  src.output_nodes = b->s_output_nodes;
+  src.counts = b->s_counts_dev;
+  SAM_GGMS(ggms_queue_pack(queue_slots_dev_ + (pos % queue_depth_) * qlay_.slot_bytes, &qlay_, &src, b->key, b->num_seeds, ss));
+  SAM_HIP(hipEventRecord(b->ev_done, ss));
+  SAM_HIP(hipEventSynchronize(b->ev_done));
+  const uint64_t status = h->counts[3 * L + 1], num_input = h->counts[3 * L];
+  uint64_t edges = 0;
+  for (uint32_t i = 0; i < L; ++i) edges += h->counts[3 * i];
+  if (status != 0) { // as Finish does for the other deployments: a kernel of the batch hit a bound
+    fprintf(stderr, "[samgraph] FATAL: device status %#llx after batch %llu on sampler %d: results are invalid\n",
+            (unsigned long long)status, (unsigned long long)b->key, worker_id_);
+    abort();
+  }
+  __atomic_store_n(&h->seq, pos + 1, __ATOMIC_RELEASE); // published
+  const double t_send = since(t1);
+  // the items the multi_gpu scripts read (dist_loops_arch5.cc:95-107); no cache-miss split here, so its item is 0
+  prof.LogEpochAdd(b->key, 0 /*kLogEpochSampleTime*/, t_sample);
+  prof.LogEpochAdd(b->key, 1 /*KLogEpochSampleGetCacheMissIndexTime*/, 0.0);
+  prof.LogEpochAdd(b->key, 2 /*kLogEpochSampleSendTime*/, t_send);
+  prof.LogEpochAdd(b->key, 3 /*kLogEpochSampleTotalTime*/, t_sample + t_send);
+  prof.LogEpochAdd(b->key, 15 /*kLogEpochNumSample*/, (double)edges);
+  prof.LogStep(b->key, 0 /*kLogL1NumSample*/, (double)edges);
+  prof.LogStep(b->key, 1 /*kLogL1NumNode*/, (double)num_input);
+  prof.LogStep(b->key, 3 /*kLogL1SampleTime*/, t_sample);
+  prof.LogStep(b->key, 4 /*kLogL1SendTime*/, t_send);
+  prof.LogStep(b->key, 17 /*kLogL2ShuffleTime*/, t_shuffle);
+}
+
+// RunCacheDataCopySubLoopOnce's q->Recv (dist_loops_arch5.cc): take the next ticket and wait for its message
+bool Engine::Receive(Batch *b) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const uint64_t pos = __atomic_fetch_add(&queue_->dequeue_pos, 1, __ATOMIC_ACQ_REL);
+  ggms_queue_header_t *h = QueueHeader(pos);
+  const std::string what = "a batch from the samplers (ticket " + std::to_string(pos) + ")";
+  if (!QueueWait(&h->seq, pos + 1, what.c_str(), true)) return false;
+  b->queue_pos = pos;
+  b->key = h->key;
+  b->num_seeds = h->num_output;
+  SAM_CHECK(b->num_seeds <= max_seeds_ && b->key < cfg.num_epoch * num_global_step_, "arch5: a queue slot with a bad header");
+  b->recv_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return true;
+}
+
+// DoGraphCopy (dist_loops_arch5.cc): the slot's arrays into the batch's buffers on this GPU, one launch on xs; the
+// slot goes back to the samplers as soon as that launch has completed (the timer's end: the host waits for it)
+void Engine::Unpack(Batch *b, hipStream_t xs) {
+  const uint32_t L = (uint32_t)cfg.fanout.size();
+  ggms_queue_batch_t dst{};
+  for (uint32_t i = 0; i < L; ++i) {
+    dst.row[i] = b->row[i];
+    dst.col[i] = b->col[i];
+    dst.data[i] = b->data[i];
+  }
+  dst.input_nodes = b->input_nodes;
+  dst.output_nodes = b->output_nodes;
+  dst.counts = b->counts_dev;
+  SAM_GGMS(ggms_launch_timer_arm(b->handoff_timer));
+  SAM_GGMS(ggms_queue_unpack(&dst, queue_slots_dev_ + (b->queue_pos % queue_depth_) * qlay_.slot_bytes, &qlay_, xs));
+  double us = 0;
+  SAM_GGMS(ggms_launch_timer_elapsed_us(b->handoff_timer, &us)); // blocks until the unpack has completed
+  __atomic_store_n(&QueueHeader(b->queue_pos)->seq, b->queue_pos + queue_depth_, __ATOMIC_RELEASE); // free
 }
 
 // ---- the host-staged feature path: arch6 without `gpu_extract` (the reference's SGNN mode) --------------------------
@@ -1473,7 +1792,7 @@ void Engine::Finish(Batch *b, Batch *prev) {
     abort();
   }
   float ms_sample = 0, ms_copy = 0;
-  (void)hipEventElapsedTime(&ms_sample, b->ev_start, b->ev_sampled);
+  if (cfg.arch != kArch5) (void)hipEventElapsedTime(&ms_sample, b->ev_start, b->ev_sampled); // (arch5: sampled elsewhere)
   if (b->lean) ms_copy = (float)(us_gather * 1e-3); // the gather kernel's own time
   else (void)hipEventElapsedTime(&ms_copy, b->ev_xstart, b->ev_done); // not from ev_sampled: that would add the queueing behind the previous extract
   const double s_copy_epoch = b->lean ? us_busy * 1e-6 : ms_copy * 1e-3;
@@ -1493,13 +1812,18 @@ void Engine::Finish(Batch *b, Batch *prev) {
   prof.LogEpochAdd(b->key, 12 /*kLogEpochFeatureBytes*/, b->num_input * row_bytes);
   prof.LogEpochAdd(b->key, 13 /*kLogEpochMissBytes*/, b->num_miss * row_bytes);
   prof.LogEpochAdd(b->key, 15 /*kLogEpochNumSample*/, (double)edges);
-  if (cfg.arch == kArch3) { // what the hand-off moved (DoGraphCopy / DoIdCopy, cuda/cuda_loops.cc:629,653) and its time
-    double us_handoff = 0;
+  if (cfg.arch == kArch3 || cfg.arch == kArch5) { // what the hand-off (arch5: the unpack) moved and its time
+    double us_handoff = 0;                           // (DoGraphCopy / DoIdCopy, cuda/cuda_loops.cc:629,653)
     SAM_GGMS(ggms_launch_timer_elapsed_us(b->handoff_timer, &us_handoff));
     const double per_edge = cfg.sample_type == GGMS_RANDOM_WALK ? 12.0 : 8.0; // row + col (+ data)
     prof.LogStep(b->key, 12 /*kLogL1GraphBytes*/, edges * per_edge);
     prof.LogStep(b->key, 11 /*kLogL1IdBytes*/, (b->num_input + b->num_seeds) * 4.0);
     prof.LogStep(b->key, 22 /*kLogL2GraphCopyTime*/, us_handoff * 1e-6);
+    if (cfg.arch == kArch5) { // RunCacheDataCopySubLoopOnce: copy time = recv + graph copy + feature copy
+      prof.LogStep(b->key, 5 /*kLogL1RecvTime*/, b->recv_s);
+      prof.LogStepAdd(b->key, 6 /*kLogL1CopyTime*/, b->recv_s + us_handoff * 1e-6);
+      prof.LogEpochAdd(b->key, 8 /*kLogEpochCopyTime*/, b->recv_s + us_handoff * 1e-6);
+    }
   }
 }
 
@@ -1513,8 +1837,10 @@ uint64_t Engine::GetNextBatch() { // operation.cc:366-378 + GraphPool::GetGraphB
     std::unique_lock<std::mutex> lk(pool_mu_);
     if (pool_.empty() && !bg_running_.load())
       fatal(__FILE__, __LINE__, "get_next_batch with nothing sampled: call sample_once() or extract_start() first");
-    pool_cv_.wait(lk, [&] { return !pool_.empty() || bg_stop_.load(); });
-    if (pool_.empty()) fatal(__FILE__, __LINE__, "engine shut down while waiting for a batch");
+    pool_cv_.wait(lk, [&] { return !pool_.empty() || bg_stop_.load() || !bg_running_.load(); });
+    if (pool_.empty())
+      fatal(__FILE__, __LINE__, bg_stop_.load() ? "engine shut down while waiting for a batch"
+                                                : "get_next_batch: the extract loop handled its count (extract_start) and ended");
     b = pool_.front();
     pool_.pop_front();
   }
@@ -1528,7 +1854,23 @@ uint64_t Engine::GetNextBatch() { // operation.cc:366-378 + GraphPool::GetGraphB
 }
 
 void Engine::ExtractStart(int count) { // dist_engine.cc StartExtract: one background sample+extract thread
-  (void)count;
+  if (cfg.arch == kArch5) { // DataCopySubLoop(count), dist_loops_arch5.cc: `count` messages, then the thread ends
+    SAM_CHECK(role_ == kRoleTrainer && train_ready_, "arch5: extract_start on a trainer, after train_init");
+    SAM_CHECK(count >= 0, "arch5: extract_start(count >= 0)");
+    if (bg_.joinable()) bg_.join(); // the previous call's loop (the scripts call it once per epoch)
+    bg_running_ = true;
+    bg_ = std::thread([this, count] {
+      SAM_HIP(hipSetDevice(device_));
+      for (int i = 0; i < count && !bg_stop_; ++i)
+        if (!EnqueueOne(true)) break; // only when shutting down
+      {
+        std::lock_guard<std::mutex> lk(pool_mu_);
+        bg_running_ = false;
+      }
+      pool_cv_.notify_all();
+    });
+    return;
+  }
   SAM_CHECK(!bg_running_.load(), "extract thread already running");
   bg_running_ = true; // set before the thread exists: nothing the thread runs looks at bg_ itself
   bg_ = std::thread([this] {

@@ -3,7 +3,8 @@
 // Counterpart of the reference's Engine / GPUEngine / DistEngine
 // (samgraph/common/engine.{h,cc}, cuda/cuda_engine.cc, dist/dist_engine.cc) for the
 // deployments on the hot path: arch1 (one process, one GPU), arch3 (one process, a
-// sampler GPU and a trainer GPU) and arch6 (one process per GPU, GGMS shards).  It owns device memory (hipMalloc, no framework allocator),
+// sampler GPU and a trainer GPU), arch5 (sampler processes and trainer processes joined by a batch queue in shared host
+// memory) and arch6 (one process per GPU, GGMS shards).  It owns device memory (hipMalloc, no framework allocator),
 // streams, the shuffler, the sampler state and the feature cache, and drives the
 // leaf operators of include/ggms.h.  Everything below is plain C++17 + HIP runtime.
 #pragma once
@@ -60,6 +61,9 @@ struct RunConfig {
   size_t random_walk_length = 0, num_random_walk = 0, num_neighbor = 0;
   double random_walk_restart_prob = 0.0;
   size_t num_worker = 1;
+  // arch5: S sampler processes, T trainer processes; the batch queue's ring size and the deadline of every wait on it
+  size_t num_sample_worker = 0, num_train_worker = 0, queue_depth = 0;
+  double queue_timeout_s = 300.0;
   int sampler_device = 0, trainer_device = 0;
   bool trainer_on_host = false; // arch0 with trainer_ctx = cpu:N (host-only plumbing runs)
   size_t omp_thread_num = 1;    // arch0: threads of the sampling / extract loops (RunConfig::omp_thread_num)
@@ -165,7 +169,10 @@ struct Batch {
   std::vector<uint32_t *> s_row, s_col, s_data;
   uint32_t *s_input_nodes = nullptr, *s_output_nodes = nullptr;
   uint64_t *s_counts_dev = nullptr;
-  ggms_launch_timer_t *handoff_timer = nullptr;
+  ggms_launch_timer_t *handoff_timer = nullptr; // (arch5: rides on the unpack launch)
+  // arch5 trainer: the queue ticket whose slot this batch came from, and the host's wait for that message
+  uint64_t queue_pos = 0;
+  double recv_s = 0;
 };
 
 class Engine {
@@ -197,6 +204,7 @@ class Engine {
   size_t NumLocalStep() const { return num_local_step_; }
   uint64_t BatchKey(uint64_t epoch, uint64_t step) const { return epoch * num_global_step_ + step; }
   int trainer_device() const { return cfg.arch == kArch3 ? trainer_device_ : device_; }
+  bool IsArch5Sampler() const { return cfg.arch == kArch5 && role_ == kRoleSampler; }
   int batch_device_type() const { return (cfg.arch == kArch0 && cfg.trainer_on_host) ? 0 : 2; } // DeviceType, common.h:48
   void Barrier(const char *what = "step");
   void *OpenPeer(const hipIpcMemHandle_t &handle, uint32_t peer, size_t bytes, const char *what);
@@ -239,6 +247,32 @@ class Engine {
   void Finish(Batch *b, Batch *prev);
   void EnablePeerAccess(); // arch3: the trainer GPU reads the sampler GPU's batch buffers in place
   void Handoff(Batch *b, hipStream_t xs);
+  void EnqueueGather(Batch *b, hipStream_t ss); // label + feature gather of a sampled (arch3: handed-off) batch
+
+  // arch5 (dist/dist_engine.cc, dist_loops_arch5.cc): a process is a sampler or a trainer.  The batch queue is one
+  // anonymous MAP_SHARED mapping made by DataInit (before the fork): a control page, then queue_depth_ slots of
+  // qlay_.slot_bytes each (include/ggms.h, ggms_queue_header_t).  Tickets: the k-th message goes to slot k % depth;
+  // a slot's `seq` word is k when a producer may fill it for ticket k, k + 1 once it holds ticket k's batch, and
+  // k + depth when the consumer has freed it (a bounded MPMC ring with one sequence word per slot).
+  enum Role { kRoleNone, kRoleSampler, kRoleTrainer };
+  Role role_ = kRoleNone;
+  struct QueueCtl;
+  QueueCtl *queue_ = nullptr;
+  char *queue_slots_ = nullptr;     // host address of slot 0
+  char *queue_slots_dev_ = nullptr; // ... the same memory as this process's device sees it (hipHostRegister, Mapped)
+  size_t queue_depth_ = 0;
+  ggms_queue_layout_t qlay_{};
+  std::unique_ptr<Batch> sbatch_; // the sampler's own batch buffers (it packs each batch before it samples the next)
+  void ComputeBounds();
+  void QueueInit();
+  void QueueMap();
+  ggms_queue_header_t *QueueHeader(uint64_t pos) const;
+  bool QueueWait(const uint64_t *word, uint64_t want, const char *what, bool stoppable);
+  void WaitRankingReady();
+  void Arch5TrainerInit(int worker_id, const std::string &ctx);
+  void SendOne();                                // a sampler's sample_once
+  bool Receive(Batch *b);                        // a trainer takes the next message (host side)
+  void Unpack(Batch *b, hipStream_t xs);         // ... copies it out of its slot and frees the slot
 
   bool data_ready_ = false, sample_ready_ = false, train_ready_ = false, shutdown_ = false;
   int worker_id_ = 0, device_ = 0;
@@ -271,7 +305,7 @@ class Engine {
   std::vector<Pipe> pipes_;
   size_t enq_count_ = 0;
   hipEvent_t last_rng_done_ = nullptr;
-  size_t max_seeds_ = 0, max_unique_ = 0;
+  size_t max_seeds_ = 0, max_unique_ = 0; // batch bounds (ComputeBounds)
   std::vector<size_t> max_input_, max_edges_;
   // shuffler
   std::vector<uint32_t> shuf_host_;

@@ -447,6 +447,40 @@ def batch_handoff(segments):
     check(lib().ggms_batch_handoff(arr, n, _stream()), "ggms_batch_handoff")
 
 
+def queue_layout(max_edges, max_input, max_output, has_data=False):
+    """ggms_queue_layout (include/ggms.h): offsets and size of one batch-queue slot for these bounds."""
+    lay = _lib.QueueLayout()
+    me = (C.c_size_t * len(max_edges))(*[int(x) for x in max_edges])
+    check(lib().ggms_queue_layout(C.byref(lay), len(max_edges), me, int(max_input), int(max_output), int(bool(has_data))),
+          "ggms_queue_layout")
+    return lay
+
+
+def _queue_batch(lay, rows, cols, datas, input_nodes, output_nodes, counts):
+    b = _lib.QueueBatch()
+    for i in range(lay.num_layer):
+        b.row[i], b.col[i] = rows[i].data_ptr(), cols[i].data_ptr()
+        b.data[i] = datas[i].data_ptr() if lay.has_data else None
+    b.input_nodes, b.output_nodes, b.counts = input_nodes.data_ptr(), output_nodes.data_ptr(), counts.data_ptr()
+    return b
+
+
+def queue_pack(slot_ptr, lay, rows, cols, datas, input_nodes, output_nodes, counts, key, num_output):
+    """ggms_queue_pack: one launch on the current stream writes the slot at device address `slot_ptr` (an int: mapped
+    host memory or device memory).  Arrays are device tensors sized to the layout's bounds; counts holds the batch's
+    3L + 8 counts words (int64, on the device), from which the kernel reads every length but the output nodes'."""
+    b = _queue_batch(lay, rows, cols, datas, input_nodes, output_nodes, counts)
+    check(lib().ggms_queue_pack(C.c_void_p(slot_ptr), C.byref(lay), C.byref(b), int(key), int(num_output), _stream()),
+          "ggms_queue_pack")
+
+
+def queue_unpack(slot_ptr, lay, rows, cols, datas, input_nodes, output_nodes, counts):
+    """ggms_queue_unpack: one launch on the current stream copies the slot's arrays and counts words into the given
+    device tensors, every length read from the slot's header by the kernel."""
+    b = _queue_batch(lay, rows, cols, datas, input_nodes, output_nodes, counts)
+    check(lib().ggms_queue_unpack(C.byref(b), C.c_void_p(slot_ptr), C.byref(lay), _stream()), "ggms_queue_unpack")
+
+
 def owner_histogram(table, nodes, num_part, slots_out, counts, num=None, num_dev=None):
     """slots_out[i] = table[nodes[i]]; counts[p] += rows of the batch owned by shard p (p = num_part: host tier)."""
     _require_gpu(nodes)
