@@ -21,6 +21,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+from engine_driver import base_config, record_batch, run_worker  # noqa: E402
+
 
 def run_started(sam, num_layers, out_prefix):
     import torch
@@ -28,20 +30,7 @@ def run_started(sam, num_layers, out_prefix):
     sam.start()
     for _ in range(sam.num_epoch() * sam.num_local_step()):
         key = sam.get_next_batch()
-        feat, label = sam.get_graph_feat(key), sam.get_graph_label(key)
-        inp, out = sam.get_graph_input_nodes(key), sam.get_graph_output_nodes(key)
-        rec = {"feat": feat.cpu().numpy(), "label": label.cpu().numpy(), "input_nodes": inp.cpu().numpy(),
-               "output_nodes": out.cpu().numpy()}
-        devices = {str(t.device) for t in (feat, label, inp, out)}
-        for i, (row, col, ns, nd) in enumerate(sam.get_graph_coo(key, num_layers)):
-            data = sam.get_graph_data(key, i)
-            rec[f"row{i}"], rec[f"col{i}"] = row.cpu().numpy(), col.cpu().numpy()
-            rec[f"data{i}"] = data.cpu().numpy()
-            rec[f"num_src{i}"], rec[f"num_dst{i}"] = ns, nd
-            assert sam.get_graph_num_edge(key, i) == row.numel()
-            devices |= {str(row.device), str(col.device)}
-        rec["miss_bytes"] = sam.get_log_step_value_by_key(key, sam.kLogL1MissBytes)
-        rec["num_sample"] = sam.get_log_step_value_by_key(key, sam.kLogL1NumSample)
+        rec, devices = record_batch(sam, key, num_layers)
         for k, v in rec.items():
             batches[f"{key}:{k}"] = v
         info["devices"].append(sorted(devices))
@@ -50,7 +39,7 @@ def run_started(sam, num_layers, out_prefix):
                               "graph_copy_s": sam.get_log_step_value_by_key(key, sam.kLogL2GraphCopyTime),
                               "copy_s": sam.get_log_step_value_by_key(key, sam.kLogL1CopyTime),
                               "feature_bytes": sam.get_log_step_value_by_key(key, sam.kLogL1FeatureBytes),
-                              "num_input": int(inp.numel()), "num_seeds": int(out.numel())})
+                              "num_input": int(rec["input_nodes"].size), "num_seeds": int(rec["output_nodes"].size)})
     torch.cuda.synchronize()
     np.savez(f"{out_prefix}.w0.npz", **batches)
     with open(f"{out_prefix}.info.json", "w") as f:
@@ -63,27 +52,14 @@ def main():
     assert mode in ("step", "start"), mode
     extra = dict(a.split("=", 1) for a in sys.argv[4:])
     import samgraph.torch as sam
-    from engine_driver import run_worker
-    fanout = [int(x) for x in extra.pop("fanout", "5 4").split()]
     # the keys and defaults of tests/engine_driver.py: an arch1 run there with the same extra keys is the comparison
-    cfg = {"dataset_path": dataset, "_arch": sam.builtin_archs["arch3"]["arch"],
-           "_sample_type": sam.sample_types[extra.pop("sample_type", "khop3")],
-           "batch_size": int(extra.pop("batch_size", 64)), "num_epoch": int(extra.pop("num_epoch", 2)),
-           "_cache_policy": sam.cache_policies[extra.pop("cache_policy", "degree")],
-           "cache_percentage": float(extra.pop("cache_percentage", 0.0)), "max_sampling_jobs": 10,
-           "max_copying_jobs": 2, "omp_thread_num": int(extra.pop("omp_thread_num", 4)), "num_layer": len(fanout),
-           "num_hidden": 256, "lr": 0.003, "dropout": 0.5, "num_fanout": len(fanout), "fanout": fanout,
-           "seed": int(extra.pop("seed", 1234)), "sampler_ctx": "cuda:0", "trainer_ctx": "cuda:1"}
-    if cfg["_sample_type"] == sam.kRandomWalk:  # operation.cc:164-175: no fanout keys, num_neighbor per layer
-        cfg.pop("num_fanout"), cfg.pop("fanout")
-        cfg.update(random_walk_length=3, random_walk_restart_prob=0.5, num_random_walk=4, num_neighbor=5)
-    cfg.update(extra)
+    cfg = base_config(sam, dataset, "arch3", {"sampler_ctx": "cuda:0", "trainer_ctx": "cuda:1", **extra})
     sam.config(cfg)
     sam.init()
     if mode == "step":
-        run_worker(sam, 0, len(fanout), out_prefix, False)
+        run_worker(sam, 0, cfg["num_layer"], out_prefix, False)
     else:
-        run_started(sam, len(fanout), out_prefix)
+        run_started(sam, cfg["num_layer"], out_prefix)
 
 
 if __name__ == "__main__":

@@ -23,6 +23,9 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from engine_driver import base_config, record_batch  # noqa: E402
 
 
 def run_sampler(sam, w, barrier, out_prefix, exit_now):
@@ -55,19 +58,7 @@ def run_trainer(sam, w, S, T, barrier, num_layers, out_prefix, mode):
             if mode == "step":
                 sam.sample_once()
             key = sam.get_next_batch()
-            feat, label = sam.get_graph_feat(key), sam.get_graph_label(key)
-            inp, out = sam.get_graph_input_nodes(key), sam.get_graph_output_nodes(key)
-            rec = {"feat": feat.cpu().numpy(), "label": label.cpu().numpy(), "input_nodes": inp.cpu().numpy(),
-                   "output_nodes": out.cpu().numpy()}
-            devices = {str(t.device) for t in (feat, label, inp, out)}
-            for i, (row, col, ns, nd) in enumerate(sam.get_graph_coo(key, num_layers)):
-                rec[f"row{i}"], rec[f"col{i}"] = row.cpu().numpy(), col.cpu().numpy()
-                rec[f"data{i}"] = sam.get_graph_data(key, i).cpu().numpy()
-                rec[f"num_src{i}"], rec[f"num_dst{i}"] = ns, nd
-                assert sam.get_graph_num_edge(key, i) == row.numel()
-                devices |= {str(row.device), str(col.device)}
-            rec["miss_bytes"] = sam.get_log_step_value_by_key(key, sam.kLogL1MissBytes)
-            rec["num_sample"] = sam.get_log_step_value_by_key(key, sam.kLogL1NumSample)
+            rec, devices = record_batch(sam, key, num_layers)
             for k, v in rec.items():
                 batches[f"{key}:{k}"] = v
             info["keys"].append(int(key))
@@ -89,22 +80,11 @@ def main():
     assert mode in ("step", "start"), mode
     extra = dict(a.split("=", 1) for a in sys.argv[6:])
     import samgraph.torch as sam
-    fanout = [int(x) for x in extra.pop("fanout", "5 4").split()]
     exit_sampler = int(extra.pop("exit_sampler", -1))
     barrier_timeout = float(extra.pop("barrier_timeout", 300))
     # the keys and defaults of tests/engine_driver.py
-    cfg = {"dataset_path": dataset, "_arch": sam.builtin_archs["arch5"]["arch"],
-           "_sample_type": sam.sample_types[extra.pop("sample_type", "khop3")],
-           "batch_size": int(extra.pop("batch_size", 64)), "num_epoch": int(extra.pop("num_epoch", 2)),
-           "_cache_policy": sam.cache_policies[extra.pop("cache_policy", "degree")],
-           "cache_percentage": float(extra.pop("cache_percentage", 0.0)), "max_sampling_jobs": 10,
-           "max_copying_jobs": 2, "omp_thread_num": int(extra.pop("omp_thread_num", 4)), "num_layer": len(fanout),
-           "num_hidden": 256, "lr": 0.003, "dropout": 0.5, "num_fanout": len(fanout), "fanout": fanout,
-           "seed": int(extra.pop("seed", 1234)), "num_sample_worker": S, "num_train_worker": T, "have_switcher": 0}
-    if cfg["_sample_type"] == sam.kRandomWalk:  # operation.cc:164-175: no fanout keys, num_neighbor per layer
-        cfg.pop("num_fanout"), cfg.pop("fanout")
-        cfg.update(random_walk_length=3, random_walk_restart_prob=0.5, num_random_walk=4, num_neighbor=5)
-    cfg.update(extra)
+    cfg = base_config(sam, dataset, "arch5", {"num_sample_worker": S, "num_train_worker": T, "have_switcher": 0, **extra})
+    num_layers = cfg["num_layer"]
     sam.config(cfg)
     sam.data_init()  # host only: the GPU is first touched in the children
     barrier = mp.get_context("fork").Barrier(S + T, timeout=barrier_timeout)
@@ -117,7 +97,7 @@ def main():
                 if role == "s":
                     run_sampler(sam, w, barrier, out_prefix, w == exit_sampler)
                 else:
-                    run_trainer(sam, w, S, T, barrier, len(fanout), out_prefix, mode)
+                    run_trainer(sam, w, S, T, barrier, num_layers, out_prefix, mode)
             except SystemExit as e:
                 code = e.code or 0
             except BaseException as e:  # noqa: BLE001

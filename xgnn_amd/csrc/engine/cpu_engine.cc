@@ -242,13 +242,13 @@ void Engine::CpuInit() { // CPUEngine::Init, cpu_engine.cc:50-110
     auto b = std::make_unique<Batch>();
     b->slot = (int)s;
     b->host = !gpu;
-    b->row.resize(L); b->col.resize(L); b->data.resize(L, nullptr);
+    b->trainer.row.resize(L); b->trainer.col.resize(L); b->trainer.data.resize(L, nullptr);
     for (uint32_t i = 0; i < L; ++i) {
-      b->row[i] = (uint32_t *)alloc(max_edges_[i] * 4);
-      b->col[i] = (uint32_t *)alloc(max_edges_[i] * 4);
+      b->trainer.row[i] = (uint32_t *)alloc(max_edges_[i] * 4);
+      b->trainer.col[i] = (uint32_t *)alloc(max_edges_[i] * 4);
     }
-    b->input_nodes = (uint32_t *)alloc(max_unique_ * 4);
-    b->output_nodes = (uint32_t *)alloc(max_seeds_ * 4);
+    b->trainer.input_nodes = (uint32_t *)alloc(max_unique_ * 4);
+    b->trainer.output_nodes = (uint32_t *)alloc(max_seeds_ * 4);
     b->feat = alloc(max_unique_ * row_bytes);
     b->label = (int64_t *)alloc(max_seeds_ * 8);
     b->counts = (uint64_t *)std::calloc(3 * L + 8, 8);
@@ -302,7 +302,7 @@ bool Engine::CpuEnqueueOne(bool background) {
   const size_t num_seeds = std::min(cfg.batch_size, C.train.size() - offset);
   b->num_seeds = num_seeds;
   b->key = BatchKey(C.cur_epoch, C.cur_step);
-  uint32_t *seeds = gpu ? S->output_nodes.data() : b->output_nodes;
+  uint32_t *seeds = gpu ? S->output_nodes.data() : b->trainer.output_nodes;
   std::memcpy(seeds, C.train.data() + offset, num_seeds * 4);
 
   // ---- DoCPUSample (cpu_loops.cc:55-192)
@@ -320,7 +320,7 @@ bool Engine::CpuEnqueueOne(bool background) {
                                     cfg.fanout[i], C.tmp_src.data(), C.tmp_dst.data());
     C.table->Populate(C.tmp_dst.data(), n_out);
     const size_t num_unique = C.table->NumItems();
-    uint32_t *row = gpu ? S->row[i].data() : b->row[i], *col = gpu ? S->col[i].data() : b->col[i];
+    uint32_t *row = gpu ? S->row[i].data() : b->trainer.row[i], *col = gpu ? S->col[i].data() : b->trainer.col[i];
     C.table->MapEdges(C.tmp_src.data(), C.tmp_dst.data(), n_out, col, row); // row = new_dst, col = new_src (:151-160)
     b->counts[3 * i + 0] = n_out;
     b->counts[3 * i + 1] = num_unique;
@@ -332,7 +332,7 @@ bool Engine::CpuEnqueueOne(bool background) {
   b->counts[3 * L] = b->num_input;
   b->counts[3 * L + 1] = 0;
   b->counts[3 * L + 2] = 0;
-  uint32_t *input_nodes = gpu ? S->input_nodes.data() : b->input_nodes;
+  uint32_t *input_nodes = gpu ? S->input_nodes.data() : b->trainer.input_nodes;
   std::memcpy(input_nodes, C.cur.data(), b->num_input * 4);
   const double sample_s = Seconds(t_sample);
 
@@ -346,11 +346,11 @@ bool Engine::CpuEnqueueOne(bool background) {
   if (gpu) {
     SAM_HIP(hipSetDevice(device_));
     for (uint32_t i = 0; i < L; ++i) {
-      SAM_HIP(hipMemcpyAsync(b->row[i], S->row[i].data(), b->counts[3 * i] * 4, hipMemcpyHostToDevice, stream_));
-      SAM_HIP(hipMemcpyAsync(b->col[i], S->col[i].data(), b->counts[3 * i] * 4, hipMemcpyHostToDevice, stream_));
+      SAM_HIP(hipMemcpyAsync(b->trainer.row[i], S->row[i].data(), b->counts[3 * i] * 4, hipMemcpyHostToDevice, stream_));
+      SAM_HIP(hipMemcpyAsync(b->trainer.col[i], S->col[i].data(), b->counts[3 * i] * 4, hipMemcpyHostToDevice, stream_));
     }
-    SAM_HIP(hipMemcpyAsync(b->input_nodes, input_nodes, b->num_input * 4, hipMemcpyHostToDevice, stream_));
-    SAM_HIP(hipMemcpyAsync(b->output_nodes, seeds, num_seeds * 4, hipMemcpyHostToDevice, stream_));
+    SAM_HIP(hipMemcpyAsync(b->trainer.input_nodes, input_nodes, b->num_input * 4, hipMemcpyHostToDevice, stream_));
+    SAM_HIP(hipMemcpyAsync(b->trainer.output_nodes, seeds, num_seeds * 4, hipMemcpyHostToDevice, stream_));
     SAM_HIP(hipMemcpyAsync(b->feat, feat, b->num_input * row_bytes, hipMemcpyHostToDevice, stream_));
     SAM_HIP(hipMemcpyAsync(b->label, label, num_seeds * 8, hipMemcpyHostToDevice, stream_));
     SAM_HIP(hipStreamSynchronize(stream_));

@@ -51,19 +51,12 @@ struct Engine::Shared {
   size_t indptr_words[kMaxWorker], indices_words[kMaxWorker], feat_rows[kMaxWorker];
 };
 
-// arch5's batch queue: the first page of its mapping, zeroed by the anonymous mapping (see QueueInit)
-struct Engine::QueueCtl {
-  alignas(64) uint64_t enqueue_pos; // next producer ticket
-  alignas(64) uint64_t dequeue_pos; // next consumer ticket
-  alignas(64) uint64_t ranking_ready; // pre_sample: sampler 0 has written ds.ranking_nodes
-};
-
 Engine &Engine::Get() {
   static Engine e;
   return e;
 }
 
-static int parse_device(const std::string &ctx) {
+int parse_device(const std::string &ctx) {
   // "cuda:3" / "cpu:0" (Context(std::string), common.cc)
   auto p = ctx.find(':');
   int id = p == std::string::npos ? 0 : std::atoi(ctx.c_str() + p + 1);
@@ -78,6 +71,14 @@ static std::string ctx_id_as_written(const std::string &ctx) { // the device id 
 }
 
 // ------------------------------------------------------------------ configuration
+// arch3 / arch5 build no GGMS shards: the keys that ask for them are refused, naming the deployment
+static void refuse_arch6_keys(std::unordered_map<std::string, std::string> &kv, const std::string &arch) {
+  const bool dist_graph = kv.count("use_dist_graph") && std::stod(kv["use_dist_graph"]) > 0.0;
+  for (const char *k : {"part_cache", "gpu_extract"})
+    if (kv.count(k) && kv[k] == "True") fatal(__FILE__, __LINE__, arch + ": " + k + " is an arch6 key (GGMS shards across workers)");
+  if (dist_graph) fatal(__FILE__, __LINE__, arch + ": use_dist_graph is an arch6 key (GGMS shards across workers)");
+}
+
 void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in) {
   auto kv = kv_in;
   SAM_CHECK(!cfg.configured, "samgraph_config called twice");
@@ -124,11 +125,7 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
       if (cfg.cache_percentage > 0 && log_access)
         fatal(__FILE__, __LINE__, "arch3: a GPU cache (cache_percentage > 0) cannot be combined with node access logging "
                                   "(SAMGRAPH_LOG_NODE_ACCESS*)");
-      const bool dist_graph = kv.count("use_dist_graph") && std::stod(kv["use_dist_graph"]) > 0.0;
-      for (const char *k : {"part_cache", "gpu_extract"})
-        if (kv.count(k) && kv[k] == "True")
-          fatal(__FILE__, __LINE__, std::string("arch3: ") + k + " is an arch6 key (GGMS shards across workers)");
-      if (dist_graph) fatal(__FILE__, __LINE__, "arch3: use_dist_graph is an arch6 key (GGMS shards across workers)");
+      refuse_arch6_keys(kv, "arch3");
       cfg.sampler_device = parse_device(sc);
       cfg.trainer_device = parse_device(tc);
       cfg.num_worker = 1;
@@ -147,11 +144,7 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
       if (kv.count("have_switcher") && kv["have_switcher"] != "0" && kv["have_switcher"] != "False")
         fatal(__FILE__, __LINE__, "arch5: have_switcher = " + kv["have_switcher"] + ": the switcher is not built "
                                   "(samgraph_switch_init); set have_switcher = 0");
-      const bool dist_graph = kv.count("use_dist_graph") && std::stod(kv["use_dist_graph"]) > 0.0;
-      for (const char *k : {"part_cache", "gpu_extract"})
-        if (kv.count(k) && kv[k] == "True")
-          fatal(__FILE__, __LINE__, std::string("arch5: ") + k + " is an arch6 key (GGMS shards across workers)");
-      if (dist_graph) fatal(__FILE__, __LINE__, "arch5: use_dist_graph is an arch6 key (GGMS shards across workers)");
+      refuse_arch6_keys(kv, "arch5");
       if (kv.count("unified_memory") && (kv["unified_memory"] == "True" || kv["unified_memory"] == "1"))
         fatal(__FILE__, __LINE__, "arch5: unified_memory is not built (arch9, unified-memory sampling)");
       // the queue: 2 slots per trainer (one being unpacked, one filled meanwhile), at least 4
@@ -654,7 +647,7 @@ bool Engine::ShufflerNext(Batch *b, hipStream_t copy_stream) {
   b->key = BatchKey(cur_epoch_, global_step_offset_ + cur_step_);
   static const bool sanity = getenv("SAMGRAPH_SANITY_CHECK") != nullptr; // run_config.cc:126-128
   if (sanity && (cfg.arch == kArch1 || cfg.arch == kArch3)) SanityCheckBatch(shuf_host_.data() + global_data_offset_ + offset, size);
-  SAM_HIP(hipMemcpyAsync(b->s_output_nodes, shuf_dev_ + offset, size * 4, hipMemcpyDeviceToDevice, copy_stream)); // Copy1D
+  SAM_HIP(hipMemcpyAsync(b->sampler.output_nodes, shuf_dev_ + offset, size * 4, hipMemcpyDeviceToDevice, copy_stream)); // Copy1D
   return true;
 }
 
@@ -742,6 +735,16 @@ void Engine::UploadGraph() {
 }
 
 // ------------------------------------------------------------------ init
+// the batch bounds every buffer of a batch (and arch5's queue slot) is sized to
+void Engine::ComputeBounds() {
+  const uint32_t L = (uint32_t)cfg.fanout.size();
+  // first batch of arch6 is x1.25 (dist_shuffler_aligned.cc:137-140): size every buffer for it
+  max_seeds_ = (size_t)(cfg.batch_size * 1.25) + 1;
+  max_input_.resize(L);
+  max_edges_.resize(L);
+  SAM_GGMS(ggms_sample_batch_capacity(max_seeds_, cfg.fanout.data(), L, max_input_.data(), max_edges_.data(), &max_unique_));
+}
+
 void Engine::SampleInit(int worker_id, const std::string &ctx) {
   SAM_CHECK(data_ready_, "samgraph_data_init first");
   if (cfg.arch == kArch5) {
@@ -830,7 +833,7 @@ void Engine::SampleInit(int worker_id, const std::string &ctx) {
     auto t0 = std::chrono::steady_clock::now();
     if (worker_id_ == 0) Presample();
     if (cfg.arch == kArch5) { // sampler 0 publishes the ranking (shared pages); the other samplers wait for it
-      if (worker_id_ == 0) __atomic_store_n(&queue_->ranking_ready, (uint64_t)1, __ATOMIC_RELEASE);
+      if (worker_id_ == 0) PublishRanking();
       else WaitRankingReady();
     } else {
       Barrier("presample ranking");
@@ -840,16 +843,7 @@ void Engine::SampleInit(int worker_id, const std::string &ctx) {
   if (cfg.arch == kArch5) { // the sampler's own batch buffers: it samples into them and packs them into a queue slot
     sbatch_ = std::make_unique<Batch>();
     Batch *b = sbatch_.get();
-    b->s_row.resize(L); b->s_col.resize(L); b->s_data.resize(L, nullptr);
-    for (uint32_t i = 0; i < L; ++i) {
-      SAM_HIP(hipMalloc((void **)&b->s_row[i], std::max<size_t>(max_edges_[i], 4) * 4));
-      SAM_HIP(hipMalloc((void **)&b->s_col[i], std::max<size_t>(max_edges_[i], 4) * 4));
-      if (cfg.sample_type == GGMS_RANDOM_WALK) SAM_HIP(hipMalloc((void **)&b->s_data[i], std::max<size_t>(max_edges_[i], 4) * 4));
-    }
-    SAM_HIP(hipMalloc((void **)&b->s_input_nodes, max_unique_ * 4));
-    SAM_HIP(hipMalloc((void **)&b->s_output_nodes, max_seeds_ * 4));
-    SAM_HIP(hipMalloc((void **)&b->s_counts_dev, (3 * L + 8) * 8));
-    SAM_HIP(hipMemset(b->s_counts_dev, 0, (3 * L + 8) * 8));
+    b->sampler.Alloc(max_edges_, max_unique_, max_seeds_, cfg.sample_type == GGMS_RANDOM_WALK);
     SAM_HIP(hipEventCreateWithFlags(&b->ev_sampled, hipEventDisableTiming));
     SAM_HIP(hipEventCreateWithFlags(&b->ev_done, hipEventDisableTiming));
     QueueMap();
@@ -931,7 +925,7 @@ void Engine::BuildCache() {
   const char *feat = (const char *)ds.feat.ptr;
   // the cache and the label table live on the trainer GPU: uploaded through a stream of that device (arch3: the
   // extract stream; the other deployments have one device, and the sampling stream as before)
-  hipStream_t bs = (cfg.arch == kArch3 || cfg.arch == kArch5) ? stream_extract_ : stream_;
+  hipStream_t bs = BatchSampledElsewhere() ? stream_extract_ : stream_;
   // labels are 8 B x N: always resident on the device (the reference keeps them on the host and
   // gathers through zero-copy in gpu_extract mode, dist_loops.cc:938-974)
   label_src_ = dev_upload(ds.label.ptr, ds.label.bytes, bs);
@@ -1037,10 +1031,38 @@ void Engine::BuildCache() {
   // miss tier: pinned host memory read by the gather kernel itself (GPUExtractMissData, :573-625); the host-staged
   // path (`gpu_extract` off) reads the table with the host cores instead and needs no device mapping of it
   // (arch3 and arch5 gather their misses the gpu_extract way: zero-copy by the trainer GPU, no CPU-staged path)
-  const bool host_tier = cfg.gpu_extract || ((cfg.arch == kArch3 || cfg.arch == kArch5) &&
-                                             (num_cached_nodes_ < ds.num_node || ds.feat_mask != 0xffffffffu));
+  const bool host_tier =
+      cfg.gpu_extract || (BatchSampledElsewhere() && (num_cached_nodes_ < ds.num_node || ds.feat_mask != 0xffffffffu));
   feat_src_ = host_tier ? map_host(ds.feat.ptr, ds.feat.bytes) : nullptr;
   SAM_HIP(hipStreamSynchronize(bs));
+}
+
+void BatchArrays::Alloc(const std::vector<size_t> &max_edges, size_t max_unique, size_t max_seeds, bool with_data) {
+  const size_t L = max_edges.size();
+  row.resize(L); col.resize(L); data.assign(L, nullptr);
+  for (size_t i = 0; i < L; ++i) {
+    SAM_HIP(hipMalloc((void **)&row[i], std::max<size_t>(max_edges[i], 4) * 4));
+    SAM_HIP(hipMalloc((void **)&col[i], std::max<size_t>(max_edges[i], 4) * 4));
+    if (with_data) SAM_HIP(hipMalloc((void **)&data[i], std::max<size_t>(max_edges[i], 4) * 4));
+  }
+  SAM_HIP(hipMalloc((void **)&input_nodes, max_unique * 4));
+  SAM_HIP(hipMalloc((void **)&output_nodes, max_seeds * 4));
+  SAM_HIP(hipMalloc((void **)&counts_dev, (3 * L + 8) * 8));
+  SAM_HIP(hipMemset(counts_dev, 0, (3 * L + 8) * 8));
+}
+
+ggms_queue_batch_t BatchArrays::View() const {
+  SAM_CHECK(row.size() <= GGMS_QUEUE_MAX_LAYERS, "at most GGMS_QUEUE_MAX_LAYERS layers");
+  ggms_queue_batch_t v{};
+  for (size_t i = 0; i < row.size(); ++i) {
+    v.row[i] = row[i];
+    v.col[i] = col[i];
+    v.data[i] = data[i];
+  }
+  v.input_nodes = input_nodes;
+  v.output_nodes = output_nodes;
+  v.counts = counts_dev;
+  return v;
 }
 
 void Engine::TrainInit(int worker_id, const std::string &ctx) {
@@ -1069,18 +1091,9 @@ void Engine::TrainInit(int worker_id, const std::string &ctx) {
   for (size_t s = 0; s < nslots; ++s) {
     auto b = std::make_unique<Batch>();
     b->slot = (int)s;
-    b->row.resize(L); b->col.resize(L); b->data.resize(L, nullptr);
-    for (uint32_t i = 0; i < L; ++i) {
-      SAM_HIP(hipMalloc((void **)&b->row[i], std::max<size_t>(max_edges_[i], 4) * 4));
-      SAM_HIP(hipMalloc((void **)&b->col[i], std::max<size_t>(max_edges_[i], 4) * 4));
-      if (cfg.sample_type == GGMS_RANDOM_WALK) SAM_HIP(hipMalloc((void **)&b->data[i], std::max<size_t>(max_edges_[i], 4) * 4));
-    }
-    SAM_HIP(hipMalloc((void **)&b->input_nodes, max_unique_ * 4));
-    SAM_HIP(hipMalloc((void **)&b->output_nodes, max_seeds_ * 4));
+    b->trainer.Alloc(max_edges_, max_unique_, max_seeds_, cfg.sample_type == GGMS_RANDOM_WALK);
     SAM_HIP(hipMalloc(&b->feat, max_unique_ * row_bytes));
     SAM_HIP(hipMalloc((void **)&b->label, max_seeds_ * 8));
-    SAM_HIP(hipMalloc((void **)&b->counts_dev, (3 * L + 8) * 8));
-    SAM_HIP(hipMemset(b->counts_dev, 0, (3 * L + 8) * 8));
     if (StagedHostTier()) { // index arrays of GetMissCacheIndex + pinned / device staging of the miss rows
       if (cache_table_) { // (no cache: no split, and the rows land in the batch's feature buffer directly)
         for (uint32_t **p : {&b->miss_src, &b->miss_dst, &b->hit_src, &b->hit_dst}) SAM_HIP(hipMalloc((void **)p, max_unique_ * 4));
@@ -1098,25 +1111,12 @@ void Engine::TrainInit(int worker_id, const std::string &ctx) {
     SAM_HIP(hipEventCreate(&b->ev_xstart));
     SAM_HIP(hipEventCreate(&b->ev_done));
     SAM_GGMS(ggms_launch_timer_create(&b->gather_timer));
-    if (cfg.arch == kArch5) SAM_GGMS(ggms_launch_timer_create(&b->handoff_timer)); // rides on the unpack
+    if (BatchSampledElsewhere()) SAM_GGMS(ggms_launch_timer_create(&b->handoff_timer));
     if (cfg.arch == kArch3) { // the sampler's side of the slot, on the sampler GPU (GetGraphFileCtx, cuda_engine.cc:437-481)
-      SAM_GGMS(ggms_launch_timer_create(&b->handoff_timer));
       SAM_HIP(hipSetDevice(device_));
-      b->s_row.resize(L); b->s_col.resize(L); b->s_data.resize(L, nullptr);
-      for (uint32_t i = 0; i < L; ++i) {
-        SAM_HIP(hipMalloc((void **)&b->s_row[i], std::max<size_t>(max_edges_[i], 4) * 4));
-        SAM_HIP(hipMalloc((void **)&b->s_col[i], std::max<size_t>(max_edges_[i], 4) * 4));
-        if (cfg.sample_type == GGMS_RANDOM_WALK) SAM_HIP(hipMalloc((void **)&b->s_data[i], std::max<size_t>(max_edges_[i], 4) * 4));
-      }
-      SAM_HIP(hipMalloc((void **)&b->s_input_nodes, max_unique_ * 4));
-      SAM_HIP(hipMalloc((void **)&b->s_output_nodes, max_seeds_ * 4));
-      SAM_HIP(hipMalloc((void **)&b->s_counts_dev, (3 * L + 8) * 8));
-      SAM_HIP(hipMemset(b->s_counts_dev, 0, (3 * L + 8) * 8));
+      b->sampler.Alloc(max_edges_, max_unique_, max_seeds_, cfg.sample_type == GGMS_RANDOM_WALK);
     } else {
-      b->s_row = b->row; b->s_col = b->col; b->s_data = b->data;
-      b->s_input_nodes = b->input_nodes;
-      b->s_output_nodes = b->output_nodes;
-      b->s_counts_dev = b->counts_dev;
+      b->sampler = b->trainer;
     }
     SAM_HIP(hipEventCreate(&b->ev_start)); // both recorded on the sampling stream
     SAM_HIP(hipEventCreate(&b->ev_sampled));
@@ -1225,14 +1225,21 @@ bool Engine::EnqueueOne(bool background) {
     b->in_use = false;
     return false;
   }
-  const uint32_t L = (uint32_t)cfg.fanout.size();
-  // The RNG pool -- and khop2's CSR -- is handed from batch to batch through rng_wait / rng_done, so the results
-  // are those of the one-batch-at-a-time loop.
   ++enq_count_;
   SAM_HIP(hipEventRecord(b->ev_start, ss));
+  SampleInto(b, P);
+  EnqueueGather(b, ss);
+  return true;
+}
+
+void Engine::SampleInto(Batch *b, Pipe &P) {
+  const uint32_t L = (uint32_t)cfg.fanout.size();
+  const BatchArrays &s = b->sampler;
   ggms_sample_extra_t extra = extra_;
-  extra.data = b->s_data.data();
+  extra.data = s.data.data();
   extra.seeds_distinct = BatchSeedsDistinct(cur_step_ * cfg.batch_size, b->num_seeds) ? 1u : 0u;
+  // The RNG pool -- and khop2's CSR -- is handed from batch to batch through rng_wait / rng_done, so the results
+  // are those of the one-batch-at-a-time loop.
   if (pipes_.size() > 1 && cfg.sample_type != GGMS_KHOP0) {
     extra.rng_wait = last_rng_done_;
     extra.rng_done = P.rng_done;
@@ -1241,30 +1248,27 @@ bool Engine::EnqueueOne(bool background) {
   // input nodes = the table's unique list (task->input_nodes, dist_loops.cc:357).  The table struct is plain data and
   // its n2o buffer the caller's: the batch builds the list directly in its slot (a later batch uses another slot)
   ggms_hashtable_t ht = P.ht;
-  ht.n2o = b->s_input_nodes;
+  ht.n2o = s.input_nodes;
   ht.n2o_size = max_unique_;
-  SAM_GGMS(ggms_sample_batch(cfg.sample_type, &graph_, b->s_output_nodes, b->num_seeds, cfg.fanout.data(), L, &ht,
-                             states_, num_states_, b->s_row.data(), b->s_col.data(), b->s_counts_dev, &extra, P.ws,
-                             ws_bytes_, ss));
+  SAM_GGMS(ggms_sample_batch(cfg.sample_type, &graph_, s.output_nodes, b->num_seeds, cfg.fanout.data(), L, &ht, states_,
+                             num_states_, s.row.data(), s.col.data(), s.counts_dev, &extra, P.ws, ws_bytes_, P.stream));
   P.ht.version = ht.version; // the batch bumped the table's version stamp
-  SAM_HIP(hipMemsetAsync(b->s_counts_dev + 3 * L + 2, 0, 8, ss));
-  SAM_HIP(hipEventRecord(b->ev_sampled, ss));
-  EnqueueGather(b, ss);
-  return true;
+  SAM_HIP(hipMemsetAsync(s.counts_dev + 3 * L + 2, 0, 8, P.stream)); // the trainer's miss count starts at 0
+  SAM_HIP(hipEventRecord(b->ev_sampled, P.stream));
 }
 
 // the labels and the feature rows of batch b, sampled on stream ss; then b goes to the pool
 void Engine::EnqueueGather(Batch *b, hipStream_t ss) {
   const uint32_t L = (uint32_t)cfg.fanout.size();
-  uint64_t *n_in = b->counts_dev + 3 * L, *n_miss = b->counts_dev + 3 * L + 2; // [3L + 1] = the batch's status word
+  uint64_t *n_in = b->trainer.counts_dev + 3 * L, *n_miss = n_in + 2; // [3L + 1] = the batch's status word
   // arch3: everything from here on runs on the trainer GPU, on the batch's extract stream -- hand-off, labels, rows,
   // counts -- and the sampling stream is left to the sampler.  arch5: the same on the trainer's GPU, starting with the
   // unpack of the batch's queue slot (there is no sampling stream)
-  const bool remote = cfg.arch == kArch3 || cfg.arch == kArch5; // the batch was sampled in another place
+  const bool remote = BatchSampledElsewhere();
   // DoGPULabelExtract (dist_loops.cc:938-974) needs the seeds only: it rides behind the batch on its sampling stream, not
   // between two gathers on the extract stream, which bounds the step.  (Not on a stream of its own: HIP streams share 4
   // hardware queues, and a fifth stream serialises streams that have nothing to do with each other.)
-  if (!remote) SAM_GGMS(ggms_extract(b->label, label_src_, b->output_nodes, b->num_seeds, 1, GGMS_I64, ss));
+  if (!remote) SAM_GGMS(ggms_extract(b->label, label_src_, b->trainer.output_nodes, b->num_seeds, 1, GGMS_I64, ss));
   const bool mock = ds.feat_mask != 0xffffffffu; // SAMGRAPH_EMPTY_FEAT: host rows are node & mask
   // The extract stream bounds the step, and every event record / wait / small copy on it is a packet the command
   // processor works through between two gathers -- 28 us of dead time per 0.7-ms step with six of them
@@ -1279,7 +1283,7 @@ void Engine::EnqueueGather(Batch *b, hipStream_t ss) {
   static const bool lean_off = [] { const char *e = getenv("SAMGRAPH_LEAN_EXTRACT"); return e && e[0] == '0'; }(); // A/B hook
   b->lean = !lean_off && !StagedHostTier() && !gather_counts && !node_access_dev_;
   if (!remote && b->lean) {
-    SAM_HIP(hipMemcpyAsync(b->counts, b->counts_dev, (3 * L + 8) * 8, hipMemcpyDeviceToHost, ss));
+    SAM_HIP(hipMemcpyAsync(b->counts, b->trainer.counts_dev, (3 * L + 8) * 8, hipMemcpyDeviceToHost, ss));
     SAM_HIP(hipEventRecord(b->ev_done, ss)); // labels and counts are out; the rows: gather_timer
   } else if (!remote) {
     SAM_HIP(hipEventRecord(b->ev_label, ss));
@@ -1292,7 +1296,7 @@ void Engine::EnqueueGather(Batch *b, hipStream_t ss) {
   else SAM_HIP(hipStreamWaitEvent(xs, b->ev_sampled, 0));
   if (remote) {
     if (cfg.arch == kArch3) Handoff(b, xs); // the batch's arrays, S -> T; the gather below reads the input nodes and their count on T
-    SAM_GGMS(ggms_extract(b->label, label_src_, b->output_nodes, b->num_seeds, 1, GGMS_I64, xs));
+    SAM_GGMS(ggms_extract(b->label, label_src_, b->trainer.output_nodes, b->num_seeds, 1, GGMS_I64, xs));
   }
   if (b->lean) SAM_GGMS(ggms_launch_timer_arm(b->gather_timer));
   else SAM_HIP(hipEventRecord(b->ev_xstart, xs)); // the extract's own start: behind the previous batch's extract on xs
@@ -1309,30 +1313,30 @@ void Engine::EnqueueGather(Batch *b, hipStream_t ss) {
     tiers.my_part = cfg.part_cache ? (uint32_t)worker_id_ : 0;
     tiers.host_feat = feat_src_;
     tiers.host_row_mask = mock ? ds.feat_mask : 0;
-    SAM_GGMS(ggms_extract_tiered(b->feat, b->input_nodes, max_unique_, n_in, &tiers, ds.feat_dim, ds.feat_dtype,
+    SAM_GGMS(ggms_extract_tiered(b->feat, b->trainer.input_nodes, max_unique_, n_in, &tiers, ds.feat_dim, ds.feat_dtype,
                                  gather_counts ? n_miss : nullptr, xs));
   } else if (cfg.UseGPUCache()) {
     // DoArch6GetCacheMissIndex + DoArch6GPUCacheFeatureCopy (dist_loops.cc:1015-1285) in one pass; everything cached in
     // node order (no table): no row can miss, the count stays the zero the sampling stream wrote
-    SAM_GGMS(ggms_extract_cached(b->feat, b->input_nodes, max_unique_, n_in, cache_table_,
+    SAM_GGMS(ggms_extract_cached(b->feat, b->trainer.input_nodes, max_unique_, n_in, cache_table_,
                                  (const void *const *)cache_parts_.data(), num_cache_part_, feat_src_, ds.feat_dim,
                                  ds.feat_dtype, (cache_table_ && can_miss) ? n_miss : nullptr, xs));
   } else if (mock) { // GPUMockExtract, cuda_loops.cc:692-700 / dist_loops.cc:608-616
-    SAM_GGMS(ggms_gather_scatter_masked(b->feat, feat_src_, b->input_nodes, nullptr, max_unique_, n_in, ds.feat_dim,
+    SAM_GGMS(ggms_gather_scatter_masked(b->feat, feat_src_, b->trainer.input_nodes, nullptr, max_unique_, n_in, ds.feat_dim,
                                         ds.feat_dtype, ds.feat_mask, xs));
   } else {
     // DoGPUFeatureExtract (cuda/cuda_loops.cc, dist_loops.cc:585-634)
-    SAM_GGMS(ggms_gather_scatter(b->feat, feat_src_, b->input_nodes, nullptr, max_unique_, n_in, ds.feat_dim,
+    SAM_GGMS(ggms_gather_scatter(b->feat, feat_src_, b->trainer.input_nodes, nullptr, max_unique_, n_in, ds.feat_dim,
                                  ds.feat_dtype, xs));
   }
   if (!b->lean) {
     if (node_access_dev_) // Profiler::LogNodeAccess (profiler.cc:570-575): visits per node, counted on the device
-      SAM_GGMS(ggms_count_nodes(node_access_dev_, b->input_nodes, max_unique_, n_in, xs));
+      SAM_GGMS(ggms_count_nodes(node_access_dev_, b->trainer.input_nodes, max_unique_, n_in, xs));
     if (!remote) SAM_HIP(hipStreamWaitEvent(xs, b->ev_label, 0)); // the batch is complete when its labels are, too
-    SAM_HIP(hipMemcpyAsync(b->counts, b->counts_dev, (3 * L + 8) * 8, hipMemcpyDeviceToHost, xs));
+    SAM_HIP(hipMemcpyAsync(b->counts, b->trainer.counts_dev, (3 * L + 8) * 8, hipMemcpyDeviceToHost, xs));
     SAM_HIP(hipEventRecord(b->ev_done, xs));
   } else if (remote) { // counts of T (the gather may have added to them) to the host behind the rows
-    SAM_HIP(hipMemcpyAsync(b->counts, b->counts_dev, (3 * L + 8) * 8, hipMemcpyDeviceToHost, xs));
+    SAM_HIP(hipMemcpyAsync(b->counts, b->trainer.counts_dev, (3 * L + 8) * 8, hipMemcpyDeviceToHost, xs));
     SAM_HIP(hipEventRecord(b->ev_done, xs));
   }
   {
@@ -1355,408 +1359,29 @@ void Engine::Handoff(Batch *b, hipStream_t xs) {
     SAM_CHECK(n < GGMS_HANDOFF_MAX_SEGS, "arch3: too many hand-off segments");
     segs[n++] = ggms_copy_seg_t{src, dst, count_dev, count_host, max_count, elem_bytes, 0};
   };
+  const BatchArrays &s = b->sampler, &t = b->trainer;
   for (uint32_t i = 0; i < L; ++i) {
-    add(b->s_row[i], b->row[i], b->s_counts_dev + 3 * i, 0, max_edges_[i], 4);
-    add(b->s_col[i], b->col[i], b->s_counts_dev + 3 * i, 0, max_edges_[i], 4);
-    if (b->s_data[i]) add(b->s_data[i], b->data[i], b->s_counts_dev + 3 * i, 0, max_edges_[i], 4);
+    add(s.row[i], t.row[i], s.counts_dev + 3 * i, 0, max_edges_[i], 4);
+    add(s.col[i], t.col[i], s.counts_dev + 3 * i, 0, max_edges_[i], 4);
+    if (s.data[i]) add(s.data[i], t.data[i], s.counts_dev + 3 * i, 0, max_edges_[i], 4);
   }
-  add(b->s_input_nodes, b->input_nodes, b->s_counts_dev + 3 * L, 0, max_unique_, 4);
-  add(b->s_output_nodes, b->output_nodes, nullptr, b->num_seeds, max_seeds_, 4);
-  add(b->s_counts_dev, b->counts_dev, nullptr, 3 * L + 8, 3 * L + 8, 8);
+  add(s.input_nodes, t.input_nodes, s.counts_dev + 3 * L, 0, max_unique_, 4);
+  add(s.output_nodes, t.output_nodes, nullptr, b->num_seeds, max_seeds_, 4);
+  add(s.counts_dev, t.counts_dev, nullptr, 3 * L + 8, 3 * L + 8, 8);
   SAM_GGMS(ggms_launch_timer_arm(b->handoff_timer)); // kLogL2GraphCopyTime: the hand-off's own time
   SAM_GGMS(ggms_batch_handoff(segs, n, xs));
 }
 
-// ---- arch5: the batch queue ----------------------------------------------------------------------------------------
-// MemoryQueue (dist/memory_queue.cc) + DistEngine's queue set-up (dist_engine.cc:395-397).  The reference serialises a
-// Task into a queue slot with host copies and a mutex-guarded ring; here the sampler's GPU writes the batch into the
-// slot itself (ggms_queue_pack: one launch, every length read on the device) and the trainer's GPU reads it out
-// (ggms_queue_unpack), and the ring is lock-free: tickets from two counters, one sequence word per slot.
-
-void Engine::ComputeBounds() {
-  const uint32_t L = (uint32_t)cfg.fanout.size();
-  // first batch of arch6 is x1.25 (dist_shuffler_aligned.cc:137-140): size every buffer for it
-  max_seeds_ = (size_t)(cfg.batch_size * 1.25) + 1;
-  max_input_.resize(L);
-  max_edges_.resize(L);
-  SAM_GGMS(ggms_sample_batch_capacity(max_seeds_, cfg.fanout.data(), L, max_input_.data(), max_edges_.data(), &max_unique_));
-}
-
-// the parent, before the fork: no GPU is touched (every process registers the slots itself, QueueMap)
-void Engine::QueueInit() {
-  static_assert(sizeof(QueueCtl) <= 4096, "the control block fits its page");
-  const auto t0 = std::chrono::steady_clock::now();
-  const uint32_t L = (uint32_t)cfg.fanout.size();
-  SAM_CHECK(L <= GGMS_QUEUE_MAX_LAYERS, "arch5: at most GGMS_QUEUE_MAX_LAYERS layers");
-  SAM_GGMS(ggms_queue_layout(&qlay_, L, max_edges_.data(), max_unique_, max_seeds_, cfg.sample_type == GGMS_RANDOM_WALK));
-  queue_depth_ = cfg.queue_depth;
-  const size_t bytes = 4096 + queue_depth_ * qlay_.slot_bytes;
-  void *m = mmap(nullptr, bytes, PROT_READ | PROT_WRITE, MAP_SHARED | MAP_ANONYMOUS, -1, 0);
-  SAM_CHECK(m != MAP_FAILED, "arch5: batch queue mmap of " + std::to_string(bytes) + " bytes failed");
-  queue_ = (QueueCtl *)m;
-  queue_slots_ = (char *)m + 4096;
-  for (size_t i = 0; i < queue_depth_; ++i) __atomic_store_n(&QueueHeader(i)->seq, (uint64_t)i, __ATOMIC_RELAXED);
-  __atomic_thread_fence(__ATOMIC_SEQ_CST);
-  prof.LogInit(/*kLogInitL2DistQueue*/ 7, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
-  log_info("arch5: batch queue of " + std::to_string(queue_depth_) + " slots x " + std::to_string(qlay_.slot_bytes) + " bytes");
-}
-
-// this process's device reads / writes the slots in place: pinned and mapped (cudaHostRegister, dist_engine.cc:217-241)
-void Engine::QueueMap() {
-  SAM_HIP(hipHostRegister(queue_slots_, queue_depth_ * qlay_.slot_bytes, hipHostRegisterMapped));
-  void *d = nullptr;
-  SAM_HIP(hipHostGetDevicePointer(&d, queue_slots_, 0));
-  queue_slots_dev_ = (char *)d;
-}
-
-ggms_queue_header_t *Engine::QueueHeader(uint64_t pos) const {
-  return (ggms_queue_header_t *)(queue_slots_ + (pos % queue_depth_) * qlay_.slot_bytes);
-}
-
-// Every wait on another process has a deadline (queue_timeout_s): a sampler or trainer that died, or that stopped
-// early, must not hold the others.  The process then ends with status 1 -- nothing in it is at fault, there is nothing
-// to dump.  false: the engine is shutting down (a background loop waiting for a message that will not come).
-bool Engine::QueueWait(const uint64_t *word, uint64_t want, const char *what, bool stoppable) {
-  const auto t0 = std::chrono::steady_clock::now();
-  for (uint64_t spin = 0;; ++spin) {
-    if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == want) return true;
-    if (spin < 4096) continue;
-    if (stoppable && bg_stop_.load()) return false;
-    if ((spin & 63) == 0) {
-      const double waited = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-      if (waited > cfg.queue_timeout_s) {
-        std::fprintf(stderr, "[samgraph-amd FATAL] %s:%d: arch5: %s %d (device %d) waited %d s for %s -- queue_timeout_s "
-                             "= %g s passed; a process on the other side died, stopped early or is stuck\n",
-                     __FILE__, __LINE__, role_ == kRoleSampler ? "sampler" : "trainer", worker_id_, device_, (int)waited,
-                     what, cfg.queue_timeout_s);
-        std::fflush(stderr);
-        _exit(1);
-      }
-    }
-    spin < 65536 ? (void)sched_yield() : (void)usleep(100);
-  }
-}
-
-// pre_sample: the other samplers and the trainers wait for sampler 0's ranking (dist_engine.cc:451-466)
-void Engine::WaitRankingReady() { QueueWait(&queue_->ranking_ready, 1, "sampler 0's presample ranking", false); }
-
-// train_init of an arch5 trainer: its GPU, its extract streams, its share of each epoch's messages, the slots
-void Engine::Arch5TrainerInit(int worker_id, const std::string &ctx) {
-  SAM_CHECK(data_ready_, "samgraph_data_init first");
-  SAM_CHECK(role_ == kRoleNone, "arch5: a process is one sampler or one trainer (one sample_init or one train_init)");
-  SAM_CHECK(worker_id >= 0 && (size_t)worker_id < cfg.num_train_worker, "arch5: train_init(worker_id) with 0 <= "
-            "worker_id < num_train_worker = " + std::to_string(cfg.num_train_worker));
-  role_ = kRoleTrainer;
-  worker_id_ = worker_id;
-  device_ = trainer_device_ = parse_device(ctx);
-  SAM_HIP(hipSetDevice(device_));
-  SAM_HIP(hipStreamCreateWithFlags(&stream_extract_, hipStreamNonBlocking));
-  if (cfg.extract_streams > 1) SAM_HIP(hipStreamCreateWithFlags(&stream_extract2_, hipStreamNonBlocking));
-  // the scripts' split of an epoch's steps over the trainers (multi_gpu/train_graphsage.py: steps w, w + T, ...)
-  const size_t T = cfg.num_train_worker;
-  num_local_step_ = num_global_step_ / T + ((size_t)worker_id < num_global_step_ % T ? 1 : 0);
-  prof.Resize(cfg.num_epoch, num_global_step_);
-  if (cfg.UsePresample()) WaitRankingReady(); // the cache is built from sampler 0's ranking
-  QueueMap();
-  sample_ready_ = true; // (the bounds are the parent's, ComputeBounds in DataInit)
-}
-
-// RunSampleSubLoopOnce (dist_loops_arch5.cc): shuffle, sample, send.  The reference's DoGetCacheMissIndex is not run:
-// the trainer's gather resolves hits itself, and a hit / miss split would only add bytes to the message.
-void Engine::SendOne() {
-  using clk = std::chrono::steady_clock;
-  auto since = [](clk::time_point t) { return std::chrono::duration<double>(clk::now() - t).count(); };
-  SAM_HIP(hipSetDevice(device_));
-  const uint32_t L = (uint32_t)cfg.fanout.size();
-  Batch *b = sbatch_.get();
-  hipStream_t ss = stream_;
-  const auto t0 = clk::now();
-  if (!ShufflerNext(b, ss))
-    fatal(__FILE__, __LINE__, "arch5: sample_once() on sampler " + std::to_string(worker_id_) + " after its last batch (" +
-                                  std::to_string(cfg.num_epoch) + " epochs x " + std::to_string(num_local_step_) +
-                                  " steps, num_local_step())");
-  const double t_shuffle = since(t0);
-  Pipe &P = pipes_[0];
-  ggms_sample_extra_t extra = extra_;
-  extra.data = b->s_data.data();
-  extra.seeds_distinct = BatchSeedsDistinct(cur_step_ * cfg.batch_size, b->num_seeds) ? 1u : 0u;
-  ggms_hashtable_t ht = P.ht;
-  ht.n2o = b->s_input_nodes;
-  ht.n2o_size = max_unique_;
-  SAM_GGMS(ggms_sample_batch(cfg.sample_type, &graph_, b->s_output_nodes, b->num_seeds, cfg.fanout.data(), L, &ht,
-                             states_, num_states_, b->s_row.data(), b->s_col.data(), b->s_counts_dev, &extra, P.ws,
-                             ws_bytes_, ss));
-  P.ht.version = ht.version;
-  SAM_HIP(hipMemsetAsync(b->s_counts_dev + 3 * L + 2, 0, 8, ss)); // the trainer's miss count starts at 0
-  SAM_HIP(hipEventRecord(b->ev_sampled, ss));
-  SAM_HIP(hipEventSynchronize(b->ev_sampled)); // DoGPUSample ends with a stream sync too
-  const double t_sample = since(t0);
-  // send: a free slot (the ticket's), the pack, its completion, then the slot is published
-  const auto t1 = clk::now();
-  const uint64_t pos = __atomic_fetch_add(&queue_->enqueue_pos, 1, __ATOMIC_ACQ_REL);
-  ggms_queue_header_t *h = QueueHeader(pos);
-  const std::string what = "a free queue slot from the trainers (ticket " + std::to_string(pos) + ")";
-  QueueWait(&h->seq, pos, what.c_str(), false);
-  ggms_queue_batch_t src{};
-  for (uint32_t i = 0; i < L; ++i) {
-    src.row[i] = b->s_row[i];
-    src.col[i] = b->s_col[i];
-    src.data[i] = b->s_data[i];
-  }
-  src.input_nodes = b->s_input_nodes;
-  src.output_nodes = b->s_output_nodes;
-  src.counts = b->s_counts_dev;
-  SAM_GGMS(ggms_queue_pack(queue_slots_dev_ + (pos % queue_depth_) * qlay_.slot_bytes, &qlay_, &src, b->key, b->num_seeds, ss));
-  SAM_HIP(hipEventRecord(b->ev_done, ss));
-  SAM_HIP(hipEventSynchronize(b->ev_done));
-  const uint64_t status = h->counts[3 * L + 1], num_input = h->counts[3 * L];
-  uint64_t edges = 0;
-  for (uint32_t i = 0; i < L; ++i) edges += h->counts[3 * i];
-  if (status != 0) { // as Finish does for the other deployments: a kernel of the batch hit a bound
-    fprintf(stderr, "[samgraph] FATAL: device status %#llx after batch %llu on sampler %d: results are invalid\n",
-            (unsigned long long)status, (unsigned long long)b->key, worker_id_);
-    abort();
-  }
-  __atomic_store_n(&h->seq, pos + 1, __ATOMIC_RELEASE); // published
-  const double t_send = since(t1);
-  // the items the multi_gpu scripts read (dist_loops_arch5.cc:95-107); no cache-miss split here, so its item is 0
-  prof.LogEpochAdd(b->key, 0 /*kLogEpochSampleTime*/, t_sample);
-  prof.LogEpochAdd(b->key, 1 /*KLogEpochSampleGetCacheMissIndexTime*/, 0.0);
-  prof.LogEpochAdd(b->key, 2 /*kLogEpochSampleSendTime*/, t_send);
-  prof.LogEpochAdd(b->key, 3 /*kLogEpochSampleTotalTime*/, t_sample + t_send);
-  prof.LogEpochAdd(b->key, 15 /*kLogEpochNumSample*/, (double)edges);
-  prof.LogStep(b->key, 0 /*kLogL1NumSample*/, (double)edges);
-  prof.LogStep(b->key, 1 /*kLogL1NumNode*/, (double)num_input);
-  prof.LogStep(b->key, 3 /*kLogL1SampleTime*/, t_sample);
-  prof.LogStep(b->key, 4 /*kLogL1SendTime*/, t_send);
-  prof.LogStep(b->key, 17 /*kLogL2ShuffleTime*/, t_shuffle);
-}
-
-// RunCacheDataCopySubLoopOnce's q->Recv (dist_loops_arch5.cc): take the next ticket and wait for its message
-bool Engine::Receive(Batch *b) {
-  const auto t0 = std::chrono::steady_clock::now();
-  const uint64_t pos = __atomic_fetch_add(&queue_->dequeue_pos, 1, __ATOMIC_ACQ_REL);
-  ggms_queue_header_t *h = QueueHeader(pos);
-  const std::string what = "a batch from the samplers (ticket " + std::to_string(pos) + ")";
-  if (!QueueWait(&h->seq, pos + 1, what.c_str(), true)) return false;
-  b->queue_pos = pos;
-  b->key = h->key;
-  b->num_seeds = h->num_output;
-  SAM_CHECK(b->num_seeds <= max_seeds_ && b->key < cfg.num_epoch * num_global_step_, "arch5: a queue slot with a bad header");
-  b->recv_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  return true;
-}
-
-// DoGraphCopy (dist_loops_arch5.cc): the slot's arrays into the batch's buffers on this GPU, one launch on xs; the
-// slot goes back to the samplers as soon as that launch has completed (the timer's end: the host waits for it)
-void Engine::Unpack(Batch *b, hipStream_t xs) {
-  const uint32_t L = (uint32_t)cfg.fanout.size();
-  ggms_queue_batch_t dst{};
-  for (uint32_t i = 0; i < L; ++i) {
-    dst.row[i] = b->row[i];
-    dst.col[i] = b->col[i];
-    dst.data[i] = b->data[i];
-  }
-  dst.input_nodes = b->input_nodes;
-  dst.output_nodes = b->output_nodes;
-  dst.counts = b->counts_dev;
-  SAM_GGMS(ggms_launch_timer_arm(b->handoff_timer));
-  SAM_GGMS(ggms_queue_unpack(&dst, queue_slots_dev_ + (b->queue_pos % queue_depth_) * qlay_.slot_bytes, &qlay_, xs));
-  double us = 0;
-  SAM_GGMS(ggms_launch_timer_elapsed_us(b->handoff_timer, &us)); // blocks until the unpack has completed
-  __atomic_store_n(&QueueHeader(b->queue_pos)->seq, b->queue_pos + queue_depth_, __ATOMIC_RELEASE); // free
-}
-
-// ---- the host-staged feature path: arch6 without `gpu_extract` (the reference's SGNN mode) --------------------------
-// Reference, cache > 0: DoArch6GetCacheMissIndex + DoCacheIdCopyToCPU + DoArch6CacheFeatureCopy (dist_loops.cc:1015-1207:
-// split on the GPU, miss ids to the host, ExtractMissData on the CPU, ONE H2D copy, CombineMissData, CombineCacheData --
-// every phase behind a StreamSync); cache 0: DoIdCopy + DoCPUFeatureExtract + DoFeatureCopy (dist_loops.cc:481-583,
-// dist_loops_arch6.cc:111-133).  Same data flow here, as a pipeline:
-//   * the split is enqueued right behind the sampler with the batch size left on the device
-//     (ggms_get_miss_cache_index_dev), the hit rows are combined from the cache shards while the host works;
-//   * the miss rows go through pinned memory (hipHostMalloc) in CHUNKS: the host team gathers chunk k + 1 while chunk k's
-//     asynchronous H2D copy and its scatter into the batch run -- the copy engine, the combine kernel and the cores
-//     overlap instead of taking turns, and the last chunks of batch k overlap the first of batch k + 1;
-//   * cache 0: every row is a miss and lands where it belongs -- chunks are copied straight into the batch's feature
-//     buffer, no split and no combine;
-//   * two short host waits per batch (sizes, miss ids) instead of one per phase.
-// `staged_serial_epochs` / `staged_serial_steps` (config keys: the first N epochs / batches) or SAMGRAPH_STAGED_SERIAL=1:
-// the reference's serial sequence instead, every phase
-// timed behind its own wait and logged under the reference's items (kLogL3CacheExtractMissTime ...): the per-phase
-// rates of study/host-extract-speed-amount/data.dat are measured this way.
-
-// one row into pinned memory: streaming stores (no read-for-ownership of a buffer the CPU never reads back)
-static inline void copy_row_stream(char *dst, const char *src, size_t bytes) {
-  typedef long long v2di __attribute__((vector_size(16), aligned(1)));
-  typedef long long v2da __attribute__((vector_size(16)));
-  size_t i = 0;
-  if (((uintptr_t)dst & 15) == 0)
-    for (; i + 16 <= bytes; i += 16) __builtin_nontemporal_store(*(const v2di *)(src + i), (v2da *)(dst + i));
-  if (i < bytes) std::memcpy(dst + i, src + i, bytes - i);
-}
-
-static inline void store_fence() { // streaming stores are weakly ordered: drain them before the DMA engine is told to read
-#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("sfence" ::: "memory");
-#else
-  std::atomic_thread_fence(std::memory_order_seq_cst);
-#endif
-}
-
-void Engine::HostGatherRows(char *rows, const uint32_t *ids, size_t first, size_t count) {
-  const char *feat = (const char *)ds.feat.ptr;
-  const size_t row_bytes = ds.feat_dim * ggms_dtype_bytes(ds.feat_dtype);
-  const uint32_t mask = ds.feat_mask;
-  host_team_->ParallelFor(count, [&](size_t lo, size_t hi, int) { // ExtractMissData, cuda_cache_manager_host.cc:268-300
-    constexpr size_t kAhead = 8; // rows: a random 512-byte row is 8 cache lines nobody has asked for yet
-    for (size_t i = lo; i < hi; ++i) {
-      if (i + kAhead < hi) {
-        const char *nx = feat + (size_t)(ids[first + i + kAhead] & mask) * row_bytes;
-        for (size_t o = 0; o < row_bytes; o += 64) __builtin_prefetch(nx + o, 0, 0);
-      }
-      copy_row_stream(rows + (first + i) * row_bytes, feat + (size_t)(ids[first + i] & mask) * row_bytes, row_bytes);
-    }
-    store_fence();
-  });
-}
-
-void Engine::StagedExtract(Batch *b, hipStream_t ss, hipStream_t xs) {
-  const uint32_t L = (uint32_t)cfg.fanout.size();
-  const size_t row_bytes = ds.feat_dim * ggms_dtype_bytes(ds.feat_dtype);
-  if (!host_team_) {
-    host_team_ = std::make_unique<Team>((int)std::max<size_t>(1, cfg.omp_thread_num));
-    log_info("staged extract: host team of " + std::to_string(host_team_->size()) + " threads (omp_thread_num)");
-  }
-  static const bool env_serial = getenv("SAMGRAPH_STAGED_SERIAL") != nullptr;
-  const bool serial = env_serial || cur_epoch_ < cfg.staged_serial_epochs || staged_batches_ < cfg.staged_serial_steps;
-  ++staged_batches_;
-  const bool have_cache = cache_table_ != nullptr;
-  uint64_t *n_in = b->counts_dev + 3 * L, *n_miss = b->counts_dev + 3 * L + 2, *n_hit = b->counts_dev + 3 * L + 3;
-  using clk = std::chrono::steady_clock;
-  auto since = [](clk::time_point t) { return std::chrono::duration<double>(clk::now() - t).count(); };
-  double t_index = 0, t_ids = 0, t_gather = 0, t_copy = 0, t_comb_miss = 0, t_comb_hit = 0;
-  auto t0 = clk::now();
-  // 0. split (GetMissCacheIndex) behind the sampler ON THE BATCH'S SAMPLING STREAM, sizes to the host: wait 1.  The
-  // extract stream may still be copying the previous batch's last chunks down -- the cores must not wait for that
-  if (have_cache)
-    SAM_GGMS(ggms_get_miss_cache_index_dev(cache_table_, b->input_nodes, max_unique_, n_in, b->miss_src, b->miss_dst, n_miss,
-                                           b->hit_src, b->hit_dst, n_hit, b->idx_ws,
-                                           ggms_cache_index_workspace_bytes(max_unique_), ss));
-  SAM_HIP(hipMemcpyAsync(b->counts, b->counts_dev, (3 * L + 8) * 8, hipMemcpyDeviceToHost, ss));
-  SAM_HIP(hipStreamSynchronize(ss));
-  const size_t num_input = b->counts[3 * L];
-  size_t num_miss = have_cache ? b->counts[3 * L + 2] : num_input, num_hit = have_cache ? b->counts[3 * L + 3] : 0;
-  if (!have_cache) { // every row comes from the host tier: the counters say so too
-    b->counts[3 * L + 2] = num_input;
-    SAM_HIP(hipMemcpyAsync(n_miss, b->counts + 3 * L + 2, 8, hipMemcpyHostToDevice, ss));
-  }
-  SAM_CHECK(num_miss + num_hit == num_input, "CHECK_EQ(num_miss + num_cache, num_input), dist_loops.cc:1047");
-  t_index = since(t0);
-  if (num_input == 0) return;
-  // 1. miss ids to the host (DoCacheIdCopyToCPU / DoIdCopy): wait 2 -- the hit rows are combined meanwhile
-  const uint32_t *ids_dev = have_cache ? b->miss_src : b->input_nodes;
-  t0 = clk::now();
-  if (num_miss) SAM_HIP(hipMemcpyAsync(b->miss_ids_host, ids_dev, num_miss * 4, hipMemcpyDeviceToHost, ss));
-  SAM_HIP(hipEventRecord(b->ev_ids, ss));
-  SAM_HIP(hipStreamWaitEvent(xs, b->ev_ids, 0)); // the extract stream's work of this batch starts behind the split
-  auto combine_hits = [&] { // CombineCacheData
-    if (!num_hit) return;
-    if (num_cache_part_ == 0)
-      SAM_GGMS(ggms_gather_scatter(b->feat, cache_parts_[0], b->hit_src, b->hit_dst, num_hit, nullptr, ds.feat_dim,
-                                   ds.feat_dtype, xs));
-    else
-      SAM_GGMS(ggms_gather_scatter_partition(b->feat, (const void *const *)cache_parts_.data(), num_cache_part_, b->hit_src,
-                                             b->hit_dst, num_hit, nullptr, ds.feat_dim, ds.feat_dtype, xs));
-  };
-  if (!serial) combine_hits(); // on the GPU while the cores gather
-  SAM_HIP(hipEventSynchronize(b->ev_ids));
-  t_ids = since(t0);
-  char *rows = (char *)b->miss_rows_host;
-  // where a chunk of miss rows lands on the device: the staging area (scattered by CombineMissData), or -- no cache,
-  // rows in batch order -- the batch's feature buffer itself
-  char *land = have_cache ? (char *)b->miss_rows_dev : (char *)b->feat;
-  if (serial) { // the reference's sequence, one phase at a time
-    t0 = clk::now();
-    HostGatherRows(rows, b->miss_ids_host, 0, num_miss);
-    t_gather = since(t0);
-    t0 = clk::now();
-    if (num_miss) SAM_HIP(hipMemcpyAsync(land, rows, num_miss * row_bytes, hipMemcpyHostToDevice, xs));
-    SAM_HIP(hipStreamSynchronize(xs));
-    t_copy = since(t0);
-    t0 = clk::now();
-    if (have_cache && num_miss)
-      SAM_GGMS(ggms_gather_scatter(b->feat, b->miss_rows_dev, nullptr, b->miss_dst, num_miss, nullptr, ds.feat_dim,
-                                   ds.feat_dtype, xs)); // CombineMissData
-    SAM_HIP(hipStreamSynchronize(xs));
-    t_comb_miss = since(t0);
-    t0 = clk::now();
-    combine_hits();
-    SAM_HIP(hipStreamSynchronize(xs));
-    t_comb_hit = since(t0);
-  } else {
-    static const size_t chunk_mb = [] { const char *e = getenv("SAMGRAPH_STAGED_CHUNK_MB"); const long v = e ? atol(e) : 0; return (size_t)(v > 0 ? v : 16); }();
-    static const size_t chunk_rows = [] { const char *e = getenv("SAMGRAPH_STAGED_CHUNK_ROWS"); const long v = e ? atol(e) : 0; return (size_t)(v > 0 ? v : 0); }(); // test hook
-    const size_t chunk = chunk_rows ? chunk_rows : std::max<size_t>(1024, (chunk_mb << 20) / row_bytes);
-    // ONE dispatch of the host team per batch: every thread walks the chunks itself (its slice of chunk 0, of chunk 1,
-    // ...) and ticks the chunk's counter; the calling thread -- thread 0 of the team, the only one that talks to HIP --
-    // hands every chunk whose counter is full to the copy engine between two of its own slices.  (One dispatch per
-    // chunk was 34 wake-ups of 15 sleeping threads per batch: a millisecond of an 11-ms step.)
-    const size_t nchunks = (num_miss + chunk - 1) / chunk;
-    const int T = host_team_->size();
-    std::vector<std::atomic<int>> ticks(nchunks);
-    for (auto &t : ticks) t.store(0, std::memory_order_relaxed);
-    size_t flushed = 0;
-    auto flush_ready = [&](bool all) {
-      while (flushed < nchunks) {
-        if (ticks[flushed].load(std::memory_order_acquire) != T) {
-          if (!all) return;
-          std::this_thread::yield();
-          continue;
-        }
-        const size_t lo = flushed * chunk, m = std::min(chunk, num_miss - lo);
-        SAM_HIP(hipMemcpyAsync(land + lo * row_bytes, rows + lo * row_bytes, m * row_bytes, hipMemcpyHostToDevice, xs));
-        if (have_cache)
-          SAM_GGMS(ggms_gather_scatter(b->feat, (char *)b->miss_rows_dev + lo * row_bytes, nullptr, b->miss_dst + lo, m, nullptr,
-                                       ds.feat_dim, ds.feat_dtype, xs)); // CombineMissData of this chunk
-        ++flushed;
-      }
-    };
-    t0 = clk::now();
-    const char *feat = (const char *)ds.feat.ptr;
-    const uint32_t *ids = b->miss_ids_host;
-    const uint32_t mask = ds.feat_mask;
-    host_team_->ParallelFor((size_t)T, [&](size_t tid, size_t, int) { // one iteration per thread: iteration == thread
-      constexpr size_t kAhead = 8;
-      for (size_t c = 0; c < nchunks; ++c) {
-        const size_t base = c * chunk, m = std::min(chunk, num_miss - base);
-        const size_t q = m / T, r = m % T;
-        const size_t lo = base + tid * q + std::min<size_t>(tid, r), hi = lo + q + (tid < r ? 1 : 0);
-        for (size_t i = lo; i < hi; ++i) {
-          if (i + kAhead < hi) {
-            const char *nx = feat + (size_t)(ids[i + kAhead] & mask) * row_bytes;
-            for (size_t o = 0; o < row_bytes; o += 64) __builtin_prefetch(nx + o, 0, 0);
-          }
-          copy_row_stream(rows + i * row_bytes, feat + (size_t)(ids[i] & mask) * row_bytes, row_bytes);
-        }
-        store_fence();
-        ticks[c].fetch_add(1, std::memory_order_release);
-        if (tid == 0) flush_ready(false);
-      }
-    });
-    t_gather = since(t0);
-    flush_ready(true);
-  }
-  // the reference's step items (profiler.h:111-116: 44 .. 49); overlapped mode: the host's own busy time per phase
-  prof.LogStep(b->key, 44, t_index);
-  prof.LogStep(b->key, 45, t_ids);
-  prof.LogStep(b->key, 46, t_gather);
-  prof.LogStep(b->key, 47, t_copy);
-  prof.LogStep(b->key, 48, t_comb_miss);
-  prof.LogStep(b->key, 49, t_comb_hit);
-  prof.LogEpochAdd(b->key, 20 /*extension: host gather seconds of the staged path*/, t_gather);
-  prof.LogEpochAdd(b->key, 21 /*extension: H2D seconds (serial mode)*/, t_copy);
-  prof.LogEpochAdd(b->key, 22 /*extension: combine-miss seconds (serial mode)*/, t_comb_miss);
-  prof.LogEpochAdd(b->key, 23 /*extension: combine-cache seconds (serial mode)*/, t_comb_hit);
+// a kernel of the batch hit a bound it must not hit (include/ggms.h, device status word): the reference CHECK-aborts in
+// these places (logging.cc:69-73), and so does the engine
+void Engine::CheckBatchStatus(uint64_t status, uint64_t key) const {
+  if (status == 0) return;
+  const std::string where = IsArch5Sampler() ? " on sampler " + std::to_string(worker_id_) : "";
+  fprintf(stderr, "[samgraph] FATAL: device status %#llx after batch %llu%s (%s%s): results are invalid\n",
+          (unsigned long long)status, (unsigned long long)key, where.c_str(),
+          (status & GGMS_STATUS_SCAN_SPIN) ? "ordered scan: look-back gave up " : "",
+          (status & GGMS_STATUS_TABLE_FULL) ? "hashed dedup table full" : "");
+  abort();
 }
 
 // block until the batch is complete, publish sizes, log the items the scripts read
@@ -1782,15 +1407,7 @@ void Engine::Finish(Batch *b, Batch *prev) {
   const uint32_t L = (uint32_t)cfg.fanout.size();
   b->num_input = b->counts[3 * L];
   b->num_miss = b->counts[3 * L + 2];
-  // a kernel of the batch hit a bound it must not hit (include/ggms.h, device status word): the reference
-  // CHECK-aborts in these places (logging.cc:69-73), and so does the engine
-  if (b->counts[3 * L + 1] != 0) {
-    fprintf(stderr, "[samgraph] FATAL: device status %#llx after batch %llu (%s%s): results are invalid\n",
-            (unsigned long long)b->counts[3 * L + 1], (unsigned long long)b->key,
-            (b->counts[3 * L + 1] & GGMS_STATUS_SCAN_SPIN) ? "ordered scan: look-back gave up " : "",
-            (b->counts[3 * L + 1] & GGMS_STATUS_TABLE_FULL) ? "hashed dedup table full" : "");
-    abort();
-  }
+  CheckBatchStatus(b->counts[3 * L + 1], b->key);
   float ms_sample = 0, ms_copy = 0;
   if (cfg.arch != kArch5) (void)hipEventElapsedTime(&ms_sample, b->ev_start, b->ev_sampled); // (arch5: sampled elsewhere)
   if (b->lean) ms_copy = (float)(us_gather * 1e-3); // the gather kernel's own time
@@ -1812,8 +1429,8 @@ void Engine::Finish(Batch *b, Batch *prev) {
   prof.LogEpochAdd(b->key, 12 /*kLogEpochFeatureBytes*/, b->num_input * row_bytes);
   prof.LogEpochAdd(b->key, 13 /*kLogEpochMissBytes*/, b->num_miss * row_bytes);
   prof.LogEpochAdd(b->key, 15 /*kLogEpochNumSample*/, (double)edges);
-  if (cfg.arch == kArch3 || cfg.arch == kArch5) { // what the hand-off (arch5: the unpack) moved and its time
-    double us_handoff = 0;                           // (DoGraphCopy / DoIdCopy, cuda/cuda_loops.cc:629,653)
+  if (BatchSampledElsewhere()) { // what the hand-off (arch5: the unpack) moved and its time
+    double us_handoff = 0;       // (DoGraphCopy / DoIdCopy, cuda/cuda_loops.cc:629,653)
     SAM_GGMS(ggms_launch_timer_elapsed_us(b->handoff_timer, &us_handoff));
     const double per_edge = cfg.sample_type == GGMS_RANDOM_WALK ? 12.0 : 8.0; // row + col (+ data)
     prof.LogStep(b->key, 12 /*kLogL1GraphBytes*/, edges * per_edge);

@@ -45,6 +45,7 @@ namespace sam {
     if (rc_ != 0) ::sam::fatal(__FILE__, __LINE__, std::string(#call " -> ") + ggms_last_error()); \
   } while (0)
 void log_info(const std::string &msg);
+int parse_device(const std::string &ctx); // the N of "cuda:N" / "cpu:N", or SAMGRAPH_FORCE_DEVICE
 
 // ---- RunConfig: run_config.h + operation.cc:64-326 -----------------------------
 enum Arch { kArch0 = 0, kArch1, kArch2, kArch3, kArch4, kArch5, kArch6, kArch7 };
@@ -134,6 +135,16 @@ class Profiler {
   std::mutex mu_;
 };
 
+// ---- the arrays of one sampled batch on one device ------------------------------
+struct BatchArrays {
+  std::vector<uint32_t *> row, col, data; // per layer; data: random walk only (else null)
+  uint32_t *input_nodes = nullptr, *output_nodes = nullptr;
+  uint64_t *counts_dev = nullptr; // 3L+8: counts, status, then rows per tier {host miss, remote, local, replica}
+  // hipMalloc on the current device at the batch bounds (Engine::ComputeBounds); counts_dev starts zeroed
+  void Alloc(const std::vector<size_t> &max_edges, size_t max_unique, size_t max_seeds, bool with_data);
+  ggms_queue_batch_t View() const; // (arch5: the batch as the queue kernels take it)
+};
+
 // ---- one mini-batch in flight (Task / TrainGraph, common.h:246-283) -------------
 struct Batch {
   uint64_t key = 0;
@@ -141,13 +152,15 @@ struct Batch {
   std::atomic<int> refs{0};
   bool in_use = false;
   bool host = false; // arch0 with a host trainer: the buffers below are host memory, complete when enqueued
-  // device buffers, allocated once at their upper bounds
-  std::vector<uint32_t *> row, col, data;
-  uint32_t *input_nodes = nullptr, *output_nodes = nullptr;
+  // device buffers, allocated once at their upper bounds: the batch as handed out, on the trainer GPU ...
+  BatchArrays trainer;
+  // ... and as the sampler writes it.  arch3: its own copies on the SAMPLER GPU, which ggms_batch_handoff copies into
+  // `trainer` (handoff_timer rides on that launch).  Every other deployment samples straight into `trainer`: these
+  // are the same pointers.
+  BatchArrays sampler;
   void *feat = nullptr;
   int64_t *label = nullptr;
-  uint64_t *counts_dev = nullptr; // 3L+8: counts, status, then rows per tier {host miss, remote, local, replica}
-  // pinned host copy (hipHostMalloc), valid after Finish()
+  // pinned host copy (hipHostMalloc) of trainer.counts_dev, valid after Finish()
   uint64_t *counts = nullptr;
   size_t num_seeds = 0, num_input = 0;
   uint64_t num_miss = 0;
@@ -163,13 +176,7 @@ struct Batch {
   // lean: this batch's extract stream carried the gather and nothing else (EnqueueOne)
   ggms_launch_timer_t *gather_timer = nullptr;
   bool lean = false;
-  // arch3: the sampler writes its own copies of row / col / data / input / output nodes / counts on the SAMPLER GPU,
-  // and ggms_batch_handoff copies them into the buffers above, on the trainer GPU (handoff_timer rides on that
-  // launch).  Every other deployment samples straight into the buffers above: these alias them.
-  std::vector<uint32_t *> s_row, s_col, s_data;
-  uint32_t *s_input_nodes = nullptr, *s_output_nodes = nullptr;
-  uint64_t *s_counts_dev = nullptr;
-  ggms_launch_timer_t *handoff_timer = nullptr; // (arch5: rides on the unpack launch)
+  ggms_launch_timer_t *handoff_timer = nullptr; // arch3: rides on the hand-off; arch5: on the unpack
   // arch5 trainer: the queue ticket whose slot this batch came from, and the host's wait for that message
   uint64_t queue_pos = 0;
   double recv_s = 0;
@@ -205,6 +212,8 @@ class Engine {
   uint64_t BatchKey(uint64_t epoch, uint64_t step) const { return epoch * num_global_step_ + step; }
   int trainer_device() const { return cfg.arch == kArch3 ? trainer_device_ : device_; }
   bool IsArch5Sampler() const { return cfg.arch == kArch5 && role_ == kRoleSampler; }
+  // arch3 / arch5: the batch is sampled elsewhere (sampler GPU / process) and handed to the trainer GPU's extract stream
+  bool BatchSampledElsewhere() const { return cfg.arch == kArch3 || cfg.arch == kArch5; }
   int batch_device_type() const { return (cfg.arch == kArch0 && cfg.trainer_on_host) ? 0 : 2; } // DeviceType, common.h:48
   void Barrier(const char *what = "step");
   void *OpenPeer(const hipIpcMemHandle_t &handle, uint32_t peer, size_t bytes, const char *what);
@@ -245,6 +254,7 @@ class Engine {
   bool CpuEnqueueOne(bool background);
   void CpuShutdown();
   void Finish(Batch *b, Batch *prev);
+  void CheckBatchStatus(uint64_t status, uint64_t key) const; // the device status word of a completed batch
   void EnablePeerAccess(); // arch3: the trainer GPU reads the sampler GPU's batch buffers in place
   void Handoff(Batch *b, hipStream_t xs);
   void EnqueueGather(Batch *b, hipStream_t ss); // label + feature gather of a sampled (arch3: handed-off) batch
@@ -268,7 +278,8 @@ class Engine {
   void QueueMap();
   ggms_queue_header_t *QueueHeader(uint64_t pos) const;
   bool QueueWait(const uint64_t *word, uint64_t want, const char *what, bool stoppable);
-  void WaitRankingReady();
+  void PublishRanking();   // pre_sample: sampler 0's ranking is written ...
+  void WaitRankingReady(); // ... and everybody else waits for it
   void Arch5TrainerInit(int worker_id, const std::string &ctx);
   void SendOne();                                // a sampler's sample_once
   bool Receive(Batch *b);                        // a trainer takes the next message (host side)
@@ -305,6 +316,7 @@ class Engine {
   std::vector<Pipe> pipes_;
   size_t enq_count_ = 0;
   hipEvent_t last_rng_done_ = nullptr;
+  void SampleInto(Batch *b, Pipe &P); // sample b's seeds into b->sampler on P's stream, then record b->ev_sampled
   size_t max_seeds_ = 0, max_unique_ = 0; // batch bounds (ComputeBounds)
   std::vector<size_t> max_input_, max_edges_;
   // shuffler
