@@ -163,6 +163,8 @@ enum ggms_sample_type {
   GGMS_KHOP3 = 7
 };
 
+/* Workspace of every leaf sampler below but random walk, whose size depends on
+ * its walk: ggms_sample_random_walk_workspace_bytes. */
 size_t ggms_sample_workspace_bytes(int sample_type, size_t num_input,
                                    size_t fanout);
 

@@ -79,6 +79,24 @@ def test_batch_entry_points_refuse_bad_layer_counts():
     assert l.ggms_sample_batch(7, C.byref(g), p, 10, f, 2, C.byref(ht), p, 100, rows, rows, p, None, p, 16, None) == INVALID  # workspace too small
 
 
+def test_batch_refuses_a_short_rng_pool_for_every_sampler_that_draws():
+    # the bound of each leaf entry point, per layer: khop1 / weighted_khop draw one stream per thread of
+    # min(tasks, roundup256(min(tasks, 512K))), tasks = max_input[i] * fanout[i]; the deepest layer has 6000 * 5 tasks
+    l = lib()
+    p = C.c_void_p(1 << 20)  # never dereferenced: the checks come first
+    f = (C.c_size_t * 2)(5, 5)
+    rows = (C.c_void_p * 2)(p, p)
+    g, ht = Graph(), HashTable()
+    g.indptr, g.indices, g.num_node = 1 << 22, 1 << 23, 1000
+    ht.o2n, ht.n2o, ht.num_items_dev, ht.o2n_size, ht.n2o_size, ht.version, ht.direct = 1, 2, 3, 1000, 1 << 20, 1, 1
+    extra = _lib.SampleExtra()
+    extra.prob_table, extra.alias_table = 1 << 24, 1 << 25
+    for sample_type in (1, 2):  # GGMS_KHOP1, GGMS_WEIGHTED_KHOP
+        assert l.ggms_sample_batch(sample_type, C.byref(g), p, 1000, f, 2, C.byref(ht), p, 6000 * 5 - 1, rows, rows, p,
+                                   C.byref(extra), p, 1 << 40, None) == INVALID
+        assert "num_states" in _err()
+
+
 def test_probe_and_samplers_refuse_nonsense():
     l = lib()
     p = C.c_void_p(1 << 20)

@@ -43,13 +43,6 @@ struct FirstLayer {
   BatchPrologue pro;
   uint32_t *n2o;
 };
-// sample_khop.hip
-size_t sample_ws_words(size_t num_input);
-size_t khop0_ws_words(size_t num_input, size_t fanout);
-int sample_khop3_impl(GraphView g, const uint32_t *input, size_t n_max, Count n, uint32_t fanout, uint32_t *out_src,
-                      uint32_t *out_dst, uint64_t *num_out_dev, uint32_t *states, uint32_t *workspace,
-                      const uint32_t *seed_local, int src_local, hipStream_t s, ScanArea *shared_scan = nullptr,
-                      const DedupInsert *insert = nullptr, const FirstLayer *first = nullptr);
 bool khop3_can_fuse_seeds(size_t num_seeds); // every tile of the first layer has a workgroup of its own
 // distinct seeds, any sampler: one launch -- table entries, head of the unique list, batch prologue (hashtable.hip)
 int seed_enter_impl(const ggms_hashtable_t *ht, const uint32_t *seeds, size_t num_seeds, const BatchPrologue &pro,
@@ -64,36 +57,53 @@ struct SeedEnter {
 };
 bool khop0_can_enter_seeds(size_t num_seeds); // its plan pass is one launch
 size_t khop0_plan_desc_words(size_t num_seeds); // descriptor words of the batch's scan area that launch uses itself
-int sample_khop0_impl(GraphView g, const uint32_t *input, size_t n_max, Count n, uint32_t fanout, uint32_t *out_src,
-                      uint32_t *out_dst, uint64_t *num_out_dev, uint32_t *workspace, const uint32_t *seed_local,
-                      int src_local, hipStream_t s, ScanArea *shared_scan = nullptr, const DedupInsert *insert = nullptr,
-                      const SeedEnter *enter = nullptr);
-int sample_khop2_impl(const uint32_t *indptr, uint32_t *indices, size_t num_node, const uint32_t *input, size_t n_max,
-                      Count n, uint32_t fanout, uint32_t *out_src, uint32_t *out_dst, uint64_t *num_out_dev,
-                      uint32_t *states, uint32_t *workspace, const uint32_t *seed_local, int src_local, hipStream_t s,
-                      ScanArea *shared_scan = nullptr);
 
+constexpr uint64_t kWeightedMaxThreads = 512 * 1024; // Constant::kWeightedKHopMaxThreads, constant.h:72
+constexpr uint32_t kDedupSlots = 50; // table slots per seed of weighted_khop_hash_dedup: fanout < 50, hash_dedup.cu:42
+
+// One sampler call: a layer of ggms_sample_batch or a leaf entry point.  The leaf path leaves `src` at {nullptr, 0}
+// and the batch's pieces (scan, insert, first, enter) null.  Sizes are the caller's; the samplers narrow them.
+struct SampleLayer {
+  const ggms_graph_t *graph;
+  const uint32_t *input;
+  size_t n_max;                  // bound of n: grids and workspace pieces are sized from it
+  size_t fanout;                 // random walk: K
+  uint32_t *out_src, *out_dst;
+  uint64_t *num_out;             // device
+  uint32_t *states, *workspace;
+  hipStream_t s;
+  Count n = {};
+  GraphView g = {};              // view_of(graph)
+  SrcMode src = {};
+  ScanArea *scan = nullptr;             // the batch's scan area; else the workspace holds a private one
+  const DedupInsert *insert = nullptr;  // direct table: the sampler enters its output itself
+  const FirstLayer *first = nullptr;    // khop3: the batch's distinct seeds ride on the first layer
+  const SeedEnter *enter = nullptr;     // khop0: its plan pass enters the batch's distinct seeds
+  const float *prob = nullptr;          // weighted family
+  const uint32_t *alias = nullptr;
+  uint32_t *out_data = nullptr;         // random walk: visit counts
+  size_t walk_length = 0, num_walk = 0;
+  double restart_prob = 0;
+};
+
+// sample_khop.hip
+size_t sample_ws_words(size_t num_input);
+size_t khop0_ws_words(size_t num_input, size_t fanout);
+int sample_khop3_impl(const SampleLayer &l);
+int sample_khop0_impl(const SampleLayer &l);
+int sample_khop2_impl(const SampleLayer &l);
 // sample_weighted.hip
 size_t weighted_ws_words(size_t num_input, size_t fanout);
-int sample_weighted_impl(const uint32_t *indptr, const uint32_t *indices, const float *prob, const uint32_t *alias,
-                         const uint32_t *input, size_t n_max, Count n, uint32_t fanout, uint32_t *out_src,
-                         uint32_t *out_dst, uint64_t *num_out_dev, uint32_t *states, uint32_t *workspace,
-                         const uint32_t *seed_local, int src_local, hipStream_t s, ScanArea *shared_scan = nullptr,
-                         uint32_t num_node = 0, const DedupInsert *insert = nullptr);
+int sample_weighted_impl(const SampleLayer &l, int type); // khop1, weighted_khop, weighted_khop_prefix
+int sample_weighted_hash_dedup_impl(const SampleLayer &l);
 // sample_random_walk.hip
 size_t random_walk_ws_words(size_t num_input, size_t walk_length, size_t num_walk, size_t K);
-int sample_random_walk_impl(GraphView g, const uint32_t *input, size_t n_max, Count n, uint32_t walk_length,
-                            double restart_prob, uint32_t num_walk, uint32_t K, uint32_t *out_src, uint32_t *out_dst,
-                            uint32_t *out_data, uint64_t *num_out_dev, uint32_t *states, uint32_t *workspace,
-                            const uint32_t *seed_local, int src_local, hipStream_t s, ScanArea *shared_scan,
-                            const DedupInsert *insert);
+int sample_random_walk_impl(const SampleLayer &l);
 size_t walk_scan_tiles(size_t num_input);
 
-int sample_weighted_hash_dedup_impl(const uint32_t *indptr, const uint32_t *indices, const float *prob,
-                                    const uint32_t *alias, const uint32_t *input, size_t n_max, Count n,
-                                    uint32_t fanout, uint32_t *out_src, uint32_t *out_dst, uint64_t *num_out_dev,
-                                    uint32_t *states, uint32_t *workspace, const uint32_t *seed_local, int src_local,
-                                    hipStream_t s, ScanArea *shared_scan = nullptr, const DedupInsert *insert = nullptr);
+// sample_batch.hip: the per-sampler rules, one copy for the leaf entry points and ggms_sample_batch
+size_t layer_ws_words(int type, size_t n, size_t fanout, size_t walk_length, size_t num_walk);
+int sample_leaf(int type, SampleLayer l, size_t num_states, size_t workspace_bytes); // a leaf entry point's body
 
 // hashtable.hip
 size_t ht_ws_words(size_t num_input);

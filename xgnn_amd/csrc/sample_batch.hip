@@ -63,6 +63,98 @@ static BatchCaps caps_of(size_t num_seeds, const size_t *fanouts, uint32_t L) {
   return c;
 }
 
+// ---- the per-sampler rules: one copy for the leaf entry points and ggms_sample_batch --------------------------
+
+size_t layer_ws_words(int type, size_t n, size_t fanout, size_t walk_length, size_t num_walk) {
+  switch (type) {
+  case GGMS_KHOP0: return khop0_ws_words(n, fanout);
+  case GGMS_KHOP1:
+  case GGMS_WEIGHTED_KHOP:
+  case GGMS_WEIGHTED_KHOP_PREFIX: return weighted_ws_words(n, fanout);
+  case GGMS_RANDOM_WALK: return random_walk_ws_words(n, walk_length, num_walk, fanout);
+  default: return sample_ws_words(n); // khop3, khop2, weighted_khop_hash_dedup
+  }
+}
+
+// fanout limits, sharded graphs, walk parameters: checked first, even by a leaf call with nothing to sample
+static int layer_shape_check(int type, const SampleLayer &l) {
+  GGMS_CHECK_ARG(l.fanout > 0); // a layer that samples nothing is a config error
+  if (type == GGMS_KHOP3) GGMS_CHECK_ARG(l.fanout < 128);                            // khop3.cu:85
+  if (type == GGMS_WEIGHTED_KHOP_HASH_DEDUP) GGMS_CHECK_ARG(l.fanout < kDedupSlots); // hash_dedup.cu:42
+  if (type == GGMS_RANDOM_WALK) GGMS_CHECK_ARG(l.walk_length > 0 && l.num_walk > 0);
+  // "this algorithm not support DistGraph engine", dist_loops.cc:167-228
+  if (type != GGMS_KHOP3 && type != GGMS_KHOP0 && type != GGMS_RANDOM_WALK) GGMS_CHECK_ARG(l.graph->num_part == 0);
+  return GGMS_OK;
+}
+
+// + the tables the sampler reads and its RNG-pool bound
+static int layer_check(int type, const SampleLayer &l, size_t num_states) {
+  const int rc = layer_shape_check(type, l);
+  if (rc != GGMS_OK) return rc;
+  const uint64_t n = l.n_max;
+  if (type == GGMS_KHOP1 || type == GGMS_KHOP2) GGMS_CHECK_ARG(l.graph->indptr && l.graph->indices);
+  if (type == GGMS_WEIGHTED_KHOP || type == GGMS_WEIGHTED_KHOP_HASH_DEDUP) GGMS_CHECK_ARG(l.prob && l.alias);
+  if (type == GGMS_WEIGHTED_KHOP_PREFIX) GGMS_CHECK_ARG(l.prob);
+  // the RNG pool: assert(i < num_random_states) in every sampler of the reference but khop0
+  switch (type) {
+  case GGMS_KHOP0: return GGMS_OK;
+  case GGMS_KHOP3: GGMS_CHECK_ARG(l.states && (n + 127) / 128 * 8 <= num_states); return GGMS_OK; // khop3.cu:89
+  case GGMS_KHOP2:                                                                                   // khop2.cu:57
+  case GGMS_WEIGHTED_KHOP_HASH_DEDUP: // hash_dedup.cu:70
+    GGMS_CHECK_ARG(l.states && (n + 1023) / 1024 * 256 <= num_states);
+    return GGMS_OK;
+  case GGMS_RANDOM_WALK:
+    GGMS_CHECK_ARG(l.states && ggms_random_walk_num_states(n, l.num_walk) <= num_states);
+    return GGMS_OK;
+  default: { // khop1.cu:51, weighted_khop.cu:52, prefix.cu:50: one stream per draw thread
+    const uint64_t tasks = n * l.fanout;
+    const uint64_t threads = tasks < kWeightedMaxThreads ? tasks : kWeightedMaxThreads;
+    const uint64_t span = (threads + 255) / 256 * 256;
+    GGMS_CHECK_ARG(l.states && (span < tasks ? span : tasks) <= num_states);
+    return GGMS_OK;
+  }
+  }
+}
+
+static int sample_layer(int type, const SampleLayer &l) {
+  switch (type) {
+  case GGMS_KHOP3: return sample_khop3_impl(l);
+  case GGMS_KHOP0: return sample_khop0_impl(l);
+  case GGMS_KHOP2: return sample_khop2_impl(l);
+  case GGMS_WEIGHTED_KHOP_HASH_DEDUP: return sample_weighted_hash_dedup_impl(l);
+  case GGMS_RANDOM_WALK: return sample_random_walk_impl(l);
+  default: return sample_weighted_impl(l, type); // khop1, weighted_khop, weighted_khop_prefix
+  }
+}
+
+// Whether the sampler enters its own output into the direct table (DedupInsert): khop3 and random walk on the way
+// out, khop0 where it produces it, the weighted family in the compaction's emit, hash_dedup by a seed's 16 lanes once
+// the seed is done.  khop2 does not: even with the four seeds of a lane in lock-step and their atomics issued together,
+// the returning atomics sit in the draw loop's dependency chain (measured on products: 0.45 -> 0.62 ms per step; the
+// separate insert launch of ht_fill_impl follows).
+static bool layer_enters_output(int type) { return type != GGMS_KHOP2; }
+
+// a leaf entry point: shape checks; nothing to sample -> a zero count (null pointers allowed); pointers, workspace and
+// RNG pool; the sampler
+int sample_leaf(int type, SampleLayer l, size_t num_states, size_t workspace_bytes) {
+  GGMS_CHECK_ARG(l.graph && l.num_out);
+  int rc = layer_shape_check(type, l);
+  if (rc != GGMS_OK) return rc;
+  if (l.n_max == 0) {
+    GGMS_HIP(hipMemsetAsync(l.num_out, 0, sizeof(uint64_t), l.s));
+    return GGMS_OK;
+  }
+  GGMS_CHECK_ARG(l.input && l.out_src && l.out_dst && l.workspace && (type != GGMS_RANDOM_WALK || l.out_data));
+  GGMS_CHECK_ARG(workspace_bytes >= layer_ws_words(type, l.n_max, l.fanout, l.walk_length, l.num_walk) * sizeof(uint32_t));
+  // 32-bit output positions; a random walk's are bounded by walk_length * num_walk < 2^31 instead
+  GGMS_CHECK_ARG(type == GGMS_RANDOM_WALK || (uint64_t)l.n_max * l.fanout < (1ull << 32));
+  rc = layer_check(type, l, num_states);
+  if (rc != GGMS_OK) return rc;
+  if (!view_of(l.graph, l.g)) return GGMS_ERR_INVALID; // after layer_check's refusal of a sharded graph
+  l.n = count_of(l.n_max);
+  return sample_layer(type, l);
+}
+
 } // namespace ggms
 
 using namespace ggms;
@@ -97,13 +189,10 @@ int ggms_sample_batch_capacity(size_t num_seeds, const size_t *fanouts, uint32_t
 static size_t sampler_ws_words(int sample_type, const BatchCaps &c, const size_t *fanouts, uint32_t L,
                                const ggms_sample_extra_t *extra) {
   size_t w = sample_ws_words(c.max_in_all);
-  for (uint32_t i = 0; i < L; ++i) {
-    if (sample_type == GGMS_KHOP0) w = std::max(w, khop0_ws_words(c.max_input[i], fanouts[i]));
-    if (sample_type == GGMS_WEIGHTED_KHOP || sample_type == GGMS_KHOP1 || sample_type == GGMS_WEIGHTED_KHOP_PREFIX)
-      w = std::max(w, weighted_ws_words(c.max_input[i], fanouts[i]));
-    if (sample_type == GGMS_RANDOM_WALK && extra)
-      w = std::max(w, random_walk_ws_words(c.max_input[i], extra->random_walk_length, extra->num_random_walk, fanouts[i]));
-  }
+  if (sample_type == GGMS_RANDOM_WALK && !extra) return w; // no walk: ggms_sample_batch refuses the call
+  for (uint32_t i = 0; i < L; ++i)
+    w = std::max(w, layer_ws_words(sample_type, c.max_input[i], fanouts[i], extra ? extra->random_walk_length : 0,
+                                   extra ? extra->num_random_walk : 0));
   return w;
 }
 
@@ -159,33 +248,27 @@ int ggms_sample_batch(int sample_type, const ggms_graph_t *graph, const ggms_id_
   GGMS_CHECK_ARG(num_layer >= 1 && num_layer <= 16);
   GGMS_CHECK_ARG(sample_type >= GGMS_KHOP0 && sample_type <= GGMS_KHOP3);
   GGMS_CHECK_ARG(num_seeds == 0 || seeds);
-  for (uint32_t i = 0; i < num_layer; ++i) GGMS_CHECK_ARG(fanouts[i] > 0); // a layer that samples nothing is a config error
   GGMS_CHECK_ARG(workspace && workspace_bytes >= ggms_sample_batch_workspace_bytes(sample_type, num_seeds, fanouts,
                                                                                    num_layer, extra));
-  if (sample_type == GGMS_WEIGHTED_KHOP)
-    GGMS_CHECK_ARG(extra && extra->prob_table && extra->alias_table && graph->num_part == 0 && states);
-  if (sample_type == GGMS_KHOP1) GGMS_CHECK_ARG(graph->num_part == 0 && graph->indptr && graph->indices && states);
-  if (sample_type == GGMS_WEIGHTED_KHOP_PREFIX)
-    GGMS_CHECK_ARG(extra && extra->prob_table && graph->num_part == 0 && states);
-  if (sample_type == GGMS_WEIGHTED_KHOP_HASH_DEDUP) {
-    GGMS_CHECK_ARG(extra && extra->prob_table && extra->alias_table && graph->num_part == 0);
-    GGMS_CHECK_ARG(states != nullptr);
-    for (uint32_t i = 0; i < num_layer; ++i) GGMS_CHECK_ARG(fanouts[i] > 0 && fanouts[i] < 50);
-  }
-  if (sample_type == GGMS_RANDOM_WALK)
-    GGMS_CHECK_ARG(extra && extra->data && extra->random_walk_length > 0 && extra->num_random_walk > 0 && states);
+  GGMS_CHECK_ARG(sample_type != GGMS_RANDOM_WALK || (extra && extra->data)); // the visit counts of every layer
   hipStream_t s = to_stream(stream);
   const BatchCaps c = caps_of(num_seeds, fanouts, num_layer);
   GGMS_CHECK_ARG(c.max_input[0] + c.max_edges[0] <= ht->n2o_size);
   GGMS_CHECK_ARG(c.max_input[0] + c.max_edges[0] < (1ull << 32) - 4); // indices and 2 + local id fit 32 bits
-  if (sample_type == GGMS_WEIGHTED_KHOP_HASH_DEDUP) GGMS_CHECK_ARG((c.max_in_all + 1023) / 1024 * 256 <= num_states);
-  if (sample_type == GGMS_KHOP2) { // unsharded CSR, mutated in place (dist_loops.cc:217-224)
-    GGMS_CHECK_ARG(graph->num_part == 0 && graph->indptr && graph->indices);
-    GGMS_CHECK_ARG(states && (c.max_in_all + 1023) / 1024 * 256 <= num_states);
+  // what every layer's sampler call shares; the loop below fills in the rest
+  SampleLayer L{graph, nullptr, 0, 0, nullptr, nullptr, nullptr, (uint32_t *)states, nullptr, s};
+  if (extra) {
+    L.prob = extra->prob_table;
+    L.alias = extra->alias_table;
+    L.walk_length = extra->random_walk_length;
+    L.num_walk = extra->num_random_walk;
+    L.restart_prob = extra->random_walk_restart_prob;
   }
-  if (sample_type == GGMS_KHOP3) {
-    GGMS_CHECK_ARG(states && (c.max_in_all + 127) / 128 * 8 <= num_states);
-    for (uint32_t i = 0; i < num_layer; ++i) GGMS_CHECK_ARG(fanouts[i] > 0 && fanouts[i] < 128);
+  for (uint32_t i = 0; i < num_layer; ++i) {
+    L.n_max = c.max_input[i];
+    L.fanout = fanouts[i];
+    const int rc = layer_check(sample_type, L, num_states);
+    if (rc != GGMS_OK) return rc;
   }
 
   const BatchLayout lay = layout_of(sample_type, num_seeds, fanouts, num_layer, c, extra);
@@ -197,6 +280,8 @@ int ggms_sample_batch(int sample_type, const ggms_graph_t *graph, const ggms_id_
   // every ordered scan of the batch (seed offsets, owner flags) shares one control/descriptor area that is
   // cleared once here: descriptors are epoch-tagged, the control words re-arm themselves
   ScanArea scan{w + lay.scan, true};
+  L.workspace = samp_ws;
+  L.scan = &scan;
   scan.chunk = w + lay.chunk;
   scan.tickets = scan.chunk + chunk_desc_words(); // chunk_desc_words() is a multiple of 4: the sets stay 16-byte aligned
   // every kernel of this batch reports a bound it hits into the BATCH's status word (behind the table's item counter;
@@ -204,8 +289,7 @@ int ggms_sample_batch(int sample_type, const ggms_graph_t *graph, const ggms_id_
   // in flight beside it (include/ggms.h, "Status words")
   scan.status = ht->num_items_dev + 1;
 
-  GraphView g;
-  if (!view_of(graph, g)) return GGMS_ERR_INVALID;
+  if (!view_of(graph, L.g)) return GGMS_ERR_INVALID;
   // hash_table->Reset (dist_loops.cc:105): a new version stamp; the item count is zeroed by the prologue below
   if (ht->version >= 0x7ffffff0u) {
     int rc0 = ggms_hashtable_init(ht, stream);
@@ -275,7 +359,6 @@ int ggms_sample_batch(int sample_type, const ggms_graph_t *graph, const ggms_id_
   size_t job_items = 0;
   for (int i = (int)num_layer - 1; i >= 0; --i) {
     const bool first = (i == (int)num_layer - 1);
-    const uint32_t *input = first ? seeds : ht->n2o;
     uint32_t *tmp_dst = w + lay.tmp_dst[i];
     const size_t n_max = c.max_input[i], e_max = c.max_edges[i];
     const Count n = first ? count_of(num_seeds) : count_of32(n_max, ht->num_items_dev);
@@ -286,64 +369,27 @@ int ggms_sample_batch(int sample_type, const ggms_graph_t *graph, const ggms_id_
     // batch order on the shared RNG pool (and on khop2's CSR): only the sampler kernels are ordered
     if (first && extra && extra->rng_wait) GGMS_HIP(hipStreamWaitEvent(s, (hipEvent_t)extra->rng_wait, 0));
     if (i == 0 && extra && extra->heavy_wait) GGMS_HIP(hipStreamWaitEvent(s, (hipEvent_t)extra->heavy_wait, 0));
-    // direct table + khop3: the sampler enters its output into the table itself (DedupInsert)
     di.base = next_base; // this layer's edges take the indices [base, base + e_max)
     di.w = (unsigned long long *)ht->o2n;
     di.version = ht->version;
-    bool inserted = false;
+    const bool inserted = ht->direct != 0 && e_max != 0 && layer_enters_output(sample_type);
+    if (inserted) di.tag = next_dedup_tag();
     if (n_max == 0) {
       GGMS_HIP(hipMemsetAsync(num_edge, 0, sizeof(uint64_t), s));
-    } else if (sample_type == GGMS_KHOP3) {
-      inserted = ht->direct != 0 && e_max != 0;
-      if (inserted) di.tag = next_dedup_tag();
-      rc = sample_khop3_impl(g, input, n_max, n, (uint32_t)fanouts[i], col[i], tmp_dst, num_edge, (uint32_t *)states,
-                             samp_ws, first ? seed_local : nullptr, 1, s, &scan, inserted ? &di : nullptr,
-                             first && fuse_seeds ? &first_layer : nullptr);
-    } else if (sample_type == GGMS_KHOP0) {
-      inserted = ht->direct != 0 && e_max != 0; // khop0 enters its output where it produces it, too
-      if (inserted) di.tag = next_dedup_tag();
-      rc = sample_khop0_impl(g, input, n_max, n, (uint32_t)fanouts[i], col[i], tmp_dst, num_edge, samp_ws,
-                             first ? seed_local : nullptr, 1, s, &scan, inserted ? &di : nullptr,
-                             first && khop0_enters ? &seed_enter : nullptr);
-    } else if (sample_type == GGMS_KHOP2) {
-      // no fused insert: even with the four seeds of a lane in lock-step and their atomics issued together, the
-      // returning atomics sit in the draw loop's dependency chain (measured on products: 0.45 -> 0.62 ms per step;
-      // the separate insert launch of ht_fill_impl follows)
-      rc = sample_khop2_impl(graph->indptr, const_cast<uint32_t *>(graph->indices), graph->num_node, input, n_max, n,
-                             (uint32_t)fanouts[i], col[i], tmp_dst, num_edge, (uint32_t *)states, samp_ws,
-                             first ? seed_local : nullptr, 1, s, &scan);
-    } else if (sample_type == GGMS_KHOP1) {
-      inserted = ht->direct != 0 && e_max != 0; // the weighted family enters its output in the compaction's emit
-      if (inserted) di.tag = next_dedup_tag();
-      rc = sample_weighted_impl(graph->indptr, graph->indices, nullptr, nullptr, input, n_max, n,
-                                (uint32_t)fanouts[i], col[i], tmp_dst, num_edge, (uint32_t *)states, samp_ws,
-                                first ? seed_local : nullptr, 1, s, &scan, graph->num_node, inserted ? &di : nullptr);
-    } else if (sample_type == GGMS_WEIGHTED_KHOP_PREFIX) {
-      inserted = ht->direct != 0 && e_max != 0;
-      if (inserted) di.tag = next_dedup_tag();
-      rc = sample_weighted_impl(graph->indptr, graph->indices, extra->prob_table, nullptr, input, n_max, n,
-                                (uint32_t)fanouts[i], col[i], tmp_dst, num_edge, (uint32_t *)states, samp_ws,
-                                first ? seed_local : nullptr, 1, s, &scan, graph->num_node, inserted ? &di : nullptr);
-    } else if (sample_type == GGMS_WEIGHTED_KHOP_HASH_DEDUP) {
-      inserted = ht->direct != 0 && e_max != 0; // a seed's picks are entered by its 16 lanes once the seed is done
-      if (inserted) di.tag = next_dedup_tag();
-      rc = sample_weighted_hash_dedup_impl(graph->indptr, graph->indices, extra->prob_table, extra->alias_table, input,
-                                           n_max, n, (uint32_t)fanouts[i], col[i], tmp_dst, num_edge,
-                                           (uint32_t *)states, samp_ws, first ? seed_local : nullptr, 1, s, &scan,
-                                           inserted ? &di : nullptr);
-    } else if (sample_type == GGMS_WEIGHTED_KHOP) {
-      inserted = ht->direct != 0 && e_max != 0;
-      if (inserted) di.tag = next_dedup_tag();
-      rc = sample_weighted_impl(graph->indptr, graph->indices, extra->prob_table, extra->alias_table, input, n_max, n,
-                                (uint32_t)fanouts[i], col[i], tmp_dst, num_edge, (uint32_t *)states, samp_ws,
-                                first ? seed_local : nullptr, 1, s, &scan, graph->num_node, inserted ? &di : nullptr);
-    } else { // random walk: fanout[i] = num_neighbor = K (operation.cc:174); enters its output like khop3
-      inserted = ht->direct != 0 && e_max != 0;
-      if (inserted) di.tag = next_dedup_tag();
-      rc = sample_random_walk_impl(g, input, n_max, n, (uint32_t)extra->random_walk_length,
-                                   extra->random_walk_restart_prob, (uint32_t)extra->num_random_walk,
-                                   (uint32_t)fanouts[i], col[i], tmp_dst, extra->data[i], num_edge, (uint32_t *)states,
-                                   samp_ws, first ? seed_local : nullptr, 1, s, &scan, inserted ? &di : nullptr);
+    } else {
+      L.input = first ? seeds : ht->n2o;
+      L.n_max = n_max;
+      L.n = n;
+      L.fanout = fanouts[i]; // random walk: num_neighbor = K (operation.cc:174)
+      L.out_src = col[i];
+      L.out_dst = tmp_dst;
+      L.num_out = num_edge;
+      L.src = SrcMode{first ? seed_local : nullptr, 1};
+      L.insert = inserted ? &di : nullptr;
+      L.first = first && fuse_seeds ? &first_layer : nullptr;
+      L.enter = first && khop0_enters ? &seed_enter : nullptr;
+      if (sample_type == GGMS_RANDOM_WALK) L.out_data = extra->data[i];
+      rc = sample_layer(sample_type, L);
     }
     if (rc != GGMS_OK) return rc;
     if (i == 0 && extra && extra->rng_done) GGMS_HIP(hipEventRecord((hipEvent_t)extra->rng_done, s));

@@ -763,17 +763,17 @@ size_t sample_ws_words(size_t num_input) {
 }
 
 template <int GPW, bool INSERT, bool FIRST>
-static int launch_khop3_fused(int grid, size_t lds, hipStream_t s, GraphView g, const uint32_t *input, Count n,
-                               uint32_t fanout, uint32_t *out_src, uint32_t *out_dst, SrcMode sm, uint32_t *states,
-                               uint32_t set_mask, uint32_t multi, FusedScan fs, DedupInsert di, FirstLayer fl) {
+static int launch_khop3_fused(int grid, size_t lds, const SampleLayer &l, uint32_t set_mask, uint32_t multi,
+                               FusedScan fs, DedupInsert di, FirstLayer fl) {
+  const uint32_t fanout = (uint32_t)l.fanout;
   const uint32_t fanout_magic = (uint32_t)((0x100000000ull + fanout - 1) / fanout); // ceil(2^32 / fanout)
   if (lds > (48u << 10)) { // large fan-outs: more dynamic LDS than the default per-kernel limit (gfx950 has 160 KB)
     static const int raised = raise_dynamic_lds(reinterpret_cast<const void *>(&k_khop3_fused<GPW, INSERT, FIRST>),
                                                 128 * 127 * 4, "k_khop3_fused (fanout >= 96)");
     if (raised != GGMS_OK) return raised;
   }
-  hipLaunchKernelGGL((k_khop3_fused<GPW, INSERT, FIRST>), dim3(grid), dim3(128 * (4 / GPW)), lds, s, g, input, n, fanout,
-                     fanout_magic, out_src, out_dst, sm, states, set_mask, multi, fs, di, fl);
+  hipLaunchKernelGGL((k_khop3_fused<GPW, INSERT, FIRST>), dim3(grid), dim3(128 * (4 / GPW)), lds, l.s, l.g, l.input, l.n,
+                     fanout, fanout_magic, l.out_src, l.out_dst, l.src, l.states, set_mask, multi, fs, di, fl);
   return GGMS_OK;
 }
 
@@ -782,16 +782,16 @@ bool khop3_can_fuse_seeds(size_t num_seeds) { return (num_seeds + 127) / 128 <= 
 // the whole layer in one launch (see k_khop3_fused).  shared_scan: the batch's scan area (cleared by the batch
 // prologue); else the workspace holds a private one that is cleared here.  insert (direct dedup table): the
 // neighbours are entered into the table on the way out.
-int sample_khop3_impl(GraphView g, const uint32_t *input, size_t n_max, Count n, uint32_t fanout, uint32_t *out_src,
-                      uint32_t *out_dst, uint64_t *num_out_dev, uint32_t *states, uint32_t *workspace,
-                      const uint32_t *seed_local, int src_local, hipStream_t s, ScanArea *shared_scan,
-                      const DedupInsert *insert, const FirstLayer *first) {
-  const size_t tiles = (n_max + 127) / 128;
-  if (first && (!insert || !shared_scan || !shared_scan->cleared || !khop3_can_fuse_seeds(n_max))) {
+int sample_khop3_impl(const SampleLayer &l) {
+  ScanArea *shared_scan = l.scan;
+  const DedupInsert *insert = l.insert;
+  const FirstLayer *first = l.first;
+  const size_t tiles = (l.n_max + 127) / 128;
+  if (first && (!insert || !shared_scan || !shared_scan->cleared || !khop3_can_fuse_seeds(l.n_max))) {
     set_error("sample_khop3: the fused first layer needs the batch's dedup insert, its scan area and one tile per workgroup");
     return GGMS_ERR_INVALID;
   }
-  uint32_t *ctl = scan_align(shared_scan ? shared_scan->words : workspace);
+  uint32_t *ctl = scan_align(shared_scan ? shared_scan->words : l.workspace);
   // tickets: the batch's next set (zeroed by the batch prologue); a private area keeps its set behind the descriptors
   uint32_t *tick = shared_scan ? take_ticket_set(shared_scan) : ctl + 8 + 2 * (tiles + 1) + 2;
   if (!tick) {
@@ -799,31 +799,30 @@ int sample_khop3_impl(GraphView g, const uint32_t *input, size_t n_max, Count n,
     return GGMS_ERR_INVALID;
   }
   if (!shared_scan)
-    GGMS_HIP(hipMemsetAsync(ctl, 0, (8 + 2 * (tiles + 1) + 2 + kTicketWords) * sizeof(uint32_t), s));
+    GGMS_HIP(hipMemsetAsync(ctl, 0, (8 + 2 * (tiles + 1) + 2 + kTicketWords) * sizeof(uint32_t), l.s));
   else if (!shared_scan->cleared)
-    GGMS_HIP(hipMemsetAsync(ctl, 0, (8 + 2 * (tiles + 1)) * sizeof(uint32_t), s));
-  const FusedScan fs{tick, reinterpret_cast<unsigned long long *>(ctl + 8), next_scan_epoch(), num_out_dev,
+    GGMS_HIP(hipMemsetAsync(ctl, 0, (8 + 2 * (tiles + 1)) * sizeof(uint32_t), l.s));
+  const FusedScan fs{tick, reinterpret_cast<unsigned long long *>(ctl + 8), next_scan_epoch(), l.num_out,
                      shared_scan ? shared_scan->status_word() : device_status_word(), scan_patience()};
-  const SrcMode sm{seed_local, src_local};
   // 64 slots up to fanout 31 (load < 0.5), else the reference's 128 (HASHTABLE_SIZE, khop3.cu:43)
-  const uint32_t set_mask = fanout < 32 ? 63u : 127u;
+  const uint32_t set_mask = l.fanout < 32 ? 63u : 127u;
   const int gpw = khop3_groups_per_wave(tiles);
   const int grid = grid_for(tiles, 1);
   // every workgroup has at most one tile: the sweep keeps four slots per lane in flight
   const uint32_t multi = tiles <= grid_cap() ? 1u : 0u;
-  const size_t lds = 128 * (size_t)fanout * sizeof(uint32_t);
+  const size_t lds = 128 * l.fanout * sizeof(uint32_t);
   const DedupInsert none{};
   const FirstLayer nofl{};
   int rc_l = GGMS_OK;
   if (first) {
-    if (gpw == 1) rc_l = launch_khop3_fused<1, true, true>(grid, lds, s, g, input, n, fanout, out_src, out_dst, sm, states, set_mask, multi, fs, *insert, *first);
-    else rc_l = launch_khop3_fused<2, true, true>(grid, lds, s, g, input, n, fanout, out_src, out_dst, sm, states, set_mask, multi, fs, *insert, *first);
+    if (gpw == 1) rc_l = launch_khop3_fused<1, true, true>(grid, lds, l, set_mask, multi, fs, *insert, *first);
+    else rc_l = launch_khop3_fused<2, true, true>(grid, lds, l, set_mask, multi, fs, *insert, *first);
   } else if (insert) {
-    if (gpw == 1) rc_l = launch_khop3_fused<1, true, false>(grid, lds, s, g, input, n, fanout, out_src, out_dst, sm, states, set_mask, multi, fs, *insert, nofl);
-    else rc_l = launch_khop3_fused<2, true, false>(grid, lds, s, g, input, n, fanout, out_src, out_dst, sm, states, set_mask, multi, fs, *insert, nofl);
+    if (gpw == 1) rc_l = launch_khop3_fused<1, true, false>(grid, lds, l, set_mask, multi, fs, *insert, nofl);
+    else rc_l = launch_khop3_fused<2, true, false>(grid, lds, l, set_mask, multi, fs, *insert, nofl);
   } else {
-    if (gpw == 1) rc_l = launch_khop3_fused<1, false, false>(grid, lds, s, g, input, n, fanout, out_src, out_dst, sm, states, set_mask, multi, fs, none, nofl);
-    else rc_l = launch_khop3_fused<2, false, false>(grid, lds, s, g, input, n, fanout, out_src, out_dst, sm, states, set_mask, multi, fs, none, nofl);
+    if (gpw == 1) rc_l = launch_khop3_fused<1, false, false>(grid, lds, l, set_mask, multi, fs, none, nofl);
+    else rc_l = launch_khop3_fused<2, false, false>(grid, lds, l, set_mask, multi, fs, none, nofl);
   }
   if (rc_l != GGMS_OK) return rc_l;
   GGMS_LAUNCH_CHECK();
@@ -847,12 +846,12 @@ size_t khop0_ws_words(size_t num_input, size_t fanout) {
 // resolve, a 256 x 1024-thread launch for the long lists, + a seed-entry launch per batch): on a stream that runs
 // beside another batch's sampler and a gather every small launch is a chain of loaded round trips
 // (profiles/r05_khop0_chain.txt).
-int sample_khop0_impl(GraphView g, const uint32_t *input, size_t n_max, Count n, uint32_t fanout, uint32_t *out_src,
-                      uint32_t *out_dst, uint64_t *num_out_dev, uint32_t *workspace, const uint32_t *seed_local,
-                      int src_local, hipStream_t s, ScanArea *shared_scan, const DedupInsert *insert,
-                      const SeedEnter *enter) {
-  const DedupInsert di = insert ? *insert : DedupInsert{}; // w == NULL: no table to enter the output into
-  uint32_t *offset = workspace;
+int sample_khop0_impl(const SampleLayer &l) {
+  const size_t n_max = l.n_max;
+  const uint32_t fanout = (uint32_t)l.fanout;
+  const SeedEnter *enter = l.enter;
+  const DedupInsert di = l.insert ? *l.insert : DedupInsert{}; // w == NULL: no table to enter the output into
+  uint32_t *offset = l.workspace;
   uint32_t *draw_base = offset + n_max;
   uint32_t *heavy_list = draw_base + n_max;
   uint32_t *heavy_count = heavy_list + n_max;
@@ -863,7 +862,7 @@ int sample_khop0_impl(GraphView g, const uint32_t *input, size_t n_max, Count n,
   const long long forced_cap = debug_knob(GGMS_DEBUG_KHOP0_DRAW_CAP);
   const size_t full_cap = khop0_draw_cap(n_max, fanout);
   const uint32_t cap = (uint32_t)(forced_cap >= 0 && (size_t)forced_cap < full_cap ? (size_t)forced_cap : full_cap);
-  const ScanArea sa = shared_scan ? *shared_scan : ScanArea{scan_scr, false};
+  const ScanArea sa = l.scan ? *l.scan : ScanArea{scan_scr, false};
   const bool one_launch = scan2_single_launch(n_max);
   if (enter && !one_launch) {
     set_error("sample_khop0: seeds can only be entered by a one-launch plan pass");
@@ -874,58 +873,58 @@ int sample_khop0_impl(GraphView g, const uint32_t *input, size_t n_max, Count n,
   if (enter) {
     store.w = enter->w;
     store.version = enter->version;
-    store.seeds = input;
+    store.seeds = l.input;
     store.n2o = enter->n2o;
     side.pro = enter->pro;
     side.has_pro = 1u;
   }
   int rc;
   if (one_launch) {
-    rc = tile_scan2(Khop0Count{g, input, fanout}, store, side, n_max, n, sa, num_out_dev, s);
+    rc = tile_scan2(Khop0Count{l.g, l.input, fanout}, store, side, n_max, l.n, sa, l.num_out, l.s);
   } else { // beyond kSinglePassTiles tiles: two plain scans, nobody to run `side`
-    GGMS_HIP(hipMemsetAsync(heavy_count, 0, sizeof(uint32_t), s));
-    rc = tile_scan2(Khop0Count{g, input, fanout}, store, NoSide{}, n_max, n, sa, num_out_dev, s);
+    GGMS_HIP(hipMemsetAsync(heavy_count, 0, sizeof(uint32_t), l.s));
+    rc = tile_scan2(Khop0Count{l.g, l.input, fanout}, store, NoSide{}, n_max, l.n, sa, l.num_out, l.s);
   }
   if (rc != GGMS_OK) return rc;
-  const SrcMode sm{seed_local, src_local};
   const bool big = fanout > kKhop0LdsFanout; // slots in the output array instead of LDS
   const size_t lds = big ? 0 : 4 * fanout * sizeof(uint32_t);
   const int grid_gen = grid_for((n_max + 63) / 64, 1);
   if (big)
-    hipLaunchKernelGGL(k_khop0_generate<true>, dim3(grid_gen), dim3(128), lds, s, g, input, n, fanout, offset, draw_base,
-                       raw, cap, out_src, out_dst, sm, heavy_count, heavy_list, di);
+    hipLaunchKernelGGL(k_khop0_generate<true>, dim3(grid_gen), dim3(128), lds, l.s, l.g, l.input, l.n, fanout, offset,
+                       draw_base, raw, cap, l.out_src, l.out_dst, l.src, heavy_count, heavy_list, di);
   else
-    hipLaunchKernelGGL(k_khop0_generate<false>, dim3(grid_gen), dim3(128), lds, s, g, input, n, fanout, offset,
-                       draw_base, raw, cap, out_src, out_dst, sm, heavy_count, heavy_list, di);
+    hipLaunchKernelGGL(k_khop0_generate<false>, dim3(grid_gen), dim3(128), lds, l.s, l.g, l.input, l.n, fanout, offset,
+                       draw_base, raw, cap, l.out_src, l.out_dst, l.src, heavy_count, heavy_list, di);
   GGMS_LAUNCH_CHECK();
   // seeds per 256-thread block of the resolve kernel: 16 lanes each, as many as 48 KB of LDS slots allow
   const uint32_t groups = big ? 16u : std::max<uint32_t>(1, std::min<uint32_t>(16, (48u << 10) / (4u * fanout)));
   if (big)
-    hipLaunchKernelGGL(k_khop0_resolve<true>, dim3(grid_for(n_max, groups)), dim3(kBlock), 0, s, g, input, n, fanout,
-                       offset, draw_base, raw, cap, out_src, out_dst, sm, heavy_count, heavy_list, groups, di);
+    hipLaunchKernelGGL(k_khop0_resolve<true>, dim3(grid_for(n_max, groups)), dim3(kBlock), 0, l.s, l.g, l.input, l.n,
+                       fanout, offset, draw_base, raw, cap, l.out_src, l.out_dst, l.src, heavy_count, heavy_list, groups,
+                       di);
   else
     hipLaunchKernelGGL(k_khop0_resolve<false>, dim3(grid_for(n_max, groups)), dim3(kBlock),
-                       groups * fanout * sizeof(uint32_t), s, g, input, n, fanout, offset, draw_base, raw, cap, out_src,
-                       out_dst, sm, heavy_count, heavy_list, groups, di);
+                       groups * fanout * sizeof(uint32_t), l.s, l.g, l.input, l.n, fanout, offset, draw_base, raw, cap,
+                       l.out_src, l.out_dst, l.src, heavy_count, heavy_list, groups, di);
   GGMS_LAUNCH_CHECK();
   return GGMS_OK;
 }
 
-int sample_khop2_impl(const uint32_t *indptr, uint32_t *indices, size_t num_node, const uint32_t *input, size_t n_max,
-                      Count n, uint32_t fanout, uint32_t *out_src, uint32_t *out_dst, uint64_t *num_out_dev,
-                      uint32_t *states, uint32_t *workspace, const uint32_t *seed_local, int src_local, hipStream_t s,
-                      ScanArea *shared_scan) {
-  (void)num_node;
-  uint32_t *offset = workspace;
+// the CSR comes from l.graph, not l.g: the draws permute graph->indices in place (dist_loops.cc:217-224)
+int sample_khop2_impl(const SampleLayer &l) {
+  const size_t n_max = l.n_max;
+  const uint32_t fanout = (uint32_t)l.fanout;
+  uint32_t *offset = l.workspace;
+  uint32_t *indices = const_cast<uint32_t *>(l.graph->indices);
   GraphView g{};
-  g.indptr = indptr;
+  g.indptr = l.graph->indptr;
   g.indices = indices;
-  const ScanArea sa = shared_scan ? *shared_scan : ScanArea{offset + n_max, false};
-  int rc = tile_scan(SeedCount{g, input, fanout}, StoreOffset{offset}, n_max, n, sa, nullptr, nullptr,
-                     num_out_dev, s);
+  const ScanArea sa = l.scan ? *l.scan : ScanArea{offset + n_max, false};
+  int rc = tile_scan(SeedCount{g, l.input, fanout}, StoreOffset{offset}, n_max, l.n, sa, nullptr, nullptr, l.num_out,
+                     l.s);
   if (rc != GGMS_OK) return rc;
-  hipLaunchKernelGGL(k_sample_khop2, dim3(grid_for(4 * ((n_max + 1023) / 1024), 1)), dim3(kWave), 0, s, indptr, indices,
-                     input, n, fanout, offset, out_src, out_dst, states, SrcMode{seed_local, src_local});
+  hipLaunchKernelGGL(k_sample_khop2, dim3(grid_for(4 * ((n_max + 1023) / 1024), 1)), dim3(kWave), 0, l.s, g.indptr,
+                     indices, l.input, l.n, fanout, offset, l.out_src, l.out_dst, l.states, l.src);
   GGMS_LAUNCH_CHECK();
   return GGMS_OK;
 }
@@ -937,67 +936,31 @@ using namespace ggms;
 extern "C" {
 
 size_t ggms_sample_workspace_bytes(int sample_type, size_t num_input, size_t fanout) {
-  if (sample_type == GGMS_KHOP0) return khop0_ws_words(num_input, fanout) * sizeof(uint32_t);
-  return sample_ws_words(num_input) * sizeof(uint32_t);
+  return layer_ws_words(sample_type, num_input, fanout, 0, 0) * sizeof(uint32_t);
 }
 
 int ggms_sample_khop3(const ggms_graph_t *graph, const ggms_id_t *input, size_t num_input, size_t fanout,
                       ggms_id_t *out_src, ggms_id_t *out_dst, uint64_t *num_out_dev, void *states,
                       size_t num_states, void *workspace, size_t workspace_bytes, ggms_stream_t stream) {
-  GGMS_CHECK_ARG(graph && num_out_dev);
-  GGMS_CHECK_ARG(fanout > 0 && fanout < 128); // khop3.cu:85
-  hipStream_t s = to_stream(stream);
-  if (num_input == 0) {
-    GGMS_HIP(hipMemsetAsync(num_out_dev, 0, sizeof(uint64_t), s));
-    return GGMS_OK;
-  }
-  GGMS_CHECK_ARG(input && out_src && out_dst && states && workspace);
-  GGMS_CHECK_ARG(workspace_bytes >= ggms_sample_workspace_bytes(GGMS_KHOP3, num_input, fanout));
-  GGMS_CHECK_ARG((uint64_t)num_input * fanout < (1ull << 32));
-  GGMS_CHECK_ARG((num_input + 127) / 128 * 8 <= num_states); // assert(i < num_random_states), khop3.cu:89
-  GraphView gv;
-  if (!view_of(graph, gv)) return GGMS_ERR_INVALID;
-  return sample_khop3_impl(gv, input, num_input, count_of(num_input), (uint32_t)fanout, out_src, out_dst,
-                           num_out_dev, (uint32_t *)states, (uint32_t *)workspace, nullptr, 0, s);
+  return sample_leaf(GGMS_KHOP3, SampleLayer{graph, input, num_input, fanout, out_src, out_dst, num_out_dev,
+                                             (uint32_t *)states, (uint32_t *)workspace, to_stream(stream)},
+                     num_states, workspace_bytes);
 }
 
 int ggms_sample_khop0(const ggms_graph_t *graph, const ggms_id_t *input, size_t num_input, size_t fanout,
                       ggms_id_t *out_src, ggms_id_t *out_dst, uint64_t *num_out_dev, void *workspace,
                       size_t workspace_bytes, ggms_stream_t stream) {
-  GGMS_CHECK_ARG(graph && num_out_dev);
-  GGMS_CHECK_ARG(fanout > 0);
-  hipStream_t s = to_stream(stream);
-  if (num_input == 0) {
-    GGMS_HIP(hipMemsetAsync(num_out_dev, 0, sizeof(uint64_t), s));
-    return GGMS_OK;
-  }
-  GGMS_CHECK_ARG(input && out_src && out_dst && workspace);
-  GGMS_CHECK_ARG(workspace_bytes >= ggms_sample_workspace_bytes(GGMS_KHOP0, num_input, fanout));
-  GGMS_CHECK_ARG((uint64_t)num_input * fanout < (1ull << 32));
-  GraphView gv;
-  if (!view_of(graph, gv)) return GGMS_ERR_INVALID;
-  return sample_khop0_impl(gv, input, num_input, count_of(num_input), (uint32_t)fanout, out_src, out_dst,
-                           num_out_dev, (uint32_t *)workspace, nullptr, 0, s);
+  return sample_leaf(GGMS_KHOP0, SampleLayer{graph, input, num_input, fanout, out_src, out_dst, num_out_dev, nullptr,
+                                             (uint32_t *)workspace, to_stream(stream)},
+                     0, workspace_bytes);
 }
 
 int ggms_sample_khop2(const ggms_graph_t *graph, const ggms_id_t *input, size_t num_input, size_t fanout,
                       ggms_id_t *out_src, ggms_id_t *out_dst, uint64_t *num_out_dev, void *states,
                       size_t num_states, void *workspace, size_t workspace_bytes, ggms_stream_t stream) {
-  GGMS_CHECK_ARG(graph && num_out_dev);
-  GGMS_CHECK_ARG(fanout > 0);
-  GGMS_CHECK_ARG(graph->num_part == 0); // CHECK(use_dist_graph == false), dist_loops.cc:219
-  hipStream_t s = to_stream(stream);
-  if (num_input == 0) {
-    GGMS_HIP(hipMemsetAsync(num_out_dev, 0, sizeof(uint64_t), s));
-    return GGMS_OK;
-  }
-  GGMS_CHECK_ARG(input && out_src && out_dst && states && workspace && graph->indptr && graph->indices);
-  GGMS_CHECK_ARG(workspace_bytes >= ggms_sample_workspace_bytes(GGMS_KHOP2, num_input, fanout));
-  GGMS_CHECK_ARG((uint64_t)num_input * fanout < (1ull << 32));
-  GGMS_CHECK_ARG((num_input + 1023) / 1024 * 256 <= num_states); // assert(i < num_random_states), khop2.cu:57
-  return sample_khop2_impl(graph->indptr, const_cast<uint32_t *>(graph->indices), graph->num_node, input, num_input,
-                           count_of(num_input), (uint32_t)fanout, out_src, out_dst, num_out_dev, (uint32_t *)states,
-                           (uint32_t *)workspace, nullptr, 0, s);
+  return sample_leaf(GGMS_KHOP2, SampleLayer{graph, input, num_input, fanout, out_src, out_dst, num_out_dev,
+                                             (uint32_t *)states, (uint32_t *)workspace, to_stream(stream)},
+                     num_states, workspace_bytes);
 }
 
 } // extern "C"

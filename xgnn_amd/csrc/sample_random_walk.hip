@@ -293,16 +293,19 @@ static int launch_topk_emit(int grid, size_t lds, hipStream_t s, uint32_t *tmp_s
 
 // shared_scan: the batch's scan area (cleared by the batch prologue); else the workspace holds a private one that
 // is cleared here.  insert (direct dedup table): the visited nodes are entered into the table on the way out.
-int sample_random_walk_impl(GraphView g, const uint32_t *input, size_t n_max, Count n, uint32_t walk_length,
-                            double restart_prob, uint32_t num_walk, uint32_t K, uint32_t *out_src, uint32_t *out_dst,
-                            uint32_t *out_data, uint64_t *num_out_dev, uint32_t *states, uint32_t *workspace,
-                            const uint32_t *seed_local, int src_local, hipStream_t s, ScanArea *shared_scan,
-                            const DedupInsert *insert) {
+int sample_random_walk_impl(const SampleLayer &l) {
+  const size_t n_max = l.n_max;
+  const Count n = l.n;
+  const uint32_t walk_length = (uint32_t)l.walk_length, num_walk = (uint32_t)l.num_walk, K = (uint32_t)l.fanout;
+  const hipStream_t s = l.s;
+  ScanArea *shared_scan = l.scan;
+  const DedupInsert *insert = l.insert;
   const uint32_t per = walk_length * num_walk;
-  uint32_t *w = workspace;
+  uint32_t *w = l.workspace;
   uint32_t *tmp_src = w; w += n_max * per;
   uint32_t *tmp_dst = w; w += n_max * per;
-  int rc = random_walk_raw_impl(g, input, n_max, n, walk_length, restart_prob, num_walk, tmp_src, tmp_dst, states, s);
+  int rc = random_walk_raw_impl(l.g, l.input, n_max, n, walk_length, l.restart_prob, num_walk, tmp_src, tmp_dst,
+                                l.states, s);
   if (rc != GGMS_OK) return rc;
   const uint32_t Kc = K < per ? K : per;
   const uint32_t T = per > kLdsVisits ? 64u : walk_tile(per, Kc);
@@ -318,9 +321,8 @@ int sample_random_walk_impl(GraphView g, const uint32_t *input, size_t n_max, Co
     GGMS_HIP(hipMemsetAsync(ctl, 0, (8 + 2 * (tiles + 1) + 2 + kTicketWords) * sizeof(uint32_t), s));
   else if (!shared_scan->cleared)
     GGMS_HIP(hipMemsetAsync(ctl, 0, (8 + 2 * (tiles + 1)) * sizeof(uint32_t), s));
-  const FusedScan fs{tick, reinterpret_cast<unsigned long long *>(ctl + 8), next_scan_epoch(), num_out_dev,
+  const FusedScan fs{tick, reinterpret_cast<unsigned long long *>(ctl + 8), next_scan_epoch(), l.num_out,
                      shared_scan ? shared_scan->status_word() : device_status_word(), scan_patience()};
-  const SrcMode sm{seed_local, src_local};
   const bool spill = per > kLdsVisits;
   const size_t lds = spill ? 0 : 2 * (size_t)(per + Kc) * T * sizeof(uint32_t);
   const int grid = grid_for(tiles, 1);
@@ -329,11 +331,11 @@ int sample_random_walk_impl(GraphView g, const uint32_t *input, size_t n_max, Co
 #define GGMS_TOPK(TT, SP)                                                                                          \
   do {                                                                                                             \
     if (insert)                                                                                                    \
-      rc_l = launch_topk_emit<TT, true, SP>(grid, lds, s, tmp_src, tmp_dst, n, (uint64_t)n_max, per, K, Kc, input, sm,    \
-                                     out_src, out_dst, out_data, fs, *insert);                                     \
+      rc_l = launch_topk_emit<TT, true, SP>(grid, lds, s, tmp_src, tmp_dst, n, (uint64_t)n_max, per, K, Kc, l.input,  \
+                                            l.src, l.out_src, l.out_dst, l.out_data, fs, *insert);                 \
     else                                                                                                           \
-      rc_l = launch_topk_emit<TT, false, SP>(grid, lds, s, tmp_src, tmp_dst, n, (uint64_t)n_max, per, K, Kc, input, sm,   \
-                                      out_src, out_dst, out_data, fs, none);                                       \
+      rc_l = launch_topk_emit<TT, false, SP>(grid, lds, s, tmp_src, tmp_dst, n, (uint64_t)n_max, per, K, Kc, l.input, \
+                                             l.src, l.out_src, l.out_dst, l.out_data, fs, none);                   \
   } while (0)
   if (spill) GGMS_TOPK(64, true);
   else if (T == 256) GGMS_TOPK(256, false);
@@ -367,21 +369,14 @@ int ggms_sample_random_walk(const ggms_graph_t *graph, const ggms_id_t *input, s
                             double restart_prob, size_t num_walk, size_t K, ggms_id_t *out_src, ggms_id_t *out_dst,
                             ggms_id_t *out_data, uint64_t *num_out_dev, void *states, size_t num_states,
                             void *workspace, size_t workspace_bytes, ggms_stream_t stream) {
-  GGMS_CHECK_ARG(graph && num_out_dev && walk_length > 0 && num_walk > 0 && K > 0);
   GGMS_CHECK_ARG(walk_length * num_walk < (1ull << 31));
-  hipStream_t s = to_stream(stream);
-  if (num_input == 0) {
-    GGMS_HIP(hipMemsetAsync(num_out_dev, 0, sizeof(uint64_t), s));
-    return GGMS_OK;
-  }
-  GGMS_CHECK_ARG(input && out_src && out_dst && out_data && states && workspace);
-  GGMS_CHECK_ARG(workspace_bytes >= ggms_sample_random_walk_workspace_bytes(num_input, walk_length, num_walk, K));
-  GGMS_CHECK_ARG(ggms_random_walk_num_states(num_input, num_walk) <= num_states); // assert(thread_id < num_random_states)
-  GraphView gv;
-  if (!view_of(graph, gv)) return GGMS_ERR_INVALID;
-  return sample_random_walk_impl(gv, input, num_input, count_of(num_input), (uint32_t)walk_length,
-                                 restart_prob, (uint32_t)num_walk, (uint32_t)K, out_src, out_dst, out_data, num_out_dev,
-                                 (uint32_t *)states, (uint32_t *)workspace, nullptr, 0, s, nullptr, nullptr);
+  SampleLayer l{graph, input, num_input, K, out_src, out_dst, num_out_dev, (uint32_t *)states, (uint32_t *)workspace,
+                to_stream(stream)};
+  l.out_data = out_data;
+  l.walk_length = walk_length;
+  l.num_walk = num_walk;
+  l.restart_prob = restart_prob;
+  return sample_leaf(GGMS_RANDOM_WALK, l, num_states, workspace_bytes);
 }
 
 } // extern "C"

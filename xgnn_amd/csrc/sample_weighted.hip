@@ -27,8 +27,6 @@
 
 namespace ggms {
 
-constexpr uint64_t kWeightedMaxThreads = 512 * 1024; // Constant::kWeightedKHopMaxThreads, constant.h:72
-
 // per-seed edge count min(deg, fanout) and its scanned offset (hash-dedup sampler: compact COO written directly)
 struct MinDegFanout {
   const uint32_t *indptr, *input;
@@ -149,12 +147,16 @@ size_t weighted_ws_words(size_t num_input, size_t fanout) {
   return num_input * fanout + 4 * num_input + sort_scratch_words(num_input) + tile_scan_words(num_input * fanout) + 64;
 }
 
-int sample_weighted_impl(const uint32_t *indptr, const uint32_t *indices, const float *prob, const uint32_t *alias,
-                         const uint32_t *input, size_t n_max, Count n, uint32_t fanout, uint32_t *out_src,
-                         uint32_t *out_dst, uint64_t *num_out_dev, uint32_t *states, uint32_t *workspace,
-                         const uint32_t *seed_local, int src_local, hipStream_t s, ScanArea *shared_scan,
-                         uint32_t num_node, const DedupInsert *insert) {
-  uint32_t *w = workspace;
+// type: khop1 (uniform, no table), weighted_khop (alias method) or weighted_khop_prefix (prefix sums)
+int sample_weighted_impl(const SampleLayer &l, int type) {
+  const uint32_t *indptr = l.graph->indptr, *indices = l.graph->indices, *input = l.input;
+  const float *prob = type == GGMS_KHOP1 ? nullptr : l.prob;
+  const uint32_t *alias = type == GGMS_WEIGHTED_KHOP ? l.alias : nullptr;
+  const size_t n_max = l.n_max;
+  const Count n = l.n;
+  const uint32_t fanout = (uint32_t)l.fanout;
+  const hipStream_t s = l.s;
+  uint32_t *w = l.workspace;
   uint32_t *tmp_dst = w;  w += n_max * fanout;
   uint32_t *k0 = w;       w += n_max;
   uint32_t *v0 = w;       w += n_max;
@@ -167,27 +169,28 @@ int sample_weighted_impl(const uint32_t *indptr, const uint32_t *indices, const 
   const dim3 draw_grid((unsigned)((threads + kBlock - 1) / kBlock));
   if (prob && alias)
     hipLaunchKernelGGL(k_weighted_draw<1>, draw_grid, dim3(kBlock), 0, s, indptr, indices, prob, alias, input, n, fanout,
-                       tmp_dst, states);
+                       tmp_dst, l.states);
   else if (prob) // prefix sums
     hipLaunchKernelGGL(k_weighted_draw<2>, draw_grid, dim3(kBlock), 0, s, indptr, indices, prob, alias, input, n, fanout,
-                       tmp_dst, states);
+                       tmp_dst, l.states);
   else // khop1: uniform with replacement
     hipLaunchKernelGGL(k_weighted_draw<0>, draw_grid, dim3(kBlock), 0, s, indptr, indices, prob, alias, input, n, fanout,
-                       tmp_dst, states);
+                       tmp_dst, l.states);
   GGMS_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_weighted_keys, dim3(grid_for(n_max, kBlock)), dim3(kBlock), 0, s, indptr, input, n, k0, v0);
   GGMS_LAUNCH_CHECK();
   // keys are node ids (< num_node) or kEmptyKey: the sort only covers the bits an id can have set, and the empty
   // key (all ones) still sorts behind every id (radix_plan)
   bool in_second = false;
-  int rc = radix_sort_pairs(k0, v0, k1, v1, n_max, n, sort_scr, s, num_node, &in_second);
+  int rc = radix_sort_pairs(k0, v0, k1, v1, n_max, n, sort_scr, s, l.graph->num_node, &in_second);
   if (rc != GGMS_OK) return rc;
   const SortedStream ss{in_second ? k1 : k0, in_second ? v1 : v0, tmp_dst, fanout, n};
   // element count of the compaction = n * fanout with n possibly on the device: a Count cannot multiply,
   // so KeepFlag bounds itself by ss.n and the scan runs over the upper bound
-  const ScanArea sa = shared_scan ? *shared_scan : ScanArea{scan_scr, false};
-  return tile_scan(KeepFlag{ss}, KeepEmit{ss, out_src, out_dst, seed_local, src_local, insert ? *insert : DedupInsert{}}, task_max,
-                   count_of(task_max), sa, nullptr, nullptr, num_out_dev, s);
+  const ScanArea sa = l.scan ? *l.scan : ScanArea{scan_scr, false};
+  return tile_scan(KeepFlag{ss}, KeepEmit{ss, l.out_src, l.out_dst, l.src.seed_local, l.src.local,
+                                          l.insert ? *l.insert : DedupInsert{}},
+                   task_max, count_of(task_max), sa, nullptr, nullptr, l.num_out, s);
 }
 
 // ---- weighted_khop_hash_dedup --------------------------------------------------------------------------
@@ -208,7 +211,6 @@ int sample_weighted_impl(const uint32_t *indptr, const uint32_t *indices, const 
 // through the reference's insert one after the other in try order, so that accepted picks, their order and the
 // table's layout are exactly the sequential ones.  If the seed completes at try t*, the generator is put back to just
 // after it.
-constexpr uint32_t kDedupSlots = 50;       // hash_dedup.cu:42
 constexpr uint32_t kDedupMaxTries = 65536; // the reference spins forever on a list without `fanout` distinct ids
 constexpr uint32_t kDedupMaxProbes = 64;   // ... and on a full table (a seed id met twice by one stream, fanout >= 25)
 
@@ -401,19 +403,15 @@ __global__ __launch_bounds__(kWave) void k_weighted_hash_dedup(const uint32_t *_
   }
 }
 
-int sample_weighted_hash_dedup_impl(const uint32_t *indptr, const uint32_t *indices, const float *prob,
-                                    const uint32_t *alias, const uint32_t *input, size_t n_max, Count n,
-                                    uint32_t fanout, uint32_t *out_src, uint32_t *out_dst, uint64_t *num_out_dev,
-                                    uint32_t *states, uint32_t *workspace, const uint32_t *seed_local, int src_local,
-                                    hipStream_t s, ScanArea *shared_scan, const DedupInsert *insert) {
-  uint32_t *offset = workspace;
-  const ScanArea sa = shared_scan ? *shared_scan : ScanArea{offset + n_max, false};
-  int rc = tile_scan(MinDegFanout{indptr, input, fanout}, StoreWord{offset}, n_max, n, sa, nullptr, nullptr,
-                     num_out_dev, s);
+int sample_weighted_hash_dedup_impl(const SampleLayer &l) {
+  const uint32_t fanout = (uint32_t)l.fanout;
+  uint32_t *offset = l.workspace;
+  const ScanArea sa = l.scan ? *l.scan : ScanArea{offset + l.n_max, false};
+  int rc = tile_scan(MinDegFanout{l.graph->indptr, l.input, fanout}, StoreWord{offset}, l.n_max, l.n, sa, nullptr,
+                     nullptr, l.num_out, l.s);
   if (rc != GGMS_OK) return rc;
-  const SrcMode sm{seed_local, src_local};
-  const DedupInsert di = insert ? *insert : DedupInsert{};
-  const size_t blocks = (n_max + 1023) / 1024; // reference blocks of 256 streams
+  const DedupInsert di = l.insert ? *l.insert : DedupInsert{};
+  const size_t blocks = (l.n_max + 1023) / 1024; // reference blocks of 256 streams
   // G = lanes that share a stream: 16; tries per round = G R with R = 1.  "About 1.5 x fanout tries per round, so that
   // an ordinary seed is done in one round trip" (R = 4 at fanout 25) was the first choice and measured WORSE: 128
   // generator steps per lane and round and 120 VGPRs (the large products layer's 5312 waves did not fit the chip at
@@ -423,8 +421,8 @@ int sample_weighted_hash_dedup_impl(const uint32_t *indptr, const uint32_t *indi
   // for the slowest of 16 streams instead of 4), as were 8 and 32 lanes per stream
   // (profiles/r03_ab_hash_dedup_lanes_per_stream.txt).  Only <16, 1> is built.
   hipLaunchKernelGGL((k_weighted_hash_dedup<16, 1>), dim3((unsigned)std::min<size_t>((256 / (64 / 16)) * blocks, 8192)),
-                     dim3(kWave), 0, s, indptr, indices, prob, alias, input, n, fanout, offset, out_src, out_dst, states,
-                     sm, di);
+                     dim3(kWave), 0, l.s, l.graph->indptr, l.graph->indices, l.prob, l.alias, l.input, l.n, fanout, offset,
+                     l.out_src, l.out_dst, l.states, l.src, di);
   GGMS_LAUNCH_CHECK();
   return GGMS_OK;
 }
@@ -443,68 +441,29 @@ int ggms_sample_weighted_khop(const ggms_graph_t *graph, const float *prob_table
                               const ggms_id_t *input, size_t num_input, size_t fanout, ggms_id_t *out_src,
                               ggms_id_t *out_dst, uint64_t *num_out_dev, void *states, size_t num_states,
                               void *workspace, size_t workspace_bytes, ggms_stream_t stream) {
-  GGMS_CHECK_ARG(graph && num_out_dev && fanout > 0);
-  GGMS_CHECK_ARG(graph->num_part == 0); // "this algorithm not support DistGraph engine", dist_loops.cc:171-172
-  hipStream_t s = to_stream(stream);
-  if (num_input == 0) {
-    GGMS_HIP(hipMemsetAsync(num_out_dev, 0, sizeof(uint64_t), s));
-    return GGMS_OK;
-  }
-  GGMS_CHECK_ARG(prob_table && alias_table && input && out_src && out_dst && states && workspace);
-  GGMS_CHECK_ARG((uint64_t)num_input * fanout < (1ull << 32));
-  GGMS_CHECK_ARG(workspace_bytes >= ggms_sample_weighted_workspace_bytes(num_input, fanout));
-  const uint64_t tasks = (uint64_t)num_input * fanout;
-  const uint64_t threads = tasks < kWeightedMaxThreads ? tasks : kWeightedMaxThreads;
-  const uint64_t span = (threads + 255) / 256 * 256;
-  GGMS_CHECK_ARG((span < tasks ? span : tasks) <= num_states); // assert(thread_id < num_random_states), :52
-  return sample_weighted_impl(graph->indptr, graph->indices, prob_table, alias_table, input, num_input,
-                              count_of(num_input), (uint32_t)fanout, out_src, out_dst, num_out_dev, (uint32_t *)states,
-                              (uint32_t *)workspace, nullptr, 0, s, nullptr, graph->num_node);
+  SampleLayer l{graph, input, num_input, fanout, out_src, out_dst, num_out_dev, (uint32_t *)states,
+                (uint32_t *)workspace, to_stream(stream)};
+  l.prob = prob_table;
+  l.alias = alias_table;
+  return sample_leaf(GGMS_WEIGHTED_KHOP, l, num_states, workspace_bytes);
 }
 
 int ggms_sample_khop1(const ggms_graph_t *graph, const ggms_id_t *input, size_t num_input, size_t fanout,
                       ggms_id_t *out_src, ggms_id_t *out_dst, uint64_t *num_out_dev, void *states,
                       size_t num_states, void *workspace, size_t workspace_bytes, ggms_stream_t stream) {
-  GGMS_CHECK_ARG(graph && num_out_dev && fanout > 0);
-  GGMS_CHECK_ARG(graph->num_part == 0); // "this algorithm not support DistGraph engine", dist_loops.cc:167-168
-  hipStream_t s = to_stream(stream);
-  if (num_input == 0) {
-    GGMS_HIP(hipMemsetAsync(num_out_dev, 0, sizeof(uint64_t), s));
-    return GGMS_OK;
-  }
-  GGMS_CHECK_ARG(input && out_src && out_dst && states && workspace);
-  GGMS_CHECK_ARG((uint64_t)num_input * fanout < (1ull << 32));
-  GGMS_CHECK_ARG(workspace_bytes >= ggms_sample_weighted_workspace_bytes(num_input, fanout));
-  const uint64_t tasks = (uint64_t)num_input * fanout;
-  const uint64_t threads = tasks < kWeightedMaxThreads ? tasks : kWeightedMaxThreads;
-  const uint64_t span = (threads + 255) / 256 * 256;
-  GGMS_CHECK_ARG((span < tasks ? span : tasks) <= num_states); // assert(thread_id < num_random_states), khop1.cu:51
-  return sample_weighted_impl(graph->indptr, graph->indices, nullptr, nullptr, input, num_input, count_of(num_input),
-                              (uint32_t)fanout, out_src, out_dst, num_out_dev, (uint32_t *)states,
-                              (uint32_t *)workspace, nullptr, 0, s, nullptr, graph->num_node);
+  return sample_leaf(GGMS_KHOP1, SampleLayer{graph, input, num_input, fanout, out_src, out_dst, num_out_dev,
+                                             (uint32_t *)states, (uint32_t *)workspace, to_stream(stream)},
+                     num_states, workspace_bytes);
 }
 
 int ggms_sample_weighted_khop_prefix(const ggms_graph_t *graph, const float *prob_prefix_table, const ggms_id_t *input,
                                      size_t num_input, size_t fanout, ggms_id_t *out_src, ggms_id_t *out_dst,
                                      uint64_t *num_out_dev, void *states, size_t num_states, void *workspace,
                                      size_t workspace_bytes, ggms_stream_t stream) {
-  GGMS_CHECK_ARG(graph && num_out_dev && fanout > 0);
-  GGMS_CHECK_ARG(graph->num_part == 0); // "this algorithm not support DistGraph engine", dist_loops.cc:209-210
-  hipStream_t s = to_stream(stream);
-  if (num_input == 0) {
-    GGMS_HIP(hipMemsetAsync(num_out_dev, 0, sizeof(uint64_t), s));
-    return GGMS_OK;
-  }
-  GGMS_CHECK_ARG(prob_prefix_table && input && out_src && out_dst && states && workspace);
-  GGMS_CHECK_ARG((uint64_t)num_input * fanout < (1ull << 32));
-  GGMS_CHECK_ARG(workspace_bytes >= ggms_sample_weighted_workspace_bytes(num_input, fanout));
-  const uint64_t tasks = (uint64_t)num_input * fanout;
-  const uint64_t threads = tasks < kWeightedMaxThreads ? tasks : kWeightedMaxThreads;
-  const uint64_t span = (threads + 255) / 256 * 256;
-  GGMS_CHECK_ARG((span < tasks ? span : tasks) <= num_states); // prefix.cu:50
-  return sample_weighted_impl(graph->indptr, graph->indices, prob_prefix_table, nullptr, input, num_input,
-                              count_of(num_input), (uint32_t)fanout, out_src, out_dst, num_out_dev, (uint32_t *)states,
-                              (uint32_t *)workspace, nullptr, 0, s, nullptr, graph->num_node);
+  SampleLayer l{graph, input, num_input, fanout, out_src, out_dst, num_out_dev, (uint32_t *)states,
+                (uint32_t *)workspace, to_stream(stream)};
+  l.prob = prob_prefix_table;
+  return sample_leaf(GGMS_WEIGHTED_KHOP_PREFIX, l, num_states, workspace_bytes);
 }
 
 int ggms_sample_weighted_khop_hash_dedup(const ggms_graph_t *graph, const float *prob_table,
@@ -512,20 +471,11 @@ int ggms_sample_weighted_khop_hash_dedup(const ggms_graph_t *graph, const float 
                                          size_t fanout, ggms_id_t *out_src, ggms_id_t *out_dst, uint64_t *num_out_dev,
                                          void *states, size_t num_states, void *workspace, size_t workspace_bytes,
                                          ggms_stream_t stream) {
-  GGMS_CHECK_ARG(graph && num_out_dev && fanout > 0 && fanout < kDedupSlots);
-  GGMS_CHECK_ARG(graph->num_part == 0); // dist_loops.cc:227-228
-  hipStream_t s = to_stream(stream);
-  if (num_input == 0) {
-    GGMS_HIP(hipMemsetAsync(num_out_dev, 0, sizeof(uint64_t), s));
-    return GGMS_OK;
-  }
-  GGMS_CHECK_ARG(prob_table && alias_table && input && out_src && out_dst && states && workspace);
-  GGMS_CHECK_ARG((uint64_t)num_input * fanout < (1ull << 32));
-  GGMS_CHECK_ARG(workspace_bytes >= ggms_sample_workspace_bytes(GGMS_WEIGHTED_KHOP_HASH_DEDUP, num_input, fanout));
-  GGMS_CHECK_ARG((num_input + 1023) / 1024 * 256 <= num_states); // assert(i < num_random_states), hash_dedup.cu:70
-  return sample_weighted_hash_dedup_impl(graph->indptr, graph->indices, prob_table, alias_table, input, num_input,
-                                         count_of(num_input), (uint32_t)fanout, out_src, out_dst, num_out_dev,
-                                         (uint32_t *)states, (uint32_t *)workspace, nullptr, 0, s, nullptr, nullptr);
+  SampleLayer l{graph, input, num_input, fanout, out_src, out_dst, num_out_dev, (uint32_t *)states,
+                (uint32_t *)workspace, to_stream(stream)};
+  l.prob = prob_table;
+  l.alias = alias_table;
+  return sample_leaf(GGMS_WEIGHTED_KHOP_HASH_DEDUP, l, num_states, workspace_bytes);
 }
 
 } // extern "C"

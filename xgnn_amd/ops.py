@@ -97,7 +97,9 @@ def _workspace(nbytes, device):
     return torch.empty(max(16, (nbytes + 3) // 4), dtype=torch.int32, device=device)
 
 
-def _sample(fn_name, sample_type, graph, inp, fanout, states):
+def _sample(fn_name, sample_type, graph, inp, fanout, states, *tables):
+    """One leaf sampler call: (out_src, out_dst, num_out[1] on device).  tables: the device arrays the entry point takes
+    between the graph and the input; states=None: a sampler without an RNG pool (khop0)."""
     _require_gpu(inp)
     _i32(inp)
     n = inp.numel()
@@ -105,16 +107,10 @@ def _sample(fn_name, sample_type, graph, inp, fanout, states):
     out_src = torch.empty(max(1, n * fanout), dtype=torch.int32, device=dev)
     out_dst = torch.empty(max(1, n * fanout), dtype=torch.int32, device=dev)
     num_out = torch.zeros(1, dtype=torch.int64, device=dev)
-    wsb = lib().ggms_sample_workspace_bytes(sample_type, n, fanout)
-    ws = _workspace(wsb, dev)
-    if fn_name in ("ggms_sample_khop3", "ggms_sample_khop2"):
-        rc = getattr(lib(), fn_name)(C.byref(graph.c), _ptr(inp), n, fanout, _ptr(out_src), _ptr(out_dst),
-                                     _ptr(num_out), _ptr(states), states.shape[0], _ptr(ws), ws.numel() * 4,
-                                     _stream())
-    else:
-        rc = lib().ggms_sample_khop0(C.byref(graph.c), _ptr(inp), n, fanout, _ptr(out_src), _ptr(out_dst),
-                                     _ptr(num_out), _ptr(ws), ws.numel() * 4, _stream())
-    check(rc, fn_name)
+    ws = _workspace(lib().ggms_sample_workspace_bytes(sample_type, n, fanout), dev)
+    rng = (_ptr(states), states.shape[0]) if states is not None else ()
+    check(getattr(lib(), fn_name)(C.byref(graph.c), *map(_ptr, tables), _ptr(inp), n, fanout, _ptr(out_src),
+                                  _ptr(out_dst), _ptr(num_out), *rng, _ptr(ws), ws.numel() * 4, _stream()), fn_name)
     return out_src, out_dst, num_out
 
 
@@ -130,52 +126,19 @@ def sample_khop0(graph, inp, fanout):
 
 def sample_weighted_khop_prefix(graph, prob_prefix_table, inp, fanout, states):
     """GPUSampleWeightedKHopPrefix (cuda_sampling_weighted_khop_prefix.cu:145-246)."""
-    _require_gpu(inp)
-    _i32(inp)
-    n = inp.numel()
-    dev = inp.device
-    out_src = torch.empty(max(1, n * fanout), dtype=torch.int32, device=dev)
-    out_dst = torch.empty(max(1, n * fanout), dtype=torch.int32, device=dev)
-    num_out = torch.zeros(1, dtype=torch.int64, device=dev)
-    ws = _workspace(lib().ggms_sample_weighted_workspace_bytes(n, fanout), dev)
-    check(lib().ggms_sample_weighted_khop_prefix(C.byref(graph.c), _ptr(prob_prefix_table), _ptr(inp), n, fanout,
-                                                 _ptr(out_src), _ptr(out_dst), _ptr(num_out), _ptr(states),
-                                                 states.shape[0], _ptr(ws), ws.numel() * 4, _stream()),
-          "ggms_sample_weighted_khop_prefix")
-    return out_src, out_dst, num_out
+    return _sample("ggms_sample_weighted_khop_prefix", WEIGHTED_KHOP_PREFIX, graph, inp, fanout, states,
+                   prob_prefix_table)
 
 
 def sample_weighted_khop_hash_dedup(graph, prob_table, alias_table, inp, fanout, states):
     """GPUSampleWeightedKHopHashDedup (cuda_sampling_weighted_khop_hash_dedup.cu:196-283)."""
-    _require_gpu(inp)
-    _i32(inp)
-    n = inp.numel()
-    dev = inp.device
-    out_src = torch.empty(max(1, n * fanout), dtype=torch.int32, device=dev)
-    out_dst = torch.empty(max(1, n * fanout), dtype=torch.int32, device=dev)
-    num_out = torch.zeros(1, dtype=torch.int64, device=dev)
-    ws = _workspace(lib().ggms_sample_workspace_bytes(WEIGHTED_KHOP_HASH_DEDUP, n, fanout), dev)
-    check(lib().ggms_sample_weighted_khop_hash_dedup(C.byref(graph.c), _ptr(prob_table), _ptr(alias_table), _ptr(inp),
-                                                     n, fanout, _ptr(out_src), _ptr(out_dst), _ptr(num_out),
-                                                     _ptr(states), states.shape[0], _ptr(ws), ws.numel() * 4,
-                                                     _stream()), "ggms_sample_weighted_khop_hash_dedup")
-    return out_src, out_dst, num_out
+    return _sample("ggms_sample_weighted_khop_hash_dedup", WEIGHTED_KHOP_HASH_DEDUP, graph, inp, fanout, states,
+                   prob_table, alias_table)
 
 
 def sample_khop1(graph, inp, fanout, states):
     """GPUSampleKHop1 (cuda_sampling_khop1.cu:130-236): uniform with replacement, adjacent duplicates dropped."""
-    _require_gpu(inp)
-    _i32(inp)
-    n = inp.numel()
-    dev = inp.device
-    out_src = torch.empty(max(1, n * fanout), dtype=torch.int32, device=dev)
-    out_dst = torch.empty(max(1, n * fanout), dtype=torch.int32, device=dev)
-    num_out = torch.zeros(1, dtype=torch.int64, device=dev)
-    ws = _workspace(lib().ggms_sample_weighted_workspace_bytes(n, fanout), dev)
-    check(lib().ggms_sample_khop1(C.byref(graph.c), _ptr(inp), n, fanout, _ptr(out_src), _ptr(out_dst), _ptr(num_out),
-                                  _ptr(states), states.shape[0], _ptr(ws), ws.numel() * 4, _stream()),
-          "ggms_sample_khop1")
-    return out_src, out_dst, num_out
+    return _sample("ggms_sample_khop1", KHOP1, graph, inp, fanout, states)
 
 
 def sample_khop2(graph, inp, fanout, states):
@@ -185,18 +148,7 @@ def sample_khop2(graph, inp, fanout, states):
 
 def sample_weighted_khop(graph, prob_table, alias_table, inp, fanout, states):
     """GPUSampleWeightedKHop (cuda_sampling_weighted_khop.cu:132-238)."""
-    _require_gpu(inp)
-    _i32(inp)
-    n = inp.numel()
-    dev = inp.device
-    out_src = torch.empty(max(1, n * fanout), dtype=torch.int32, device=dev)
-    out_dst = torch.empty(max(1, n * fanout), dtype=torch.int32, device=dev)
-    num_out = torch.zeros(1, dtype=torch.int64, device=dev)
-    ws = _workspace(lib().ggms_sample_weighted_workspace_bytes(n, fanout), dev)
-    check(lib().ggms_sample_weighted_khop(C.byref(graph.c), _ptr(prob_table), _ptr(alias_table), _ptr(inp), n, fanout,
-                                          _ptr(out_src), _ptr(out_dst), _ptr(num_out), _ptr(states), states.shape[0],
-                                          _ptr(ws), ws.numel() * 4, _stream()), "ggms_sample_weighted_khop")
-    return out_src, out_dst, num_out
+    return _sample("ggms_sample_weighted_khop", WEIGHTED_KHOP, graph, inp, fanout, states, prob_table, alias_table)
 
 
 def sample_random_walk(graph, inp, walk_length, restart_prob, num_walk, K, states):
