@@ -408,6 +408,19 @@ int ggms_gather_scatter_masked(void *out, const void *src,
  * input nodes to the host and counts there); num may be overridden by a device count. */
 int ggms_count_nodes(uint32_t *freq, const ggms_id_t *nodes, size_t num_nodes,
                      const uint64_t *num_nodes_dev, ggms_stream_t stream);
+/* L-hop closure of a seed set (DoGPUSampleAllNeighbour, cuda/cuda_loops.cc:526-598): the presample_static ranking's
+ * per-batch work.  closure[hop_offsets_dev[h] .. hop_offsets_dev[h + 1]) = the nodes at BFS distance exactly h from
+ * the seeds, h = 0 .. num_hop (h = 0: the distinct seeds); each node once, order within a hop unspecified.
+ *   visit    num_node words, zeroed ONCE by the caller; every call passes a nonzero `stamp` no word holds yet (1, 2,
+ *            3, ...), so the words are never cleared between calls
+ *   freq     optional (NULL): freq[v] += 1 for every closure node
+ *   closure  num_node ids (the closure never holds more); hop_offsets_dev: num_hop + 2 words
+ *   seeds    ids below num_node
+ * Every size stays on the device; neighbour lists are read through the graph view (sharded graphs included). */
+size_t ggms_khop_closure_workspace_bytes(size_t num_node);
+int ggms_khop_closure(const ggms_graph_t *graph, const ggms_id_t *seeds, size_t num_seeds, uint32_t num_hop,
+                      uint32_t *visit, uint32_t stamp, uint32_t *freq, ggms_id_t *closure,
+                      uint64_t *hop_offsets_dev, void *workspace, size_t workspace_bytes, ggms_stream_t stream);
 size_t ggms_cache_index_workspace_bytes(size_t num_nodes);
 /* GetMissCacheIndex :355-441 (kernels :40-169): stable split of `nodes` into
  * miss (src = global id, dst = output row) and hit (src = slot, dst = row). */

@@ -124,6 +124,8 @@ SYMBOLS = {
     "ggms_map_edges": (_i, [C.POINTER(HashTable), _vp, _vp, _vp, _vp, _sz, _vp]),
     "ggms_extract": (_i, [_vp, _vp, _vp, _sz, _sz, _i, _vp]),
     "ggms_count_nodes": (_i, [_vp, _vp, _sz, _vp, _vp]),
+    "ggms_khop_closure_workspace_bytes": (_sz, [_sz]),
+    "ggms_khop_closure": (_i, [C.POINTER(Graph), _vp, _sz, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ggms_cache_index_workspace_bytes": (_sz, [_sz]),
     "ggms_get_miss_cache_index": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ggms_get_miss_cache_index_dev": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -347,6 +347,12 @@ void Engine::LoadDataset() {
   if (cfg.UseGPUCache()) { // engine.cc:395-440
     static const char *rank_files[] = {"cache_by_degree.bin", "cache_by_heuristic.bin", nullptr, "cache_by_degree_hop.bin",
                                        nullptr, "cache_by_fake_optimal.bin", nullptr, "cache_by_random.bin"};
+    if (cfg.cache_policy == 4 && cfg.arch == kArch0) // cpu/cpu_engine.cc:159
+      fatal(__FILE__, __LINE__, "arch0: cache policy presample_static (4) is not built for the CPU engine: it ranks the "
+                                "nodes with a GPU closure kernel (arch3, arch5, arch6); see DESIGN.md");
+    if (cfg.cache_policy == 6)
+      fatal(__FILE__, __LINE__, "cache policy dynamic_cache (6) is not built: it needs arch4 and a per-batch cache "
+                                "replacement manager; see DESIGN.md");
     if (cfg.UsePresample()) {
       // filled by worker 0 in SampleInit, read by every worker (dist_engine.cc:455-466): shared pages
       ds.ranking_nodes.bytes = ds.num_node * 4;
@@ -355,7 +361,7 @@ void Engine::LoadDataset() {
       ds.ranking_nodes.shared_anon = true;
     } else {
       SAM_CHECK(cfg.cache_policy >= 0 && cfg.cache_policy < 8 && rank_files[cfg.cache_policy],
-                "cache policy not built (presample_static / dynamic): see DESIGN.md");
+                "cache policy " + std::to_string(cfg.cache_policy) + " is not a cache policy: see DESIGN.md");
       ds.ranking_nodes = MapFile(rank_files[cfg.cache_policy], ds.num_node * 4, false);
     }
   }
@@ -871,10 +877,14 @@ void Engine::EnablePeerAccess() {
 // PreSampler (dist/pre_sampler.cc:39-139): sample `presample_epoch` epochs of the WHOLE train set with a
 // GPUShuffler of its own, count how often each node is an input node, rank by (freq << 32 | id) descending.
 // Counting happens on the device (one atomicAdd per input node) instead of D2H copy + OpenMP loop.
+// presample_static (GPUEngine's pre-sampler, cuda/pre_sampler.cc:58-111): the same epochs, but a batch counts its
+// whole L-hop closure (ggms_khop_closure, each node once per batch) instead of its sampled input nodes; no RNG state
+// is consumed, so the training batches that follow are those of a run without presample.
 void Engine::Presample() {
   const uint32_t L = (uint32_t)cfg.fanout.size();
   const size_t n_train = ds.num_train;
   const size_t steps = (n_train + cfg.batch_size - 1) / cfg.batch_size; // drop_last = false, :41-42
+  const bool closure = cfg.cache_policy == 4 /*kCacheByPreSampleStatic*/;
   std::vector<uint32_t> data((const uint32_t *)ds.train_set.ptr, (const uint32_t *)ds.train_set.ptr + n_train);
   uint32_t *d_train = nullptr, *d_freq = nullptr;
   uint64_t *d_counts = nullptr;
@@ -882,12 +892,23 @@ void Engine::Presample() {
   SAM_HIP(hipMalloc((void **)&d_freq, ds.num_node * 4));
   SAM_HIP(hipMalloc((void **)&d_counts, (3 * L + 8) * 8));
   SAM_HIP(hipMemsetAsync(d_freq, 0, ds.num_node * 4, stream_));
-  std::vector<uint32_t *> row(L), col(L), dat(L, nullptr);
-  for (uint32_t i = 0; i < L; ++i) {
+  // presample_static: visit stamps + the closure + its workspace, about 3 x 4 B x num_node, freed before BuildCache
+  uint32_t *d_visit = nullptr, *d_closure = nullptr;
+  void *d_cws = nullptr;
+  const size_t cws_bytes = closure ? ggms_khop_closure_workspace_bytes(ds.num_node) : 0;
+  if (closure) {
+    SAM_HIP(hipMalloc((void **)&d_visit, ds.num_node * 4));
+    SAM_HIP(hipMalloc((void **)&d_closure, ds.num_node * 4));
+    SAM_HIP(hipMalloc(&d_cws, cws_bytes));
+    SAM_HIP(hipMemsetAsync(d_visit, 0, ds.num_node * 4, stream_));
+  }
+  std::vector<uint32_t *> row(closure ? 0 : L), col(closure ? 0 : L), dat(closure ? 0 : L, nullptr);
+  for (uint32_t i = 0; i < row.size(); ++i) {
     SAM_HIP(hipMalloc((void **)&row[i], std::max<size_t>(max_edges_[i], 4) * 4));
     SAM_HIP(hipMalloc((void **)&col[i], std::max<size_t>(max_edges_[i], 4) * 4));
     if (cfg.sample_type == GGMS_RANDOM_WALK) SAM_HIP(hipMalloc((void **)&dat[i], std::max<size_t>(max_edges_[i], 4) * 4));
   }
+  uint32_t stamp = 0; // closure k of the presample: stamp k, so `visit` is zeroed once
   for (size_t e = 0; e < cfg.presample_epoch; ++e) {
     const uint64_t seed = cfg.has_seed ? cfg.seed + 0x5a5a5aull + e
                                        : (uint64_t)std::chrono::system_clock::now().time_since_epoch().count();
@@ -899,6 +920,11 @@ void Engine::Presample() {
     SAM_HIP(hipMemcpyAsync(d_train, data.data(), n_train * 4, hipMemcpyHostToDevice, stream_));
     for (size_t s = 0; s < steps; ++s) {
       const size_t off = s * cfg.batch_size, size = std::min(cfg.batch_size, n_train - off);
+      if (closure) { // DoGPUSampleAllNeighbour + the count (cuda/pre_sampler.cc:58-111); the hop offsets go to d_counts
+        SAM_GGMS(ggms_khop_closure(&graph_, d_train + off, size, L, d_visit, ++stamp, d_freq, d_closure, d_counts, d_cws,
+                                   cws_bytes, stream_));
+        continue;
+      }
       ggms_sample_extra_t extra = extra_;
       extra.data = dat.data();
       extra.seeds_distinct = train_distinct_ ? 1u : 0u; // slices of a permutation of the train set
@@ -909,6 +935,12 @@ void Engine::Presample() {
     }
     SAM_HIP(hipStreamSynchronize(stream_)); // `data` is reshuffled on the host next
   }
+  if (closure) { // the closures' scans report a bound they hit in the device's status word
+    uint32_t st = 0;
+    SAM_GGMS(ggms_device_status(&st, 1));
+    SAM_CHECK(st == 0, "presample_static: a closure's scan reported device status " + std::to_string(st));
+    (void)hipFree(d_visit); (void)hipFree(d_closure); (void)hipFree(d_cws);
+  }
   std::vector<uint32_t> freq(ds.num_node);
   SAM_HIP(hipMemcpy(freq.data(), d_freq, ds.num_node * 4, hipMemcpyDeviceToHost));
   std::vector<uint64_t> keys(ds.num_node);
@@ -916,7 +948,7 @@ void Engine::Presample() {
   std::sort(keys.begin(), keys.end(), std::greater<uint64_t>());                            // :113-119
   uint32_t *rank = (uint32_t *)ds.ranking_nodes.ptr;
   for (size_t i = 0; i < ds.num_node; ++i) rank[i] = (uint32_t)keys[i]; // GetRankNode :141-151
-  for (uint32_t i = 0; i < L; ++i) { (void)hipFree(row[i]); (void)hipFree(col[i]); if (dat[i]) (void)hipFree(dat[i]); }
+  for (size_t i = 0; i < row.size(); ++i) { (void)hipFree(row[i]); (void)hipFree(col[i]); if (dat[i]) (void)hipFree(dat[i]); }
   (void)hipFree(d_train); (void)hipFree(d_freq); (void)hipFree(d_counts);
 }
 

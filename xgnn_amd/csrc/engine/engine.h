@@ -85,7 +85,10 @@ struct RunConfig {
   size_t presample_epoch = 0;
   size_t staged_serial_epochs = 0; // host-staged path: the first N epochs run the reference's serial, per-phase-timed sequence
   size_t staged_serial_steps = 0;  // ... or this worker's first N batches
-  bool UsePresample() const { return UseGPUCache() && (cache_policy == 2 /*kCacheByPreSample*/); }
+  // worker 0 ranks the nodes at init: pre_sample (sampled input nodes) or presample_static (L-hop closures)
+  bool UsePresample() const {
+    return UseGPUCache() && (cache_policy == 2 /*kCacheByPreSample*/ || cache_policy == 4 /*kCacheByPreSampleStatic*/);
+  }
   bool UseGPUCache() const { return cache_percentage > 0 && arch != kArch1; } // run_config.h:124-126
 };
 

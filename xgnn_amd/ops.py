@@ -260,6 +260,25 @@ def get_miss_cache_index(table, nodes):
     return outs[0], outs[1], num_miss, outs[2], outs[3], num_hit
 
 
+def khop_closure(graph, seeds, num_hop, visit, stamp, freq=None):
+    """L-hop closure of `seeds` (DoGPUSampleAllNeighbour, cuda_loops.cc:526-598).  visit: num_node int32 words the
+    caller zeroed once; stamp: nonzero and new to `visit` on every call; freq (optional): += 1 per closure node.
+    Returns (closure, hop_offsets): closure[hop_offsets[h]:hop_offsets[h + 1]] = the nodes at distance exactly h
+    (order within a hop unspecified); hop_offsets is an int64 device tensor of num_hop + 2 words."""
+    _require_gpu(seeds)
+    _i32(seeds)
+    dev = seeds.device
+    n = graph.c.num_node
+    assert visit.numel() >= n and (freq is None or freq.numel() >= n), "visit / freq need num_node words"
+    closure = torch.empty(max(1, n), dtype=torch.int32, device=dev)
+    hop_offsets = torch.empty(num_hop + 2, dtype=torch.int64, device=dev)
+    ws = _workspace(lib().ggms_khop_closure_workspace_bytes(n), dev)
+    check(lib().ggms_khop_closure(C.byref(graph.c), _ptr(seeds), seeds.numel(), num_hop, _ptr(visit), stamp, _ptr(freq),
+                                  _ptr(closure), _ptr(hop_offsets), _ptr(ws), ws.numel() * 4, _stream()),
+          "ggms_khop_closure")
+    return closure[: int(hop_offsets[-1].item())], hop_offsets
+
+
 def gather_scatter(out, src, src_index, dst_index, num=None, num_dev=None):
     """combine_cache_data / extract_miss_data / combine_miss_data (cuda_cache_manager_device.cu:209-275)."""
     _require_gpu(out)
