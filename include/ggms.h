@@ -57,7 +57,9 @@ const char *ggms_last_error(void);
 /* Status words.  The reference CHECK-aborts when a device-side bound is hit (logging.cc:69-73); kernels here
  * cannot abort, so they OR a bit into a status word and return:
  *   GGMS_STATUS_SCAN_SPIN   an ordered scan's look-back gave up waiting for a predecessor tile (protocol error);
- *   GGMS_STATUS_TABLE_FULL  the hashed dedup table had no free bucket for a key (sized too small).
+ *   GGMS_STATUS_TABLE_FULL  the hashed dedup table had no free bucket for a key (sized too small);
+ *   GGMS_STATUS_PREFETCH_FULL  ggms_sample_batch_prefetch: the expansion had more edges than its capacity
+ *                              (counts_dev[3 L + 6] holds the number it needed).
  * Results of a call that set a bit are invalid.  Two kinds of word:
  *   - every BATCH has its own: the second word behind its table's item counter (ggms_hashtable_t.num_items_dev[1],
  *     zeroed by ggms_hashtable_init).  Every kernel of a ggms_sample_batch call ORs into that word only, the
@@ -69,6 +71,7 @@ const char *ggms_last_error(void);
  *     non-blocking streams included) and then zeroes it. */
 #define GGMS_STATUS_SCAN_SPIN 1u
 #define GGMS_STATUS_TABLE_FULL 2u
+#define GGMS_STATUS_PREFETCH_FULL 4u
 int ggms_device_status(uint32_t *status_host, int clear);
 /* Rate probe for the bench report (no reference counterpart): num_requests random requests on a caller-owned table
  * of table_words 64-bit words -- GGMS_PROBE_ATOMIC: one returning 64-bit atomicMin each (what a dedup insert is),
@@ -379,6 +382,36 @@ int ggms_sample_batch(int sample_type, const ggms_graph_t *graph,
                       ggms_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * arch4's batch with early feature prefetch -- DoGPUSampleDyCache (cuda/cuda_loops.cc:294-524).  The layers of
+ * ggms_sample_batch, except:
+ *   - after the second-to-last layer's table fill, every neighbour of every node entered so far (n2o[0, k)) is
+ *     entered too, new nodes taking the next local ids in first-occurrence order over the concatenated lists
+ *     (GPUExtractNeighbour + FillWithDupMutable); `expand_start` is recorded before that and `input_final` right
+ *     after it: from then on n2o and counts_dev[3 L] hold the batch's final input nodes (NULL = no event);
+ *   - the last layer samples from n2o[0, k), the set as it stood BEFORE the expansion, and inserts nothing: its row
+ *     ids are look-ups.  It draws exactly what ggms_sample_batch's last layer draws, so every edge equals that
+ *     call's for the same RNG pool, and num_src(0) = counts_dev[3 L] is the size of the superset;
+ *   - counts_dev[3 L + 6] = edges of the expansion.  More than max_prefetch_edges: GGMS_STATUS_PREFETCH_FULL in
+ *     the batch's status word, nothing is truncated silently (the batch is invalid).
+ * Sample types khop0, khop1 and weighted_khop (cuda_loops.cc:347-377), num_layer >= 2 and the direct table layout
+ * only; anything else is an argument error.  ht->n2o_size >= the max_input_nodes of the capacity call.
+ * Capacity (host): k = the unique bound after L - 1 layers; max_prefetch_edges = min(sum of the k largest degrees,
+ * max_edges_budget), max_input_nodes = min(num_node, k + max_prefetch_edges).  indptr is the HOST CSR offsets.
+ * ------------------------------------------------------------------------- */
+int ggms_sample_batch_prefetch_capacity(size_t num_seeds, const size_t *fanouts, uint32_t num_layer,
+                                        const ggms_id_t *indptr, size_t num_node, size_t max_edges_budget,
+                                        size_t *max_prefetch_edges, size_t *max_input_nodes);
+size_t ggms_sample_batch_prefetch_workspace_bytes(int sample_type, size_t num_seeds, const size_t *fanouts,
+                                                  uint32_t num_layer, const ggms_sample_extra_t *extra,
+                                                  size_t max_prefetch_edges);
+int ggms_sample_batch_prefetch(int sample_type, const ggms_graph_t *graph, const ggms_id_t *seeds, size_t num_seeds,
+                               const size_t *fanouts, uint32_t num_layer, ggms_hashtable_t *ht, void *states,
+                               size_t num_states, ggms_id_t *const *row, ggms_id_t *const *col, uint64_t *counts_dev,
+                               const ggms_sample_extra_t *extra, size_t max_prefetch_edges, ggms_event_t expand_start,
+                               ggms_event_t input_final, void *workspace, size_t workspace_bytes,
+                               ggms_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Feature extract -- GPUExtract, cuda/cuda_extraction.cu:74-117:
  * dst[i, :] = src[index[i], :].  src may be device or device-mapped host
  * memory (gpu_extract zero-copy path, dist_loops.cc:585-634).
@@ -473,6 +506,21 @@ int ggms_extract_cached(void *out, const ggms_id_t *nodes, size_t num_nodes,
                         const void *const *parts, uint32_t num_part,
                         const void *host_feat, size_t dim, int dtype,
                         uint64_t *num_miss_dev, ggms_stream_t stream);
+
+/* dynamic_cache (arch4; GPUDynamicCacheManager + DoDynamicCacheFeatureCopy, cuda/cuda_loops.cc:1073-1215): the
+ * trainer GPU keeps the previous batch's rows.  stamps: one 64-bit word per node, (seq << 32) | slot, zeroed once
+ * (ggms_dynamic_cache_reset).  Batch `seq` (1 .. 2^32 - 1; seq 1 finds no hits):
+ *   ggms_extract_dynamic   out[i,:] = stamps[n] >> 32 == seq - 1 ? prev_feat[(uint32_t)stamps[n],:] : host_feat[n,:]
+ *                          for n = nodes[i]; *num_miss_dev += rows read from host_feat (may be NULL)
+ *   ggms_dynamic_cache_publish   stamps[nodes[i]] = (seq << 32) | i, on the same stream after the gather
+ * so the next batch (seq + 1) finds this batch's rows in ITS feature buffer.  When seq wraps, the caller resets the
+ * table and starts again at 1.  The bytes equal a plain gather of `nodes` whatever the hit rate. */
+int ggms_dynamic_cache_reset(uint64_t *stamps, size_t num_node, ggms_stream_t stream);
+int ggms_extract_dynamic(void *out, const ggms_id_t *nodes, size_t num_nodes, const uint64_t *num_nodes_dev,
+                         const uint64_t *stamps, uint32_t seq, const void *prev_feat, const void *host_feat,
+                         size_t dim, int dtype, uint64_t *num_miss_dev, ggms_stream_t stream);
+int ggms_dynamic_cache_publish(uint64_t *stamps, const ggms_id_t *nodes, size_t num_nodes,
+                               const uint64_t *num_nodes_dev, uint32_t seq, ggms_stream_t stream);
 
 /* Every tier of the store behind one gather (GGMS across GPUs with hot-row replication):
  *   slot = table ? table[node] : node            (table NULL: full cache, slot = node id)

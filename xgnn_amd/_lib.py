@@ -138,6 +138,15 @@ SYMBOLS = {
     "ggms_gather_scatter_masked": (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _i, _u32, _vp]),
     "ggms_ipc_safe_bytes": (_sz, [_sz]),
     "ggms_extract_tiered": (_i, [_vp, _vp, _sz, _vp, C.POINTER(FeatureTiers), _sz, _i, _vp, _vp]),
+    "ggms_sample_batch_prefetch_capacity": (_i, [_sz, C.POINTER(_sz), _u32, _vp, _sz, _sz, C.POINTER(_sz),
+                                                 C.POINTER(_sz)]),
+    "ggms_sample_batch_prefetch_workspace_bytes": (_sz, [_i, _sz, C.POINTER(_sz), _u32, C.POINTER(SampleExtra), _sz]),
+    "ggms_sample_batch_prefetch": (_i, [_i, C.POINTER(Graph), _vp, _sz, C.POINTER(_sz), _u32, C.POINTER(HashTable), _vp,
+                                        _sz, C.POINTER(_vp), C.POINTER(_vp), _vp, C.POINTER(SampleExtra), _sz, _vp, _vp,
+                                        _vp, _sz, _vp]),
+    "ggms_dynamic_cache_reset": (_i, [_vp, _sz, _vp]),
+    "ggms_extract_dynamic": (_i, [_vp, _vp, _sz, _vp, _vp, _u32, _vp, _vp, _sz, _i, _vp, _vp]),
+    "ggms_dynamic_cache_publish": (_i, [_vp, _vp, _sz, _vp, _u32, _vp]),
     "ggms_device_count": (_i, [C.POINTER(_i)]),
     "ggms_peer_access": (_i, [_i, _i, C.POINTER(_i)]),
     "ggms_detect_topology": (_i, [C.POINTER(Topology), _sz, _i]),

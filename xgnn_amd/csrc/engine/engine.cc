@@ -112,20 +112,22 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
       cfg.trainer_device = parse_device(kv["trainer_ctx"]);
       cfg.num_worker = 1;
       break;
-    case kArch3: { // GPUEngine::ArchCheck (cuda/cuda_engine.cc:410-435): one GPU samples, a different GPU trains
-      SAM_CHECK(kv.count("sampler_ctx") && kv.count("trainer_ctx"), "arch3 needs sampler_ctx/trainer_ctx");
+    case kArch3:   // GPUEngine::ArchCheck (cuda/cuda_engine.cc:410-435): one GPU samples, a different GPU trains
+    case kArch4: { // the same, + early prefetch and dynamic_cache (cuda/cuda_loops_arch4.cc)
+      const std::string a = cfg.arch == kArch4 ? "arch4" : "arch3";
+      SAM_CHECK(kv.count("sampler_ctx") && kv.count("trainer_ctx"), a + " needs sampler_ctx/trainer_ctx");
       const std::string sc = kv["sampler_ctx"], tc = kv["trainer_ctx"];
       if (sc.rfind("cuda", 0) != 0 || tc.rfind("cuda", 0) != 0)
-        fatal(__FILE__, __LINE__, "arch3: sampler_ctx and trainer_ctx must both be GPU contexts (cuda:N), got " + sc +
+        fatal(__FILE__, __LINE__, a + ": sampler_ctx and trainer_ctx must both be GPU contexts (cuda:N), got " + sc +
                                       " and " + tc);
       if (ctx_id_as_written(sc) == ctx_id_as_written(tc))
-        fatal(__FILE__, __LINE__, "arch3: sampler_ctx and trainer_ctx are the same GPU (" + sc + "): arch3 samples on one "
+        fatal(__FILE__, __LINE__, a + ": sampler_ctx and trainer_ctx are the same GPU (" + sc + "): " + a + " samples on one "
                                       "GPU and trains on another; one GPU for both is arch1");
       const bool log_access = getenv("SAMGRAPH_LOG_NODE_ACCESS") || getenv("SAMGRAPH_LOG_NODE_ACCESS_SIMPLE");
       if (cfg.cache_percentage > 0 && log_access)
-        fatal(__FILE__, __LINE__, "arch3: a GPU cache (cache_percentage > 0) cannot be combined with node access logging "
+        fatal(__FILE__, __LINE__, a + ": a GPU cache (cache_percentage > 0) cannot be combined with node access logging "
                                   "(SAMGRAPH_LOG_NODE_ACCESS*)");
-      refuse_arch6_keys(kv, "arch3");
+      refuse_arch6_keys(kv, a);
       cfg.sampler_device = parse_device(sc);
       cfg.trainer_device = parse_device(tc);
       cfg.num_worker = 1;
@@ -164,8 +166,8 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
       SAM_CHECK(cfg.num_worker >= 1, "num_worker >= 1");
       break;
     default:
-      fatal(__FILE__, __LINE__, "only arch0 (CPU), arch1 (standalone), arch3 (dedicated), arch5 (factored) and arch6 "
-                                "(SGNN/XGNN) are built; see DESIGN.md");
+      fatal(__FILE__, __LINE__, "only arch0 (CPU), arch1 (standalone), arch3 (dedicated), arch4 (dedicated with prefetch), "
+                                "arch5 (factored) and arch6 (SGNN/XGNN) are built; see DESIGN.md");
   }
   if (cfg.sample_type != GGMS_RANDOM_WALK) { // operation.cc:150-163
     SAM_CHECK(kv.count("num_fanout") && kv.count("fanout"), "khop sampling needs num_fanout/fanout");
@@ -213,6 +215,27 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
     cfg.pipelines = 1;
   }
   SAM_CHECK(cfg.sample_type >= GGMS_KHOP0 && cfg.sample_type <= GGMS_KHOP3, "unknown sample type");
+  if (cfg.arch == kArch4) { // DoGPUSampleDyCache's switch (cuda/cuda_loops.cc:347-377) and what it needs
+    if (cfg.sample_type != GGMS_KHOP0 && cfg.sample_type != GGMS_KHOP1 && cfg.sample_type != GGMS_WEIGHTED_KHOP)
+      fatal(__FILE__, __LINE__, "arch4: _sample_type " + std::to_string(cfg.sample_type) + " is not supported: the "
+                                "prefetching sampler takes khop0, khop1 and weighted_khop only");
+    if (cfg.fanout.size() < 2)
+      fatal(__FILE__, __LINE__, "arch4: num_layer " + std::to_string(cfg.fanout.size()) + ": the expansion follows the "
+                                "second-to-last layer, so arch4 needs at least 2 layers");
+    // a non-zero percentage takes the reference's static-cache branch (cuda/cuda_engine.cc:160-186), which its arch4
+    // copy loop never reads: refused rather than built and ignored
+    if (cfg.cache_policy == 6 && cfg.cache_percentage > 0)
+      fatal(__FILE__, __LINE__, "arch4: cache policy dynamic_cache (6) takes cache_percentage 0 (got " +
+                                kv["cache_percentage"] + "): it caches the previous batch's rows, not a ranked share");
+    if (cfg.cache_policy != 6 && cfg.cache_percentage > 0)
+      fatal(__FILE__, __LINE__, "arch4: cache_percentage " + kv["cache_percentage"] + " with the static cache policy " +
+                                std::to_string(cfg.cache_policy) + ": arch4 reads every row from host memory or, with "
+                                "dynamic_cache, from the previous batch; set cache_percentage 0");
+    if (!cfg.direct_table) fatal(__FILE__, __LINE__, "arch4: hash_table = hashed: the superset needs the direct table layout");
+    cfg.dynamic_cache = cfg.cache_policy == 6;
+    if (cfg.dynamic_cache) cfg.extract_streams = 1; // gathers in batch order, each after the one whose rows it reads
+    if (kv.count("prefetch_max_edges")) cfg.prefetch_max_edges = std::stoull(kv["prefetch_max_edges"]);
+  }
   if (cfg.sample_type == GGMS_WEIGHTED_KHOP || cfg.sample_type == GGMS_KHOP2 || cfg.sample_type == GGMS_KHOP1 ||
       cfg.sample_type == GGMS_WEIGHTED_KHOP_PREFIX ||
       cfg.sample_type == GGMS_WEIGHTED_KHOP_HASH_DEDUP) // dist_loops.cc:167-168,171-172,209-210,219-220,227-228
@@ -350,7 +373,7 @@ void Engine::LoadDataset() {
     if (cfg.cache_policy == 4 && cfg.arch == kArch0) // cpu/cpu_engine.cc:159
       fatal(__FILE__, __LINE__, "arch0: cache policy presample_static (4) is not built for the CPU engine: it ranks the "
                                 "nodes with a GPU closure kernel (arch3, arch5, arch6); see DESIGN.md");
-    if (cfg.cache_policy == 6)
+    if (cfg.cache_policy == 6) // (arch4 refuses a percentage in Configure)
       fatal(__FILE__, __LINE__, "cache policy dynamic_cache (6) is not built: it needs arch4 and a per-batch cache "
                                 "replacement manager; see DESIGN.md");
     if (cfg.UsePresample()) {
@@ -652,7 +675,7 @@ bool Engine::ShufflerNext(Batch *b, hipStream_t copy_stream) {
   b->num_seeds = size;
   b->key = BatchKey(cur_epoch_, global_step_offset_ + cur_step_);
   static const bool sanity = getenv("SAMGRAPH_SANITY_CHECK") != nullptr; // run_config.cc:126-128
-  if (sanity && (cfg.arch == kArch1 || cfg.arch == kArch3)) SanityCheckBatch(shuf_host_.data() + global_data_offset_ + offset, size);
+  if (sanity && (cfg.arch == kArch1 || Dedicated())) SanityCheckBatch(shuf_host_.data() + global_data_offset_ + offset, size);
   SAM_HIP(hipMemcpyAsync(b->sampler.output_nodes, shuf_dev_ + offset, size * 4, hipMemcpyDeviceToDevice, copy_stream)); // Copy1D
   return true;
 }
@@ -749,6 +772,9 @@ void Engine::ComputeBounds() {
   max_input_.resize(L);
   max_edges_.resize(L);
   SAM_GGMS(ggms_sample_batch_capacity(max_seeds_, cfg.fanout.data(), L, max_input_.data(), max_edges_.data(), &max_unique_));
+  if (cfg.arch == kArch4) // the superset: min(N, k + the k largest degrees), within the edge budget
+    SAM_GGMS(ggms_sample_batch_prefetch_capacity(max_seeds_, cfg.fanout.data(), L, (const ggms_id_t *)ds.indptr.ptr,
+                                                 ds.num_node, cfg.prefetch_max_edges, &max_prefetch_edges_, &max_unique_));
 }
 
 void Engine::SampleInit(int worker_id, const std::string &ctx) {
@@ -761,7 +787,7 @@ void Engine::SampleInit(int worker_id, const std::string &ctx) {
   }
   worker_id_ = worker_id;
   device_ = parse_device(ctx);
-  trainer_device_ = cfg.arch == kArch3 ? cfg.trainer_device : device_;
+  trainer_device_ = Dedicated() ? cfg.trainer_device : device_;
   if (trainer_device_ != device_) EnablePeerAccess();
   SAM_HIP(hipSetDevice(device_));
   SAM_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
@@ -812,7 +838,9 @@ void Engine::SampleInit(int worker_id, const std::string &ctx) {
   const uint64_t seed = cfg.has_seed ? cfg.seed + 1000003ull * worker_id
                                      : (uint64_t)std::chrono::system_clock::now().time_since_epoch().count();
   SAM_GGMS(ggms_random_states_init(states_, num_states_, seed, stream_));
-  ws_bytes_ = ggms_sample_batch_workspace_bytes(cfg.sample_type, max_seeds_, cfg.fanout.data(), L, &extra_);
+  ws_bytes_ = cfg.arch == kArch4 ? ggms_sample_batch_prefetch_workspace_bytes(cfg.sample_type, max_seeds_, cfg.fanout.data(),
+                                                                          L, &extra_, max_prefetch_edges_)
+                                 : ggms_sample_batch_workspace_bytes(cfg.sample_type, max_seeds_, cfg.fanout.data(), L, &extra_);
   SAM_HIP(hipMalloc(&ws_, ws_bytes_));
   // pipeline 0 = {stream_, ht_, ws_}; the others get their own stream, table and workspace
   pipes_.assign(cfg.pipelines, Pipe{});
@@ -1102,8 +1130,8 @@ void Engine::TrainInit(int worker_id, const std::string &ctx) {
     Arch5TrainerInit(worker_id, ctx);
   else
     SAM_CHECK(sample_ready_, "samgraph_sample_init first");
-  if (cfg.arch == kArch3)
-    SAM_CHECK(parse_device(ctx) == trainer_device_, "arch3: train_init on the config's trainer_ctx");
+  if (Dedicated())
+    SAM_CHECK(parse_device(ctx) == trainer_device_, "arch3 / arch4: train_init on the config's trainer_ctx");
   else
     SAM_CHECK(parse_device(ctx) == device_, "arch6: sampler and trainer share the GPU (cuda_cache_manager_host.cc:152-155)");
   SAM_HIP(hipSetDevice(trainer_device_));
@@ -1120,6 +1148,13 @@ void Engine::TrainInit(int worker_id, const std::string &ctx) {
   size_t nslots = 2;
   if (cfg.raw.count("max_copying_jobs")) nslots = std::max<size_t>(2, std::min<size_t>(4, std::stoull(cfg.raw["max_copying_jobs"]) + 1));
   nslots = std::max(nslots, 2 + cfg.lookahead); // the trainer's batch + the one asked for + the ones enqueued ahead
+  if (cfg.dynamic_cache) { // + the previous batch, held until the next gather has read its rows (dyn_hold)
+    nslots += 1;
+    SAM_CHECK(ds.feat_mask == 0xffffffffu, "arch4: dynamic_cache with SAMGRAPH_EMPTY_FEAT (a mock feature table) is not built");
+    SAM_HIP(hipMalloc((void **)&dyn_stamps_, std::max<size_t>(ds.num_node, 1) * 8));
+    SAM_GGMS(ggms_dynamic_cache_reset(dyn_stamps_, ds.num_node, stream_extract_));
+    SAM_HIP(hipStreamSynchronize(stream_extract_));
+  }
   for (size_t s = 0; s < nslots; ++s) {
     auto b = std::make_unique<Batch>();
     b->slot = (int)s;
@@ -1144,7 +1179,7 @@ void Engine::TrainInit(int worker_id, const std::string &ctx) {
     SAM_HIP(hipEventCreate(&b->ev_done));
     SAM_GGMS(ggms_launch_timer_create(&b->gather_timer));
     if (BatchSampledElsewhere()) SAM_GGMS(ggms_launch_timer_create(&b->handoff_timer));
-    if (cfg.arch == kArch3) { // the sampler's side of the slot, on the sampler GPU (GetGraphFileCtx, cuda_engine.cc:437-481)
+    if (Dedicated()) { // the sampler's side of the slot, on the sampler GPU (GetGraphFileCtx, cuda_engine.cc:437-481)
       SAM_HIP(hipSetDevice(device_));
       b->sampler.Alloc(max_edges_, max_unique_, max_seeds_, cfg.sample_type == GGMS_RANDOM_WALK);
     } else {
@@ -1152,6 +1187,10 @@ void Engine::TrainInit(int worker_id, const std::string &ctx) {
     }
     SAM_HIP(hipEventCreate(&b->ev_start)); // both recorded on the sampling stream
     SAM_HIP(hipEventCreate(&b->ev_sampled));
+    if (cfg.arch == kArch4) {
+      SAM_HIP(hipEventCreate(&b->ev_expand));
+      SAM_HIP(hipEventCreate(&b->ev_final));
+    }
     SAM_HIP(hipSetDevice(trainer_device_));
     slots_.push_back(std::move(b));
   }
@@ -1172,7 +1211,7 @@ void Engine::Init() { // samgraph_init, single process
 // GPUEngine::Start (cuda/cuda_engine.cc:292-317): arch3 starts its background sample + hand-off + extract loop, and the
 // caller only asks for batches (get_next_batch).  The other deployments start theirs with extract_start, or not at all.
 void Engine::Start() {
-  if (cfg.arch == kArch3) ExtractStart(0);
+  if (Dedicated()) ExtractStart(0);
 }
 
 void Engine::Shutdown() {
@@ -1234,7 +1273,7 @@ bool Engine::EnqueueOne(bool background) {
     int dev = -1;
     ~RestoreDevice() { if (dev >= 0) (void)hipSetDevice(dev); }
   } restore;
-  if (cfg.arch == kArch3) SAM_HIP(hipGetDevice(&restore.dev));
+  if (Dedicated()) SAM_HIP(hipGetDevice(&restore.dev));
   SAM_HIP(hipSetDevice(device_));
   Batch *b = AcquireSlot(background);
   if (!b) return false;
@@ -1282,8 +1321,14 @@ void Engine::SampleInto(Batch *b, Pipe &P) {
   ggms_hashtable_t ht = P.ht;
   ht.n2o = s.input_nodes;
   ht.n2o_size = max_unique_;
-  SAM_GGMS(ggms_sample_batch(cfg.sample_type, &graph_, s.output_nodes, b->num_seeds, cfg.fanout.data(), L, &ht, states_,
-                             num_states_, s.row.data(), s.col.data(), s.counts_dev, &extra, P.ws, ws_bytes_, P.stream));
+  if (cfg.arch == kArch4) // DoGPUSampleDyCache: the input set is final at ev_final, before the last layer
+    SAM_GGMS(ggms_sample_batch_prefetch(cfg.sample_type, &graph_, s.output_nodes, b->num_seeds, cfg.fanout.data(), L, &ht,
+                                        states_, num_states_, s.row.data(), s.col.data(), s.counts_dev, &extra,
+                                        max_prefetch_edges_, (ggms_event_t)b->ev_expand, (ggms_event_t)b->ev_final, P.ws,
+                                        ws_bytes_, P.stream));
+  else
+    SAM_GGMS(ggms_sample_batch(cfg.sample_type, &graph_, s.output_nodes, b->num_seeds, cfg.fanout.data(), L, &ht, states_,
+                               num_states_, s.row.data(), s.col.data(), s.counts_dev, &extra, P.ws, ws_bytes_, P.stream));
   P.ht.version = ht.version; // the batch bumped the table's version stamp
   SAM_HIP(hipMemsetAsync(s.counts_dev + 3 * L + 2, 0, 8, P.stream)); // the trainer's miss count starts at 0
   SAM_HIP(hipEventRecord(b->ev_sampled, P.stream));
@@ -1324,16 +1369,32 @@ void Engine::EnqueueGather(Batch *b, hipStream_t ss) {
   // extract overlaps batch k+1's sampling (the reference serialises them, dist_loops_arch6.cc:248-251)
   hipStream_t xs = (b->lean && stream_extract2_ && (enq_count_ & 1)) ? stream_extract2_ : stream_extract_;
   if (remote) SAM_HIP(hipSetDevice(trainer_device_));
+  const bool arch4 = cfg.arch == kArch4;
   if (cfg.arch == kArch5) Unpack(b, xs); // the batch's arrays, queue slot -> T (the slot is free again when it returns)
-  else SAM_HIP(hipStreamWaitEvent(xs, b->ev_sampled, 0));
+  else SAM_HIP(hipStreamWaitEvent(xs, arch4 ? b->ev_final : b->ev_sampled, 0)); // arch4: as soon as the input set is final
   if (remote) {
     if (cfg.arch == kArch3) Handoff(b, xs); // the batch's arrays, S -> T; the gather below reads the input nodes and their count on T
+    if (arch4) { // input nodes + their count and the seeds now; the miss count starts at 0 on T (the sampler's comes later)
+      Handoff(b, xs, kHandoffIds);
+      SAM_HIP(hipMemsetAsync(n_miss, 0, 8, xs));
+    }
     SAM_GGMS(ggms_extract(b->label, label_src_, b->trainer.output_nodes, b->num_seeds, 1, GGMS_I64, xs));
   }
   if (b->lean) SAM_GGMS(ggms_launch_timer_arm(b->gather_timer));
   else SAM_HIP(hipEventRecord(b->ev_xstart, xs)); // the extract's own start: behind the previous batch's extract on xs
+  uint32_t dyn_seq = 0;
+  if (cfg.dynamic_cache) { // batch order on one extract stream; seq wraps: the table starts again from zero
+    if (++dyn_seq_ == 0) {
+      SAM_GGMS(ggms_dynamic_cache_reset(dyn_stamps_, ds.num_node, xs));
+      dyn_seq_ = 1;
+    }
+    dyn_seq = dyn_seq_;
+  }
   if (StagedHostTier()) {
     StagedExtract(b, ss, xs);
+  } else if (cfg.dynamic_cache) { // DoDynamicCacheFeatureCopy (cuda/cuda_loops.cc:1073-1215) as one gather
+    SAM_GGMS(ggms_extract_dynamic(b->feat, b->trainer.input_nodes, max_unique_, n_in, dyn_stamps_, dyn_seq,
+                                  dyn_prev_ ? dyn_prev_->feat : nullptr, feat_src_, ds.feat_dim, ds.feat_dtype, n_miss, xs));
   } else if (cfg.UseGPUCache() && (mock || num_replica_)) { // every tier in one gather; rows per tier counted
     if (gather_counts) SAM_HIP(hipMemsetAsync(n_miss, 0, 4 * 8, xs)); // {host, remote shard, local shard, replica} = counts[3L+2 .. 3L+5]
     ggms_feature_tiers_t tiers{};
@@ -1361,6 +1422,16 @@ void Engine::EnqueueGather(Batch *b, hipStream_t ss) {
     SAM_GGMS(ggms_gather_scatter(b->feat, feat_src_, b->trainer.input_nodes, nullptr, max_unique_, n_in, ds.feat_dim,
                                  ds.feat_dtype, xs));
   }
+  if (cfg.dynamic_cache) { // the next batch finds these rows in b->feat; b holds the batch it read until it is finished
+    SAM_GGMS(ggms_dynamic_cache_publish(dyn_stamps_, b->trainer.input_nodes, max_unique_, n_in, dyn_seq, xs));
+    b->dyn_hold = dyn_prev_;
+    if (dyn_prev_) dyn_prev_->refs.fetch_add(1);
+    dyn_prev_ = b;
+  }
+  if (arch4) { // the COO once the sampler is done (DoGraphCopy)
+    SAM_HIP(hipStreamWaitEvent(xs, b->ev_sampled, 0));
+    Handoff(b, xs, kHandoffGraph);
+  }
   if (!b->lean) {
     if (node_access_dev_) // Profiler::LogNodeAccess (profiler.cc:570-575): visits per node, counted on the device
       SAM_GGMS(ggms_count_nodes(node_access_dev_, b->trainer.input_nodes, max_unique_, n_in, xs));
@@ -1382,7 +1453,9 @@ void Engine::EnqueueGather(Batch *b, hipStream_t ss) {
 // length is read by the kernel from the sampler's counts words (the output nodes' from the host: the shuffler knows
 // it), so the batch is still enqueued without a host round trip.  The counts words themselves are the last segment:
 // the status word [3L + 1] and the zeroed miss count travel with them.
-void Engine::Handoff(Batch *b, hipStream_t xs) {
+// arch4 splits it: kHandoffIds (input nodes, their count, the seeds) at "input set final", kHandoffGraph (the COO and the
+// other counts words, the trainer's miss count left alone) at the sampler's end.
+void Engine::Handoff(Batch *b, hipStream_t xs, HandoffPart part) {
   const uint32_t L = (uint32_t)cfg.fanout.size();
   ggms_copy_seg_t segs[GGMS_HANDOFF_MAX_SEGS];
   uint32_t n = 0;
@@ -1392,14 +1465,29 @@ void Engine::Handoff(Batch *b, hipStream_t xs) {
     segs[n++] = ggms_copy_seg_t{src, dst, count_dev, count_host, max_count, elem_bytes, 0};
   };
   const BatchArrays &s = b->sampler, &t = b->trainer;
+  if (part == kHandoffIds) {
+    add(s.input_nodes, t.input_nodes, s.counts_dev + 3 * L, 0, max_unique_, 4);
+    add(s.output_nodes, t.output_nodes, nullptr, b->num_seeds, max_seeds_, 4);
+    // (segments start 16-byte aligned: from the even word at or before [3L]; [3L - 1] is num_dst(L - 1) = |seeds|)
+    const uint32_t w0 = (3 * L) & ~1u;
+    add(s.counts_dev + w0, t.counts_dev + w0, nullptr, 3 * L + 1 - w0, 3 * L + 1 - w0, 8);
+    SAM_GGMS(ggms_batch_handoff(segs, n, xs));
+    return;
+  }
   for (uint32_t i = 0; i < L; ++i) {
     add(s.row[i], t.row[i], s.counts_dev + 3 * i, 0, max_edges_[i], 4);
     add(s.col[i], t.col[i], s.counts_dev + 3 * i, 0, max_edges_[i], 4);
     if (s.data[i]) add(s.data[i], t.data[i], s.counts_dev + 3 * i, 0, max_edges_[i], 4);
   }
-  add(s.input_nodes, t.input_nodes, s.counts_dev + 3 * L, 0, max_unique_, 4);
-  add(s.output_nodes, t.output_nodes, nullptr, b->num_seeds, max_seeds_, 4);
-  add(s.counts_dev, t.counts_dev, nullptr, 3 * L + 8, 3 * L + 8, 8);
+  if (part == kHandoffGraph) { // counts [0, 3L + 2) (status included) and the expansion's edge count [3L + 6]
+    add(s.counts_dev, t.counts_dev, nullptr, 3 * L + 2, 3 * L + 2, 8);
+    const uint32_t w6 = (3 * L + 6) & ~1u; // (aligned as above: [3L + 5] is a tier counter arch4 does not use)
+    add(s.counts_dev + w6, t.counts_dev + w6, nullptr, 3 * L + 7 - w6, 3 * L + 7 - w6, 8);
+  } else {
+    add(s.input_nodes, t.input_nodes, s.counts_dev + 3 * L, 0, max_unique_, 4);
+    add(s.output_nodes, t.output_nodes, nullptr, b->num_seeds, max_seeds_, 4);
+    add(s.counts_dev, t.counts_dev, nullptr, 3 * L + 8, 3 * L + 8, 8);
+  }
   SAM_GGMS(ggms_launch_timer_arm(b->handoff_timer)); // kLogL2GraphCopyTime: the hand-off's own time
   SAM_GGMS(ggms_batch_handoff(segs, n, xs));
 }
@@ -1439,7 +1527,16 @@ void Engine::Finish(Batch *b, Batch *prev) {
   const uint32_t L = (uint32_t)cfg.fanout.size();
   b->num_input = b->counts[3 * L];
   b->num_miss = b->counts[3 * L + 2];
+  if (b->dyn_hold) { // this batch's gather is complete: the batch it read may go
+    b->dyn_hold->refs.fetch_sub(1);
+    b->dyn_hold = nullptr;
+  }
+  if (cfg.arch == kArch4 && (b->counts[3 * L + 1] & GGMS_STATUS_PREFETCH_FULL))
+    fatal(__FILE__, __LINE__, "arch4: batch " + std::to_string(b->key) + ": the expansion needed " +
+                                  std::to_string(b->counts[3 * L + 6]) + " edges, capacity " +
+                                  std::to_string(max_prefetch_edges_) + " (config key prefetch_max_edges)");
   CheckBatchStatus(b->counts[3 * L + 1], b->key);
+  if (cfg.arch == kArch4 && !cfg.dynamic_cache) b->num_miss = b->num_input; // every row is read from host memory
   float ms_sample = 0, ms_copy = 0;
   if (cfg.arch != kArch5) (void)hipEventElapsedTime(&ms_sample, b->ev_start, b->ev_sampled); // (arch5: sampled elsewhere)
   if (b->lean) ms_copy = (float)(us_gather * 1e-3); // the gather kernel's own time
@@ -1468,6 +1565,14 @@ void Engine::Finish(Batch *b, Batch *prev) {
     prof.LogStep(b->key, 12 /*kLogL1GraphBytes*/, edges * per_edge);
     prof.LogStep(b->key, 11 /*kLogL1IdBytes*/, (b->num_input + b->num_seeds) * 4.0);
     prof.LogStep(b->key, 22 /*kLogL2GraphCopyTime*/, us_handoff * 1e-6);
+    if (cfg.arch == kArch4) { // the expansion's own time, and how far ahead of the sampler's end the gather could start
+      float ms_nb = 0, ms_adv = 0;
+      (void)hipEventElapsedTime(&ms_nb, b->ev_expand, b->ev_final);
+      (void)hipEventElapsedTime(&ms_adv, b->ev_final, b->ev_sampled);
+      prof.LogStep(b->key, 15 /*kLogL1GetNeighbourTime*/, ms_nb * 1e-3);
+      prof.LogStep(b->key, 14 /*kLogL1PrefetchAdvanced*/, ms_adv * 1e-3);
+      if (cfg.dynamic_cache) prof.LogStep(b->key, 26 /*kLogL2CacheCopyTime*/, ms_copy * 1e-3);
+    }
     if (cfg.arch == kArch5) { // RunCacheDataCopySubLoopOnce: copy time = recv + graph copy + feature copy
       prof.LogStep(b->key, 5 /*kLogL1RecvTime*/, b->recv_s);
       prof.LogStepAdd(b->key, 6 /*kLogL1CopyTime*/, b->recv_s + us_handoff * 1e-6);

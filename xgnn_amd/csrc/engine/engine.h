@@ -83,6 +83,10 @@ struct RunConfig {
                         // measured on papers100M-shaped GCN: a second pipeline loses 2-3 % (the step is bound by the memory
                         // fabric, not by sampler latency) and costs a second 8 B x num_node table
   size_t presample_epoch = 0;
+  // arch4: dynamic_cache (cache_policy 6) -- the trainer GPU keeps the previous batch's rows; the expansion's edge
+  // budget of one batch (config key `prefetch_max_edges`; ggms_sample_batch_prefetch_capacity)
+  bool dynamic_cache = false;
+  size_t prefetch_max_edges = (size_t)1 << 26;
   size_t staged_serial_epochs = 0; // host-staged path: the first N epochs run the reference's serial, per-phase-timed sequence
   size_t staged_serial_steps = 0;  // ... or this worker's first N batches
   // worker 0 ranks the nodes at init: pre_sample (sampled input nodes) or presample_static (L-hop closures)
@@ -180,6 +184,10 @@ struct Batch {
   ggms_launch_timer_t *gather_timer = nullptr;
   bool lean = false;
   ggms_launch_timer_t *handoff_timer = nullptr; // arch3: rides on the hand-off; arch5: on the unpack
+  // arch4: around the expansion on the sampling stream (recorded by ggms_sample_batch_prefetch); the trainer's stream
+  // starts the gather at ev_final, the COO hand-off waits for ev_sampled
+  hipEvent_t ev_expand = nullptr, ev_final = nullptr;
+  Batch *dyn_hold = nullptr; // dynamic_cache: the previous batch, whose rows this batch's gather reads
   // arch5 trainer: the queue ticket whose slot this batch came from, and the host's wait for that message
   uint64_t queue_pos = 0;
   double recv_s = 0;
@@ -213,10 +221,12 @@ class Engine {
   size_t NumStep() const { return num_global_step_; }
   size_t NumLocalStep() const { return num_local_step_; }
   uint64_t BatchKey(uint64_t epoch, uint64_t step) const { return epoch * num_global_step_ + step; }
-  int trainer_device() const { return cfg.arch == kArch3 ? trainer_device_ : device_; }
+  // arch3 / arch4: one GPU samples, another trains (arch4 adds the early prefetch and dynamic_cache)
+  bool Dedicated() const { return cfg.arch == kArch3 || cfg.arch == kArch4; }
+  int trainer_device() const { return Dedicated() ? trainer_device_ : device_; }
   bool IsArch5Sampler() const { return cfg.arch == kArch5 && role_ == kRoleSampler; }
   // arch3 / arch5: the batch is sampled elsewhere (sampler GPU / process) and handed to the trainer GPU's extract stream
-  bool BatchSampledElsewhere() const { return cfg.arch == kArch3 || cfg.arch == kArch5; }
+  bool BatchSampledElsewhere() const { return Dedicated() || cfg.arch == kArch5; }
   int batch_device_type() const { return (cfg.arch == kArch0 && cfg.trainer_on_host) ? 0 : 2; } // DeviceType, common.h:48
   void Barrier(const char *what = "step");
   void *OpenPeer(const hipIpcMemHandle_t &handle, uint32_t peer, size_t bytes, const char *what);
@@ -259,7 +269,8 @@ class Engine {
   void Finish(Batch *b, Batch *prev);
   void CheckBatchStatus(uint64_t status, uint64_t key) const; // the device status word of a completed batch
   void EnablePeerAccess(); // arch3: the trainer GPU reads the sampler GPU's batch buffers in place
-  void Handoff(Batch *b, hipStream_t xs);
+  enum HandoffPart { kHandoffAll, kHandoffIds, kHandoffGraph }; // arch4: ids at "input set final", the COO at the end
+  void Handoff(Batch *b, hipStream_t xs, HandoffPart part = kHandoffAll);
   void EnqueueGather(Batch *b, hipStream_t ss); // label + feature gather of a sampled (arch3: handed-off) batch
 
   // arch5 (dist/dist_engine.cc, dist_loops_arch5.cc): a process is a sampler or a trainer.  The batch queue is one
@@ -321,6 +332,11 @@ class Engine {
   hipEvent_t last_rng_done_ = nullptr;
   void SampleInto(Batch *b, Pipe &P); // sample b's seeds into b->sampler on P's stream, then record b->ev_sampled
   size_t max_seeds_ = 0, max_unique_ = 0; // batch bounds (ComputeBounds)
+  size_t max_prefetch_edges_ = 0;         // arch4: the expansion's capacity (max_unique_ is then the superset's)
+  // dynamic_cache: node -> (seq << 32) | slot of its last batch, on the trainer GPU; the batch the next gather reads
+  uint64_t *dyn_stamps_ = nullptr;
+  uint32_t dyn_seq_ = 0;
+  Batch *dyn_prev_ = nullptr;
   std::vector<size_t> max_input_, max_edges_;
   // shuffler
   std::vector<uint32_t> shuf_host_;

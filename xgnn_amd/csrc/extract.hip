@@ -92,6 +92,36 @@ struct CachedRows {
   }
 };
 
+// dynamic_cache (arch4): a row the previous batch also had is read from that batch's feature buffer (HBM), every other
+// row from the device-mapped host table.  The stamp word of a node is (seq << 32) | slot of its last batch; prev_seq = 0:
+// no previous batch (seq 1, or a reset table), nothing hits.
+struct DynamicRows {
+  const uint32_t *nodes;
+  const unsigned long long *stamps;
+  const char *prev;
+  const char *host;
+  uint64_t row_bytes;
+  uint32_t prev_seq;
+  static constexpr bool kTiers = false;
+  __device__ __forceinline__ const char *row(uint64_t i, uint32_t &tier) const {
+    const uint32_t node = nodes[i];
+    const unsigned long long e = stamps[node];
+    const bool hit = prev_seq != 0 && (uint32_t)(e >> 32) == prev_seq;
+    tier = hit ? 0u : kTierHost;
+    return hit ? prev + (uint64_t)(uint32_t)e * row_bytes : host + (uint64_t)node * row_bytes;
+  }
+};
+
+// after batch seq's gather: its rows are in ITS feature buffer at their positions
+__global__ __launch_bounds__(kBlock) void k_dynamic_publish(unsigned long long *__restrict__ stamps,
+                                                            const uint32_t *__restrict__ nodes, Count n_arg,
+                                                            uint32_t seq) {
+  const uint64_t n = n_arg.get();
+  const unsigned long long hi = (unsigned long long)seq << 32;
+  for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock)
+    stamps[nodes[i]] = hi | (uint32_t)i;
+}
+
 // All tiers of the store in one locator (ggms_extract_tiered): slot = table ? table[node] : node;
 //   kEmptyKey            -> host tier, row `node` of the device-mapped host table      (GPUExtractMissData)
 //   slot <  num_replica  -> this GPU's replica of the hottest rows, row `slot`         (hot-row replication)
@@ -522,6 +552,39 @@ int ggms_extract_tiered(void *out, const ggms_id_t *nodes, size_t num_nodes, con
                   tiers->my_part, tiers->host_row_mask ? tiers->host_row_mask : 0xffffffffu};
   return launch_gather((char *)out, rows, nullptr, num_nodes, count_of(num_nodes, num_nodes_dev), row_bytes, cb,
                        tier_rows_dev, to_stream(stream));
+}
+
+int ggms_dynamic_cache_reset(uint64_t *stamps, size_t num_node, ggms_stream_t stream) {
+  GGMS_CHECK_ARG(stamps || num_node == 0);
+  if (num_node) GGMS_HIP(hipMemsetAsync(stamps, 0, num_node * sizeof(uint64_t), to_stream(stream)));
+  return GGMS_OK;
+}
+
+int ggms_extract_dynamic(void *out, const ggms_id_t *nodes, size_t num_nodes, const uint64_t *num_nodes_dev,
+                         const uint64_t *stamps, uint32_t seq, const void *prev_feat, const void *host_feat,
+                         size_t dim, int dtype, uint64_t *num_miss_dev, ggms_stream_t stream) {
+  const size_t es = ggms_dtype_bytes(dtype);
+  GGMS_CHECK_ARG(es != 0 && dim != 0 && seq != 0);
+  if (num_nodes == 0) return GGMS_OK;
+  GGMS_CHECK_ARG(out && nodes && stamps && host_feat && (seq == 1 || prev_feat));
+  GGMS_CHECK_ARG(num_nodes < (1ull << 32)); // slots travel in the low half of a stamp word
+  const size_t row_bytes = dim * es;
+  const int cb = pick_chunk(row_bytes, (uintptr_t)out | (uintptr_t)host_feat | (uintptr_t)prev_feat);
+  DynamicRows rows{nodes, (const unsigned long long *)stamps, (const char *)prev_feat, (const char *)host_feat,
+                   row_bytes, seq - 1};
+  return launch_gather((char *)out, rows, nullptr, num_nodes, count_of(num_nodes, num_nodes_dev), row_bytes, cb,
+                       num_miss_dev, to_stream(stream));
+}
+
+int ggms_dynamic_cache_publish(uint64_t *stamps, const ggms_id_t *nodes, size_t num_nodes,
+                               const uint64_t *num_nodes_dev, uint32_t seq, ggms_stream_t stream) {
+  GGMS_CHECK_ARG(seq != 0);
+  if (num_nodes == 0) return GGMS_OK;
+  GGMS_CHECK_ARG(stamps && nodes && num_nodes < (1ull << 32));
+  hipLaunchKernelGGL(k_dynamic_publish, dim3(grid_for(num_nodes, kBlock)), dim3(kBlock), 0, to_stream(stream),
+                     (unsigned long long *)stamps, nodes, count_of(num_nodes, num_nodes_dev), seq);
+  GGMS_LAUNCH_CHECK();
+  return GGMS_OK;
 }
 
 // ---- launch timer ---------------------------------------------------------------------------------------------------

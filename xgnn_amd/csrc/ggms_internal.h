@@ -131,6 +131,14 @@ int ht_fill_impl(const ggms_hashtable_t *ht, const uint32_t *input, size_t n_max
                  bool inserted, ScanArea scan, uint64_t *mirror_a, uint64_t *mirror_b, hipStream_t s, uint32_t *mapped,
                  const BatchPrologue *prologue, int rest, const uint64_t *n_dev_for_rest);
 
+// prefetch.hip: arch4's expansion list.  pre: max_nodes words; scan_words: prefetch_scan_words(max_nodes); the scan's
+// total goes to *total_dev and *need_dev; a total above max_edges sets GGMS_STATUS_PREFETCH_FULL in *status and zeroes
+// *total_dev and *num_nodes_dev.  keys: max_edges words.
+size_t prefetch_scan_words(size_t max_nodes);
+int prefetch_list_impl(const GraphView &g, const uint32_t *nodes, size_t max_nodes, uint64_t *num_nodes_dev,
+                       uint32_t *pre, uint32_t *scan_words, uint32_t *status, uint64_t *total_dev, size_t max_edges,
+                       uint64_t *need_dev, uint32_t *keys, hipStream_t s);
+
 // extract.hip: hands the launch timer armed on this thread (include/ggms.h) to the launch about to be issued -- its
 // start / stop events for hipExtLaunchKernel -- and disarms it; false if none is armed
 bool take_armed_timer(hipEvent_t *start, hipEvent_t *stop);

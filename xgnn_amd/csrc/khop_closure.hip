@@ -104,23 +104,6 @@ struct StorePrefix {
   __device__ __forceinline__ void operator()(uint64_t i, uint32_t, uint32_t excl) const { pre[i] = excl; }
 };
 
-// the last frontier index i with pre[i] <= e (pre[0] = 0 <= e): one wave, 64 probes per step
-__device__ __forceinline__ uint64_t wave_find_node(const uint32_t *pre, uint64_t F, uint64_t e) {
-  const uint32_t lane = lane_id();
-  uint64_t lo = 0, len = F;
-  while (len > kWave) {
-    const uint64_t step = (len + kWave - 1) / kWave;
-    const uint64_t idx = lo + lane * step;
-    const bool ok = idx < lo + len && pre[idx] <= e;
-    const uint32_t c = (uint32_t)__popcll(__ballot(ok)); // lanes 0 .. c-1 (pre is non-decreasing; lane 0 always)
-    const uint64_t end = lo + len;
-    lo += (uint64_t)(c - 1) * step;
-    len = end - lo < step ? end - lo : step;
-  }
-  const bool ok = lane < len && pre[lo + lane] <= e;
-  return lo + (uint64_t)__popcll(__ballot(ok)) - 1;
-}
-
 __global__ __launch_bounds__(kBlock) void k_closure_expand(GraphView g, ClosureOut o, const uint32_t *__restrict__ pre,
                                                            const uint64_t *hop_offsets, uint32_t h,
                                                            const ClosureCtl *ctl) {

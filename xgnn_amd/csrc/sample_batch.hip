@@ -34,6 +34,8 @@
 // ggms_sample_extra_t.rng_wait / rng_done chain only the sampler kernels, which share
 // the RNG pool, in batch order.
 #include <algorithm>
+#include <functional>
+#include <vector>
 
 #include "ggms_internal.h"
 #include "tile_scan.h"
@@ -199,13 +201,15 @@ static size_t sampler_ws_words(int sample_type, const BatchCaps &c, const size_t
 // ---- workspace layout of one batch (uint32 words; every piece starts 16-byte aligned) --------------------------
 struct BatchLayout {
   size_t seed_local, samp_ws, tmp_dst[16], cand, lost, scan, chunk, total;
+  size_t pf_keys, pf_local, pf_pre, pf_scan, pf_total; // ggms_sample_batch_prefetch only
   size_t dedup_items; // entries of cand / lost
   size_t scan_tiles;  // descriptors the scans of the batch may use (cleared by the batch prologue)
 };
 static inline size_t up4(size_t w) { return (w + 3) & ~(size_t)3; }
 
+// pf_edges: the prefetching batch's expansion capacity (its keys are one more fill of the batch); 0 = none
 static BatchLayout layout_of(int sample_type, size_t num_seeds, const size_t *fanouts, uint32_t L, const BatchCaps &c,
-                             const ggms_sample_extra_t *extra) {
+                             const ggms_sample_extra_t *extra, size_t pf_edges = 0) {
   BatchLayout l{};
   size_t w = 0;
   l.seed_local = w;  w += up4(num_seeds + 16);
@@ -214,7 +218,7 @@ static BatchLayout layout_of(int sample_type, size_t num_seeds, const size_t *fa
     l.tmp_dst[i] = w;
     w += up4(c.max_edges[i] + 16);
   }
-  l.dedup_items = std::max(c.max_e_all, num_seeds);
+  l.dedup_items = std::max({c.max_e_all, num_seeds, pf_edges});
   l.cand = w;        w += up4(l.dedup_items + 16);          // hashed layout: bucket positions
   l.lost = w;        w += up4(2 * (l.dedup_items + 16));    // 64-bit tags
   // ONE scan area for the batch: sampler offsets (tiles of 128 seeds), owner scans (tiles of 2048 items), the
@@ -228,6 +232,13 @@ static BatchLayout layout_of(int sample_type, size_t num_seeds, const size_t *fa
   // cleared by the batch prologue too
   l.chunk = w;
   w += up4(chunk_desc_words() + (size_t)kTicketSets * kTicketWords);
+  if (pf_edges) { // the expansion: its keys, their local ids, the degree scan over the set after L - 1 layers
+    l.pf_keys = w;   w += up4(pf_edges + 16);
+    l.pf_local = w;  w += up4(pf_edges + 16);
+    l.pf_pre = w;    w += up4(c.max_input[0] + 16);
+    l.pf_scan = w;   w += up4(prefetch_scan_words(c.max_input[0]) + 16);
+    l.pf_total = w;  w += 4;
+  }
   l.total = w;
   return l;
 }
@@ -239,22 +250,18 @@ size_t ggms_sample_batch_workspace_bytes(int sample_type, size_t num_seeds, cons
   return layout_of(sample_type, num_seeds, fanouts, num_layer, c, extra).total * sizeof(uint32_t) + 16;
 }
 
-int ggms_sample_batch(int sample_type, const ggms_graph_t *graph, const ggms_id_t *seeds, size_t num_seeds,
-                      const size_t *fanouts, uint32_t num_layer, ggms_hashtable_t *ht, void *states,
-                      size_t num_states, ggms_id_t *const *row, ggms_id_t *const *col, uint64_t *counts_dev,
-                      const ggms_sample_extra_t *extra, void *workspace, size_t workspace_bytes,
-                      ggms_stream_t stream) {
-  GGMS_CHECK_ARG(graph && fanouts && ht && row && col && counts_dev);
-  GGMS_CHECK_ARG(num_layer >= 1 && num_layer <= 16);
-  GGMS_CHECK_ARG(sample_type >= GGMS_KHOP0 && sample_type <= GGMS_KHOP3);
-  GGMS_CHECK_ARG(num_seeds == 0 || seeds);
-  GGMS_CHECK_ARG(workspace && workspace_bytes >= ggms_sample_batch_workspace_bytes(sample_type, num_seeds, fanouts,
-                                                                                   num_layer, extra));
-  GGMS_CHECK_ARG(sample_type != GGMS_RANDOM_WALK || (extra && extra->data)); // the visit counts of every layer
-  hipStream_t s = to_stream(stream);
+// ggms_sample_batch_prefetch's part of a batch (NULL: a plain ggms_sample_batch)
+struct Prefetch {
+  size_t max_edges;
+  hipEvent_t start, final;
+};
+
+// the body of ggms_sample_batch and ggms_sample_batch_prefetch; every argument check is the caller's
+static int sample_batch_impl(int sample_type, const ggms_graph_t *graph, const ggms_id_t *seeds, size_t num_seeds,
+                             const size_t *fanouts, uint32_t num_layer, ggms_hashtable_t *ht, void *states,
+                             size_t num_states, ggms_id_t *const *row, ggms_id_t *const *col, uint64_t *counts_dev,
+                             const ggms_sample_extra_t *extra, void *workspace, const Prefetch *pf, hipStream_t s) {
   const BatchCaps c = caps_of(num_seeds, fanouts, num_layer);
-  GGMS_CHECK_ARG(c.max_input[0] + c.max_edges[0] <= ht->n2o_size);
-  GGMS_CHECK_ARG(c.max_input[0] + c.max_edges[0] < (1ull << 32) - 4); // indices and 2 + local id fit 32 bits
   // what every layer's sampler call shares; the loop below fills in the rest
   SampleLayer L{graph, nullptr, 0, 0, nullptr, nullptr, nullptr, (uint32_t *)states, nullptr, s};
   if (extra) {
@@ -271,7 +278,8 @@ int ggms_sample_batch(int sample_type, const ggms_graph_t *graph, const ggms_id_
     if (rc != GGMS_OK) return rc;
   }
 
-  const BatchLayout lay = layout_of(sample_type, num_seeds, fanouts, num_layer, c, extra);
+  const BatchLayout lay = layout_of(sample_type, num_seeds, fanouts, num_layer, c, extra,
+                                    pf ? std::max<size_t>(pf->max_edges, 1) : 0);
   uint32_t *w = (uint32_t *)(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
   uint32_t *seed_local = w + lay.seed_local;
   uint32_t *samp_ws = w + lay.samp_ws;
@@ -292,7 +300,7 @@ int ggms_sample_batch(int sample_type, const ggms_graph_t *graph, const ggms_id_
   if (!view_of(graph, L.g)) return GGMS_ERR_INVALID;
   // hash_table->Reset (dist_loops.cc:105): a new version stamp; the item count is zeroed by the prologue below
   if (ht->version >= 0x7ffffff0u) {
-    int rc0 = ggms_hashtable_init(ht, stream);
+    int rc0 = ggms_hashtable_init(ht, (ggms_stream_t)s);
     if (rc0 != GGMS_OK) return rc0;
   }
   ht->version += 1;
@@ -359,20 +367,47 @@ int ggms_sample_batch(int sample_type, const ggms_graph_t *graph, const ggms_id_
   size_t job_items = 0;
   for (int i = (int)num_layer - 1; i >= 0; --i) {
     const bool first = (i == (int)num_layer - 1);
+    const bool last_pf = pf && i == 0; // the prefetching batch's last layer (num_layer >= 2: never the first)
     uint32_t *tmp_dst = w + lay.tmp_dst[i];
     const size_t n_max = c.max_input[i], e_max = c.max_edges[i];
-    const Count n = first ? count_of(num_seeds) : count_of32(n_max, ht->num_items_dev);
+    // the last layer of a prefetching batch samples from the set BEFORE the expansion: its size as the previous fill
+    // recorded it (num_dst(0)), not the table's count
+    const Count n = first ? count_of(num_seeds)
+                          : (last_pf ? count_of(n_max, counts_dev + 2) : count_of32(n_max, ht->num_items_dev));
     uint64_t *num_edge = counts_dev + 3 * i + 0;
     uint64_t *num_src = counts_dev + 3 * i + 1;                       // unique nodes after this layer (:304)
     uint64_t *next_dst = i > 0 ? counts_dev + 3 * (i - 1) + 2         // = next layer's frontier size (:305)
                                : counts_dev + 3 * num_layer;          // = number of input nodes
     // batch order on the shared RNG pool (and on khop2's CSR): only the sampler kernels are ordered
     if (first && extra && extra->rng_wait) GGMS_HIP(hipStreamWaitEvent(s, (hipEvent_t)extra->rng_wait, 0));
-    if (i == 0 && extra && extra->heavy_wait) GGMS_HIP(hipStreamWaitEvent(s, (hipEvent_t)extra->heavy_wait, 0));
-    di.base = next_base; // this layer's edges take the indices [base, base + e_max)
     di.w = (unsigned long long *)ht->o2n;
     di.version = ht->version;
-    const bool inserted = ht->direct != 0 && e_max != 0 && layer_enters_output(sample_type);
+    if (last_pf) { // the expansion: one more fill of the batch, over every neighbour of n2o[0, k)
+      if (pf->start) GGMS_HIP(hipEventRecord(pf->start, s));
+      uint32_t *keys = w + lay.pf_keys, *local = w + lay.pf_local;
+      uint64_t *total = reinterpret_cast<uint64_t *>(w + lay.pf_total);
+      rc = prefetch_list_impl(L.g, ht->n2o, n_max, counts_dev + 2, w + lay.pf_pre, w + lay.pf_scan, scan.status, total,
+                              pf->max_edges, counts_dev + 3 * num_layer + 6, keys, s);
+      if (rc != GGMS_OK) return rc;
+      if (pf->max_edges == 0) { // no list to enter: the set is final as it is
+        hipLaunchKernelGGL(k_record, dim3(1), dim3(64), 0, s, counts_dev + 1, count_of32(0, ht->num_items_dev));
+        hipLaunchKernelGGL(k_record, dim3(1), dim3(64), 0, s, counts_dev + 3 * num_layer, count_of32(0, ht->num_items_dev));
+        GGMS_LAUNCH_CHECK();
+      } else { // new nodes join n2o in first-occurrence order; num_src(0) and the input count get the new size
+        di.base = next_base;
+        rc = ht_fill_impl(ht, keys, pf->max_edges, count_of(pf->max_edges, total), di, false, scan, counts_dev + 1,
+                          counts_dev + 3 * num_layer, s, local, nullptr, kRestDefer, nullptr);
+        if (rc != GGMS_OK) return rc;
+        di.map.base[di.map.n] = next_base; // the last layer's look-ups find the new nodes' ids in `local`
+        di.map.arr[di.map.n] = local;
+        ++di.map.n;
+        next_base += (uint32_t)pf->max_edges;
+      }
+      if (pf->final) GGMS_HIP(hipEventRecord(pf->final, s));
+    }
+    if (i == 0 && extra && extra->heavy_wait) GGMS_HIP(hipStreamWaitEvent(s, (hipEvent_t)extra->heavy_wait, 0));
+    di.base = next_base; // this layer's edges take the indices [base, base + e_max)
+    const bool inserted = !last_pf && ht->direct != 0 && e_max != 0 && layer_enters_output(sample_type);
     if (inserted) di.tag = next_dedup_tag();
     if (n_max == 0) {
       GGMS_HIP(hipMemsetAsync(num_edge, 0, sizeof(uint64_t), s));
@@ -400,6 +435,15 @@ int ggms_sample_batch(int sample_type, const ggms_graph_t *graph, const ggms_id_
       GGMS_LAUNCH_CHECK();
       continue;
     }
+    if (last_pf) { // every sampled neighbour is in the table already: row = its id, looked up with the other layers'
+      GGMS_HIP(hipMemsetAsync(row[i], 0xff, e_max * sizeof(uint32_t), s));
+      jobs.row[num_jobs] = row[i];
+      jobs.key[num_jobs] = tmp_dst;
+      jobs.num[num_jobs] = num_edge;
+      ++num_jobs;
+      job_items = std::max(job_items, e_max);
+      continue;
+    }
     // FillWithDuplicates (:279) + the dst half of GPUMapEdges (:296): row[i] = local id of every sampled neighbour
     // (direct table: the instances that do not own their key are resolved for all layers at once, below)
     rc = ht_fill_impl(ht, tmp_dst, e_max, ne, di, inserted, scan, num_src, next_dst, s, row[i], nullptr,
@@ -419,6 +463,87 @@ int ggms_sample_batch(int sample_type, const ggms_graph_t *graph, const ggms_id_
   }
   // the rest of GPUMapEdges' dst half for every layer + the batch's status word (counts_dev[3 L + 1])
   return launch_map_rest_all(ht, jobs, num_jobs, job_items, di.map, counts_dev + 3 * num_layer + 1, s);
+}
+
+int ggms_sample_batch(int sample_type, const ggms_graph_t *graph, const ggms_id_t *seeds, size_t num_seeds,
+                      const size_t *fanouts, uint32_t num_layer, ggms_hashtable_t *ht, void *states,
+                      size_t num_states, ggms_id_t *const *row, ggms_id_t *const *col, uint64_t *counts_dev,
+                      const ggms_sample_extra_t *extra, void *workspace, size_t workspace_bytes,
+                      ggms_stream_t stream) {
+  GGMS_CHECK_ARG(graph && fanouts && ht && row && col && counts_dev);
+  GGMS_CHECK_ARG(num_layer >= 1 && num_layer <= 16);
+  GGMS_CHECK_ARG(sample_type >= GGMS_KHOP0 && sample_type <= GGMS_KHOP3);
+  GGMS_CHECK_ARG(num_seeds == 0 || seeds);
+  GGMS_CHECK_ARG(workspace && workspace_bytes >= ggms_sample_batch_workspace_bytes(sample_type, num_seeds, fanouts,
+                                                                                   num_layer, extra));
+  GGMS_CHECK_ARG(sample_type != GGMS_RANDOM_WALK || (extra && extra->data)); // the visit counts of every layer
+  const BatchCaps c = caps_of(num_seeds, fanouts, num_layer);
+  GGMS_CHECK_ARG(c.max_input[0] + c.max_edges[0] <= ht->n2o_size);
+  GGMS_CHECK_ARG(c.max_input[0] + c.max_edges[0] < (1ull << 32) - 4); // indices and 2 + local id fit 32 bits
+  return sample_batch_impl(sample_type, graph, seeds, num_seeds, fanouts, num_layer, ht, states, num_states, row, col,
+                           counts_dev, extra, workspace, nullptr, to_stream(stream));
+}
+
+// ---- arch4: the prefetching batch ----------------------------------------------------------------------------------
+int ggms_sample_batch_prefetch_capacity(size_t num_seeds, const size_t *fanouts, uint32_t num_layer,
+                                        const ggms_id_t *indptr, size_t num_node, size_t max_edges_budget,
+                                        size_t *max_prefetch_edges, size_t *max_input_nodes) {
+  GGMS_CHECK_ARG(fanouts && num_layer >= 2 && num_layer <= 16 && (indptr || num_node == 0));
+  const BatchCaps c = caps_of(num_seeds, fanouts, num_layer);
+  const size_t k = std::min(c.max_input[0], num_node); // unique nodes after L - 1 layers
+  // the k largest degrees bound the expansion's edges (every node of the set contributes its whole list)
+  std::vector<uint32_t> deg(num_node);
+  for (size_t v = 0; v < num_node; ++v) deg[v] = indptr[v + 1] - indptr[v];
+  if (k < num_node) std::nth_element(deg.begin(), deg.begin() + k, deg.end(), std::greater<uint32_t>());
+  size_t top = 0;
+  for (size_t v = 0; v < k; ++v) top += deg[v];
+  const size_t e = std::min(top, max_edges_budget);
+  if (max_prefetch_edges) *max_prefetch_edges = e;
+  if (max_input_nodes) *max_input_nodes = std::min(num_node, k + e);
+  return GGMS_OK;
+}
+
+size_t ggms_sample_batch_prefetch_workspace_bytes(int sample_type, size_t num_seeds, const size_t *fanouts,
+                                                  uint32_t num_layer, const ggms_sample_extra_t *extra,
+                                                  size_t max_prefetch_edges) {
+  if (!fanouts || num_layer < 2 || num_layer > 16) return 0;
+  const BatchCaps c = caps_of(num_seeds, fanouts, num_layer);
+  // pf_edges = 0 would drop the pieces: keep them (4 words each) for an expansion that can have no edge
+  return layout_of(sample_type, num_seeds, fanouts, num_layer, c, extra, std::max<size_t>(max_prefetch_edges, 1)).total *
+             sizeof(uint32_t) + 16;
+}
+
+int ggms_sample_batch_prefetch(int sample_type, const ggms_graph_t *graph, const ggms_id_t *seeds, size_t num_seeds,
+                               const size_t *fanouts, uint32_t num_layer, ggms_hashtable_t *ht, void *states,
+                               size_t num_states, ggms_id_t *const *row, ggms_id_t *const *col, uint64_t *counts_dev,
+                               const ggms_sample_extra_t *extra, size_t max_prefetch_edges, ggms_event_t expand_start,
+                               ggms_event_t input_final, void *workspace, size_t workspace_bytes,
+                               ggms_stream_t stream) {
+  // the reference's switch (cuda_loops.cc:347-377) builds the dynamic-cache batch for these three samplers only
+  if (sample_type != GGMS_KHOP0 && sample_type != GGMS_KHOP1 && sample_type != GGMS_WEIGHTED_KHOP) {
+    set_error("ggms_sample_batch_prefetch: sample type %d is not supported (khop0, khop1 and weighted_khop only)",
+              sample_type);
+    return GGMS_ERR_INVALID;
+  }
+  // without a second-to-last layer the reference never enters the last layer's samples, so it cannot remap them
+  if (num_layer < 2 || num_layer > 16) {
+    set_error("ggms_sample_batch_prefetch: num_layer %u (2 .. 16 layers: the expansion follows the second-to-last)",
+              num_layer);
+    return GGMS_ERR_INVALID;
+  }
+  GGMS_CHECK_ARG(graph && fanouts && ht && row && col && counts_dev);
+  GGMS_CHECK_ARG(ht->direct); // one word per node id: the superset can be far beyond PredictNumNodes
+  GGMS_CHECK_ARG(num_seeds == 0 || seeds);
+  GGMS_CHECK_ARG(workspace && workspace_bytes >= ggms_sample_batch_prefetch_workspace_bytes(
+                                                     sample_type, num_seeds, fanouts, num_layer, extra, max_prefetch_edges));
+  const BatchCaps c = caps_of(num_seeds, fanouts, num_layer);
+  const size_t k = c.max_input[0];
+  GGMS_CHECK_ARG(std::min<size_t>(graph->num_node, k + max_prefetch_edges) <= ht->n2o_size);
+  // the batch's index space: seeds, the first L - 1 layers, the expansion, the last layer
+  GGMS_CHECK_ARG(k + max_prefetch_edges + c.max_edges[0] < (1ull << 32) - 4);
+  const Prefetch pf{max_prefetch_edges, (hipEvent_t)expand_start, (hipEvent_t)input_final};
+  return sample_batch_impl(sample_type, graph, seeds, num_seeds, fanouts, num_layer, ht, states, num_states, row, col,
+                           counts_dev, extra, workspace, &pf, to_stream(stream));
 }
 
 } // extern "C"

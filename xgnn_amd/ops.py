@@ -686,3 +686,102 @@ class BatchSampler:
             layers.append(dict(row=self.row[i][:ne], col=self.col[i][:ne], num_src=c[3 * i + 1], num_dst=c[3 * i + 2],
                                data=self.data[i][:ne] if self.data is not None else None))
         return dict(layers=layers, input_nodes=self._n2o[: c[3 * self.L]])
+
+
+def prefetch_capacity(num_seeds, fanouts, indptr_host, max_edges_budget):
+    """ggms_sample_batch_prefetch_capacity: (max_prefetch_edges, max_input_nodes) of an arch4 batch of num_seeds seeds.
+    indptr_host: the host CSR offsets (uint32 / int32 numpy array of num_node + 1 entries)."""
+    L = len(fanouts)
+    f = (C.c_size_t * L)(*[int(x) for x in fanouts])
+    ip = np.ascontiguousarray(indptr_host).view(np.uint32)
+    me, mi = C.c_size_t(0), C.c_size_t(0)
+    check(lib().ggms_sample_batch_prefetch_capacity(int(num_seeds), f, L, ip.ctypes.data_as(C.c_void_p), ip.size - 1,
+                                                    int(max_edges_budget), C.byref(me), C.byref(mi)),
+          "ggms_sample_batch_prefetch_capacity")
+    return me.value, mi.value
+
+
+class PrefetchBatchSampler:
+    """arch4's batch (DoGPUSampleDyCache, cuda_loops.cc:294-524) through ggms_sample_batch_prefetch: the layers of
+    BatchSampler, the expansion after the second-to-last layer, the last layer sampled from the set before it.
+    One slot, one pipeline; the RNG pool is BatchSampler's for the same arguments."""
+
+    def __init__(self, graph, indptr_host, fanouts, batch_size, sample_type=KHOP0, seed=0, device="cuda",
+                 prob_table=None, alias_table=None, max_edges_budget=1 << 26, max_seeds=None):
+        self.graph, self.fanouts, self.sample_type = graph, [int(f) for f in fanouts], sample_type
+        L = self.L = len(self.fanouts)
+        self._f = (C.c_size_t * L)(*self.fanouts)
+        self.max_seeds = int(batch_size * 1.25) + 1 if max_seeds is None else int(max_seeds)
+        mi, me, mu = (C.c_size_t * L)(), (C.c_size_t * L)(), C.c_size_t(0)
+        check(lib().ggms_sample_batch_capacity(self.max_seeds, self._f, L, mi, me, C.byref(mu)), "capacity")
+        self.max_input, self.max_edges = list(mi), list(me)
+        self.max_prefetch_edges, self.max_unique = prefetch_capacity(self.max_seeds, self.fanouts, indptr_host,
+                                                                     max_edges_budget)
+        self.ht = OrderedHashTable(self.max_unique, device, num_node=graph.c.num_node)
+        nstates = lib().ggms_random_states_count(sample_type, self._f, L, self.max_seeds, 0)
+        nstates = max(nstates, (max(self.max_input) + 127) // 128 * 8, (max(self.max_input) + 1023) // 1024 * 256)
+        self.states = random_states(nstates, seed, device) if sample_type != KHOP0 else None
+        self.row = [torch.empty(max(4, e), dtype=torch.int32, device=device) for e in self.max_edges]
+        self.col = [torch.empty(max(4, e), dtype=torch.int32, device=device) for e in self.max_edges]
+        self._rows = (C.c_void_p * L)(*[t.data_ptr() for t in self.row])
+        self._cols = (C.c_void_p * L)(*[t.data_ptr() for t in self.col])
+        self.counts = torch.zeros(3 * L + 8, dtype=torch.int64, device=device)
+        self._keep = (prob_table, alias_table)
+        self._extra = _lib.SampleExtra()
+        self._extra.prob_table = prob_table.data_ptr() if prob_table is not None else None
+        self._extra.alias_table = alias_table.data_ptr() if alias_table is not None else None
+        wsb = lib().ggms_sample_batch_prefetch_workspace_bytes(sample_type, self.max_seeds, self._f, L,
+                                                               C.byref(self._extra), self.max_prefetch_edges)
+        self.ws = _workspace(wsb, device)
+
+    def sample(self, seeds, distinct=False, input_final=None):
+        """Enqueue one batch; input_final (torch.cuda.Event, optional) is recorded once the input nodes are final."""
+        _i32(seeds)
+        n = seeds.numel()
+        assert n <= self.max_seeds
+        self._extra.seeds_distinct = 1 if distinct else 0
+        ev = C.c_void_p(input_final.cuda_event) if input_final is not None else None
+        check(lib().ggms_sample_batch_prefetch(self.sample_type, C.byref(self.graph.c), _ptr(seeds), n, self._f, self.L,
+                                               C.byref(self.ht.c), _ptr(self.states),
+                                               self.states.shape[0] if self.states is not None else 0, self._rows,
+                                               self._cols, _ptr(self.counts), C.byref(self._extra),
+                                               self.max_prefetch_edges, None, ev, _ptr(self.ws), self.ws.numel() * 4,
+                                               _stream()),
+              "ggms_sample_batch_prefetch")
+
+    def result(self):
+        """Sync and slice the outputs; raises on a non-zero batch status (GGMS_STATUS_PREFETCH_FULL: expansion over
+        capacity, `needed` edges)."""
+        c = self.counts.cpu().tolist()
+        L = self.L
+        if c[3 * L + 1]:
+            check_device_status("ggms_sample_batch_prefetch")
+            raise _lib.GgmsError(f"ggms_sample_batch_prefetch: device status {c[3 * L + 1]:#x} "
+                                 f"(expansion needed {c[3 * L + 6]} edges, capacity {self.max_prefetch_edges})")
+        layers = [dict(row=self.row[i][:c[3 * i]], col=self.col[i][:c[3 * i]], num_src=c[3 * i + 1],
+                       num_dst=c[3 * i + 2]) for i in range(L)]
+        return dict(layers=layers, input_nodes=self.ht.n2o[: c[3 * L]], expansion_edges=c[3 * L + 6])
+
+
+def dynamic_cache_reset(stamps):
+    """dynamic_cache: zero the stamp table (int64, one word per node)."""
+    check(lib().ggms_dynamic_cache_reset(_ptr(stamps), stamps.numel(), _stream()), "ggms_dynamic_cache_reset")
+
+
+def extract_dynamic(out, nodes, stamps, seq, prev_feat, host_feat, num=None, num_dev=None, num_miss=None):
+    """dynamic_cache gather of batch `seq`: rows batch seq - 1 published come from prev_feat, the rest from host_feat."""
+    _require_gpu(out)
+    if num is None:
+        num = nodes.numel()
+    check(lib().ggms_extract_dynamic(_ptr(out), _ptr(nodes), num, _ptr(num_dev), _ptr(stamps), int(seq), _ptr(prev_feat),
+                                     _ptr(host_feat), _dim_of(out), DTYPE_CODE[out.dtype], _ptr(num_miss), _stream()),
+          "ggms_extract_dynamic")
+    return out
+
+
+def dynamic_cache_publish(stamps, nodes, seq, num=None, num_dev=None):
+    """stamps[nodes[i]] = (seq << 32) | i: batch seq's rows are in its own feature buffer."""
+    if num is None:
+        num = nodes.numel()
+    check(lib().ggms_dynamic_cache_publish(_ptr(stamps), _ptr(nodes), num, _ptr(num_dev), int(seq), _stream()),
+          "ggms_dynamic_cache_publish")
