@@ -80,6 +80,24 @@ LEAF = [  # (name, sample type, N, graph kwargs, fanouts, seeds)
 ]
 
 
+def _batch_equals_the_replay(bs, code, ip, ix, seeds, fan, states, kw, distinct, trial):
+    """One batch of `bs` against prefetch_replay of the oracle's plain batch (which advances `states`); returns the
+    replay."""
+    bs.sample(torch.from_numpy(seeds.view(np.int32)).to(bs.counts.device), distinct=distinct)
+    got = bs.result()
+    want = prefetch_replay(oracle.do_sample(code, ip, ix, seeds, fan, states, **kw), ip, ix)
+    assert got["expansion_edges"] == want["expansion_edges"]
+    np.testing.assert_array_equal(got["input_nodes"].cpu().numpy().view(np.uint32), want["input_nodes"])
+    for i, w in enumerate(want["layers"]):
+        g = got["layers"][i]
+        np.testing.assert_array_equal(g["row"].cpu().numpy().view(np.uint32), w["row"], err_msg=f"row{i} {trial}")
+        np.testing.assert_array_equal(g["col"].cpu().numpy().view(np.uint32), w["col"], err_msg=f"col{i} {trial}")
+        assert (g["num_src"], g["num_dst"]) == (w["num_src"], w["num_dst"]), (i, trial)
+    if states is not None:
+        assert bs.states.cpu().numpy().tobytes() == states.tobytes(), trial
+    return want
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", LEAF, ids=[c[0] for c in LEAF])
 def test_prefetch_sampler_equals_the_replay(case):
@@ -103,18 +121,64 @@ def test_prefetch_sampler_equals_the_replay(case):
         seeds = rs.permutation(N)[:ns].astype(np.uint32) if distinct else rs.randint(0, N, ns).astype(np.uint32)
         if hub is not None and hub not in seeds:  # (a distinct list must not get it twice)
             seeds[0] = hub
-        bs.sample(torch.from_numpy(seeds.view(np.int32)).to(dev), distinct=distinct)
-        got = bs.result()
-        want = prefetch_replay(oracle.do_sample(CODE[st], ip, ix, seeds, fan, states, **kw), ip, ix)
-        assert got["expansion_edges"] == want["expansion_edges"]
-        np.testing.assert_array_equal(got["input_nodes"].cpu().numpy().view(np.uint32), want["input_nodes"])
-        for i, w in enumerate(want["layers"]):
-            g = got["layers"][i]
-            np.testing.assert_array_equal(g["row"].cpu().numpy().view(np.uint32), w["row"], err_msg=f"row{i} {trial}")
-            np.testing.assert_array_equal(g["col"].cpu().numpy().view(np.uint32), w["col"], err_msg=f"col{i} {trial}")
-            assert (g["num_src"], g["num_dst"]) == (w["num_src"], w["num_dst"]), (i, trial)
-        if states is not None:
-            assert bs.states.cpu().numpy().tobytes() == states.tobytes(), trial
+        _batch_equals_the_replay(bs, CODE[st], ip, ix, seeds, fan, states, kw, distinct, trial)
+
+
+def _csr_of(N, lists):
+    """CSR of N nodes from {node: neighbours}; every other node has no list."""
+    deg = np.zeros(N, np.int64)
+    for v, nb in lists.items():
+        deg[v] = len(nb)
+    ip = np.concatenate([[0], np.cumsum(deg)]).astype(np.uint32)
+    ix = np.concatenate([np.asarray(lists[v], np.uint32) for v in sorted(lists)] + [np.zeros(0, np.uint32)])
+    return ip, ix
+
+
+def _empty_run():
+    """Seeds in order: a node of degree 1, 3000 nodes without a list, a node of degree 3.  With distinct seeds the
+    unique list starts in seed order, so the expansion's first (and only) edge tile meets a run of empty lists longer
+    than the walk stages at once: the tile takes a second round."""
+    rs = np.random.RandomState(21)
+    lists = {0: [3500], 3001: [3600, 3601, 3602]}
+    lists.update({v: rs.randint(3002, 4000, 4) for v in range(3002, 4000)})
+    ip, ix = _csr_of(4000, lists)
+    return ip, ix, np.arange(3002, dtype=np.uint32)
+
+
+def _no_edges():
+    """Every seed without a list: the expansion has no edge at all."""
+    rs = np.random.RandomState(22)
+    ip, ix = _csr_of(300, {v: rs.randint(0, 300, 3) for v in range(100, 300)})
+    return ip, ix, np.arange(100, dtype=np.uint32)
+
+
+def _full_tiles():
+    """512 seeds of degree 8 whose neighbours are seeds: the expansion is exactly two full edge tiles."""
+    rs = np.random.RandomState(23)
+    ip, ix = _csr_of(600, {v: rs.randint(0, 512, 8) for v in range(512)})
+    return ip, ix, np.arange(512, dtype=np.uint32)
+
+
+WALK = [("empty-run", _empty_run, None), ("no-edges", _no_edges, 0), ("full-tiles", _full_tiles, 4096)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", WALK, ids=[c[0] for c in WALK])
+def test_prefetch_expansion_walk_edge_cases(case):
+    """khop0, two layers, seeds in a fixed order: a second round inside an edge tile, an expansion without edges, and
+    one that ends exactly on a tile boundary -- each equal to the replay, with and without the distinct-seed promise."""
+    from xgnn_amd import ops
+    _, make, edges = case
+    ip, ix, seeds = make()
+    dev = torch.device("cuda", 0)
+    bs = ops.PrefetchBatchSampler(_device_graph(ip, ix, dev), ip, [5, 4], seeds.size, sample_type=ops.KHOP0, seed=9,
+                                  device=dev)
+    for trial, distinct in enumerate([True, False]):
+        want = _batch_equals_the_replay(bs, oracle.KHOP0, ip, ix, seeds, [5, 4], None, {}, distinct, trial)
+        if edges is not None:
+            assert want["expansion_edges"] == edges
+        else:  # the run of empty lists sits inside the list that is expanded, before its last edges
+            assert want["k"] > 3002 and 4 < want["expansion_edges"] < 2048
 
 
 @pytest.mark.gpu

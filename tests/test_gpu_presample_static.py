@@ -135,6 +135,38 @@ def test_closure_freq_counts_each_node_once_per_call(ops):
     ops.check_device_status("khop_closure freq")
 
 
+def _sparse_lists_csr():
+    """Every 50th of 8000 nodes has a list of 20 neighbours, the rest have none."""
+    N = 8000
+    deg = np.zeros(N, np.int64)
+    deg[::50] = 20
+    ip = np.zeros(N + 1, np.uint32)
+    ip[1:] = np.cumsum(deg)
+    return ip, np.random.RandomState(6).randint(0, N, int(ip[-1])).astype(np.uint32)
+
+
+@pytest.mark.gpu
+def test_closure_frontier_with_long_runs_of_empty_lists(ops):
+    """A frontier of 6000 nodes of which every 50th has a list: between two lists of one edge tile lie more frontier
+    nodes than the walk stages at once, so a tile takes several rounds.  Levels equal the BFS, freq counts each closure
+    node once."""
+    ip, ix = _sparse_lists_csr()
+    N = ip.size - 1
+    seeds = np.arange(6000, dtype=np.uint32)
+    want = bfs_levels(ip, ix, seeds, 2)
+    assert want[0].size == 6000 and want[1].size > 0  # the hop-0 frontier is expanded into something new
+    g = ops.DeviceGraph(_dev(ip), _dev(ix))
+    visit = torch.zeros(N, dtype=torch.int32, device="cuda")
+    freq = torch.zeros(N, dtype=torch.int32, device="cuda")
+    got = _closure_levels(ops, g, seeds, 2, visit, 1, freq)
+    for h in range(3):
+        np.testing.assert_array_equal(got[h], want[h], err_msg=f"hop {h}")
+    want_freq = np.zeros(N, np.int64)
+    want_freq[np.concatenate(want)] = 1
+    np.testing.assert_array_equal(freq.cpu().numpy(), want_freq)
+    ops.check_device_status("khop_closure empty runs")
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("P", [2, 3])
 def test_closure_through_topology_shards(ops, P):

@@ -330,22 +330,4 @@ __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t x, uint32_t *s
   return base + incl - x;
 }
 
-// the last index i < F with pre[i] <= e, pre non-decreasing with pre[0] = 0 <= e (the owner of edge e in an edge-tiled
-// walk over a list of neighbour lists: khop_closure.hip, prefetch.hip): one wave, 64 probes per step
-__device__ __forceinline__ uint64_t wave_find_node(const uint32_t *pre, uint64_t F, uint64_t e) {
-  const uint32_t lane = lane_id();
-  uint64_t lo = 0, len = F;
-  while (len > kWave) {
-    const uint64_t step = (len + kWave - 1) / kWave;
-    const uint64_t idx = lo + lane * step;
-    const bool ok = idx < lo + len && pre[idx] <= e;
-    const uint32_t c = (uint32_t)__popcll(__ballot(ok)); // lanes 0 .. c-1 (pre is non-decreasing; lane 0 always)
-    const uint64_t end = lo + len;
-    lo += (uint64_t)(c - 1) * step;
-    len = end - lo < step ? end - lo : step;
-  }
-  const bool ok = lane < len && pre[lo + lane] <= e;
-  return lo + (uint64_t)__popcll(__ballot(ok)) - 1;
-}
-
 } // namespace ggms

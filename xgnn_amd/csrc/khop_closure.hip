@@ -5,20 +5,14 @@
 // far, then a hash-table dedup, with four host syncs per hop.  Here the result is a set, not an ordered unique list, so
 // a node is claimed with one atomic on a direct-indexed stamp word, and only the frontier is expanded:
 //   hop 0      k_closure_seeds: every seed claims its word; the winners are hop 0
-//   hop h > 0  tile_scan over the frontier's degrees (pre[i] = first edge of frontier node i, total on the device),
-//              then k_closure_expand walks the frontier's edges in tiles of kEdgeTile: a workgroup finds the node of its
-//              first edge, stages the list heads of the nodes its tile touches in LDS, and each lane takes kPerThread
-//              edges -- a hub's list is spread over as many workgroups as it has tiles
+//   hop h > 0  the frontier's edges in tiles (edge_tiles.h): a tile_scan over the frontier's degrees (size and edge
+//              total on the device), then k_closure_expand = the shared walk with a sink that claims and appends
 //   boundary   k_closure_mark: hop_offsets[h] = the append cursor, and the size of the next frontier
 // Appends: a lane that wins a word keeps the node in a register; the workgroup sums its winners and takes its range of
 // the closure with ONE atomic per round on the cursor (cdna_hip_programming.md Guideline 12).  No host round trip.
-#include "tile_scan.h"
+#include "edge_tiles.h"
 
 namespace ggms {
-
-constexpr uint32_t kPerThread = 8;
-constexpr uint32_t kEdgeTile = kBlock * kPerThread; // edges (or seeds) per workgroup round
-constexpr uint32_t kWin = kEdgeTile;                // frontier nodes staged per round at most
 
 // workspace: these control words, then pre (num_node words), then the scan area
 struct ClosureCtl {
@@ -88,82 +82,22 @@ __global__ void k_closure_mark(uint64_t *hop_offsets, uint32_t h, ClosureCtl *ct
   ctl->front = end - hop_offsets[h - 1];
 }
 
-// scan value / emit over the frontier: degree of closure[f0 + i]; pre[i] = edges of the frontier nodes before i
-struct FrontierDegree {
-  GraphView g;
-  const uint32_t *closure;
-  const uint64_t *f0;
-  __device__ __forceinline__ uint32_t operator()(uint64_t i) const {
-    uint32_t len;
-    g.neighbours(closure[*f0 + i], len);
-    return len;
-  }
-};
-struct StorePrefix {
-  uint32_t *pre;
-  __device__ __forceinline__ void operator()(uint64_t i, uint32_t, uint32_t excl) const { pre[i] = excl; }
-};
-
+// hop h: the walk over the frontier closure[hop_offsets[h - 1], +ctl->front); a neighbour in range is claimed
 __global__ __launch_bounds__(kBlock) void k_closure_expand(GraphView g, ClosureOut o, const uint32_t *__restrict__ pre,
                                                            const uint64_t *hop_offsets, uint32_t h,
                                                            const ClosureCtl *ctl) {
-  __shared__ uint32_t s_pre[kWin + 1];
-  __shared__ const uint32_t *s_ptr[kWin];
   __shared__ uint32_t smem[kBlock / kWave];
   __shared__ unsigned long long s_base;
-  __shared__ uint64_t s_lo;
   const uint64_t f0 = hop_offsets[h - 1];
   const uint64_t F = ctl->front;
   const uint64_t E = ctl->edges;
-  for (uint64_t t = blockIdx.x; t * kEdgeTile < E; t += gridDim.x) {
-    const uint64_t e0 = t * kEdgeTile;
-    const uint64_t e1 = E - e0 < kEdgeTile ? E : e0 + kEdgeTile;
-    if (threadIdx.x < kWave) {
-      const uint64_t n = wave_find_node(pre, F, e0);
-      if (threadIdx.x == 0) s_lo = n;
-    }
-    __syncthreads();
-    uint64_t nw = s_lo, cur = e0;
-    while (cur < e1) { // uniform; more than one round only where a long run of short or empty lists meets the tile
-      // stage the list heads of frontier nodes nw, nw + 1, ... up to the first one that starts at or past e1
-      uint32_t wlen = 0;
-      for (;;) {
-        const uint32_t j = wlen + threadIdx.x;
-        const uint64_t i = nw + j;
-        const uint64_t p = i < F ? pre[i] : E;
-        s_pre[j] = (uint32_t)p;
-        if (p < e1) {
-          uint32_t len;
-          s_ptr[j] = g.neighbours(o.closure[f0 + i], len);
-        }
-        wlen += kBlock;
-        if (__syncthreads_or(p >= e1) || wlen == kWin) break;
-      }
-      if (threadIdx.x == 0) s_pre[wlen] = (uint32_t)(nw + wlen < F ? pre[nw + wlen] : E);
-      __syncthreads();
-      const uint64_t s_end = s_pre[wlen];
-      const uint64_t stop = s_end < e1 ? s_end : e1;
-      uint32_t v[kPerThread], valid = 0;
+  walk_edge_tiles(g, o.closure + f0, F, pre, E, [&](const uint32_t (&v)[kPerThread], uint32_t have, uint64_t) {
+    uint32_t valid = 0;
 #pragma unroll
-      for (uint32_t k = 0; k < kPerThread; ++k) {
-        const uint64_t e = cur + k * kBlock + threadIdx.x;
-        v[k] = 0;
-        if (e < stop) {
-          uint32_t lo = 0, len = wlen; // the last staged node that starts at or before e (s_pre[0] <= cur <= e)
-          while (len > 1) {
-            const uint32_t half = len >> 1;
-            if (s_pre[lo + half] <= (uint32_t)e) lo += half;
-            len -= half;
-          }
-          v[k] = s_ptr[lo][(uint32_t)e - s_pre[lo]];
-          if (v[k] < o.num_node) valid |= 1u << k;
-        }
-      }
-      claim_append(o, v, valid, smem, s_base); // its barriers come after every read of s_pre / s_ptr above
-      cur = stop;
-      nw += wlen;
-    }
-  }
+    for (uint32_t k = 0; k < kPerThread; ++k)
+      if (v[k] < o.num_node) valid |= have & (1u << k);
+    claim_append(o, v, valid, smem, s_base);
+  });
 }
 
 } // namespace ggms
@@ -173,7 +107,7 @@ using namespace ggms;
 extern "C" {
 
 size_t ggms_khop_closure_workspace_bytes(size_t num_node) {
-  return sizeof(ClosureCtl) + closure_pre_words(num_node) * 4 + (tile_scan_words(num_node) + 2) * 4;
+  return sizeof(ClosureCtl) + closure_pre_words(num_node) * 4 + edge_scan_words(num_node) * 4;
 }
 
 int ggms_khop_closure(const ggms_graph_t *graph, const ggms_id_t *seeds, size_t num_seeds, uint32_t num_hop,
@@ -201,7 +135,7 @@ int ggms_khop_closure(const ggms_graph_t *graph, const ggms_id_t *seeds, size_t 
   GGMS_LAUNCH_CHECK();
   for (uint32_t h = 1; h <= num_hop; ++h) {
     // pre[i] over the frontier closure[hop_offsets[h - 1], hop_offsets[h]); its size and edge total stay on the device
-    int rc = tile_scan(FrontierDegree{g, closure, hop_offsets_dev + (h - 1)}, StorePrefix{pre}, N,
+    int rc = tile_scan(ListDegree{g, closure, hop_offsets_dev + (h - 1)}, StorePrefix{pre}, N,
                        count_of(N, &ctl->front), ScanArea{scan_words, false}, nullptr, nullptr, &ctl->edges, s);
     if (rc != GGMS_OK) return rc;
     // a persistent grid: the frontier's edge count is only known on the device
