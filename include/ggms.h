@@ -40,7 +40,8 @@ enum ggms_status {
   GGMS_ERR_NO_DEVICE = -3
 };
 
-/* DataType, common.h:38-46 (same integer codes) */
+/* DataType, common.h:38-46 (same integer codes); GGMS_BF16 is an extension (the reference has no such type): a
+ * feature table may be bf16, and every call that moves rows as bytes takes it like any other 2-byte type */
 enum ggms_dtype {
   GGMS_F32 = 0,
   GGMS_F64 = 1,
@@ -48,7 +49,8 @@ enum ggms_dtype {
   GGMS_U8 = 3,
   GGMS_I32 = 4,
   GGMS_I8 = 5,
-  GGMS_I64 = 6
+  GGMS_I64 = 6,
+  GGMS_BF16 = 7
 };
 
 int ggms_abi_version(void);
@@ -549,6 +551,35 @@ int ggms_extract_tiered(void *out, const ggms_id_t *nodes, size_t num_nodes,
 
 
 /* ---------------------------------------------------------------------------
+ * Converting gathers (an extension; the reference has none): the table's rows are stored in one of F16, BF16, F32
+ * and delivered in another of the three, in the gather's one pass -- no second pass over the batch to cast it.
+ * Each call is its plain namesake with `src_dtype, out_dtype` in place of `dtype`: same arguments, same row
+ * locators, counters and launch path (a launch timer rides on it, GGMS_EXTRACT_BLOCKS caps its grid).  `out` holds
+ * rows of dim x ggms_dtype_bytes(out_dtype) bytes, every source rows of dim x ggms_dtype_bytes(src_dtype).
+ *   - src_dtype == out_dtype (any dtype) IS the plain call;
+ *   - otherwise both must be one of F16 / BF16 / F32, else GGMS_ERR_INVALID;
+ *   - widening (F16, BF16 -> F32) is exact, subnormals included; narrowing (F32 -> F16, BF16) rounds to nearest
+ *     even, overflows to +-inf and produces subnormals; F16 <-> BF16 goes through f32; NaN stays NaN (payload
+ *     unspecified);
+ *   - rows move in chunks of 8, 4, 2 or 1 ELEMENTS (at most 16 bytes on the wider side: 8 between F16 and BF16,
+ *     4 with F32 on one side): the widest that divides dim with every source base aligned to chunk x source element
+ *     bytes and `out` to chunk x output element bytes.
+ * ggms_gather_scatter_convert is the general form of ggms_gather_scatter_masked: src_index and dst_index may each be
+ * NULL (identity); src_row_mask applies to src_index's values (0xffffffff: none).
+ * ggms_gather_scatter_partition and ggms_extract_dynamic have no converting form.
+ * ------------------------------------------------------------------------- */
+int ggms_gather_scatter_convert(void *out, const void *src, const ggms_id_t *src_index, const ggms_id_t *dst_index,
+                                size_t num, const uint64_t *num_dev, size_t dim, int src_dtype, int out_dtype,
+                                uint32_t src_row_mask, ggms_stream_t stream);
+int ggms_extract_cached_convert(void *out, const ggms_id_t *nodes, size_t num_nodes, const uint64_t *num_nodes_dev,
+                                const ggms_id_t *table, const void *const *parts, uint32_t num_part,
+                                const void *host_feat, size_t dim, int src_dtype, int out_dtype,
+                                uint64_t *num_miss_dev, ggms_stream_t stream);
+int ggms_extract_tiered_convert(void *out, const ggms_id_t *nodes, size_t num_nodes, const uint64_t *num_nodes_dev,
+                                const ggms_feature_tiers_t *tiers, size_t dim, int src_dtype, int out_dtype,
+                                uint64_t *tier_rows_dev, ggms_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Launch timer: a row gather's OWN start / end timestamps, with no packet of their own on the stream.
  * The reference times its extract with a host timer around a stream sync (dist_loops.cc:1276-1281,
  * kLogL1CopyTime); a pipelined caller has to use events instead, and every hipEventRecord / hipStreamWaitEvent
@@ -557,7 +588,8 @@ int ggms_extract_tiered(void *out, const ggms_id_t *nodes, size_t num_nodes,
  * two events ride ON the dispatch packet of the next row-gather launch (hipExtLaunchKernel): the kernel's own
  * start and end timestamps, and its end event is what another stream waits for ("the slot's rows are out").
  *   arm(t):      the next launch of ggms_extract* / ggms_gather_scatter* / ggms_mock_extract / ggms_batch_handoff /
- *                ggms_queue_pack / ggms_queue_unpack
+ *                ggms_queue_pack / ggms_queue_unpack (the converting forms included: ggms_gather_scatter_convert,
+ *                ggms_extract_cached_convert, ggms_extract_tiered_convert)
  *                issued by THIS thread
  *                carries the timer (thread-local, consumed by that one launch; a call that launches nothing --
  *                zero rows -- leaves it armed)

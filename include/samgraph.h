@@ -92,7 +92,7 @@ typedef struct {
 } samgraph_tensor_t;
 
 /* each checks key == current batch key like CHECK_EQ(key, graph_batch->key) (adapter.cc:68) */
-void samgraph_get_graph_feat(uint64_t key, samgraph_tensor_t *out);              /* :62-77   */
+void samgraph_get_graph_feat(uint64_t key, samgraph_tensor_t *out);              /* :62-77; dtype: config key feat_out_dtype, else the table's */
 void samgraph_get_graph_label(uint64_t key, samgraph_tensor_t *out);             /* :79-92   */
 void samgraph_get_graph_row(uint64_t key, int layer_idx, samgraph_tensor_t *out);/* :94-106  */
 void samgraph_get_graph_col(uint64_t key, int layer_idx, samgraph_tensor_t *out);/* :108-120 */

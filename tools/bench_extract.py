@@ -1,10 +1,28 @@
 """Diagnostic micro-benchmark of the row gather over row widths and dtypes (not part of the product).
-Prints, per case: the gather, torch.index_select and a straight copy of the same bytes, as algorithmic TB/s
-(4-B index + row read + row write) and as a fraction of the 8 TB/s HBM peak."""
+Without arguments it prints, per case: the gather, torch.index_select and a straight copy of the same bytes, as
+algorithmic TB/s (4-B index + row read + row write) and as a fraction of the 8 TB/s HBM peak.
+
+    python tools/bench_extract.py --table-dtype f16 --out-dtype f32 [--dim 128] [--rows N] [--table-rows N]
+times the converting gather of one pair (ggms_gather_scatter_convert; the same dtype twice is the plain gather), and
+    python tools/bench_extract.py --ab [--out FILE]
+the comparison behind `feat_out_dtype` in one process, alternating order, table in HBM: (a) plain f16 gather + torch
+.float(), (b) fused f16 -> f32, (c) plain f32, (d) f32 -> bf16."""
+import argparse
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from xgnn_amd import ops
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--table-dtype", choices=["f32", "f16", "bf16"])
+ap.add_argument("--out-dtype", choices=["f32", "f16", "bf16"])
+ap.add_argument("--dim", type=int, default=128)
+ap.add_argument("--rows", type=int, default=2_960_000, help="rows per gather (bench.py's papers100M-shaped batch)")
+ap.add_argument("--table-rows", type=int, default=16_000_000)
+ap.add_argument("--ab", action="store_true")
+ap.add_argument("--out", help="--ab: also write the report to this file")
+args = ap.parse_args()
+DT = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
 
 dev = torch.device("cuda", 0)
 N, n = 2_449_029, 1_280_000
@@ -22,6 +40,63 @@ def timeit(fn, reps=20):
     torch.cuda.synchronize()
     return e0.elapsed_time(e1) / reps * 1e-3
 
+
+def convert_setup(table_dtype, out_dtype, idx, table=None):
+    """(table, out, gather) of one pair; bytes per row = 4 (index) + row read + row written."""
+    if table is None:
+        table = torch.randn(args.table_rows, args.dim, device=dev).to(DT[table_dtype])
+    out = torch.empty((idx.numel(), args.dim), dtype=DT[out_dtype], device=dev)
+    return table, out, lambda: ops.gather_scatter_convert(out, table, idx, None)
+
+
+def run_ab():
+    idx = torch.randint(0, args.table_rows, (args.rows,), device=dev, dtype=torch.int32)
+    t16, out16, plain16 = convert_setup("f16", "f16", idx)
+    _, out32f, fused = convert_setup("f16", "f32", idx, t16)
+    t32, out32, plain32 = convert_setup("f32", "f32", idx)
+    _, outbf, to_bf16 = convert_setup("f32", "bf16", idx, t32)
+
+    cases = [("a  f16 table, plain gather + torch .float()", lambda: (plain16(), out16.float())),
+             ("b  f16 -> f32 fused (8-B load, 16-B store per chunk)", fused),
+             ("c  f32 table, plain gather", plain32),
+             ("d  f32 -> bf16 fused (16-B load, 8-B store per chunk)", to_bf16)]
+    fused()
+    plain16()
+    assert torch.equal(out32f, out16.float())  # the same rows either way
+    times = {name: [] for name, _ in cases}
+    for rnd in range(5):  # alternating order: forward, backward, ...
+        for name, fn in (cases if rnd % 2 == 0 else cases[::-1]):
+            times[name].append(timeit(fn, reps=30))
+    med = {k[0]: sorted(v)[len(v) // 2] for k, v in times.items()}
+    lines = [f"feat_out_dtype A/B: {args.rows} rows x dim {args.dim}, table {args.table_rows} rows in HBM, one process, "
+             f"5 rounds x 30 launches per case in alternating order, median of the rounds (min .. max)",
+             f"device: {torch.cuda.get_device_name(0)}"]
+    for name, v in times.items():
+        lines.append(f"{name:58s} {sorted(v)[len(v) // 2] * 1e3:7.4f} ms  ({min(v) * 1e3:.4f} .. {max(v) * 1e3:.4f})")
+    lines += [f"b / a = {med['b'] / med['a']:.3f} (bytes: 0.60)   b / c = {med['b'] / med['c']:.3f} (bytes: 0.75)   "
+              f"d / c = {med['d'] / med['c']:.3f} (bytes: 0.75)",
+              f"acceptance: b < a: {'PASS' if med['b'] < med['a'] else 'FAIL'};  b <= 1.05 c: "
+              f"{'PASS' if med['b'] <= 1.05 * med['c'] else 'FAIL'};  d <= 1.05 c: {'PASS' if med['d'] <= 1.05 * med['c'] else 'FAIL'}"]
+    text = "\n".join(lines)
+    print(text, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
+if args.ab:
+    run_ab()
+    sys.exit(0)
+if args.table_dtype or args.out_dtype:
+    td, od = args.table_dtype or args.out_dtype, args.out_dtype or args.table_dtype
+    idx = torch.randint(0, args.table_rows, (args.rows,), device=dev, dtype=torch.int32)
+    table, out, fn = convert_setup(td, od, idx)
+    t = timeit(fn)
+    by = args.rows * (4 + args.dim * (table.element_size() + out.element_size()))
+    print(f"{td} -> {od}, {args.rows} rows x dim {args.dim}: {t * 1e6:.1f} us, {by / t / 1e12:.2f} TB/s algorithmic "
+          f"({by / t / 8e12:.2f} of 8)")
+    sys.exit(0)
 
 idx = torch.randperm(N, device=dev)[:n].to(torch.int32)
 idx64 = idx.long()

@@ -143,6 +143,7 @@ size_t ggms_dtype_bytes(int dtype) {
     case GGMS_I32: return 4;
     case GGMS_I8: return 1;
     case GGMS_I64: return 8;
+    case GGMS_BF16: return 2;
     default: return 0;
   }
 }

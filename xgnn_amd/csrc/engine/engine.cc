@@ -215,6 +215,20 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
     cfg.pipelines = 1;
   }
   SAM_CHECK(cfg.sample_type >= GGMS_KHOP0 && cfg.sample_type <= GGMS_KHOP3, "unknown sample type");
+  if (kv.count("feat_out_dtype")) { // extension: deliver the batch's rows in this dtype, converted by the gather itself
+    static const std::map<std::string, int> names = {{"f32", GGMS_F32}, {"f16", GGMS_F16}, {"bf16", GGMS_BF16}};
+    const std::string v = kv["feat_out_dtype"];
+    if (!names.count(v))
+      fatal(__FILE__, __LINE__, "feat_out_dtype = " + v + ": the converting gather delivers f32, f16 or bf16");
+    cfg.feat_out_dtype = names.at(v);
+    // (the table's side of the pair is checked when meta.txt has been read: LoadDataset)
+    if (cfg.arch == kArch0)
+      fatal(__FILE__, __LINE__, "arch0: feat_out_dtype is not built for the CPU engine: its extractor copies rows, it does "
+                                "not convert them");
+    if (cfg.arch == kArch6 && !cfg.gpu_extract && cfg.cache_percentage < 1.0)
+      fatal(__FILE__, __LINE__, "arch6: feat_out_dtype needs gpu_extract = True or cache_percentage 1.0: the host-staged "
+                                "tier's rows land in the batch by hipMemcpyAsync, which does not convert");
+  }
   if (cfg.arch == kArch4) { // DoGPUSampleDyCache's switch (cuda/cuda_loops.cc:347-377) and what it needs
     if (cfg.sample_type != GGMS_KHOP0 && cfg.sample_type != GGMS_KHOP1 && cfg.sample_type != GGMS_WEIGHTED_KHOP)
       fatal(__FILE__, __LINE__, "arch4: _sample_type " + std::to_string(cfg.sample_type) + " is not supported: the "
@@ -233,6 +247,9 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
                                 "dynamic_cache, from the previous batch; set cache_percentage 0");
     if (!cfg.direct_table) fatal(__FILE__, __LINE__, "arch4: hash_table = hashed: the superset needs the direct table layout");
     cfg.dynamic_cache = cfg.cache_policy == 6;
+    if (cfg.dynamic_cache && cfg.feat_out_dtype >= 0)
+      fatal(__FILE__, __LINE__, "arch4: feat_out_dtype with cache policy dynamic_cache (6): a gather reads the previous "
+                                "batch's rows (the output dtype) beside the host table's (the table dtype), one dtype per source");
     if (cfg.dynamic_cache) cfg.extract_streams = 1; // gathers in batch order, each after the one whose rows it reads
     if (kv.count("prefetch_max_edges")) cfg.prefetch_max_edges = std::stoull(kv["prefetch_max_edges"]);
   }
@@ -291,9 +308,12 @@ void Engine::LoadDataset() {
     if (k == "FEAT_DATA_TYPE") {
       static const std::map<std::string, int> names = {{"F32", GGMS_F32}, {"F64", GGMS_F64}, {"F16", GGMS_F16},
                                                        {"U8", GGMS_U8},   {"I32", GGMS_I32}, {"I8", GGMS_I8},
-                                                       {"I64", GGMS_I64}};
+                                                       {"I64", GGMS_I64}, {"BF16", GGMS_BF16}};
       SAM_CHECK(names.count(v), "unknown FEAT_DATA_TYPE " + v);
       ds.feat_dtype = names.at(v);
+      if (cfg.feat_out_dtype >= 0 && ds.feat_dtype != GGMS_F32 && ds.feat_dtype != GGMS_F16 && ds.feat_dtype != GGMS_BF16)
+        fatal(__FILE__, __LINE__, "feat_out_dtype with FEAT_DATA_TYPE " + v + ": the gather converts F16, BF16 and F32 "
+                                  "tables only");
     } else {
       meta[k] = std::stoull(v);
     }
@@ -1159,7 +1179,7 @@ void Engine::TrainInit(int worker_id, const std::string &ctx) {
     auto b = std::make_unique<Batch>();
     b->slot = (int)s;
     b->trainer.Alloc(max_edges_, max_unique_, max_seeds_, cfg.sample_type == GGMS_RANDOM_WALK);
-    SAM_HIP(hipMalloc(&b->feat, max_unique_ * row_bytes));
+    SAM_HIP(hipMalloc(&b->feat, max_unique_ * ds.feat_dim * ggms_dtype_bytes(batch_feat_dtype()))); // rows as delivered
     SAM_HIP(hipMalloc((void **)&b->label, max_seeds_ * 8));
     if (StagedHostTier()) { // index arrays of GetMissCacheIndex + pinned / device staging of the miss rows
       if (cache_table_) { // (no cache: no split, and the rows land in the batch's feature buffer directly)
@@ -1382,6 +1402,9 @@ void Engine::EnqueueGather(Batch *b, hipStream_t ss) {
   }
   if (b->lean) SAM_GGMS(ggms_launch_timer_arm(b->gather_timer));
   else SAM_HIP(hipEventRecord(b->ev_xstart, xs)); // the extract's own start: behind the previous batch's extract on xs
+  // the rows are delivered in the batch's dtype (config key feat_out_dtype; the table's own without the key, which is
+  // the plain gather: a *_convert call with one dtype IS its plain namesake)
+  const int out_dtype = batch_feat_dtype();
   uint32_t dyn_seq = 0;
   if (cfg.dynamic_cache) { // batch order on one extract stream; seq wraps: the table starts again from zero
     if (++dyn_seq_ == 0) {
@@ -1406,21 +1429,19 @@ void Engine::EnqueueGather(Batch *b, hipStream_t ss) {
     tiers.my_part = cfg.part_cache ? (uint32_t)worker_id_ : 0;
     tiers.host_feat = feat_src_;
     tiers.host_row_mask = mock ? ds.feat_mask : 0;
-    SAM_GGMS(ggms_extract_tiered(b->feat, b->trainer.input_nodes, max_unique_, n_in, &tiers, ds.feat_dim, ds.feat_dtype,
-                                 gather_counts ? n_miss : nullptr, xs));
+    SAM_GGMS(ggms_extract_tiered_convert(b->feat, b->trainer.input_nodes, max_unique_, n_in, &tiers, ds.feat_dim,
+                                         ds.feat_dtype, out_dtype, gather_counts ? n_miss : nullptr, xs));
   } else if (cfg.UseGPUCache()) {
     // DoArch6GetCacheMissIndex + DoArch6GPUCacheFeatureCopy (dist_loops.cc:1015-1285) in one pass; everything cached in
     // node order (no table): no row can miss, the count stays the zero the sampling stream wrote
-    SAM_GGMS(ggms_extract_cached(b->feat, b->trainer.input_nodes, max_unique_, n_in, cache_table_,
-                                 (const void *const *)cache_parts_.data(), num_cache_part_, feat_src_, ds.feat_dim,
-                                 ds.feat_dtype, (cache_table_ && can_miss) ? n_miss : nullptr, xs));
-  } else if (mock) { // GPUMockExtract, cuda_loops.cc:692-700 / dist_loops.cc:608-616
-    SAM_GGMS(ggms_gather_scatter_masked(b->feat, feat_src_, b->trainer.input_nodes, nullptr, max_unique_, n_in, ds.feat_dim,
-                                        ds.feat_dtype, ds.feat_mask, xs));
+    SAM_GGMS(ggms_extract_cached_convert(b->feat, b->trainer.input_nodes, max_unique_, n_in, cache_table_,
+                                         (const void *const *)cache_parts_.data(), num_cache_part_, feat_src_, ds.feat_dim,
+                                         ds.feat_dtype, out_dtype, (cache_table_ && can_miss) ? n_miss : nullptr, xs));
   } else {
-    // DoGPUFeatureExtract (cuda/cuda_loops.cc, dist_loops.cc:585-634)
-    SAM_GGMS(ggms_gather_scatter(b->feat, feat_src_, b->trainer.input_nodes, nullptr, max_unique_, n_in, ds.feat_dim,
-                                 ds.feat_dtype, xs));
+    // DoGPUFeatureExtract (cuda/cuda_loops.cc, dist_loops.cc:585-634); with SAMGRAPH_EMPTY_FEAT GPUMockExtract
+    // (cuda_loops.cc:692-700 / dist_loops.cc:608-616): row = node & mask (all ones otherwise)
+    SAM_GGMS(ggms_gather_scatter_convert(b->feat, feat_src_, b->trainer.input_nodes, nullptr, max_unique_, n_in,
+                                         ds.feat_dim, ds.feat_dtype, out_dtype, ds.feat_mask, xs));
   }
   if (cfg.dynamic_cache) { // the next batch finds these rows in b->feat; b holds the batch it read until it is finished
     SAM_GGMS(ggms_dynamic_cache_publish(dyn_stamps_, b->trainer.input_nodes, max_unique_, n_in, dyn_seq, xs));
@@ -1544,6 +1565,9 @@ void Engine::Finish(Batch *b, Batch *prev) {
   const double s_copy_epoch = b->lean ? us_busy * 1e-6 : ms_copy * 1e-3;
   uint64_t edges = 0;
   for (uint32_t i = 0; i < L; ++i) edges += b->counts[3 * i];
+  // feature bytes: what the gather wrote to the batch (rows in the delivered dtype); miss bytes: what it read from the
+  // host tier (rows in the table's dtype)
+  const double out_row_bytes = (double)ds.feat_dim * ggms_dtype_bytes(batch_feat_dtype());
   const double row_bytes = (double)ds.feat_dim * ggms_dtype_bytes(ds.feat_dtype);
   // item codes: profiler.h:58-140 (kLogL1NumSample = 0, kLogL1NumNode = 1, kLogL1SampleTime = 3,
   // kLogL1CopyTime = 6, kLogL1FeatureBytes = 9, kLogL1MissBytes = 13; epoch items :119-137)
@@ -1551,11 +1575,11 @@ void Engine::Finish(Batch *b, Batch *prev) {
   prof.LogStep(b->key, 1, (double)b->num_input);
   prof.LogStep(b->key, 3, ms_sample * 1e-3);
   prof.LogStep(b->key, 6, ms_copy * 1e-3);
-  prof.LogStep(b->key, 9, b->num_input * row_bytes);
+  prof.LogStep(b->key, 9, b->num_input * out_row_bytes);
   prof.LogStep(b->key, 13, b->num_miss * row_bytes);
   prof.LogEpochAdd(b->key, 0 /*kLogEpochSampleTime*/, ms_sample * 1e-3);
   prof.LogEpochAdd(b->key, 8 /*kLogEpochCopyTime*/, s_copy_epoch);
-  prof.LogEpochAdd(b->key, 12 /*kLogEpochFeatureBytes*/, b->num_input * row_bytes);
+  prof.LogEpochAdd(b->key, 12 /*kLogEpochFeatureBytes*/, b->num_input * out_row_bytes);
   prof.LogEpochAdd(b->key, 13 /*kLogEpochMissBytes*/, b->num_miss * row_bytes);
   prof.LogEpochAdd(b->key, 15 /*kLogEpochNumSample*/, (double)edges);
   if (BatchSampledElsewhere()) { // what the hand-off (arch5: the unpack) moved and its time

@@ -87,6 +87,9 @@ struct RunConfig {
   // budget of one batch (config key `prefetch_max_edges`; ggms_sample_batch_prefetch_capacity)
   bool dynamic_cache = false;
   size_t prefetch_max_edges = (size_t)1 << 26;
+  // extension (config key `feat_out_dtype` = f32 | f16 | bf16): the dtype the batch's feature rows are DELIVERED in; the
+  // gather converts from the table's (FEAT_DATA_TYPE) in its one pass.  -1: key absent, the table's dtype
+  int feat_out_dtype = -1;
   size_t staged_serial_epochs = 0; // host-staged path: the first N epochs run the reference's serial, per-phase-timed sequence
   size_t staged_serial_steps = 0;  // ... or this worker's first N batches
   // worker 0 ranks the nodes at init: pre_sample (sampled input nodes) or presample_static (L-hop closures)
@@ -227,6 +230,8 @@ class Engine {
   bool IsArch5Sampler() const { return cfg.arch == kArch5 && role_ == kRoleSampler; }
   // arch3 / arch5: the batch is sampled elsewhere (sampler GPU / process) and handed to the trainer GPU's extract stream
   bool BatchSampledElsewhere() const { return Dedicated() || cfg.arch == kArch5; }
+  // dtype of a batch's feature buffer: the configured feat_out_dtype, else the table's
+  int batch_feat_dtype() const { return cfg.feat_out_dtype < 0 ? ds.feat_dtype : cfg.feat_out_dtype; }
   int batch_device_type() const { return (cfg.arch == kArch0 && cfg.trainer_on_host) ? 0 : 2; } // DeviceType, common.h:48
   void Barrier(const char *what = "step");
   void *OpenPeer(const hipIpcMemHandle_t &handle, uint32_t peer, size_t bytes, const char *what);

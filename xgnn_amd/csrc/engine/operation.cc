@@ -86,7 +86,7 @@ void samgraph_dump_trace(void) { Engine::Get().prof.DumpTrace(); }
 void samgraph_get_graph_feat(uint64_t key, samgraph_tensor_t *out) {
   auto &E = Engine::Get();
   auto *b = E.Current(key);
-  fill(out, b->feat, (int64_t)b->num_input, (int64_t)E.ds.feat_dim, 2, E.ds.feat_dtype, E.batch_device_type(), E.trainer_device());
+  fill(out, b->feat, (int64_t)b->num_input, (int64_t)E.ds.feat_dim, 2, E.batch_feat_dtype(), E.batch_device_type(), E.trainer_device());
 }
 void samgraph_get_graph_label(uint64_t key, samgraph_tensor_t *out) {
   auto &E = Engine::Get();

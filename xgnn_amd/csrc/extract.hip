@@ -35,6 +35,61 @@ template <> struct ChunkT<4> { using type = uint32_t; };
 template <> struct ChunkT<2> { using type = uint16_t; };
 template <> struct ChunkT<1> { using type = uint8_t; };
 
+// ---- what a chunk is ----------------------------------------------------------------------------------------------
+// The sweep moves CHUNKS: a fixed number of elements of a row, read as Src and written as Dst.  The plain gather's
+// chunk is CB bytes on both sides.  A converting gather (ggms_*_convert: an F16 / BF16 / F32 table delivered in
+// another of the three types) has chunks of EPC elements: EPC x source element bytes in, EPC x output element bytes
+// out, converted at store time -- the registers a lane holds between its loads and its first store are the SOURCE
+// chunks only, whichever side is the wider one.
+template <int CB> struct CopyChunk {
+  static constexpr int kSrcBytes = CB, kDstBytes = CB;
+  using Src = typename ChunkT<CB>::type;
+  using Dst = Src;
+  static __device__ __forceinline__ Dst convert(Src v) { return v; }
+};
+
+// element types by ggms_dtype code: the bits as stored, and the value as f32 (every conversion goes through f32)
+template <int DT> struct Elem;
+template <> struct Elem<GGMS_F32> {
+  using bits = uint32_t;
+  static __device__ __forceinline__ float to_f32(bits b) { return __builtin_bit_cast(float, b); }
+  static __device__ __forceinline__ bits from_f32(float f) { return __builtin_bit_cast(bits, f); }
+};
+template <> struct Elem<GGMS_F16> { // the casts are IEEE: widening exact (subnormals included), narrowing
+  using bits = uint16_t;            // round-to-nearest-even with overflow to inf and subnormal results kept
+  static __device__ __forceinline__ float to_f32(bits b) { return (float)__builtin_bit_cast(_Float16, b); }
+  static __device__ __forceinline__ bits from_f32(float f) { return __builtin_bit_cast(bits, (_Float16)f); }
+};
+template <> struct Elem<GGMS_BF16> { // the upper half of an f32
+  using bits = uint16_t;
+  static __device__ __forceinline__ float to_f32(bits b) { return __builtin_bit_cast(float, (uint32_t)b << 16); }
+  static __device__ __forceinline__ bits from_f32(float f) {
+    const uint32_t u = __builtin_bit_cast(uint32_t, f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (bits)((u >> 16) | 0x40u); // NaN stays NaN (quiet)
+    return (bits)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16); // nearest even; a carry out of the mantissa ends in inf
+  }
+};
+template <typename T, int N> struct VecT { typedef T type __attribute__((ext_vector_type(N))); };
+template <typename T> struct VecT<T, 1> { using type = T; };
+
+template <int EPC, int SRC_DT, int DST_DT> struct ConvertChunk {
+  using S = Elem<SRC_DT>;
+  using D = Elem<DST_DT>;
+  static constexpr int kSrcBytes = EPC * (int)sizeof(typename S::bits), kDstBytes = EPC * (int)sizeof(typename D::bits);
+  using Src = typename VecT<typename S::bits, EPC>::type;
+  using Dst = typename VecT<typename D::bits, EPC>::type;
+  static __device__ __forceinline__ Dst convert(Src v) {
+    if constexpr (EPC == 1) {
+      return D::from_f32(S::to_f32(v));
+    } else {
+      Dst o;
+#pragma unroll
+      for (int e = 0; e < EPC; ++e) o[e] = D::from_f32(S::to_f32(v[e]));
+      return o;
+    }
+  }
+};
+
 // which tier served a row (0 = not counted); counters[tier - 1] in ggms_extract_tiered
 constexpr uint32_t kTierHost = 1, kTierRemote = 2, kTierLocal = 3, kTierReplica = 4;
 
@@ -216,16 +271,18 @@ __device__ __forceinline__ void store_chunk(uint64_t addr, V v) {
 // U = independent chunk loads in flight per lane (16, or 8 for rows of fewer than 8 chunks)
 // Loads and stores are non-temporal: a batch's rows are read once and the gathered batch is a > 100-MB stream that
 // nothing re-reads from cache (measured + 3..5 % on MI355X each, profiles/r01-r02).
-template <int CB, typename Rows, bool IDENT_DST, int U>
+template <typename Chunk, typename Rows, bool IDENT_DST, int U>
 __global__ __launch_bounds__(kBlock) void k_gather_rows(char *__restrict__ out, Rows rows,
                                                         const uint32_t *__restrict__ dst_index, Count n_arg,
                                                         uint32_t rc, uint32_t magic, uint64_t *miss_count) {
-  using V = typename ChunkT<CB>::type;
+  using SV = typename Chunk::Src;
+  using DV = typename Chunk::Dst;
+  constexpr uint32_t SB = Chunk::kSrcBytes, DB = Chunk::kDstBytes;
   const uint64_t n = n_arg.get();
   const uint32_t lane = lane_id();
   const uint64_t wave = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
   const uint64_t num_waves = (uint64_t)gridDim.x * (kBlock / kWave);
-  const uint64_t row_bytes = (uint64_t)rc * CB;
+  const uint64_t row_bytes = (uint64_t)rc * DB; // of an OUTPUT row (the locator knows the source's)
   const uint64_t num_tiles = (n + kWave - 1) / kWave;
 
   // resolve one row per lane for tile `t`: source pointer (+ destination pointer)
@@ -263,10 +320,10 @@ __global__ __launch_bounds__(kBlock) void k_gather_rows(char *__restrict__ out, 
     }
     const uint64_t row0 = tile * kWave;
     const uint32_t rows_here = (n - row0 < (uint64_t)kWave) ? (uint32_t)(n - row0) : (uint32_t)kWave;
-    const uint32_t total = rows_here * rc; // 16-byte chunks in this tile
+    const uint32_t total = rows_here * rc; // chunks in this tile
     const uint64_t out_tile = (uint64_t)(out + row0 * row_bytes);
     for (uint32_t c0 = 0; c0 < total; c0 += kWave * U) {
-      V tmp[U];
+      SV tmp[U];
       uint32_t cc[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -276,19 +333,19 @@ __global__ __launch_bounds__(kBlock) void k_gather_rows(char *__restrict__ out, 
         const uint32_t r = __umulhi(cc[u], magic) + (rc == 1 ? cc[u] : 0u);
         const uint32_t col = cc[u] - r * rc;
         const uint64_t p = shfl_u64(sp, (int)r);
-        tmp[u] = load_chunk<V, true>(p + (uint64_t)col * CB);
+        tmp[u] = load_chunk<SV, true>(p + (uint64_t)col * SB);
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const uint32_t c = c0 + u * kWave + lane;
         uint64_t q;
         if constexpr (IDENT_DST) {
-          q = out_tile + (uint64_t)cc[u] * CB;
+          q = out_tile + (uint64_t)cc[u] * DB;
         } else {
           const uint32_t r = __umulhi(cc[u], magic) + (rc == 1 ? cc[u] : 0u);
-          q = shfl_u64(dp, (int)r) + (uint64_t)(cc[u] - r * rc) * CB;
+          q = shfl_u64(dp, (int)r) + (uint64_t)(cc[u] - r * rc) * DB;
         }
-        if (c < total) store_chunk<V, true>(q, tmp[u]);
+        if (c < total) store_chunk<DV, true>(q, Chunk::convert(tmp[u]));
       }
     }
     sp = sp_n; dp = dp_n; miss = miss_n;
@@ -308,21 +365,24 @@ __global__ __launch_bounds__(kBlock) void k_gather_rows(char *__restrict__ out, 
 
 // Rows of 8192 chunks or more (>= 128 KiB at 16-byte chunks; the tile sweep's chunk -> row division is exact only
 // below that): every row is a long contiguous stream by itself, so one workgroup copies one row.
-template <int CB, typename Rows>
+template <typename Chunk, typename Rows>
 __global__ __launch_bounds__(kBlock) void k_gather_long_rows(char *__restrict__ out, Rows rows,
                                                              const uint32_t *__restrict__ dst_index, Count n_arg,
                                                              uint64_t rc, uint64_t *miss_count) {
-  using V = typename ChunkT<CB>::type;
+  using SV = typename Chunk::Src;
+  using DV = typename Chunk::Dst;
+  constexpr uint32_t SB = Chunk::kSrcBytes, DB = Chunk::kDstBytes;
   const uint64_t n = n_arg.get();
   for (uint64_t i = blockIdx.x; i < n; i += gridDim.x) {
     uint32_t tier = 0;
     const uint64_t sp = (uint64_t)rows.row(i, tier);
-    const uint64_t dp = (uint64_t)(out + (dst_index ? (uint64_t)dst_index[i] : i) * rc * CB);
+    const uint64_t dp = (uint64_t)(out + (dst_index ? (uint64_t)dst_index[i] : i) * rc * DB);
     if (miss_count && threadIdx.x == 0) {
       if (tier == kTierHost) atomicAdd((unsigned long long *)miss_count, 1ull);
       else if (Rows::kTiers && tier >= kTierRemote) atomicAdd((unsigned long long *)miss_count + (tier - 1), 1ull);
     }
-    for (uint64_t c = threadIdx.x; c < rc; c += kBlock) store_chunk<V, true>(dp + c * CB, load_chunk<V, true>(sp + c * CB));
+    for (uint64_t c = threadIdx.x; c < rc; c += kBlock)
+      store_chunk<DV, true>(dp + c * DB, Chunk::convert(load_chunk<SV, true>(sp + c * SB)));
   }
 }
 
@@ -333,10 +393,17 @@ __global__ __launch_bounds__(kBlock) void k_copy_words(uint32_t *__restrict__ ds
   for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) dst[i] = src[i];
 }
 
-static inline int pick_chunk(size_t row_bytes, uintptr_t align_bits) {
-  for (int cb = 16; cb > 1; cb >>= 1)
-    if (row_bytes % cb == 0 && (align_bits % cb) == 0) return cb;
+// The widest chunk, in ELEMENTS (a power of two up to max_epc), that divides a row of `dim` elements and keeps both
+// sides aligned to their own chunk size: epc x src_es bytes for every source base, epc x dst_es bytes for `out`
+// (*_bits: the addresses ORed together).
+static inline int pick_chunk(size_t dim, int max_epc, size_t src_es, uintptr_t src_bits, size_t dst_es, uintptr_t dst_bits) {
+  for (int epc = max_epc; epc > 1; epc >>= 1)
+    if (dim % epc == 0 && src_bits % (epc * src_es) == 0 && dst_bits % (epc * dst_es) == 0) return epc;
   return 1;
+}
+// the plain gather: rows of bytes, chunks of up to 16 of them
+static inline int pick_chunk(size_t row_bytes, uintptr_t align_bits) {
+  return pick_chunk(row_bytes, 16, 1, align_bits, 1, align_bits);
 }
 
 } // namespace ggms
@@ -373,24 +440,22 @@ static inline void launch_rows(F kernel, int grid, hipStream_t stream, Args... a
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, stream, args...);
 }
 
-template <typename Rows>
-static int launch_gather(char *out, Rows rows, const uint32_t *dst_index, size_t n_max, Count n,
-                         size_t row_bytes, int cb, uint64_t *miss_count, hipStream_t stream) {
+// Every row gather goes out through here: `rc` chunks per row, moved as Chunk says.  SCATTER false: the caller never
+// has a dst_index (no scatter form of the kernel is built for it).
+template <typename Chunk, typename Rows, bool SCATTER = true>
+static int launch_chunks(char *out, Rows rows, const uint32_t *dst_index, size_t n_max, Count n, uint64_t rc,
+                         uint64_t *miss_count, hipStream_t stream) {
   if (n_max == 0) return GGMS_OK;
-  const uint64_t rc = row_bytes / cb;
   if (rc == 0) {
     set_error("extract: empty rows");
     return GGMS_ERR_INVALID;
   }
+  if (!SCATTER && dst_index) {
+    set_error("extract: this gather has no scatter form");
+    return GGMS_ERR_INVALID;
+  }
   if (rc >= 8192) {
-    const int g = grid_for(n_max, 1);
-    switch (cb) {
-      case 16: launch_rows(k_gather_long_rows<16, Rows>, g, stream, out, rows, dst_index, n, rc, miss_count); break;
-      case 8: launch_rows(k_gather_long_rows<8, Rows>, g, stream, out, rows, dst_index, n, rc, miss_count); break;
-      case 4: launch_rows(k_gather_long_rows<4, Rows>, g, stream, out, rows, dst_index, n, rc, miss_count); break;
-      case 2: launch_rows(k_gather_long_rows<2, Rows>, g, stream, out, rows, dst_index, n, rc, miss_count); break;
-      default: launch_rows(k_gather_long_rows<1, Rows>, g, stream, out, rows, dst_index, n, rc, miss_count); break;
-    }
+    launch_rows(k_gather_long_rows<Chunk, Rows>, grid_for(n_max, 1), stream, out, rows, dst_index, n, rc, miss_count);
     GGMS_LAUNCH_CHECK();
     return GGMS_OK;
   }
@@ -406,34 +471,162 @@ static int launch_gather(char *out, Rows rows, const uint32_t *dst_index, size_t
   // 16 independent chunk loads per lane once a row has >= 8 chunks, else 8 (measured: 0.58 -> 0.60 of peak at 400-B
   // rows, 0.65 -> 0.70 at 512-B rows, and the gather holds its rate when the sampler runs beside it)
   const bool deep = rc >= 8;
-#define GGMS_LAUNCH(CB, ID)                                                                                          \
+#define GGMS_LAUNCH(ID)                                                                                              \
   do {                                                                                                               \
     if (deep)                                                                                                        \
-      launch_rows(k_gather_rows<CB, Rows, ID, 16>, grid, stream, out, rows, dst_index, n, (uint32_t)rc, magic, miss_count); \
+      launch_rows(k_gather_rows<Chunk, Rows, ID, 16>, grid, stream, out, rows, dst_index, n, (uint32_t)rc, magic, miss_count); \
     else                                                                                                             \
-      launch_rows(k_gather_rows<CB, Rows, ID, 8>, grid, stream, out, rows, dst_index, n, (uint32_t)rc, magic, miss_count); \
+      launch_rows(k_gather_rows<Chunk, Rows, ID, 8>, grid, stream, out, rows, dst_index, n, (uint32_t)rc, magic, miss_count); \
   } while (0)
-#define GGMS_CASE(CB)                                        \
-  case CB:                                                   \
-    if (dst_index == nullptr) GGMS_LAUNCH(CB, true);         \
-    else GGMS_LAUNCH(CB, false);                             \
-    break;
-  switch (cb) {
-    GGMS_CASE(16)
-    GGMS_CASE(8)
-    GGMS_CASE(4)
-    GGMS_CASE(2)
-    GGMS_CASE(1)
+  if (dst_index == nullptr) {
+    GGMS_LAUNCH(true);
+  } else if constexpr (SCATTER) {
+    GGMS_LAUNCH(false);
   }
-#undef GGMS_CASE
 #undef GGMS_LAUNCH
   GGMS_LAUNCH_CHECK();
   return GGMS_OK;
 }
 
+template <typename Rows>
+static int launch_gather(char *out, Rows rows, const uint32_t *dst_index, size_t n_max, Count n,
+                         size_t row_bytes, int cb, uint64_t *miss_count, hipStream_t stream) {
+  const uint64_t rc = row_bytes / cb;
+  switch (cb) {
+    case 16: return launch_chunks<CopyChunk<16>>(out, rows, dst_index, n_max, n, rc, miss_count, stream);
+    case 8: return launch_chunks<CopyChunk<8>>(out, rows, dst_index, n_max, n, rc, miss_count, stream);
+    case 4: return launch_chunks<CopyChunk<4>>(out, rows, dst_index, n_max, n, rc, miss_count, stream);
+    case 2: return launch_chunks<CopyChunk<2>>(out, rows, dst_index, n_max, n, rc, miss_count, stream);
+    default: return launch_chunks<CopyChunk<1>>(out, rows, dst_index, n_max, n, rc, miss_count, stream);
+  }
+}
+
+// ---- how a call's rows are moved -------------------------------------------------------------------------------------
+// src_dt == dst_dt (any dtype): as bytes, the plain gather.  Otherwise both are one of F16 / BF16 / F32 and the gather
+// converts (ConvertChunk): the same locators, sweep and launch path, chunks of `epc` elements.
+struct RowMove {
+  int src_dt, dst_dt;
+  size_t dim, src_es, dst_es;
+  bool converts() const { return src_dt != dst_dt; }
+  size_t src_row_bytes() const { return dim * src_es; }
+};
+static inline bool is_float_dtype(int dt) { return dt == GGMS_F16 || dt == GGMS_BF16 || dt == GGMS_F32; }
+static bool row_move(int src_dt, int dst_dt, size_t dim, RowMove &m) {
+  m = RowMove{src_dt, dst_dt, dim, ggms_dtype_bytes(src_dt), ggms_dtype_bytes(dst_dt)};
+  if (m.src_es == 0 || m.dst_es == 0 || dim == 0) {
+    set_error("extract: invalid argument: dtype %d -> %d, dim %zu (unknown dtype or empty rows)", src_dt, dst_dt, dim);
+    return false;
+  }
+  if (m.converts() && !(is_float_dtype(src_dt) && is_float_dtype(dst_dt))) {
+    set_error("extract: invalid argument: no conversion from dtype %d to dtype %d (a converting gather takes F16, BF16 "
+              "and F32 on either side)", src_dt, dst_dt);
+    return false;
+  }
+  return true;
+}
+
+// A chunk's wider side is at most 16 bytes (one load or store instruction per chunk and side, consecutive lanes on
+// consecutive addresses): 8 elements between the 16-bit types, 4 when one side is f32.  Measured against 8-element
+// chunks for those (a 16-B load with two 16-B stores, two 16-B loads with a 16-B store): profiles/feat_convert_ab.txt.
+constexpr int convert_max_epc(size_t src_es, size_t dst_es) { return (int)(16 / (src_es > dst_es ? src_es : dst_es)); }
+
+template <int SRC_DT, int DST_DT, bool SCATTER, typename Rows>
+static int launch_convert_pair(char *out, Rows rows, const uint32_t *dst_index, size_t n_max, Count n, size_t dim,
+                               int epc, uint64_t *miss_count, hipStream_t stream) {
+  const uint64_t rc = dim / epc;
+  if constexpr (convert_max_epc(sizeof(typename Elem<SRC_DT>::bits), sizeof(typename Elem<DST_DT>::bits)) == 8)
+    if (epc == 8)
+      return launch_chunks<ConvertChunk<8, SRC_DT, DST_DT>, Rows, SCATTER>(out, rows, dst_index, n_max, n, rc, miss_count, stream);
+  switch (epc) {
+    case 4: return launch_chunks<ConvertChunk<4, SRC_DT, DST_DT>, Rows, SCATTER>(out, rows, dst_index, n_max, n, rc, miss_count, stream);
+    case 2: return launch_chunks<ConvertChunk<2, SRC_DT, DST_DT>, Rows, SCATTER>(out, rows, dst_index, n_max, n, rc, miss_count, stream);
+    case 1: return launch_chunks<ConvertChunk<1, SRC_DT, DST_DT>, Rows, SCATTER>(out, rows, dst_index, n_max, n, rc, miss_count, stream);
+  }
+  set_error("extract: no %d-element chunk for dtype %d -> %d", epc, SRC_DT, DST_DT);
+  return GGMS_ERR_INVALID;
+}
+
+// src_bits: every source base pointer the locator may use, ORed (shard bases come from hipMalloc /
+// hipIpcOpenMemHandle / hipHostMalloc, >= 256-B aligned, and may be left out)
+template <bool SCATTER = true, typename Rows>
+static int launch_move(char *out, Rows rows, const uint32_t *dst_index, size_t n_max, Count n, const RowMove &m,
+                       uintptr_t src_bits, uint64_t *miss_count, hipStream_t stream) {
+  if (!m.converts())
+    return launch_gather(out, rows, dst_index, n_max, n, m.src_row_bytes(),
+                         pick_chunk(m.src_row_bytes(), (uintptr_t)out | src_bits), miss_count, stream);
+  const int epc = pick_chunk(m.dim, convert_max_epc(m.src_es, m.dst_es), m.src_es, src_bits, m.dst_es, (uintptr_t)out);
+#define GGMS_PAIR(S, D)                                                                                              \
+  if (m.src_dt == S && m.dst_dt == D)                                                                                \
+    return launch_convert_pair<S, D, SCATTER>(out, rows, dst_index, n_max, n, m.dim, epc, miss_count, stream);
+  GGMS_PAIR(GGMS_F16, GGMS_F32)
+  GGMS_PAIR(GGMS_BF16, GGMS_F32)
+  GGMS_PAIR(GGMS_F32, GGMS_F16)
+  GGMS_PAIR(GGMS_F32, GGMS_BF16)
+  GGMS_PAIR(GGMS_F16, GGMS_BF16)
+  GGMS_PAIR(GGMS_BF16, GGMS_F16)
+#undef GGMS_PAIR
+  set_error("extract: no conversion from dtype %d to dtype %d", m.src_dt, m.dst_dt);
+  return GGMS_ERR_INVALID;
+}
+
 } // namespace ggms
 
 using namespace ggms;
+
+// The bodies behind the entry points that exist in a plain and a converting form (ggms_*_convert): one dtype is the
+// plain call, two are the converting one.
+static int gather_scatter_rows(void *out, const void *src, const ggms_id_t *src_index, const ggms_id_t *dst_index,
+                               size_t num, const uint64_t *num_dev, size_t dim, int src_dtype, int out_dtype,
+                               uint32_t src_row_mask, ggms_stream_t stream) {
+  RowMove m;
+  if (!row_move(src_dtype, out_dtype, dim, m)) return GGMS_ERR_INVALID;
+  if (num == 0) return GGMS_OK;
+  GGMS_CHECK_ARG(out && src);
+  PlainRows rows{(const char *)src, src_index, m.src_row_bytes(), src_row_mask};
+  return launch_move((char *)out, rows, dst_index, num, count_of(num, num_dev), m, (uintptr_t)src, nullptr,
+                     to_stream(stream));
+}
+
+static int extract_cached_rows(void *out, const ggms_id_t *nodes, size_t num_nodes, const uint64_t *num_nodes_dev,
+                               const ggms_id_t *table, const void *const *parts, uint32_t num_part,
+                               const void *host_feat, size_t dim, int src_dtype, int out_dtype, uint64_t *num_miss_dev,
+                               ggms_stream_t stream) {
+  RowMove m;
+  if (!row_move(src_dtype, out_dtype, dim, m)) return GGMS_ERR_INVALID;
+  if (num_nodes == 0) return GGMS_OK;
+  GGMS_CHECK_ARG(out && nodes && parts);
+  PartPtrs pp;
+  if (!part_ptrs(parts, num_part, pp)) return GGMS_ERR_INVALID;
+  const Divisor div = divisor_of(num_part ? num_part : 1);
+  if (!table) { // full cache in node order: slot = node id
+    IdentRows rows{pp, nodes, m.src_row_bytes(), div};
+    if (num_miss_dev) GGMS_HIP(hipMemsetAsync(num_miss_dev, 0, sizeof(uint64_t), to_stream(stream)));
+    return launch_move<false>((char *)out, rows, nullptr, num_nodes, count_of(num_nodes, num_nodes_dev), m, 0, nullptr,
+                              to_stream(stream));
+  }
+  CachedRows rows{pp, nodes, table, (const char *)host_feat, m.src_row_bytes(), div};
+  return launch_move<false>((char *)out, rows, nullptr, num_nodes, count_of(num_nodes, num_nodes_dev), m,
+                            (uintptr_t)host_feat, num_miss_dev, to_stream(stream));
+}
+
+static int extract_tiered_rows(void *out, const ggms_id_t *nodes, size_t num_nodes, const uint64_t *num_nodes_dev,
+                               const ggms_feature_tiers_t *tiers, size_t dim, int src_dtype, int out_dtype,
+                               uint64_t *tier_rows_dev, ggms_stream_t stream) {
+  RowMove m;
+  if (!row_move(src_dtype, out_dtype, dim, m)) return GGMS_ERR_INVALID;
+  GGMS_CHECK_ARG(tiers);
+  if (num_nodes == 0) return GGMS_OK;
+  GGMS_CHECK_ARG(out && nodes && tiers->parts && tiers->num_part >= 1 && tiers->my_part < tiers->num_part);
+  GGMS_CHECK_ARG(tiers->num_replica == 0 || tiers->replica);
+  GGMS_CHECK_ARG(tiers->num_replica < (1ull << 32));
+  PartPtrs pp;
+  if (!part_ptrs(tiers->parts, tiers->num_part, pp)) return GGMS_ERR_INVALID;
+  TieredRows rows{pp, nodes, tiers->table, (const char *)tiers->host_feat,
+                  (const char *)tiers->replica, m.src_row_bytes(), (uint32_t)tiers->num_replica,
+                  divisor_of(tiers->num_part), tiers->my_part, tiers->host_row_mask ? tiers->host_row_mask : 0xffffffffu};
+  return launch_move<false>((char *)out, rows, nullptr, num_nodes, count_of(num_nodes, num_nodes_dev), m,
+                            (uintptr_t)tiers->host_feat | (uintptr_t)tiers->replica, tier_rows_dev, to_stream(stream));
+}
 
 extern "C" {
 
@@ -463,10 +656,7 @@ int ggms_gather_scatter(void *out, const void *src, const ggms_id_t *src_index, 
     GGMS_LAUNCH_CHECK();
     return GGMS_OK;
   }
-  const int cb = pick_chunk(row_bytes, (uintptr_t)out | (uintptr_t)src);
-  PlainRows rows{(const char *)src, src_index, row_bytes};
-  return launch_gather((char *)out, rows, dst_index, num, count_of(num, num_dev), row_bytes, cb, nullptr,
-                       to_stream(stream));
+  return gather_scatter_rows(out, src, src_index, dst_index, num, num_dev, dim, dtype, dtype, 0xffffffffu, stream);
 }
 
 // ggms_gather_scatter with the source row taken as src_index[i] & src_row_mask: gpu_mock_extract
@@ -474,15 +664,14 @@ int ggms_gather_scatter(void *out, const void *src, const ggms_id_t *src_index, 
 int ggms_gather_scatter_masked(void *out, const void *src, const ggms_id_t *src_index, const ggms_id_t *dst_index,
                                size_t num, const uint64_t *num_dev, size_t dim, int dtype, uint32_t src_row_mask,
                                ggms_stream_t stream) {
-  const size_t es = ggms_dtype_bytes(dtype);
-  GGMS_CHECK_ARG(es != 0 && dim != 0);
-  if (num == 0) return GGMS_OK;
-  GGMS_CHECK_ARG(out && src && src_index);
-  const size_t row_bytes = dim * es;
-  const int cb = pick_chunk(row_bytes, (uintptr_t)out | (uintptr_t)src);
-  PlainRows rows{(const char *)src, src_index, row_bytes, src_row_mask};
-  return launch_gather((char *)out, rows, dst_index, num, count_of(num, num_dev), row_bytes, cb, nullptr,
-                       to_stream(stream));
+  GGMS_CHECK_ARG(num == 0 || src_index);
+  return gather_scatter_rows(out, src, src_index, dst_index, num, num_dev, dim, dtype, dtype, src_row_mask, stream);
+}
+
+int ggms_gather_scatter_convert(void *out, const void *src, const ggms_id_t *src_index, const ggms_id_t *dst_index,
+                                size_t num, const uint64_t *num_dev, size_t dim, int src_dtype, int out_dtype,
+                                uint32_t src_row_mask, ggms_stream_t stream) {
+  return gather_scatter_rows(out, src, src_index, dst_index, num, num_dev, dim, src_dtype, out_dtype, src_row_mask, stream);
 }
 
 // GPUMockExtract (cuda_extraction.cu:119-160): dst[i, :] = src[index[i] & (2^mock_bits - 1), :]
@@ -514,44 +703,29 @@ int ggms_extract_cached(void *out, const ggms_id_t *nodes, size_t num_nodes, con
                         const ggms_id_t *table, const void *const *parts, uint32_t num_part,
                         const void *host_feat, size_t dim, int dtype, uint64_t *num_miss_dev,
                         ggms_stream_t stream) {
-  const size_t es = ggms_dtype_bytes(dtype);
-  GGMS_CHECK_ARG(es != 0 && dim != 0);
-  if (num_nodes == 0) return GGMS_OK;
-  GGMS_CHECK_ARG(out && nodes && parts);
-  const size_t row_bytes = dim * es;
-  PartPtrs pp;
-  if (!part_ptrs(parts, num_part, pp)) return GGMS_ERR_INVALID;
-  const Divisor div = divisor_of(num_part ? num_part : 1);
-  if (!table) { // full cache in node order: slot = node id
-    IdentRows rows{pp, nodes, row_bytes, div};
-    if (num_miss_dev) GGMS_HIP(hipMemsetAsync(num_miss_dev, 0, sizeof(uint64_t), to_stream(stream)));
-    return launch_gather((char *)out, rows, nullptr, num_nodes, count_of(num_nodes, num_nodes_dev), row_bytes,
-                         pick_chunk(row_bytes, (uintptr_t)out), nullptr, to_stream(stream));
-  }
-  const int cb = pick_chunk(row_bytes, (uintptr_t)out | (uintptr_t)host_feat);
-  CachedRows rows{pp, nodes, table, (const char *)host_feat, row_bytes, div};
-  return launch_gather((char *)out, rows, nullptr, num_nodes, count_of(num_nodes, num_nodes_dev), row_bytes,
-                       cb, num_miss_dev, to_stream(stream));
+  return extract_cached_rows(out, nodes, num_nodes, num_nodes_dev, table, parts, num_part, host_feat, dim, dtype, dtype,
+                             num_miss_dev, stream);
+}
+
+int ggms_extract_cached_convert(void *out, const ggms_id_t *nodes, size_t num_nodes, const uint64_t *num_nodes_dev,
+                                const ggms_id_t *table, const void *const *parts, uint32_t num_part,
+                                const void *host_feat, size_t dim, int src_dtype, int out_dtype,
+                                uint64_t *num_miss_dev, ggms_stream_t stream) {
+  return extract_cached_rows(out, nodes, num_nodes, num_nodes_dev, table, parts, num_part, host_feat, dim, src_dtype,
+                             out_dtype, num_miss_dev, stream);
 }
 
 int ggms_extract_tiered(void *out, const ggms_id_t *nodes, size_t num_nodes, const uint64_t *num_nodes_dev,
                         const ggms_feature_tiers_t *tiers, size_t dim, int dtype, uint64_t *tier_rows_dev,
                         ggms_stream_t stream) {
-  const size_t es = ggms_dtype_bytes(dtype);
-  GGMS_CHECK_ARG(es != 0 && dim != 0 && tiers);
-  if (num_nodes == 0) return GGMS_OK;
-  GGMS_CHECK_ARG(out && nodes && tiers->parts && tiers->num_part >= 1 && tiers->my_part < tiers->num_part);
-  GGMS_CHECK_ARG(tiers->num_replica == 0 || tiers->replica);
-  GGMS_CHECK_ARG(tiers->num_replica < (1ull << 32));
-  const size_t row_bytes = dim * es;
-  const int cb = pick_chunk(row_bytes, (uintptr_t)out | (uintptr_t)tiers->host_feat | (uintptr_t)tiers->replica);
-  PartPtrs pp;
-  if (!part_ptrs(tiers->parts, tiers->num_part, pp)) return GGMS_ERR_INVALID;
-  TieredRows rows{pp, nodes, tiers->table, (const char *)tiers->host_feat,
-                  (const char *)tiers->replica, row_bytes, (uint32_t)tiers->num_replica, divisor_of(tiers->num_part),
-                  tiers->my_part, tiers->host_row_mask ? tiers->host_row_mask : 0xffffffffu};
-  return launch_gather((char *)out, rows, nullptr, num_nodes, count_of(num_nodes, num_nodes_dev), row_bytes, cb,
-                       tier_rows_dev, to_stream(stream));
+  return extract_tiered_rows(out, nodes, num_nodes, num_nodes_dev, tiers, dim, dtype, dtype, tier_rows_dev, stream);
+}
+
+int ggms_extract_tiered_convert(void *out, const ggms_id_t *nodes, size_t num_nodes, const uint64_t *num_nodes_dev,
+                                const ggms_feature_tiers_t *tiers, size_t dim, int src_dtype, int out_dtype,
+                                uint64_t *tier_rows_dev, ggms_stream_t stream) {
+  return extract_tiered_rows(out, nodes, num_nodes, num_nodes_dev, tiers, dim, src_dtype, out_dtype, tier_rows_dev,
+                             stream);
 }
 
 int ggms_dynamic_cache_reset(uint64_t *stamps, size_t num_node, ggms_stream_t stream) {

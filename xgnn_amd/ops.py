@@ -16,10 +16,10 @@ from ._lib import Graph as _CGraph, HashTable as _CHashTable, check, lib
 
 EMPTY_KEY = 0xFFFFFFFF
 
-# DataType codes, samgraph/common/common.h:38-46
+# DataType codes, samgraph/common/common.h:38-46; 7 = GGMS_BF16 (an extension, include/ggms.h)
 DTYPE_CODE = {
     torch.float32: 0, torch.float64: 1, torch.float16: 2, torch.uint8: 3,
-    torch.int32: 4, torch.int8: 5, torch.int64: 6, torch.int16: 2, torch.bfloat16: 2,
+    torch.int32: 4, torch.int8: 5, torch.int64: 6, torch.int16: 2, torch.bfloat16: 7,
 }
 
 KHOP0, KHOP1, WEIGHTED_KHOP, RANDOM_WALK, WEIGHTED_KHOP_PREFIX, KHOP2, WEIGHTED_KHOP_HASH_DEDUP, KHOP3 = range(8)
@@ -289,6 +289,18 @@ def gather_scatter(out, src, src_index, dst_index, num=None, num_dev=None):
     return out
 
 
+def gather_scatter_convert(out, src, src_index, dst_index, num=None, num_dev=None, src_row_mask=0xFFFFFFFF):
+    """ggms_gather_scatter_convert: out[dst(i), :] = src[src(i) & mask, :] delivered in out's dtype (src and out each
+    float16, bfloat16 or float32; the same dtype on both sides is the plain gather)."""
+    _require_gpu(out)
+    if num is None:
+        num = (src_index if src_index is not None else dst_index).numel()
+    check(lib().ggms_gather_scatter_convert(_ptr(out), _ptr(src), _ptr(src_index), _ptr(dst_index), num, _ptr(num_dev),
+                                            _dim_of(out), DTYPE_CODE[src.dtype], DTYPE_CODE[out.dtype], src_row_mask,
+                                            _stream()), "ggms_gather_scatter_convert")
+    return out
+
+
 class PartTable:
     """HOST array of shard base pointers (DeviceDistFeature / DeviceDistGraph, dist_graph.h:114-212): the operators
     hand the pointers to their kernels by value, at most GGMS_MAX_PARTS = 8 shards."""
@@ -333,6 +345,44 @@ def extract_cached(out, nodes, table, parts_table, num_part, host_feat, num=None
     return out
 
 
+def extract_cached_convert(out, src_dtype, nodes, table, parts_table, num_part, host_feat, num=None, num_dev=None,
+                           num_miss=None):
+    """extract_cached with every source (shards, host rows) in `src_dtype` and the rows delivered in out's dtype."""
+    _require_gpu(out)
+    if num is None:
+        num = nodes.numel()
+    check(lib().ggms_extract_cached_convert(_ptr(out), _ptr(nodes), num, _ptr(num_dev), _ptr(table), parts_table.ptr(),
+                                            num_part, _ptr(host_feat), _dim_of(out), DTYPE_CODE[src_dtype],
+                                            DTYPE_CODE[out.dtype], _ptr(num_miss), _stream()),
+          "ggms_extract_cached_convert")
+    return out
+
+
+def _feature_tiers(table, replica, parts_table, num_part, my_part, host_feat, host_row_mask=0):
+    t = _lib.FeatureTiers()
+    t.table = table.data_ptr() if table is not None else None
+    t.replica = replica.data_ptr() if replica is not None else None
+    t.num_replica = replica.shape[0] if replica is not None else 0
+    t.parts = parts_table.ptr().value
+    t.num_part, t.my_part = num_part, my_part
+    t.host_feat = host_feat.data_ptr() if host_feat is not None else None
+    t.host_row_mask = host_row_mask
+    return t
+
+
+def extract_tiered_convert(out, src_dtype, nodes, table, replica, parts_table, num_part, my_part, host_feat, num=None,
+                           num_dev=None, tier_rows=None, host_row_mask=0):
+    """extract_tiered with every tier in `src_dtype` and the rows delivered in out's dtype."""
+    _require_gpu(out)
+    if num is None:
+        num = nodes.numel()
+    t = _feature_tiers(table, replica, parts_table, num_part, my_part, host_feat, host_row_mask)
+    check(lib().ggms_extract_tiered_convert(_ptr(out), _ptr(nodes), num, _ptr(num_dev), C.byref(t), _dim_of(out),
+                                            DTYPE_CODE[src_dtype], DTYPE_CODE[out.dtype], _ptr(tier_rows), _stream()),
+          "ggms_extract_tiered_convert")
+    return out
+
+
 def extract_tiered(out, nodes, table, replica, parts_table, num_part, my_part, host_feat, num=None, num_dev=None,
                    tier_rows=None):
     """Every tier of the GGMS store in one gather (include/ggms.h ggms_extract_tiered): replica of the hottest
@@ -341,13 +391,7 @@ def extract_tiered(out, nodes, table, replica, parts_table, num_part, my_part, h
     _require_gpu(out)
     if num is None:
         num = nodes.numel()
-    t = _lib.FeatureTiers()
-    t.table = table.data_ptr() if table is not None else None
-    t.replica = replica.data_ptr() if replica is not None else None
-    t.num_replica = replica.shape[0] if replica is not None else 0
-    t.parts = parts_table.ptr().value
-    t.num_part, t.my_part = num_part, my_part
-    t.host_feat = host_feat.data_ptr() if host_feat is not None else None
+    t = _feature_tiers(table, replica, parts_table, num_part, my_part, host_feat)
     check(lib().ggms_extract_tiered(_ptr(out), _ptr(nodes), num, _ptr(num_dev), C.byref(t), _dim_of(out),
                                     DTYPE_CODE[out.dtype], _ptr(tier_rows), _stream()), "ggms_extract_tiered")
     return out

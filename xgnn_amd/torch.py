@@ -13,7 +13,7 @@ import torch
 from .common import *  # noqa: F401,F403  (enum mirrors, like `from samgraph.common import *`)
 from .common import _basics, Tensor as _CTensor
 
-for _name in ("config init start num_class feat_dim num_epoch steps_per_epoch get_next_batch get_graph_num_src "
+for _name in ("init start num_class feat_dim num_epoch steps_per_epoch get_next_batch get_graph_num_src "
               "get_graph_num_dst get_graph_num_edge shutdown sample_once log_step log_step_add log_epoch_add "
               "get_log_init_value get_log_step_value get_log_epoch_value report_init report_step report_step_average "
               "report_epoch report_epoch_average report_node_access trace_step_begin trace_step_end "
@@ -24,7 +24,23 @@ for _name in ("config init start num_class feat_dim num_epoch steps_per_epoch ge
 
 # DataType code -> (numpy typestr, torch dtype); common/common.h:38-46, adapter.cc:33-53
 _DT = {0: ("<f4", torch.float32), 1: ("<f8", torch.float64), 2: ("<f2", torch.float16), 3: ("|u1", torch.uint8),
-       4: ("<i4", torch.int32), 5: ("|i1", torch.int8), 6: ("<i8", torch.int64)}
+       4: ("<i4", torch.int32), 5: ("|i1", torch.int8), 6: ("<i8", torch.int64),
+       # GGMS_BF16 (an extension): neither numpy nor the CUDA array interface has a bf16 typestr, so the buffer is
+       # viewed as 16-bit integers and re-viewed as bfloat16 (_as_dtype)
+       7: ("<i2", torch.bfloat16)}
+
+# config key `feat_out_dtype` was given: get_graph_feat hands the rows out as the gather delivered them
+_feat_as_delivered = False
+
+
+def config(run_config):
+    global _feat_as_delivered
+    _feat_as_delivered = "feat_out_dtype" in run_config
+    return _basics.config(run_config)
+
+
+def _as_dtype(tensor, code):
+    return tensor.view(torch.bfloat16) if code == 7 else tensor
 
 
 class _DeviceView(object):
@@ -54,7 +70,7 @@ def _wrap(t, key):
         dev = torch.device("cuda", t.device_id)
         if n == 0:
             return torch.empty(tuple(int(t.shape[i]) for i in range(t.ndim)), dtype=_DT[t.dtype][1], device=dev)
-        return torch.as_tensor(_DeviceView(t, key), device=dev)
+        return _as_dtype(torch.as_tensor(_DeviceView(t, key), device=dev), t.dtype)  # (a view: the retain stays with it)
     # host memory: numpy view over the mapped dataset file (GetDatasetFeature, adapter.cc:136-152)
     shape = tuple(int(t.shape[i]) for i in range(t.ndim))
     if n == 0 or not t.data:
@@ -63,7 +79,7 @@ def _wrap(t, key):
     a = np.frombuffer(buf, dtype=_DT[t.dtype][0]).reshape(shape)
     # a batch of the CPU deployment (arch0, host trainer) lives in a slot the engine reuses: hand out a copy;
     # the dataset tensors (key None) stay zero-copy views of the mapped files
-    return torch.from_numpy(a.copy() if key is not None else a)
+    return _as_dtype(torch.from_numpy(a.copy() if key is not None else a), t.dtype)
 
 
 def _get(fn, key, *args):
@@ -74,7 +90,7 @@ def _get(fn, key, *args):
 
 def get_graph_feat(batch_key):
     batch_feat = _get("samgraph_get_graph_feat", batch_key)
-    if batch_feat.dtype != torch.float32:
+    if not _feat_as_delivered and batch_feat.dtype != torch.float32:
         batch_feat = batch_feat.float()
     return batch_feat
 
