@@ -41,7 +41,11 @@ enum ggms_status {
 };
 
 /* DataType, common.h:38-46 (same integer codes); GGMS_BF16 is an extension (the reference has no such type): a
- * feature table may be bf16, and every call that moves rows as bytes takes it like any other 2-byte type */
+ * feature table may be bf16, and every call that moves rows as bytes takes it like any other 2-byte type.
+ * GGMS_F8E4M3 / GGMS_F8E5M2 (extensions too) are the OCP 8-bit floats, one byte per element: E4M3 is the "fn" variant
+ * (bias 7, no infinities, NaN = 0x7f / 0xff, largest finite 448), E5M2 is IEEE-like (bias 15, +-inf = 0x7c / 0xfc);
+ * NOT the FNUZ variants.  Table types: moved as bytes like U8, decoded by the converting gathers below.  Codes 8 .. 15
+ * are unknown (ggms_dtype_bytes = 0). */
 enum ggms_dtype {
   GGMS_F32 = 0,
   GGMS_F64 = 1,
@@ -50,7 +54,9 @@ enum ggms_dtype {
   GGMS_I32 = 4,
   GGMS_I8 = 5,
   GGMS_I64 = 6,
-  GGMS_BF16 = 7
+  GGMS_BF16 = 7,
+  GGMS_F8E4M3 = 16,
+  GGMS_F8E5M2 = 17
 };
 
 int ggms_abi_version(void);
@@ -557,12 +563,16 @@ int ggms_extract_tiered(void *out, const ggms_id_t *nodes, size_t num_nodes,
  * locators, counters and launch path (a launch timer rides on it, GGMS_EXTRACT_BLOCKS caps its grid).  `out` holds
  * rows of dim x ggms_dtype_bytes(out_dtype) bytes, every source rows of dim x ggms_dtype_bytes(src_dtype).
  *   - src_dtype == out_dtype (any dtype) IS the plain call;
- *   - otherwise both must be one of F16 / BF16 / F32, else GGMS_ERR_INVALID;
+ *   - otherwise both must be one of F16 / BF16 / F32, else GGMS_ERR_INVALID -- with one extension on the source side:
+ *     an FP8 dtype (F8E4M3, F8E5M2) is a legal src_dtype with out_dtype in {F32, F16, BF16}, or with out_dtype ==
+ *     src_dtype (the plain call); it is never a legal out_dtype for another source (GGMS_ERR_INVALID with a message,
+ *     like every unknown pair).  Decoding is exact for every finite code into all three outputs; E5M2's +-inf stay
+ *     +-inf, a NaN code gives a NaN, -0 stays -0;
  *   - widening (F16, BF16 -> F32) is exact, subnormals included; narrowing (F32 -> F16, BF16) rounds to nearest
  *     even, overflows to +-inf and produces subnormals; F16 <-> BF16 goes through f32; NaN stays NaN (payload
  *     unspecified);
- *   - rows move in chunks of 8, 4, 2 or 1 ELEMENTS (at most 16 bytes on the wider side: 8 between F16 and BF16,
- *     4 with F32 on one side): the widest that divides dim with every source base aligned to chunk x source element
+ *   - rows move in chunks of 8, 4, 2 or 1 ELEMENTS (at most 16 bytes on the wider side: 8 between F16 and BF16 and
+ *     from FP8 into either, 4 with F32 on one side): the widest that divides dim with every source base aligned to chunk x source element
  *     bytes and `out` to chunk x output element bytes.
  * ggms_gather_scatter_convert is the general form of ggms_gather_scatter_masked: src_index and dst_index may each be
  * NULL (identity); src_row_mask applies to src_index's values (0xffffffff: none).

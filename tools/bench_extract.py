@@ -6,23 +6,33 @@ algorithmic TB/s (4-B index + row read + row write) and as a fraction of the 8 T
 times the converting gather of one pair (ggms_gather_scatter_convert; the same dtype twice is the plain gather), and
     python tools/bench_extract.py --ab [--out FILE]
 the comparison behind `feat_out_dtype` in one process, alternating order, table in HBM: (a) plain f16 gather + torch
-.float(), (b) fused f16 -> f32, (c) plain f32, (d) f32 -> bf16."""
+.float(), (b) fused f16 -> f32, (c) plain f32, (d) f32 -> bf16, and
+    python tools/bench_extract.py --fp8-ab [--dim 128 --rows N --table-rows N] [--parent-lib SO] [--alt-lib SO] [--out FILE]
+the comparison behind FP8 tables: the six FP8 -> f32 / f16 / bf16 gathers beside the plain f32 gather and the f16 -> X
+gathers (of another build of the library too: --parent-lib; --alt-lib adds the FP8 gathers of a trial build), and a
+straight copy as the session's copy ceiling."""
 import argparse
+import ctypes as C
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from xgnn_amd import ops
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--table-dtype", choices=["f32", "f16", "bf16"])
+ap.add_argument("--table-dtype", choices=["f32", "f16", "bf16", "f8e4m3", "f8e5m2"])
 ap.add_argument("--out-dtype", choices=["f32", "f16", "bf16"])
 ap.add_argument("--dim", type=int, default=128)
 ap.add_argument("--rows", type=int, default=2_960_000, help="rows per gather (bench.py's papers100M-shaped batch)")
 ap.add_argument("--table-rows", type=int, default=16_000_000)
 ap.add_argument("--ab", action="store_true")
-ap.add_argument("--out", help="--ab: also write the report to this file")
+ap.add_argument("--fp8-ab", action="store_true")
+ap.add_argument("--parent-lib", help="--fp8-ab: a libggms_hip.so of another build, timed beside this one")
+ap.add_argument("--alt-lib", help="--fp8-ab: a trial build whose FP8 gathers are timed too")
+ap.add_argument("--alt-name", default="trial build")
+ap.add_argument("--out", help="--ab / --fp8-ab: also write the report to this file")
 args = ap.parse_args()
-DT = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
+DT = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16, "f8e4m3": torch.float8_e4m3fn,
+      "f8e5m2": torch.float8_e5m2}
 
 dev = torch.device("cuda", 0)
 N, n = 2_449_029, 1_280_000
@@ -41,10 +51,16 @@ def timeit(fn, reps=20):
     return e0.elapsed_time(e1) / reps * 1e-3
 
 
+def make_table(table_dtype):
+    if table_dtype.startswith("f8"):  # random codes: the decode has no data-dependent branch
+        return torch.randint(0, 256, (args.table_rows, args.dim), device=dev, dtype=torch.uint8).view(DT[table_dtype])
+    return torch.randn(args.table_rows, args.dim, device=dev).to(DT[table_dtype])
+
+
 def convert_setup(table_dtype, out_dtype, idx, table=None):
     """(table, out, gather) of one pair; bytes per row = 4 (index) + row read + row written."""
     if table is None:
-        table = torch.randn(args.table_rows, args.dim, device=dev).to(DT[table_dtype])
+        table = make_table(table_dtype)
     out = torch.empty((idx.numel(), args.dim), dtype=DT[out_dtype], device=dev)
     return table, out, lambda: ops.gather_scatter_convert(out, table, idx, None)
 
@@ -85,8 +101,85 @@ def run_ab():
             f.write(text + "\n")
 
 
+def run_fp8_ab():
+    """Every case = one ggms_gather_scatter_convert launch on the same index; 5 rounds x 30 launches in alternating
+    order; algorithmic bytes = rows x (4 + dim x (table + output element bytes))."""
+    idx = torch.randint(0, args.table_rows, (args.rows,), device=dev, dtype=torch.int32)
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def entry(path):
+        fn = C.CDLL(path).ggms_gather_scatter_convert
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_uint32, C.c_void_p]
+        return fn
+
+    from xgnn_amd import _lib
+    libs = [("this build", entry(_lib.LIB_PATH))]
+    if args.parent_lib:
+        libs.append(("parent build", entry(args.parent_lib)))
+    tables = {k: make_table(k) for k in ("f32", "f16", "f8e4m3", "f8e5m2")}
+    outs = {k: torch.empty((args.rows, args.dim), dtype=DT[k], device=dev) for k in ("f32", "f16", "bf16")}
+    cases = []
+
+    def add(name, fn, td, od):
+        t, o = tables[td], outs[od]
+        code = ops.DTYPE_CODE
+
+        def run():
+            rc = fn(o.data_ptr(), t.data_ptr(), idx.data_ptr(), None, args.rows, None, args.dim, code[t.dtype],
+                    code[o.dtype], 0xFFFFFFFF, stream)
+            assert rc == 0, (name, rc)
+        by = args.rows * (4 + args.dim * (t.element_size() + o.element_size()))
+        cases.append((name, run, by))
+
+    for lib_name, fn in libs:
+        add(f"{lib_name}: f32 plain", fn, "f32", "f32")
+        for od in ("f32", "f16", "bf16"):
+            add(f"{lib_name}: f16 -> {od}", fn, "f16", od)
+    for td in ("f8e4m3", "f8e5m2"):
+        for od in ("f32", "f16", "bf16"):
+            add(f"this build: {td} -> {od}", libs[0][1], td, od)
+    if args.alt_lib:
+        fn = entry(args.alt_lib)
+        for td in ("f8e4m3", "f8e5m2"):  # the trial differs in the chunk of the f32 output only
+            add(f"{args.alt_name}: {td} -> f32", fn, td, "f32")
+    # the session's copy ceiling: a straight device copy of the f32 output's size (read + write)
+    src_copy = torch.empty_like(outs["f32"])
+    cases.append(("straight copy (torch copy_), f32 output size", lambda: outs["f32"].copy_(src_copy),
+                  2 * outs["f32"].numel() * 4))
+    times = {name: [] for name, _, _ in cases}
+    for rnd in range(5):
+        for name, fn, _ in (cases if rnd % 2 == 0 else cases[::-1]):
+            times[name].append(timeit(fn, reps=30))
+    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    ceiling = cases[-1][2] / med[cases[-1][0]]
+    lines = [f"FP8 table A/B: {args.rows} rows x dim {args.dim}, tables of {args.table_rows} rows in HBM, one process, "
+             f"5 rounds x 30 launches per case in alternating order, median of the rounds (min .. max; spread = "
+             f"(max - min) / median)",
+             f"device: {torch.cuda.get_device_name(0)}; copy ceiling of this session: {ceiling / 1e12:.3f} TB/s"]
+    for name, _, by in cases:
+        v = times[name]
+        lines.append(f"{name:46s} {med[name] * 1e3:7.4f} ms  ({min(v) * 1e3:.4f} .. {max(v) * 1e3:.4f}; spread "
+                     f"{(max(v) - min(v)) / med[name] * 100:4.1f} %)  {by / med[name] / 1e12:5.2f} TB/s algorithmic = "
+                     f"{by / med[name] / ceiling:.3f} of the copy ceiling")
+    ref = "parent build" if args.parent_lib else "this build"
+    for td in ("f8e4m3", "f8e5m2"):
+        for od in ("f32", "f16", "bf16"):
+            a, b = med[f"this build: {td} -> {od}"], med[f"{ref}: f16 -> {od}"]
+            lines.append(f"{td} -> {od} / {ref}'s f16 -> {od} = {a / b:.3f}")
+    text = "\n".join(lines)
+    print(text, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
 if args.ab:
     run_ab()
+    sys.exit(0)
+if args.fp8_ab:
+    run_fp8_ab()
     sys.exit(0)
 if args.table_dtype or args.out_dtype:
     td, od = args.table_dtype or args.out_dtype, args.out_dtype or args.table_dtype

@@ -144,6 +144,8 @@ size_t ggms_dtype_bytes(int dtype) {
     case GGMS_I8: return 1;
     case GGMS_I64: return 8;
     case GGMS_BF16: return 2;
+    case GGMS_F8E4M3: return 1;
+    case GGMS_F8E5M2: return 1;
     default: return 0;
   }
 }

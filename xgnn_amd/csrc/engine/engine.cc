@@ -308,12 +308,15 @@ void Engine::LoadDataset() {
     if (k == "FEAT_DATA_TYPE") {
       static const std::map<std::string, int> names = {{"F32", GGMS_F32}, {"F64", GGMS_F64}, {"F16", GGMS_F16},
                                                        {"U8", GGMS_U8},   {"I32", GGMS_I32}, {"I8", GGMS_I8},
-                                                       {"I64", GGMS_I64}, {"BF16", GGMS_BF16}};
+                                                       {"I64", GGMS_I64}, {"BF16", GGMS_BF16},
+                                                       {"F8E4M3", GGMS_F8E4M3}, {"F8E5M2", GGMS_F8E5M2}};
       SAM_CHECK(names.count(v), "unknown FEAT_DATA_TYPE " + v);
       ds.feat_dtype = names.at(v);
-      if (cfg.feat_out_dtype >= 0 && ds.feat_dtype != GGMS_F32 && ds.feat_dtype != GGMS_F16 && ds.feat_dtype != GGMS_BF16)
-        fatal(__FILE__, __LINE__, "feat_out_dtype with FEAT_DATA_TYPE " + v + ": the gather converts F16, BF16 and F32 "
-                                  "tables only");
+      // (an FP8 table is a source of the converting gather only: without the key its rows are moved as bytes)
+      if (cfg.feat_out_dtype >= 0 && ds.feat_dtype != GGMS_F32 && ds.feat_dtype != GGMS_F16 && ds.feat_dtype != GGMS_BF16 &&
+          ds.feat_dtype != GGMS_F8E4M3 && ds.feat_dtype != GGMS_F8E5M2)
+        fatal(__FILE__, __LINE__, "feat_out_dtype with FEAT_DATA_TYPE " + v + ": the gather converts F16, BF16, F32, "
+                                  "F8E4M3 and F8E5M2 tables only");
     } else {
       meta[k] = std::stoull(v);
     }

@@ -22,6 +22,7 @@
 
 #include <hip/hip_ext.h>
 
+#include "fp8_decode.h"
 #include "ggms_device.h"
 
 namespace ggms {
@@ -38,7 +39,7 @@ template <> struct ChunkT<1> { using type = uint8_t; };
 // ---- what a chunk is ----------------------------------------------------------------------------------------------
 // The sweep moves CHUNKS: a fixed number of elements of a row, read as Src and written as Dst.  The plain gather's
 // chunk is CB bytes on both sides.  A converting gather (ggms_*_convert: an F16 / BF16 / F32 table delivered in
-// another of the three types) has chunks of EPC elements: EPC x source element bytes in, EPC x output element bytes
+// another of the three types, or an FP8 table delivered in one of them) has chunks of EPC elements: EPC x source element bytes in, EPC x output element bytes
 // out, converted at store time -- the registers a lane holds between its loads and its first store are the SOURCE
 // chunks only, whichever side is the wider one.
 template <int CB> struct CopyChunk {
@@ -69,6 +70,15 @@ template <> struct Elem<GGMS_BF16> { // the upper half of an f32
     return (bits)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16); // nearest even; a carry out of the mantissa ends in inf
   }
 };
+// the OCP 8-bit floats (fp8_decode.h): SOURCE types only -- no from_f32, so no pair with one of them as output exists
+template <> struct Elem<GGMS_F8E4M3> {
+  using bits = uint8_t;
+  static __device__ __forceinline__ float to_f32(bits b) { return fp8_e4m3_to_f32(b); }
+};
+template <> struct Elem<GGMS_F8E5M2> {
+  using bits = uint8_t;
+  static __device__ __forceinline__ float to_f32(bits b) { return fp8_e5m2_to_f32(b); }
+};
 template <typename T, int N> struct VecT { typedef T type __attribute__((ext_vector_type(N))); };
 template <typename T> struct VecT<T, 1> { using type = T; };
 
@@ -78,13 +88,19 @@ template <int EPC, int SRC_DT, int DST_DT> struct ConvertChunk {
   static constexpr int kSrcBytes = EPC * (int)sizeof(typename S::bits), kDstBytes = EPC * (int)sizeof(typename D::bits);
   using Src = typename VecT<typename S::bits, EPC>::type;
   using Dst = typename VecT<typename D::bits, EPC>::type;
+  // every FP8 value is a bf16 number (at most 3 mantissa bits): the upper half of its f32, no rounding step
+  static constexpr bool kTruncates = (SRC_DT == GGMS_F8E4M3 || SRC_DT == GGMS_F8E5M2) && DST_DT == GGMS_BF16;
+  static __device__ __forceinline__ typename D::bits one(typename S::bits b) {
+    if constexpr (kTruncates) return (typename D::bits)(__builtin_bit_cast(uint32_t, S::to_f32(b)) >> 16);
+    else return D::from_f32(S::to_f32(b));
+  }
   static __device__ __forceinline__ Dst convert(Src v) {
     if constexpr (EPC == 1) {
-      return D::from_f32(S::to_f32(v));
+      return one(v);
     } else {
       Dst o;
 #pragma unroll
-      for (int e = 0; e < EPC; ++e) o[e] = D::from_f32(S::to_f32(v[e]));
+      for (int e = 0; e < EPC; ++e) o[e] = one(v[e]);
       return o;
     }
   }
@@ -502,8 +518,9 @@ static int launch_gather(char *out, Rows rows, const uint32_t *dst_index, size_t
 }
 
 // ---- how a call's rows are moved -------------------------------------------------------------------------------------
-// src_dt == dst_dt (any dtype): as bytes, the plain gather.  Otherwise both are one of F16 / BF16 / F32 and the gather
-// converts (ConvertChunk): the same locators, sweep and launch path, chunks of `epc` elements.
+// src_dt == dst_dt (any dtype): as bytes, the plain gather.  Otherwise the output is one of F16 / BF16 / F32, the source
+// one of those or an FP8 type (decoded, never produced), and the gather converts (ConvertChunk): the same locators,
+// sweep and launch path, chunks of `epc` elements.
 struct RowMove {
   int src_dt, dst_dt;
   size_t dim, src_es, dst_es;
@@ -511,15 +528,16 @@ struct RowMove {
   size_t src_row_bytes() const { return dim * src_es; }
 };
 static inline bool is_float_dtype(int dt) { return dt == GGMS_F16 || dt == GGMS_BF16 || dt == GGMS_F32; }
+static inline bool is_fp8_dtype(int dt) { return dt == GGMS_F8E4M3 || dt == GGMS_F8E5M2; }
 static bool row_move(int src_dt, int dst_dt, size_t dim, RowMove &m) {
   m = RowMove{src_dt, dst_dt, dim, ggms_dtype_bytes(src_dt), ggms_dtype_bytes(dst_dt)};
   if (m.src_es == 0 || m.dst_es == 0 || dim == 0) {
     set_error("extract: invalid argument: dtype %d -> %d, dim %zu (unknown dtype or empty rows)", src_dt, dst_dt, dim);
     return false;
   }
-  if (m.converts() && !(is_float_dtype(src_dt) && is_float_dtype(dst_dt))) {
+  if (m.converts() && !((is_float_dtype(src_dt) || is_fp8_dtype(src_dt)) && is_float_dtype(dst_dt))) {
     set_error("extract: invalid argument: no conversion from dtype %d to dtype %d (a converting gather takes F16, BF16 "
-              "and F32 on either side)", src_dt, dst_dt);
+              "and F32 on either side, F8E4M3 and F8E5M2 as the source only)", src_dt, dst_dt);
     return false;
   }
   return true;
@@ -528,6 +546,8 @@ static bool row_move(int src_dt, int dst_dt, size_t dim, RowMove &m) {
 // A chunk's wider side is at most 16 bytes (one load or store instruction per chunk and side, consecutive lanes on
 // consecutive addresses): 8 elements between the 16-bit types, 4 when one side is f32.  Measured against 8-element
 // chunks for those (a 16-B load with two 16-B stores, two 16-B loads with a 16-B store): profiles/feat_convert_ab.txt.
+// An FP8 source follows the same rule: 8 elements into a 16-bit type (8-B load, 16-B store), 4 into f32 (4-B load,
+// 16-B store); profiles/fp8_table_ab.txt.
 constexpr int convert_max_epc(size_t src_es, size_t dst_es) { return (int)(16 / (src_es > dst_es ? src_es : dst_es)); }
 
 template <int SRC_DT, int DST_DT, bool SCATTER, typename Rows>
@@ -564,6 +584,12 @@ static int launch_move(char *out, Rows rows, const uint32_t *dst_index, size_t n
   GGMS_PAIR(GGMS_F32, GGMS_BF16)
   GGMS_PAIR(GGMS_F16, GGMS_BF16)
   GGMS_PAIR(GGMS_BF16, GGMS_F16)
+  GGMS_PAIR(GGMS_F8E4M3, GGMS_F32)
+  GGMS_PAIR(GGMS_F8E4M3, GGMS_F16)
+  GGMS_PAIR(GGMS_F8E4M3, GGMS_BF16)
+  GGMS_PAIR(GGMS_F8E5M2, GGMS_F32)
+  GGMS_PAIR(GGMS_F8E5M2, GGMS_F16)
+  GGMS_PAIR(GGMS_F8E5M2, GGMS_BF16)
 #undef GGMS_PAIR
   set_error("extract: no conversion from dtype %d to dtype %d", m.src_dt, m.dst_dt);
   return GGMS_ERR_INVALID;

@@ -3,7 +3,7 @@
 There is no network, so ogbn-products / papers100M cannot be downloaded; these
 generators produce power-law in-neighbour CSRs with the same node count, mean
 degree, feature width and train-set size, plus exactly representable features
-so gathers can be checked bit for bit.  numpy only (host side).
+so gathers can be checked bit for bit.  numpy only (host side), but for the FP8 tables, which use torch's CPU casts.
 """
 import numpy as np
 
@@ -147,6 +147,7 @@ def write_dataset(path, graph, feat=None, label=None, valid_frac=0.02, test_frac
     """Write a dataset directory in the reference's on-disk format (datagen/README.md:37-51,
     samgraph/common/constant.cc:23-51, engine.cc:109-443): meta.txt (tab separated) + raw little-endian
     arrays: indptr/indices/train_set/test_set/valid_set/cache_by_* uint32, feat row-major, label int64;
+    feat_dtype "F8E4M3" / "F8E5M2": feat is a torch.float8_e4m3fn / float8_e5m2 tensor, or its bytes as a uint8 array;
     weights (one float per edge) adds prob_table.bin / alias_table.bin / prob_prefix_table.bin.
     minimal: what a sampling + extract run needs and nothing that costs minutes at papers100M size -- one-node
     valid / test sets instead of random slices of the complement, no cache_by_random.bin."""
@@ -168,6 +169,8 @@ def write_dataset(path, graph, feat=None, label=None, valid_frac=0.02, test_frac
     valid.tofile(os.path.join(path, "valid_set.bin"))
     test.tofile(os.path.join(path, "test_set.bin"))
     if feat is not None:
+        if feat_dtype in FP8_FORMATS:
+            feat = _fp8_bytes(feat, feat_dtype)
         np.ascontiguousarray(feat).tofile(os.path.join(path, "feat.bin"))
     if label is not None:
         np.ascontiguousarray(label, dtype=np.int64).tofile(os.path.join(path, "label.bin"))
@@ -187,3 +190,70 @@ def write_dataset(path, graph, feat=None, label=None, valid_frac=0.02, test_frac
         if feat_dtype != "F32":
             f.write(f"FEAT_DATA_TYPE\t{feat_dtype}\n")
     return path
+
+
+# FEAT_DATA_TYPE names of the OCP 8-bit float tables (include/ggms.h: GGMS_F8E4M3 = 16, GGMS_F8E5M2 = 17)
+FP8_FORMATS = ("F8E4M3", "F8E5M2")
+E4M3_MAX = 448.0  # the largest finite E4M3 value; the format has no infinity
+
+
+def _fp8_torch_dtype(fmt):
+    import torch
+    return {"F8E4M3": torch.float8_e4m3fn, "F8E5M2": torch.float8_e5m2}[fmt]
+
+
+def _fp8_bytes(feat, fmt):
+    """The bytes of an FP8 table: a torch tensor of the format's dtype, or a uint8 array that already holds them."""
+    import torch
+    if isinstance(feat, torch.Tensor):
+        assert feat.dtype == _fp8_torch_dtype(fmt), (feat.dtype, fmt)
+        return feat.contiguous().view(torch.uint8).numpy()
+    feat = np.asarray(feat)
+    assert feat.dtype == np.uint8, f"an {fmt} table is passed as its torch dtype or as uint8 bytes, not {feat.dtype}"
+    return feat
+
+
+def quantize_features(path_in, path_out, fmt, chunk_rows=1 << 20):
+    """Rewrite the F32 / F16 dataset at path_in as the same dataset with an FP8 feature table (fmt "F8E4M3" or
+    "F8E5M2") at path_out: every other file is linked (or copied where a link is not possible), feat.bin is cast on the
+    CPU with torch, round to nearest even, one chunk of rows at a time, and meta.txt names the new FEAT_DATA_TYPE.
+    A one-off offline step; there is no kernel for it.
+
+    E4M3 has no infinity and torch's cast turns everything beyond its range into NaN, so for E4M3 the values are
+    clamped to +-448 (the largest finite value) FIRST: an out-of-range input saturates; NaN stays NaN.  E5M2 is cast
+    as it is: overflow becomes +-inf, as in every IEEE-like format.  Unscaled: values are stored as they are."""
+    import os
+    import shutil
+    import torch
+    assert fmt in FP8_FORMATS, fmt
+    with open(os.path.join(path_in, "meta.txt")) as f:
+        meta = [line.split() for line in f if line.strip()]
+    kv = dict(meta)
+    src_name = kv.get("FEAT_DATA_TYPE", "F32")
+    assert src_name in ("F32", "F16"), f"quantize_features reads F32 and F16 tables, not {src_name}"
+    src_dt = np.float32 if src_name == "F32" else np.float16
+    n, dim = int(kv["NUM_NODE"]), int(kv["FEAT_DIM"])
+    os.makedirs(path_out, exist_ok=True)
+    for name in os.listdir(path_in):
+        if name in ("feat.bin", "meta.txt"):
+            continue
+        src, dst = os.path.join(path_in, name), os.path.join(path_out, name)
+        if os.path.exists(dst):
+            os.remove(dst)
+        try:
+            os.link(src, dst)
+        except OSError:
+            shutil.copyfile(src, dst)
+    table = np.memmap(os.path.join(path_in, "feat.bin"), dtype=src_dt, mode="r", shape=(n, dim))
+    with open(os.path.join(path_out, "feat.bin"), "wb") as out:
+        for r in range(0, n, chunk_rows):
+            v = torch.from_numpy(np.array(table[r:r + chunk_rows])).float()
+            if fmt == "F8E4M3":
+                v = v.clamp(-E4M3_MAX, E4M3_MAX)
+            out.write(v.to(_fp8_torch_dtype(fmt)).view(torch.uint8).numpy().tobytes())
+    with open(os.path.join(path_out, "meta.txt"), "w") as f:
+        for k, v in meta:
+            if k != "FEAT_DATA_TYPE":
+                f.write(f"{k}\t{v}\n")
+        f.write(f"FEAT_DATA_TYPE\t{fmt}\n")
+    return path_out

@@ -16,10 +16,12 @@ from ._lib import Graph as _CGraph, HashTable as _CHashTable, check, lib
 
 EMPTY_KEY = 0xFFFFFFFF
 
-# DataType codes, samgraph/common/common.h:38-46; 7 = GGMS_BF16 (an extension, include/ggms.h)
+# DataType codes, samgraph/common/common.h:38-46; 7 = GGMS_BF16, 16 / 17 = GGMS_F8E4M3 / GGMS_F8E5M2 (the OCP 8-bit
+# floats as TABLE types) are extensions, include/ggms.h
 DTYPE_CODE = {
     torch.float32: 0, torch.float64: 1, torch.float16: 2, torch.uint8: 3,
     torch.int32: 4, torch.int8: 5, torch.int64: 6, torch.int16: 2, torch.bfloat16: 7,
+    torch.float8_e4m3fn: 16, torch.float8_e5m2: 17,
 }
 
 KHOP0, KHOP1, WEIGHTED_KHOP, RANDOM_WALK, WEIGHTED_KHOP_PREFIX, KHOP2, WEIGHTED_KHOP_HASH_DEDUP, KHOP3 = range(8)
@@ -291,7 +293,8 @@ def gather_scatter(out, src, src_index, dst_index, num=None, num_dev=None):
 
 def gather_scatter_convert(out, src, src_index, dst_index, num=None, num_dev=None, src_row_mask=0xFFFFFFFF):
     """ggms_gather_scatter_convert: out[dst(i), :] = src[src(i) & mask, :] delivered in out's dtype (src and out each
-    float16, bfloat16 or float32; the same dtype on both sides is the plain gather)."""
+    float16, bfloat16 or float32, src also float8_e4m3fn or float8_e5m2; the same dtype on both sides is the plain
+    gather)."""
     _require_gpu(out)
     if num is None:
         num = (src_index if src_index is not None else dst_index).numel()
@@ -519,7 +522,9 @@ class _RawDevice:
 
 
 _TYPESTR = {torch.float32: "<f4", torch.float64: "<f8", torch.float16: "<f2", torch.uint8: "|u1",
-            torch.int32: "<i4", torch.int8: "|i1", torch.int64: "<i8"}
+            torch.int32: "<i4", torch.int8: "|i1", torch.int64: "<i8",
+            # the OCP 8-bit floats have no typestr: bytes, re-viewed as the dtype
+            torch.float8_e4m3fn: "|u1", torch.float8_e5m2: "|u1"}
 
 
 class RegisteredHost:
@@ -564,7 +569,7 @@ class SharedShard:
         with torch.cuda.device(self.device):
             check(lib().ggms_device_alloc(C.byref(p), nbytes), "ggms_device_alloc")
         self.ptr = p.value
-        self.tensor = torch.as_tensor(_RawDevice(self.ptr, self.shape, _TYPESTR[dtype]), device=self.device)
+        self.tensor = torch.as_tensor(_RawDevice(self.ptr, self.shape, _TYPESTR[dtype]), device=self.device).view(dtype)
         self._imported = []
 
     def export_handle(self):

@@ -27,7 +27,10 @@ _DT = {0: ("<f4", torch.float32), 1: ("<f8", torch.float64), 2: ("<f2", torch.fl
        4: ("<i4", torch.int32), 5: ("|i1", torch.int8), 6: ("<i8", torch.int64),
        # GGMS_BF16 (an extension): neither numpy nor the CUDA array interface has a bf16 typestr, so the buffer is
        # viewed as 16-bit integers and re-viewed as bfloat16 (_as_dtype)
-       7: ("<i2", torch.bfloat16)}
+       7: ("<i2", torch.bfloat16),
+       # GGMS_F8E4M3 / GGMS_F8E5M2 (extensions): the OCP 8-bit floats have no typestr either -- bytes, re-viewed
+       16: ("|u1", torch.float8_e4m3fn), 17: ("|u1", torch.float8_e5m2)}
+_FP8 = (torch.float8_e4m3fn, torch.float8_e5m2)
 
 # config key `feat_out_dtype` was given: get_graph_feat hands the rows out as the gather delivered them
 _feat_as_delivered = False
@@ -40,7 +43,7 @@ def config(run_config):
 
 
 def _as_dtype(tensor, code):
-    return tensor.view(torch.bfloat16) if code == 7 else tensor
+    return tensor.view(_DT[code][1]) if code in (7, 16, 17) else tensor
 
 
 class _DeviceView(object):
@@ -90,7 +93,9 @@ def _get(fn, key, *args):
 
 def get_graph_feat(batch_key):
     batch_feat = _get("samgraph_get_graph_feat", batch_key)
-    if not _feat_as_delivered and batch_feat.dtype != torch.float32:
+    # without the key an F16 / BF16 / integer table is cast to float32 here, as the reference's adapter does; an FP8
+    # table's rows stay the bytes the gather moved (decoding is the gather's job: feat_out_dtype)
+    if not _feat_as_delivered and batch_feat.dtype != torch.float32 and batch_feat.dtype not in _FP8:
         batch_feat = batch_feat.float()
     return batch_feat
 
