@@ -45,7 +45,18 @@ enum ggms_status {
  * GGMS_F8E4M3 / GGMS_F8E5M2 (extensions too) are the OCP 8-bit floats, one byte per element: E4M3 is the "fn" variant
  * (bias 7, no infinities, NaN = 0x7f / 0xff, largest finite 448), E5M2 is IEEE-like (bias 15, +-inf = 0x7c / 0xfc);
  * NOT the FNUZ variants.  Table types: moved as bytes like U8, decoded by the converting gathers below.  Codes 8 .. 15
- * are unknown (ggms_dtype_bytes = 0). */
+ * are unknown (ggms_dtype_bytes = 0).
+ * GGMS_Q8ROW (an extension) is a ROW format, not an element type: 8-bit codes with one scale and one offset per row.
+ *   - a row of `dim` elements is `dim` unsigned 8-bit codes, then zero bytes up to the next multiple of 8, then
+ *     float32 scale and float32 bias, both little endian; rows lie round_up(dim, 8) + 8 bytes apart
+ *     (ggms_row_bytes), so every row's trailer is 8-byte aligned whenever the table's base is;
+ *   - element value = fl32(fl32(float(code) * scale) + bias): an IEEE single multiply, then an IEEE single add, each
+ *     rounded to nearest even, NOT fused -- numpy's codes.astype(float32) * scale[:, None] + bias[:, None]; narrowed
+ *     to F16 / BF16 as an F32 table's values are (subnormal results and subnormal scales: unspecified);
+ *   - a SOURCE of the converting gathers only (into F32, F16, BF16; every base 8-byte aligned).  It has no element
+ *     size: ggms_dtype_bytes(GGMS_Q8ROW) = 0, so every plain entry point refuses the code as it refuses an unknown
+ *     one.  A Q8ROW table that has to move as bytes (cache fill, shards, replicas, the host table, IPC) moves as a
+ *     GGMS_U8 table of dim = ggms_row_bytes(GGMS_Q8ROW, dim) through the plain calls. */
 enum ggms_dtype {
   GGMS_F32 = 0,
   GGMS_F64 = 1,
@@ -56,7 +67,8 @@ enum ggms_dtype {
   GGMS_I64 = 6,
   GGMS_BF16 = 7,
   GGMS_F8E4M3 = 16,
-  GGMS_F8E5M2 = 17
+  GGMS_F8E5M2 = 17,
+  GGMS_Q8ROW = 18
 };
 
 int ggms_abi_version(void);
@@ -119,6 +131,9 @@ void ggms_debug_delay_next_scan(uint32_t sleeps);
 #define GGMS_DEBUG_NUM_KNOBS 3
 void ggms_debug_set_knob(int knob, long long value);
 size_t ggms_dtype_bytes(int dtype);
+/* bytes from one stored row of `dim` elements to the next: dim x ggms_dtype_bytes(dtype) for the element types,
+ * round_up(dim, 8) + 8 for GGMS_Q8ROW, 0 for an unknown code */
+size_t ggms_row_bytes(int dtype, size_t dim);
 
 /* ---------------------------------------------------------------------------
  * Graph view.  num_part == 0: DeviceNormalGraph (cuda/dist_graph.h:160-180),
@@ -568,6 +583,10 @@ int ggms_extract_tiered(void *out, const ggms_id_t *nodes, size_t num_nodes,
  *     src_dtype (the plain call); it is never a legal out_dtype for another source (GGMS_ERR_INVALID with a message,
  *     like every unknown pair).  Decoding is exact for every finite code into all three outputs; E5M2's +-inf stay
  *     +-inf, a NaN code gives a NaN, -0 stays -0;
+ *   - GGMS_Q8ROW is a legal src_dtype with out_dtype in {F32, F16, BF16} and in no other pair, not even with itself
+ *     (GGMS_ERR_INVALID with a message).  Its source rows lie ggms_row_bytes(GGMS_Q8ROW, dim) apart, every source
+ *     base (src, shards, replica, host_feat) must be 8-byte aligned (else GGMS_ERR_INVALID, nothing launched;
+ *     hipMalloc, pinned and IPC bases always are), and a chunk is 8, 4, 2 or 1 codes by the same 16-byte rule;
  *   - widening (F16, BF16 -> F32) is exact, subnormals included; narrowing (F32 -> F16, BF16) rounds to nearest
  *     even, overflows to +-inf and produces subnormals; F16 <-> BF16 goes through f32; NaN stays NaN (payload
  *     unspecified);

@@ -53,6 +53,10 @@ size_t samgraph_steps_per_epoch(void);
 size_t samgraph_num_local_step(void);
 size_t samgraph_num_class(void);
 size_t samgraph_feat_dim(void);
+/* an extension: bytes of one feature row -- delivered == 0: as STORED in the table, the cache, its shards and replicas
+ * (feat_dim x the table's element bytes; a Q8ROW row's codes, pad and trailer); else as DELIVERED in a batch
+ * (feat_dim x the batch dtype's element bytes: feat_out_dtype, or the table's dtype without the key) */
+size_t samgraph_feat_row_bytes(int delivered);
 uint64_t samgraph_get_next_batch(void);                 /* :366-378 */
 void samgraph_sample_once(void);                        /* :380     */
 size_t samgraph_get_graph_num_src(uint64_t key, int graph_id);

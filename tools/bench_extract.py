@@ -10,7 +10,11 @@ the comparison behind `feat_out_dtype` in one process, alternating order, table 
     python tools/bench_extract.py --fp8-ab [--dim 128 --rows N --table-rows N] [--parent-lib SO] [--alt-lib SO] [--out FILE]
 the comparison behind FP8 tables: the six FP8 -> f32 / f16 / bf16 gathers beside the plain f32 gather and the f16 -> X
 gathers (of another build of the library too: --parent-lib; --alt-lib adds the FP8 gathers of a trial build), and a
-straight copy as the session's copy ceiling."""
+straight copy as the session's copy ceiling, and
+    python tools/bench_extract.py --q8row-ab [--dim 128 --rows N --table-rows N] --parent-lib SO [--out FILE]
+the comparison behind Q8ROW (row-scaled 8-bit) tables: the three Q8ROW -> f32 / f16 / bf16 gathers beside the f16 -> X
+gathers of the parent build's library, the FP8 gathers and a straight copy; condition: a Q8ROW gather is no slower than
+the parent's f16 -> X gather of the same output beyond the 3.5 % drift of a session."""
 import argparse
 import ctypes as C
 import os, sys
@@ -26,7 +30,8 @@ ap.add_argument("--rows", type=int, default=2_960_000, help="rows per gather (be
 ap.add_argument("--table-rows", type=int, default=16_000_000)
 ap.add_argument("--ab", action="store_true")
 ap.add_argument("--fp8-ab", action="store_true")
-ap.add_argument("--parent-lib", help="--fp8-ab: a libggms_hip.so of another build, timed beside this one")
+ap.add_argument("--q8row-ab", action="store_true")
+ap.add_argument("--parent-lib", help="--fp8-ab / --q8row-ab: a libggms_hip.so of another build, timed beside this one")
 ap.add_argument("--alt-lib", help="--fp8-ab: a trial build whose FP8 gathers are timed too")
 ap.add_argument("--alt-name", default="trial build")
 ap.add_argument("--out", help="--ab / --fp8-ab: also write the report to this file")
@@ -175,11 +180,87 @@ def run_fp8_ab():
             f.write(text + "\n")
 
 
+def run_q8row_ab():
+    """Every case = one ggms_gather_scatter_convert launch on the same index; 5 rounds x 30 launches in alternating
+    order; algorithmic bytes = rows x (4 + stored row bytes + dim x output element bytes)."""
+    idx = torch.randint(0, args.table_rows, (args.rows,), device=dev, dtype=torch.int32)
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def entry(path):
+        fn = C.CDLL(path).ggms_gather_scatter_convert
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_uint32, C.c_void_p]
+        return fn
+
+    from xgnn_amd import _lib
+    this, parent = entry(_lib.LIB_PATH), entry(args.parent_lib) if args.parent_lib else None
+    stride = ops.row_bytes(ops.Q8ROW, args.dim)
+    q8 = torch.randint(0, 256, (args.table_rows, stride), device=dev, dtype=torch.uint8)
+    trailer = torch.empty((args.table_rows, 2), dtype=torch.float32, device=dev)
+    trailer[:, 0].uniform_(1e-3, 1e-1)   # scale
+    trailer[:, 1].uniform_(-10.0, 10.0)  # bias
+    q8[:, stride - 8:] = trailer.view(torch.uint8)
+    q8[:, args.dim:stride - 8] = 0
+    tables = {"f16": (make_table("f16"), 2, 2 * args.dim), "f8e4m3": (make_table("f8e4m3"), 16, args.dim),
+              "f8e5m2": (make_table("f8e5m2"), 17, args.dim), "q8row": (q8, ops.Q8ROW, stride)}
+    outs = {k: torch.empty((args.rows, args.dim), dtype=DT[k], device=dev) for k in ("f32", "f16", "bf16")}
+    cases = []
+
+    def add(name, fn, td, od):
+        (t, code, row), o = tables[td], outs[od]
+
+        def run():
+            rc = fn(o.data_ptr(), t.data_ptr(), idx.data_ptr(), None, args.rows, None, args.dim, code,
+                    ops.DTYPE_CODE[o.dtype], 0xFFFFFFFF, stream)
+            assert rc == 0, (name, rc)
+        cases.append((name, run, args.rows * (4 + row + args.dim * o.element_size())))
+
+    for od in ("f32", "f16", "bf16"):  # the three sets alternate: parent's f16 -> X, FP8 -> X, Q8ROW -> X
+        if parent:
+            add(f"parent build: f16 -> {od}", parent, "f16", od)
+        add(f"this build: f16 -> {od}", this, "f16", od)
+        for td in ("f8e4m3", "f8e5m2", "q8row"):
+            add(f"this build: {td} -> {od}", this, td, od)
+    src_copy = torch.empty_like(outs["f32"])
+    cases.append(("straight copy (torch copy_), f32 output size", lambda: outs["f32"].copy_(src_copy),
+                  2 * outs["f32"].numel() * 4))
+    times = {name: [] for name, _, _ in cases}
+    for rnd in range(5):
+        for name, fn, _ in (cases if rnd % 2 == 0 else cases[::-1]):
+            times[name].append(timeit(fn, reps=30))
+    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    ceiling = cases[-1][2] / med[cases[-1][0]]
+    lines = [f"Q8ROW table A/B: {args.rows} rows x dim {args.dim} (stored row {stride} B), tables of {args.table_rows} rows "
+             f"in HBM, one process, 5 rounds x 30 launches per case in alternating order, median of the rounds (min .. "
+             f"max; spread = (max - min) / median)",
+             f"device: {torch.cuda.get_device_name(0)}; copy ceiling of this session: {ceiling / 1e12:.3f} TB/s"]
+    for name, _, by in cases:
+        v = times[name]
+        lines.append(f"{name:46s} {med[name] * 1e3:7.4f} ms  ({min(v) * 1e3:.4f} .. {max(v) * 1e3:.4f}; spread "
+                     f"{(max(v) - min(v)) / med[name] * 100:4.1f} %)  {by / med[name] / 1e12:5.2f} TB/s algorithmic = "
+                     f"{by / med[name] / ceiling:.3f} of the copy ceiling")
+    ref = "parent build" if parent else "this build"
+    for od in ("f32", "f16", "bf16"):
+        a, b = med[f"this build: q8row -> {od}"], med[f"{ref}: f16 -> {od}"]
+        lines.append(f"q8row -> {od} / {ref}'s f16 -> {od} = {a / b:.3f}  (bytes: "
+                     f"{(4 + stride + args.dim * outs[od].element_size()) / (4 + args.dim * (2 + outs[od].element_size())):.3f}; "
+                     f"condition <= 1.035: {'PASS' if a <= 1.035 * b else 'OPEN'})")
+    text = "\n".join(lines)
+    print(text, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
 if args.ab:
     run_ab()
     sys.exit(0)
 if args.fp8_ab:
     run_fp8_ab()
+    sys.exit(0)
+if args.q8row_ab:
+    run_q8row_ab()
     sys.exit(0)
 if args.table_dtype or args.out_dtype:
     td, od = args.table_dtype or args.out_dtype, args.out_dtype or args.table_dtype

@@ -85,6 +85,7 @@ SYMBOLS = {
     "ggms_debug_set_knob": (None, [_i, C.c_longlong]),
     "ggms_fabric_probe": (_i, [_i, _vp, _sz, _sz, _u32, _vp, _vp]),
     "ggms_dtype_bytes": (_sz, [_i]),
+    "ggms_row_bytes": (_sz, [_i, _sz]),
     "ggms_random_states_init": (_i, [_vp, _sz, _u64, _vp]),
     "ggms_random_states_count": (_sz, [_i, C.POINTER(_sz), _sz, _sz, _sz]),
     "ggms_sample_workspace_bytes": (_sz, [_i, _sz, _sz]),

@@ -89,7 +89,8 @@ SAMGRAPH_SYMBOLS = {
     "samgraph_um_sample_init": (None, [_i]), "samgraph_switch_init": (None, [_i, C.c_char_p, C.c_double]),
     "samgraph_wait_one_child": (_i, []), "samgraph_forward_barrier": (None, []),
     "samgraph_num_epoch": (_sz, []), "samgraph_steps_per_epoch": (_sz, []), "samgraph_num_local_step": (_sz, []),
-    "samgraph_num_class": (_sz, []), "samgraph_feat_dim": (_sz, []), "samgraph_get_next_batch": (_u64, []),
+    "samgraph_num_class": (_sz, []), "samgraph_feat_dim": (_sz, []),
+    "samgraph_feat_row_bytes": (_sz, [_i]), "samgraph_get_next_batch": (_u64, []),
     "samgraph_sample_once": (None, []),
     "samgraph_get_graph_num_src": (_sz, [_u64, _i]), "samgraph_get_graph_num_dst": (_sz, [_u64, _i]),
     "samgraph_get_graph_num_edge": (_sz, [_u64, _i]),
@@ -152,6 +153,10 @@ class SamGraphBasics(object):
     def shutdown(self): return self.C_LIB_CTYPES.samgraph_shutdown()
     def num_class(self): return self.C_LIB_CTYPES.samgraph_num_class()
     def feat_dim(self): return self.C_LIB_CTYPES.samgraph_feat_dim()
+
+    def feat_row_bytes(self, delivered=False):
+        """Bytes of one feature row as stored in the table (a Q8ROW row: codes, pad, trailer) or as delivered in a batch."""
+        return self.C_LIB_CTYPES.samgraph_feat_row_bytes(1 if delivered else 0)
     def num_epoch(self): return self.C_LIB_CTYPES.samgraph_num_epoch()
     def steps_per_epoch(self): return self.C_LIB_CTYPES.samgraph_steps_per_epoch()
     def get_next_batch(self): return self.C_LIB_CTYPES.samgraph_get_next_batch()

@@ -146,8 +146,13 @@ size_t ggms_dtype_bytes(int dtype) {
     case GGMS_BF16: return 2;
     case GGMS_F8E4M3: return 1;
     case GGMS_F8E5M2: return 1;
-    default: return 0;
+    default: return 0; // GGMS_Q8ROW too: a row of codes with a trailer has no element size (ggms_row_bytes)
   }
+}
+
+size_t ggms_row_bytes(int dtype, size_t dim) {
+  if (dtype == GGMS_Q8ROW) return ((dim + 7) & ~(size_t)7) + 8; // codes, zero pad to a multiple of 8, f32 scale, f32 bias
+  return dim * ggms_dtype_bytes(dtype);
 }
 
 int ggms_random_states_init(void *states, size_t num_states, uint64_t seed, ggms_stream_t stream) {

@@ -226,7 +226,7 @@ void Engine::CpuInit() { // CPUEngine::Init, cpu_engine.cc:50-110
     SAM_HIP(hipSetDevice(device_));
     SAM_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
   }
-  const size_t row_bytes = ds.feat_dim * ggms_dtype_bytes(ds.feat_dtype);
+  const size_t row_bytes = ds.feat_row_bytes();
   size_t nslots = 2;
   if (cfg.raw.count("max_copying_jobs")) nslots = std::max<size_t>(2, std::min<size_t>(4, std::stoull(cfg.raw["max_copying_jobs"]) + 1));
   nslots = std::max(nslots, 2 + cfg.lookahead);
@@ -338,7 +338,7 @@ bool Engine::CpuEnqueueOne(bool background) {
 
   // ---- DoFeatureExtract (:194-228) + DoGraphCopy / DoFeatureCopy (:230-299)
   const auto t_copy = std::chrono::steady_clock::now();
-  const size_t row_bytes = ds.feat_dim * ggms_dtype_bytes(ds.feat_dtype);
+  const size_t row_bytes = ds.feat_row_bytes();
   void *feat = gpu ? (void *)S->feat.data() : b->feat;
   int64_t *label = gpu ? S->label.data() : b->label;
   Extract(C.team, feat, ds.feat.ptr, input_nodes, b->num_input, row_bytes, ds.feat_mask);

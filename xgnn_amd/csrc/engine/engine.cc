@@ -309,14 +309,20 @@ void Engine::LoadDataset() {
       static const std::map<std::string, int> names = {{"F32", GGMS_F32}, {"F64", GGMS_F64}, {"F16", GGMS_F16},
                                                        {"U8", GGMS_U8},   {"I32", GGMS_I32}, {"I8", GGMS_I8},
                                                        {"I64", GGMS_I64}, {"BF16", GGMS_BF16},
-                                                       {"F8E4M3", GGMS_F8E4M3}, {"F8E5M2", GGMS_F8E5M2}};
+                                                       {"F8E4M3", GGMS_F8E4M3}, {"F8E5M2", GGMS_F8E5M2},
+                                                       {"Q8ROW", GGMS_Q8ROW}};
       SAM_CHECK(names.count(v), "unknown FEAT_DATA_TYPE " + v);
       ds.feat_dtype = names.at(v);
       // (an FP8 table is a source of the converting gather only: without the key its rows are moved as bytes)
       if (cfg.feat_out_dtype >= 0 && ds.feat_dtype != GGMS_F32 && ds.feat_dtype != GGMS_F16 && ds.feat_dtype != GGMS_BF16 &&
-          ds.feat_dtype != GGMS_F8E4M3 && ds.feat_dtype != GGMS_F8E5M2)
+          ds.feat_dtype != GGMS_F8E4M3 && ds.feat_dtype != GGMS_F8E5M2 && ds.feat_dtype != GGMS_Q8ROW)
         fatal(__FILE__, __LINE__, "feat_out_dtype with FEAT_DATA_TYPE " + v + ": the gather converts F16, BF16, F32, "
-                                  "F8E4M3 and F8E5M2 tables only");
+                                  "F8E4M3, F8E5M2 and Q8ROW tables only");
+      // a row-scaled table has no element type to hand out raw: only the converting gather can deliver its rows
+      if (ds.feat_dtype == GGMS_Q8ROW && cfg.feat_out_dtype < 0)
+        fatal(__FILE__, __LINE__, "FEAT_DATA_TYPE Q8ROW needs the config key feat_out_dtype (f32 | f16 | bf16): a row of "
+                                  "8-bit codes with its scale and bias is decoded by the feature gather, there is no "
+                                  "element type to deliver it in as it is");
     } else {
       meta[k] = std::stoull(v);
     }
@@ -334,7 +340,7 @@ void Engine::LoadDataset() {
   size_t fake_dim = 0;
   if (const char *e = getenv("SAMGRAPH_FAKE_FEAT_DIM")) fake_dim = std::strtoull(e, nullptr, 10);
   if (fake_dim) ds.feat_dim = fake_dim;
-  const size_t row_bytes = ds.feat_dim * ggms_dtype_bytes(ds.feat_dtype);
+  const size_t row_bytes = ds.feat_row_bytes();
   ds.feat_rows = ds.num_node;
   size_t empty_bits = 0; // SAMGRAPH_EMPTY_FEAT = k (run_config.cc:137-139, engine.cc:205-207): a 2^k-row stand-in table,
                          // node v reads row v & (2^k - 1) (gpu_mock_extract / cpu_mock_extract)
@@ -1004,7 +1010,7 @@ void Engine::Presample() {
 }
 
 void Engine::BuildCache() {
-  const size_t row_bytes = ds.feat_dim * ggms_dtype_bytes(ds.feat_dtype);
+  const size_t row_bytes = ds.feat_row_bytes();
   const char *feat = (const char *)ds.feat.ptr;
   // the cache and the label table live on the trainer GPU: uploaded through a stream of that device (arch3: the
   // extract stream; the other deployments have one device, and the sampling stream as before)
@@ -1167,7 +1173,7 @@ void Engine::TrainInit(int worker_id, const std::string &ctx) {
   }
   // batch slots (GraphPool(max_copying_jobs), cuda_engine.cc:151): buffers sized once at their bounds
   const uint32_t L = (uint32_t)cfg.fanout.size();
-  const size_t row_bytes = ds.feat_dim * ggms_dtype_bytes(ds.feat_dtype);
+  const size_t row_bytes = ds.feat_row_bytes();
   size_t nslots = 2;
   if (cfg.raw.count("max_copying_jobs")) nslots = std::max<size_t>(2, std::min<size_t>(4, std::stoull(cfg.raw["max_copying_jobs"]) + 1));
   nslots = std::max(nslots, 2 + cfg.lookahead); // the trainer's batch + the one asked for + the ones enqueued ahead
@@ -1182,7 +1188,7 @@ void Engine::TrainInit(int worker_id, const std::string &ctx) {
     auto b = std::make_unique<Batch>();
     b->slot = (int)s;
     b->trainer.Alloc(max_edges_, max_unique_, max_seeds_, cfg.sample_type == GGMS_RANDOM_WALK);
-    SAM_HIP(hipMalloc(&b->feat, max_unique_ * ds.feat_dim * ggms_dtype_bytes(batch_feat_dtype()))); // rows as delivered
+    SAM_HIP(hipMalloc(&b->feat, max_unique_ * batch_feat_row_bytes())); // rows as delivered
     SAM_HIP(hipMalloc((void **)&b->label, max_seeds_ * 8));
     if (StagedHostTier()) { // index arrays of GetMissCacheIndex + pinned / device staging of the miss rows
       if (cache_table_) { // (no cache: no split, and the rows land in the batch's feature buffer directly)
@@ -1570,8 +1576,8 @@ void Engine::Finish(Batch *b, Batch *prev) {
   for (uint32_t i = 0; i < L; ++i) edges += b->counts[3 * i];
   // feature bytes: what the gather wrote to the batch (rows in the delivered dtype); miss bytes: what it read from the
   // host tier (rows in the table's dtype)
-  const double out_row_bytes = (double)ds.feat_dim * ggms_dtype_bytes(batch_feat_dtype());
-  const double row_bytes = (double)ds.feat_dim * ggms_dtype_bytes(ds.feat_dtype);
+  const double out_row_bytes = (double)batch_feat_row_bytes();
+  const double row_bytes = (double)ds.feat_row_bytes();
   // item codes: profiler.h:58-140 (kLogL1NumSample = 0, kLogL1NumNode = 1, kLogL1SampleTime = 3,
   // kLogL1CopyTime = 6, kLogL1FeatureBytes = 9, kLogL1MissBytes = 13; epoch items :119-137)
   prof.LogStep(b->key, 0, (double)edges);

@@ -115,6 +115,9 @@ struct Dataset {
   // SAMGRAPH_EMPTY_FEAT = k (engine.cc:198-235): the feature table is a 2^k-row stand-in, row of node v = v & mask
   uint32_t feat_mask = 0xffffffffu;
   size_t feat_rows = 0; // rows of ds.feat (num_node, or 2^k)
+  // bytes from one STORED row of the table to the next: what sizes and strides the table, the cache, its shards and
+  // replicas and the staging buffers (feat_dim x element bytes; a Q8ROW row is its codes, pad and scale / bias trailer)
+  size_t feat_row_bytes() const { return ggms_row_bytes(feat_dtype, feat_dim); }
 };
 
 // ---- Profiler log store: profiler.h:166-215 ------------------------------------
@@ -232,6 +235,8 @@ class Engine {
   bool BatchSampledElsewhere() const { return Dedicated() || cfg.arch == kArch5; }
   // dtype of a batch's feature buffer: the configured feat_out_dtype, else the table's
   int batch_feat_dtype() const { return cfg.feat_out_dtype < 0 ? ds.feat_dtype : cfg.feat_out_dtype; }
+  // bytes of one row of a batch's feature buffer: always dim x batch dtype, whatever the table stores per row
+  size_t batch_feat_row_bytes() const { return ds.feat_dim * ggms_dtype_bytes(batch_feat_dtype()); }
   int batch_device_type() const { return (cfg.arch == kArch0 && cfg.trainer_on_host) ? 0 : 2; } // DeviceType, common.h:48
   void Barrier(const char *what = "step");
   void *OpenPeer(const hipIpcMemHandle_t &handle, uint32_t peer, size_t bytes, const char *what);

@@ -51,6 +51,10 @@ size_t samgraph_steps_per_epoch(void) { return Engine::Get().NumStep(); }
 size_t samgraph_num_local_step(void) { return Engine::Get().NumLocalStep(); }
 size_t samgraph_num_class(void) { return Engine::Get().ds.num_class; }
 size_t samgraph_feat_dim(void) { return Engine::Get().ds.feat_dim; }
+size_t samgraph_feat_row_bytes(int delivered) {
+  auto &E = Engine::Get();
+  return delivered ? E.batch_feat_row_bytes() : E.ds.feat_row_bytes();
+}
 uint64_t samgraph_get_next_batch(void) { return Engine::Get().GetNextBatch(); }
 void samgraph_sample_once(void) { Engine::Get().RunSampleOnce(); }
 
@@ -110,6 +114,10 @@ void samgraph_get_graph_data(uint64_t key, int l, samgraph_tensor_t *out) {
 }
 void samgraph_get_dataset_feat(samgraph_tensor_t *out) {
   auto &E = Engine::Get();
+  if (E.ds.feat_dtype == GGMS_Q8ROW) { // no element type: the stored rows as bytes, (rows, stride) of U8
+    fill(out, E.ds.feat.ptr, (int64_t)E.ds.feat_rows, (int64_t)E.ds.feat_row_bytes(), 2, GGMS_U8, 0, 0);
+    return;
+  }
   fill(out, E.ds.feat.ptr, (int64_t)E.ds.feat_rows, (int64_t)E.ds.feat_dim, 2, E.ds.feat_dtype, 0, 0);
 }
 void samgraph_get_dataset_label(samgraph_tensor_t *out) {

@@ -49,7 +49,7 @@ static inline void store_fence() { // streaming stores are weakly ordered: drain
 
 void Engine::HostGatherRows(char *rows, const uint32_t *ids, size_t first, size_t count) {
   const char *feat = (const char *)ds.feat.ptr;
-  const size_t row_bytes = ds.feat_dim * ggms_dtype_bytes(ds.feat_dtype);
+  const size_t row_bytes = ds.feat_row_bytes();
   const uint32_t mask = ds.feat_mask;
   host_team_->ParallelFor(count, [&](size_t lo, size_t hi, int) { // ExtractMissData, cuda_cache_manager_host.cc:268-300
     constexpr size_t kAhead = 8; // rows: a random 512-byte row is 8 cache lines nobody has asked for yet
@@ -66,7 +66,7 @@ void Engine::HostGatherRows(char *rows, const uint32_t *ids, size_t first, size_
 
 void Engine::StagedExtract(Batch *b, hipStream_t ss, hipStream_t xs) {
   const uint32_t L = (uint32_t)cfg.fanout.size();
-  const size_t row_bytes = ds.feat_dim * ggms_dtype_bytes(ds.feat_dtype);
+  const size_t row_bytes = ds.feat_row_bytes();
   if (!host_team_) {
     host_team_ = std::make_unique<Team>((int)std::max<size_t>(1, cfg.omp_thread_num));
     log_info("staged extract: host team of " + std::to_string(host_team_->size()) + " threads (omp_thread_num)");

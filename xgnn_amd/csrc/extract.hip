@@ -43,6 +43,7 @@ template <> struct ChunkT<1> { using type = uint8_t; };
 // out, converted at store time -- the registers a lane holds between its loads and its first store are the SOURCE
 // chunks only, whichever side is the wider one.
 template <int CB> struct CopyChunk {
+  static constexpr bool kScaled = false; // (ScaledChunk below)
   static constexpr int kSrcBytes = CB, kDstBytes = CB;
   using Src = typename ChunkT<CB>::type;
   using Dst = Src;
@@ -85,6 +86,7 @@ template <typename T> struct VecT<T, 1> { using type = T; };
 template <int EPC, int SRC_DT, int DST_DT> struct ConvertChunk {
   using S = Elem<SRC_DT>;
   using D = Elem<DST_DT>;
+  static constexpr bool kScaled = false;
   static constexpr int kSrcBytes = EPC * (int)sizeof(typename S::bits), kDstBytes = EPC * (int)sizeof(typename D::bits);
   using Src = typename VecT<typename S::bits, EPC>::type;
   using Dst = typename VecT<typename D::bits, EPC>::type;
@@ -105,6 +107,40 @@ template <int EPC, int SRC_DT, int DST_DT> struct ConvertChunk {
     }
   }
 };
+
+// A row-scaled 8-bit table (GGMS_Q8ROW, include/ggms.h): a row is `dim` unsigned codes, zero bytes up to the next
+// multiple of 8, then the row's f32 scale and f32 bias.  The chunk is EPC code bytes; its value needs the two numbers
+// that belong to the ROW, so convert takes them beside the chunk's bits: the sweep loads a row's 8-byte trailer with
+// the row's pointer (the lane that resolves the row keeps both) and hands scale and bias to the chunk's lane the way
+// it hands out the pointer.  value = fl32(fl32(float(code) * scale) + bias), two IEEE operations: NOT an FMA, whose
+// single rounding gives other bits (hipcc contracts a * b + c by default, through __fmul_rn / __fadd_rn too, which
+// are plain operators in its headers; the pragma takes the licence away for these two operations).
+template <int EPC, int DST_DT> struct ScaledChunk {
+  using D = Elem<DST_DT>;
+  static constexpr bool kScaled = true;
+  static constexpr int kSrcBytes = EPC, kDstBytes = EPC * (int)sizeof(typename D::bits);
+  using Src = typename VecT<uint8_t, EPC>::type;
+  using Dst = typename VecT<typename D::bits, EPC>::type;
+  static __device__ __forceinline__ typename D::bits one(uint8_t code, float scale, float bias) {
+#pragma clang fp contract(off)
+    const float scaled = (float)code * scale;
+    const float value = scaled + bias;
+    return D::from_f32(value);
+  }
+  static __device__ __forceinline__ Dst convert(Src v, uint32_t scale_bits, uint32_t bias_bits) {
+    const float scale = __builtin_bit_cast(float, scale_bits), bias = __builtin_bit_cast(float, bias_bits);
+    if constexpr (EPC == 1) {
+      return one(v, scale, bias);
+    } else {
+      Dst o;
+#pragma unroll
+      for (int e = 0; e < EPC; ++e) o[e] = one(v[e], scale, bias);
+      return o;
+    }
+  }
+};
+// where a Q8ROW row of `code_bytes` codes keeps its trailer, and the stride of such rows
+__host__ __device__ constexpr uint64_t q8row_trailer_offset(uint64_t code_bytes) { return (code_bytes + 7u) & ~(uint64_t)7u; }
 
 // which tier served a row (0 = not counted); counters[tier - 1] in ggms_extract_tiered
 constexpr uint32_t kTierHost = 1, kTierRemote = 2, kTierLocal = 3, kTierReplica = 4;
@@ -301,17 +337,22 @@ __global__ __launch_bounds__(kBlock) void k_gather_rows(char *__restrict__ out, 
   const uint64_t row_bytes = (uint64_t)rc * DB; // of an OUTPUT row (the locator knows the source's)
   const uint64_t num_tiles = (n + kWave - 1) / kWave;
 
-  // resolve one row per lane for tile `t`: source pointer (+ destination pointer)
-  auto resolve = [&](uint64_t t, uint64_t &sp, uint64_t &dp, uint32_t &miss) {
+  // resolve one row per lane for tile `t`: source pointer (+ destination pointer; + the row's scale and bias, the
+  // 8-byte trailer behind a Q8ROW row's codes)
+  [[maybe_unused]] const uint64_t trailer = q8row_trailer_offset((uint64_t)rc * SB);
+  auto resolve = [&](uint64_t t, uint64_t &sp, uint64_t &dp, uint32_t &miss, [[maybe_unused]] u32x2_t &sb) {
     const uint64_t my_row = t * kWave + lane;
     sp = 0; dp = 0; miss = 0;
+    if constexpr (Chunk::kScaled) sb = u32x2_t{0u, 0u};
     if (t < num_tiles && my_row < n) {
       sp = (uint64_t)rows.row(my_row, miss);
+      if constexpr (Chunk::kScaled) sb = load_chunk<u32x2_t, true>(sp + trailer);
       if constexpr (!IDENT_DST) dp = (uint64_t)(out + (uint64_t)dst_index[my_row] * row_bytes);
     }
   };
 
   uint64_t sp, dp;
+  [[maybe_unused]] u32x2_t sb; // {scale, bias} of my row, as bits (ScaledChunk only)
   uint32_t miss; // tier of my row (kTierHost = a cache miss)
   // rows per tier: counted per wave in registers, combined per workgroup in LDS and added to the caller's counters
   // ONCE per workgroup at the end.  (An atomic per wave and tile -- 46 K tiles x 3 tiers on one line -- is served one
@@ -319,13 +360,14 @@ __global__ __launch_bounds__(kBlock) void k_gather_rows(char *__restrict__ out, 
   uint32_t tier_acc[kTierReplica + 1] = {};
   __shared__ unsigned int s_tier[kTierReplica + 1];
   if (miss_count && threadIdx.x <= kTierReplica) s_tier[threadIdx.x] = 0u;
-  resolve(wave, sp, dp, miss);
+  resolve(wave, sp, dp, miss, sb);
   for (uint64_t tile = wave; tile < num_tiles; tile += num_waves) {
     // software pipeline: the next tile's index -> table -> pointer chain is in flight while this
     // tile's rows stream
     uint64_t sp_n, dp_n;
+    [[maybe_unused]] u32x2_t sb_n;
     uint32_t miss_n;
-    resolve(tile + num_waves, sp_n, dp_n, miss_n);
+    resolve(tile + num_waves, sp_n, dp_n, miss_n, sb_n);
 
     if (miss_count) {
       tier_acc[0] += (uint32_t)__popcll(__ballot(miss == kTierHost));
@@ -361,10 +403,19 @@ __global__ __launch_bounds__(kBlock) void k_gather_rows(char *__restrict__ out, 
           const uint32_t r = __umulhi(cc[u], magic) + (rc == 1 ? cc[u] : 0u);
           q = shfl_u64(dp, (int)r) + (uint64_t)(cc[u] - r * rc) * DB;
         }
-        if (c < total) store_chunk<DV, true>(q, Chunk::convert(tmp[u]));
+        if constexpr (Chunk::kScaled) {
+          // the chunk's row once more (the load loop's `r` is not kept: one multiply-high per chunk instead of U
+          // registers held across the loads), for the owner lane's scale and bias
+          const uint32_t r = __umulhi(cc[u], magic) + (rc == 1 ? cc[u] : 0u);
+          const uint32_t scale = __shfl(sb.x, (int)r, 64), bias = __shfl(sb.y, (int)r, 64);
+          if (c < total) store_chunk<DV, true>(q, Chunk::convert(tmp[u], scale, bias));
+        } else {
+          if (c < total) store_chunk<DV, true>(q, Chunk::convert(tmp[u]));
+        }
       }
     }
     sp = sp_n; dp = dp_n; miss = miss_n;
+    if constexpr (Chunk::kScaled) sb = sb_n;
   }
   if (miss_count) { // uniform: every wave of the workgroup gets here
     __syncthreads(); // s_tier is zeroed
@@ -397,8 +448,14 @@ __global__ __launch_bounds__(kBlock) void k_gather_long_rows(char *__restrict__ 
       if (tier == kTierHost) atomicAdd((unsigned long long *)miss_count, 1ull);
       else if (Rows::kTiers && tier >= kTierRemote) atomicAdd((unsigned long long *)miss_count + (tier - 1), 1ull);
     }
-    for (uint64_t c = threadIdx.x; c < rc; c += kBlock)
-      store_chunk<DV, true>(dp + c * DB, Chunk::convert(load_chunk<SV, true>(sp + c * SB)));
+    if constexpr (Chunk::kScaled) { // the row's scale and bias: one load, the same for every lane
+      const u32x2_t sb = load_chunk<u32x2_t, true>(sp + q8row_trailer_offset(rc * SB));
+      for (uint64_t c = threadIdx.x; c < rc; c += kBlock)
+        store_chunk<DV, true>(dp + c * DB, Chunk::convert(load_chunk<SV, true>(sp + c * SB), sb.x, sb.y));
+    } else {
+      for (uint64_t c = threadIdx.x; c < rc; c += kBlock)
+        store_chunk<DV, true>(dp + c * DB, Chunk::convert(load_chunk<SV, true>(sp + c * SB)));
+    }
   }
 }
 
@@ -520,17 +577,32 @@ static int launch_gather(char *out, Rows rows, const uint32_t *dst_index, size_t
 // ---- how a call's rows are moved -------------------------------------------------------------------------------------
 // src_dt == dst_dt (any dtype): as bytes, the plain gather.  Otherwise the output is one of F16 / BF16 / F32, the source
 // one of those or an FP8 type (decoded, never produced), and the gather converts (ConvertChunk): the same locators,
-// sweep and launch path, chunks of `epc` elements.
+// sweep and launch path, chunks of `epc` elements.  A Q8ROW source (row-scaled codes, a source only and never moved
+// "plain": it has no element size) goes the same way with ScaledChunk; its element is the one-byte code and its rows
+// lie ggms_row_bytes apart.
 struct RowMove {
   int src_dt, dst_dt;
-  size_t dim, src_es, dst_es;
+  size_t dim, src_es, dst_es, src_stride;
   bool converts() const { return src_dt != dst_dt; }
-  size_t src_row_bytes() const { return dim * src_es; }
+  size_t src_row_bytes() const { return src_stride; } // the distance between two stored rows
 };
 static inline bool is_float_dtype(int dt) { return dt == GGMS_F16 || dt == GGMS_BF16 || dt == GGMS_F32; }
 static inline bool is_fp8_dtype(int dt) { return dt == GGMS_F8E4M3 || dt == GGMS_F8E5M2; }
 static bool row_move(int src_dt, int dst_dt, size_t dim, RowMove &m) {
-  m = RowMove{src_dt, dst_dt, dim, ggms_dtype_bytes(src_dt), ggms_dtype_bytes(dst_dt)};
+  if (src_dt == GGMS_Q8ROW || dst_dt == GGMS_Q8ROW) {
+    if (src_dt != GGMS_Q8ROW || !is_float_dtype(dst_dt)) {
+      set_error("extract: invalid argument: no conversion from dtype %d to dtype %d (Q8ROW is the source of a "
+                "converting gather into F16, BF16 or F32, nothing else)", src_dt, dst_dt);
+      return false;
+    }
+    m = RowMove{src_dt, dst_dt, dim, 1, ggms_dtype_bytes(dst_dt), ggms_row_bytes(src_dt, dim)};
+    if (dim == 0) {
+      set_error("extract: invalid argument: dtype %d -> %d, dim %zu (unknown dtype or empty rows)", src_dt, dst_dt, dim);
+      return false;
+    }
+    return true;
+  }
+  m = RowMove{src_dt, dst_dt, dim, ggms_dtype_bytes(src_dt), ggms_dtype_bytes(dst_dt), ggms_row_bytes(src_dt, dim)};
   if (m.src_es == 0 || m.dst_es == 0 || dim == 0) {
     set_error("extract: invalid argument: dtype %d -> %d, dim %zu (unknown dtype or empty rows)", src_dt, dst_dt, dim);
     return false;
@@ -566,6 +638,23 @@ static int launch_convert_pair(char *out, Rows rows, const uint32_t *dst_index, 
   return GGMS_ERR_INVALID;
 }
 
+// Q8ROW -> DST_DT: ScaledChunk in the widest chunk the rule above allows (a one-byte source element)
+template <int DST_DT, bool SCATTER, typename Rows>
+static int launch_scaled(char *out, Rows rows, const uint32_t *dst_index, size_t n_max, Count n, size_t dim, int epc,
+                         uint64_t *miss_count, hipStream_t stream) {
+  const uint64_t rc = dim / epc;
+  if constexpr (convert_max_epc(1, sizeof(typename Elem<DST_DT>::bits)) == 8)
+    if (epc == 8)
+      return launch_chunks<ScaledChunk<8, DST_DT>, Rows, SCATTER>(out, rows, dst_index, n_max, n, rc, miss_count, stream);
+  switch (epc) {
+    case 4: return launch_chunks<ScaledChunk<4, DST_DT>, Rows, SCATTER>(out, rows, dst_index, n_max, n, rc, miss_count, stream);
+    case 2: return launch_chunks<ScaledChunk<2, DST_DT>, Rows, SCATTER>(out, rows, dst_index, n_max, n, rc, miss_count, stream);
+    case 1: return launch_chunks<ScaledChunk<1, DST_DT>, Rows, SCATTER>(out, rows, dst_index, n_max, n, rc, miss_count, stream);
+  }
+  set_error("extract: no %d-element chunk for dtype %d -> %d", epc, GGMS_Q8ROW, DST_DT);
+  return GGMS_ERR_INVALID;
+}
+
 // src_bits: every source base pointer the locator may use, ORed (shard bases come from hipMalloc /
 // hipIpcOpenMemHandle / hipHostMalloc, >= 256-B aligned, and may be left out)
 template <bool SCATTER = true, typename Rows>
@@ -575,6 +664,20 @@ static int launch_move(char *out, Rows rows, const uint32_t *dst_index, size_t n
     return launch_gather(out, rows, dst_index, n_max, n, m.src_row_bytes(),
                          pick_chunk(m.src_row_bytes(), (uintptr_t)out | src_bits), miss_count, stream);
   const int epc = pick_chunk(m.dim, convert_max_epc(m.src_es, m.dst_es), m.src_es, src_bits, m.dst_es, (uintptr_t)out);
+  if (m.src_dt == GGMS_Q8ROW) {
+    // rows lie a multiple of 8 bytes apart, so an 8-byte aligned base puts every row's trailer where one 8-byte load
+    // reads it (the callers of a Q8ROW gather put their shard bases into src_bits too)
+    if (src_bits % 8 != 0) {
+      set_error("extract: invalid argument: a Q8ROW source base is not 8-byte aligned (every row ends in an 8-byte "
+                "scale / bias trailer, read by one load)");
+      return GGMS_ERR_INVALID;
+    }
+    switch (m.dst_dt) {
+      case GGMS_F32: return launch_scaled<GGMS_F32, SCATTER>(out, rows, dst_index, n_max, n, m.dim, epc, miss_count, stream);
+      case GGMS_F16: return launch_scaled<GGMS_F16, SCATTER>(out, rows, dst_index, n_max, n, m.dim, epc, miss_count, stream);
+      case GGMS_BF16: return launch_scaled<GGMS_BF16, SCATTER>(out, rows, dst_index, n_max, n, m.dim, epc, miss_count, stream);
+    }
+  }
 #define GGMS_PAIR(S, D)                                                                                              \
   if (m.src_dt == S && m.dst_dt == D)                                                                                \
     return launch_convert_pair<S, D, SCATTER>(out, rows, dst_index, n_max, n, m.dim, epc, miss_count, stream);
@@ -598,6 +701,15 @@ static int launch_move(char *out, Rows rows, const uint32_t *dst_index, size_t n
 } // namespace ggms
 
 using namespace ggms;
+
+// The shard bases of a Q8ROW gather, ORed (launch_move checks their alignment; every other gather leaves them out:
+// shard bases come from hipMalloc / hipIpcOpenMemHandle / hipHostMalloc, and its chunk choice is unchanged by this)
+static inline uintptr_t part_align_bits(const PartPtrs &pp, uint32_t num_part, const RowMove &m) {
+  uintptr_t bits = 0;
+  if (m.src_dt == GGMS_Q8ROW)
+    for (uint32_t p = 0; p < (num_part ? num_part : 1); ++p) bits |= (uintptr_t)pp.p[p];
+  return bits;
+}
 
 // The bodies behind the entry points that exist in a plain and a converting form (ggms_*_convert): one dtype is the
 // plain call, two are the converting one.
@@ -624,15 +736,16 @@ static int extract_cached_rows(void *out, const ggms_id_t *nodes, size_t num_nod
   PartPtrs pp;
   if (!part_ptrs(parts, num_part, pp)) return GGMS_ERR_INVALID;
   const Divisor div = divisor_of(num_part ? num_part : 1);
+  const uintptr_t part_bits = part_align_bits(pp, num_part, m);
   if (!table) { // full cache in node order: slot = node id
     IdentRows rows{pp, nodes, m.src_row_bytes(), div};
     if (num_miss_dev) GGMS_HIP(hipMemsetAsync(num_miss_dev, 0, sizeof(uint64_t), to_stream(stream)));
-    return launch_move<false>((char *)out, rows, nullptr, num_nodes, count_of(num_nodes, num_nodes_dev), m, 0, nullptr,
-                              to_stream(stream));
+    return launch_move<false>((char *)out, rows, nullptr, num_nodes, count_of(num_nodes, num_nodes_dev), m, part_bits,
+                              nullptr, to_stream(stream));
   }
   CachedRows rows{pp, nodes, table, (const char *)host_feat, m.src_row_bytes(), div};
   return launch_move<false>((char *)out, rows, nullptr, num_nodes, count_of(num_nodes, num_nodes_dev), m,
-                            (uintptr_t)host_feat, num_miss_dev, to_stream(stream));
+                            (uintptr_t)host_feat | part_bits, num_miss_dev, to_stream(stream));
 }
 
 static int extract_tiered_rows(void *out, const ggms_id_t *nodes, size_t num_nodes, const uint64_t *num_nodes_dev,
@@ -651,7 +764,8 @@ static int extract_tiered_rows(void *out, const ggms_id_t *nodes, size_t num_nod
                   (const char *)tiers->replica, m.src_row_bytes(), (uint32_t)tiers->num_replica,
                   divisor_of(tiers->num_part), tiers->my_part, tiers->host_row_mask ? tiers->host_row_mask : 0xffffffffu};
   return launch_move<false>((char *)out, rows, nullptr, num_nodes, count_of(num_nodes, num_nodes_dev), m,
-                            (uintptr_t)tiers->host_feat | (uintptr_t)tiers->replica, tier_rows_dev, to_stream(stream));
+                            (uintptr_t)tiers->host_feat | (uintptr_t)tiers->replica | part_align_bits(pp, tiers->num_part, m),
+                            tier_rows_dev, to_stream(stream));
 }
 
 extern "C" {

@@ -148,6 +148,7 @@ def write_dataset(path, graph, feat=None, label=None, valid_frac=0.02, test_frac
     samgraph/common/constant.cc:23-51, engine.cc:109-443): meta.txt (tab separated) + raw little-endian
     arrays: indptr/indices/train_set/test_set/valid_set/cache_by_* uint32, feat row-major, label int64;
     feat_dtype "F8E4M3" / "F8E5M2": feat is a torch.float8_e4m3fn / float8_e5m2 tensor, or its bytes as a uint8 array;
+    feat_dtype "Q8ROW": feat is the packed (n, q8row_stride(feat_dim)) uint8 rows of pack_q8row;
     weights (one float per edge) adds prob_table.bin / alias_table.bin / prob_prefix_table.bin.
     minimal: what a sampling + extract run needs and nothing that costs minutes at papers100M size -- one-node
     valid / test sets instead of random slices of the complement, no cache_by_random.bin."""
@@ -171,6 +172,10 @@ def write_dataset(path, graph, feat=None, label=None, valid_frac=0.02, test_frac
     if feat is not None:
         if feat_dtype in FP8_FORMATS:
             feat = _fp8_bytes(feat, feat_dtype)
+        if feat_dtype == "Q8ROW":
+            feat = np.asarray(feat)
+            assert feat.dtype == np.uint8 and feat.shape == (n, q8row_stride(meta["feat_dim"])), \
+                f"a Q8ROW table is the packed uint8 rows ({n}, {q8row_stride(meta['feat_dim'])}), not {feat.dtype} {feat.shape}"
         np.ascontiguousarray(feat).tofile(os.path.join(path, "feat.bin"))
     if label is not None:
         np.ascontiguousarray(label, dtype=np.int64).tofile(os.path.join(path, "label.bin"))
@@ -213,9 +218,60 @@ def _fp8_bytes(feat, fmt):
     return feat
 
 
+# ---- Q8ROW: row-scaled 8-bit tables (include/ggms.h: GGMS_Q8ROW = 18) ------------------------------------------------
+# A row of `dim` elements is `dim` uint8 codes, zero bytes up to the next multiple of 8, then the row's little-endian
+# float32 scale and float32 bias; element value = float32(float32(code * scale) + bias), two roundings.
+def q8row_stride(dim):
+    """Bytes from one Q8ROW row of `dim` elements to the next (ggms_row_bytes)."""
+    return (dim + 7) // 8 * 8 + 8
+
+
+def pack_q8row(codes, scale, bias):
+    """(n, dim) uint8 codes + (n,) float32 scale and bias -> the (n, q8row_stride(dim)) uint8 rows of a Q8ROW table."""
+    codes = np.asarray(codes)
+    assert codes.dtype == np.uint8 and codes.ndim == 2, (codes.dtype, codes.shape)
+    n, dim = codes.shape
+    pad = q8row_stride(dim) - 8
+    rows = np.zeros((n, pad + 8), np.uint8)
+    rows[:, :dim] = codes
+    rows[:, pad:pad + 4] = np.ascontiguousarray(scale, dtype="<f4").reshape(n, 1).view(np.uint8)
+    rows[:, pad + 4:] = np.ascontiguousarray(bias, dtype="<f4").reshape(n, 1).view(np.uint8)
+    return rows
+
+
+def unpack_q8row(rows, dim):
+    """The inverse of pack_q8row: (codes, scale, bias) of packed rows (copies; the pad bytes are not looked at)."""
+    rows = np.asarray(rows)
+    assert rows.dtype == np.uint8 and rows.ndim == 2 and rows.shape[1] == q8row_stride(dim), (rows.dtype, rows.shape, dim)
+    pad = q8row_stride(dim) - 8
+    scale = np.ascontiguousarray(rows[:, pad:pad + 4]).view("<f4").ravel().astype(np.float32)
+    bias = np.ascontiguousarray(rows[:, pad + 4:]).view("<f4").ravel().astype(np.float32)
+    return np.ascontiguousarray(rows[:, :dim]), scale, bias
+
+
+def quantize_q8row(values, first_row=0):
+    """(n, dim) finite F32 / F16 values -> (codes, scale, bias), per row and computed in float64: bias = min,
+    scale = float32((max - min) / 255), code = clip(rint((x - bias) / scale), 0, 255); a constant row (and one whose
+    range is so small that the scale rounds to 0) gets scale 0 and codes 0, and decodes to its minimum.  A row holding
+    NaN or +-inf is an error that names the row (first_row + its index)."""
+    v = np.asarray(values).astype(np.float64)
+    bad = ~np.isfinite(v).all(axis=1)
+    if bad.any():
+        raise ValueError(f"quantize_features: row {first_row + int(np.flatnonzero(bad)[0])} holds NaN or inf: a "
+                         "row-scaled table has no code for either")
+    lo, hi = v.min(axis=1), v.max(axis=1)
+    scale = ((hi - lo) / 255.0).astype(np.float32)
+    s64 = scale.astype(np.float64)[:, None]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        q = np.rint((v - lo[:, None]) / s64)
+    codes = np.where(s64 > 0, np.clip(q, 0, 255), 0).astype(np.uint8)
+    return codes, scale, lo.astype(np.float32)  # (the minimum of F32 / F16 values is an f32 number)
+
+
 def quantize_features(path_in, path_out, fmt, chunk_rows=1 << 20):
-    """Rewrite the F32 / F16 dataset at path_in as the same dataset with an FP8 feature table (fmt "F8E4M3" or
-    "F8E5M2") at path_out: every other file is linked (or copied where a link is not possible), feat.bin is cast on the
+    """Rewrite the F32 / F16 dataset at path_in as the same dataset with an 8-bit feature table at path_out: fmt
+    "Q8ROW" quantises every row to 8-bit codes with the row's own scale and bias (quantize_q8row); for an FP8 feature
+    table (fmt "F8E4M3" or "F8E5M2"): every other file is linked (or copied where a link is not possible), feat.bin is cast on the
     CPU with torch, round to nearest even, one chunk of rows at a time, and meta.txt names the new FEAT_DATA_TYPE.
     A one-off offline step; there is no kernel for it.
 
@@ -225,7 +281,7 @@ def quantize_features(path_in, path_out, fmt, chunk_rows=1 << 20):
     import os
     import shutil
     import torch
-    assert fmt in FP8_FORMATS, fmt
+    assert fmt in FP8_FORMATS or fmt == "Q8ROW", fmt
     with open(os.path.join(path_in, "meta.txt")) as f:
         meta = [line.split() for line in f if line.strip()]
     kv = dict(meta)
@@ -247,6 +303,9 @@ def quantize_features(path_in, path_out, fmt, chunk_rows=1 << 20):
     table = np.memmap(os.path.join(path_in, "feat.bin"), dtype=src_dt, mode="r", shape=(n, dim))
     with open(os.path.join(path_out, "feat.bin"), "wb") as out:
         for r in range(0, n, chunk_rows):
+            if fmt == "Q8ROW":
+                out.write(pack_q8row(*quantize_q8row(table[r:r + chunk_rows], first_row=r)).tobytes())
+                continue
             v = torch.from_numpy(np.array(table[r:r + chunk_rows])).float()
             if fmt == "F8E4M3":
                 v = v.clamp(-E4M3_MAX, E4M3_MAX)

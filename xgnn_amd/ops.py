@@ -24,6 +24,27 @@ DTYPE_CODE = {
     torch.float8_e4m3fn: 16, torch.float8_e5m2: 17,
 }
 
+# GGMS_Q8ROW (include/ggms.h): a ROW format, 8-bit codes with a float32 scale and bias per row.  No torch dtype stands
+# for it: such a table is a torch.uint8 tensor of shape (rows, row_bytes(Q8ROW, dim)) passed with src_dtype=Q8ROW.
+Q8ROW = 18
+
+
+def _dtype_code(dtype):
+    """ggms_dtype code of a torch dtype, or the code itself."""
+    return dtype if isinstance(dtype, int) else DTYPE_CODE[dtype]
+
+
+def row_bytes(dtype, dim):
+    """ggms_row_bytes: bytes from one stored row of `dim` elements to the next (dtype: a torch dtype or a code)."""
+    return lib().ggms_row_bytes(_dtype_code(dtype), dim)
+
+
+def _check_q8row(src, src_dtype, dim):
+    if _dtype_code(src_dtype) == Q8ROW and src is not None:
+        assert src.dtype == torch.uint8 and src.shape[-1] == row_bytes(Q8ROW, dim), \
+            f"a Q8ROW table of dim {dim} is a uint8 tensor of (rows, {row_bytes(Q8ROW, dim)}), not {src.dtype} {tuple(src.shape)}"
+
+
 KHOP0, KHOP1, WEIGHTED_KHOP, RANDOM_WALK, WEIGHTED_KHOP_PREFIX, KHOP2, WEIGHTED_KHOP_HASH_DEDUP, KHOP3 = range(8)
 
 
@@ -291,15 +312,18 @@ def gather_scatter(out, src, src_index, dst_index, num=None, num_dev=None):
     return out
 
 
-def gather_scatter_convert(out, src, src_index, dst_index, num=None, num_dev=None, src_row_mask=0xFFFFFFFF):
+def gather_scatter_convert(out, src, src_index, dst_index, num=None, num_dev=None, src_row_mask=0xFFFFFFFF,
+                           src_dtype=None):
     """ggms_gather_scatter_convert: out[dst(i), :] = src[src(i) & mask, :] delivered in out's dtype (src and out each
     float16, bfloat16 or float32, src also float8_e4m3fn or float8_e5m2; the same dtype on both sides is the plain
-    gather)."""
+    gather).  src_dtype=Q8ROW: src is the uint8 (rows, row_bytes(Q8ROW, dim)) tensor of a row-scaled table, dim is out's."""
     _require_gpu(out)
     if num is None:
         num = (src_index if src_index is not None else dst_index).numel()
+    src_dtype = src.dtype if src_dtype is None else src_dtype
+    _check_q8row(src, src_dtype, _dim_of(out))
     check(lib().ggms_gather_scatter_convert(_ptr(out), _ptr(src), _ptr(src_index), _ptr(dst_index), num, _ptr(num_dev),
-                                            _dim_of(out), DTYPE_CODE[src.dtype], DTYPE_CODE[out.dtype], src_row_mask,
+                                            _dim_of(out), _dtype_code(src_dtype), DTYPE_CODE[out.dtype], src_row_mask,
                                             _stream()), "ggms_gather_scatter_convert")
     return out
 
@@ -350,12 +374,14 @@ def extract_cached(out, nodes, table, parts_table, num_part, host_feat, num=None
 
 def extract_cached_convert(out, src_dtype, nodes, table, parts_table, num_part, host_feat, num=None, num_dev=None,
                            num_miss=None):
-    """extract_cached with every source (shards, host rows) in `src_dtype` and the rows delivered in out's dtype."""
+    """extract_cached with every source (shards, host rows) in `src_dtype` and the rows delivered in out's dtype
+    (src_dtype=Q8ROW: every source is uint8 rows of row_bytes(Q8ROW, dim) bytes)."""
     _require_gpu(out)
     if num is None:
         num = nodes.numel()
+    _check_q8row(host_feat, src_dtype, _dim_of(out))
     check(lib().ggms_extract_cached_convert(_ptr(out), _ptr(nodes), num, _ptr(num_dev), _ptr(table), parts_table.ptr(),
-                                            num_part, _ptr(host_feat), _dim_of(out), DTYPE_CODE[src_dtype],
+                                            num_part, _ptr(host_feat), _dim_of(out), _dtype_code(src_dtype),
                                             DTYPE_CODE[out.dtype], _ptr(num_miss), _stream()),
           "ggms_extract_cached_convert")
     return out
@@ -375,13 +401,16 @@ def _feature_tiers(table, replica, parts_table, num_part, my_part, host_feat, ho
 
 def extract_tiered_convert(out, src_dtype, nodes, table, replica, parts_table, num_part, my_part, host_feat, num=None,
                            num_dev=None, tier_rows=None, host_row_mask=0):
-    """extract_tiered with every tier in `src_dtype` and the rows delivered in out's dtype."""
+    """extract_tiered with every tier in `src_dtype` and the rows delivered in out's dtype (src_dtype=Q8ROW: every
+    tier is uint8 rows of row_bytes(Q8ROW, dim) bytes)."""
     _require_gpu(out)
     if num is None:
         num = nodes.numel()
+    _check_q8row(host_feat, src_dtype, _dim_of(out))
+    _check_q8row(replica, src_dtype, _dim_of(out))
     t = _feature_tiers(table, replica, parts_table, num_part, my_part, host_feat, host_row_mask)
     check(lib().ggms_extract_tiered_convert(_ptr(out), _ptr(nodes), num, _ptr(num_dev), C.byref(t), _dim_of(out),
-                                            DTYPE_CODE[src_dtype], DTYPE_CODE[out.dtype], _ptr(tier_rows), _stream()),
+                                            _dtype_code(src_dtype), DTYPE_CODE[out.dtype], _ptr(tier_rows), _stream()),
           "ggms_extract_tiered_convert")
     return out
 

@@ -19,7 +19,7 @@ for _name in ("init start num_class feat_dim num_epoch steps_per_epoch get_next_
               "report_epoch report_epoch_average report_node_access trace_step_begin trace_step_end "
               "trace_step_begin_now trace_step_end_now dump_trace forward_barrier wait_one_child log_step_by_key "
               "get_log_step_value_by_key data_init sample_init train_init extract_start num_local_step "
-              "um_sample_init switch_init").split():
+              "um_sample_init switch_init feat_row_bytes").split():
     globals()[_name] = getattr(_basics, _name)
 
 # DataType code -> (numpy typestr, torch dtype); common/common.h:38-46, adapter.cc:33-53
@@ -30,6 +30,8 @@ _DT = {0: ("<f4", torch.float32), 1: ("<f8", torch.float64), 2: ("<f2", torch.fl
        7: ("<i2", torch.bfloat16),
        # GGMS_F8E4M3 / GGMS_F8E5M2 (extensions): the OCP 8-bit floats have no typestr either -- bytes, re-viewed
        16: ("|u1", torch.float8_e4m3fn), 17: ("|u1", torch.float8_e5m2)}
+# (GGMS_Q8ROW = 18 is a row format with no element type: never a batch's dtype -- the engine refuses such a table without
+# feat_out_dtype -- and get_dataset_feat reports the stored rows as uint8 of shape (rows, ggms_row_bytes), code 3)
 _FP8 = (torch.float8_e4m3fn, torch.float8_e5m2)
 
 # config key `feat_out_dtype` was given: get_graph_feat hands the rows out as the gather delivered them
