@@ -609,6 +609,28 @@ int ggms_extract_tiered_convert(void *out, const ggms_id_t *nodes, size_t num_no
                                 uint64_t *tier_rows_dev, ggms_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Row quantiser (an extension): the WRITE side of the narrow tables the converting gathers read.  `num_rows` dense
+ * rows of `dim` elements of src_dtype (GGMS_F32 or GGMS_F16) are encoded into out_dtype -- GGMS_F16, GGMS_BF16,
+ * GGMS_F8E4M3, GGMS_F8E5M2 or GGMS_Q8ROW -- with output rows ggms_row_bytes(out_dtype, dim) apart.  One streaming
+ * pass; bit for bit what the CPU tools of xgnn_amd/datagen.py (quantize_features) compute:
+ *   - F16 / BF16: round to nearest even, overflow to +-inf, subnormals kept (the converting gather's narrowing);
+ *   - F8E4M3: round to nearest even after a clamp to +-448 (no infinity: +-inf and everything beyond saturate);
+ *     F8E5M2: round to nearest even, overflow to +-inf.  -0 keeps its sign, subnormal codes are produced, NaN gives a
+ *     NaN code.  An F16 source is widened to f32 first (exact);
+ *   - Q8ROW, in float64: lo / hi = the row's minimum / maximum, scale = f32((hi - lo) / 255), code = clip(rint((x -
+ *     lo) / scale), 0, 255) with rint rounding halves to even, every code 0 when the f32 scale is 0 (it may be an f32
+ *     subnormal), bias = lo; pad bytes zero.  Of zeros of both signs the minimum is -0.0.
+ *     A row that holds NaN or +-inf has no codes: its whole output row is written as zero bytes and first_row + its
+ *     index is folded into *bad_row with a 64-bit atomic minimum -- the caller sets the word to UINT64_MAX before the
+ *     call and reads the smallest bad row after it; bad_row == NULL: no report.  The other formats never report.
+ * GGMS_ERR_INVALID (nothing launched) for any other pair of dtypes, src_dtype == out_dtype, dim == 0, a `src` that is
+ * not 4-byte aligned, or an `out` that is not aligned to its element (Q8ROW: to 8 bytes, every row's trailer is one
+ * store).  Loads are up to 16 bytes wide where `src` and dim allow it.  num_rows == 0 is GGMS_OK.
+ * ------------------------------------------------------------------------- */
+int ggms_quantize_rows(void *out, int out_dtype, const void *src, int src_dtype, size_t num_rows, size_t dim,
+                       uint64_t first_row, uint64_t *bad_row /* device, may be NULL */, ggms_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Launch timer: a row gather's OWN start / end timestamps, with no packet of their own on the stream.
  * The reference times its extract with a host timer around a stream sync (dist_loops.cc:1276-1281,
  * kLogL1CopyTime); a pipelined caller has to use events instead, and every hipEventRecord / hipStreamWaitEvent

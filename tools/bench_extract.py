@@ -14,7 +14,12 @@ straight copy as the session's copy ceiling, and
     python tools/bench_extract.py --q8row-ab [--dim 128 --rows N --table-rows N] --parent-lib SO [--out FILE]
 the comparison behind Q8ROW (row-scaled 8-bit) tables: the three Q8ROW -> f32 / f16 / bf16 gathers beside the f16 -> X
 gathers of the parent build's library, the FP8 gathers and a straight copy; condition: a Q8ROW gather is no slower than
-the parent's f16 -> X gather of the same output beyond the 3.5 % drift of a session."""
+the parent's f16 -> X gather of the same output beyond the 3.5 % drift of a session, and
+    python tools/bench_extract.py --quantize-ab [--dim 128 --rows N] [--parent-lib SO] [--out FILE]
+the comparison behind the row quantiser (ggms_quantize_rows): F32 rows encoded into each of F16, BF16, F8E4M3, F8E5M2
+and Q8ROW beside the plain F32 gather of the same rows through an identity index (ggms_gather_scatter; of the parent
+build's library with --parent-lib) and a straight device copy of the input bytes; condition: no encode is slower than
+that gather beyond the 3.5 % drift of a session."""
 import argparse
 import ctypes as C
 import os, sys
@@ -31,6 +36,7 @@ ap.add_argument("--table-rows", type=int, default=16_000_000)
 ap.add_argument("--ab", action="store_true")
 ap.add_argument("--fp8-ab", action="store_true")
 ap.add_argument("--q8row-ab", action="store_true")
+ap.add_argument("--quantize-ab", action="store_true")
 ap.add_argument("--parent-lib", help="--fp8-ab / --q8row-ab: a libggms_hip.so of another build, timed beside this one")
 ap.add_argument("--alt-lib", help="--fp8-ab: a trial build whose FP8 gathers are timed too")
 ap.add_argument("--alt-name", default="trial build")
@@ -253,6 +259,69 @@ def run_q8row_ab():
             f.write(text + "\n")
 
 
+def run_quantize_ab():
+    """Every case = one launch over the same args.rows x args.dim F32 rows; 5 rounds x 30 launches in alternating order;
+    algorithmic bytes = rows x (source row + written row) (+ 4 per row for the gather's index)."""
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    from xgnn_amd import _lib
+    src = torch.randn(args.rows, args.dim, device=dev)
+    idx = torch.arange(args.rows, device=dev, dtype=torch.int32)
+    out32 = torch.empty_like(src)
+
+    def gather(path):
+        fn = C.CDLL(path).ggms_gather_scatter
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+
+        def run():
+            rc = fn(out32.data_ptr(), src.data_ptr(), idx.data_ptr(), None, args.rows, None, args.dim, 0, stream)
+            assert rc == 0, rc
+        return run
+
+    ref = "parent build" if args.parent_lib else "this build"
+    row32 = args.dim * 4
+    cases = [(f"{ref}: f32 plain gather, identity index", gather(args.parent_lib or _lib.LIB_PATH), args.rows * (4 + 2 * row32))]
+    if args.parent_lib:
+        cases.append(("this build: f32 plain gather, identity index", gather(_lib.LIB_PATH), args.rows * (4 + 2 * row32)))
+    stores = [("f16", torch.float16), ("bf16", torch.bfloat16), ("f8e4m3", torch.float8_e4m3fn),
+              ("f8e5m2", torch.float8_e5m2), ("q8row", ops.Q8ROW)]
+    for name, dt in stores:
+        out = ops.quantize_rows(src, dt)  # (allocated once; Q8ROW's check reads one word back, left out of the timing)
+        row = ops.row_bytes(dt, args.dim)
+        cases.append((f"this build: f32 -> {name}", lambda dt=dt, out=out: ops.quantize_rows(src, dt, out=out, check=False),
+                      args.rows * (row32 + row)))
+    cases.append(("straight copy (torch copy_) of the input bytes", lambda: out32.copy_(src), 2 * args.rows * row32))
+    times = {name: [] for name, _, _ in cases}
+    for rnd in range(5):
+        for name, fn, _ in (cases if rnd % 2 == 0 else cases[::-1]):
+            times[name].append(timeit(fn, reps=30))
+    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    ceiling = cases[-1][2] / med[cases[-1][0]]
+    lines = [f"row quantiser A/B: {args.rows} rows x dim {args.dim}, F32 source in HBM, one process, 5 rounds x 30 launches "
+             f"per case in alternating order, median of the rounds (min .. max; spread = (max - min) / median)",
+             f"device: {torch.cuda.get_device_name(0)}; copy ceiling of this session: {ceiling / 1e12:.3f} TB/s"]
+    for name, _, by in cases:
+        v = times[name]
+        lines.append(f"{name:50s} {med[name] * 1e3:7.4f} ms  ({min(v) * 1e3:.4f} .. {max(v) * 1e3:.4f}; spread "
+                     f"{(max(v) - min(v)) / med[name] * 100:4.1f} %)  {by / med[name] / 1e12:5.2f} TB/s algorithmic = "
+                     f"{by / med[name] / ceiling:.3f} of the copy ceiling")
+    b = med[cases[0][0]]
+    for name, dt in stores:
+        a = med[f"this build: f32 -> {name}"]
+        lines.append(f"f32 -> {name} / {ref}'s f32 plain gather = {a / b:.3f}  (bytes: "
+                     f"{(row32 + ops.row_bytes(dt, args.dim)) / (4 + 2 * row32):.3f}; condition <= 1.035: "
+                     f"{'PASS' if a <= 1.035 * b else 'OPEN'})")
+    text = "\n".join(lines)
+    print(text, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
+if args.quantize_ab:
+    run_quantize_ab()
+    sys.exit(0)
 if args.ab:
     run_ab()
     sys.exit(0)

@@ -79,6 +79,13 @@ static void refuse_arch6_keys(std::unordered_map<std::string, std::string> &kv, 
   if (dist_graph) fatal(__FILE__, __LINE__, arch + ": use_dist_graph is an arch6 key (GGMS shards across workers)");
 }
 
+// a row-scaled table (FEAT_DATA_TYPE Q8ROW on disk, or made by feat_store_dtype = Q8ROW) without feat_out_dtype
+static const char *const kQ8RowNeedsOutDtype =
+    "FEAT_DATA_TYPE Q8ROW needs the config key feat_out_dtype (f32 | f16 | bf16): a row of 8-bit codes with its scale and "
+    "bias is decoded by the feature gather, there is no element type to deliver it in as it is";
+static const std::map<std::string, int> kStoreDtypes = {{"F16", GGMS_F16}, {"BF16", GGMS_BF16}, {"F8E4M3", GGMS_F8E4M3},
+                                                        {"F8E5M2", GGMS_F8E5M2}, {"Q8ROW", GGMS_Q8ROW}};
+
 void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in) {
   auto kv = kv_in;
   SAM_CHECK(!cfg.configured, "samgraph_config called twice");
@@ -229,6 +236,22 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
       fatal(__FILE__, __LINE__, "arch6: feat_out_dtype needs gpu_extract = True or cache_percentage 1.0: the host-staged "
                                 "tier's rows land in the batch by hipMemcpyAsync, which does not convert");
   }
+  if (kv.count("feat_store_dtype")) { // extension: the F32 / F16 table on disk is encoded into this type on the trainer GPU
+    const std::string v = kv["feat_store_dtype"];
+    if (!kStoreDtypes.count(v))
+      fatal(__FILE__, __LINE__, "feat_store_dtype = " + v + ": unknown store type; the GPU quantiser writes F16, BF16, "
+                                "F8E4M3, F8E5M2 or Q8ROW");
+    cfg.feat_store_dtype = kStoreDtypes.at(v);
+    if (cfg.arch == kArch0)
+      fatal(__FILE__, __LINE__, "arch0: feat_store_dtype needs a GPU: the table is encoded by a kernel, and the CPU engine "
+                                "has no GPU; quantise the dataset offline (datagen.quantize_features)");
+    if (cfg.arch == kArch5 || cfg.arch == kArch6)
+      fatal(__FILE__, __LINE__, std::string(cfg.arch == kArch5 ? "arch5" : "arch6") + ": feat_store_dtype is not built: the "
+                                "process that loads the dataset forks its workers and must not initialise the GPU before it "
+                                "forks; quantise the dataset offline (datagen.quantize_features)");
+    // the batch dtype rule of a table of that type (the table's side of it is checked in LoadDataset)
+    if (cfg.feat_store_dtype == GGMS_Q8ROW && cfg.feat_out_dtype < 0) fatal(__FILE__, __LINE__, kQ8RowNeedsOutDtype);
+  }
   if (cfg.arch == kArch4) { // DoGPUSampleDyCache's switch (cuda/cuda_loops.cc:347-377) and what it needs
     if (cfg.sample_type != GGMS_KHOP0 && cfg.sample_type != GGMS_KHOP1 && cfg.sample_type != GGMS_WEIGHTED_KHOP)
       fatal(__FILE__, __LINE__, "arch4: _sample_type " + std::to_string(cfg.sample_type) + " is not supported: the "
@@ -319,10 +342,7 @@ void Engine::LoadDataset() {
         fatal(__FILE__, __LINE__, "feat_out_dtype with FEAT_DATA_TYPE " + v + ": the gather converts F16, BF16, F32, "
                                   "F8E4M3, F8E5M2 and Q8ROW tables only");
       // a row-scaled table has no element type to hand out raw: only the converting gather can deliver its rows
-      if (ds.feat_dtype == GGMS_Q8ROW && cfg.feat_out_dtype < 0)
-        fatal(__FILE__, __LINE__, "FEAT_DATA_TYPE Q8ROW needs the config key feat_out_dtype (f32 | f16 | bf16): a row of "
-                                  "8-bit codes with its scale and bias is decoded by the feature gather, there is no "
-                                  "element type to deliver it in as it is");
+      if (ds.feat_dtype == GGMS_Q8ROW && cfg.feat_out_dtype < 0) fatal(__FILE__, __LINE__, kQ8RowNeedsOutDtype);
     } else {
       meta[k] = std::stoull(v);
     }
@@ -340,6 +360,16 @@ void Engine::LoadDataset() {
   size_t fake_dim = 0;
   if (const char *e = getenv("SAMGRAPH_FAKE_FEAT_DIM")) fake_dim = std::strtoull(e, nullptr, 10);
   if (fake_dim) ds.feat_dim = fake_dim;
+  if (cfg.feat_store_dtype >= 0) { // what QuantizeStore reads: a real F32 / F16 table of another type than the store's
+    const std::string key = "feat_store_dtype = " + cfg.raw["feat_store_dtype"];
+    if (ds.feat_dtype != GGMS_F32 && ds.feat_dtype != GGMS_F16)
+      fatal(__FILE__, __LINE__, key + ": the quantiser reads FEAT_DATA_TYPE F32 or F16, this dataset's table has another type");
+    if (ds.feat_dtype == cfg.feat_store_dtype)
+      fatal(__FILE__, __LINE__, key + ": FEAT_DATA_TYPE is that type already, there is nothing to encode; drop the key");
+    if (fake_dim || getenv("SAMGRAPH_EMPTY_FEAT") || !file_exists(cfg.dataset_path + "feat.bin"))
+      fatal(__FILE__, __LINE__, key + ": needs the dataset's own feat.bin; a stand-in table (SAMGRAPH_EMPTY_FEAT, "
+                                "SAMGRAPH_FAKE_FEAT_DIM, or a dataset without feat.bin) is not quantised");
+  }
   const size_t row_bytes = ds.feat_row_bytes();
   ds.feat_rows = ds.num_node;
   size_t empty_bits = 0; // SAMGRAPH_EMPTY_FEAT = k (run_config.cc:137-139, engine.cc:205-207): a 2^k-row stand-in table,
@@ -1009,6 +1039,77 @@ void Engine::Presample() {
   (void)hipFree(d_train); (void)hipFree(d_freq); (void)hipFree(d_counts);
 }
 
+// Config key feat_store_dtype: the table of the dataset (F32 or F16, a mapped file) is encoded into the store type by
+// the trainer GPU, 64 MB-class chunks through two sets of pinned staging buffers -- the host cores fill one while the
+// GPU works on the other -- and lands in an anonymous host table that takes the place of ds.feat.  After this the
+// dataset is what a meta.txt naming the store type would have loaded; BuildCache and everything behind it see no
+// difference.
+void Engine::QuantizeStore() {
+  const auto t0 = std::chrono::steady_clock::now();
+  const int store = cfg.feat_store_dtype;
+  const size_t src_row = ds.feat_row_bytes(), dst_row = ggms_row_bytes(store, ds.feat_dim), n = ds.num_node;
+  hipStream_t bs = BatchSampledElsewhere() ? stream_extract_ : stream_;
+  HostArray q;
+  q.bytes = n * dst_row;
+  q.ptr = mmap(nullptr, std::max<size_t>(q.bytes, 1), PROT_READ | PROT_WRITE, MAP_SHARED | MAP_ANONYMOUS, -1, 0);
+  SAM_CHECK(q.ptr != MAP_FAILED, "feat_store_dtype: mmap of the quantised table failed");
+  q.shared_anon = true;
+  const size_t step = std::max<size_t>(1, (64u << 20) / src_row);
+  char *in[2], *out[2], *d_in[2], *d_out[2];
+  hipEvent_t done[2];
+  size_t first[2] = {0, 0}, rows[2] = {0, 0}; // the chunk whose codes out[k] receives
+  for (int k = 0; k < 2; ++k) {
+    SAM_HIP(hipHostMalloc((void **)&in[k], step * src_row));
+    SAM_HIP(hipHostMalloc((void **)&out[k], step * dst_row));
+    SAM_HIP(hipMalloc((void **)&d_in[k], step * src_row));
+    SAM_HIP(hipMalloc((void **)&d_out[k], step * dst_row));
+    SAM_HIP(hipEventCreateWithFlags(&done[k], hipEventDisableTiming));
+  }
+  uint64_t *d_bad = nullptr, bad = ~0ull;
+  SAM_HIP(hipMalloc((void **)&d_bad, sizeof(uint64_t)));
+  SAM_HIP(hipMemcpyAsync(d_bad, &bad, sizeof(bad), hipMemcpyHostToDevice, bs));
+  SAM_HIP(hipStreamSynchronize(bs));
+  Team team((int)std::max<size_t>(1, cfg.omp_thread_num));
+  const char *feat = (const char *)ds.feat.ptr;
+  auto collect = [&](int k) { // chunk in out[k] -> its place in the new table
+    SAM_HIP(hipEventSynchronize(done[k]));
+    std::memcpy((char *)q.ptr + first[k] * dst_row, out[k], rows[k] * dst_row);
+    rows[k] = 0;
+  };
+  size_t c = 0;
+  for (size_t lo = 0; lo < n; lo += step, ++c) {
+    const int k = (int)(c & 1);
+    const size_t m = std::min(step, n - lo);
+    if (rows[k]) collect(k); // (also: the copy that last read in[k] is done)
+    team.ParallelFor(m, [&](size_t a, size_t b, int) { std::memcpy(in[k] + a * src_row, feat + (lo + a) * src_row, (b - a) * src_row); });
+    SAM_HIP(hipMemcpyAsync(d_in[k], in[k], m * src_row, hipMemcpyHostToDevice, bs));
+    SAM_GGMS(ggms_quantize_rows(d_out[k], store, d_in[k], ds.feat_dtype, m, ds.feat_dim, lo, d_bad, bs));
+    SAM_HIP(hipMemcpyAsync(out[k], d_out[k], m * dst_row, hipMemcpyDeviceToHost, bs));
+    SAM_HIP(hipEventRecord(done[k], bs));
+    first[k] = lo;
+    rows[k] = m;
+  }
+  for (int k = 0; k < 2; ++k)
+    if (rows[(c + k) & 1]) collect((int)((c + k) & 1)); // the older chunk first
+  SAM_HIP(hipMemcpy(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost));
+  for (int k = 0; k < 2; ++k) {
+    (void)hipHostFree(in[k]); (void)hipHostFree(out[k]); (void)hipFree(d_in[k]); (void)hipFree(d_out[k]);
+    (void)hipEventDestroy(done[k]);
+  }
+  (void)hipFree(d_bad);
+  if (bad != ~0ull)
+    fatal(__FILE__, __LINE__, "feat_store_dtype = Q8ROW: row " + std::to_string(bad) + " of feat.bin holds NaN or inf: a "
+                              "row-scaled table has no code for either");
+  const size_t before = ds.feat.bytes;
+  if (ds.feat.ptr && ds.feat.bytes) munmap(ds.feat.ptr, ds.feat.bytes); // the mapped file (arch1 / arch3 / arch4: never shared)
+  ds.feat = q;
+  ds.feat_dtype = store;
+  const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  prof.LogInit(/*extension slot: quantise the feature store*/ 41, s);
+  std::fprintf(stderr, "[samgraph-amd] feat_store_dtype = %s: feature table quantised on GPU %d in %.3f s, %zu -> %zu bytes\n",
+               cfg.raw["feat_store_dtype"].c_str(), trainer_device_, s, before, q.bytes);
+}
+
 void Engine::BuildCache() {
   const size_t row_bytes = ds.feat_row_bytes();
   const char *feat = (const char *)ds.feat.ptr;
@@ -1164,6 +1265,7 @@ void Engine::TrainInit(int worker_id, const std::string &ctx) {
   else
     SAM_CHECK(parse_device(ctx) == device_, "arch6: sampler and trainer share the GPU (cuda_cache_manager_host.cc:152-155)");
   SAM_HIP(hipSetDevice(trainer_device_));
+  if (cfg.feat_store_dtype >= 0) QuantizeStore();
   auto t0 = std::chrono::steady_clock::now();
   BuildCache();
   prof.LogInit(/*kLogInitL2BuildCache*/ 10, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());

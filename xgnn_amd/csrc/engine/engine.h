@@ -90,6 +90,10 @@ struct RunConfig {
   // extension (config key `feat_out_dtype` = f32 | f16 | bf16): the dtype the batch's feature rows are DELIVERED in; the
   // gather converts from the table's (FEAT_DATA_TYPE) in its one pass.  -1: key absent, the table's dtype
   int feat_out_dtype = -1;
+  // extension (config key `feat_store_dtype` = F16 | BF16 | F8E4M3 | F8E5M2 | Q8ROW): the F32 / F16 table on disk is
+  // encoded into this type by the trainer GPU before the cache is built (Engine::QuantizeStore); from then on the
+  // dataset is what a meta.txt naming the type would have loaded.  -1: key absent, the table stays as it is on disk
+  int feat_store_dtype = -1;
   size_t staged_serial_epochs = 0; // host-staged path: the first N epochs run the reference's serial, per-phase-timed sequence
   size_t staged_serial_steps = 0;  // ... or this worker's first N batches
   // worker 0 ranks the nodes at init: pre_sample (sampled input nodes) or presample_static (L-hop closures)
@@ -255,6 +259,7 @@ class Engine {
   bool topo_valid_ = false;
   void UploadGraph();
   void Presample();
+  void QuantizeStore(); // config key feat_store_dtype: ds.feat re-encoded by ggms_quantize_rows, before BuildCache
   void BuildCache();
   Batch *AcquireSlot(bool background);
   // `gpu_extract` off (SGNN mode of arch6): miss ids -> host, CPU gather into pinned memory, async H2D, combine

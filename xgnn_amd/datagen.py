@@ -268,12 +268,14 @@ def quantize_q8row(values, first_row=0):
     return codes, scale, lo.astype(np.float32)  # (the minimum of F32 / F16 values is an f32 number)
 
 
-def quantize_features(path_in, path_out, fmt, chunk_rows=1 << 20):
+def quantize_features(path_in, path_out, fmt, chunk_rows=1 << 20, device=None):
     """Rewrite the F32 / F16 dataset at path_in as the same dataset with an 8-bit feature table at path_out: fmt
     "Q8ROW" quantises every row to 8-bit codes with the row's own scale and bias (quantize_q8row); for an FP8 feature
     table (fmt "F8E4M3" or "F8E5M2"): every other file is linked (or copied where a link is not possible), feat.bin is cast on the
     CPU with torch, round to nearest even, one chunk of rows at a time, and meta.txt names the new FEAT_DATA_TYPE.
-    A one-off offline step; there is no kernel for it.
+    device=None: on the CPU, numpy / torch in float64, as described here.  device="cuda:0" (a torch device string): every
+    chunk is uploaded, encoded by the GPU (ops.quantize_rows, ggms_quantize_rows) and written out -- the same files byte
+    for byte; with a device fmt may also be "F16" (from an F32 table) or "BF16".
 
     E4M3 has no infinity and torch's cast turns everything beyond its range into NaN, so for E4M3 the values are
     clamped to +-448 (the largest finite value) FIRST: an out-of-range input saturates; NaN stays NaN.  E5M2 is cast
@@ -281,12 +283,13 @@ def quantize_features(path_in, path_out, fmt, chunk_rows=1 << 20):
     import os
     import shutil
     import torch
-    assert fmt in FP8_FORMATS or fmt == "Q8ROW", fmt
+    assert fmt in FP8_FORMATS or fmt == "Q8ROW" or (device is not None and fmt in ("F16", "BF16")), fmt
     with open(os.path.join(path_in, "meta.txt")) as f:
         meta = [line.split() for line in f if line.strip()]
     kv = dict(meta)
     src_name = kv.get("FEAT_DATA_TYPE", "F32")
     assert src_name in ("F32", "F16"), f"quantize_features reads F32 and F16 tables, not {src_name}"
+    assert src_name != fmt, f"the table is {fmt} already"
     src_dt = np.float32 if src_name == "F32" else np.float16
     n, dim = int(kv["NUM_NODE"]), int(kv["FEAT_DIM"])
     os.makedirs(path_out, exist_ok=True)
@@ -303,6 +306,13 @@ def quantize_features(path_in, path_out, fmt, chunk_rows=1 << 20):
     table = np.memmap(os.path.join(path_in, "feat.bin"), dtype=src_dt, mode="r", shape=(n, dim))
     with open(os.path.join(path_out, "feat.bin"), "wb") as out:
         for r in range(0, n, chunk_rows):
+            if device is not None:
+                from . import ops
+                out_dtype = ops.Q8ROW if fmt == "Q8ROW" else \
+                    {"F16": torch.float16, "BF16": torch.bfloat16}.get(fmt) or _fp8_torch_dtype(fmt)
+                rows = ops.quantize_rows(torch.from_numpy(np.array(table[r:r + chunk_rows])).to(device), out_dtype, first_row=r)
+                out.write(rows.view(torch.uint8).cpu().numpy().tobytes())
+                continue
             if fmt == "Q8ROW":
                 out.write(pack_q8row(*quantize_q8row(table[r:r + chunk_rows], first_row=r)).tobytes())
                 continue

@@ -328,6 +328,35 @@ def gather_scatter_convert(out, src, src_index, dst_index, num=None, num_dev=Non
     return out
 
 
+def quantize_rows(src, out_dtype, out=None, first_row=0, check=True):
+    """ggms_quantize_rows: the 2-D float32 / float16 device tensor `src` encoded into out_dtype -- torch.float16,
+    torch.bfloat16, torch.float8_e4m3fn, torch.float8_e5m2, or Q8ROW (returned as the uint8 (rows, row_bytes(Q8ROW, dim))
+    tensor of a row-scaled table) -- bit for bit what datagen.quantize_features computes on the CPU.  A Q8ROW row that
+    holds NaN or inf has no codes: with check=True the smallest such row (first_row + its index) is read back and raised
+    as quantize_q8row raises it; with check=False its output row is zero bytes and nothing is said."""
+    _require_gpu(src)
+    assert src.dim() == 2 and src.dtype in (torch.float32, torch.float16), \
+        f"quantize_rows reads a 2-D float32 or float16 tensor, not {src.dtype} {tuple(src.shape)}"
+    rows, dim = src.shape
+    if not (src.stride(1) == 1 and src.stride(0) == dim) and rows * dim:
+        src = src.contiguous()
+    code = _dtype_code(out_dtype)
+    if out is None:
+        out = torch.empty((rows, row_bytes(Q8ROW, dim)), dtype=torch.uint8, device=src.device) if code == Q8ROW else \
+            torch.empty((rows, dim), dtype=out_dtype, device=src.device)
+    assert out.is_contiguous() and out.device == src.device
+    bad = None
+    if code == Q8ROW and check:
+        bad = torch.full((1,), -1, dtype=torch.int64, device=src.device)  # UINT64_MAX
+    _lib.check(lib().ggms_quantize_rows(_ptr(out), code, _ptr(src), DTYPE_CODE[src.dtype], rows, dim, first_row, _ptr(bad),
+                                        _stream()), "ggms_quantize_rows")
+    if bad is not None:
+        row = int(bad.item())
+        if row != -1:
+            raise ValueError(f"quantize_features: row {row} holds NaN or inf: a row-scaled table has no code for either")
+    return out
+
+
 class PartTable:
     """HOST array of shard base pointers (DeviceDistFeature / DeviceDistGraph, dist_graph.h:114-212): the operators
     hand the pointers to their kernels by value, at most GGMS_MAX_PARTS = 8 shards."""

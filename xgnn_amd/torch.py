@@ -34,13 +34,14 @@ _DT = {0: ("<f4", torch.float32), 1: ("<f8", torch.float64), 2: ("<f2", torch.fl
 # feat_out_dtype -- and get_dataset_feat reports the stored rows as uint8 of shape (rows, ggms_row_bytes), code 3)
 _FP8 = (torch.float8_e4m3fn, torch.float8_e5m2)
 
-# config key `feat_out_dtype` was given: get_graph_feat hands the rows out as the gather delivered them
+# config key `feat_out_dtype` or `feat_store_dtype` was given (the caller chose the batch's dtype, or asked for a narrow
+# store and gets its type): get_graph_feat hands the rows out as the gather delivered them
 _feat_as_delivered = False
 
 
 def config(run_config):
     global _feat_as_delivered
-    _feat_as_delivered = "feat_out_dtype" in run_config
+    _feat_as_delivered = "feat_out_dtype" in run_config or "feat_store_dtype" in run_config
     return _basics.config(run_config)
 
 
