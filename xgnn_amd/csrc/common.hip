@@ -5,6 +5,7 @@
 #include <mutex>
 #include <random>
 
+#include "row_formats.h"
 #include "tile_scan.h"
 
 namespace ggms {
@@ -151,7 +152,7 @@ size_t ggms_dtype_bytes(int dtype) {
 }
 
 size_t ggms_row_bytes(int dtype, size_t dim) {
-  if (dtype == GGMS_Q8ROW) return ((dim + 7) & ~(size_t)7) + 8; // codes, zero pad to a multiple of 8, f32 scale, f32 bias
+  if (dtype == GGMS_Q8ROW) return (size_t)q8row_stride(dim);
   return dim * ggms_dtype_bytes(dtype);
 }
 

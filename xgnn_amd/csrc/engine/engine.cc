@@ -2,6 +2,7 @@
 // /root/reference/samgraph/common/.
 #include "engine.h"
 #include "team.h"
+#include "../row_formats.h"
 
 #include <fcntl.h>
 #include <pthread.h>
@@ -83,8 +84,12 @@ static void refuse_arch6_keys(std::unordered_map<std::string, std::string> &kv, 
 static const char *const kQ8RowNeedsOutDtype =
     "FEAT_DATA_TYPE Q8ROW needs the config key feat_out_dtype (f32 | f16 | bf16): a row of 8-bit codes with its scale and "
     "bias is decoded by the feature gather, there is no element type to deliver it in as it is";
-static const std::map<std::string, int> kStoreDtypes = {{"F16", GGMS_F16}, {"BF16", GGMS_BF16}, {"F8E4M3", GGMS_F8E4M3},
-                                                        {"F8E5M2", GGMS_F8E5M2}, {"Q8ROW", GGMS_Q8ROW}};
+// the dtype names of meta.txt's FEAT_DATA_TYPE; feat_store_dtype takes those of them the quantiser writes
+static const std::map<std::string, int> kFeatDtypeNames = {{"F32", GGMS_F32}, {"F64", GGMS_F64}, {"F16", GGMS_F16},
+                                                           {"U8", GGMS_U8},   {"I32", GGMS_I32}, {"I8", GGMS_I8},
+                                                           {"I64", GGMS_I64}, {"BF16", GGMS_BF16},
+                                                           {"F8E4M3", GGMS_F8E4M3}, {"F8E5M2", GGMS_F8E5M2},
+                                                           {"Q8ROW", GGMS_Q8ROW}};
 
 void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in) {
   auto kv = kv_in;
@@ -238,10 +243,11 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
   }
   if (kv.count("feat_store_dtype")) { // extension: the F32 / F16 table on disk is encoded into this type on the trainer GPU
     const std::string v = kv["feat_store_dtype"];
-    if (!kStoreDtypes.count(v))
+    const auto name = kFeatDtypeNames.find(v);
+    if (name == kFeatDtypeNames.end() || !ggms::quantiser_writes(name->second))
       fatal(__FILE__, __LINE__, "feat_store_dtype = " + v + ": unknown store type; the GPU quantiser writes F16, BF16, "
                                 "F8E4M3, F8E5M2 or Q8ROW");
-    cfg.feat_store_dtype = kStoreDtypes.at(v);
+    cfg.feat_store_dtype = name->second;
     if (cfg.arch == kArch0)
       fatal(__FILE__, __LINE__, "arch0: feat_store_dtype needs a GPU: the table is encoded by a kernel, and the CPU engine "
                                 "has no GPU; quantise the dataset offline (datagen.quantize_features)");
@@ -329,16 +335,10 @@ void Engine::LoadDataset() {
     std::string k, v;
     if (!(iss >> k >> v)) break;
     if (k == "FEAT_DATA_TYPE") {
-      static const std::map<std::string, int> names = {{"F32", GGMS_F32}, {"F64", GGMS_F64}, {"F16", GGMS_F16},
-                                                       {"U8", GGMS_U8},   {"I32", GGMS_I32}, {"I8", GGMS_I8},
-                                                       {"I64", GGMS_I64}, {"BF16", GGMS_BF16},
-                                                       {"F8E4M3", GGMS_F8E4M3}, {"F8E5M2", GGMS_F8E5M2},
-                                                       {"Q8ROW", GGMS_Q8ROW}};
-      SAM_CHECK(names.count(v), "unknown FEAT_DATA_TYPE " + v);
-      ds.feat_dtype = names.at(v);
+      SAM_CHECK(kFeatDtypeNames.count(v), "unknown FEAT_DATA_TYPE " + v);
+      ds.feat_dtype = kFeatDtypeNames.at(v);
       // (an FP8 table is a source of the converting gather only: without the key its rows are moved as bytes)
-      if (cfg.feat_out_dtype >= 0 && ds.feat_dtype != GGMS_F32 && ds.feat_dtype != GGMS_F16 && ds.feat_dtype != GGMS_BF16 &&
-          ds.feat_dtype != GGMS_F8E4M3 && ds.feat_dtype != GGMS_F8E5M2 && ds.feat_dtype != GGMS_Q8ROW)
+      if (cfg.feat_out_dtype >= 0 && !ggms::gather_converts_from(ds.feat_dtype))
         fatal(__FILE__, __LINE__, "feat_out_dtype with FEAT_DATA_TYPE " + v + ": the gather converts F16, BF16, F32, "
                                   "F8E4M3, F8E5M2 and Q8ROW tables only");
       // a row-scaled table has no element type to hand out raw: only the converting gather can deliver its rows
@@ -362,7 +362,7 @@ void Engine::LoadDataset() {
   if (fake_dim) ds.feat_dim = fake_dim;
   if (cfg.feat_store_dtype >= 0) { // what QuantizeStore reads: a real F32 / F16 table of another type than the store's
     const std::string key = "feat_store_dtype = " + cfg.raw["feat_store_dtype"];
-    if (ds.feat_dtype != GGMS_F32 && ds.feat_dtype != GGMS_F16)
+    if (!ggms::quantiser_reads(ds.feat_dtype))
       fatal(__FILE__, __LINE__, key + ": the quantiser reads FEAT_DATA_TYPE F32 or F16, this dataset's table has another type");
     if (ds.feat_dtype == cfg.feat_store_dtype)
       fatal(__FILE__, __LINE__, key + ": FEAT_DATA_TYPE is that type already, there is nothing to encode; drop the key");

@@ -22,14 +22,13 @@
 
 #include <hip/hip_ext.h>
 
-#include "fp8_decode.h"
 #include "ggms_device.h"
+#include "row_formats.h"
 
 namespace ggms {
 
 template <int BYTES> struct ChunkT;
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
 template <> struct ChunkT<16> { using type = u32x4_t; };
 template <> struct ChunkT<8> { using type = u32x2_t; };
 template <> struct ChunkT<4> { using type = uint32_t; };
@@ -49,39 +48,6 @@ template <int CB> struct CopyChunk {
   using Dst = Src;
   static __device__ __forceinline__ Dst convert(Src v) { return v; }
 };
-
-// element types by ggms_dtype code: the bits as stored, and the value as f32 (every conversion goes through f32)
-template <int DT> struct Elem;
-template <> struct Elem<GGMS_F32> {
-  using bits = uint32_t;
-  static __device__ __forceinline__ float to_f32(bits b) { return __builtin_bit_cast(float, b); }
-  static __device__ __forceinline__ bits from_f32(float f) { return __builtin_bit_cast(bits, f); }
-};
-template <> struct Elem<GGMS_F16> { // the casts are IEEE: widening exact (subnormals included), narrowing
-  using bits = uint16_t;            // round-to-nearest-even with overflow to inf and subnormal results kept
-  static __device__ __forceinline__ float to_f32(bits b) { return (float)__builtin_bit_cast(_Float16, b); }
-  static __device__ __forceinline__ bits from_f32(float f) { return __builtin_bit_cast(bits, (_Float16)f); }
-};
-template <> struct Elem<GGMS_BF16> { // the upper half of an f32
-  using bits = uint16_t;
-  static __device__ __forceinline__ float to_f32(bits b) { return __builtin_bit_cast(float, (uint32_t)b << 16); }
-  static __device__ __forceinline__ bits from_f32(float f) {
-    const uint32_t u = __builtin_bit_cast(uint32_t, f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (bits)((u >> 16) | 0x40u); // NaN stays NaN (quiet)
-    return (bits)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16); // nearest even; a carry out of the mantissa ends in inf
-  }
-};
-// the OCP 8-bit floats (fp8_decode.h): SOURCE types only -- no from_f32, so no pair with one of them as output exists
-template <> struct Elem<GGMS_F8E4M3> {
-  using bits = uint8_t;
-  static __device__ __forceinline__ float to_f32(bits b) { return fp8_e4m3_to_f32(b); }
-};
-template <> struct Elem<GGMS_F8E5M2> {
-  using bits = uint8_t;
-  static __device__ __forceinline__ float to_f32(bits b) { return fp8_e5m2_to_f32(b); }
-};
-template <typename T, int N> struct VecT { typedef T type __attribute__((ext_vector_type(N))); };
-template <typename T> struct VecT<T, 1> { using type = T; };
 
 template <int EPC, int SRC_DT, int DST_DT> struct ConvertChunk {
   using S = Elem<SRC_DT>;
@@ -139,9 +105,6 @@ template <int EPC, int DST_DT> struct ScaledChunk {
     }
   }
 };
-// where a Q8ROW row of `code_bytes` codes keeps its trailer, and the stride of such rows
-__host__ __device__ constexpr uint64_t q8row_trailer_offset(uint64_t code_bytes) { return (code_bytes + 7u) & ~(uint64_t)7u; }
-
 // which tier served a row (0 = not counted); counters[tier - 1] in ggms_extract_tiered
 constexpr uint32_t kTierHost = 1, kTierRemote = 2, kTierLocal = 3, kTierReplica = 4;
 
@@ -303,23 +266,6 @@ __device__ __forceinline__ uint64_t shfl_u64(uint64_t v, int src) {
   return ((uint64_t)hi << 32) | lo;
 }
 
-// chunk loads: plain or non-temporal (rows of a batch are read once)
-// The pointers travel through ds_bpermute as integers; tell the compiler they are GLOBAL so it emits
-// global_load/global_store (vmcnt only) instead of flat_* (vmcnt + lgkmcnt, aperture check).
-template <typename V, bool NT>
-__device__ __forceinline__ V load_chunk(uint64_t addr) {
-  typedef const V __attribute__((address_space(1))) *gp_t;
-  gp_t p = (gp_t)addr;
-  if constexpr (NT) return __builtin_nontemporal_load(p);
-  else return *p;
-}
-template <typename V, bool NT>
-__device__ __forceinline__ void store_chunk(uint64_t addr, V v) {
-  typedef V __attribute__((address_space(1))) *gp_t;
-  if constexpr (NT) __builtin_nontemporal_store(v, (gp_t)addr);
-  else *(gp_t)addr = v;
-}
-
 // U = independent chunk loads in flight per lane (16, or 8 for rows of fewer than 8 chunks)
 // Loads and stores are non-temporal: a batch's rows are read once and the gathered batch is a > 100-MB stream that
 // nothing re-reads from cache (measured + 3..5 % on MI355X each, profiles/r01-r02).
@@ -466,19 +412,6 @@ __global__ __launch_bounds__(kBlock) void k_copy_words(uint32_t *__restrict__ ds
   for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) dst[i] = src[i];
 }
 
-// The widest chunk, in ELEMENTS (a power of two up to max_epc), that divides a row of `dim` elements and keeps both
-// sides aligned to their own chunk size: epc x src_es bytes for every source base, epc x dst_es bytes for `out`
-// (*_bits: the addresses ORed together).
-static inline int pick_chunk(size_t dim, int max_epc, size_t src_es, uintptr_t src_bits, size_t dst_es, uintptr_t dst_bits) {
-  for (int epc = max_epc; epc > 1; epc >>= 1)
-    if (dim % epc == 0 && src_bits % (epc * src_es) == 0 && dst_bits % (epc * dst_es) == 0) return epc;
-  return 1;
-}
-// the plain gather: rows of bytes, chunks of up to 16 of them
-static inline int pick_chunk(size_t row_bytes, uintptr_t align_bits) {
-  return pick_chunk(row_bytes, 16, 1, align_bits, 1, align_bits);
-}
-
 } // namespace ggms
 
 // ---- launch timer (include/ggms.h): a pair of events that ride on the next gather's own dispatch packet ------------
@@ -586,28 +519,19 @@ struct RowMove {
   bool converts() const { return src_dt != dst_dt; }
   size_t src_row_bytes() const { return src_stride; } // the distance between two stored rows
 };
-static inline bool is_float_dtype(int dt) { return dt == GGMS_F16 || dt == GGMS_BF16 || dt == GGMS_F32; }
-static inline bool is_fp8_dtype(int dt) { return dt == GGMS_F8E4M3 || dt == GGMS_F8E5M2; }
 static bool row_move(int src_dt, int dst_dt, size_t dim, RowMove &m) {
-  if (src_dt == GGMS_Q8ROW || dst_dt == GGMS_Q8ROW) {
-    if (src_dt != GGMS_Q8ROW || !is_float_dtype(dst_dt)) {
-      set_error("extract: invalid argument: no conversion from dtype %d to dtype %d (Q8ROW is the source of a "
-                "converting gather into F16, BF16 or F32, nothing else)", src_dt, dst_dt);
-      return false;
-    }
-    m = RowMove{src_dt, dst_dt, dim, 1, ggms_dtype_bytes(dst_dt), ggms_row_bytes(src_dt, dim)};
-    if (dim == 0) {
-      set_error("extract: invalid argument: dtype %d -> %d, dim %zu (unknown dtype or empty rows)", src_dt, dst_dt, dim);
-      return false;
-    }
-    return true;
+  const bool q8row = src_dt == GGMS_Q8ROW; // its element is the one-byte code
+  if ((q8row || dst_dt == GGMS_Q8ROW) && !(q8row && is_float_dtype(dst_dt))) {
+    set_error("extract: invalid argument: no conversion from dtype %d to dtype %d (Q8ROW is the source of a "
+              "converting gather into F16, BF16 or F32, nothing else)", src_dt, dst_dt);
+    return false;
   }
-  m = RowMove{src_dt, dst_dt, dim, ggms_dtype_bytes(src_dt), ggms_dtype_bytes(dst_dt), ggms_row_bytes(src_dt, dim)};
+  m = RowMove{src_dt, dst_dt, dim, q8row ? 1 : ggms_dtype_bytes(src_dt), ggms_dtype_bytes(dst_dt), ggms_row_bytes(src_dt, dim)};
   if (m.src_es == 0 || m.dst_es == 0 || dim == 0) {
     set_error("extract: invalid argument: dtype %d -> %d, dim %zu (unknown dtype or empty rows)", src_dt, dst_dt, dim);
     return false;
   }
-  if (m.converts() && !((is_float_dtype(src_dt) || is_fp8_dtype(src_dt)) && is_float_dtype(dst_dt))) {
+  if (m.converts() && !(gather_converts_from(src_dt) && is_float_dtype(dst_dt))) {
     set_error("extract: invalid argument: no conversion from dtype %d to dtype %d (a converting gather takes F16, BF16 "
               "and F32 on either side, F8E4M3 and F8E5M2 as the source only)", src_dt, dst_dt);
     return false;
@@ -622,36 +546,32 @@ static bool row_move(int src_dt, int dst_dt, size_t dim, RowMove &m) {
 // 16-B store); profiles/fp8_table_ab.txt.
 constexpr int convert_max_epc(size_t src_es, size_t dst_es) { return (int)(16 / (src_es > dst_es ? src_es : dst_es)); }
 
-template <int SRC_DT, int DST_DT, bool SCATTER, typename Rows>
-static int launch_convert_pair(char *out, Rows rows, const uint32_t *dst_index, size_t n_max, Count n, size_t dim,
-                               int epc, uint64_t *miss_count, hipStream_t stream) {
-  const uint64_t rc = dim / epc;
-  if constexpr (convert_max_epc(sizeof(typename Elem<SRC_DT>::bits), sizeof(typename Elem<DST_DT>::bits)) == 8)
-    if (epc == 8)
-      return launch_chunks<ConvertChunk<8, SRC_DT, DST_DT>, Rows, SCATTER>(out, rows, dst_index, n_max, n, rc, miss_count, stream);
-  switch (epc) {
-    case 4: return launch_chunks<ConvertChunk<4, SRC_DT, DST_DT>, Rows, SCATTER>(out, rows, dst_index, n_max, n, rc, miss_count, stream);
-    case 2: return launch_chunks<ConvertChunk<2, SRC_DT, DST_DT>, Rows, SCATTER>(out, rows, dst_index, n_max, n, rc, miss_count, stream);
-    case 1: return launch_chunks<ConvertChunk<1, SRC_DT, DST_DT>, Rows, SCATTER>(out, rows, dst_index, n_max, n, rc, miss_count, stream);
-  }
-  set_error("extract: no %d-element chunk for dtype %d -> %d", epc, SRC_DT, DST_DT);
-  return GGMS_ERR_INVALID;
-}
+// A chunk FAMILY: one converting pair in every chunk width it is built in (kMaxEpc: the rule above)
+template <int SRC_DT, int DST_DT> struct ConvertFamily {
+  static constexpr int kSrcDt = SRC_DT, kDstDt = DST_DT;
+  static constexpr int kMaxEpc = convert_max_epc(sizeof(typename Elem<SRC_DT>::bits), sizeof(typename Elem<DST_DT>::bits));
+  template <int EPC> using Chunk = ConvertChunk<EPC, SRC_DT, DST_DT>;
+};
+template <int DST_DT> struct ScaledFamily { // Q8ROW -> DST_DT: a one-byte source element
+  static constexpr int kSrcDt = GGMS_Q8ROW, kDstDt = DST_DT;
+  static constexpr int kMaxEpc = convert_max_epc(1, sizeof(typename Elem<DST_DT>::bits));
+  template <int EPC> using Chunk = ScaledChunk<EPC, DST_DT>;
+};
 
-// Q8ROW -> DST_DT: ScaledChunk in the widest chunk the rule above allows (a one-byte source element)
-template <int DST_DT, bool SCATTER, typename Rows>
-static int launch_scaled(char *out, Rows rows, const uint32_t *dst_index, size_t n_max, Count n, size_t dim, int epc,
+// rows of `dim` elements in the family's chunk of `epc` of them (8-element chunks exist where kMaxEpc allows them only)
+template <typename Family, bool SCATTER, typename Rows>
+static int launch_family(char *out, Rows rows, const uint32_t *dst_index, size_t n_max, Count n, size_t dim, int epc,
                          uint64_t *miss_count, hipStream_t stream) {
   const uint64_t rc = dim / epc;
-  if constexpr (convert_max_epc(1, sizeof(typename Elem<DST_DT>::bits)) == 8)
+  if constexpr (Family::kMaxEpc == 8)
     if (epc == 8)
-      return launch_chunks<ScaledChunk<8, DST_DT>, Rows, SCATTER>(out, rows, dst_index, n_max, n, rc, miss_count, stream);
+      return launch_chunks<typename Family::template Chunk<8>, Rows, SCATTER>(out, rows, dst_index, n_max, n, rc, miss_count, stream);
   switch (epc) {
-    case 4: return launch_chunks<ScaledChunk<4, DST_DT>, Rows, SCATTER>(out, rows, dst_index, n_max, n, rc, miss_count, stream);
-    case 2: return launch_chunks<ScaledChunk<2, DST_DT>, Rows, SCATTER>(out, rows, dst_index, n_max, n, rc, miss_count, stream);
-    case 1: return launch_chunks<ScaledChunk<1, DST_DT>, Rows, SCATTER>(out, rows, dst_index, n_max, n, rc, miss_count, stream);
+    case 4: return launch_chunks<typename Family::template Chunk<4>, Rows, SCATTER>(out, rows, dst_index, n_max, n, rc, miss_count, stream);
+    case 2: return launch_chunks<typename Family::template Chunk<2>, Rows, SCATTER>(out, rows, dst_index, n_max, n, rc, miss_count, stream);
+    case 1: return launch_chunks<typename Family::template Chunk<1>, Rows, SCATTER>(out, rows, dst_index, n_max, n, rc, miss_count, stream);
   }
-  set_error("extract: no %d-element chunk for dtype %d -> %d", epc, GGMS_Q8ROW, DST_DT);
+  set_error("extract: no %d-element chunk for dtype %d -> %d", epc, Family::kSrcDt, Family::kDstDt);
   return GGMS_ERR_INVALID;
 }
 
@@ -673,14 +593,14 @@ static int launch_move(char *out, Rows rows, const uint32_t *dst_index, size_t n
       return GGMS_ERR_INVALID;
     }
     switch (m.dst_dt) {
-      case GGMS_F32: return launch_scaled<GGMS_F32, SCATTER>(out, rows, dst_index, n_max, n, m.dim, epc, miss_count, stream);
-      case GGMS_F16: return launch_scaled<GGMS_F16, SCATTER>(out, rows, dst_index, n_max, n, m.dim, epc, miss_count, stream);
-      case GGMS_BF16: return launch_scaled<GGMS_BF16, SCATTER>(out, rows, dst_index, n_max, n, m.dim, epc, miss_count, stream);
+      case GGMS_F32: return launch_family<ScaledFamily<GGMS_F32>, SCATTER>(out, rows, dst_index, n_max, n, m.dim, epc, miss_count, stream);
+      case GGMS_F16: return launch_family<ScaledFamily<GGMS_F16>, SCATTER>(out, rows, dst_index, n_max, n, m.dim, epc, miss_count, stream);
+      case GGMS_BF16: return launch_family<ScaledFamily<GGMS_BF16>, SCATTER>(out, rows, dst_index, n_max, n, m.dim, epc, miss_count, stream);
     }
   }
 #define GGMS_PAIR(S, D)                                                                                              \
   if (m.src_dt == S && m.dst_dt == D)                                                                                \
-    return launch_convert_pair<S, D, SCATTER>(out, rows, dst_index, n_max, n, m.dim, epc, miss_count, stream);
+    return launch_family<ConvertFamily<S, D>, SCATTER>(out, rows, dst_index, n_max, n, m.dim, epc, miss_count, stream);
   GGMS_PAIR(GGMS_F16, GGMS_F32)
   GGMS_PAIR(GGMS_BF16, GGMS_F32)
   GGMS_PAIR(GGMS_F32, GGMS_F16)

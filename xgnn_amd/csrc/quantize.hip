@@ -13,27 +13,11 @@
 //     wave, one pass.  Rows of more than kRegDim elements take k_q8row_long: one wave per row, which reads it twice.
 //   * The encode itself is float64, as quantize_q8row computes it: one subtraction, one correctly rounded division and
 //     one round-half-even per element.
-#include "elem_types.h"
+#include "row_formats.h"
 #include "fp8_encode.h"
 #include "ggms_device.h"
 
 namespace ggms {
-
-// ---- streaming loads and stores (as extract.hip's): non-temporal, on GLOBAL addresses so that the compiler emits
-// global_load / global_store (vmcnt only) instead of flat_* ----------------------------------------------------------
-template <typename V, bool NT>
-__device__ __forceinline__ V load_chunk(uint64_t addr) {
-  typedef const V __attribute__((address_space(1))) *gp_t;
-  gp_t p = (gp_t)addr;
-  if constexpr (NT) return __builtin_nontemporal_load(p);
-  else return *p;
-}
-template <typename V, bool NT>
-__device__ __forceinline__ void store_chunk(uint64_t addr, V v) {
-  typedef V __attribute__((address_space(1))) *gp_t;
-  if constexpr (NT) __builtin_nontemporal_store(v, (gp_t)addr);
-  else *(gp_t)addr = v;
-}
 
 // ---- element encoders: f32 -> the output type's bits --------------------------------------------------------------
 template <int DT> struct Encode {
@@ -48,15 +32,6 @@ template <> struct Encode<GGMS_F8E5M2> {
   using bits = uint8_t;
   static __device__ __forceinline__ bits one(float f) { return f32_to_fp8_e5m2(f); }
 };
-
-template <typename VT, int N> __device__ __forceinline__ auto vec_get(const VT &v, int e) {
-  if constexpr (N == 1) return v;
-  else return v[e];
-}
-template <typename VT, int N, typename T> __device__ __forceinline__ void vec_set(VT &v, int e, T x) {
-  if constexpr (N == 1) v = x;
-  else v[e] = x;
-}
 
 // ---- the elementwise formats ----------------------------------------------------------------------------------------
 constexpr int kElemU = 4; // independent chunk loads per lane before the first store
@@ -100,8 +75,6 @@ __global__ __launch_bounds__(kBlock) void k_encode_elems(char *__restrict__ out,
 // ---- Q8ROW -------------------------------------------------------------------------------------------------------------
 constexpr int kRegElems = 16;      // row values a lane keeps between the reduction and the encode
 constexpr size_t kRegDim = 1024;   // 64 lanes x kRegElems: the longest row k_q8row_rows holds in registers
-
-__host__ __device__ constexpr uint64_t q8row_codes_end(uint64_t dim) { return (dim + 7u) & ~(uint64_t)7u; } // = the trailer
 
 // Finite f32 bits as unsigned keys in the order of their values, -0 below +0: min and max are integer operations, and
 // the minimum of a row whose smallest values are zeros of both signs is -0.0 whatever order the lanes meet them in
@@ -159,10 +132,9 @@ struct RowScale {
 // the row's tail, by one lane: zero pad up to the trailer, {scale, bias}, and a bad row's report
 __device__ __forceinline__ void q8row_finish(uint64_t out_row, uint32_t dim, const RowScale &rs, bool bad, uint64_t row_id,
                                              unsigned long long *bad_row) {
-  const uint32_t trailer = (uint32_t)q8row_codes_end(dim);
+  const uint32_t trailer = (uint32_t)q8row_trailer_offset(dim);
   for (uint32_t i = dim; i < trailer; ++i) store_chunk<uint8_t, true>(out_row + i, (uint8_t)0);
-  typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-  store_chunk<u32x2, true>(out_row + trailer, u32x2{rs.scale_bits, rs.bias_bits});
+  store_chunk<u32x2_t, true>(out_row + trailer, u32x2_t{rs.scale_bits, rs.bias_bits});
   if (bad && bad_row) atomicMin(bad_row, (unsigned long long)row_id);
 }
 
@@ -188,7 +160,7 @@ __global__ __launch_bounds__(kBlock) void k_q8row_rows(char *__restrict__ out, c
   const uint32_t rows_per_wave = (uint32_t)kWave >> group_log2;
   const uint64_t wave = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6, num_waves = (uint64_t)gridDim.x * (kBlock / kWave);
   const uint32_t chunks = dim / V; // whole: V divides dim
-  const uint64_t out_stride = q8row_codes_end(dim) + 8u;
+  const uint64_t out_stride = q8row_stride(dim);
   for (uint64_t r0 = wave * rows_per_wave; r0 < num_rows; r0 += num_waves * rows_per_wave) { // uniform per wave
     const uint64_t row = r0 + sub;
     const bool live = row < num_rows;
@@ -230,7 +202,7 @@ __global__ __launch_bounds__(kBlock) void k_q8row_long(char *__restrict__ out, c
   const uint32_t lane = lane_id();
   const uint64_t wave = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6, num_waves = (uint64_t)gridDim.x * (kBlock / kWave);
   const uint32_t chunks = dim / V;
-  const uint64_t out_stride = q8row_codes_end(dim) + 8u;
+  const uint64_t out_stride = q8row_stride(dim);
   for (uint64_t row = wave; row < num_rows; row += num_waves) {
     const uint64_t src_row = (uint64_t)src + row * dim * ES, out_row = (uint64_t)out + row * out_stride;
     RowRange range;
@@ -253,17 +225,10 @@ __global__ __launch_bounds__(kBlock) void k_q8row_long(char *__restrict__ out, c
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
-// the widest power-of-two count of elements (at most 16 source bytes) that `divides` allows and both bases are aligned to
-static inline int pick_epc(size_t src_es, uintptr_t src, size_t dst_es, uintptr_t dst, size_t divides) {
-  for (int epc = (int)(16 / src_es); epc > 1; epc >>= 1)
-    if (divides % epc == 0 && src % (epc * src_es) == 0 && dst % (epc * dst_es) == 0) return epc;
-  return 1;
-}
-
 template <int SRC_DT, int DST_DT>
 static int launch_encode(char *out, const char *src, uint64_t n, hipStream_t stream) {
   constexpr size_t SES = sizeof(typename Elem<SRC_DT>::bits), DES = sizeof(typename Encode<DST_DT>::bits);
-  const int epc = pick_epc(SES, (uintptr_t)src, DES, (uintptr_t)out, 0); // flat: whole chunks, then single elements
+  const int epc = pick_chunk(0, (int)(16 / SES), SES, (uintptr_t)src, DES, (uintptr_t)out); // flat: whole chunks, then single elements
   const int grid = grid_for(n / epc + 1, (size_t)kBlock * kElemU);
 #define GGMS_EPC(E)                                                                                                   \
   case E:                                                                                                            \
@@ -304,7 +269,7 @@ static int launch_q8row(char *out, const char *src, size_t num_rows, size_t dim,
   constexpr size_t SES = sizeof(typename Elem<SRC_DT>::bits);
   // every row starts dim x SES bytes after the last: a chunk width must divide dim and suit the base.  The codes'
   // side follows: `out` and the row stride are multiples of 8, a chunk of V codes starts at a multiple of V.
-  switch (pick_epc(SES, (uintptr_t)src, 1, 0, dim)) {
+  switch (pick_chunk(dim, (int)(16 / SES), SES, (uintptr_t)src, 1, 0)) {
     case 1: return launch_q8row_v<SRC_DT, 1>(out, src, num_rows, dim, first_row, bad_row, stream);
     case 2: return launch_q8row_v<SRC_DT, 2>(out, src, num_rows, dim, first_row, bad_row, stream);
     case 4: return launch_q8row_v<SRC_DT, 4>(out, src, num_rows, dim, first_row, bad_row, stream);
@@ -320,10 +285,7 @@ using namespace ggms;
 
 extern "C" int ggms_quantize_rows(void *out, int out_dtype, const void *src, int src_dtype, size_t num_rows, size_t dim,
                                   uint64_t first_row, uint64_t *bad_row, ggms_stream_t stream) {
-  const bool src_ok = src_dtype == GGMS_F32 || src_dtype == GGMS_F16;
-  const bool out_ok = out_dtype == GGMS_F16 || out_dtype == GGMS_BF16 || out_dtype == GGMS_F8E4M3 ||
-                      out_dtype == GGMS_F8E5M2 || out_dtype == GGMS_Q8ROW;
-  if (!src_ok || !out_ok || src_dtype == out_dtype || dim == 0) {
+  if (!quantiser_reads(src_dtype) || !quantiser_writes(out_dtype) || src_dtype == out_dtype || dim == 0) {
     set_error("quantize_rows: invalid argument: dtype %d -> %d, dim %zu (the source is F32 or F16, the output another "
               "type of F16, BF16, F8E4M3, F8E5M2 and Q8ROW; rows are not empty)", src_dtype, out_dtype, dim);
     return GGMS_ERR_INVALID;
