@@ -44,7 +44,7 @@ def run_sampler(sam, w, barrier, out_prefix, exit_now):
     sam.shutdown()
 
 
-def run_trainer(sam, w, S, T, barrier, num_layers, out_prefix, mode):
+def run_trainer(sam, w, S, T, barrier, num_layers, out_prefix, mode, record_batch):
     import torch
     barrier.wait()
     sam.train_init(w, f"cuda:{S + w}")
@@ -75,7 +75,8 @@ def run_trainer(sam, w, S, T, barrier, num_layers, out_prefix, mode):
     sam.shutdown()
 
 
-def main():
+def main(record_batch=record_batch):
+    """record_batch(sam, key, num_layers) -> (the batch's .npz entries, the devices of its tensors)."""
     dataset, out_prefix, S, T, mode = sys.argv[1], sys.argv[2], int(sys.argv[3]), int(sys.argv[4]), sys.argv[5]
     assert mode in ("step", "start"), mode
     extra = dict(a.split("=", 1) for a in sys.argv[6:])
@@ -97,7 +98,7 @@ def main():
                 if role == "s":
                     run_sampler(sam, w, barrier, out_prefix, w == exit_sampler)
                 else:
-                    run_trainer(sam, w, S, T, barrier, num_layers, out_prefix, mode)
+                    run_trainer(sam, w, S, T, barrier, num_layers, out_prefix, mode, record_batch)
             except SystemExit as e:
                 code = e.code or 0
             except BaseException as e:  # noqa: BLE001

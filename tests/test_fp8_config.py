@@ -1,43 +1,17 @@
 """FEAT_DATA_TYPE F8E4M3 / F8E5M2 on the host: which configurations config + data_init take (no GPU touched) and which
 they refuse, in the words the refusals had before FP8 tables existed."""
-import os
-import subprocess
-import sys
-
 import pytest
 
-from fp8_common import E4M3, E5M2, write_fp8_dataset
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-BASE = {'_arch': 1, 'sampler_ctx': 'cuda:0', 'trainer_ctx': 'cuda:0', '_sample_type': 0, 'batch_size': 64,
-        'num_epoch': 1, '_cache_policy': 0, 'cache_percentage': 0.0, 'max_sampling_jobs': 1, 'max_copying_jobs': 1,
-        'omp_thread_num': 1, 'num_layer': 2, 'num_hidden': 8, 'lr': 0.1, 'dropout': 0.5, 'num_fanout': 2,
-        'fanout': [5, 4]}
+from config_run import ARCH0, run_config
+from feat_formats import E4M3, E5M2, write_dataset
 
 
 @pytest.fixture(scope="module")
 def datasets(tmp_path_factory):
     root = tmp_path_factory.mktemp("fp8_cfg")
-    return {"F8E4M3": write_fp8_dataset(root / "e4m3", E4M3, 20), "F8E5M2": write_fp8_dataset(root / "e5m2", E5M2, 20)}
+    return {"F8E4M3": write_dataset(root / "e4m3", E4M3, 20), "F8E5M2": write_dataset(root / "e5m2", E5M2, 20)}
 
 
-def _run(path, extra, tail=""):
-    cfg = dict(BASE, dataset_path=path)
-    cfg.update(extra)
-    code = f"""
-import sys; sys.path.insert(0, {ROOT!r})
-import samgraph.torch as sam
-sam.config({cfg!r})
-sam.data_init()
-print('configured', sam.num_class(), sam.feat_dim())
-{tail}
-"""
-    env = {k: v for k, v in os.environ.items() if not k.startswith("SAMGRAPH_")}
-    return subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=env)
-
-
-ARCH0 = dict(_arch=0, sampler_ctx='cpu:0', trainer_ctx='cpu:0')
 ACCEPTED = [("arch1-no-key", "F8E4M3", {}), ("arch0-no-key", "F8E5M2", ARCH0)]
 for _out in ("f32", "f16", "bf16"):
     ACCEPTED += [
@@ -52,7 +26,7 @@ for _out in ("f32", "f16", "bf16"):
 @pytest.mark.parametrize("case", ACCEPTED, ids=[c[0] for c in ACCEPTED])
 def test_fp8_table_accepted(datasets, case):
     _, table, extra = case
-    out = _run(datasets[table]["path"], extra)
+    out = run_config(datasets[table]["path"], extra)
     assert out.returncode == 0, out.stderr[-2000:]
     assert out.stdout.split() == ["configured", "13", "20"]
 
@@ -72,7 +46,7 @@ REFUSED = [
 @pytest.mark.parametrize("case", REFUSED, ids=[c[0] for c in REFUSED])
 def test_fp8_table_refused_in_the_existing_words(datasets, case):
     _, table, extra, words = case
-    out = _run(datasets[table]["path"], extra)
+    out = run_config(datasets[table]["path"], extra)
     assert out.returncode < 0 and "configured" not in out.stdout, out.stderr[-2000:]  # SIGABRT, like every fatal
     assert "feat_out_dtype" in out.stderr, out.stderr[-2000:]
     for w in words:
@@ -88,7 +62,7 @@ import torch
 f = sam.get_dataset_feat()
 print('feat', tuple(f.shape), f.dtype, f.element_size(), f.view(torch.uint8)[:300].flatten().tolist() == EXPECT)
 """.replace("EXPECT", repr(d["feat"][:300].ravel().tolist()))
-    out = _run(d["path"], {}, tail)
+    out = run_config(d["path"], {}, tail)
     assert out.returncode == 0, out.stderr[-2000:]
     name = {"F8E4M3": "torch.float8_e4m3fn", "F8E5M2": "torch.float8_e5m2"}[table]
     assert f"feat (3000, 20) {name} 1 True" in out.stdout, out.stdout

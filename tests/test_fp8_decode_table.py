@@ -6,12 +6,12 @@ import numpy as np
 import pytest
 import torch
 
-from fp8_common import (BF16, E4M3, E5M2, F16, F32, FP8, FP8_NAMES, FP8_TORCH, decode_bits, truth, truth_closed_form,
-                        truth_torch)
-from feat_convert_common import to_f32
+from feat_formats import BF16, E4M3, E5M2, F16, F32, NAMES, TORCH, decode_bits, to_f32, truth, truth_closed_form, truth_torch
+
+FP8 = (E4M3, E5M2)
 
 
-@pytest.mark.parametrize("fmt", FP8, ids=[FP8_NAMES[f] for f in FP8])
+@pytest.mark.parametrize("fmt", FP8, ids=[NAMES[f] for f in FP8])
 def test_truth_table_torch_and_closed_form_agree(fmt):
     a, b = truth_torch(fmt), truth_closed_form(fmt)
     nan_a, nan_b = np.isnan(a), np.isnan(b)
@@ -27,7 +27,7 @@ def test_truth_table_torch_and_closed_form_agree(fmt):
     assert b.view(np.uint32)[0x80] == 0x80000000 and b.view(np.uint32)[0x00] == 0
 
 
-@pytest.mark.parametrize("fmt", FP8, ids=[FP8_NAMES[f] for f in FP8])
+@pytest.mark.parametrize("fmt", FP8, ids=[NAMES[f] for f in FP8])
 def test_every_finite_code_is_exact_in_f16_and_bf16(fmt):
     """So the gather has no rounding mode to choose, and the GPU tests may compare bitwise."""
     t = truth(fmt)
@@ -64,7 +64,7 @@ def test_quantize_features_round_trip(tmp_path, src):
     g = dict(indptr=ip, indices=ix, train_set=np.arange(50, dtype=np.uint32), meta=dict(feat_dim=dim, num_class=3))
     d_in = datagen.write_dataset(str(tmp_path / "in"), g, feat=feat, label=np.zeros(n, np.int64), feat_dtype=src)
     for fmt in FP8:
-        d_out = datagen.quantize_features(d_in, str(tmp_path / FP8_NAMES[fmt]), FP8_NAMES[fmt])
+        d_out = datagen.quantize_features(d_in, str(tmp_path / NAMES[fmt]), NAMES[fmt])
         q = np.fromfile(os.path.join(d_out, "feat.bin"), np.uint8).reshape(n, dim)
         vals = truth(fmt)[q]
         want = torch.from_numpy(feat.astype(np.float32))
@@ -78,10 +78,10 @@ def test_quantize_features_round_trip(tmp_path, src):
         assert vals[0, 3] == 0 and np.signbit(vals[0, 3])
         assert vals[1, :4].tolist() == [0.5, 3.0, -1.75, 2.0 ** -6]
         # the table is torch's round-to-nearest-even cast of the (clamped) values
-        assert np.array_equal(q, want.to(FP8_TORCH[fmt]).view(torch.uint8).numpy())
+        assert np.array_equal(q, want.to(TORCH[fmt]).view(torch.uint8).numpy())
         with open(os.path.join(d_out, "meta.txt")) as f:
             meta = dict(line.split() for line in f)
-        assert meta["FEAT_DATA_TYPE"] == FP8_NAMES[fmt] and meta["NUM_NODE"] == str(n) and meta["FEAT_DIM"] == str(dim)
+        assert meta["FEAT_DATA_TYPE"] == NAMES[fmt] and meta["NUM_NODE"] == str(n) and meta["FEAT_DIM"] == str(dim)
         for name in ("indptr.bin", "indices.bin", "train_set.bin", "label.bin", "cache_by_degree.bin"):
             with open(os.path.join(d_in, name), "rb") as a, open(os.path.join(d_out, name), "rb") as b:
                 assert a.read() == b.read(), name
@@ -94,10 +94,10 @@ def test_write_dataset_takes_fp8_tensors_and_bytes(tmp_path):
     g = dict(indptr=ip, indices=ix, train_set=np.arange(8, dtype=np.uint32), meta=dict(feat_dim=4, num_class=3))
     b = np.arange(160, dtype=np.uint8).reshape(40, 4)
     for fmt in FP8:
-        for how, feat in (("tensor", torch.from_numpy(b).view(FP8_TORCH[fmt])), ("bytes", b)):
-            d = datagen.write_dataset(str(tmp_path / f"{FP8_NAMES[fmt]}{how}"), g, feat=feat, feat_dtype=FP8_NAMES[fmt])
+        for how, feat in (("tensor", torch.from_numpy(b).view(TORCH[fmt])), ("bytes", b)):
+            d = datagen.write_dataset(str(tmp_path / f"{NAMES[fmt]}{how}"), g, feat=feat, feat_dtype=NAMES[fmt])
             assert np.array_equal(np.fromfile(os.path.join(d, "feat.bin"), np.uint8), b.ravel())
             with open(os.path.join(d, "meta.txt")) as f:
-                assert f"FEAT_DATA_TYPE\t{FP8_NAMES[fmt]}\n" in f.read()
+                assert f"FEAT_DATA_TYPE\t{NAMES[fmt]}\n" in f.read()
     with pytest.raises(AssertionError):
         datagen.write_dataset(str(tmp_path / "bad"), g, feat=b.astype(np.float32), feat_dtype="F8E4M3")

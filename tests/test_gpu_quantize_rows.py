@@ -7,9 +7,8 @@ import numpy as np
 import pytest
 import torch
 
-from feat_convert_common import BF16, F16, F32, assert_same_bits, from_f32, tensor_bits
-from q8row_common import Table, stride
-from quantize_common import FP8, assert_fp8_bytes, cpu_q8row, write_finite_dataset
+from feat_formats import (BF16, CODES, F16, F32, TORCH, assert_bits, assert_fp8_bytes, cpu_q8row, from_f32, q8row_table, stride,
+                          tensor_bits, write_finite_dataset)
 from xgnn_amd import datagen, ops
 from xgnn_amd._lib import GgmsError
 
@@ -26,7 +25,7 @@ def _gpu_bytes(t):
 @pytest.mark.parametrize("fmt", ["F8E4M3", "F8E5M2"])
 def test_fp8_from_every_f16(fmt):
     half = np.arange(65536, dtype=np.uint16).view(np.float16).reshape(512, 128)
-    got = _gpu_bytes(ops.quantize_rows(torch.from_numpy(half).to(DEV), FP8[fmt]))
+    got = _gpu_bytes(ops.quantize_rows(torch.from_numpy(half).to(DEV), TORCH[CODES[fmt]]))
     assert_fp8_bytes(got, half.astype(np.float32), fmt, f"f16 -> {fmt}")
 
 
@@ -43,7 +42,7 @@ def _edge_table(codes):
 
 
 def _all_codes(dt):
-    if dt in FP8.values():
+    if dt.itemsize == 1:
         return torch.arange(256, dtype=torch.uint8).view(dt).float().numpy()
     bits = np.random.RandomState(11).randint(0, 1 << 16, 4096).astype(np.int16)
     return torch.from_numpy(bits).view(dt).float().numpy()
@@ -51,23 +50,23 @@ def _all_codes(dt):
 
 @pytest.mark.parametrize("fmt", ["F8E4M3", "F8E5M2"])
 def test_fp8_from_f32_codes_ties_and_edges(fmt):
-    v = _edge_table(_all_codes(FP8[fmt]))
-    got = _gpu_bytes(ops.quantize_rows(torch.from_numpy(v).to(DEV), FP8[fmt]))
+    v = _edge_table(_all_codes(TORCH[CODES[fmt]]))
+    got = _gpu_bytes(ops.quantize_rows(torch.from_numpy(v).to(DEV), TORCH[CODES[fmt]]))
     assert_fp8_bytes(got, v, fmt, f"f32 -> {fmt}")
 
 
 @pytest.mark.parametrize("dt", [F16, BF16], ids=["F16", "BF16"])
 def test_16_bit_from_f32_codes_ties_and_edges(dt):
-    tdt = {F16: torch.float16, BF16: torch.bfloat16}[dt]
+    tdt = TORCH[dt]
     v = _edge_table(_all_codes(tdt))
     got = tensor_bits(ops.quantize_rows(torch.from_numpy(v).to(DEV), tdt), dt)
-    assert_same_bits(got, tensor_bits(torch.from_numpy(v).to(tdt), dt), dt, f"f32 -> {tdt}")
+    assert_bits(got, tensor_bits(torch.from_numpy(v).to(tdt), dt), np.isnan(v), f"f32 -> {tdt}", dt=dt)
 
 
 def test_bf16_from_every_f16():
     half = np.arange(65536, dtype=np.uint16).view(np.float16).reshape(512, 128)
     got = tensor_bits(ops.quantize_rows(torch.from_numpy(half).to(DEV), torch.bfloat16), BF16)
-    assert_same_bits(got, from_f32(half.astype(np.float32), BF16), BF16, "f16 -> bf16")
+    assert_bits(got, from_f32(half.astype(np.float32), BF16), np.isnan(half), "f16 -> bf16", dt=BF16)
 
 
 def test_flat_tail_and_misaligned_bases():
@@ -163,12 +162,12 @@ def test_q8row_bad_rows():
 
 
 def test_q8row_round_trip_through_the_gather():
-    """The gather's decode of the GPU-made table is q8row_common's decode of the CPU-made one."""
-    v = _q8row_rows(300, 20, np.float32, seed=9)[13:] * np.float32(1e-3)  # (q8row_common wants scales of 0 or >= 2^-100)
+    """The gather's decode of the GPU-made table is feat_formats' decode of the CPU-made one."""
+    v = _q8row_rows(300, 20, np.float32, seed=9)[13:] * np.float32(1e-3)  # (q8row_table wants scales of 0 or >= 2^-100)
     v = v[np.abs(v).max(axis=1) < 1e30]
     codes, scale, bias = datagen.quantize_q8row(v)
     keep = (scale == 0) | (scale >= 2.0 ** -100)
-    v, table = v[keep], Table(codes[keep], scale[keep], bias[keep])
+    v, table = v[keep], q8row_table(codes[keep], scale[keep], bias[keep])
     q = ops.quantize_rows(torch.from_numpy(np.ascontiguousarray(v)).to(DEV), ops.Q8ROW)
     out = torch.empty((v.shape[0], 20), dtype=torch.float32, device=DEV)
     ops.gather_scatter_convert(out, q, None, None, num=v.shape[0], src_dtype=ops.Q8ROW)

@@ -2,43 +2,19 @@
 a row-scaled table NEEDS feat_out_dtype; with the key the refusals are the ones every converting table gets, in their
 words -- and what the engine sizes: a table of rows x stride bytes, a batch buffer of dim x batch dtype."""
 import os
-import subprocess
-import sys
 
 import pytest
 
-from q8row_common import stride, write_q8row_dataset
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-BASE = {'_arch': 1, 'sampler_ctx': 'cuda:0', 'trainer_ctx': 'cuda:0', '_sample_type': 0, 'batch_size': 64,
-        'num_epoch': 1, '_cache_policy': 0, 'cache_percentage': 0.0, 'max_sampling_jobs': 1, 'max_copying_jobs': 1,
-        'omp_thread_num': 1, 'num_layer': 2, 'num_hidden': 8, 'lr': 0.1, 'dropout': 0.5, 'num_fanout': 2,
-        'fanout': [5, 4]}
+from config_run import ARCH0, run_config
+from feat_formats import Q8ROW, stride, write_dataset
 
 
 @pytest.fixture(scope="module")
 def datasets(tmp_path_factory):
     root = tmp_path_factory.mktemp("q8row_cfg")
-    return {dim: write_q8row_dataset(root / f"q8x{dim}", dim) for dim in (20, 128)}
+    return {dim: write_dataset(root / f"q8x{dim}", Q8ROW, dim) for dim in (20, 128)}
 
 
-def _run(path, extra, tail=""):
-    cfg = dict(BASE, dataset_path=path)
-    cfg.update(extra)
-    code = f"""
-import sys; sys.path.insert(0, {ROOT!r})
-import samgraph.torch as sam
-sam.config({cfg!r})
-sam.data_init()
-print('configured', sam.num_class(), sam.feat_dim())
-{tail}
-"""
-    env = {k: v for k, v in os.environ.items() if not k.startswith("SAMGRAPH_")}
-    return subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=env)
-
-
-ARCH0 = dict(_arch=0, sampler_ctx='cpu:0', trainer_ctx='cpu:0')
 ARCH6 = dict(_arch=6, num_worker=1, cache_percentage=0.25, gpu_extract="True")
 NO_KEY = [("arch1", {}), ("arch0", ARCH0), ("arch3", dict(_arch=3, trainer_ctx='cuda:1')), ("arch6-gpu-extract", ARCH6),
           ("arch4-dynamic-cache", dict(_arch=4, sampler_ctx='cuda:1', _cache_policy=6))]
@@ -46,7 +22,7 @@ NO_KEY = [("arch1", {}), ("arch0", ARCH0), ("arch3", dict(_arch=3, trainer_ctx='
 
 @pytest.mark.parametrize("case", NO_KEY, ids=[c[0] for c in NO_KEY])
 def test_q8row_table_without_feat_out_dtype_is_fatal(datasets, case):
-    out = _run(datasets[20]["path"], case[1])
+    out = run_config(datasets[20]["path"], case[1])
     assert out.returncode < 0 and "configured" not in out.stdout, out.stderr[-2000:]  # SIGABRT, like every fatal
     assert "feat_out_dtype" in out.stderr and "Q8ROW" in out.stderr, out.stderr[-2000:]
 
@@ -63,7 +39,7 @@ REFUSED = [
 @pytest.mark.parametrize("case", REFUSED, ids=[c[0] for c in REFUSED])
 def test_q8row_table_refused_in_the_existing_words(datasets, case):
     _, extra, words = case
-    out = _run(datasets[20]["path"], extra)
+    out = run_config(datasets[20]["path"], extra)
     assert out.returncode < 0 and "configured" not in out.stdout, out.stderr[-2000:]
     assert "feat_out_dtype" in out.stderr, out.stderr[-2000:]
     for w in words:
@@ -88,8 +64,8 @@ import torch
 f = sam.get_dataset_feat()
 print('feat', tuple(f.shape), f.dtype, f.numel() * f.element_size(), f[:40].flatten().tolist() == EXPECT)
 print('row bytes', sam.feat_row_bytes(), sam.feat_row_bytes(delivered=True))
-""".replace("EXPECT", repr(d["table"].rows[:40].ravel().tolist()))
-    out = _run(d["path"], extra, tail)
+""".replace("EXPECT", repr(d["table"].stored[:40].ravel().tolist()))
+    out = run_config(d["path"], extra, tail)
     assert out.returncode == 0, out.stderr[-2000:]
     assert out.stdout.split()[:3] == ["configured", "13", str(dim)]
     assert f"feat (3000, {stride(dim)}) torch.uint8 {3000 * stride(dim)} True" in out.stdout, out.stdout
@@ -104,5 +80,5 @@ def test_a_table_one_byte_short_of_rows_x_stride_is_refused(datasets, tmp_path):
     shutil.copytree(datasets[20]["path"], short)
     with open(short / "feat.bin", "r+b") as f:
         f.truncate(3000 * stride(20) - 1)
-    out = _run(str(short), dict(feat_out_dtype='f32'))
+    out = run_config(str(short), dict(feat_out_dtype='f32'))
     assert out.returncode < 0 and "feat.bin" in out.stderr and "smaller" in out.stderr, out.stderr[-2000:]

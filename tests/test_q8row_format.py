@@ -5,7 +5,7 @@ import os
 import numpy as np
 import pytest
 
-from q8row_common import Q8ROW, stride
+from feat_formats import Q8ROW, stride
 
 
 def test_pack_unpack_round_trip():

@@ -3,16 +3,14 @@ and refuses what it must before it launches anything; datagen.quantize_features(
 wrote; and config + data_init refuse the key wherever the engine cannot quantise, naming the key and the reason."""
 import ctypes as C
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import xgnn_amd
-from feat_convert_common import F16, F32, write_feat_dataset
-from quantize_common import cpu_fp8, cpu_q8row, write_finite_dataset
+from config_run import ARCH0, run_config
+from feat_formats import F16, F32, cpu_fp8, cpu_q8row, write_dataset, write_finite_dataset
 from xgnn_amd import _lib, datagen
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -61,7 +59,7 @@ def test_valid_call_without_a_gpu_is_a_hip_error(out_dt):
 def datasets(tmp_path_factory):
     root = tmp_path_factory.mktemp("quantize_host")
     return {"f32": write_finite_dataset(root / "f32x20", F32, 20), "f16": write_finite_dataset(root / "f16x128", F16, 128),
-            "raw": write_feat_dataset(root / "raw_f32x20", F32, 20)}
+            "raw": write_dataset(root / "raw_f32x20", F32, 20)}
 
 
 @pytest.mark.parametrize("name,fmt", [("f32", "Q8ROW"), ("f16", "Q8ROW"), ("raw", "F8E4M3"), ("raw", "F8E5M2"), ("f16", "F8E4M3")])
@@ -82,25 +80,6 @@ def test_cpu_path_keeps_its_three_formats(datasets, tmp_path):
 
 
 # ---- config + data_init: tests/test_q8row_config.py's mechanism ------------------------------------------------------
-BASE = {'_arch': 1, 'sampler_ctx': 'cuda:0', 'trainer_ctx': 'cuda:0', '_sample_type': 0, 'batch_size': 64,
-        'num_epoch': 1, '_cache_policy': 0, 'cache_percentage': 0.0, 'max_sampling_jobs': 1, 'max_copying_jobs': 1,
-        'omp_thread_num': 1, 'num_layer': 2, 'num_hidden': 8, 'lr': 0.1, 'dropout': 0.5, 'num_fanout': 2,
-        'fanout': [5, 4]}
-
-
-def _run(path, extra, env_extra=None):
-    cfg = dict(BASE, dataset_path=path)
-    cfg.update(extra)
-    code = f"""
-import sys; sys.path.insert(0, {ROOT!r})
-import samgraph.torch as sam
-sam.config({cfg!r})
-sam.data_init()
-print('configured', sam.num_class(), sam.feat_dim())
-"""
-    env = {k: v for k, v in os.environ.items() if not k.startswith("SAMGRAPH_")}
-    env.update(env_extra or {})
-    return subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=env)
 
 
 @pytest.fixture(scope="module")
@@ -117,7 +96,6 @@ def cfg_datasets(datasets, tmp_path_factory):
     return out
 
 
-ARCH0 = dict(_arch=0, sampler_ctx='cpu:0', trainer_ctx='cpu:0')
 REFUSED = [
     ("arch0", "f32", dict(ARCH0, feat_store_dtype="F8E4M3"), None, ["arch0", "GPU"]),
     ("arch5", "f32", dict(_arch=5, num_sample_worker=1, num_train_worker=1, feat_store_dtype="F8E4M3"), None, ["arch5", "fork"]),
@@ -137,7 +115,7 @@ REFUSED = [
 @pytest.mark.parametrize("case", REFUSED, ids=[c[0] for c in REFUSED])
 def test_feat_store_dtype_refused_by_key_and_reason(cfg_datasets, case):
     _, name, extra, env, words = case
-    out = _run(cfg_datasets[name]["path"], extra, env)
+    out = run_config(cfg_datasets[name]["path"], extra, env_extra=env)
     assert out.returncode < 0 and "configured" not in out.stdout, (out.stdout, out.stderr[-2000:])  # SIGABRT, like every fatal
     assert "feat_store_dtype" in out.stderr, out.stderr[-2000:]
     for w in words:
@@ -147,7 +125,7 @@ def test_feat_store_dtype_refused_by_key_and_reason(cfg_datasets, case):
 @pytest.mark.parametrize("arch", [dict(), dict(_arch=3, trainer_ctx='cuda:1'), dict(_arch=4, sampler_ctx='cuda:1')],
                          ids=["arch1", "arch3", "arch4"])
 def test_q8row_store_without_feat_out_dtype_dies_in_the_existing_words(cfg_datasets, arch):
-    out = _run(cfg_datasets["f32"]["path"], dict(arch, feat_store_dtype="Q8ROW"))
+    out = run_config(cfg_datasets["f32"]["path"], dict(arch, feat_store_dtype="Q8ROW"))
     assert out.returncode < 0 and "configured" not in out.stdout, out.stderr[-2000:]
     assert "FEAT_DATA_TYPE Q8ROW needs the config key feat_out_dtype (f32 | f16 | bf16)" in out.stderr, out.stderr[-2000:]
 
@@ -162,5 +140,5 @@ ACCEPTED = [("arch1-q8row", "f32", dict(feat_store_dtype="Q8ROW", feat_out_dtype
 def test_feat_store_dtype_accepted_on_the_host(cfg_datasets, case):
     """config + data_init touch no GPU: the table is still the one on disk, quantised when the trainer GPU is set up."""
     _, name, extra = case
-    out = _run(cfg_datasets[name]["path"], extra)
+    out = run_config(cfg_datasets[name]["path"], extra)
     assert out.returncode == 0 and out.stdout.split()[:1] == ["configured"], out.stderr[-2000:]
