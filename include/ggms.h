@@ -519,11 +519,14 @@ int ggms_gather_scatter_partition(void *out, const void *const *parts,
 /* One-pass replacement of GetMissCacheIndex + GPUExtractMissData +
  * CombineCacheData (dist_loops.cc:1209-1285): out[i,:] = table[nodes[i]] ==
  * kEmptyKey ? host_feat[nodes[i],:] : parts[slot % P][slot / P,:].
- * num_part == 0 -> single cache array parts[0].  Also counts misses.  parts: HOST array, as above.
+ * num_part == 0 -> single cache array parts[0].  parts: HOST array, as above.
+ * num_miss_dev (optional, a zeroed uint64): with a table, the rows read from host_feat are ADDED to it (two calls
+ * leave the sum of both); num_nodes_dev, where given, bounds what is counted as it bounds what is gathered.
  * table == NULL: the whole feature table is cached and kept in NODE order (slot = node id):
  * out[i,:] = parts[node % P][node / P,:] with no table read and no miss tier -- the layout of a full cache
- * is not observable through the reference's interface, and the gather loses one dependent random read per row.
- * The same convention holds for ggms_owner_histogram. */
+ * is not observable through the reference's interface, and the gather loses one dependent random read per row;
+ * *num_miss_dev is then SET to 0, whatever it held.
+ * The same convention (slot = node id) holds for ggms_owner_histogram. */
 int ggms_extract_cached(void *out, const ggms_id_t *nodes, size_t num_nodes,
                         const uint64_t *num_nodes_dev, const ggms_id_t *table,
                         const void *const *parts, uint32_t num_part,

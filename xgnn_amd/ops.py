@@ -268,18 +268,37 @@ def mock_extract(src, index, mock_bits, out=None):
     return out
 
 
-def get_miss_cache_index(table, nodes):
-    """GetMissCacheIndex (cuda_cache_manager_device.cu:355-441).  Counts stay on the device."""
+def count_nodes(freq, nodes, num=None, num_dev=None):
+    """The presample ranking's counter (dist/pre_sampler.cc:79-111): freq[nodes[i]] += 1 for i < num (freq: int32, one
+    word per node).  With num_dev (device int64[1]) num is an upper bound."""
     _require_gpu(nodes)
-    n = nodes.numel()
+    _i32(nodes)
+    n = nodes.numel() if num is None else int(num)
+    check(lib().ggms_count_nodes(_ptr(freq), _ptr(nodes), n, _ptr(num_dev), _stream()), "ggms_count_nodes")
+    return freq
+
+
+def get_miss_cache_index(table, nodes, num=None, num_dev=None, outs=None):
+    """GetMissCacheIndex (cuda_cache_manager_device.cu:355-441).  Counts stay on the device.  With num_dev (device
+    int64[1]) the batch size is read on the device and num is its upper bound: it sizes the launch, the four index
+    arrays and the workspace (ggms_get_miss_cache_index_dev).  outs (optional): the caller's four int32 index arrays
+    (miss src, miss dst, hit src, hit dst) of at least num entries each."""
+    _require_gpu(nodes)
+    n = nodes.numel() if num is None else int(num)
     dev = nodes.device
-    outs = [torch.empty(max(1, n), dtype=torch.int32, device=dev) for _ in range(4)]
+    if outs is None:
+        outs = [torch.empty(max(1, n), dtype=torch.int32, device=dev) for _ in range(4)]
+    assert len(outs) == 4 and all(_i32(o).numel() >= n for o in outs)
     num_miss = torch.zeros(1, dtype=torch.int64, device=dev)
     num_hit = torch.zeros(1, dtype=torch.int64, device=dev)
     ws = _workspace(lib().ggms_cache_index_workspace_bytes(n), dev)
-    check(lib().ggms_get_miss_cache_index(_ptr(table), _ptr(nodes), n, _ptr(outs[0]), _ptr(outs[1]), _ptr(num_miss),
-                                          _ptr(outs[2]), _ptr(outs[3]), _ptr(num_hit), _ptr(ws), ws.numel() * 4,
-                                          _stream()), "ggms_get_miss_cache_index")
+    tail = (_ptr(outs[0]), _ptr(outs[1]), _ptr(num_miss), _ptr(outs[2]), _ptr(outs[3]), _ptr(num_hit), _ptr(ws),
+            ws.numel() * 4, _stream())
+    if num_dev is None:
+        check(lib().ggms_get_miss_cache_index(_ptr(table), _ptr(nodes), n, *tail), "ggms_get_miss_cache_index")
+    else:
+        check(lib().ggms_get_miss_cache_index_dev(_ptr(table), _ptr(nodes), n, _ptr(num_dev), *tail),
+              "ggms_get_miss_cache_index_dev")
     return outs[0], outs[1], num_miss, outs[2], outs[3], num_hit
 
 
