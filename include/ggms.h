@@ -186,7 +186,8 @@ enum ggms_sample_type {
   GGMS_WEIGHTED_KHOP_PREFIX = 4,
   GGMS_KHOP2 = 5,
   GGMS_WEIGHTED_KHOP_HASH_DEDUP = 6,
-  GGMS_KHOP3 = 7
+  GGMS_KHOP3 = 7,
+  GGMS_KHOP_LABOR = 8 /* an extension: ggms_sample_khop_labor below */
 };
 
 /* Workspace of every leaf sampler below but random walk, whose size depends on
@@ -207,6 +208,27 @@ int ggms_sample_khop0(const ggms_graph_t *graph, const ggms_id_t *input,
                       ggms_id_t *out_dst, uint64_t *num_out_dev,
                       void *workspace, size_t workspace_bytes,
                       ggms_stream_t stream);
+
+/* khop_labor (an extension; the reference has no such sampler): fixed-fanout LABOR / bottom-k sampling.  The random
+ * variate belongs to the NODE: every seed of a layer that could pick neighbour t sees the same number for t, so seeds
+ * with overlapping lists pick overlapping neighbours and a batch touches fewer distinct nodes; each seed on its own
+ * still gets a uniform sample without replacement (khop0's / khop3's marginal).
+ *   fmix32(x)   MurmurHash3's 32-bit finaliser: x ^= x >> 16; x *= 0x85ebca6b; x ^= x >> 13; x *= 0xc2b2ae35;
+ *               x ^= x >> 16 (mod 2^32)
+ *   key         position p of the seed's list t_0 .. t_{d-1} (global ids, CSR order) has the 64-bit key
+ *               (fmix32(t_p ^ layer_salt) << 32) | p; equal ids (multi-edges) tie on the hash and break by position
+ *   selected    the min(fanout, d) positions with the smallest keys; seeds in input order, within a seed ascending
+ *               position (d <= fanout: the whole list in order); duplicate seeds get the same neighbours
+ * No RNG pool and no state: the output is a pure function of (graph, input, fanout, layer_salt).  Sharded graphs are
+ * read like khop0's.  fanout 1 .. 127; 128 and more is an argument error (GGMS_ERR_INVALID).
+ * Workspace: ggms_sample_workspace_bytes(GGMS_KHOP_LABOR, ...).
+ * In ggms_sample_batch, layer i uses layer_salt = fmix32(labor_salt + 0x9e3779b9 * (i + 1)) with the batch's
+ * ggms_sample_extra_t.labor_salt (extra == NULL: 0); states may be NULL, rng_wait / rng_done are ignored. */
+int ggms_sample_khop_labor(const ggms_graph_t *graph, const ggms_id_t *input,
+                           size_t num_input, size_t fanout, uint32_t layer_salt,
+                           ggms_id_t *out_src, ggms_id_t *out_dst,
+                           uint64_t *num_out_dev, void *workspace,
+                           size_t workspace_bytes, ggms_stream_t stream);
 
 /* GPUSampleWeightedKHopPrefix, cuda/cuda_sampling_weighted_khop_prefix.cu:145-246:
  * prob_prefix_table = per-list inclusive prefix sums of the edge weights; one
@@ -349,7 +371,7 @@ int ggms_map_edges(const ggms_hashtable_t *ht, const ggms_id_t *global_src,
  * index of each key's first occurrence, not local ids (the ids are in row / n2o),
  * so ggms_map_edges on it is meaningless until the next fill after a reset.
  * ------------------------------------------------------------------------- */
-/* per-sample-type extras of ggms_sample_batch (NULL for khop0/khop3) */
+/* per-sample-type extras of ggms_sample_batch (NULL for khop0/khop3; khop_labor: NULL = batch salt 0) */
 typedef struct {
   const float *prob_table;        /* weighted_khop[_hash_dedup]: dataset->prob_table (engine.cc:372-384);
                                      weighted_khop_prefix: dataset->prob_prefix_table, alias_table NULL */
@@ -381,7 +403,8 @@ typedef struct {
    * first is told so through `lost`, like any other beaten candidate), the other samplers use one small launch.
    * Results are identical to the general path for distinct seeds; with duplicated seeds they are undefined. */
   uint32_t seeds_distinct;
-  uint32_t _pad;
+  /* khop_labor: the batch salt (it took the place of the struct's trailing pad word: same layout, same size) */
+  uint32_t labor_salt;
 } ggms_sample_extra_t;
 
 /* events for the ordering above (thin hipEvent_t handles, timing disabled) */

@@ -24,7 +24,7 @@ class SampleExtra(C.Structure):
     _fields_ = [("prob_table", C.c_void_p), ("alias_table", C.c_void_p), ("random_walk_length", C.c_size_t),
                 ("random_walk_restart_prob", C.c_double), ("num_random_walk", C.c_size_t), ("data", C.c_void_p),
                 ("rng_wait", C.c_void_p), ("rng_done", C.c_void_p), ("heavy_wait", C.c_void_p),
-                ("seeds_distinct", C.c_uint32), ("_pad", C.c_uint32)]
+                ("seeds_distinct", C.c_uint32), ("labor_salt", C.c_uint32)]
 
 
 class FeatureTiers(C.Structure):
@@ -91,6 +91,7 @@ SYMBOLS = {
     "ggms_sample_workspace_bytes": (_sz, [_i, _sz, _sz]),
     "ggms_sample_khop3": (_i, [C.POINTER(Graph), _vp, _sz, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "ggms_sample_khop0": (_i, [C.POINTER(Graph), _vp, _sz, _sz, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ggms_sample_khop_labor": (_i, [C.POINTER(Graph), _vp, _sz, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ggms_sample_khop1": (_i, [C.POINTER(Graph), _vp, _sz, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "ggms_sample_khop2": (_i, [C.POINTER(Graph), _vp, _sz, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "ggms_sample_weighted_workspace_bytes": (_sz, [_sz, _sz]),

@@ -10,6 +10,7 @@ from . import _lib
 # ---- enum mirrors (common/__init__.py:40-76, common.h:38-95) ----------------------------------
 kCPU, kMMAP, kGPU = 0, 1, 2
 kKHop0, kKHop1, kWeightedKHop, kRandomWalk, kWeightedKHopPrefix, kKHop2, kWeightedKHopHashDedup, kKHop3 = range(8)
+kKHopLabor = 8  # an extension: fixed-fanout LABOR sampling (include/ggms.h, GGMS_KHOP_LABOR)
 kArch0, kArch1, kArch2, kArch3, kArch4, kArch5, kArch6, kArch7 = range(8)
 (kCacheByDegree, kCacheByHeuristic, kCacheByPreSample, kCacheByDegreeHop, kCacheByPreSampleStatic,
  kCacheByFakeOptimal, kDynamicCache, kCacheByRandom) = range(8)
@@ -26,7 +27,7 @@ def gpu(device_id=0):
 sample_types = {
     'khop0': kKHop0, 'khop1': kKHop1, 'khop2': kKHop2, 'khop3': kKHop3, 'random_walk': kRandomWalk,
     'weighted_khop': kWeightedKHop, 'weighted_khop_prefix': kWeightedKHopPrefix,
-    'weighted_khop_hash_dedup': kWeightedKHopHashDedup,
+    'weighted_khop_hash_dedup': kWeightedKHopHashDedup, 'khop_labor': kKHopLabor,
 }
 builtin_archs = {
     'arch0': {'arch': kArch0, 'sampler_ctx': cpu(), 'trainer_ctx': gpu(0)},

@@ -2,6 +2,7 @@
 // /root/reference/samgraph/common/.
 #include "engine.h"
 #include "team.h"
+#include "../labor_hash.h"
 #include "../row_formats.h"
 
 #include <fcntl.h>
@@ -226,7 +227,12 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
     cfg.lookahead = 0;
     cfg.pipelines = 1;
   }
-  SAM_CHECK(cfg.sample_type >= GGMS_KHOP0 && cfg.sample_type <= GGMS_KHOP3, "unknown sample type");
+  SAM_CHECK(cfg.sample_type >= GGMS_KHOP0 && cfg.sample_type <= GGMS_KHOP_LABOR, "unknown sample type");
+  if (cfg.sample_type == GGMS_KHOP_LABOR && cfg.arch == kArch0)
+    fatal(__FILE__, __LINE__, "arch0: _sample_type 8 (khop_labor) is not supported: the CPU engine has no sampler for "
+                              "it; it samples with khop0 or khop2");
+  // khop_labor's batch salts: taken here, once, so that every process forked from this one derives the same salts
+  cfg.labor_seed = cfg.has_seed ? cfg.seed : (uint64_t)std::chrono::system_clock::now().time_since_epoch().count();
   if (kv.count("feat_out_dtype")) { // extension: deliver the batch's rows in this dtype, converted by the gather itself
     static const std::map<std::string, int> names = {{"f32", GGMS_F32}, {"f16", GGMS_F16}, {"bf16", GGMS_BF16}};
     const std::string v = kv["feat_out_dtype"];
@@ -886,17 +892,22 @@ void Engine::SampleInit(int worker_id, const std::string &ctx) {
   extra_.random_walk_restart_prob = cfg.random_walk_restart_prob;
   extra_.num_random_walk = cfg.num_random_walk;
   // GPURandomStates dist_engine.cc:432-433; seed = wall clock unless the "seed" key is given
-  num_states_ = ggms_random_states_count(cfg.sample_type, cfg.fanout.data(), L, max_seeds_, cfg.num_random_walk);
-  size_t max_in = 0;
-  for (auto v : max_input_) max_in = std::max(max_in, v);
-  num_states_ = std::max(num_states_, (max_in + 127) / 128 * 8);
-  num_states_ = std::max(num_states_, (max_in + 1023) / 1024 * 256); // khop2: one stream per thread of a 1024-seed tile
-  if (cfg.sample_type == GGMS_RANDOM_WALK)
-    num_states_ = std::max(num_states_, ggms_random_walk_num_states(max_in, cfg.num_random_walk));
-  SAM_HIP(hipMalloc(&states_, num_states_ * GGMS_RNG_STATE_BYTES));
-  const uint64_t seed = cfg.has_seed ? cfg.seed + 1000003ull * worker_id
-                                     : (uint64_t)std::chrono::system_clock::now().time_since_epoch().count();
-  SAM_GGMS(ggms_random_states_init(states_, num_states_, seed, stream_));
+  if (cfg.sample_type == GGMS_KHOP_LABOR) { // stateless: its variates are hashes of (node id, salt) -- no RNG pool
+    num_states_ = 0;
+    states_ = nullptr;
+  } else {
+    num_states_ = ggms_random_states_count(cfg.sample_type, cfg.fanout.data(), L, max_seeds_, cfg.num_random_walk);
+    size_t max_in = 0;
+    for (auto v : max_input_) max_in = std::max(max_in, v);
+    num_states_ = std::max(num_states_, (max_in + 127) / 128 * 8);
+    num_states_ = std::max(num_states_, (max_in + 1023) / 1024 * 256); // khop2: one stream per thread of a 1024-seed tile
+    if (cfg.sample_type == GGMS_RANDOM_WALK)
+      num_states_ = std::max(num_states_, ggms_random_walk_num_states(max_in, cfg.num_random_walk));
+    SAM_HIP(hipMalloc(&states_, num_states_ * GGMS_RNG_STATE_BYTES));
+    const uint64_t seed = cfg.has_seed ? cfg.seed + 1000003ull * worker_id
+                                       : (uint64_t)std::chrono::system_clock::now().time_since_epoch().count();
+    SAM_GGMS(ggms_random_states_init(states_, num_states_, seed, stream_));
+  }
   ws_bytes_ = cfg.arch == kArch4 ? ggms_sample_batch_prefetch_workspace_bytes(cfg.sample_type, max_seeds_, cfg.fanout.data(),
                                                                           L, &extra_, max_prefetch_edges_)
                                  : ggms_sample_batch_workspace_bytes(cfg.sample_type, max_seeds_, cfg.fanout.data(), L, &extra_);
@@ -1015,6 +1026,7 @@ void Engine::Presample() {
       ggms_sample_extra_t extra = extra_;
       extra.data = dat.data();
       extra.seeds_distinct = train_distinct_ ? 1u : 0u; // slices of a permutation of the train set
+      extra.labor_salt = ggms::labor_batch_salt(cfg.labor_seed, e, s); // the training rule, on the presample's own epochs
       // pipeline 0's table: its version stamp keeps counting when the training batches follow
       SAM_GGMS(ggms_sample_batch(cfg.sample_type, &graph_, d_train + off, size, cfg.fanout.data(), L, &pipes_[0].ht,
                                  states_, num_states_, row.data(), col.data(), d_counts, &extra, ws_, ws_bytes_, stream_));
@@ -1442,7 +1454,9 @@ void Engine::SampleInto(Batch *b, Pipe &P) {
   extra.seeds_distinct = BatchSeedsDistinct(cur_step_ * cfg.batch_size, b->num_seeds) ? 1u : 0u;
   // The RNG pool -- and khop2's CSR -- is handed from batch to batch through rng_wait / rng_done, so the results
   // are those of the one-batch-at-a-time loop.
-  if (pipes_.size() > 1 && cfg.sample_type != GGMS_KHOP0) {
+  // khop_labor: the salt follows the batch's key -- (epoch, global index in the epoch) -- not the order of enqueueing
+  extra.labor_salt = ggms::labor_batch_salt(cfg.labor_seed, b->key / num_global_step_, b->key % num_global_step_);
+  if (pipes_.size() > 1 && cfg.sample_type != GGMS_KHOP0 && cfg.sample_type != GGMS_KHOP_LABOR) {
     extra.rng_wait = last_rng_done_;
     extra.rng_done = P.rng_done;
     last_rng_done_ = P.rng_done;

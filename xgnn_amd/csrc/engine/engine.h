@@ -76,6 +76,7 @@ struct RunConfig {
   // extensions (optional keys)
   bool has_seed = false;
   uint64_t seed = 0;
+  uint64_t labor_seed = 0; // khop_labor's batch salts: `seed`, or a wall-clock base taken once, when the run is configured
   bool direct_table = true;
   size_t lookahead = 2; // batches sample_once() keeps enqueued beyond the one it was asked for (config key `lookahead`)
   size_t extract_streams = 2; // lean batches' gathers alternate between this many streams (1 or 2; config key `extract_streams`)

@@ -84,6 +84,7 @@ struct SampleLayer {
   uint32_t *out_data = nullptr;         // random walk: visit counts
   size_t walk_length = 0, num_walk = 0;
   double restart_prob = 0;
+  uint32_t salt = 0;                    // khop_labor: the layer salt
 };
 
 // sample_khop.hip
@@ -100,6 +101,10 @@ int sample_weighted_hash_dedup_impl(const SampleLayer &l);
 size_t random_walk_ws_words(size_t num_input, size_t walk_length, size_t num_walk, size_t K);
 int sample_random_walk_impl(const SampleLayer &l);
 size_t walk_scan_tiles(size_t num_input);
+
+// sample_labor.hip
+size_t labor_ws_words(size_t num_input);
+int sample_khop_labor_impl(const SampleLayer &l);
 
 // sample_batch.hip: the per-sampler rules, one copy for the leaf entry points and ggms_sample_batch
 size_t layer_ws_words(int type, size_t n, size_t fanout, size_t walk_length, size_t num_walk);

@@ -38,6 +38,7 @@
 #include <vector>
 
 #include "ggms_internal.h"
+#include "labor_hash.h"
 #include "tile_scan.h"
 
 namespace ggms {
@@ -74,6 +75,7 @@ size_t layer_ws_words(int type, size_t n, size_t fanout, size_t walk_length, siz
   case GGMS_WEIGHTED_KHOP:
   case GGMS_WEIGHTED_KHOP_PREFIX: return weighted_ws_words(n, fanout);
   case GGMS_RANDOM_WALK: return random_walk_ws_words(n, walk_length, num_walk, fanout);
+  case GGMS_KHOP_LABOR: return labor_ws_words(n);
   default: return sample_ws_words(n); // khop3, khop2, weighted_khop_hash_dedup
   }
 }
@@ -83,9 +85,11 @@ static int layer_shape_check(int type, const SampleLayer &l) {
   GGMS_CHECK_ARG(l.fanout > 0); // a layer that samples nothing is a config error
   if (type == GGMS_KHOP3) GGMS_CHECK_ARG(l.fanout < 128);                            // khop3.cu:85
   if (type == GGMS_WEIGHTED_KHOP_HASH_DEDUP) GGMS_CHECK_ARG(l.fanout < kDedupSlots); // hash_dedup.cu:42
+  if (type == GGMS_KHOP_LABOR) GGMS_CHECK_ARG(l.fanout < 128); // the hub route ranks its selection in LDS
   if (type == GGMS_RANDOM_WALK) GGMS_CHECK_ARG(l.walk_length > 0 && l.num_walk > 0);
   // "this algorithm not support DistGraph engine", dist_loops.cc:167-228
-  if (type != GGMS_KHOP3 && type != GGMS_KHOP0 && type != GGMS_RANDOM_WALK) GGMS_CHECK_ARG(l.graph->num_part == 0);
+  if (type != GGMS_KHOP3 && type != GGMS_KHOP0 && type != GGMS_RANDOM_WALK && type != GGMS_KHOP_LABOR)
+    GGMS_CHECK_ARG(l.graph->num_part == 0);
   return GGMS_OK;
 }
 
@@ -99,7 +103,8 @@ static int layer_check(int type, const SampleLayer &l, size_t num_states) {
   if (type == GGMS_WEIGHTED_KHOP_PREFIX) GGMS_CHECK_ARG(l.prob);
   // the RNG pool: assert(i < num_random_states) in every sampler of the reference but khop0
   switch (type) {
-  case GGMS_KHOP0: return GGMS_OK;
+  case GGMS_KHOP0:
+  case GGMS_KHOP_LABOR: return GGMS_OK; // stateless
   case GGMS_KHOP3: GGMS_CHECK_ARG(l.states && (n + 127) / 128 * 8 <= num_states); return GGMS_OK; // khop3.cu:89
   case GGMS_KHOP2:                                                                                   // khop2.cu:57
   case GGMS_WEIGHTED_KHOP_HASH_DEDUP: // hash_dedup.cu:70
@@ -125,6 +130,7 @@ static int sample_layer(int type, const SampleLayer &l) {
   case GGMS_KHOP2: return sample_khop2_impl(l);
   case GGMS_WEIGHTED_KHOP_HASH_DEDUP: return sample_weighted_hash_dedup_impl(l);
   case GGMS_RANDOM_WALK: return sample_random_walk_impl(l);
+  case GGMS_KHOP_LABOR: return sample_khop_labor_impl(l);
   default: return sample_weighted_impl(l, type); // khop1, weighted_khop, weighted_khop_prefix
   }
 }
@@ -133,8 +139,10 @@ static int sample_layer(int type, const SampleLayer &l) {
 // out, khop0 where it produces it, the weighted family in the compaction's emit, hash_dedup by a seed's 16 lanes once
 // the seed is done.  khop2 does not: even with the four seeds of a lane in lock-step and their atomics issued together,
 // the returning atomics sit in the draw loop's dependency chain (measured on products: 0.45 -> 0.62 ms per step; the
-// separate insert launch of ht_fill_impl follows).
-static bool layer_enters_output(int type) { return type != GGMS_KHOP2; }
+// separate insert launch of ht_fill_impl follows).  khop_labor does not either: its selection writes each edge from
+// the lane that held the key, after a search that is all ballots -- a returning atomic per edge there would serialise
+// behind the search of the seed's whole wave, and the sampler stays a pure function of its inputs.
+static bool layer_enters_output(int type) { return type != GGMS_KHOP2 && type != GGMS_KHOP_LABOR; }
 
 // a leaf entry point: shape checks; nothing to sample -> a zero count (null pointers allowed); pointers, workspace and
 // RNG pool; the sampler
@@ -271,6 +279,7 @@ static int sample_batch_impl(int sample_type, const ggms_graph_t *graph, const g
     L.num_walk = extra->num_random_walk;
     L.restart_prob = extra->random_walk_restart_prob;
   }
+  const bool ordered_rng = sample_type != GGMS_KHOP_LABOR; // a stateless sampler has nothing to order between batches
   for (uint32_t i = 0; i < num_layer; ++i) {
     L.n_max = c.max_input[i];
     L.fanout = fanouts[i];
@@ -379,7 +388,7 @@ static int sample_batch_impl(int sample_type, const ggms_graph_t *graph, const g
     uint64_t *next_dst = i > 0 ? counts_dev + 3 * (i - 1) + 2         // = next layer's frontier size (:305)
                                : counts_dev + 3 * num_layer;          // = number of input nodes
     // batch order on the shared RNG pool (and on khop2's CSR): only the sampler kernels are ordered
-    if (first && extra && extra->rng_wait) GGMS_HIP(hipStreamWaitEvent(s, (hipEvent_t)extra->rng_wait, 0));
+    if (first && ordered_rng && extra && extra->rng_wait) GGMS_HIP(hipStreamWaitEvent(s, (hipEvent_t)extra->rng_wait, 0));
     di.w = (unsigned long long *)ht->o2n;
     di.version = ht->version;
     if (last_pf) { // the expansion: one more fill of the batch, over every neighbour of n2o[0, k)
@@ -416,6 +425,7 @@ static int sample_batch_impl(int sample_type, const ggms_graph_t *graph, const g
       L.n_max = n_max;
       L.n = n;
       L.fanout = fanouts[i]; // random walk: num_neighbor = K (operation.cc:174)
+      L.salt = labor_layer_salt(extra ? extra->labor_salt : 0u, (uint32_t)i);
       L.out_src = col[i];
       L.out_dst = tmp_dst;
       L.num_out = num_edge;
@@ -427,7 +437,7 @@ static int sample_batch_impl(int sample_type, const ggms_graph_t *graph, const g
       rc = sample_layer(sample_type, L);
     }
     if (rc != GGMS_OK) return rc;
-    if (i == 0 && extra && extra->rng_done) GGMS_HIP(hipEventRecord((hipEvent_t)extra->rng_done, s));
+    if (i == 0 && ordered_rng && extra && extra->rng_done) GGMS_HIP(hipEventRecord((hipEvent_t)extra->rng_done, s));
     const Count ne = count_of(e_max, num_edge);
     if (e_max == 0) { // nothing can be sampled: the counts are the current table size
       hipLaunchKernelGGL(k_record, dim3(1), dim3(64), 0, s, num_src, count_of32(0, ht->num_items_dev));
@@ -472,7 +482,7 @@ int ggms_sample_batch(int sample_type, const ggms_graph_t *graph, const ggms_id_
                       ggms_stream_t stream) {
   GGMS_CHECK_ARG(graph && fanouts && ht && row && col && counts_dev);
   GGMS_CHECK_ARG(num_layer >= 1 && num_layer <= 16);
-  GGMS_CHECK_ARG(sample_type >= GGMS_KHOP0 && sample_type <= GGMS_KHOP3);
+  GGMS_CHECK_ARG(sample_type >= GGMS_KHOP0 && sample_type <= GGMS_KHOP_LABOR);
   GGMS_CHECK_ARG(num_seeds == 0 || seeds);
   GGMS_CHECK_ARG(workspace && workspace_bytes >= ggms_sample_batch_workspace_bytes(sample_type, num_seeds, fanouts,
                                                                                    num_layer, extra));

@@ -46,6 +46,8 @@ def _check_q8row(src, src_dtype, dim):
 
 
 KHOP0, KHOP1, WEIGHTED_KHOP, RANDOM_WALK, WEIGHTED_KHOP_PREFIX, KHOP2, WEIGHTED_KHOP_HASH_DEDUP, KHOP3 = range(8)
+KHOP_LABOR = 8  # an extension: per-node shared randomness (include/ggms.h)
+_STATELESS = (KHOP0, KHOP_LABOR)  # samplers without an RNG pool
 
 
 def _require_gpu(t):
@@ -120,9 +122,10 @@ def _workspace(nbytes, device):
     return torch.empty(max(16, (nbytes + 3) // 4), dtype=torch.int32, device=device)
 
 
-def _sample(fn_name, sample_type, graph, inp, fanout, states, *tables):
+def _sample(fn_name, sample_type, graph, inp, fanout, states, *tables, salt=None):
     """One leaf sampler call: (out_src, out_dst, num_out[1] on device).  tables: the device arrays the entry point takes
-    between the graph and the input; states=None: a sampler without an RNG pool (khop0)."""
+    between the graph and the input; states=None: a sampler without an RNG pool (khop0, khop_labor); salt: khop_labor's
+    layer salt, passed behind the fanout."""
     _require_gpu(inp)
     _i32(inp)
     n = inp.numel()
@@ -132,7 +135,8 @@ def _sample(fn_name, sample_type, graph, inp, fanout, states, *tables):
     num_out = torch.zeros(1, dtype=torch.int64, device=dev)
     ws = _workspace(lib().ggms_sample_workspace_bytes(sample_type, n, fanout), dev)
     rng = (_ptr(states), states.shape[0]) if states is not None else ()
-    check(getattr(lib(), fn_name)(C.byref(graph.c), *map(_ptr, tables), _ptr(inp), n, fanout, _ptr(out_src),
+    salt = (C.c_uint32(salt & 0xFFFFFFFF),) if salt is not None else ()
+    check(getattr(lib(), fn_name)(C.byref(graph.c), *map(_ptr, tables), _ptr(inp), n, fanout, *salt, _ptr(out_src),
                                   _ptr(out_dst), _ptr(num_out), *rng, _ptr(ws), ws.numel() * 4, _stream()), fn_name)
     return out_src, out_dst, num_out
 
@@ -145,6 +149,11 @@ def sample_khop3(graph, inp, fanout, states):
 def sample_khop0(graph, inp, fanout):
     """GPUSampleKHop0 (cuda_sampling_khop0.cu:243-335)."""
     return _sample("ggms_sample_khop0", KHOP0, graph, inp, fanout, None)
+
+
+def sample_khop_labor(graph, inp, fanout, layer_salt):
+    """ggms_sample_khop_labor: the min(fanout, degree) neighbours with the smallest fmix32(id ^ layer_salt), per seed."""
+    return _sample("ggms_sample_khop_labor", KHOP_LABOR, graph, inp, fanout, None, salt=layer_salt)
 
 
 def sample_weighted_khop_prefix(graph, prob_prefix_table, inp, fanout, states):
@@ -705,7 +714,7 @@ class BatchSampler:
         nstates = max(nstates, (max(self.max_input) + 127) // 128 * 8, (max(self.max_input) + 1023) // 1024 * 256)
         if sample_type == RANDOM_WALK:
             nstates = max(nstates, lib().ggms_random_walk_num_states(max(self.max_input), num_random_walk))
-        self.states = random_states(nstates, seed, device) if sample_type != KHOP0 else None
+        self.states = random_states(nstates, seed, device) if sample_type not in _STATELESS else None
         self.num_slots = num_slots
         self.rows = [[torch.empty(max(1, e), dtype=torch.int32, device=device) for e in self.max_edges]
                      for _ in range(num_slots)]
@@ -738,7 +747,7 @@ class BatchSampler:
         self.ws = self.wss[0]
         # batch-order events on the RNG pool; only needed when batches overlap
         self._events = []
-        if num_pipelines > 1 and sample_type != KHOP0:
+        if num_pipelines > 1 and sample_type not in _STATELESS:
             for _ in range(num_pipelines):
                 e = C.c_void_p()
                 check(lib().ggms_event_create(C.byref(e)), "ggms_event_create")
@@ -760,11 +769,12 @@ class BatchSampler:
         except Exception:
             pass
 
-    def sample(self, seeds, slot=0, copy_input_nodes=False, heavy_wait=None, distinct=False):
+    def sample(self, seeds, slot=0, copy_input_nodes=False, heavy_wait=None, distinct=False, labor_salt=0):
         """Enqueue one batch into output slot `slot`; read counts / row / col / ht.n2o after a sync.
         copy_input_nodes: also copy the unique list (ht.n2o, reused by a later batch) into the slot.
         distinct: the caller promises pairwise distinct seeds (ggms_sample_extra_t.seeds_distinct) -- a slice of a
         shuffled train set is; the seeds' insert / ordered scan / look-up launches are then skipped.
+        labor_salt: khop_labor's batch salt (ggms_sample_extra_t.labor_salt); the other samplers ignore it.
         Batch b runs on pipeline b % num_pipelines (its table is `self.ht` until the next call)."""
         _i32(seeds)
         n = seeds.numel()
@@ -787,6 +797,7 @@ class BatchSampler:
         # heavy_wait (torch.cuda.Event): the last layer's sampler launch waits for it (ggms_sample_extra_t.heavy_wait)
         ex.heavy_wait = C.c_void_p(heavy_wait.cuda_event) if heavy_wait is not None else None
         ex.seeds_distinct = 1 if distinct else 0
+        ex.labor_salt = labor_salt & 0xFFFFFFFF
         ws = self.wss[pipe]
         # copy_input_nodes: the slot keeps the batch's unique list.  The table's n2o buffer is the caller's
         # (ggms_hashtable_t is plain data), so the batch simply builds the list IN the slot's buffer -- no copy
