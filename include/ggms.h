@@ -426,6 +426,44 @@ int ggms_sample_batch(int sample_type, const ggms_graph_t *graph,
                       uint64_t *counts_dev, const ggms_sample_extra_t *extra,
                       void *workspace, size_t workspace_bytes,
                       ggms_stream_t stream);
+/* The local ids of the RAW seeds of a batch (they may repeat): the first layer's `col` source.  Host arithmetic only:
+ * *seed_ids_dev = the address inside `workspace` where the num_seeds ids lie.  Valid after a ggms_sample_batch call
+ * with the same arguments that did not take the distinct-seeds path (there local id = position), until that workspace
+ * is used again; the prefetching batch has no such call.  A batch numbers its nodes by first occurrence (the canonical
+ * order above), so n2o[seed_ids[p]] == seeds[p] for every position p. */
+int ggms_sample_batch_seed_ids(int sample_type, size_t num_seeds, const size_t *fanouts, uint32_t num_layer,
+                               const ggms_sample_extra_t *extra, const void *workspace,
+                               const ggms_id_t **seed_ids_dev);
+
+/* ---------------------------------------------------------------------------
+ * Link-prediction seeds (an extension; the reference has no such operator): a batch of positive EDGE ids becomes the
+ * seed list of a sampled batch -- sources, destinations and num_negative negative destinations per positive.
+ * Stateless like khop_labor: a pure function of (graph, edge_ids, num_negative, mode, salt).
+ *   edge id     e is a position in graph->indices, e < E = indptr[num_node].  Its source u is the one row with
+ *               indptr[u] <= e < indptr[u + 1] (an upper-bound search over indptr: rows of degree 0 are skipped by
+ *               construction), its destination v = indices[e].  Edge ids are positions of ONE CSR: unsharded graphs
+ *               only (num_part != 0: GGMS_ERR_INVALID); num_node < 2^32, indptr[0] = 0.
+ *   endpoints   B = num_pos, K = num_negative: [0, B) the sources, [B, 2 B) the destinations, [2 B + i K + j] negative
+ *               j of positive i.  Positive pair i = (position i, position B + i); negative pair (i, j) = (position i,
+ *               position 2 B + i K + j).
+ *   candidates  8 attempts per negative: cand(e, j, a) = mulhi32(fmix32(fmix32(e ^ salt) + 0x9e3779b9 * (8 j + a + 1)),
+ *               num_node), arithmetic mod 2^32, mulhi32(h, n) = (uint64(h) * n) >> 32, fmix32 as khop_labor's above.
+ *               The variate is keyed by the edge ID, not by the edge's place in the call: the same edge with the same
+ *               salt gets the same negatives wherever it stands.
+ *   modes       GGMS_NEG_UNIFORM: negative j = cand(e, j, 0), nothing is rejected.
+ *               GGMS_NEG_EXCLUDE: a candidate w is rejected if w == u or w occurs in u's list (which holds v); the
+ *               negative is the first accepted candidate over a = 0 .. 7; all eight rejected: cand(e, j, 7), and
+ *               *num_forced_dev is incremented (one 64-bit atomic per wave at most, none where nothing is forced).
+ * num_negative 1 .. 64 (else GGMS_ERR_INVALID); num_pos == 0 is GGMS_OK with nothing launched.  num_forced_dev is
+ * zeroed by the caller and may be NULL.  An edge id >= E is a caller error: nothing is read out of bounds, and that
+ * positive's 2 + K positions get GGMS_EMPTY_KEY.  One launch: no workspace, no allocation, no synchronisation; a list
+ * is read at most twice whatever its length (attempt 0 of every negative, then attempts 1 .. 7 of the rejected ones).
+ * ------------------------------------------------------------------------- */
+#define GGMS_NEG_UNIFORM 0
+#define GGMS_NEG_EXCLUDE 1
+int ggms_link_seeds(const ggms_graph_t *graph, const ggms_id_t *edge_ids, size_t num_pos, uint32_t num_negative,
+                    int mode, uint32_t salt, ggms_id_t *endpoints /* num_pos * (2 + num_negative) ids */,
+                    uint64_t *num_forced_dev /* zeroed by the caller; may be NULL */, ggms_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * arch4's batch with early feature prefetch -- DoGPUSampleDyCache (cuda/cuda_loops.cc:294-524).  The layers of

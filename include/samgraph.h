@@ -105,6 +105,15 @@ void samgraph_get_dataset_feat(samgraph_tensor_t *out);                         
 void samgraph_get_dataset_label(samgraph_tensor_t *out);                         /* :154-167 */
 void samgraph_get_graph_input_nodes(uint64_t key, samgraph_tensor_t *out);       /* :169-180 */
 void samgraph_get_graph_output_nodes(uint64_t key, samgraph_tensor_t *out);      /* :182-193 */
+/* Extensions for config key task = link_prediction (arch1; keys num_negative = 1 .. 64, negative_mode = uniform |
+ * exclude).  A batch is B = batch_size positive edges of the shuffled train edge set (train_edge_set.bin: uint32
+ * positions in indices.bin; absent: every edge) with K = num_negative negative destinations each (ggms_link_seeds,
+ * include/ggms.h).  Its output nodes are the B (2 + K) endpoints: [0, B) sources, [B, 2 B) destinations,
+ * [2 B + i K + j] negative j of positive i.  samgraph_get_graph_seed_ids gives the LOCAL id of each of them (uint32
+ * ids as I32, B (2 + K) entries, same layout): the ids the first sampled layer's col uses, rows of the batch's input
+ * nodes and of its feature tensor.  samgraph_num_negative: K, or 0 for a node_classification run. */
+void samgraph_get_graph_seed_ids(uint64_t key, samgraph_tensor_t *out);
+size_t samgraph_num_negative(void);
 /* a batch's buffers stay valid while its retain count is > 0 */
 void samgraph_batch_retain(uint64_t key);
 void samgraph_batch_release(uint64_t key);

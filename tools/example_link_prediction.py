@@ -1,0 +1,87 @@
+"""Link prediction with GraphSAGE on batches from the samgraph_* engine (task = link_prediction), in plain PyTorch-ROCm.
+
+tools/example_train_sage.py's DGL-free model; the head is a dot product of the two endpoints' embeddings, trained with
+binary cross-entropy over the batch's positive pairs (label 1) and negative pairs (label 0).  A usage example of the
+pair interface, not a tuned model:
+
+    sam.config({..., "task": "link_prediction", "num_negative": K, "negative_mode": "exclude"})
+    pos_src, pos_dst, neg_src, neg_dst = sam.get_graph_link_pairs(key)   # local ids: rows of the model's output
+
+batch_size counts positive EDGES; the batch's seed list is their B (2 + K) endpoints, so the first sampled layer's
+num_dst is B (2 + K) while the distinct endpoints are the first max(id) + 1 nodes of the batch.
+
+    python tools/example_link_prediction.py <dataset_dir> [--epochs 2] [--batch-size 512] [--num-negative 3]
+"""
+import argparse
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+import samgraph.torch as sam  # noqa: E402
+from example_train_sage import SageLayer  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("dataset")
+    ap.add_argument("--epochs", type=int, default=2)
+    ap.add_argument("--batch-size", type=int, default=512, help="positive edges per batch")
+    ap.add_argument("--num-negative", type=int, default=3)
+    ap.add_argument("--negative-mode", default="exclude", choices=["uniform", "exclude"])
+    ap.add_argument("--fanout", type=int, nargs="+", default=[10, 5])
+    ap.add_argument("--sample-type", default="khop3")
+    ap.add_argument("--hidden", type=int, default=64)
+    ap.add_argument("--seed", type=int, default=1)
+    args = ap.parse_args()
+    L = len(args.fanout)
+    sam.config({"dataset_path": args.dataset, "_arch": sam.builtin_archs["arch1"]["arch"],
+                "_sample_type": sam.sample_types[args.sample_type], "batch_size": args.batch_size,
+                "num_epoch": args.epochs, "_cache_policy": sam.cache_policies["degree"], "cache_percentage": 0.0,
+                "max_sampling_jobs": 10, "max_copying_jobs": 1, "omp_thread_num": 4, "num_layer": L,
+                "num_hidden": args.hidden, "lr": 0.003, "dropout": 0.0, "num_fanout": L, "fanout": args.fanout,
+                "sampler_ctx": "cuda:0", "trainer_ctx": "cuda:0", "seed": args.seed,
+                "task": "link_prediction", "num_negative": args.num_negative, "negative_mode": args.negative_mode})
+    sam.init()
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(args.seed)
+    dims = [sam.feat_dim()] + [args.hidden] * L
+    layers = torch.nn.ModuleList([SageLayer(dims[i], dims[i + 1]) for i in range(L)]).to(dev)
+    opt = torch.optim.Adam(layers.parameters(), lr=0.003)
+    steps = sam.steps_per_epoch()
+    for epoch in range(args.epochs):
+        t0, pairs, loss_sum, hits = time.time(), 0, 0.0, 0
+        for step in range(steps):
+            sam.sample_once()
+            key = sam.get_next_batch()
+            pos_src, pos_dst, neg_src, neg_dst = (t.long() for t in sam.get_graph_link_pairs(key))
+            num_out = int(sam.get_graph_seed_ids(key).max()) + 1  # distinct endpoints: the first nodes of the batch
+            h = sam.get_graph_feat(key) / 65536.0  # the synthetic features are integers in [0, 65535]
+            coo = sam.get_graph_coo(key, L)  # layer 0 = outermost hop (largest frontier)
+            for i in range(L):
+                row, col, num_src, num_dst = coo[i]
+                assert h.shape[0] == num_src
+                h = layers[i](h, row.long(), col.long(), num_dst if i + 1 < L else num_out)
+                if i + 1 < L:
+                    h = torch.relu(h)
+            pos = (h[pos_src] * h[pos_dst]).sum(1)
+            neg = (h[neg_src] * h[neg_dst]).sum(2).flatten()
+            score = torch.cat([pos, neg])
+            target = torch.cat([torch.ones_like(pos), torch.zeros_like(neg)])
+            loss = torch.nn.functional.binary_cross_entropy_with_logits(score, target)
+            opt.zero_grad()
+            loss.backward()
+            opt.step()
+            pairs += score.numel()
+            loss_sum += float(loss) * score.numel()
+            hits += int(((score > 0) == (target > 0)).sum())
+        print(f"epoch {epoch}: {steps} steps, loss {loss_sum / pairs:.4f}, pair acc {hits / pairs:.3f}, "
+              f"{time.time() - t0:.2f} s, sampled {sam.get_log_epoch_value(epoch, sam.kLogEpochNumSample):.0f} edges",
+              flush=True)
+    sam.shutdown()
+
+
+if __name__ == "__main__":
+    main()

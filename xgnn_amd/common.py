@@ -110,6 +110,7 @@ SAMGRAPH_SYMBOLS = {
     "samgraph_get_graph_data": (None, [_u64, _i, _TP]), "samgraph_get_dataset_feat": (None, [_TP]),
     "samgraph_get_dataset_label": (None, [_TP]), "samgraph_get_graph_input_nodes": (None, [_u64, _TP]),
     "samgraph_get_graph_output_nodes": (None, [_u64, _TP]),
+    "samgraph_get_graph_seed_ids": (None, [_u64, _TP]), "samgraph_num_negative": (_sz, []),
     "samgraph_batch_retain": (None, [_u64]), "samgraph_batch_release": (None, [_u64]),
 }
 
@@ -158,6 +159,7 @@ class SamGraphBasics(object):
     def feat_row_bytes(self, delivered=False):
         """Bytes of one feature row as stored in the table (a Q8ROW row: codes, pad, trailer) or as delivered in a batch."""
         return self.C_LIB_CTYPES.samgraph_feat_row_bytes(1 if delivered else 0)
+    def num_negative(self): return self.C_LIB_CTYPES.samgraph_num_negative()
     def num_epoch(self): return self.C_LIB_CTYPES.samgraph_num_epoch()
     def steps_per_epoch(self): return self.C_LIB_CTYPES.samgraph_steps_per_epoch()
     def get_next_batch(self): return self.C_LIB_CTYPES.samgraph_get_next_batch()

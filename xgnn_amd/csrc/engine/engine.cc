@@ -264,6 +264,34 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
     // the batch dtype rule of a table of that type (the table's side of it is checked in LoadDataset)
     if (cfg.feat_store_dtype == GGMS_Q8ROW && cfg.feat_out_dtype < 0) fatal(__FILE__, __LINE__, kQ8RowNeedsOutDtype);
   }
+  if (kv.count("task")) { // extension: what a batch is made of
+    const std::string v = kv["task"];
+    if (v != "node_classification" && v != "link_prediction")
+      fatal(__FILE__, __LINE__, "task = " + v + ": node_classification (the default) or link_prediction");
+    cfg.link_prediction = v == "link_prediction";
+  }
+  if (cfg.link_prediction) {
+    static const char *const arch_names[] = {"arch0", "arch1", "arch2", "arch3", "arch4", "arch5", "arch6", "arch7"};
+    if (cfg.arch != kArch1)
+      fatal(__FILE__, __LINE__, std::string(arch_names[cfg.arch]) + ": task = link_prediction is not built: edge seeds, "
+                                "negative sampling and the pair ids run in arch1's sampling chain only");
+    if (cfg.sample_type == GGMS_RANDOM_WALK)
+      fatal(__FILE__, __LINE__, "task = link_prediction with _sample_type 3 (random_walk) is not built: the pair ids are "
+                                "the k-hop batch's seed ids");
+    if (kv.count("num_negative")) {
+      long long k = 0;
+      try { k = std::stoll(kv["num_negative"]); } catch (...) { k = 0; }
+      if (k < 1 || k > 64)
+        fatal(__FILE__, __LINE__, "num_negative = " + kv["num_negative"] + ": 1 .. 64 negatives per positive edge");
+      cfg.num_negative = (uint32_t)k;
+    }
+    if (kv.count("negative_mode")) {
+      const std::string v = kv["negative_mode"];
+      if (v != "uniform" && v != "exclude")
+        fatal(__FILE__, __LINE__, "negative_mode = " + v + ": uniform or exclude (the default)");
+      cfg.negative_mode = v == "uniform" ? GGMS_NEG_UNIFORM : GGMS_NEG_EXCLUDE;
+    }
+  }
   if (cfg.arch == kArch4) { // DoGPUSampleDyCache's switch (cuda/cuda_loops.cc:347-377) and what it needs
     if (cfg.sample_type != GGMS_KHOP0 && cfg.sample_type != GGMS_KHOP1 && cfg.sample_type != GGMS_WEIGHTED_KHOP)
       fatal(__FILE__, __LINE__, "arch4: _sample_type " + std::to_string(cfg.sample_type) + " is not supported: the "
@@ -426,6 +454,30 @@ void Engine::LoadDataset() {
   ds.train_set = MapFile("train_set.bin", ds.num_train * 4, false);
   ds.test_set = MapFile("test_set.bin", ds.num_test * 4, false);
   ds.valid_set = MapFile("valid_set.bin", ds.num_valid * 4, false);
+  if (cfg.link_prediction) { // the train edge set: positions in indices.bin
+    const std::string name = cfg.dataset_path + "train_edge_set.bin";
+    if (file_exists(name)) {
+      struct stat st;
+      SAM_CHECK(stat(name.c_str(), &st) == 0 && st.st_size % 4 == 0, "train_edge_set.bin: uint32 CSR positions expected");
+      ds.num_train_edge = (size_t)st.st_size / 4;
+      ds.train_edge_set = MapFile("train_edge_set.bin", ds.num_train_edge * 4, false);
+      ds.train_edges = (const uint32_t *)ds.train_edge_set.ptr;
+      for (size_t i = 0; i < ds.num_train_edge; ++i)
+        if (ds.train_edges[i] >= ds.num_edge)
+          fatal(__FILE__, __LINE__, "train_edge_set.bin: entry " + std::to_string(i) + " is " +
+                                        std::to_string(ds.train_edges[i]) + ", the graph has " +
+                                        std::to_string(ds.num_edge) + " edges (ids are positions in indices.bin)");
+    } else { // every edge once per epoch
+      if (ds.num_edge >= (1ull << 32))
+        fatal(__FILE__, __LINE__, "task = link_prediction without train_edge_set.bin takes every edge: " +
+                                      std::to_string(ds.num_edge) + " edges do not fit 32-bit edge ids");
+      ds.all_edges.resize(ds.num_edge);
+      for (size_t i = 0; i < ds.num_edge; ++i) ds.all_edges[i] = (uint32_t)i;
+      ds.train_edges = ds.all_edges.data();
+      ds.num_train_edge = ds.num_edge;
+    }
+    SAM_CHECK(ds.num_train_edge > 0, "task = link_prediction: the train edge set is empty");
+  }
   if (cfg.sample_type == GGMS_WEIGHTED_KHOP || cfg.sample_type == GGMS_WEIGHTED_KHOP_HASH_DEDUP) { // engine.cc:372-384
     ds.prob_table = MapFile("prob_table.bin", ds.num_edge * 4, false);
     ds.alias_table = MapFile("alias_table.bin", ds.num_edge * 4, false);
@@ -627,7 +679,7 @@ void *Engine::OpenPeer(const hipIpcMemHandle_t &handle, uint32_t peer, size_t by
 // (dist/dist_shuffler_aligned.cc:37-146) for arch6, DistShuffler (dist/dist_shuffler.cc:37-90) for arch5's samplers:
 // same Fisher-Yates with std::default_random_engine(seed) + uniform_int_distribution<size_t>(i, n-1).
 void Engine::ShufflerInit() {
-  const uint32_t *train = (const uint32_t *)ds.train_set.ptr;
+  const uint32_t *train = SeedSet();
   if (cfg.arch == kArch5) {
     // the epoch's ceil(num_train / batch_size) steps in consecutive ranges: the first (steps % S) samplers take one step
     // more ("large"), e.g. 15 steps over 4 samplers = 4, 4, 4, 3.  No padding, the last batch may be short.  (The
@@ -644,7 +696,7 @@ void Engine::ShufflerInit() {
                                num_data_ > global_data_offset_ ? num_data_ - global_data_offset_ : 0);
   } else {
     const size_t nw = cfg.arch == kArch6 ? cfg.num_worker : 1;
-    const size_t origin = ds.num_train;
+    const size_t origin = SeedSetSize();
     num_data_ = (origin + nw - 1) / nw * nw; // aligned to num_worker (:46)
     shuf_host_.assign(train, train + origin);
     for (size_t i = 0; i < num_data_ - origin; ++i) shuf_host_.push_back(train[i]); // :52-54
@@ -654,14 +706,14 @@ void Engine::ShufflerInit() {
     global_step_offset_ = num_local_step_ * worker_id_;
     global_data_offset_ = num_local_data_ * worker_id_;
   }
-  const size_t origin = ds.num_train;
+  const size_t origin = SeedSetSize();
   cur_epoch_ = 0;
   cur_step_ = num_local_step_;
   shuf_initialized_ = false;
   SAM_HIP(hipMalloc((void **)&shuf_dev_, std::max<size_t>(1, num_local_data_) * 4));
   { // a train SET: no node twice (what lets a batch promise distinct seeds to the sampler)
     std::vector<bool> seen(ds.num_node, false);
-    train_distinct_ = true;
+    train_distinct_ = !cfg.link_prediction; // (the endpoints of a batch of edges repeat: never promised distinct)
     for (size_t i = 0; i < origin && train_distinct_; ++i) {
       if (train[i] >= ds.num_node || seen[train[i]]) train_distinct_ = false;
       else seen[train[i]] = true;
@@ -693,10 +745,10 @@ void Engine::Reshuffle() {
   }
   // where the padding copies went (at most num_worker - 1 nodes appear twice in the aligned epoch)
   pad_pairs_.clear();
-  if (num_data_ > ds.num_train) {
-    const uint32_t *train = (const uint32_t *)ds.train_set.ptr;
+  if (num_data_ > SeedSetSize()) {
+    const uint32_t *train = SeedSet();
     std::unordered_map<uint32_t, size_t> first;
-    for (size_t i = 0; i < num_data_ - ds.num_train; ++i) first[train[i]] = (size_t)-1;
+    for (size_t i = 0; i < num_data_ - SeedSetSize(); ++i) first[train[i]] = (size_t)-1;
     for (size_t pos = 0; pos < num_data_; ++pos) {
       auto it = first.find(data[pos]);
       if (it == first.end()) continue;
@@ -740,6 +792,12 @@ bool Engine::ShufflerNext(Batch *b, hipStream_t copy_stream) {
   b->num_seeds = size;
   b->key = BatchKey(cur_epoch_, global_step_offset_ + cur_step_);
   static const bool sanity = getenv("SAMGRAPH_SANITY_CHECK") != nullptr; // run_config.cc:126-128
+  if (cfg.link_prediction) { // the slice holds edge ids: SampleInto turns them into the batch's seed list
+    b->num_pos = size;
+    b->num_seeds = size * (2 + cfg.num_negative);
+    SAM_HIP(hipMemcpyAsync(b->edge_ids, shuf_dev_ + offset, size * 4, hipMemcpyDeviceToDevice, copy_stream));
+    return true;
+  }
   if (sanity && (cfg.arch == kArch1 || Dedicated())) SanityCheckBatch(shuf_host_.data() + global_data_offset_ + offset, size);
   SAM_HIP(hipMemcpyAsync(b->sampler.output_nodes, shuf_dev_ + offset, size * 4, hipMemcpyDeviceToDevice, copy_stream)); // Copy1D
   return true;
@@ -834,6 +892,8 @@ void Engine::ComputeBounds() {
   const uint32_t L = (uint32_t)cfg.fanout.size();
   // first batch of arch6 is x1.25 (dist_shuffler_aligned.cc:137-140): size every buffer for it
   max_seeds_ = (size_t)(cfg.batch_size * 1.25) + 1;
+  // link_prediction: the seed list is the endpoints and negatives of batch_size positive edges
+  if (cfg.link_prediction) max_seeds_ = cfg.batch_size * (2 + cfg.num_negative);
   max_input_.resize(L);
   max_edges_.resize(L);
   SAM_GGMS(ggms_sample_batch_capacity(max_seeds_, cfg.fanout.data(), L, max_input_.data(), max_edges_.data(), &max_unique_));
@@ -1304,6 +1364,10 @@ void Engine::TrainInit(int worker_id, const std::string &ctx) {
     b->trainer.Alloc(max_edges_, max_unique_, max_seeds_, cfg.sample_type == GGMS_RANDOM_WALK);
     SAM_HIP(hipMalloc(&b->feat, max_unique_ * batch_feat_row_bytes())); // rows as delivered
     SAM_HIP(hipMalloc((void **)&b->label, max_seeds_ * 8));
+    if (cfg.link_prediction) {
+      SAM_HIP(hipMalloc((void **)&b->edge_ids, cfg.batch_size * 4));
+      SAM_HIP(hipMalloc((void **)&b->seed_ids, max_seeds_ * 4));
+    }
     if (StagedHostTier()) { // index arrays of GetMissCacheIndex + pinned / device staging of the miss rows
       if (cache_table_) { // (no cache: no split, and the rows land in the batch's feature buffer directly)
         for (uint32_t **p : {&b->miss_src, &b->miss_dst, &b->hit_src, &b->hit_dst}) SAM_HIP(hipMalloc((void **)p, max_unique_ * 4));
@@ -1456,6 +1520,17 @@ void Engine::SampleInto(Batch *b, Pipe &P) {
   // are those of the one-batch-at-a-time loop.
   // khop_labor: the salt follows the batch's key -- (epoch, global index in the epoch) -- not the order of enqueueing
   extra.labor_salt = ggms::labor_batch_salt(cfg.labor_seed, b->key / num_global_step_, b->key % num_global_step_);
+  if (cfg.link_prediction) {
+    // edge ids -> sources, destinations, negatives, straight into the batch's output nodes.  The salt follows the
+    // batch's key like khop_labor's: a batch is a function of its key, whatever pipeline draws it.  The forced count
+    // takes a spare counts word and travels to the host with the counts.
+    uint64_t *forced = s.counts_dev + 3 * L + 7;
+    SAM_HIP(hipMemsetAsync(forced, 0, 8, P.stream));
+    const uint32_t salt = ggms::fmix32(extra.labor_salt ^ 0x6c696e6bu);
+    SAM_GGMS(ggms_link_seeds(&graph_, b->edge_ids, b->num_pos, cfg.num_negative, cfg.negative_mode, salt, s.output_nodes,
+                             forced, P.stream));
+    extra.seeds_distinct = 0;
+  }
   if (pipes_.size() > 1 && cfg.sample_type != GGMS_KHOP0 && cfg.sample_type != GGMS_KHOP_LABOR) {
     extra.rng_wait = last_rng_done_;
     extra.rng_done = P.rng_done;
@@ -1475,6 +1550,11 @@ void Engine::SampleInto(Batch *b, Pipe &P) {
     SAM_GGMS(ggms_sample_batch(cfg.sample_type, &graph_, s.output_nodes, b->num_seeds, cfg.fanout.data(), L, &ht, states_,
                                num_states_, s.row.data(), s.col.data(), s.counts_dev, &extra, P.ws, ws_bytes_, P.stream));
   P.ht.version = ht.version; // the batch bumped the table's version stamp
+  if (cfg.link_prediction) { // the pair ids: out of the workspace, which the pipeline's next batch rewrites
+    const ggms_id_t *ids = nullptr;
+    SAM_GGMS(ggms_sample_batch_seed_ids(cfg.sample_type, b->num_seeds, cfg.fanout.data(), L, &extra, P.ws, &ids));
+    SAM_HIP(hipMemcpyAsync(b->seed_ids, ids, b->num_seeds * 4, hipMemcpyDeviceToDevice, P.stream));
+  }
   SAM_HIP(hipMemsetAsync(s.counts_dev + 3 * L + 2, 0, 8, P.stream)); // the trainer's miss count starts at 0
   SAM_HIP(hipEventRecord(b->ev_sampled, P.stream));
 }
@@ -1682,6 +1762,14 @@ void Engine::Finish(Batch *b, Batch *prev) {
                                   std::to_string(b->counts[3 * L + 6]) + " edges, capacity " +
                                   std::to_string(max_prefetch_edges_) + " (config key prefetch_max_edges)");
   CheckBatchStatus(b->counts[3 * L + 1], b->key);
+  if (cfg.link_prediction) { // negatives whose eight candidates were all rejected, per epoch
+    link_forced_ += b->counts[3 * L + 7];
+    if (b->key % num_global_step_ == num_global_step_ - 1) {
+      log_info("link_prediction: epoch " + std::to_string(b->key / num_global_step_) + ": " + std::to_string(link_forced_) +
+               " forced negatives of " + std::to_string(ds.num_train_edge * cfg.num_negative));
+      link_forced_ = 0;
+    }
+  }
   if (cfg.arch == kArch4 && !cfg.dynamic_cache) b->num_miss = b->num_input; // every row is read from host memory
   float ms_sample = 0, ms_copy = 0;
   if (cfg.arch != kArch5) (void)hipEventElapsedTime(&ms_sample, b->ev_start, b->ev_sampled); // (arch5: sampled elsewhere)

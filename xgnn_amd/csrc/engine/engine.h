@@ -95,6 +95,12 @@ struct RunConfig {
   // encoded into this type by the trainer GPU before the cache is built (Engine::QuantizeStore); from then on the
   // dataset is what a meta.txt naming the type would have loaded.  -1: key absent, the table stays as it is on disk
   int feat_store_dtype = -1;
+  // extension (config keys `task` = node_classification | link_prediction, `num_negative` = 1 .. 64, `negative_mode` =
+  // uniform | exclude; arch1): a batch is batch_size positive EDGES of the shuffled train edge set; its seed list is
+  // their endpoints and num_negative negative destinations each (ggms_link_seeds), batch_size x (2 + num_negative) ids
+  bool link_prediction = false;
+  uint32_t num_negative = 1;
+  int negative_mode = GGMS_NEG_EXCLUDE;
   size_t staged_serial_epochs = 0; // host-staged path: the first N epochs run the reference's serial, per-phase-timed sequence
   size_t staged_serial_steps = 0;  // ... or this worker's first N batches
   // worker 0 ranks the nodes at init: pre_sample (sampled input nodes) or presample_static (L-hop closures)
@@ -115,6 +121,12 @@ struct Dataset {
   int feat_dtype = GGMS_F32;
   size_t num_train = 0, num_valid = 0, num_test = 0;
   HostArray indptr, indices, feat, label, train_set, valid_set, test_set, ranking_nodes, prob_table, alias_table;
+  // task = link_prediction: the train edge set, CSR positions below num_edge -- train_edge_set.bin, or every edge
+  // (`all_edges`, built at load) where the dataset has no such file
+  HostArray train_edge_set;
+  std::vector<uint32_t> all_edges;
+  const uint32_t *train_edges = nullptr;
+  size_t num_train_edge = 0;
   bool feat_is_fake = false;
   bool feat_is_zero = false; // the stand-in table of a dataset without feat.bin that nobody has written: every row is zero
   // SAMGRAPH_EMPTY_FEAT = k (engine.cc:198-235): the feature table is a 2^k-row stand-in, row of node v = v & mask
@@ -181,6 +193,10 @@ struct Batch {
   // pinned host copy (hipHostMalloc) of trainer.counts_dev, valid after Finish()
   uint64_t *counts = nullptr;
   size_t num_seeds = 0, num_input = 0;
+  // task = link_prediction: the batch's positive edge ids (what the shuffler hands out), and the local id of every
+  // entry of the seed list -- the pair ids -- copied out of the sampling workspace before the next batch reuses it
+  uint32_t *edge_ids = nullptr, *seed_ids = nullptr;
+  size_t num_pos = 0;
   uint64_t num_miss = 0;
   hipEvent_t ev_seeds = nullptr, ev_start = nullptr, ev_sampled = nullptr, ev_xstart = nullptr, ev_done = nullptr;
   // arch6 with `gpu_extract` off: the host-staged miss path (dist_loops.cc:1015-1207)
@@ -252,6 +268,10 @@ class Engine {
   HostArray MapFile(const std::string &name, size_t bytes, bool to_shared_anon);
   // shuffler (cuda/cuda_shuffler.cc, dist/dist_shuffler_aligned.cc)
   void ShufflerInit();
+  // what the shuffler permutes: the train node set, or the train edge set of a link_prediction run
+  const uint32_t *SeedSet() const { return cfg.link_prediction ? ds.train_edges : (const uint32_t *)ds.train_set.ptr; }
+  size_t SeedSetSize() const { return cfg.link_prediction ? ds.num_train_edge : ds.num_train; }
+  uint64_t link_forced_ = 0; // link_prediction: forced negatives of the batches handed out so far in this epoch
   bool ShufflerNext(Batch *b, hipStream_t copy_stream); // false at end of training
   void Reshuffle();
   // GGMS

@@ -134,6 +134,14 @@ void samgraph_get_graph_output_nodes(uint64_t key, samgraph_tensor_t *out) {
   auto *b = E.Current(key);
   fill(out, b->trainer.output_nodes, (int64_t)b->num_seeds, 1, 1, GGMS_I32, E.batch_device_type(), E.trainer_device());
 }
+// task = link_prediction: the local id of every entry of the batch's seed list (output nodes), i.e. the pair ids
+void samgraph_get_graph_seed_ids(uint64_t key, samgraph_tensor_t *out) {
+  auto &E = Engine::Get();
+  if (!E.cfg.link_prediction) sam::fatal(__FILE__, __LINE__, "samgraph_get_graph_seed_ids needs task = link_prediction");
+  auto *b = E.Current(key);
+  fill(out, b->seed_ids, (int64_t)b->num_seeds, 1, 1, GGMS_I32, E.batch_device_type(), E.trainer_device());
+}
+size_t samgraph_num_negative(void) { return Engine::Get().cfg.link_prediction ? Engine::Get().cfg.num_negative : 0; }
 void samgraph_batch_retain(uint64_t key) { Engine::Get().Retain(key); }
 void samgraph_batch_release(uint64_t key) { Engine::Get().Release(key); }
 

@@ -494,6 +494,20 @@ int ggms_sample_batch(int sample_type, const ggms_graph_t *graph, const ggms_id_
                            counts_dev, extra, workspace, nullptr, to_stream(stream));
 }
 
+// The raw seeds' local ids are `seed_local`, a piece of its own that only the batch's look-ups read after the seeds'
+// fill has written it (kRestNow: every position, owners or not): it survives to the end of the batch as it is.
+int ggms_sample_batch_seed_ids(int sample_type, size_t num_seeds, const size_t *fanouts, uint32_t num_layer,
+                               const ggms_sample_extra_t *extra, const void *workspace, const ggms_id_t **seed_ids_dev) {
+  GGMS_CHECK_ARG(fanouts && workspace && seed_ids_dev);
+  GGMS_CHECK_ARG(num_layer >= 1 && num_layer <= 16);
+  GGMS_CHECK_ARG(sample_type >= GGMS_KHOP0 && sample_type <= GGMS_KHOP_LABOR);
+  const BatchCaps c = caps_of(num_seeds, fanouts, num_layer);
+  const BatchLayout lay = layout_of(sample_type, num_seeds, fanouts, num_layer, c, extra);
+  const uint32_t *w = (const uint32_t *)(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
+  *seed_ids_dev = w + lay.seed_local;
+  return GGMS_OK;
+}
+
 // ---- arch4: the prefetching batch ----------------------------------------------------------------------------------
 int ggms_sample_batch_prefetch_capacity(size_t num_seeds, const size_t *fanouts, uint32_t num_layer,
                                         const ggms_id_t *indptr, size_t num_node, size_t max_edges_budget,

@@ -143,13 +143,15 @@ def build_prob_prefix_table(indptr, weights, num_threads=8):
 
 
 def write_dataset(path, graph, feat=None, label=None, valid_frac=0.02, test_frac=0.05, feat_dtype="F32", weights=None,
-                  minimal=False):
+                  minimal=False, train_edges=None):
     """Write a dataset directory in the reference's on-disk format (datagen/README.md:37-51,
     samgraph/common/constant.cc:23-51, engine.cc:109-443): meta.txt (tab separated) + raw little-endian
     arrays: indptr/indices/train_set/test_set/valid_set/cache_by_* uint32, feat row-major, label int64;
     feat_dtype "F8E4M3" / "F8E5M2": feat is a torch.float8_e4m3fn / float8_e5m2 tensor, or its bytes as a uint8 array;
     feat_dtype "Q8ROW": feat is the packed (n, q8row_stride(feat_dim)) uint8 rows of pack_q8row;
     weights (one float per edge) adds prob_table.bin / alias_table.bin / prob_prefix_table.bin.
+    train_edges (uint32 positions in indices, each below the edge count) adds train_edge_set.bin, the set a
+    link_prediction run shuffles (config key `task`); without it such a run takes every edge.
     minimal: what a sampling + extract run needs and nothing that costs minutes at papers100M size -- one-node
     valid / test sets instead of random slices of the complement, no cache_by_random.bin."""
     import os
@@ -169,6 +171,10 @@ def write_dataset(path, graph, feat=None, label=None, valid_frac=0.02, test_frac
     train.astype(np.uint32).tofile(os.path.join(path, "train_set.bin"))
     valid.tofile(os.path.join(path, "valid_set.bin"))
     test.tofile(os.path.join(path, "test_set.bin"))
+    if train_edges is not None:
+        train_edges = np.ascontiguousarray(train_edges, dtype=np.uint32)
+        assert train_edges.size == 0 or int(train_edges.max()) < ix.size, "train_edges: positions in indices, below the edge count"
+        train_edges.tofile(os.path.join(path, "train_edge_set.bin"))
     if feat is not None:
         if feat_dtype in FP8_FORMATS:
             feat = _fp8_bytes(feat, feat_dtype)

@@ -156,6 +156,23 @@ def sample_khop_labor(graph, inp, fanout, layer_salt):
     return _sample("ggms_sample_khop_labor", KHOP_LABOR, graph, inp, fanout, None, salt=layer_salt)
 
 
+NEG_UNIFORM, NEG_EXCLUDE = 0, 1  # ggms_link_seeds modes
+
+
+def link_seeds(graph, edge_ids, num_negative, mode=NEG_EXCLUDE, salt=0, count_forced=True):
+    """ggms_link_seeds: positive edge ids (CSR positions) -> (endpoints, num_forced[1] on device).  endpoints holds
+    B sources, B destinations and B x num_negative negative destinations (include/ggms.h); num_forced counts the
+    negatives of mode NEG_EXCLUDE whose eight candidates were all rejected (None with count_forced=False)."""
+    _require_gpu(edge_ids)
+    _i32(edge_ids)
+    n = edge_ids.numel()
+    out = torch.empty(max(1, n * (2 + max(0, num_negative))), dtype=torch.int32, device=edge_ids.device)
+    forced = torch.zeros(1, dtype=torch.int64, device=edge_ids.device) if count_forced else None
+    check(lib().ggms_link_seeds(C.byref(graph.c), _ptr(edge_ids), n, num_negative, mode, salt & 0xFFFFFFFF, _ptr(out),
+                                _ptr(forced), _stream()), "ggms_link_seeds")
+    return out[: n * (2 + num_negative)], forced
+
+
 def sample_weighted_khop_prefix(graph, prob_prefix_table, inp, fanout, states):
     """GPUSampleWeightedKHopPrefix (cuda_sampling_weighted_khop_prefix.cu:145-246)."""
     return _sample("ggms_sample_weighted_khop_prefix", WEIGHTED_KHOP_PREFIX, graph, inp, fanout, states,
@@ -799,6 +816,7 @@ class BatchSampler:
         ex.seeds_distinct = 1 if distinct else 0
         ex.labor_salt = labor_salt & 0xFFFFFFFF
         ws = self.wss[pipe]
+        self._seed_ids_of = None if distinct else (n, ws)
         # copy_input_nodes: the slot keeps the batch's unique list.  The table's n2o buffer is the caller's
         # (ggms_hashtable_t is plain data), so the batch simply builds the list IN the slot's buffer -- no copy
         self._n2o = self.input_nodes[slot] if copy_input_nodes else self.ht.n2o
@@ -810,6 +828,19 @@ class BatchSampler:
                                       self._cols[slot], _ptr(counts), C.byref(ex), _ptr(ws), ws.numel() * 4,
                                       _stream()),
               "ggms_sample_batch")
+
+    def seed_ids(self):
+        """Local ids of the raw seeds of the last batch (ggms_sample_batch_seed_ids): a device view into that batch's
+        workspace, valid until its pipeline samples again.  input_nodes[seed_ids[p]] == seeds[p]; the ids a
+        link-prediction batch's pairs are made of.  Not for a batch sampled with distinct=True (its ids are positions)."""
+        if getattr(self, "_seed_ids_of", None) is None:
+            raise _lib.GgmsError("seed_ids(): the last batch took the distinct-seeds path (or nothing was sampled)")
+        n, ws = self._seed_ids_of
+        p = C.c_void_p()
+        check(lib().ggms_sample_batch_seed_ids(self.sample_type, n, self._f, self.L, C.byref(self._extra), _ptr(ws),
+                                               C.byref(p)), "ggms_sample_batch_seed_ids")
+        off = (p.value - ws.data_ptr()) // 4
+        return ws[off: off + n]
 
     def result(self):
         """Sync and slice the outputs (host round trip: for tests and hand-off, not for the hot loop)."""

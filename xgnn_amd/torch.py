@@ -19,7 +19,7 @@ for _name in ("init start num_class feat_dim num_epoch steps_per_epoch get_next_
               "report_epoch report_epoch_average report_node_access trace_step_begin trace_step_end "
               "trace_step_begin_now trace_step_end_now dump_trace forward_barrier wait_one_child log_step_by_key "
               "get_log_step_value_by_key data_init sample_init train_init extract_start num_local_step "
-              "um_sample_init switch_init feat_row_bytes").split():
+              "um_sample_init switch_init feat_row_bytes num_negative").split():
     globals()[_name] = getattr(_basics, _name)
 
 # DataType code -> (numpy typestr, torch dtype); common/common.h:38-46, adapter.cc:33-53
@@ -111,6 +111,21 @@ def get_dataset_feat(): return _get("samgraph_get_dataset_feat", None)
 def get_dataset_label(): return _get("samgraph_get_dataset_label", None)
 def get_graph_input_nodes(batch_key): return _get("samgraph_get_graph_input_nodes", batch_key)
 def get_graph_output_nodes(batch_key): return _get("samgraph_get_graph_output_nodes", batch_key)
+
+
+def get_graph_seed_ids(batch_key): return _get("samgraph_get_graph_seed_ids", batch_key)
+
+
+def get_graph_link_pairs(batch_key):
+    """(pos_src, pos_dst, neg_src, neg_dst) of a link_prediction batch: views of the batch's one id tensor
+    (get_graph_seed_ids), B positives and K negatives each -- pos_src, pos_dst of shape (B,), neg_src (pos_src expanded)
+    and neg_dst of shape (B, K).  The values are local ids into the batch's node numbering: rows of get_graph_feat /
+    get_graph_input_nodes, the ids the first sampled layer's col uses."""
+    ids = get_graph_seed_ids(batch_key)
+    k = num_negative()  # noqa: F405
+    b = ids.numel() // (2 + k)
+    pos_src, pos_dst = ids[:b], ids[b:2 * b]
+    return pos_src, pos_dst, pos_src.unsqueeze(1).expand(b, k), ids[2 * b:].view(b, k)
 
 
 def _create_dgl_block(data, num_src_nodes, num_dst_nodes):
