@@ -90,6 +90,7 @@ def test_plain_run_is_the_headline_alone_and_dumps_its_last_step(tmp_path):
     assert c[3 * 2 + 1] == 0 and ids.size == c[3 * 2] > 0 and a["layer0_row"].size == c[0] and a["layer1_col"].size == c[3]
     assert 0 < a["labels"].size <= 640 and 0 <= a["labels"].min() and a["labels"].max() < 47  # label = node id % num_class
     dim = a["features"].shape[1]
+    # (bench.py's own row form, periodic in the row number: addressing at large offsets is test_gpu_large_offsets.py's)
     assert np.array_equal(a["features"], ((ids[:, None] * dim + np.arange(dim)) & 0xFFFF).astype(np.float32))
 
 

@@ -16,7 +16,16 @@ Leaf coverage of the node-list entry points (include/ggms.h) after this file and
   ggms_extract_tiered             P 4 + replica + host tier, device count, the four counters add
   ggms_extract_dynamic / _publish device count over two batches, stamps, hit count
   ggms_owner_histogram / _bucket  n edges, P 1 .. 64, every table kind, device count (test_gpu_owner_split.py)
-Still open: the RCCL all-to-all on more than one GPU, and P > 8 through peer pointers."""
+Past 2^31 / 2^32 BYTES (test_gpu_large_offsets.py): ggms_extract, ggms_mock_extract, ggms_gather_scatter (source index,
+  dst_index scatter, dense output, identity copy, long rows), ggms_gather_scatter_convert (F16 / F32 / F8E4M3 / Q8ROW
+  sources), ggms_gather_scatter_partition, ggms_extract_cached (hit tier, miss tier, table == NULL), ggms_extract_tiered
+  (replica, remote shard, host tier), ggms_extract_dynamic / _publish (prev_feat slots and host rows), ggms_quantize_rows
+  (source and output), ggms_batch_handoff.  Past edge POSITION 2^30 and 2^31 (test_gpu_high_offset_graph.py): the khop0 /
+  khop1 / khop2 / khop3 / khop_labor leaves, random walk, ggms_sample_batch (khop3, khop0), ggms_sample_batch_prefetch,
+  ggms_khop_closure, ggms_link_seeds; the three weighted samplers at 2^31.
+Still open: the RCCL all-to-all on more than one GPU, and P > 8 through peer pointers; E within a few thousand of 2^32,
+which no test reaches (a 17 GB index array); outputs past 2^32 ROWS; bench.py's own row check, which is periodic in the
+row number (test_bench_gpu.py)."""
 import numpy as np
 import pytest
 

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import oracle
+from graphgen import torch_feature_rows
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -35,12 +36,9 @@ def u32(t, n=None):
 
 
 def feat_rows(node_ids, out, dim):
-    """feat[i, j] = float((i*dim + j) & 0xFFFF): exactly representable, so gathers compare bit for bit."""
-    cols = torch.arange(dim, dtype=torch.int64, device=out.device)
-    step = 1 << 21
-    for lo in range(0, node_ids.numel(), step):
-        ids = node_ids[lo:lo + step].to(out.device, torch.int64)
-        out[lo:lo + step] = ((ids[:, None] * dim + cols[None, :]) & 0xFFFF).to(torch.float32)
+    """Rows `node_ids` of graphgen's feature code (aperiodic, exactly representable), generated on out's device: a gather
+    that loses high bits of a row's byte offset delivers a row with other contents (test_feature_code.py)."""
+    torch_feature_rows(node_ids.to(out.device), dim, torch.float32, out=out)
 
 
 @pytest.fixture(scope="module")

@@ -3,7 +3,7 @@ import numpy as np
 import pytest
 
 import oracle
-from graphgen import hub_csr, exact_features, powerlaw_csr
+from graphgen import hub_csr, exact_features, powerlaw_csr, torch_fill_features
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -138,7 +138,7 @@ def test_extract_row_sizes_around_the_tile_sweep_limit(ops):
 def test_extract_large_properties(ops):
     """products-sized gather: checksum + idempotence (size-independent properties)."""
     N, dim, n = 2_449_029, 100, 1_190_000
-    feat = torch.arange(N * dim, dtype=torch.int32, device="cuda").bitwise_and_(0xFFFF).to(torch.float32).view(N, dim)
+    feat = torch_fill_features(torch.empty((N, dim), dtype=torch.float32, device="cuda"))
     g = torch.Generator(device="cuda").manual_seed(1)
     idx = torch.randint(0, N, (n,), dtype=torch.int32, device="cuda", generator=g)
     out = ops.extract(feat, idx)
