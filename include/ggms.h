@@ -79,11 +79,11 @@ const char *ggms_last_error(void);
  *   GGMS_STATUS_SCAN_SPIN   an ordered scan's look-back gave up waiting for a predecessor tile (protocol error);
  *   GGMS_STATUS_TABLE_FULL  the hashed dedup table had no free bucket for a key (sized too small);
  *   GGMS_STATUS_PREFETCH_FULL  ggms_sample_batch_prefetch: the expansion had more edges than its capacity
- *                              (counts_dev[3 L + 6] holds the number it needed).
+ *                              (counts_dev[GGMS_COUNT_EXPANSION(L)] holds the number it needed).
  * Results of a call that set a bit are invalid.  Two kinds of word:
  *   - every BATCH has its own: the second word behind its table's item counter (ggms_hashtable_t.num_items_dev[1],
  *     zeroed by ggms_hashtable_init).  Every kernel of a ggms_sample_batch call ORs into that word only, the
- *     batch's last kernel moves it into counts_dev[3 L + 1] (exchange with 0: the next batch on that table starts
+ *     batch's last kernel moves it into counts_dev[GGMS_COUNT_STATUS(L)] (exchange with 0: the next batch on that table starts
  *     clean) -- so with several batches in flight a failure is reported by the batch it happened in, and only by
  *     it.  A non-zero word is also ORed into the device word below;
  *   - one per DEVICE, sticky, for the leaf operators (and as the record of failed batches): it stays set until
@@ -354,15 +354,56 @@ int ggms_map_edges(const ggms_hashtable_t *ht, const ggms_id_t *global_src,
                    ggms_id_t *new_dst, size_t num_edges, ggms_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Batch counts words.  Every sampled batch of L layers carries one array of 64-bit words, on the device (counts_dev)
+ * and, in the engine, as a pinned host copy.  This is its whole layout; nothing else may index it by number.
+ *   GGMS_COUNT_EDGES(i)        [3i]      num_edge(i): row[i] / col[i] hold that many entries
+ *   GGMS_COUNT_SRC(i)          [3i + 1]  num_src(i): unique nodes after layer i
+ *   GGMS_COUNT_DST(i)          [3i + 2]  num_dst(i): size of layer i's frontier
+ *   GGMS_COUNT_INPUT(L)        [3L]      number of input nodes; the list is ht->n2o
+ *       written by ggms_sample_batch / ggms_sample_batch_prefetch, in every deployment
+ *   GGMS_COUNT_STATUS(L)       [3L + 1]  status word of THIS batch (0 = ok; "Status words" above)
+ *       written by the batch's last kernel, in every deployment
+ *   GGMS_COUNT_TIER(L, k)      [3L+2+k]  rows the feature gather served from tier k = GGMS_TIER_HOST, _REMOTE (a peer's
+ *                                        shard), _LOCAL (this GPU's shard), _REPLICA: ggms_extract_tiered's tier_rows_dev
+ *       zeroed by the engine, then ADDED to by its tiered gather (GPU cache with replicas, or a mock feature table)
+ *   GGMS_COUNT_MISS(L)         = GGMS_COUNT_TIER(L, GGMS_TIER_HOST): the batch's miss count
+ *       zeroed by the engine behind the sampler in every deployment; added to by whichever gather the engine runs
+ *       (tiered, cached, dynamic_cache), written by the host-staged path's split
+ *   GGMS_COUNT_STAGED_HIT(L)   = GGMS_COUNT_TIER(L, GGMS_TIER_REMOTE): the cached rows of the host-staged miss path
+ *       written by ggms_get_miss_cache_index_dev in the engine's host-staged extract (`gpu_extract` off) only.  A
+ *       batch is gathered EITHER by that path or by the tiered gather, never both: the two meanings never meet
+ *   GGMS_COUNT_EXPANSION(L)    [3L + 6]  edges the expansion needed
+ *       written by ggms_sample_batch_prefetch (arch4)
+ *   GGMS_COUNT_LINK_FORCED(L)  [3L + 7]  forced negatives of a link-prediction batch (ggms_link_seeds' num_forced_dev)
+ *       zeroed and passed to ggms_link_seeds by the engine, task = link_prediction
+ * (The engine's host sampler, arch0, fills the sampler's words and a zero miss count in the host copy itself.)
+ * ggms_sample_batch writes the first GGMS_COUNTS_SAMPLE_WORDS(L) words and needs no more; ggms_sample_batch_prefetch,
+ * the engine, the arch3 / arch4 hand-off and the arch5 queue work on all GGMS_COUNTS_WORDS(L).
+ * ------------------------------------------------------------------------- */
+#define GGMS_COUNTS_WORDS(L) (3 * (L) + 8)
+#define GGMS_COUNTS_SAMPLE_WORDS(L) (3 * (L) + 2)
+#define GGMS_COUNT_EDGES(i) (3 * (i))
+#define GGMS_COUNT_SRC(i) (3 * (i) + 1)
+#define GGMS_COUNT_DST(i) (3 * (i) + 2)
+#define GGMS_COUNT_INPUT(L) (3 * (L))
+#define GGMS_COUNT_STATUS(L) (3 * (L) + 1)
+#define GGMS_TIER_HOST 0
+#define GGMS_TIER_REMOTE 1
+#define GGMS_TIER_LOCAL 2
+#define GGMS_TIER_REPLICA 3
+#define GGMS_NUM_TIERS 4
+#define GGMS_COUNT_TIER(L, k) (3 * (L) + 2 + (k))
+#define GGMS_COUNT_MISS(L) GGMS_COUNT_TIER(L, GGMS_TIER_HOST)
+#define GGMS_COUNT_STAGED_HIT(L) GGMS_COUNT_TIER(L, GGMS_TIER_REMOTE)
+#define GGMS_COUNT_EXPANSION(L) (3 * (L) + 6)
+#define GGMS_COUNT_LINK_FORCED(L) (3 * (L) + 7)
+
+/* ---------------------------------------------------------------------------
  * One mini-batch of k-layer sampling -- DoGPUSample, dist/dist_loops.cc:62-368
  * (cuda/cuda_loops.cc:54-292): Reset + FillWithDupRevised(seeds), then for
  * layer i = L-1 .. 0 {sample, FillWithDuplicates, GPUMapEdges}.  Enqueued on
- * `stream` without any host round trip; all sizes are left on the device:
- *   counts_dev[3*i + 0] = num_edge(i)   row[i]/col[i] hold that many entries
- *   counts_dev[3*i + 1] = num_src(i)    (= unique nodes after layer i)
- *   counts_dev[3*i + 2] = num_dst(i)    (= size of layer i's frontier)
- *   counts_dev[3*L]     = number of input nodes; the list is ht->n2o
- *   counts_dev[3*L + 1] = status word of THIS batch (0 = ok; "Status words" above)
+ * `stream` without any host round trip; all sizes are left on the device, in
+ * counts_dev[0, GGMS_COUNTS_SAMPLE_WORDS(L)) ("Batch counts words" above).
  * row[i] = local id of the sampled neighbour, col[i] = local id of the seed
  * (TrainGraph, dist_loops.cc:303-322).  row/col are HOST arrays of L device
  * pointers with the capacities ggms_sample_batch_capacity reports; fanouts is
@@ -471,11 +512,11 @@ int ggms_link_seeds(const ggms_graph_t *graph, const ggms_id_t *edge_ids, size_t
  *   - after the second-to-last layer's table fill, every neighbour of every node entered so far (n2o[0, k)) is
  *     entered too, new nodes taking the next local ids in first-occurrence order over the concatenated lists
  *     (GPUExtractNeighbour + FillWithDupMutable); `expand_start` is recorded before that and `input_final` right
- *     after it: from then on n2o and counts_dev[3 L] hold the batch's final input nodes (NULL = no event);
+ *     after it: from then on n2o and counts_dev[GGMS_COUNT_INPUT(L)] hold the batch's final input nodes (NULL = no event);
  *   - the last layer samples from n2o[0, k), the set as it stood BEFORE the expansion, and inserts nothing: its row
  *     ids are look-ups.  It draws exactly what ggms_sample_batch's last layer draws, so every edge equals that
- *     call's for the same RNG pool, and num_src(0) = counts_dev[3 L] is the size of the superset;
- *   - counts_dev[3 L + 6] = edges of the expansion.  More than max_prefetch_edges: GGMS_STATUS_PREFETCH_FULL in
+ *     call's for the same RNG pool, and num_src(0) = counts_dev[GGMS_COUNT_INPUT(L)] is the size of the superset;
+ *   - counts_dev[GGMS_COUNT_EXPANSION(L)] = edges of the expansion.  More than max_prefetch_edges: GGMS_STATUS_PREFETCH_FULL in
  *     the batch's status word, nothing is truncated silently (the batch is invalid).
  * Sample types khop0, khop1 and weighted_khop (cuda_loops.cc:347-377), num_layer >= 2 and the direct table layout
  * only; anything else is an argument error.  ht->n2o_size >= the max_input_nodes of the capacity call.
@@ -762,14 +803,14 @@ int ggms_batch_handoff(const ggms_copy_seg_t *segs, uint32_t num_segs, ggms_stre
  * a launch: it belongs to the host's ticket protocol.  A launch timer armed on the calling thread rides on the launch.
  * ------------------------------------------------------------------------- */
 #define GGMS_QUEUE_MAX_LAYERS 16
-#define GGMS_QUEUE_MAX_COUNTS (3 * GGMS_QUEUE_MAX_LAYERS + 8)
+#define GGMS_QUEUE_MAX_COUNTS GGMS_COUNTS_WORDS(GGMS_QUEUE_MAX_LAYERS)
 typedef struct {
   uint64_t seq;        /* host only: the slot's sequence word (ticket protocol) */
   uint64_t key;        /* batch key, epoch * steps_per_epoch + global step */
   uint64_t num_output; /* output nodes (the batch's seeds) */
   uint64_t num_layer;
   uint64_t _rsv[4];
-  uint64_t counts[GGMS_QUEUE_MAX_COUNTS]; /* the first 3 * num_layer + 8 words: the batch's counts words */
+  uint64_t counts[GGMS_QUEUE_MAX_COUNTS]; /* the first GGMS_COUNTS_WORDS(num_layer): the batch's counts words */
 } ggms_queue_header_t;                    /* 512 bytes */
 typedef struct {
   uint32_t num_layer;
@@ -783,7 +824,7 @@ typedef struct {
 typedef struct { /* one batch's arrays on a device; data[i] is NULL unless the layout has_data */
   ggms_id_t *row[GGMS_QUEUE_MAX_LAYERS], *col[GGMS_QUEUE_MAX_LAYERS], *data[GGMS_QUEUE_MAX_LAYERS];
   ggms_id_t *input_nodes, *output_nodes;
-  uint64_t *counts; /* 3 * num_layer + 8 words */
+  uint64_t *counts; /* GGMS_COUNTS_WORDS(num_layer) words */
 } ggms_queue_batch_t;
 int ggms_queue_layout(ggms_queue_layout_t *layout, uint32_t num_layer, const size_t *max_edges, size_t max_input,
                       size_t max_output, int has_data);

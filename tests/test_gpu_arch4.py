@@ -11,6 +11,7 @@ import torch
 
 import oracle
 from test_engine import make_dataset
+from xgnn_amd._lib import COUNT_EXPANSION
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DRIVER4 = os.path.join(ROOT, "tests", "arch4_driver.py")
@@ -200,7 +201,7 @@ def test_prefetch_sampler_reports_an_undersized_expansion():
     bs.sample(torch.from_numpy(seeds.view(np.int32)).to(dev), distinct=True)
     with pytest.raises(GgmsError, match="0x4"):
         bs.result()
-    need = int(bs.counts[3 * 2 + 6].item())
+    need = int(bs.counts[COUNT_EXPANSION(2)].item())
     assert need == prefetch_replay(oracle.do_sample(oracle.KHOP0, ip, ix, seeds, [3, 2]), ip, ix)["expansion_edges"]
     assert need > 5000
     small = np.array([v for v in range(N) if ip[v + 1] - ip[v] < 3][:20], np.uint32)

@@ -17,6 +17,7 @@ import oracle
 from test_arch5_config import dist_shuffler_slices
 from test_engine import _check, make_dataset
 from test_gpu_arch3 import _presample_states, _weighted_dataset
+from xgnn_amd._lib import COUNTS_WORDS, COUNT_EDGES, COUNT_INPUT
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DRIVER5 = os.path.join(ROOT, "tests", "arch5_driver.py")
@@ -201,10 +202,10 @@ def test_queue_pack_unpack_leaf_against_numpy():
             n_out = [65, 0, 3, 99][trial]
             src = {name: torch.from_numpy(rng.randint(0, 1 << 31, bound, dtype=np.int64).astype(np.int32)).to(dev)
                    for name, _, bound in segs}
-            counts = rng.randint(0, 1 << 40, 3 * L + 8).astype(np.int64)
+            counts = rng.randint(0, 1 << 40, COUNTS_WORDS(L)).astype(np.int64)
             for i in range(L):
-                counts[3 * i] = edges[i]
-            counts[3 * L] = n_in
+                counts[COUNT_EDGES(i)] = edges[i]
+            counts[COUNT_INPUT(L)] = n_in
             counts_dev = torch.from_numpy(counts).to(dev)
             host[:] = 0xA5
             key = 1000 + trial
@@ -215,8 +216,8 @@ def test_queue_pack_unpack_leaf_against_numpy():
             assert hdr[0] == np.uint64(0xA5A5A5A5A5A5A5A5)  # seq: the host's
             assert (int(hdr[1]), int(hdr[2]), int(hdr[3])) == (key, min(n_out, max_output), L)
             assert (host[32:64] == 0xA5).all()
-            assert np.array_equal(hdr[8:8 + 3 * L + 8].view(np.int64), counts)
-            assert (host[64 + 8 * (3 * L + 8):512] == 0xA5).all()
+            assert np.array_equal(hdr[8:8 + COUNTS_WORDS(L)].view(np.int64), counts)
+            assert (host[64 + 8 * COUNTS_WORDS(L):512] == 0xA5).all()
             lengths = {f"{a}{i}": min(edges[i], max_edges[i]) for a in ("row", "col", "data") for i in range(L)}
             lengths.update(input=min(n_in, max_input), output=min(n_out, max_output))
             for name, off, bound in segs:
@@ -226,7 +227,7 @@ def test_queue_pack_unpack_leaf_against_numpy():
                 assert (host[off + n * 4:off + bound * 4] == 0xA5).all(), (trial, name)
             # unpack into poisoned buffers one element longer than the bound: nothing past the length is written
             dst = {name: torch.full((bound + 1,), -7, dtype=torch.int32, device=dev) for name, _, bound in segs}
-            dcounts = torch.full((3 * L + 9,), -7, dtype=torch.int64, device=dev)
+            dcounts = torch.full((COUNTS_WORDS(L) + 1,), -7, dtype=torch.int64, device=dev)
             ops.queue_unpack(dptr.value, lay, [dst[f"row{i}"] for i in range(L)], [dst[f"col{i}"] for i in range(L)],
                              [dst[f"data{i}"] for i in range(L)], dst["input"], dst["output"], dcounts)
             torch.cuda.synchronize()

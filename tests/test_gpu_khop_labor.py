@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import khop_labor_ref as ref
+from xgnn_amd._lib import COUNT_EDGES, COUNT_INPUT, COUNT_STATUS
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -152,7 +153,7 @@ def test_leaf_through_sharded_views(ops, P):
 def run_batch(ops, bs, seeds, salt, distinct):
     bs.sample(dev(seeds), distinct=distinct, labor_salt=salt)
     c = bs.counts.cpu().tolist()
-    assert c[3 * bs.L + 1] == 0  # the batch's status word
+    assert c[COUNT_STATUS(bs.L)] == 0  # the batch's status word
     return bs.result(), c
 
 
@@ -178,10 +179,10 @@ def test_batch_equals_the_reference_chain(ops, batch_graph, fanouts, direct):
         got, c = run_batch(ops, bs, seeds, salt, distinct)
         want = ref.sample_batch(ip, ix, seeds, fanouts, salt)
         np.testing.assert_array_equal(host_u32(got["input_nodes"]), want["input_nodes"])
-        assert c[3 * len(fanouts)] == want["input_nodes"].size
+        assert c[COUNT_INPUT(len(fanouts))] == want["input_nodes"].size
         for i in range(len(fanouts)):
             gl, wl = got["layers"][i], want["layers"][i]
-            assert (c[3 * i], gl["num_src"], gl["num_dst"]) == (wl["row"].size, wl["num_src"], wl["num_dst"]), (rep, i)
+            assert (c[COUNT_EDGES(i)], gl["num_src"], gl["num_dst"]) == (wl["row"].size, wl["num_src"], wl["num_dst"]), (rep, i)
             np.testing.assert_array_equal(host_u32(gl["row"]), wl["row"], err_msg=f"row layer {i} rep {rep}")
             np.testing.assert_array_equal(host_u32(gl["col"]), wl["col"], err_msg=f"col layer {i} rep {rep}")
 

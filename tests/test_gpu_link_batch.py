@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import link_ref as ref
+from xgnn_amd._lib import COUNT_STATUS
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -67,7 +68,7 @@ def test_seed_ids_are_the_first_occurrence_ranks(ops, graph, name, direct):
         bs.sample(seeds_dev, distinct=False, labor_salt=rep)
         ids = host_u32(bs.seed_ids().clone())
         got = bs.result()
-        assert bs.counts.cpu().tolist()[3 * L + 1] == 0
+        assert bs.counts.cpu().tolist()[COUNT_STATUS(L)] == 0
         want_ids, uniq = ref.first_occurrence_ranks(seeds)
         np.testing.assert_array_equal(ids, want_ids)
         nodes = host_u32(got["input_nodes"])

@@ -4,6 +4,7 @@ import pytest
 
 import oracle
 from graphgen import hub_csr, exact_features, powerlaw_csr, torch_fill_features
+from xgnn_amd._lib import COUNT_DST, COUNT_EDGES, COUNT_INPUT, COUNT_SRC
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -731,12 +732,12 @@ def test_batches_in_flight_keep_batch_order(ops, stype):
     for b in range(NB):
         want = oracle.do_sample(ocode, ip, ix, seeds[b], fanouts, orc_states)
         c = bs.counts_slots[b].cpu().tolist()
-        np.testing.assert_array_equal(host_u32(bs.input_nodes[b], c[3 * len(fanouts)]), want["input_nodes"])
+        np.testing.assert_array_equal(host_u32(bs.input_nodes[b], c[COUNT_INPUT(len(fanouts))]), want["input_nodes"])
         for i in range(len(fanouts)):
             wl = want["layers"][i]
-            assert (c[3 * i], c[3 * i + 1], c[3 * i + 2]) == (wl["row"].size, wl["num_src"], wl["num_dst"]), (b, i)
-            np.testing.assert_array_equal(host_u32(bs.rows[b][i], c[3 * i]), wl["row"], err_msg=f"row {b}/{i}")
-            np.testing.assert_array_equal(host_u32(bs.cols[b][i], c[3 * i]), wl["col"], err_msg=f"col {b}/{i}")
+            assert (c[COUNT_EDGES(i)], c[COUNT_SRC(i)], c[COUNT_DST(i)]) == (wl["row"].size, wl["num_src"], wl["num_dst"]), (b, i)
+            np.testing.assert_array_equal(host_u32(bs.rows[b][i], c[COUNT_EDGES(i)]), wl["row"], err_msg=f"row {b}/{i}")
+            np.testing.assert_array_equal(host_u32(bs.cols[b][i], c[COUNT_EDGES(i)]), wl["col"], err_msg=f"col {b}/{i}")
     np.testing.assert_array_equal(host_u32(t_ix), ix)
 
 

@@ -7,6 +7,7 @@ import pytest
 import oracle
 import test_gpu_parity as P
 from graphgen import powerlaw_csr
+from xgnn_amd._lib import COUNT_DST, COUNT_EDGES, COUNT_INPUT, COUNT_SRC, COUNT_STATUS
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -90,13 +91,13 @@ def test_a_failed_batch_reports_its_own_status_and_only_it(ops):
         with torch.cuda.stream(streams[b % 2]):
             bs.sample(t_seeds[b], slot=b, copy_input_nodes=True)
     torch.cuda.synchronize()
-    st = [int(bs.counts_slots[b][3 * L + 1].item()) for b in range(2)]
+    st = [int(bs.counts_slots[b][COUNT_STATUS(L)].item()) for b in range(2)]
     assert st[0] & 2 and st[1] == 0, st
     assert ops.device_status(clear=True) & 2  # the sticky record of the failed batch
     # the clean neighbour's results are what the one-at-a-time loop gives for batch 1 AFTER batch 0's draws: the RNG
     # pool is consumed in batch order whatever happened to batch 0's table -- so check it structurally instead
     c = bs.counts_slots[1].cpu().tolist()
-    inp = P.host_u32(bs.input_nodes[1], c[3 * L])
+    inp = P.host_u32(bs.input_nodes[1], c[COUNT_INPUT(L)])
     assert np.unique(inp).size == inp.size and np.array_equal(inp[:nseed], seeds[1])
     # the same table, full size again: its next batch is clean (the failed batch's last kernel took the word)
     bs.hts[0].c.o2n_size = full_size
@@ -104,7 +105,7 @@ def test_a_failed_batch_reports_its_own_status_and_only_it(ops):
         with torch.cuda.stream(streams[b % 2]):
             bs.sample(t_seeds[b], slot=b, copy_input_nodes=True)
     torch.cuda.synchronize()
-    assert [int(bs.counts_slots[b][3 * L + 1].item()) for b in (2, 3)] == [0, 0]
+    assert [int(bs.counts_slots[b][COUNT_STATUS(L)].item()) for b in (2, 3)] == [0, 0]
     assert ops.device_status() == 0
 
 
@@ -196,13 +197,13 @@ def test_distinct_seed_batches_in_flight(ops):
     for b in range(NB):
         want = oracle.do_sample(oracle.KHOP3, ip, ix, seeds[b], fanouts, orc_states)
         c = bs.counts_slots[b].cpu().tolist()
-        assert c[3 * len(fanouts) + 1] == 0
-        np.testing.assert_array_equal(P.host_u32(bs.input_nodes[b], c[3 * len(fanouts)]), want["input_nodes"])
+        assert c[COUNT_STATUS(len(fanouts))] == 0
+        np.testing.assert_array_equal(P.host_u32(bs.input_nodes[b], c[COUNT_INPUT(len(fanouts))]), want["input_nodes"])
         for i in range(len(fanouts)):
             wl = want["layers"][i]
-            assert (c[3 * i], c[3 * i + 1], c[3 * i + 2]) == (wl["row"].size, wl["num_src"], wl["num_dst"]), (b, i)
-            np.testing.assert_array_equal(P.host_u32(bs.rows[b][i], c[3 * i]), wl["row"], err_msg=f"row {b}/{i}")
-            np.testing.assert_array_equal(P.host_u32(bs.cols[b][i], c[3 * i]), wl["col"], err_msg=f"col {b}/{i}")
+            assert (c[COUNT_EDGES(i)], c[COUNT_SRC(i)], c[COUNT_DST(i)]) == (wl["row"].size, wl["num_src"], wl["num_dst"]), (b, i)
+            np.testing.assert_array_equal(P.host_u32(bs.rows[b][i], c[COUNT_EDGES(i)]), wl["row"], err_msg=f"row {b}/{i}")
+            np.testing.assert_array_equal(P.host_u32(bs.cols[b][i], c[COUNT_EDGES(i)]), wl["col"], err_msg=f"col {b}/{i}")
 
 
 # ------------------------------------------------------------------ sharded topology (DeviceDistGraph)

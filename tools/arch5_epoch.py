@@ -74,14 +74,14 @@ def rate(a):
 
     s = C.c_void_p(stream.cuda_stream)
     for fill in a.fill:
-        counts = np.zeros(3 * L + 8, np.int64)
+        counts = np.zeros(_lib.COUNTS_WORDS(L), np.int64)
         for i in range(L):
-            counts[3 * i] = int(me[i] * fill)
-        counts[3 * L] = int(mu.value * fill)
+            counts[_lib.COUNT_EDGES(i)] = int(me[i] * fill)
+        counts[_lib.COUNT_INPUT(L)] = int(mu.value * fill)
         n_out = int(max_seeds * fill)
         counts_dev = torch.from_numpy(counts).to(dev)
         dcounts = torch.empty_like(counts_dev)
-        moved = (sum(2 * counts[3 * i] for i in range(L)) + counts[3 * L] + n_out) * 4 + 8 * (3 * L + 8)
+        moved = (sum(2 * counts[_lib.COUNT_EDGES(i)] for i in range(L)) + counts[_lib.COUNT_INPUT(L)] + n_out) * 4 + 8 * counts.size
 
         def pack():
             ops.queue_pack(dptr.value, lay, rows, cols, [None] * L, inp, outn, counts_dev, 1, n_out)
@@ -105,8 +105,8 @@ def rate(a):
         dinp.zero_()
         unpack()
         torch.cuda.synchronize()
-        n_in = int(counts[3 * L])
-        assert torch.equal(dinp[:n_in], inp[:n_in]) and torch.equal(drows[-1][:counts[3 * (L - 1)]], rows[-1][:counts[3 * (L - 1)]])
+        n_in, e_last = int(counts[_lib.COUNT_INPUT(L)]), counts[_lib.COUNT_EDGES(L - 1)]
+        assert torch.equal(dinp[:n_in], inp[:n_in]) and torch.equal(drows[-1][:e_last], rows[-1][:e_last])
         med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
         out["results"].append({
             "fill": fill, "bytes_moved": int(moved),

@@ -24,6 +24,7 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from xgnn_amd import datagen, ops  # noqa: E402
+from xgnn_amd._lib import COUNT_EDGES, COUNT_INPUT, COUNT_STATUS  # noqa: E402
 import khop_labor_ref as ref  # noqa: E402
 
 
@@ -64,12 +65,12 @@ class Run:
     def gather(self, slot):
         c = self.bs.counts_slots[slot]
         ops.gather_scatter(self.out[slot], self.feat, self.bs.input_nodes[slot], None, num=self.bs.max_unique,
-                           num_dev=c[3 * self.L:3 * self.L + 1])
+                           num_dev=c[COUNT_INPUT(self.L):COUNT_INPUT(self.L) + 1])
 
     def counts(self, slot):
         c = self.bs.counts_slots[slot].cpu().tolist()
-        assert c[3 * self.L + 1] == 0, "batch status word"
-        return c[3 * self.L], sum(c[3 * i] for i in range(self.L))
+        assert c[COUNT_STATUS(self.L)] == 0, "batch status word"
+        return c[COUNT_INPUT(self.L)], sum(c[COUNT_EDGES(i)] for i in range(self.L))
 
     def timed(self, fn, steps):
         torch.cuda.synchronize()

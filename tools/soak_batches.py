@@ -16,6 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import oracle  # noqa: E402
 from xgnn_amd import datagen, ops  # noqa: E402
+from xgnn_amd._lib import COUNT_DST, COUNT_EDGES, COUNT_INPUT, COUNT_SRC, COUNT_STATUS  # noqa: E402
 
 if os.environ.get("GGMS_TEST_SCAN_PATIENCE") is not None:  # 0: every look-back that finds a word missing serves itself
     from xgnn_amd import lib  # noqa: E402
@@ -62,15 +63,15 @@ for fanouts in ([5, 5, 5], [10, 5]) if walk else ([25, 10], [5, 10, 15]):
     for b in range(nb):
         want = oracle.do_sample(ocode, ip, ix, seeds[b], fanouts, states, **okw)
         c = bs.counts_slots[b].cpu().tolist()
-        assert c[3 * L + 1] == 0, (fanouts, b, "batch status word", c[3 * L + 1])
-        assert np.array_equal(u32(bs.input_nodes[b], c[3 * L]), want["input_nodes"]), (fanouts, b, "input_nodes")
+        assert c[COUNT_STATUS(L)] == 0, (fanouts, b, "batch status word", c[COUNT_STATUS(L)])
+        assert np.array_equal(u32(bs.input_nodes[b], c[COUNT_INPUT(L)]), want["input_nodes"]), (fanouts, b, "input_nodes")
         for i in range(L):
             wl = want["layers"][i]
-            assert (c[3 * i], c[3 * i + 1], c[3 * i + 2]) == (wl["row"].size, wl["num_src"], wl["num_dst"]), (fanouts, b, i)
-            assert np.array_equal(u32(bs.rows[b][i], c[3 * i]), wl["row"]), (fanouts, b, i, "row")
-            assert np.array_equal(u32(bs.cols[b][i], c[3 * i]), wl["col"]), (fanouts, b, i, "col")
+            assert (c[COUNT_EDGES(i)], c[COUNT_SRC(i)], c[COUNT_DST(i)]) == (wl["row"].size, wl["num_src"], wl["num_dst"]), (fanouts, b, i)
+            assert np.array_equal(u32(bs.rows[b][i], c[COUNT_EDGES(i)]), wl["row"]), (fanouts, b, i, "row")
+            assert np.array_equal(u32(bs.cols[b][i], c[COUNT_EDGES(i)]), wl["col"]), (fanouts, b, i, "col")
             if walk:
-                assert np.array_equal(u32(bs.datas[b][i], c[3 * i]), wl["data"]), (fanouts, b, i, "data")
+                assert np.array_equal(u32(bs.datas[b][i], c[COUNT_EDGES(i)]), wl["data"]), (fanouts, b, i, "data")
     print(f"soak ok: {stype} {fanouts}: {nb} batches of 8000 seeds on {K} pipelines, all equal to the oracle "
           f"({time.time() - t0:.1f} s)", flush=True)
     del bs

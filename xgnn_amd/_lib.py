@@ -43,6 +43,23 @@ class CopySeg(C.Structure):
 _QL = 16  # GGMS_QUEUE_MAX_LAYERS
 
 
+# "Batch counts words" of include/ggms.h, name for name (GGMS_ dropped); tests/test_counts_layout.py holds the two equal
+def COUNTS_WORDS(L): return 3 * L + 8
+def COUNTS_SAMPLE_WORDS(L): return 3 * L + 2
+def COUNT_EDGES(i): return 3 * i
+def COUNT_SRC(i): return 3 * i + 1
+def COUNT_DST(i): return 3 * i + 2
+def COUNT_INPUT(L): return 3 * L
+def COUNT_STATUS(L): return 3 * L + 1
+TIER_HOST, TIER_REMOTE, TIER_LOCAL, TIER_REPLICA = range(4)
+def COUNT_TIER(L, k): return 3 * L + 2 + k
+def COUNT_MISS(L): return COUNT_TIER(L, TIER_HOST)
+def COUNT_STAGED_HIT(L): return COUNT_TIER(L, TIER_REMOTE)
+def COUNT_EXPANSION(L): return 3 * L + 6
+def COUNT_LINK_FORCED(L): return 3 * L + 7
+QUEUE_MAX_COUNTS = COUNTS_WORDS(_QL)
+
+
 class QueueLayout(C.Structure):
     """ggms_queue_layout_t"""
     _fields_ = [("num_layer", C.c_uint32), ("has_data", C.c_uint32), ("max_edges", C.c_uint64 * _QL),

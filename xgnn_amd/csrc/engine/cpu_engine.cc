@@ -251,7 +251,7 @@ void Engine::CpuInit() { // CPUEngine::Init, cpu_engine.cc:50-110
     b->trainer.output_nodes = (uint32_t *)alloc(max_seeds_ * 4);
     b->feat = alloc(max_unique_ * row_bytes);
     b->label = (int64_t *)alloc(max_seeds_ * 8);
-    b->counts = (uint64_t *)std::calloc(3 * L + 8, 8);
+    b->counts = (uint64_t *)std::calloc(GGMS_COUNTS_WORDS(L), 8);
     if (gpu) {
       auto &S = C.staging[s];
       S.row.resize(L); S.col.resize(L);
@@ -322,16 +322,16 @@ bool Engine::CpuEnqueueOne(bool background) {
     const size_t num_unique = C.table->NumItems();
     uint32_t *row = gpu ? S->row[i].data() : b->trainer.row[i], *col = gpu ? S->col[i].data() : b->trainer.col[i];
     C.table->MapEdges(C.tmp_src.data(), C.tmp_dst.data(), n_out, col, row); // row = new_dst, col = new_src (:151-160)
-    b->counts[3 * i + 0] = n_out;
-    b->counts[3 * i + 1] = num_unique;
-    b->counts[3 * i + 2] = n_in;
+    b->counts[GGMS_COUNT_EDGES(i)] = n_out;
+    b->counts[GGMS_COUNT_SRC(i)] = num_unique;
+    b->counts[GGMS_COUNT_DST(i)] = n_in;
     edges += n_out;
     C.cur.assign(C.table->Unique(), C.table->Unique() + num_unique);
   }
   b->num_input = C.cur.size();
-  b->counts[3 * L] = b->num_input;
-  b->counts[3 * L + 1] = 0;
-  b->counts[3 * L + 2] = 0;
+  b->counts[GGMS_COUNT_INPUT(L)] = b->num_input;
+  b->counts[GGMS_COUNT_STATUS(L)] = 0;
+  b->counts[GGMS_COUNT_MISS(L)] = 0;
   uint32_t *input_nodes = gpu ? S->input_nodes.data() : b->trainer.input_nodes;
   std::memcpy(input_nodes, C.cur.data(), b->num_input * 4);
   const double sample_s = Seconds(t_sample);
@@ -346,8 +346,8 @@ bool Engine::CpuEnqueueOne(bool background) {
   if (gpu) {
     SAM_HIP(hipSetDevice(device_));
     for (uint32_t i = 0; i < L; ++i) {
-      SAM_HIP(hipMemcpyAsync(b->trainer.row[i], S->row[i].data(), b->counts[3 * i] * 4, hipMemcpyHostToDevice, stream_));
-      SAM_HIP(hipMemcpyAsync(b->trainer.col[i], S->col[i].data(), b->counts[3 * i] * 4, hipMemcpyHostToDevice, stream_));
+      SAM_HIP(hipMemcpyAsync(b->trainer.row[i], S->row[i].data(), b->counts[GGMS_COUNT_EDGES(i)] * 4, hipMemcpyHostToDevice, stream_));
+      SAM_HIP(hipMemcpyAsync(b->trainer.col[i], S->col[i].data(), b->counts[GGMS_COUNT_EDGES(i)] * 4, hipMemcpyHostToDevice, stream_));
     }
     SAM_HIP(hipMemcpyAsync(b->trainer.input_nodes, input_nodes, b->num_input * 4, hipMemcpyHostToDevice, stream_));
     SAM_HIP(hipMemcpyAsync(b->trainer.output_nodes, seeds, num_seeds * 4, hipMemcpyHostToDevice, stream_));

@@ -1048,7 +1048,7 @@ void Engine::Presample() {
   uint64_t *d_counts = nullptr;
   SAM_HIP(hipMalloc((void **)&d_train, std::max<size_t>(n_train, 1) * 4));
   SAM_HIP(hipMalloc((void **)&d_freq, ds.num_node * 4));
-  SAM_HIP(hipMalloc((void **)&d_counts, (3 * L + 8) * 8));
+  SAM_HIP(hipMalloc((void **)&d_counts, CountsBytes(L)));
   SAM_HIP(hipMemsetAsync(d_freq, 0, ds.num_node * 4, stream_));
   // presample_static: visit stamps + the closure + its workspace, about 3 x 4 B x num_node, freed before BuildCache
   uint32_t *d_visit = nullptr, *d_closure = nullptr;
@@ -1090,7 +1090,7 @@ void Engine::Presample() {
       // pipeline 0's table: its version stamp keeps counting when the training batches follow
       SAM_GGMS(ggms_sample_batch(cfg.sample_type, &graph_, d_train + off, size, cfg.fanout.data(), L, &pipes_[0].ht,
                                  states_, num_states_, row.data(), col.data(), d_counts, &extra, ws_, ws_bytes_, stream_));
-      SAM_GGMS(ggms_count_nodes(d_freq, pipes_[0].ht.n2o, max_unique_, d_counts + 3 * L, stream_));
+      SAM_GGMS(ggms_count_nodes(d_freq, pipes_[0].ht.n2o, max_unique_, d_counts + GGMS_COUNT_INPUT(L), stream_));
     }
     SAM_HIP(hipStreamSynchronize(stream_)); // `data` is reshuffled on the host next
   }
@@ -1309,8 +1309,8 @@ void BatchArrays::Alloc(const std::vector<size_t> &max_edges, size_t max_unique,
   }
   SAM_HIP(hipMalloc((void **)&input_nodes, max_unique * 4));
   SAM_HIP(hipMalloc((void **)&output_nodes, max_seeds * 4));
-  SAM_HIP(hipMalloc((void **)&counts_dev, (3 * L + 8) * 8));
-  SAM_HIP(hipMemset(counts_dev, 0, (3 * L + 8) * 8));
+  SAM_HIP(hipMalloc((void **)&counts_dev, CountsBytes(L)));
+  SAM_HIP(hipMemset(counts_dev, 0, CountsBytes(L)));
 }
 
 ggms_queue_batch_t BatchArrays::View() const {
@@ -1378,8 +1378,8 @@ void Engine::TrainInit(int worker_id, const std::string &ctx) {
       SAM_HIP(hipHostMalloc(&b->miss_rows_host, max_unique_ * row_bytes));
       SAM_HIP(hipHostMalloc((void **)&b->miss_ids_host, max_unique_ * 4));
     }
-    SAM_HIP(hipHostMalloc((void **)&b->counts, (3 * L + 8) * 8));
-    std::memset(b->counts, 0, (3 * L + 8) * 8);
+    SAM_HIP(hipHostMalloc((void **)&b->counts, CountsBytes(L)));
+    std::memset(b->counts, 0, CountsBytes(L));
     SAM_HIP(hipEventCreateWithFlags(&b->ev_seeds, hipEventDisableTiming));
     SAM_HIP(hipEventCreateWithFlags(&b->ev_label, hipEventDisableTiming));
     SAM_HIP(hipEventCreate(&b->ev_xstart));
@@ -1523,8 +1523,8 @@ void Engine::SampleInto(Batch *b, Pipe &P) {
   if (cfg.link_prediction) {
     // edge ids -> sources, destinations, negatives, straight into the batch's output nodes.  The salt follows the
     // batch's key like khop_labor's: a batch is a function of its key, whatever pipeline draws it.  The forced count
-    // takes a spare counts word and travels to the host with the counts.
-    uint64_t *forced = s.counts_dev + 3 * L + 7;
+    // travels to the host with the counts.
+    uint64_t *forced = s.counts_dev + GGMS_COUNT_LINK_FORCED(L);
     SAM_HIP(hipMemsetAsync(forced, 0, 8, P.stream));
     const uint32_t salt = ggms::fmix32(extra.labor_salt ^ 0x6c696e6bu);
     SAM_GGMS(ggms_link_seeds(&graph_, b->edge_ids, b->num_pos, cfg.num_negative, cfg.negative_mode, salt, s.output_nodes,
@@ -1555,14 +1555,14 @@ void Engine::SampleInto(Batch *b, Pipe &P) {
     SAM_GGMS(ggms_sample_batch_seed_ids(cfg.sample_type, b->num_seeds, cfg.fanout.data(), L, &extra, P.ws, &ids));
     SAM_HIP(hipMemcpyAsync(b->seed_ids, ids, b->num_seeds * 4, hipMemcpyDeviceToDevice, P.stream));
   }
-  SAM_HIP(hipMemsetAsync(s.counts_dev + 3 * L + 2, 0, 8, P.stream)); // the trainer's miss count starts at 0
+  SAM_HIP(hipMemsetAsync(s.counts_dev + GGMS_COUNT_MISS(L), 0, 8, P.stream)); // the trainer's miss count starts at 0
   SAM_HIP(hipEventRecord(b->ev_sampled, P.stream));
 }
 
 // the labels and the feature rows of batch b, sampled on stream ss; then b goes to the pool
 void Engine::EnqueueGather(Batch *b, hipStream_t ss) {
   const uint32_t L = (uint32_t)cfg.fanout.size();
-  uint64_t *n_in = b->trainer.counts_dev + 3 * L, *n_miss = n_in + 2; // [3L + 1] = the batch's status word
+  uint64_t *n_in = b->trainer.counts_dev + GGMS_COUNT_INPUT(L), *n_miss = b->trainer.counts_dev + GGMS_COUNT_MISS(L);
   // arch3: everything from here on runs on the trainer GPU, on the batch's extract stream -- hand-off, labels, rows,
   // counts -- and the sampling stream is left to the sampler.  arch5: the same on the trainer's GPU, starting with the
   // unpack of the batch's queue slot (there is no sampling stream)
@@ -1585,7 +1585,7 @@ void Engine::EnqueueGather(Batch *b, hipStream_t ss) {
   static const bool lean_off = [] { const char *e = getenv("SAMGRAPH_LEAN_EXTRACT"); return e && e[0] == '0'; }(); // A/B hook
   b->lean = !lean_off && !StagedHostTier() && !gather_counts && !node_access_dev_;
   if (!remote && b->lean) {
-    SAM_HIP(hipMemcpyAsync(b->counts, b->trainer.counts_dev, (3 * L + 8) * 8, hipMemcpyDeviceToHost, ss));
+    SAM_HIP(hipMemcpyAsync(b->counts, b->trainer.counts_dev, CountsBytes(L), hipMemcpyDeviceToHost, ss));
     SAM_HIP(hipEventRecord(b->ev_done, ss)); // labels and counts are out; the rows: gather_timer
   } else if (!remote) {
     SAM_HIP(hipEventRecord(b->ev_label, ss));
@@ -1624,7 +1624,7 @@ void Engine::EnqueueGather(Batch *b, hipStream_t ss) {
     SAM_GGMS(ggms_extract_dynamic(b->feat, b->trainer.input_nodes, max_unique_, n_in, dyn_stamps_, dyn_seq,
                                   dyn_prev_ ? dyn_prev_->feat : nullptr, feat_src_, ds.feat_dim, ds.feat_dtype, n_miss, xs));
   } else if (cfg.UseGPUCache() && (mock || num_replica_)) { // every tier in one gather; rows per tier counted
-    if (gather_counts) SAM_HIP(hipMemsetAsync(n_miss, 0, 4 * 8, xs)); // {host, remote shard, local shard, replica} = counts[3L+2 .. 3L+5]
+    if (gather_counts) SAM_HIP(hipMemsetAsync(n_miss, 0, GGMS_NUM_TIERS * 8, xs)); // every GGMS_COUNT_TIER word
     ggms_feature_tiers_t tiers{};
     tiers.table = cache_table_;
     tiers.replica = d_replica_;
@@ -1662,10 +1662,10 @@ void Engine::EnqueueGather(Batch *b, hipStream_t ss) {
     if (node_access_dev_) // Profiler::LogNodeAccess (profiler.cc:570-575): visits per node, counted on the device
       SAM_GGMS(ggms_count_nodes(node_access_dev_, b->trainer.input_nodes, max_unique_, n_in, xs));
     if (!remote) SAM_HIP(hipStreamWaitEvent(xs, b->ev_label, 0)); // the batch is complete when its labels are, too
-    SAM_HIP(hipMemcpyAsync(b->counts, b->trainer.counts_dev, (3 * L + 8) * 8, hipMemcpyDeviceToHost, xs));
+    SAM_HIP(hipMemcpyAsync(b->counts, b->trainer.counts_dev, CountsBytes(L), hipMemcpyDeviceToHost, xs));
     SAM_HIP(hipEventRecord(b->ev_done, xs));
   } else if (remote) { // counts of T (the gather may have added to them) to the host behind the rows
-    SAM_HIP(hipMemcpyAsync(b->counts, b->trainer.counts_dev, (3 * L + 8) * 8, hipMemcpyDeviceToHost, xs));
+    SAM_HIP(hipMemcpyAsync(b->counts, b->trainer.counts_dev, CountsBytes(L), hipMemcpyDeviceToHost, xs));
     SAM_HIP(hipEventRecord(b->ev_done, xs));
   }
   {
@@ -1678,7 +1678,7 @@ void Engine::EnqueueGather(Batch *b, hipStream_t ss) {
 // arch3: DoGraphCopy + DoIdCopy (cuda/cuda_loops.cc:600-655) as one launch on the trainer GPU's extract stream.  Every
 // length is read by the kernel from the sampler's counts words (the output nodes' from the host: the shuffler knows
 // it), so the batch is still enqueued without a host round trip.  The counts words themselves are the last segment:
-// the status word [3L + 1] and the zeroed miss count travel with them.
+// the status word and the zeroed miss count travel with them.
 // arch4 splits it: kHandoffIds (input nodes, their count, the seeds) at "input set final", kHandoffGraph (the COO and the
 // other counts words, the trainer's miss count left alone) at the sampler's end.
 void Engine::Handoff(Batch *b, hipStream_t xs, HandoffPart part) {
@@ -1691,28 +1691,31 @@ void Engine::Handoff(Batch *b, hipStream_t xs, HandoffPart part) {
     segs[n++] = ggms_copy_seg_t{src, dst, count_dev, count_host, max_count, elem_bytes, 0};
   };
   const BatchArrays &s = b->sampler, &t = b->trainer;
+  // counts words [first, last]; a segment starts 16-byte aligned: at the even word at or before `first`, so one word
+  // more may travel -- each call says why that word is harmless
+  auto add_counts = [&](uint32_t first, uint32_t last) {
+    const uint32_t w = first & ~1u;
+    add(s.counts_dev + w, t.counts_dev + w, nullptr, last + 1 - w, last + 1 - w, 8);
+  };
   if (part == kHandoffIds) {
-    add(s.input_nodes, t.input_nodes, s.counts_dev + 3 * L, 0, max_unique_, 4);
+    add(s.input_nodes, t.input_nodes, s.counts_dev + GGMS_COUNT_INPUT(L), 0, max_unique_, 4);
     add(s.output_nodes, t.output_nodes, nullptr, b->num_seeds, max_seeds_, 4);
-    // (segments start 16-byte aligned: from the even word at or before [3L]; [3L - 1] is num_dst(L - 1) = |seeds|)
-    const uint32_t w0 = (3 * L) & ~1u;
-    add(s.counts_dev + w0, t.counts_dev + w0, nullptr, 3 * L + 1 - w0, 3 * L + 1 - w0, 8);
+    add_counts(GGMS_COUNT_INPUT(L), GGMS_COUNT_INPUT(L)); // (the word before it is GGMS_COUNT_DST(L - 1) = |seeds|)
     SAM_GGMS(ggms_batch_handoff(segs, n, xs));
     return;
   }
   for (uint32_t i = 0; i < L; ++i) {
-    add(s.row[i], t.row[i], s.counts_dev + 3 * i, 0, max_edges_[i], 4);
-    add(s.col[i], t.col[i], s.counts_dev + 3 * i, 0, max_edges_[i], 4);
-    if (s.data[i]) add(s.data[i], t.data[i], s.counts_dev + 3 * i, 0, max_edges_[i], 4);
+    add(s.row[i], t.row[i], s.counts_dev + GGMS_COUNT_EDGES(i), 0, max_edges_[i], 4);
+    add(s.col[i], t.col[i], s.counts_dev + GGMS_COUNT_EDGES(i), 0, max_edges_[i], 4);
+    if (s.data[i]) add(s.data[i], t.data[i], s.counts_dev + GGMS_COUNT_EDGES(i), 0, max_edges_[i], 4);
   }
-  if (part == kHandoffGraph) { // counts [0, 3L + 2) (status included) and the expansion's edge count [3L + 6]
-    add(s.counts_dev, t.counts_dev, nullptr, 3 * L + 2, 3 * L + 2, 8);
-    const uint32_t w6 = (3 * L + 6) & ~1u; // (aligned as above: [3L + 5] is a tier counter arch4 does not use)
-    add(s.counts_dev + w6, t.counts_dev + w6, nullptr, 3 * L + 7 - w6, 3 * L + 7 - w6, 8);
+  if (part == kHandoffGraph) { // what the sampler wrote (status included) and the expansion's edge count
+    add_counts(0, GGMS_COUNT_STATUS(L));
+    add_counts(GGMS_COUNT_EXPANSION(L), GGMS_COUNT_EXPANSION(L)); // (the word before it is a tier counter arch4 does not use)
   } else {
-    add(s.input_nodes, t.input_nodes, s.counts_dev + 3 * L, 0, max_unique_, 4);
+    add(s.input_nodes, t.input_nodes, s.counts_dev + GGMS_COUNT_INPUT(L), 0, max_unique_, 4);
     add(s.output_nodes, t.output_nodes, nullptr, b->num_seeds, max_seeds_, 4);
-    add(s.counts_dev, t.counts_dev, nullptr, 3 * L + 8, 3 * L + 8, 8);
+    add_counts(0, GGMS_COUNTS_WORDS(L) - 1);
   }
   SAM_GGMS(ggms_launch_timer_arm(b->handoff_timer)); // kLogL2GraphCopyTime: the hand-off's own time
   SAM_GGMS(ggms_batch_handoff(segs, n, xs));
@@ -1751,19 +1754,19 @@ void Engine::Finish(Batch *b, Batch *prev) {
     }
   }
   const uint32_t L = (uint32_t)cfg.fanout.size();
-  b->num_input = b->counts[3 * L];
-  b->num_miss = b->counts[3 * L + 2];
+  b->num_input = b->counts[GGMS_COUNT_INPUT(L)];
+  b->num_miss = b->counts[GGMS_COUNT_MISS(L)];
   if (b->dyn_hold) { // this batch's gather is complete: the batch it read may go
     b->dyn_hold->refs.fetch_sub(1);
     b->dyn_hold = nullptr;
   }
-  if (cfg.arch == kArch4 && (b->counts[3 * L + 1] & GGMS_STATUS_PREFETCH_FULL))
+  if (cfg.arch == kArch4 && (b->counts[GGMS_COUNT_STATUS(L)] & GGMS_STATUS_PREFETCH_FULL))
     fatal(__FILE__, __LINE__, "arch4: batch " + std::to_string(b->key) + ": the expansion needed " +
-                                  std::to_string(b->counts[3 * L + 6]) + " edges, capacity " +
+                                  std::to_string(b->counts[GGMS_COUNT_EXPANSION(L)]) + " edges, capacity " +
                                   std::to_string(max_prefetch_edges_) + " (config key prefetch_max_edges)");
-  CheckBatchStatus(b->counts[3 * L + 1], b->key);
+  CheckBatchStatus(b->counts[GGMS_COUNT_STATUS(L)], b->key);
   if (cfg.link_prediction) { // negatives whose eight candidates were all rejected, per epoch
-    link_forced_ += b->counts[3 * L + 7];
+    link_forced_ += b->counts[GGMS_COUNT_LINK_FORCED(L)];
     if (b->key % num_global_step_ == num_global_step_ - 1) {
       log_info("link_prediction: epoch " + std::to_string(b->key / num_global_step_) + ": " + std::to_string(link_forced_) +
                " forced negatives of " + std::to_string(ds.num_train_edge * cfg.num_negative));
@@ -1777,7 +1780,7 @@ void Engine::Finish(Batch *b, Batch *prev) {
   else (void)hipEventElapsedTime(&ms_copy, b->ev_xstart, b->ev_done); // not from ev_sampled: that would add the queueing behind the previous extract
   const double s_copy_epoch = b->lean ? us_busy * 1e-6 : ms_copy * 1e-3;
   uint64_t edges = 0;
-  for (uint32_t i = 0; i < L; ++i) edges += b->counts[3 * i];
+  for (uint32_t i = 0; i < L; ++i) edges += b->counts[GGMS_COUNT_EDGES(i)];
   // feature bytes: what the gather wrote to the batch (rows in the delivered dtype); miss bytes: what it read from the
   // host tier (rows in the table's dtype)
   const double out_row_bytes = (double)batch_feat_row_bytes();

@@ -165,11 +165,13 @@ class Profiler {
   std::mutex mu_;
 };
 
+inline size_t CountsBytes(size_t L) { return GGMS_COUNTS_WORDS(L) * sizeof(uint64_t); } // a batch's counts words
+
 // ---- the arrays of one sampled batch on one device ------------------------------
 struct BatchArrays {
   std::vector<uint32_t *> row, col, data; // per layer; data: random walk only (else null)
   uint32_t *input_nodes = nullptr, *output_nodes = nullptr;
-  uint64_t *counts_dev = nullptr; // 3L+8: counts, status, then rows per tier {host miss, remote, local, replica}
+  uint64_t *counts_dev = nullptr; // GGMS_COUNTS_WORDS(L) words (include/ggms.h, "Batch counts words")
   // hipMalloc on the current device at the batch bounds (Engine::ComputeBounds); counts_dev starts zeroed
   void Alloc(const std::vector<size_t> &max_edges, size_t max_unique, size_t max_seeds, bool with_data);
   ggms_queue_batch_t View() const; // (arch5: the batch as the queue kernels take it)

@@ -58,9 +58,9 @@ size_t samgraph_feat_row_bytes(int delivered) {
 uint64_t samgraph_get_next_batch(void) { return Engine::Get().GetNextBatch(); }
 void samgraph_sample_once(void) { Engine::Get().RunSampleOnce(); }
 
-size_t samgraph_get_graph_num_src(uint64_t key, int g) { return Engine::Get().Current(key)->counts[3 * g + 1]; }
-size_t samgraph_get_graph_num_dst(uint64_t key, int g) { return Engine::Get().Current(key)->counts[3 * g + 2]; }
-size_t samgraph_get_graph_num_edge(uint64_t key, int g) { return Engine::Get().Current(key)->counts[3 * g + 0]; }
+size_t samgraph_get_graph_num_src(uint64_t key, int g) { return Engine::Get().Current(key)->counts[GGMS_COUNT_SRC(g)]; }
+size_t samgraph_get_graph_num_dst(uint64_t key, int g) { return Engine::Get().Current(key)->counts[GGMS_COUNT_DST(g)]; }
+size_t samgraph_get_graph_num_edge(uint64_t key, int g) { return Engine::Get().Current(key)->counts[GGMS_COUNT_EDGES(g)]; }
 
 void samgraph_log_step(uint64_t e, uint64_t s, int item, double v) { auto &E = Engine::Get(); E.prof.LogStep(E.BatchKey(e, s), item, v); }
 void samgraph_log_step_by_key(uint64_t key, int item, double v) { Engine::Get().prof.LogStep(key, item, v); }
@@ -100,17 +100,17 @@ void samgraph_get_graph_label(uint64_t key, samgraph_tensor_t *out) {
 void samgraph_get_graph_row(uint64_t key, int l, samgraph_tensor_t *out) {
   auto &E = Engine::Get();
   auto *b = E.Current(key);
-  fill(out, b->trainer.row[l], (int64_t)b->counts[3 * l], 1, 1, GGMS_I32, E.batch_device_type(), E.trainer_device());
+  fill(out, b->trainer.row[l], (int64_t)b->counts[GGMS_COUNT_EDGES(l)], 1, 1, GGMS_I32, E.batch_device_type(), E.trainer_device());
 }
 void samgraph_get_graph_col(uint64_t key, int l, samgraph_tensor_t *out) {
   auto &E = Engine::Get();
   auto *b = E.Current(key);
-  fill(out, b->trainer.col[l], (int64_t)b->counts[3 * l], 1, 1, GGMS_I32, E.batch_device_type(), E.trainer_device());
+  fill(out, b->trainer.col[l], (int64_t)b->counts[GGMS_COUNT_EDGES(l)], 1, 1, GGMS_I32, E.batch_device_type(), E.trainer_device());
 }
 void samgraph_get_graph_data(uint64_t key, int l, samgraph_tensor_t *out) {
   auto &E = Engine::Get();
   auto *b = E.Current(key);
-  fill(out, b->trainer.data[l], b->trainer.data[l] ? (int64_t)b->counts[3 * l] : 0, 1, 1, GGMS_I32, E.batch_device_type(), E.trainer_device());
+  fill(out, b->trainer.data[l], b->trainer.data[l] ? (int64_t)b->counts[GGMS_COUNT_EDGES(l)] : 0, 1, 1, GGMS_I32, E.batch_device_type(), E.trainer_device());
 }
 void samgraph_get_dataset_feat(samgraph_tensor_t *out) {
   auto &E = Engine::Get();

@@ -134,9 +134,9 @@ void Engine::SendOne() {
   SAM_GGMS(ggms_queue_pack(queue_slots_dev_ + (pos % queue_depth_) * qlay_.slot_bytes, &qlay_, &src, b->key, b->num_seeds, ss));
   SAM_HIP(hipEventRecord(b->ev_done, ss));
   SAM_HIP(hipEventSynchronize(b->ev_done));
-  const uint64_t status = h->counts[3 * L + 1], num_input = h->counts[3 * L];
+  const uint64_t status = h->counts[GGMS_COUNT_STATUS(L)], num_input = h->counts[GGMS_COUNT_INPUT(L)];
   uint64_t edges = 0;
-  for (uint32_t i = 0; i < L; ++i) edges += h->counts[3 * i];
+  for (uint32_t i = 0; i < L; ++i) edges += h->counts[GGMS_COUNT_EDGES(i)];
   CheckBatchStatus(status, b->key);
   __atomic_store_n(&h->seq, pos + 1, __ATOMIC_RELEASE); // published
   const double t_send = since(t1);

@@ -75,7 +75,8 @@ void Engine::StagedExtract(Batch *b, hipStream_t ss, hipStream_t xs) {
   const bool serial = env_serial || cur_epoch_ < cfg.staged_serial_epochs || staged_batches_ < cfg.staged_serial_steps;
   ++staged_batches_;
   const bool have_cache = cache_table_ != nullptr;
-  uint64_t *n_in = b->trainer.counts_dev + 3 * L, *n_miss = n_in + 2, *n_hit = n_in + 3;
+  uint64_t *cd = b->trainer.counts_dev;
+  uint64_t *n_in = cd + GGMS_COUNT_INPUT(L), *n_miss = cd + GGMS_COUNT_MISS(L), *n_hit = cd + GGMS_COUNT_STAGED_HIT(L);
   using clk = std::chrono::steady_clock;
   auto since = [](clk::time_point t) { return std::chrono::duration<double>(clk::now() - t).count(); };
   double t_index = 0, t_ids = 0, t_gather = 0, t_copy = 0, t_comb_miss = 0, t_comb_hit = 0;
@@ -86,13 +87,14 @@ void Engine::StagedExtract(Batch *b, hipStream_t ss, hipStream_t xs) {
     SAM_GGMS(ggms_get_miss_cache_index_dev(cache_table_, b->trainer.input_nodes, max_unique_, n_in, b->miss_src, b->miss_dst, n_miss,
                                            b->hit_src, b->hit_dst, n_hit, b->idx_ws,
                                            ggms_cache_index_workspace_bytes(max_unique_), ss));
-  SAM_HIP(hipMemcpyAsync(b->counts, b->trainer.counts_dev, (3 * L + 8) * 8, hipMemcpyDeviceToHost, ss));
+  SAM_HIP(hipMemcpyAsync(b->counts, b->trainer.counts_dev, CountsBytes(L), hipMemcpyDeviceToHost, ss));
   SAM_HIP(hipStreamSynchronize(ss));
-  const size_t num_input = b->counts[3 * L];
-  size_t num_miss = have_cache ? b->counts[3 * L + 2] : num_input, num_hit = have_cache ? b->counts[3 * L + 3] : 0;
+  const size_t num_input = b->counts[GGMS_COUNT_INPUT(L)];
+  size_t num_miss = have_cache ? b->counts[GGMS_COUNT_MISS(L)] : num_input;
+  size_t num_hit = have_cache ? b->counts[GGMS_COUNT_STAGED_HIT(L)] : 0;
   if (!have_cache) { // every row comes from the host tier: the counters say so too
-    b->counts[3 * L + 2] = num_input;
-    SAM_HIP(hipMemcpyAsync(n_miss, b->counts + 3 * L + 2, 8, hipMemcpyHostToDevice, ss));
+    b->counts[GGMS_COUNT_MISS(L)] = num_input;
+    SAM_HIP(hipMemcpyAsync(n_miss, b->counts + GGMS_COUNT_MISS(L), 8, hipMemcpyHostToDevice, ss));
   }
   SAM_CHECK(num_miss + num_hit == num_input, "CHECK_EQ(num_miss + num_cache, num_input), dist_loops.cc:1047");
   t_index = since(t0);

@@ -136,15 +136,15 @@ static int queue_segments(ggms_copy_seg_t *segs, uint32_t *n, const ggms_queue_l
   };
   for (uint32_t i = 0; i < L; ++i) {
     if (!b->row[i] || !b->col[i] || (lay->has_data && !b->data[i])) return GGMS_ERR_INVALID;
-    add(b->row[i], lay->off_row[i], counts + 3 * i, 0, lay->max_edges[i], 4);
-    add(b->col[i], lay->off_col[i], counts + 3 * i, 0, lay->max_edges[i], 4);
-    if (lay->has_data) add(b->data[i], lay->off_data[i], counts + 3 * i, 0, lay->max_edges[i], 4);
+    add(b->row[i], lay->off_row[i], counts + GGMS_COUNT_EDGES(i), 0, lay->max_edges[i], 4);
+    add(b->col[i], lay->off_col[i], counts + GGMS_COUNT_EDGES(i), 0, lay->max_edges[i], 4);
+    if (lay->has_data) add(b->data[i], lay->off_data[i], counts + GGMS_COUNT_EDGES(i), 0, lay->max_edges[i], 4);
   }
   if (!b->input_nodes || !b->output_nodes || !b->counts) return GGMS_ERR_INVALID;
-  add(b->input_nodes, lay->off_input, counts + 3 * L, 0, lay->max_input, 4);
+  add(b->input_nodes, lay->off_input, counts + GGMS_COUNT_INPUT(L), 0, lay->max_input, 4);
   if (to_slot) add(b->output_nodes, lay->off_output, nullptr, num_output, lay->max_output, 4);
   else add(b->output_nodes, lay->off_output, &h->num_output, 0, lay->max_output, 4);
-  add(b->counts, offsetof(ggms_queue_header_t, counts), nullptr, 3 * L + 8, 3 * L + 8, 8);
+  add(b->counts, offsetof(ggms_queue_header_t, counts), nullptr, GGMS_COUNTS_WORDS(L), GGMS_COUNTS_WORDS(L), 8);
   *n = k;
   return GGMS_OK;
 }

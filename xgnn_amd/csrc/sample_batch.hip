@@ -318,7 +318,7 @@ static int sample_batch_impl(int sample_type, const ggms_graph_t *graph, const g
   // scan-area clear, item count reset, num_dst of the first layer = |seeds| (dist_loops.cc:305).
   BatchPrologue pro{scan_align(scan.words), (uint32_t)(8 + 2 * lay.scan_tiles),
                     scan.chunk, (uint32_t)(chunk_desc_words() + (size_t)kTicketSets * kTicketWords), ht->num_items_dev,
-                    counts_dev + 3 * (num_layer - 1) + 2};
+                    counts_dev + GGMS_COUNT_DST(num_layer - 1)};
   // direct table = batch mode of the dedup protocol (ggms_device.h): one index space for the whole batch, seeds first
   DedupInsert di{};
   di.cand = item_pos;
@@ -381,31 +381,32 @@ static int sample_batch_impl(int sample_type, const ggms_graph_t *graph, const g
     const size_t n_max = c.max_input[i], e_max = c.max_edges[i];
     // the last layer of a prefetching batch samples from the set BEFORE the expansion: its size as the previous fill
     // recorded it (num_dst(0)), not the table's count
-    const Count n = first ? count_of(num_seeds)
-                          : (last_pf ? count_of(n_max, counts_dev + 2) : count_of32(n_max, ht->num_items_dev));
-    uint64_t *num_edge = counts_dev + 3 * i + 0;
-    uint64_t *num_src = counts_dev + 3 * i + 1;                       // unique nodes after this layer (:304)
-    uint64_t *next_dst = i > 0 ? counts_dev + 3 * (i - 1) + 2         // = next layer's frontier size (:305)
-                               : counts_dev + 3 * num_layer;          // = number of input nodes
+    uint64_t *num_dst0 = counts_dev + GGMS_COUNT_DST(0);
+    const Count n = first ? count_of(num_seeds) : (last_pf ? count_of(n_max, num_dst0) : count_of32(n_max, ht->num_items_dev));
+    uint64_t *num_edge = counts_dev + GGMS_COUNT_EDGES(i);
+    uint64_t *num_src = counts_dev + GGMS_COUNT_SRC(i);                 // unique nodes after this layer (:304)
+    uint64_t *next_dst = i > 0 ? counts_dev + GGMS_COUNT_DST(i - 1)     // = next layer's frontier size (:305)
+                               : counts_dev + GGMS_COUNT_INPUT(num_layer); // = number of input nodes
     // batch order on the shared RNG pool (and on khop2's CSR): only the sampler kernels are ordered
     if (first && ordered_rng && extra && extra->rng_wait) GGMS_HIP(hipStreamWaitEvent(s, (hipEvent_t)extra->rng_wait, 0));
     di.w = (unsigned long long *)ht->o2n;
     di.version = ht->version;
-    if (last_pf) { // the expansion: one more fill of the batch, over every neighbour of n2o[0, k)
+    if (last_pf) { // the expansion: one more fill of the batch, over every neighbour of n2o[0, k).  Layer 0: num_src
+                   // is num_src(0), next_dst the input count
       if (pf->start) GGMS_HIP(hipEventRecord(pf->start, s));
       uint32_t *keys = w + lay.pf_keys, *local = w + lay.pf_local;
       uint64_t *total = reinterpret_cast<uint64_t *>(w + lay.pf_total);
-      rc = prefetch_list_impl(L.g, ht->n2o, n_max, counts_dev + 2, w + lay.pf_pre, w + lay.pf_scan, scan.status, total,
-                              pf->max_edges, counts_dev + 3 * num_layer + 6, keys, s);
+      rc = prefetch_list_impl(L.g, ht->n2o, n_max, num_dst0, w + lay.pf_pre, w + lay.pf_scan, scan.status, total,
+                              pf->max_edges, counts_dev + GGMS_COUNT_EXPANSION(num_layer), keys, s);
       if (rc != GGMS_OK) return rc;
       if (pf->max_edges == 0) { // no list to enter: the set is final as it is
-        hipLaunchKernelGGL(k_record, dim3(1), dim3(64), 0, s, counts_dev + 1, count_of32(0, ht->num_items_dev));
-        hipLaunchKernelGGL(k_record, dim3(1), dim3(64), 0, s, counts_dev + 3 * num_layer, count_of32(0, ht->num_items_dev));
+        hipLaunchKernelGGL(k_record, dim3(1), dim3(64), 0, s, num_src, count_of32(0, ht->num_items_dev));
+        hipLaunchKernelGGL(k_record, dim3(1), dim3(64), 0, s, next_dst, count_of32(0, ht->num_items_dev));
         GGMS_LAUNCH_CHECK();
       } else { // new nodes join n2o in first-occurrence order; num_src(0) and the input count get the new size
         di.base = next_base;
-        rc = ht_fill_impl(ht, keys, pf->max_edges, count_of(pf->max_edges, total), di, false, scan, counts_dev + 1,
-                          counts_dev + 3 * num_layer, s, local, nullptr, kRestDefer, nullptr);
+        rc = ht_fill_impl(ht, keys, pf->max_edges, count_of(pf->max_edges, total), di, false, scan, num_src, next_dst, s,
+                          local, nullptr, kRestDefer, nullptr);
         if (rc != GGMS_OK) return rc;
         di.map.base[di.map.n] = next_base; // the last layer's look-ups find the new nodes' ids in `local`
         di.map.arr[di.map.n] = local;
@@ -471,8 +472,8 @@ static int sample_batch_impl(int sample_type, const ggms_graph_t *graph, const g
       job_items = std::max(job_items, e_max);
     }
   }
-  // the rest of GPUMapEdges' dst half for every layer + the batch's status word (counts_dev[3 L + 1])
-  return launch_map_rest_all(ht, jobs, num_jobs, job_items, di.map, counts_dev + 3 * num_layer + 1, s);
+  // the rest of GPUMapEdges' dst half for every layer + the batch's status word (GGMS_COUNT_STATUS)
+  return launch_map_rest_all(ht, jobs, num_jobs, job_items, di.map, counts_dev + GGMS_COUNT_STATUS(num_layer), s);
 }
 
 int ggms_sample_batch(int sample_type, const ggms_graph_t *graph, const ggms_id_t *seeds, size_t num_seeds,

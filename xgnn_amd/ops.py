@@ -13,6 +13,8 @@ import torch
 
 from . import _lib
 from ._lib import Graph as _CGraph, HashTable as _CHashTable, check, lib
+from ._lib import (COUNTS_SAMPLE_WORDS, COUNTS_WORDS, COUNT_DST, COUNT_EDGES, COUNT_EXPANSION, COUNT_INPUT, COUNT_SRC,
+                   COUNT_STATUS)
 
 EMPTY_KEY = 0xFFFFFFFF
 
@@ -702,7 +704,47 @@ class SharedShard:
             self.ptr = None
 
 
-class BatchSampler:
+class _BatchBuffers:
+    """What BatchSampler and PrefetchBatchSampler set up and slice alike; whatever differs between them is an argument."""
+
+    def _init_capacity(self, graph, fanouts, sample_type, max_seeds, prob_table, alias_table):
+        self.graph, self.fanouts, self.sample_type = graph, [int(f) for f in fanouts], sample_type
+        L = self.L = len(self.fanouts)
+        self._f = (C.c_size_t * L)(*self.fanouts)
+        self.max_seeds = max_seeds
+        mi, me, mu = (C.c_size_t * L)(), (C.c_size_t * L)(), C.c_size_t(0)
+        check(lib().ggms_sample_batch_capacity(max_seeds, self._f, L, mi, me, C.byref(mu)), "capacity")
+        self.max_input, self.max_edges, self.max_unique = list(mi), list(me), mu.value
+        self._keep = (prob_table, alias_table)
+        self._extra = _lib.SampleExtra()
+        self._extra.prob_table = prob_table.data_ptr() if prob_table is not None else None
+        self._extra.alias_table = alias_table.data_ptr() if alias_table is not None else None
+
+    def _init_states(self, stateless, seed, device, num_random_walk=0):
+        """the RNG pool (None for the sample types in `stateless`)"""
+        nstates = lib().ggms_random_states_count(self.sample_type, self._f, self.L, self.max_seeds, num_random_walk)
+        nstates = max(nstates, (max(self.max_input) + 127) // 128 * 8, (max(self.max_input) + 1023) // 1024 * 256)
+        if self.sample_type == RANDOM_WALK:
+            nstates = max(nstates, lib().ggms_random_walk_num_states(max(self.max_input), num_random_walk))
+        self.states = random_states(nstates, seed, device) if self.sample_type not in stateless else None
+
+    def _layer_buffers(self, min_len, device):
+        """one id buffer per layer at its edge bound (min_len at least), and the host array of their device pointers"""
+        ts = [torch.empty(max(min_len, e), dtype=torch.int32, device=device) for e in self.max_edges]
+        return ts, (C.c_void_p * self.L)(*[t.data_ptr() for t in ts])
+
+    def _sliced(self, what, detail=None):
+        """Sync; raise on a non-zero batch status; -> (the counts words as a host list, the per-layer slices)."""
+        c = self.counts.cpu().tolist()
+        status = c[COUNT_STATUS(self.L)]
+        if status:  # a kernel of the batch hit a bound it must not hit: the outputs are invalid
+            check_device_status(what)
+            raise _lib.GgmsError(f"{what}: device status {status:#x}" + (detail(c) if detail else ""))
+        return c, [dict(row=self.row[i][:c[COUNT_EDGES(i)]], col=self.col[i][:c[COUNT_EDGES(i)]],
+                        num_src=c[COUNT_SRC(i)], num_dst=c[COUNT_DST(i)]) for i in range(self.L)]
+
+
+class BatchSampler(_BatchBuffers):
     """DoGPUSample (dist_loops.cc:62-368) as one enqueue: buffers sized once, reused every batch.
 
     num_slots      output slots (the engine's batch slots): a batch's COO / counts / input-node copy stay valid
@@ -714,46 +756,29 @@ class BatchSampler:
     def __init__(self, graph, fanouts, batch_size, sample_type=KHOP3, seed=0, device="cuda", direct_table=True,
                  prob_table=None, alias_table=None, random_walk_length=0, random_walk_restart_prob=0.0,
                  num_random_walk=0, num_slots=1, num_pipelines=1):
-        self.graph, self.fanouts, self.sample_type = graph, [int(f) for f in fanouts], sample_type
-        L = len(self.fanouts)
-        self.L = L
-        self._f = (C.c_size_t * L)(*self.fanouts)
-        mi, me, mu = (C.c_size_t * L)(), (C.c_size_t * L)(), C.c_size_t(0)
         # first batch of an epoch may be 1.25x (dist_shuffler_aligned.cc:137-140): size for it
-        self.max_seeds = int(batch_size * 1.25) + 1
-        check(lib().ggms_sample_batch_capacity(self.max_seeds, self._f, L, mi, me, C.byref(mu)), "capacity")
-        self.max_input, self.max_edges, self.max_unique = list(mi), list(me), mu.value
+        self._init_capacity(graph, fanouts, sample_type, int(batch_size * 1.25) + 1, prob_table, alias_table)
+        L = self.L
         self.num_pipelines = num_pipelines
         self.hts = [OrderedHashTable(self.max_unique, device, num_node=graph.c.num_node if direct_table else None)
                     for _ in range(num_pipelines)]
         self.ht = self.hts[0]
-        nstates = lib().ggms_random_states_count(sample_type, self._f, L, self.max_seeds, num_random_walk)
-        nstates = max(nstates, (max(self.max_input) + 127) // 128 * 8, (max(self.max_input) + 1023) // 1024 * 256)
-        if sample_type == RANDOM_WALK:
-            nstates = max(nstates, lib().ggms_random_walk_num_states(max(self.max_input), num_random_walk))
-        self.states = random_states(nstates, seed, device) if sample_type not in _STATELESS else None
+        self._init_states(_STATELESS, seed, device, num_random_walk)
         self.num_slots = num_slots
-        self.rows = [[torch.empty(max(1, e), dtype=torch.int32, device=device) for e in self.max_edges]
-                     for _ in range(num_slots)]
-        self.cols = [[torch.empty(max(1, e), dtype=torch.int32, device=device) for e in self.max_edges]
-                     for _ in range(num_slots)]
-        self._rows = [(C.c_void_p * L)(*[t.data_ptr() for t in r]) for r in self.rows]
-        self._cols = [(C.c_void_p * L)(*[t.data_ptr() for t in c]) for c in self.cols]
-        self.counts_slots = [torch.zeros(3 * L + 2, dtype=torch.int64, device=device) for _ in range(num_slots)]
+        def per_slot():  # -> every slot's buffers, every slot's pointer array
+            made = [self._layer_buffers(1, device) for _ in range(num_slots)]
+            return [t for t, _ in made], [p for _, p in made]
+        (self.rows, self._rows), (self.cols, self._cols) = per_slot(), per_slot()
+        self.counts_slots = [torch.zeros(COUNTS_SAMPLE_WORDS(L), dtype=torch.int64, device=device)
+                             for _ in range(num_slots)]
         self.input_nodes = [torch.empty(self.max_unique, dtype=torch.int32, device=device) for _ in range(num_slots)]
         self.row, self.col, self.counts = self.rows[0], self.cols[0], self.counts_slots[0]
         self.data = None
         self.datas = None
-        self._keep = (prob_table, alias_table)
         if sample_type == RANDOM_WALK:
-            self.datas = [[torch.empty(max(1, e), dtype=torch.int32, device=device) for e in self.max_edges]
-                          for _ in range(num_slots)]
-            self._datas = [(C.c_void_p * L)(*[t.data_ptr() for t in d]) for d in self.datas]
+            self.datas, self._datas = per_slot()
             self.data = self.datas[0]
         # one extras struct per (pipeline, slot) use: filled in sample()
-        self._extra = _lib.SampleExtra()
-        self._extra.prob_table = prob_table.data_ptr() if prob_table is not None else None
-        self._extra.alias_table = alias_table.data_ptr() if alias_table is not None else None
         self._extra.random_walk_length = random_walk_length
         self._extra.random_walk_restart_prob = random_walk_restart_prob
         self._extra.num_random_walk = num_random_walk
@@ -844,16 +869,10 @@ class BatchSampler:
 
     def result(self):
         """Sync and slice the outputs (host round trip: for tests and hand-off, not for the hot loop)."""
-        c = self.counts.cpu().tolist()
-        if c[3 * self.L + 1]:  # a kernel of the batch hit a bound it must not hit: the outputs are invalid
-            check_device_status("ggms_sample_batch")
-            raise _lib.GgmsError(f"ggms_sample_batch: device status {c[3 * self.L + 1]:#x}")
-        layers = []
-        for i in range(self.L):
-            ne = c[3 * i]
-            layers.append(dict(row=self.row[i][:ne], col=self.col[i][:ne], num_src=c[3 * i + 1], num_dst=c[3 * i + 2],
-                               data=self.data[i][:ne] if self.data is not None else None))
-        return dict(layers=layers, input_nodes=self._n2o[: c[3 * self.L]])
+        c, layers = self._sliced("ggms_sample_batch")
+        for i, lay in enumerate(layers):
+            lay["data"] = self.data[i][:c[COUNT_EDGES(i)]] if self.data is not None else None
+        return dict(layers=layers, input_nodes=self._n2o[: c[COUNT_INPUT(self.L)]])
 
 
 def prefetch_capacity(num_seeds, fanouts, indptr_host, max_edges_budget):
@@ -869,35 +888,22 @@ def prefetch_capacity(num_seeds, fanouts, indptr_host, max_edges_budget):
     return me.value, mi.value
 
 
-class PrefetchBatchSampler:
+class PrefetchBatchSampler(_BatchBuffers):
     """arch4's batch (DoGPUSampleDyCache, cuda_loops.cc:294-524) through ggms_sample_batch_prefetch: the layers of
     BatchSampler, the expansion after the second-to-last layer, the last layer sampled from the set before it.
     One slot, one pipeline; the RNG pool is BatchSampler's for the same arguments."""
 
     def __init__(self, graph, indptr_host, fanouts, batch_size, sample_type=KHOP0, seed=0, device="cuda",
                  prob_table=None, alias_table=None, max_edges_budget=1 << 26, max_seeds=None):
-        self.graph, self.fanouts, self.sample_type = graph, [int(f) for f in fanouts], sample_type
-        L = self.L = len(self.fanouts)
-        self._f = (C.c_size_t * L)(*self.fanouts)
-        self.max_seeds = int(batch_size * 1.25) + 1 if max_seeds is None else int(max_seeds)
-        mi, me, mu = (C.c_size_t * L)(), (C.c_size_t * L)(), C.c_size_t(0)
-        check(lib().ggms_sample_batch_capacity(self.max_seeds, self._f, L, mi, me, C.byref(mu)), "capacity")
-        self.max_input, self.max_edges = list(mi), list(me)
+        self._init_capacity(graph, fanouts, sample_type, int(batch_size * 1.25) + 1 if max_seeds is None else int(max_seeds),
+                            prob_table, alias_table)
+        L = self.L
         self.max_prefetch_edges, self.max_unique = prefetch_capacity(self.max_seeds, self.fanouts, indptr_host,
                                                                      max_edges_budget)
         self.ht = OrderedHashTable(self.max_unique, device, num_node=graph.c.num_node)
-        nstates = lib().ggms_random_states_count(sample_type, self._f, L, self.max_seeds, 0)
-        nstates = max(nstates, (max(self.max_input) + 127) // 128 * 8, (max(self.max_input) + 1023) // 1024 * 256)
-        self.states = random_states(nstates, seed, device) if sample_type != KHOP0 else None
-        self.row = [torch.empty(max(4, e), dtype=torch.int32, device=device) for e in self.max_edges]
-        self.col = [torch.empty(max(4, e), dtype=torch.int32, device=device) for e in self.max_edges]
-        self._rows = (C.c_void_p * L)(*[t.data_ptr() for t in self.row])
-        self._cols = (C.c_void_p * L)(*[t.data_ptr() for t in self.col])
-        self.counts = torch.zeros(3 * L + 8, dtype=torch.int64, device=device)
-        self._keep = (prob_table, alias_table)
-        self._extra = _lib.SampleExtra()
-        self._extra.prob_table = prob_table.data_ptr() if prob_table is not None else None
-        self._extra.alias_table = alias_table.data_ptr() if alias_table is not None else None
+        self._init_states((KHOP0,), seed, device)
+        (self.row, self._rows), (self.col, self._cols) = self._layer_buffers(4, device), self._layer_buffers(4, device)
+        self.counts = torch.zeros(COUNTS_WORDS(L), dtype=torch.int64, device=device)
         wsb = lib().ggms_sample_batch_prefetch_workspace_bytes(sample_type, self.max_seeds, self._f, L,
                                                                C.byref(self._extra), self.max_prefetch_edges)
         self.ws = _workspace(wsb, device)
@@ -920,15 +926,10 @@ class PrefetchBatchSampler:
     def result(self):
         """Sync and slice the outputs; raises on a non-zero batch status (GGMS_STATUS_PREFETCH_FULL: expansion over
         capacity, `needed` edges)."""
-        c = self.counts.cpu().tolist()
-        L = self.L
-        if c[3 * L + 1]:
-            check_device_status("ggms_sample_batch_prefetch")
-            raise _lib.GgmsError(f"ggms_sample_batch_prefetch: device status {c[3 * L + 1]:#x} "
-                                 f"(expansion needed {c[3 * L + 6]} edges, capacity {self.max_prefetch_edges})")
-        layers = [dict(row=self.row[i][:c[3 * i]], col=self.col[i][:c[3 * i]], num_src=c[3 * i + 1],
-                       num_dst=c[3 * i + 2]) for i in range(L)]
-        return dict(layers=layers, input_nodes=self.ht.n2o[: c[3 * L]], expansion_edges=c[3 * L + 6])
+        needed = COUNT_EXPANSION(self.L)
+        c, layers = self._sliced("ggms_sample_batch_prefetch", lambda c: f" (expansion needed {c[needed]} edges, "
+                                                                         f"capacity {self.max_prefetch_edges})")
+        return dict(layers=layers, input_nodes=self.ht.n2o[: c[COUNT_INPUT(self.L)]], expansion_edges=c[needed])
 
 
 def dynamic_cache_reset(stamps):
