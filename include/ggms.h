@@ -507,6 +507,40 @@ int ggms_link_seeds(const ggms_graph_t *graph, const ggms_id_t *edge_ids, size_t
                     uint64_t *num_forced_dev /* zeroed by the caller; may be NULL */, ggms_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Positive edges out of the sampled layers (an extension; the reference has no such operator): a link-prediction batch
+ * samples the neighbourhood of its positives' endpoints from the graph that holds the positives, so (u, v) itself shows
+ * up among u's sampled neighbours.  This call removes every such edge from the layers of a sampled batch, in place.
+ *   ids         are compared for equality only: the call works in any id space, as long as the pairs and row / col
+ *               share it (the engine passes local ids: the batch's seed ids).
+ *   direction   col is the node whose list was read, row the sampled neighbour, as ggms_sample_batch writes them.
+ *               GGMS_DROP_FORWARD drops an edge with (col, row) == (pair_src[i], pair_dst[i]) for some i -- the positive
+ *               (u -> v) itself; GGMS_DROP_REVERSE one with (col, row) == (pair_dst[i], pair_src[i]) -- its mirror.
+ *               `which` is either bit or both.
+ *   matching    every instance of a matching edge goes (multi-edges included); a pair (u, u) matches the self-loop
+ *               under either bit; repeated pairs are legal; a pair holding GGMS_EMPTY_KEY matches nothing.
+ *   per layer i n_i = counts_dev[GGMS_COUNT_EDGES(i)] is read on the device; max_edges[i] (>= n_i, below 2^32 - 1024)
+ *               only sizes launches and workspace.  On return row[i] / col[i] hold the kept edges in their original
+ *               relative order (stable) and counts_dev[GGMS_COUNT_EDGES(i)] their number; entries behind it are
+ *               unspecified.  No other counts word is touched -- num_src / num_dst keep their values: the node set of a
+ *               batch does not change.  num_dropped_dev (num_layer words, may be NULL): the dropped edges of layer i
+ *               are ADDED to word i.  row / col are HOST arrays of num_layer device pointers.
+ *   arguments   which == 0 or num_pairs == 0: GGMS_OK with nothing launched (the other arguments are still checked);
+ *               which > 3, num_layer == 0 or > 16, a null array, a workspace below
+ *               ggms_drop_pair_edges_workspace_bytes (0 for arguments out of range): GGMS_ERR_INVALID with a message.
+ * Like every entry point: no allocation, no synchronisation, every size stays on the device, no host round trip
+ * between layers.  One memset and FOUR launches per call, whatever num_pairs, num_layer and the n_i are: the pair
+ * table, then for all layers together a snapshot of row / col into the workspace, the prefix of the kept counts, and
+ * the compaction from the snapshot back into row / col.  No workgroup waits for another one.
+ * ------------------------------------------------------------------------- */
+#define GGMS_DROP_FORWARD 1u
+#define GGMS_DROP_REVERSE 2u
+size_t ggms_drop_pair_edges_workspace_bytes(size_t num_pairs, const size_t *max_edges, uint32_t num_layer);
+int ggms_drop_pair_edges(const ggms_id_t *pair_src, const ggms_id_t *pair_dst, size_t num_pairs, uint32_t which,
+                         ggms_id_t *const *row, ggms_id_t *const *col, const size_t *max_edges, uint32_t num_layer,
+                         uint64_t *counts_dev, uint64_t *num_dropped_dev /* num_layer words, ADDED to; may be NULL */,
+                         void *workspace, size_t workspace_bytes, ggms_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * arch4's batch with early feature prefetch -- DoGPUSampleDyCache (cuda/cuda_loops.cc:294-524).  The layers of
  * ggms_sample_batch, except:
  *   - after the second-to-last layer's table fill, every neighbour of every node entered so far (n2o[0, k)) is

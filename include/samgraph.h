@@ -111,9 +111,15 @@ void samgraph_get_graph_output_nodes(uint64_t key, samgraph_tensor_t *out);     
  * include/ggms.h).  Its output nodes are the B (2 + K) endpoints: [0, B) sources, [B, 2 B) destinations,
  * [2 B + i K + j] negative j of positive i.  samgraph_get_graph_seed_ids gives the LOCAL id of each of them (uint32
  * ids as I32, B (2 + K) entries, same layout): the ids the first sampled layer's col uses, rows of the batch's input
- * nodes and of its feature tensor.  samgraph_num_negative: K, or 0 for a node_classification run. */
+ * nodes and of its feature tensor.  samgraph_num_negative: K, or 0 for a node_classification run.
+ * Config key exclude_seed_edges = none | self | both (read with the task only): the batch's positive edges (u -> v), and
+ * with `both` their mirrors (v -> u), are removed from every sampled layer on the device (ggms_drop_pair_edges) before
+ * the batch is handed out: samgraph_get_graph_row / _col / _num_edge show the filtered layers, num_src / num_dst and the
+ * node lists are unchanged.  samgraph_get_graph_num_excluded: the edges removed from this batch, all layers together
+ * (0 without the key). */
 void samgraph_get_graph_seed_ids(uint64_t key, samgraph_tensor_t *out);
 size_t samgraph_num_negative(void);
+size_t samgraph_get_graph_num_excluded(uint64_t key);
 /* a batch's buffers stay valid while its retain count is > 0 */
 void samgraph_batch_retain(uint64_t key);
 void samgraph_batch_release(uint64_t key);

@@ -4,6 +4,9 @@
     python tools/bench_link.py --graph papers100M
     python tools/bench_link.py --graph hub                   # a 10^6-neighbour hub as the source of one positive
     python tools/bench_link.py --graph products --engine     # + the whole arch1 step through samgraph.torch
+    python tools/bench_link.py --graph products --no-leaf --drop --engine --exclude-ab 3
+                                                             # exclude_seed_edges: the filter alone, and the arch1 step
+                                                             # with `both` next to `none`, alternating
 
 Leaf: B positive edges drawn uniformly from the graph's edges, K negatives each, both modes; the launch is issued
 `--steps` times back to back between two events (buffers allocated once, the C entry point called directly), median
@@ -118,6 +121,64 @@ def leaf_records(args, g):
             print(json.dumps(rec), flush=True)
 
 
+def drop_records(args, g):
+    """ggms_drop_pair_edges alone: one khop3 batch over the endpoints of B positives (K negatives each, --fanout), its
+    layers restored before every call, the call between two events of its own; median over --steps x --rounds calls.
+    Next to the time: the bytes of row + col read and written once (16 per edge, what an in-place pass would move) and
+    the bytes the snapshot scheme moves (32 per edge), each divided by the time."""
+    import torch
+    from xgnn_amd import ops
+    from xgnn_amd._lib import COUNT_EDGES, check, lib
+    dev = torch.device("cuda", 0)
+    to_dev = lambda a: torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a).to(dev)  # noqa: E731
+    ip, ix = g["indptr"], g["indices"]
+    E = int(ip[-1])
+    graph = ops.DeviceGraph(to_dev(ip), to_dev(ix))
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    rng = np.random.RandomState(args.seed)
+    L = len(args.fanout)
+    for B in args.batch:
+        eids = to_dev(rng.randint(0, E, B).astype(np.uint32))
+        for K in args.num_negative:
+            seeds, _ = ops.link_seeds(graph, eids, K, ops.NEG_EXCLUDE, 99)
+            bs = ops.BatchSampler(graph, args.fanout, seeds.numel(), sample_type=ops.KHOP3, seed=7, device=dev)
+            bs.sample(seeds.contiguous())
+            bs.result()
+            ids = bs.seed_ids().clone()
+            counts0 = bs.counts.clone()
+            n = [int(counts0[COUNT_EDGES(i)]) for i in range(L)]
+            saved = [(bs.row[i][:n[i]].clone(), bs.col[i][:n[i]].clone()) for i in range(L)]
+            me = (C.c_size_t * L)(*bs.max_edges)
+            ws = torch.empty(lib().ggms_drop_pair_edges_workspace_bytes(B, me, L) // 4 + 4, dtype=torch.int32, device=dev)
+            rows, cols = (C.c_void_p * L)(*[t.data_ptr() for t in bs.row]), (C.c_void_p * L)(*[t.data_ptr() for t in bs.col])
+            dropped = torch.zeros(L, dtype=torch.int64, device=dev)
+            rec = dict(graph=args.graph, B=B, K=K, fanouts=args.fanout, edges=n, steps=args.steps, rounds=args.rounds)
+            for name, which in (("self", 1), ("both", 3)):
+                us = []
+                for _ in range(args.rounds):
+                    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                           for _ in range(args.steps)]
+                    for a, b in evs:
+                        for i, (r, c) in enumerate(saved):
+                            bs.row[i][:n[i]].copy_(r)
+                            bs.col[i][:n[i]].copy_(c)
+                        bs.counts.copy_(counts0)
+                        dropped.zero_()
+                        a.record()
+                        check(lib().ggms_drop_pair_edges(ptr(ids), C.c_void_p(ids.data_ptr() + 4 * B), B, which, rows, cols,
+                                                         me, L, ptr(bs.counts), ptr(dropped), ptr(ws), ws.numel() * 4,
+                                                         stream), "drop_pair_edges")
+                        b.record()
+                    torch.cuda.synchronize()
+                    us += [a.elapsed_time(b) * 1e3 for a, b in evs]
+                t = float(np.median(us))
+                rec[name] = dict(drop_us=round(t, 2), dropped=dropped.cpu().tolist(),
+                                 once_GBps=round(16 * sum(n) / t * 1e-3, 1), moved_GBps=round(32 * sum(n) / t * 1e-3, 1))
+            assert ops.device_status() == 0
+            print(json.dumps(rec), flush=True)
+
+
 def engine_child(a):
     import samgraph.torch as sam
     cfg = {"dataset_path": a.engine_child, "_arch": sam.builtin_archs["arch1"]["arch"],
@@ -128,19 +189,23 @@ def engine_child(a):
            "trainer_ctx": "cuda:0", "seed": a.seed}
     if a.child_task == "link_prediction":
         cfg.update(task="link_prediction", num_negative=a.child_k, negative_mode=a.child_mode)
+        if a.child_exclude:
+            cfg.update(exclude_seed_edges=a.child_exclude)
     sam.config(cfg)
     sam.init()
     steps = sam.steps_per_epoch()
     out = None
     for e in range(sam.num_epoch()):
         t0 = time.perf_counter()
-        rows = 0
+        rows = excluded = 0
         for _ in range(steps):
             sam.sample_once()
             key = sam.get_next_batch()
             rows += sam.get_graph_num_src(key, 0)
+            excluded += sam.get_graph_num_excluded(key)
         wall = time.perf_counter() - t0
         out = dict(steps=steps, ms_per_step=round(wall / steps * 1e3, 4), input_nodes_per_step=rows // steps,
+                   excluded_per_step=excluded // steps,
                    sample_ms_per_step=round(sam.get_log_epoch_value(e, sam.kLogEpochSampleTime) / steps * 1e3, 4),
                    edges_per_step=int(sam.get_log_epoch_value(e, sam.kLogEpochNumSample) / steps))
     sam.shutdown()
@@ -159,16 +224,25 @@ def engine_records(args, g):
             edges = np.random.RandomState(args.seed).randint(0, E, 48 * B).astype(np.uint32)
             datagen.write_dataset(d, g, minimal=True, train_edges=edges)
             for K in args.num_negative:
-                runs = [("link_prediction", B, m) for m in args.modes] + [("node_classification", B * (2 + K), "")]
+                # (task, batch, negative_mode, exclude_seed_edges, name); --exclude-ab R: the step with the filter (`both`)
+                # next to the same step without it (`none`), R times each, alternating, instead of the runs above
+                runs = [("link_prediction", B, m, "", m) for m in args.modes] + \
+                       [("node_classification", B * (2 + K), "", "", f"node_classification_{B * (2 + K)}_seeds")]
+                if args.exclude_ab:
+                    runs = [("link_prediction", B, args.modes[-1], x, f"exclude_seed_edges_{x}")
+                            for _ in range(args.exclude_ab) for x in ("none", "both")]
                 rec = dict(graph=args.graph, B=B, K=K, fanouts=args.fanout)
-                for task, batch, mode in runs:
+                for task, batch, mode, exclude, name in runs:
                     cmd = [sys.executable, os.path.abspath(__file__), "--engine-child", d + "/", "--child-task", task,
                            "--child-batch", str(batch), "--child-k", str(K), "--child-mode", mode or "exclude",
-                           "--seed", str(args.seed), "--fanout"] + [str(f) for f in args.fanout]
+                           "--child-exclude", exclude, "--seed", str(args.seed), "--fanout"] + [str(f) for f in args.fanout]
                     r = subprocess.run(["timeout", "-k", "10", str(args.child_timeout)] + cmd, capture_output=True, text=True)
                     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
-                    name = mode if task == "link_prediction" else f"node_classification_{batch}_seeds"
-                    rec[name] = json.loads(lines[-1]) if r.returncode == 0 and lines else dict(error=r.stderr[-300:])
+                    got = json.loads(lines[-1]) if r.returncode == 0 and lines else dict(error=r.stderr[-300:])
+                    if args.exclude_ab:
+                        rec.setdefault(name, []).append(got)
+                    else:
+                        rec[name] = got
                     if r.returncode in (124, 134, 137, 139):  # a time limit or a crash: nothing more on this GPU
                         print(json.dumps(rec), flush=True)
                         sys.exit(r.returncode)
@@ -195,6 +269,10 @@ def main():
     ap.add_argument("--child-batch", type=int, default=1000, help=argparse.SUPPRESS)
     ap.add_argument("--child-k", type=int, default=1, help=argparse.SUPPRESS)
     ap.add_argument("--child-mode", default="exclude", help=argparse.SUPPRESS)
+    ap.add_argument("--child-exclude", default="", help=argparse.SUPPRESS)
+    ap.add_argument("--drop", action="store_true", help="the edge filter (ggms_drop_pair_edges) alone, on a khop3 batch")
+    ap.add_argument("--exclude-ab", type=int, default=0, metavar="R",
+                    help="with --engine: exclude_seed_edges = none / both, R runs each, alternating")
     args = ap.parse_args()
     if args.engine_child:
         return engine_child(args)
@@ -203,6 +281,8 @@ def main():
     g = make_graph(args.graph, args.seed)
     if not args.no_leaf:
         leaf_records(args, g)
+    if args.drop:
+        drop_records(args, g)
     if args.engine:
         # the leaf part's context must not sit beside the engine children's on the device's memory
         torch.cuda.empty_cache()

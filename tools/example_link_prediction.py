@@ -4,13 +4,15 @@ tools/example_train_sage.py's DGL-free model; the head is a dot product of the t
 binary cross-entropy over the batch's positive pairs (label 1) and negative pairs (label 0).  A usage example of the
 pair interface, not a tuned model:
 
-    sam.config({..., "task": "link_prediction", "num_negative": K, "negative_mode": "exclude"})
+    sam.config({..., "task": "link_prediction", "num_negative": K, "negative_mode": "exclude",
+                "exclude_seed_edges": "both"})   # the positives and their mirrors leave the sampled layers
     pos_src, pos_dst, neg_src, neg_dst = sam.get_graph_link_pairs(key)   # local ids: rows of the model's output
 
 batch_size counts positive EDGES; the batch's seed list is their B (2 + K) endpoints, so the first sampled layer's
 num_dst is B (2 + K) while the distinct endpoints are the first max(id) + 1 nodes of the batch.
 
     python tools/example_link_prediction.py <dataset_dir> [--epochs 2] [--batch-size 512] [--num-negative 3]
+        [--exclude-seed-edges none|self|both]
 """
 import argparse
 import os
@@ -31,6 +33,8 @@ def main():
     ap.add_argument("--batch-size", type=int, default=512, help="positive edges per batch")
     ap.add_argument("--num-negative", type=int, default=3)
     ap.add_argument("--negative-mode", default="exclude", choices=["uniform", "exclude"])
+    ap.add_argument("--exclude-seed-edges", default="both", choices=["none", "self", "both"],
+                    help="take the batch's positive edges (self), and their mirrors (both), out of the sampled layers")
     ap.add_argument("--fanout", type=int, nargs="+", default=[10, 5])
     ap.add_argument("--sample-type", default="khop3")
     ap.add_argument("--hidden", type=int, default=64)
@@ -43,7 +47,8 @@ def main():
                 "max_sampling_jobs": 10, "max_copying_jobs": 1, "omp_thread_num": 4, "num_layer": L,
                 "num_hidden": args.hidden, "lr": 0.003, "dropout": 0.0, "num_fanout": L, "fanout": args.fanout,
                 "sampler_ctx": "cuda:0", "trainer_ctx": "cuda:0", "seed": args.seed,
-                "task": "link_prediction", "num_negative": args.num_negative, "negative_mode": args.negative_mode})
+                "task": "link_prediction", "num_negative": args.num_negative, "negative_mode": args.negative_mode,
+                "exclude_seed_edges": args.exclude_seed_edges})
     sam.init()
     dev = torch.device("cuda", 0)
     torch.manual_seed(args.seed)
@@ -52,7 +57,7 @@ def main():
     opt = torch.optim.Adam(layers.parameters(), lr=0.003)
     steps = sam.steps_per_epoch()
     for epoch in range(args.epochs):
-        t0, pairs, loss_sum, hits = time.time(), 0, 0.0, 0
+        t0, pairs, loss_sum, hits, excluded = time.time(), 0, 0.0, 0, 0
         for step in range(steps):
             sam.sample_once()
             key = sam.get_next_batch()
@@ -75,11 +80,12 @@ def main():
             loss.backward()
             opt.step()
             pairs += score.numel()
+            excluded += sam.get_graph_num_excluded(key)
             loss_sum += float(loss) * score.numel()
             hits += int(((score > 0) == (target > 0)).sum())
         print(f"epoch {epoch}: {steps} steps, loss {loss_sum / pairs:.4f}, pair acc {hits / pairs:.3f}, "
-              f"{time.time() - t0:.2f} s, sampled {sam.get_log_epoch_value(epoch, sam.kLogEpochNumSample):.0f} edges",
-              flush=True)
+              f"{time.time() - t0:.2f} s, sampled {sam.get_log_epoch_value(epoch, sam.kLogEpochNumSample):.0f} edges, "
+              f"{excluded} more excluded", flush=True)
     sam.shutdown()
 
 

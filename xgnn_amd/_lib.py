@@ -137,6 +137,9 @@ SYMBOLS = {
                                C.POINTER(_vp), C.POINTER(_vp), _vp, C.POINTER(SampleExtra), _vp, _sz, _vp]),
     "ggms_sample_batch_seed_ids": (_i, [_i, _sz, C.POINTER(_sz), _u32, C.POINTER(SampleExtra), _vp, C.POINTER(_vp)]),
     "ggms_link_seeds": (_i, [C.POINTER(Graph), _vp, _sz, _u32, _i, _u32, _vp, _vp, _vp]),
+    "ggms_drop_pair_edges_workspace_bytes": (_sz, [_sz, C.POINTER(_sz), _u32]),
+    "ggms_drop_pair_edges": (_i, [_vp, _vp, _sz, _u32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz), _u32, _vp, _vp,
+                                  _vp, _sz, _vp]),
     "ggms_hashtable_num_buckets": (_sz, [_sz]),
     "ggms_hashtable_init": (_i, [C.POINTER(HashTable), _vp]),
     "ggms_hashtable_reset": (_i, [C.POINTER(HashTable), _vp]),

@@ -111,6 +111,7 @@ SAMGRAPH_SYMBOLS = {
     "samgraph_get_dataset_label": (None, [_TP]), "samgraph_get_graph_input_nodes": (None, [_u64, _TP]),
     "samgraph_get_graph_output_nodes": (None, [_u64, _TP]),
     "samgraph_get_graph_seed_ids": (None, [_u64, _TP]), "samgraph_num_negative": (_sz, []),
+    "samgraph_get_graph_num_excluded": (_sz, [_u64]),
     "samgraph_batch_retain": (None, [_u64]), "samgraph_batch_release": (None, [_u64]),
 }
 
@@ -160,6 +161,7 @@ class SamGraphBasics(object):
         """Bytes of one feature row as stored in the table (a Q8ROW row: codes, pad, trailer) or as delivered in a batch."""
         return self.C_LIB_CTYPES.samgraph_feat_row_bytes(1 if delivered else 0)
     def num_negative(self): return self.C_LIB_CTYPES.samgraph_num_negative()
+    def get_graph_num_excluded(self, key): return self.C_LIB_CTYPES.samgraph_get_graph_num_excluded(key)
     def num_epoch(self): return self.C_LIB_CTYPES.samgraph_num_epoch()
     def steps_per_epoch(self): return self.C_LIB_CTYPES.samgraph_steps_per_epoch()
     def get_next_batch(self): return self.C_LIB_CTYPES.samgraph_get_next_batch()

@@ -291,6 +291,13 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
         fatal(__FILE__, __LINE__, "negative_mode = " + v + ": uniform or exclude (the default)");
       cfg.negative_mode = v == "uniform" ? GGMS_NEG_UNIFORM : GGMS_NEG_EXCLUDE;
     }
+    if (kv.count("exclude_seed_edges")) {
+      const std::string v = kv["exclude_seed_edges"];
+      if (v != "none" && v != "self" && v != "both")
+        fatal(__FILE__, __LINE__, "exclude_seed_edges = " + v + ": none (the default), self (the positive edges leave "
+                                  "the sampled layers) or both (and their mirrors)");
+      cfg.exclude_seed_edges = v == "none" ? 0u : v == "self" ? GGMS_DROP_FORWARD : (GGMS_DROP_FORWARD | GGMS_DROP_REVERSE);
+    }
   }
   if (cfg.arch == kArch4) { // DoGPUSampleDyCache's switch (cuda/cuda_loops.cc:347-377) and what it needs
     if (cfg.sample_type != GGMS_KHOP0 && cfg.sample_type != GGMS_KHOP1 && cfg.sample_type != GGMS_WEIGHTED_KHOP)
@@ -991,6 +998,11 @@ void Engine::SampleInit(int worker_id, const std::string &ctx) {
     SAM_GGMS(ggms_hashtable_init(&P.ht, stream_));
     SAM_HIP(hipMalloc(&P.ws, ws_bytes_));
   }
+  if (cfg.link_prediction && cfg.exclude_seed_edges) { // the edge filter's workspace, one per pipeline
+    drop_ws_bytes_ = ggms_drop_pair_edges_workspace_bytes(cfg.batch_size, max_edges_.data(), L);
+    SAM_CHECK(drop_ws_bytes_ > 0, "exclude_seed_edges: the batch bounds are out of ggms_drop_pair_edges' range");
+    for (Pipe &P : pipes_) SAM_HIP(hipMalloc(&P.drop_ws, drop_ws_bytes_));
+  }
   SAM_HIP(hipStreamSynchronize(stream_));
   prof.Resize(cfg.num_epoch, num_global_step_);
   if (cfg.UsePresample()) { // dist_engine.cc:455-466: worker 0 ranks the nodes, everybody waits
@@ -1367,6 +1379,11 @@ void Engine::TrainInit(int worker_id, const std::string &ctx) {
     if (cfg.link_prediction) {
       SAM_HIP(hipMalloc((void **)&b->edge_ids, cfg.batch_size * 4));
       SAM_HIP(hipMalloc((void **)&b->seed_ids, max_seeds_ * 4));
+      if (cfg.exclude_seed_edges) { // the dropped count of every layer: its own words, not counts words
+        SAM_HIP(hipMalloc((void **)&b->excluded_dev, L * 8));
+        SAM_HIP(hipHostMalloc((void **)&b->excluded, L * 8));
+        std::memset(b->excluded, 0, L * 8);
+      }
     }
     if (StagedHostTier()) { // index arrays of GetMissCacheIndex + pinned / device staging of the miss rows
       if (cache_table_) { // (no cache: no split, and the rows land in the batch's feature buffer directly)
@@ -1554,6 +1571,17 @@ void Engine::SampleInto(Batch *b, Pipe &P) {
     const ggms_id_t *ids = nullptr;
     SAM_GGMS(ggms_sample_batch_seed_ids(cfg.sample_type, b->num_seeds, cfg.fanout.data(), L, &extra, P.ws, &ids));
     SAM_HIP(hipMemcpyAsync(b->seed_ids, ids, b->num_seeds * 4, hipMemcpyDeviceToDevice, P.stream));
+    if (cfg.exclude_seed_edges) {
+      // The positives leave the layers before anything reads them: pair i is (ids[i], ids[B + i]), the batch's own seed
+      // ids in the sampling workspace (local ids, the id space of row / col); the filter works in P.drop_ws.  The layers'
+      // edge counts are replaced on the device, in front of ev_sampled: the counts that go to the host, the COO the
+      // trainer is handed and the blocks built from it all see the filtered layers.
+      SAM_HIP(hipMemsetAsync(b->excluded_dev, 0, L * 8, P.stream));
+      SAM_GGMS(ggms_drop_pair_edges(ids, ids + b->num_pos, b->num_pos, cfg.exclude_seed_edges, s.row.data(), s.col.data(),
+                                    max_edges_.data(), L, s.counts_dev, b->excluded_dev, P.drop_ws, drop_ws_bytes_,
+                                    P.stream));
+      SAM_HIP(hipMemcpyAsync(b->excluded, b->excluded_dev, L * 8, hipMemcpyDeviceToHost, P.stream));
+    }
   }
   SAM_HIP(hipMemsetAsync(s.counts_dev + GGMS_COUNT_MISS(L), 0, 8, P.stream)); // the trainer's miss count starts at 0
   SAM_HIP(hipEventRecord(b->ev_sampled, P.stream));
@@ -1767,10 +1795,16 @@ void Engine::Finish(Batch *b, Batch *prev) {
   CheckBatchStatus(b->counts[GGMS_COUNT_STATUS(L)], b->key);
   if (cfg.link_prediction) { // negatives whose eight candidates were all rejected, per epoch
     link_forced_ += b->counts[GGMS_COUNT_LINK_FORCED(L)];
+    for (uint32_t i = 0; b->excluded && i < L; ++i) link_excluded_ += b->excluded[i];
     if (b->key % num_global_step_ == num_global_step_ - 1) {
       log_info("link_prediction: epoch " + std::to_string(b->key / num_global_step_) + ": " + std::to_string(link_forced_) +
                " forced negatives of " + std::to_string(ds.num_train_edge * cfg.num_negative));
+      if (cfg.exclude_seed_edges)
+        log_info("link_prediction: epoch " + std::to_string(b->key / num_global_step_) + ": " +
+                 std::to_string(link_excluded_) + " sampled edges excluded (exclude_seed_edges = " +
+                 (cfg.exclude_seed_edges == GGMS_DROP_FORWARD ? "self" : "both") + ")");
       link_forced_ = 0;
+      link_excluded_ = 0;
     }
   }
   if (cfg.arch == kArch4 && !cfg.dynamic_cache) b->num_miss = b->num_input; // every row is read from host memory

@@ -101,6 +101,9 @@ struct RunConfig {
   bool link_prediction = false;
   uint32_t num_negative = 1;
   int negative_mode = GGMS_NEG_EXCLUDE;
+  // extension (config key `exclude_seed_edges` = none | self | both; read with task = link_prediction only): the batch's
+  // positive edges (self), and their mirrors (both), leave its sampled layers (ggms_drop_pair_edges' `which`; 0 = none)
+  uint32_t exclude_seed_edges = 0;
   size_t staged_serial_epochs = 0; // host-staged path: the first N epochs run the reference's serial, per-phase-timed sequence
   size_t staged_serial_steps = 0;  // ... or this worker's first N batches
   // worker 0 ranks the nodes at init: pre_sample (sampled input nodes) or presample_static (L-hop closures)
@@ -199,6 +202,9 @@ struct Batch {
   // entry of the seed list -- the pair ids -- copied out of the sampling workspace before the next batch reuses it
   uint32_t *edge_ids = nullptr, *seed_ids = nullptr;
   size_t num_pos = 0;
+  // exclude_seed_edges: the edges ggms_drop_pair_edges took out of each layer -- device words (zeroed per batch) and
+  // their pinned host copy, valid with the counts.  Null without the key: the batch then carries no extra packet.
+  uint64_t *excluded_dev = nullptr, *excluded = nullptr;
   uint64_t num_miss = 0;
   hipEvent_t ev_seeds = nullptr, ev_start = nullptr, ev_sampled = nullptr, ev_xstart = nullptr, ev_done = nullptr;
   // arch6 with `gpu_extract` off: the host-staged miss path (dist_loops.cc:1015-1207)
@@ -364,7 +370,11 @@ class Engine {
     ggms_hashtable_t ht{};
     void *ws = nullptr;
     hipEvent_t rng_done = nullptr;
+    void *drop_ws = nullptr; // exclude_seed_edges: ggms_drop_pair_edges' workspace, a piece of its own (the seed ids it
+                             // reads lie in `ws`)
   };
+  size_t drop_ws_bytes_ = 0;
+  uint64_t link_excluded_ = 0; // exclude_seed_edges: edges dropped from the batches handed out so far in this epoch
   std::vector<Pipe> pipes_;
   size_t enq_count_ = 0;
   hipEvent_t last_rng_done_ = nullptr;

@@ -141,6 +141,14 @@ void samgraph_get_graph_seed_ids(uint64_t key, samgraph_tensor_t *out) {
   auto *b = E.Current(key);
   fill(out, b->seed_ids, (int64_t)b->num_seeds, 1, 1, GGMS_I32, E.batch_device_type(), E.trainer_device());
 }
+// exclude_seed_edges: the edges the filter took out of this batch's layers, all layers together (0 without the key)
+size_t samgraph_get_graph_num_excluded(uint64_t key) {
+  auto &E = Engine::Get();
+  auto *b = E.Current(key);
+  size_t total = 0;
+  for (size_t i = 0; b->excluded && i < E.cfg.fanout.size(); ++i) total += b->excluded[i];
+  return total;
+}
 size_t samgraph_num_negative(void) { return Engine::Get().cfg.link_prediction ? Engine::Get().cfg.num_negative : 0; }
 void samgraph_batch_retain(uint64_t key) { Engine::Get().Retain(key); }
 void samgraph_batch_release(uint64_t key) { Engine::Get().Release(key); }

@@ -175,6 +175,39 @@ def link_seeds(graph, edge_ids, num_negative, mode=NEG_EXCLUDE, salt=0, count_fo
     return out[: n * (2 + num_negative)], forced
 
 
+DROP_FORWARD, DROP_REVERSE = 1, 2  # ggms_drop_pair_edges' `which` bits
+
+
+def drop_pair_edges(pair_src, pair_dst, which, rows, cols, counts, max_edges=None, num_dropped=None):
+    """ggms_drop_pair_edges: drop from every layer (rows[i], cols[i], counts[COUNT_EDGES(i)] edges) the edges with
+    (col, row) == (pair_src[p], pair_dst[p]) (DROP_FORWARD) and / or (pair_dst[p], pair_src[p]) (DROP_REVERSE), in
+    place and stable; counts (a device int64 tensor in the batch counts layout) gets the new edge counts.  max_edges:
+    the layers' bounds (default: the tensors' lengths).  Returns num_dropped, a device int64 tensor of len(rows) words
+    the dropped edges are ADDED to (a fresh zeroed one unless given)."""
+    L = len(rows)
+    _require_gpu(counts)
+    dev = counts.device
+    assert counts.dtype == torch.int64 and counts.is_contiguous()
+    for t in list(rows) + list(cols):
+        _require_gpu(_i32(t))
+    n = 0
+    if pair_src is not None:
+        _require_gpu(_i32(pair_src))
+        _require_gpu(_i32(pair_dst))
+        n = pair_src.numel()
+        assert pair_dst.numel() == n
+    me = [int(x) for x in max_edges] if max_edges is not None else [min(r.numel(), c.numel()) for r, c in zip(rows, cols)]
+    c_me = (C.c_size_t * max(1, L))(*me)
+    if num_dropped is None:
+        num_dropped = torch.zeros(max(1, L), dtype=torch.int64, device=dev)
+    ws = _workspace(lib().ggms_drop_pair_edges_workspace_bytes(n, c_me, L), dev)
+    c_rows = (C.c_void_p * max(1, L))(*[t.data_ptr() for t in rows])
+    c_cols = (C.c_void_p * max(1, L))(*[t.data_ptr() for t in cols])
+    check(lib().ggms_drop_pair_edges(_ptr(pair_src), _ptr(pair_dst), n, which, c_rows, c_cols, c_me, L, _ptr(counts),
+                                     _ptr(num_dropped), _ptr(ws), ws.numel() * 4, _stream()), "ggms_drop_pair_edges")
+    return num_dropped
+
+
 def sample_weighted_khop_prefix(graph, prob_prefix_table, inp, fanout, states):
     """GPUSampleWeightedKHopPrefix (cuda_sampling_weighted_khop_prefix.cu:145-246)."""
     return _sample("ggms_sample_weighted_khop_prefix", WEIGHTED_KHOP_PREFIX, graph, inp, fanout, states,
@@ -866,6 +899,11 @@ class BatchSampler(_BatchBuffers):
                                                C.byref(p)), "ggms_sample_batch_seed_ids")
         off = (p.value - ws.data_ptr()) // 4
         return ws[off: off + n]
+
+    def drop_pair_edges(self, pair_src, pair_dst, which):
+        """ggms_drop_pair_edges on the last sampled batch: the edges between the pairs (local ids, e.g. slices of
+        seed_ids()) leave its layers; result() then shows the filtered layers.  -> dropped edges per layer (device)."""
+        return drop_pair_edges(pair_src, pair_dst, which, self.row, self.col, self.counts, self.max_edges)
 
     def result(self):
         """Sync and slice the outputs (host round trip: for tests and hand-off, not for the hot loop)."""

@@ -19,7 +19,7 @@ for _name in ("init start num_class feat_dim num_epoch steps_per_epoch get_next_
               "report_epoch report_epoch_average report_node_access trace_step_begin trace_step_end "
               "trace_step_begin_now trace_step_end_now dump_trace forward_barrier wait_one_child log_step_by_key "
               "get_log_step_value_by_key data_init sample_init train_init extract_start num_local_step "
-              "um_sample_init switch_init feat_row_bytes num_negative").split():
+              "um_sample_init switch_init feat_row_bytes num_negative get_graph_num_excluded").split():
     globals()[_name] = getattr(_basics, _name)
 
 # DataType code -> (numpy typestr, torch dtype); common/common.h:38-46, adapter.cc:33-53
