@@ -1,5 +1,6 @@
 """A second, independent restatement of the reference's sampling paths (khop3 + the layer loop, khop0, weighted_khop,
-random walk + top-K) -- plain Python loops written against the CUDA text,
+weighted_khop_prefix, weighted_khop_hash_dedup with the two bounds of include/ggms.h, khop1, random walk + top-K) --
+plain Python loops written against the CUDA text,
 not against oracle/ggms_oracle.c -- and the C oracle must agree with it on small cases.
 
 What this adds: the oracle is one reading of racy CUDA code; this twin is the same canonical reading
@@ -242,6 +243,115 @@ def random_walk_twin(indptr, indices, inp, walk_length, restart_prob, num_walk, 
     return src, dst, data
 
 
+def _task_streams(num_task):
+    """Threads of the task-per-thread launches (khop1.cu:153-156, weighted_khop_prefix.cu:172-175): min(tasks, 512 K)
+    rounded up to whole blocks of 256; thread t keeps generator t and takes tasks t, t + span, ..."""
+    return (min(num_task, 512 * 1024) + 255) // 256 * 256
+
+
+def _sort_and_drop_adjacent(src, dst):
+    """SortPairs by src (stable: an LSD radix sort) and count_edge / compact_edge as khop1.cu:74-126 and
+    weighted_khop_prefix.cu:94-144 have them: entry i stays unless its src is kEmptyKey or (src, dst) equals entry
+    i + 1's; the last entry stays unless empty."""
+    n = len(src)
+    order = sorted(range(n), key=lambda i: src[i])
+    s, d = [src[i] for i in order], [dst[i] for i in order]
+    keep = [s[i] != EMPTY and (i == n - 1 or s[i] != s[i + 1] or d[i] != d[i + 1]) for i in range(n)]
+    return [s[i] for i in range(n) if keep[i]], [d[i] for i in range(n) if keep[i]]
+
+
+def khop1_twin(indptr, indices, inp, fanout, states):
+    """sample_khop1 (cuda/cuda_sampling_khop1.cu:42-72): task t -> seed t / fanout, ONE draw, neighbour curand % len;
+    a seed without neighbours leaves kEmptyKey and takes no draw."""
+    num_task = len(inp) * fanout
+    span = _task_streams(num_task)
+    src, dst = [EMPTY] * num_task, [EMPTY] * num_task
+    for t in range(min(span, num_task)):
+        for task in range(t, num_task, span):
+            rid = int(inp[task // fanout])
+            lo, ln = int(indptr[rid]), int(indptr[rid + 1]) - int(indptr[rid])
+            if ln:
+                src[task], dst[task] = rid, int(indices[lo + states[t].next() % ln])
+    return _sort_and_drop_adjacent(src, dst)
+
+
+def weighted_khop_prefix_twin(indptr, indices, prefix, inp, fanout, states):
+    """sample_weighted_khop_prefix (cuda/cuda_sampling_weighted_khop_prefix.cu:41-92): ONE curand_uniform per task,
+    scaled IN FLOAT by the list's last prefix sum; `x <= prefix[first]` takes the first neighbour, otherwise the
+    bracket (low, high] = (first, last] is halved while it spans two or more, `prefix[mid] >= x` moving high, and the
+    neighbour at `high` is taken."""
+    f32 = np.float32
+    num_task = len(inp) * fanout
+    span = _task_streams(num_task)
+    src, dst = [EMPTY] * num_task, [EMPTY] * num_task
+    for t in range(min(span, num_task)):
+        for task in range(t, num_task, span):
+            rid = int(inp[task // fanout])
+            lo, ln = int(indptr[rid]), int(indptr[rid + 1]) - int(indptr[rid])
+            if ln == 0:
+                continue
+            x = f32(curand_uniform_twin(states[t].next()) * f32(prefix[lo + ln - 1]))   # f32 * f32, rounded once
+            if x <= f32(prefix[lo]):
+                pick = lo
+            else:
+                low, high = lo, lo + ln - 1
+                while high - low >= 2:
+                    mid = (low + high) >> 1
+                    if f32(prefix[mid]) >= x:
+                        high = mid
+                    else:
+                        low = mid
+                pick = high
+            src[task], dst[task] = rid, int(indices[pick])
+    return _sort_and_drop_adjacent(src, dst)
+
+
+def weighted_khop_hash_dedup_twin(indptr, indices, prob, alias, inp, fanout, states):
+    """sample_weighted_khop_hash_dedup + insert_hash_table + count_edge / compact_edge
+    (cuda/cuda_sampling_weighted_khop_hash_dedup.cu:41-115, launch :212-231: blocks of 256 threads over tiles of 1024
+    seeds; thread t of block b keeps generator 256 b + t and walks seeds 1024 b + t + 256 r).  The thread's 50 slots
+    {value, round} are set to kEmptyKey once per launch and never cleared between seeds: a slot is free for a seed when
+    its round is not the seed's ID, so an earlier seed of the thread with the same id still counts.  A candidate is
+    two draws: position curand % len, then curand_uniform u, the alias taken when u > prob (STRICTLY greater; the plain
+    sampler takes the neighbour when u < prob).
+    The two bounds include/ggms.h adds where the reference would spin: a probe walk ends after 64 steps and the candidate
+    is taken (nothing stored); a seed that has drawn 65536 candidates takes every further one, new or not."""
+    n = len(inp)
+    rows = [None] * n
+    for b in range((n + 1023) // 1024):
+        for t in range(256):
+            st = states[256 * b + t]
+            value, round_ = [EMPTY] * 50, [EMPTY] * 50
+            for index in range(1024 * b + t, min(1024 * (b + 1), n), 256):
+                rid = int(inp[index])
+                lo, ln = int(indptr[rid]), int(indptr[rid + 1]) - int(indptr[rid])
+                if ln <= fanout:
+                    rows[index] = [int(indices[lo + j]) for j in range(ln)]
+                    continue
+                picks, drawn = [], 0
+                while len(picks) < fanout:
+                    k = st.next() % ln
+                    u = curand_uniform_twin(st.next())
+                    drawn += 1
+                    cand = int(alias[lo + k]) if u > np.float32(prob[lo + k]) else int(indices[lo + k])
+                    pos, gap, new = cand % 50, 1, True
+                    for _ in range(64):
+                        if round_[pos] != rid:
+                            round_[pos], value[pos] = rid, cand
+                            break
+                        if value[pos] == cand:
+                            new = False
+                            break
+                        pos = (pos + gap) % 50
+                        gap += 1
+                    if new or drawn > 65536:
+                        picks.append(cand)
+                rows[index] = picks
+    src = [int(inp[i]) for i in range(n) for _ in rows[i]]
+    dst = [d for i in range(n) for d in rows[i]]
+    return src, dst
+
+
 @pytest.fixture(scope="module")
 def const(golden_dir):
     return json.load(open(os.path.join(golden_dir, "xorwow_constants.json")))
@@ -330,3 +440,102 @@ def test_c_oracle_random_walk_agrees_with_the_python_twin(const, n, wl, p, nw, K
     assert [a.tolist() for a in got] == [list(w) for w in want]
     for t in range(0, nstates, 5):
         assert int(orc_states["d"][t]) == twin_states[t].d and orc_states["v"][t].tolist() == twin_states[t].v
+
+
+# ---------------------------------------------- weighted_khop_prefix, weighted_khop_hash_dedup, khop1
+def _twin_states(orc_states, const):
+    """Twin generators in the states of an oracle pool (fresh, warmed or hand-made)."""
+    out = []
+    for s in orc_states:
+        x = Xorwow.__new__(Xorwow)
+        x.d, x.v, x.weyl = int(s["d"]), [int(w) for w in s["v"]], const["weyl_increment"]["value"]
+        out.append(x)
+    return out
+
+
+def _assert_same_states(orc_states, twin_states):
+    for t in range(len(twin_states)):
+        assert int(orc_states["d"][t]) == twin_states[t].d and orc_states["v"][t].tolist() == twin_states[t].v, f"stream {t}"
+
+
+def _weighted_powerlaw(seed):
+    ip, ix = powerlaw_csr(1500, mean_deg=9, seed=6)            # includes nodes without neighbours
+    w = np.random.RandomState(seed).randint(1, 11, ix.size).astype(np.float32)
+    return ip, ix, w
+
+
+@pytest.mark.parametrize("n,fanout,seed", [(200, 5, 1), (77, 12, 2), (3000, 3, 3), (64, 1, 4)])
+def test_c_oracle_khop1_agrees_with_the_python_twin(const, n, fanout, seed):
+    ip, ix, _ = _weighted_powerlaw(seed)
+    inp = np.random.RandomState(seed + 10).randint(0, ip.size - 1, n).astype(np.uint32)  # repeated seeds allowed
+    orc_states = oracle.random_states(_task_streams(n * fanout), seed)
+    twin_states = _twin_states(orc_states, const)
+    want = khop1_twin(ip, ix, inp, fanout, twin_states)
+    got = oracle.sample_khop1(ip, ix, inp, fanout, orc_states)
+    assert [a.tolist() for a in got] == [list(w) for w in want]
+    _assert_same_states(orc_states, twin_states)
+
+
+@pytest.mark.parametrize("n,fanout,seed", [(200, 5, 1), (77, 12, 2), (3000, 3, 3), (64, 1, 4)])
+def test_c_oracle_weighted_khop_prefix_agrees_with_the_python_twin(const, n, fanout, seed):
+    ip, ix, w = _weighted_powerlaw(seed)
+    pre = oracle.create_prob_prefix_table(ip, w)
+    inp = np.random.RandomState(seed + 10).randint(0, ip.size - 1, n).astype(np.uint32)
+    orc_states = oracle.random_states(_task_streams(n * fanout), seed)
+    twin_states = _twin_states(orc_states, const)
+    want = weighted_khop_prefix_twin(ip, ix, pre, inp, fanout, twin_states)
+    got = oracle.sample_weighted_khop_prefix(ip, ix, pre, inp, fanout, orc_states)
+    assert [a.tolist() for a in got] == [list(w_) for w_ in want]
+    _assert_same_states(orc_states, twin_states)
+
+
+@pytest.mark.parametrize("fanout", [1, 3])
+def test_c_oracle_weighted_khop_prefix_agrees_with_the_python_twin_on_table_edges(const, fanout):
+    """Lengths 1 - 3, zero weights, a sum that stops growing, an all-zero list (weighted_cases.prefix_edge_lists), and
+    u * total equal to a prefix value exactly (hand-made states)."""
+    import weighted_cases as wc
+    cases = [(w, None) for w in wc.prefix_edge_lists()] + [(wc.TIE_W, "tie")]
+    for w, how in cases:
+        g = wc.shared_list_graph(64, w)
+        inp = np.arange(g.M, dtype=np.uint32)
+        n = _task_streams(g.M * fanout)
+        orc_states = wc.tie_states(n) if how else oracle.random_states(n, 31)
+        twin_states = _twin_states(orc_states, const)
+        want = weighted_khop_prefix_twin(g.indptr, g.indices, g.prefix, inp, fanout, twin_states)
+        got = oracle.sample_weighted_khop_prefix(g.indptr, g.indices, g.prefix, inp, fanout, orc_states)
+        assert [a.tolist() for a in got] == [list(w_) for w_ in want], w[:10]
+        _assert_same_states(orc_states, twin_states)
+
+
+@pytest.mark.parametrize("n,fanout,seed", [(300, 5, 1), (1100, 30, 2), (1025, 49, 3)])
+def test_c_oracle_weighted_khop_hash_dedup_agrees_with_the_python_twin(const, n, fanout, seed):
+    """Alias tables from weights; one stream meets the longest list three times (positions 0, 256, 512): its table
+    still holds the earlier copies' entries, and from fanout 25 on it fills up (the 64-step probe bound)."""
+    ip, ix, w = _weighted_powerlaw(seed)
+    prob, alias = oracle.create_alias_table(ip, ix, w)
+    inp = np.random.RandomState(seed + 10).randint(0, ip.size - 1, n).astype(np.uint32)
+    if n > 512:
+        inp[[0, 256, 512]] = int(np.argmax(np.diff(ip.astype(np.int64))))
+    orc_states = oracle.random_states((n + 1023) // 1024 * 256, seed)
+    twin_states = _twin_states(orc_states, const)
+    want = weighted_khop_hash_dedup_twin(ip, ix, prob, alias, inp, fanout, twin_states)
+    got = oracle.sample_weighted_khop_hash_dedup(ip, ix, prob, alias, inp, fanout, orc_states)
+    assert [a.tolist() for a in got] == [list(w_) for w_ in want]
+    _assert_same_states(orc_states, twin_states)
+
+
+@pytest.mark.parametrize("fanout,variant", [(5, "base"), (17, "after"), (18, "pair")])
+def test_c_oracle_hash_dedup_give_up_agrees_with_the_python_twin(const, fanout, variant):
+    """Lists without `fanout` distinct candidates: both restatements stop rejecting after the same candidate (65536
+    drawn), so the picks AND the generators agree -- one candidate earlier or later shifts every later draw of the
+    stream.  17: the seed completes on candidate 65552; 18: it needs 65553; `after`: the stream serves two more long
+    lists from the state the give-up seed leaves."""
+    import weighted_cases as wc
+    ip, ix, prob, alias = wc.giveup_graph(fanout)
+    inp = wc.giveup_seeds(fanout, variant)
+    orc_states = oracle.random_states(wc.stream_states(inp.size), 0x1001)
+    twin_states = _twin_states(orc_states, const)
+    want = weighted_khop_hash_dedup_twin(ip, ix, prob, alias, inp, fanout, twin_states)
+    got = oracle.sample_weighted_khop_hash_dedup(ip, ix, prob, alias, inp, fanout, orc_states)
+    assert [a.tolist() for a in got] == [list(w_) for w_ in want]
+    _assert_same_states(orc_states, twin_states)
