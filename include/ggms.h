@@ -770,6 +770,31 @@ int ggms_quantize_rows(void *out, int out_dtype, const void *src, int src_dtype,
                        uint64_t first_row, uint64_t *bad_row /* device, may be NULL */, ggms_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Row update (an extension; the reference's tables are read-only): a learnable F32 table takes the gradient of the
+ * rows a batch gathered -- the write side of the row sweep, fused with the optimiser's rule.  `table`, `state` and
+ * `grad` are F32 (4-byte aligned); grad is (count, dim) row-major and contiguous, and row i of grad belongs to table
+ * row nodes[i].  Every operation below is ONE IEEE f32 operation (round to nearest even, subnormals kept, correctly
+ * rounded divide and square root), none contracted into an FMA: numpy's float32 arithmetic gives the same bits.
+ *   GGMS_UPDATE_SGD       w = fl(w - fl(lr * g))
+ *   GGMS_UPDATE_ADAGRAD   s = fl(state + fl(g * g)); state = s; w = fl(w - fl(fl(lr * g) / fl(fl(sqrt(s)) + eps)))
+ *                         element-wise, `state` shaped like the table (NULL for SGD, which ignores it)
+ *   count    num_nodes_dev == NULL: num_nodes; else min(*num_nodes_dev, num_nodes), read in the kernel -- num_nodes then
+ *            only bounds the launch, and rows of grad behind the device count are not applied
+ *   nodes    must be PAIRWISE DISTINCT (a batch's input nodes are): with repeats the result is undefined.  An entry
+ *            equal to GGMS_EMPTY_KEY is skipped.  No other row of table or state is touched.
+ * In place, one launch: no atomics, no workspace, no synchronisation.  Chunks of 16, 8 or 4 bytes by dim x 4 and the
+ * three bases' alignment, as the gather picks them.
+ * GGMS_ERR_INVALID with a message, before any device call: an unknown rule; dim 0; a non-finite lr; Adagrad with
+ * eps <= 0 or a non-finite eps; and, with num_nodes > 0, a null table, nodes or grad; Adagrad without state; a base
+ * that is not 4-byte aligned.  num_nodes == 0 is GGMS_OK with nothing launched.
+ * ------------------------------------------------------------------------- */
+#define GGMS_UPDATE_SGD 0
+#define GGMS_UPDATE_ADAGRAD 1
+int ggms_update_rows(void *table, void *state /* NULL for SGD */, const ggms_id_t *nodes, size_t num_nodes,
+                     const uint64_t *num_nodes_dev /* NULL: num_nodes is the count, else it is the bound */,
+                     const void *grad, size_t dim, int rule, float lr, float eps, ggms_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Launch timer: a row gather's OWN start / end timestamps, with no packet of their own on the stream.
  * The reference times its extract with a host timer around a stream sync (dist_loops.cc:1276-1281,
  * kLogL1CopyTime); a pipelined caller has to use events instead, and every hipEventRecord / hipStreamWaitEvent

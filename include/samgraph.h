@@ -120,6 +120,24 @@ void samgraph_get_graph_output_nodes(uint64_t key, samgraph_tensor_t *out);     
 void samgraph_get_graph_seed_ids(uint64_t key, samgraph_tensor_t *out);
 size_t samgraph_num_negative(void);
 size_t samgraph_get_graph_num_excluded(uint64_t key);
+/* Extensions for config key feat_learnable = sgd | adagrad (arch1, FEAT_DATA_TYPE F32; with it feat_lr: required,
+ * finite; feat_eps: Adagrad only, default 1e-10, > 0).  The table on the device is LEARNABLE: it starts as feat.bin, and
+ *   samgraph_update_graph_feat(key, grad, num_rows, dim, caller_stream)   applies ggms_update_rows' rule (include/ggms.h)
+ *     to the table rows of the CURRENT batch's input nodes: grad is device memory, F32, (num_rows, dim) contiguous, row i
+ *     the gradient of row i of samgraph_get_graph_feat(key), produced on caller_stream (a hipStream_t).  Another shape
+ *     than (the batch's num_input, feat_dim) is fatal.  Nothing waits on the host: caller_stream is tied in by events on
+ *     both sides, so the gradient's memory may be released to a stream-ordered allocator right after the call.
+ * Gathers and updates run on ONE stream (extract_streams is forced to 1), in the order of the calls that enqueue them:
+ * a batch's rows reflect exactly the updates whose call came before the samgraph_sample_once call that enqueued the
+ * batch.  With lookahead = h and the loop {sample_once; get_next_batch; train; update}, batch j sees the updates of
+ * batches 0 .. j-h-1; lookahead = 0 is fully synchronous.  A row is never torn.  samgraph_extract_start is fatal with
+ * the key (a background thread would make that a matter of timing).
+ *   samgraph_get_store_feat / samgraph_get_store_state   the live table and the Adagrad accumulator, (num_node, dim) F32
+ *     on the trainer GPU, zero-copy; fatal without the key (the state: without adagrad).  samgraph_get_dataset_feat
+ *     keeps returning the mapped file. */
+void samgraph_update_graph_feat(uint64_t key, const void *grad, size_t num_rows, size_t dim, void *caller_stream);
+void samgraph_get_store_feat(samgraph_tensor_t *out);
+void samgraph_get_store_state(samgraph_tensor_t *out);
 /* a batch's buffers stay valid while its retain count is > 0 */
 void samgraph_batch_retain(uint64_t key);
 void samgraph_batch_release(uint64_t key);

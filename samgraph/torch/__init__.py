@@ -9,4 +9,5 @@ from xgnn_amd.torch import (config, init, start, num_class, feat_dim, num_epoch,
                             num_local_step, um_sample_init, switch_init, get_graph_feat, get_graph_label, get_graph_row, get_graph_col,
                             get_graph_data, get_dgl_blocks, get_dgl_blocks_with_weights, get_dataset_feat,
                             get_dataset_label, get_graph_input_nodes, get_graph_output_nodes, load_subtensor,
-                            notify_sampler_ready, wait_for_sampler_ready, get_graph_coo)
+                            notify_sampler_ready, wait_for_sampler_ready, get_graph_coo,
+                            update_graph_feat, get_store_feat, get_store_state)

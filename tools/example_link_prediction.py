@@ -12,7 +12,12 @@ batch_size counts positive EDGES; the batch's seed list is their B (2 + K) endpo
 num_dst is B (2 + K) while the distinct endpoints are the first max(id) + 1 nodes of the batch.
 
     python tools/example_link_prediction.py <dataset_dir> [--epochs 2] [--batch-size 512] [--num-negative 3]
-        [--exclude-seed-edges none|self|both]
+        [--exclude-seed-edges none|self|both] [--learn-features sgd|adagrad --feat-lr 0.05]
+
+--learn-features makes the engine's feature table the model's trainable input embedding (config keys feat_learnable,
+feat_lr): the batch's rows become a leaf that requires grad, and after backward() their gradient goes back with
+sam.update_graph_feat(key, h.grad) -- the table moves on the device, no copy of it lives in torch.  The rows are used
+as they are (no 1 / 65536): give such a dataset a feat.bin that is an embedding's initial value, small random numbers.
 """
 import argparse
 import os
@@ -39,9 +44,13 @@ def main():
     ap.add_argument("--sample-type", default="khop3")
     ap.add_argument("--hidden", type=int, default=64)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--learn-features", choices=["sgd", "adagrad"],
+                    help="train the feature table itself with this rule (config key feat_learnable)")
+    ap.add_argument("--feat-lr", type=float, default=0.05, help="learning rate of the feature table (feat_lr)")
     args = ap.parse_args()
     L = len(args.fanout)
-    sam.config({"dataset_path": args.dataset, "_arch": sam.builtin_archs["arch1"]["arch"],
+    learn = {"feat_learnable": args.learn_features, "feat_lr": args.feat_lr} if args.learn_features else {}
+    sam.config({**learn, "dataset_path": args.dataset, "_arch": sam.builtin_archs["arch1"]["arch"],
                 "_sample_type": sam.sample_types[args.sample_type], "batch_size": args.batch_size,
                 "num_epoch": args.epochs, "_cache_policy": sam.cache_policies["degree"], "cache_percentage": 0.0,
                 "max_sampling_jobs": 10, "max_copying_jobs": 1, "omp_thread_num": 4, "num_layer": L,
@@ -63,7 +72,10 @@ def main():
             key = sam.get_next_batch()
             pos_src, pos_dst, neg_src, neg_dst = (t.long() for t in sam.get_graph_link_pairs(key))
             num_out = int(sam.get_graph_seed_ids(key).max()) + 1  # distinct endpoints: the first nodes of the batch
-            h = sam.get_graph_feat(key) / 65536.0  # the synthetic features are integers in [0, 65535]
+            if learn:  # the rows as they are: a leaf whose gradient goes back to the table
+                h = feat = sam.get_graph_feat(key).requires_grad_()
+            else:
+                h = sam.get_graph_feat(key) / 65536.0  # the synthetic features are integers in [0, 65535]
             coo = sam.get_graph_coo(key, L)  # layer 0 = outermost hop (largest frontier)
             for i in range(L):
                 row, col, num_src, num_dst = coo[i]
@@ -79,6 +91,8 @@ def main():
             opt.zero_grad()
             loss.backward()
             opt.step()
+            if learn:
+                sam.update_graph_feat(key, feat.grad)
             pairs += score.numel()
             excluded += sam.get_graph_num_excluded(key)
             loss_sum += float(loss) * score.numel()

@@ -166,6 +166,7 @@ SYMBOLS = {
     "ggms_extract_cached_convert": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _u32, _vp, _sz, _i, _i, _vp, _vp]),
     "ggms_extract_tiered_convert": (_i, [_vp, _vp, _sz, _vp, C.POINTER(FeatureTiers), _sz, _i, _i, _vp, _vp]),
     "ggms_quantize_rows": (_i, [_vp, _i, _vp, _i, _sz, _sz, _u64, _vp, _vp]),
+    "ggms_update_rows": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _sz, _i, C.c_float, C.c_float, _vp]),
     "ggms_sample_batch_prefetch_capacity": (_i, [_sz, C.POINTER(_sz), _u32, _vp, _sz, _sz, C.POINTER(_sz),
                                                  C.POINTER(_sz)]),
     "ggms_sample_batch_prefetch_workspace_bytes": (_sz, [_i, _sz, C.POINTER(_sz), _u32, C.POINTER(SampleExtra), _sz]),

@@ -299,6 +299,40 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
       cfg.exclude_seed_edges = v == "none" ? 0u : v == "self" ? GGMS_DROP_FORWARD : (GGMS_DROP_FORWARD | GGMS_DROP_REVERSE);
     }
   }
+  if (kv.count("feat_learnable")) { // extension: the device table is trainable (samgraph_update_graph_feat)
+    static const char *const arch_names[] = {"arch0", "arch1", "arch2", "arch3", "arch4", "arch5", "arch6", "arch7"};
+    if (cfg.arch != kArch1)
+      fatal(__FILE__, __LINE__, std::string(arch_names[cfg.arch]) + ": feat_learnable is not built: only arch1 keeps the "
+                                "whole table in one GPU's memory; the cache tiers and shards of the other deployments "
+                                "have no write path");
+    const std::string v = kv["feat_learnable"];
+    if (v != "sgd" && v != "adagrad") fatal(__FILE__, __LINE__, "feat_learnable = " + v + ": sgd or adagrad");
+    cfg.feat_learnable = v == "sgd" ? GGMS_UPDATE_SGD : GGMS_UPDATE_ADAGRAD;
+    // a whole, finite number that is finite as the f32 the kernel takes
+    auto number = [&](const char *key, float &out) {
+      const std::string s = kv[key];
+      char *end = nullptr;
+      const double d = std::strtod(s.c_str(), &end);
+      out = (float)d;
+      return !s.empty() && end == s.c_str() + s.size() && std::isfinite(d) && std::isfinite(out);
+    };
+    if (!kv.count("feat_lr")) fatal(__FILE__, __LINE__, "feat_learnable needs the config key feat_lr (the table's learning rate)");
+    if (!number("feat_lr", cfg.feat_lr)) fatal(__FILE__, __LINE__, "feat_lr = " + kv["feat_lr"] + ": a finite number");
+    if (cfg.feat_learnable == GGMS_UPDATE_ADAGRAD && kv.count("feat_eps") && !(number("feat_eps", cfg.feat_eps) && cfg.feat_eps > 0))
+      fatal(__FILE__, __LINE__, "feat_eps = " + kv["feat_eps"] + ": a finite number > 0 (as f32)");
+    if (kv.count("feat_store_dtype"))
+      fatal(__FILE__, __LINE__, "feat_learnable with feat_store_dtype: the update reads and writes F32 rows, an encoded "
+                                "table has none");
+    if (cfg.feat_out_dtype >= 0 && cfg.feat_out_dtype != GGMS_F32)
+      fatal(__FILE__, __LINE__, "feat_learnable with feat_out_dtype = " + kv["feat_out_dtype"] + ": the gradient comes back "
+                                "in f32, row for row of what the batch delivered; f32 or no key");
+    if (getenv("SAMGRAPH_EMPTY_FEAT"))
+      fatal(__FILE__, __LINE__, "feat_learnable with SAMGRAPH_EMPTY_FEAT: several nodes share a row of a masked mock "
+                                "table, an update has no single row to move");
+    // gathers and updates are totally ordered on the one extract stream: a batch's rows reflect exactly the updates
+    // enqueued before its gather was
+    cfg.extract_streams = 1;
+  }
   if (cfg.arch == kArch4) { // DoGPUSampleDyCache's switch (cuda/cuda_loops.cc:347-377) and what it needs
     if (cfg.sample_type != GGMS_KHOP0 && cfg.sample_type != GGMS_KHOP1 && cfg.sample_type != GGMS_WEIGHTED_KHOP)
       fatal(__FILE__, __LINE__, "arch4: _sample_type " + std::to_string(cfg.sample_type) + " is not supported: the "
@@ -393,6 +427,13 @@ void Engine::LoadDataset() {
   ds.num_node = meta["NUM_NODE"]; ds.num_edge = meta["NUM_EDGE"]; ds.feat_dim = meta["FEAT_DIM"];
   ds.num_class = meta["NUM_CLASS"]; ds.num_train = meta["NUM_TRAIN_SET"]; ds.num_test = meta["NUM_TEST_SET"];
   ds.num_valid = meta["NUM_VALID_SET"];
+  if (cfg.feat_learnable >= 0 && ds.feat_dtype != GGMS_F32) {
+    std::string name = std::to_string(ds.feat_dtype);
+    for (const auto &kvp : kFeatDtypeNames)
+      if (kvp.second == ds.feat_dtype) name = kvp.first;
+    fatal(__FILE__, __LINE__, "feat_learnable with FEAT_DATA_TYPE " + name + ": the learnable table is F32 (the update's "
+                              "arithmetic is f32, one rounding per operation)");
+  }
   const bool share = cfg.arch == kArch6; // forked workers read the same pages
   ds.indptr = MapFile("indptr.bin", (ds.num_node + 1) * 4, share);
   ds.indices = MapFile("indices.bin", ds.num_edge * 4, share);
@@ -1212,6 +1253,14 @@ void Engine::BuildCache() {
       // arch1: the whole table lives in HBM and is gathered directly (cuda_loops_arch1.cc:61)
       d_feat_ = dev_upload(feat, ds.feat.bytes, bs);
       feat_src_ = d_feat_;
+      if (cfg.feat_learnable >= 0) { // the upload is the learnable table's initial value; Adagrad's accumulator starts at 0
+        if (cfg.feat_learnable == GGMS_UPDATE_ADAGRAD) {
+          SAM_HIP(hipMalloc(&d_feat_state_, std::max<size_t>(ds.feat.bytes, 16)));
+          SAM_HIP(hipMemsetAsync(d_feat_state_, 0, ds.feat.bytes, bs));
+        }
+        SAM_HIP(hipEventCreateWithFlags(&ev_grad_, hipEventDisableTiming));
+        SAM_HIP(hipEventCreateWithFlags(&ev_updated_, hipEventDisableTiming));
+      }
     } else {
       feat_src_ = map_host(ds.feat.ptr, ds.feat.bytes); // cache 0 %: DoGPUFeatureExtract from host, dist_loops.cc:585-634
     }
@@ -1881,7 +1930,48 @@ uint64_t Engine::GetNextBatch() { // operation.cc:366-378 + GraphPool::GetGraphB
   return b->key;
 }
 
+// samgraph_update_graph_feat (config key feat_learnable).  Gathers and updates share the one extract stream, so they are
+// totally ordered by the order of the calls that enqueue them: this update is seen by every batch a LATER sample_once
+// enqueues and by none enqueued before.  No host synchronisation: two events tie the caller's stream in.
+// (No stream of its own: see the note on the 4 hardware queues in EnqueueGather.)
+void Engine::UpdateGraphFeat(uint64_t key, const void *grad, size_t num_rows, size_t dim, hipStream_t caller) {
+  if (cfg.feat_learnable < 0) fatal(__FILE__, __LINE__, "samgraph_update_graph_feat needs the config key feat_learnable");
+  SAM_CHECK(train_ready_ && d_feat_, "engine not initialised");
+  Batch *b = Current(key); // the batch is still held: its input nodes and their count are read on the device
+  if (num_rows != b->num_input || dim != ds.feat_dim)
+    fatal(__FILE__, __LINE__, "samgraph_update_graph_feat: the gradient is (" + std::to_string(num_rows) + ", " +
+                                  std::to_string(dim) + "), batch " + std::to_string(key) + " delivered (" +
+                                  std::to_string(b->num_input) + ", " + std::to_string(ds.feat_dim) + ") rows");
+  SAM_CHECK(grad != nullptr || num_rows == 0, "samgraph_update_graph_feat: null gradient");
+  const uint32_t L = (uint32_t)cfg.fanout.size();
+  SAM_HIP(hipEventRecord(ev_grad_, caller)); // the gradient is produced on the caller's stream
+  SAM_HIP(hipStreamWaitEvent(stream_extract_, ev_grad_, 0));
+  SAM_GGMS(ggms_update_rows(d_feat_, d_feat_state_, b->trainer.input_nodes, num_rows,
+                            b->trainer.counts_dev + GGMS_COUNT_INPUT(L), grad, ds.feat_dim, cfg.feat_learnable, cfg.feat_lr,
+                            cfg.feat_eps, stream_extract_));
+  // the caller's stream goes on behind the update: its allocator cannot hand the gradient's memory to later work on that
+  // stream before the kernel has read it
+  SAM_HIP(hipEventRecord(ev_updated_, stream_extract_));
+  SAM_HIP(hipStreamWaitEvent(caller, ev_updated_, 0));
+}
+
+void *Engine::StoreFeat(const char *who) const {
+  if (cfg.feat_learnable < 0) fatal(__FILE__, __LINE__, std::string(who) + " needs the config key feat_learnable");
+  SAM_CHECK(d_feat_ != nullptr, "engine not initialised");
+  return d_feat_;
+}
+
+void *Engine::StoreState(const char *who) const {
+  if (cfg.feat_learnable != GGMS_UPDATE_ADAGRAD)
+    fatal(__FILE__, __LINE__, std::string(who) + " needs the config key feat_learnable = adagrad (SGD keeps no state)");
+  SAM_CHECK(d_feat_state_ != nullptr, "engine not initialised");
+  return d_feat_state_;
+}
+
 void Engine::ExtractStart(int count) { // dist_engine.cc StartExtract: one background sample+extract thread
+  if (cfg.feat_learnable >= 0)
+    fatal(__FILE__, __LINE__, "extract_start with feat_learnable: a background thread would make the updates a batch "
+                              "sees a matter of timing; call sample_once()");
   if (cfg.arch == kArch5) { // DataCopySubLoop(count), dist_loops_arch5.cc: `count` messages, then the thread ends
     SAM_CHECK(role_ == kRoleTrainer && train_ready_, "arch5: extract_start on a trainer, after train_init");
     SAM_CHECK(count >= 0, "arch5: extract_start(count >= 0)");

@@ -104,6 +104,11 @@ struct RunConfig {
   // extension (config key `exclude_seed_edges` = none | self | both; read with task = link_prediction only): the batch's
   // positive edges (self), and their mirrors (both), leave its sampled layers (ggms_drop_pair_edges' `which`; 0 = none)
   uint32_t exclude_seed_edges = 0;
+  // extension (config keys `feat_learnable` = sgd | adagrad, `feat_lr`, `feat_eps`; arch1, F32 tables): the device table
+  // is LEARNABLE -- samgraph_update_graph_feat applies a batch's gradient to the rows the batch gathered
+  // (ggms_update_rows' rule; -1: key absent, the table is read-only).  The other two keys are read with the first only
+  int feat_learnable = -1;
+  float feat_lr = 0.0f, feat_eps = 1e-10f;
   size_t staged_serial_epochs = 0; // host-staged path: the first N epochs run the reference's serial, per-phase-timed sequence
   size_t staged_serial_steps = 0;  // ... or this worker's first N batches
   // worker 0 ranks the nodes at init: pre_sample (sampled input nodes) or presample_static (L-hop closures)
@@ -251,6 +256,11 @@ class Engine {
   Batch *Current(uint64_t key);
   void Retain(uint64_t key);
   void Release(uint64_t key);
+  // feat_learnable: the current batch's gradient, (num_input, feat_dim) F32 produced on `caller`, moves the table rows the
+  // batch gathered; the live table and (Adagrad) its accumulator as they lie on the trainer GPU
+  void UpdateGraphFeat(uint64_t key, const void *grad, size_t num_rows, size_t dim, hipStream_t caller);
+  void *StoreFeat(const char *who) const;
+  void *StoreState(const char *who) const;
 
   size_t NumEpoch() const { return cfg.num_epoch; }
   size_t NumStep() const { return num_global_step_; }
@@ -406,6 +416,8 @@ class Engine {
   size_t num_replica_ = 0;                     // hybrid store: slots [0, num_replica_) live in d_replica_ on every GPU
   void *d_replica_ = nullptr;
   void *d_feat_ = nullptr;                     // full feature table on the device (arch1) ...
+  void *d_feat_state_ = nullptr;               // feat_learnable = adagrad: the accumulator, shaped like d_feat_
+  hipEvent_t ev_grad_ = nullptr, ev_updated_ = nullptr; // feat_learnable: caller's stream -> extract stream and back
   const void *feat_src_ = nullptr;             // ... or device-mapped host memory (gpu_extract / miss tier)
   const void *label_src_ = nullptr;
   // batches

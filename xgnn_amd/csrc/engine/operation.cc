@@ -149,6 +149,18 @@ size_t samgraph_get_graph_num_excluded(uint64_t key) {
   for (size_t i = 0; b->excluded && i < E.cfg.fanout.size(); ++i) total += b->excluded[i];
   return total;
 }
+// config key feat_learnable: the gradient of the current batch's rows moves the table; the live table and its state
+void samgraph_update_graph_feat(uint64_t key, const void *grad, size_t num_rows, size_t dim, void *caller_stream) {
+  Engine::Get().UpdateGraphFeat(key, grad, num_rows, dim, (hipStream_t)caller_stream);
+}
+void samgraph_get_store_feat(samgraph_tensor_t *out) {
+  auto &E = Engine::Get();
+  fill(out, E.StoreFeat("samgraph_get_store_feat"), (int64_t)E.ds.num_node, (int64_t)E.ds.feat_dim, 2, GGMS_F32, 2, E.trainer_device());
+}
+void samgraph_get_store_state(samgraph_tensor_t *out) {
+  auto &E = Engine::Get();
+  fill(out, E.StoreState("samgraph_get_store_state"), (int64_t)E.ds.num_node, (int64_t)E.ds.feat_dim, 2, GGMS_F32, 2, E.trainer_device());
+}
 size_t samgraph_num_negative(void) { return Engine::Get().cfg.link_prediction ? Engine::Get().cfg.num_negative : 0; }
 void samgraph_batch_retain(uint64_t key) { Engine::Get().Retain(key); }
 void samgraph_batch_release(uint64_t key) { Engine::Get().Release(key); }

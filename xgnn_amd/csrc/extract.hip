@@ -260,12 +260,6 @@ static inline bool part_ptrs(const void *const *parts, uint32_t num_part, PartPt
   return true;
 }
 
-__device__ __forceinline__ uint64_t shfl_u64(uint64_t v, int src) {
-  const uint32_t lo = __shfl((uint32_t)v, src, 64);
-  const uint32_t hi = __shfl((uint32_t)(v >> 32), src, 64);
-  return ((uint64_t)hi << 32) | lo;
-}
-
 // U = independent chunk loads in flight per lane (16, or 8 for rows of fewer than 8 chunks)
 // Loads and stores are non-temporal: a batch's rows are read once and the gathered batch is a > 100-MB stream that
 // nothing re-reads from cache (measured + 3..5 % on MI355X each, profiles/r01-r02).

@@ -296,6 +296,13 @@ int raise_dynamic_lds(const void *func, size_t bytes, const char *who);         
 // ---- wave / block prefix sums (wave64) -------------------------------------
 __device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63u; }
 
+// a 64-bit value (a row pointer or offset) from lane `src`: two ds_bpermute, no LDS memory
+__device__ __forceinline__ uint64_t shfl_u64(uint64_t v, int src) {
+  const uint32_t lo = __shfl((uint32_t)v, src, 64);
+  const uint32_t hi = __shfl((uint32_t)(v >> 32), src, 64);
+  return ((uint64_t)hi << 32) | lo;
+}
+
 __device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t x) {
 #pragma unroll
   for (int off = 1; off < 64; off <<= 1) {

@@ -408,6 +408,31 @@ def gather_scatter_convert(out, src, src_index, dst_index, num=None, num_dev=Non
     return out
 
 
+UPDATE_SGD, UPDATE_ADAGRAD = 0, 1  # GGMS_UPDATE_*: the rules of ggms_update_rows (include/ggms.h)
+
+
+def update_rows(table, nodes, grad, rule, lr, eps=1e-10, state=None, num=None, num_dev=None):
+    """ggms_update_rows: the float32 `table` (rows, dim) takes the gradient of the rows `nodes` names, in place --
+    row i of the contiguous float32 `grad` belongs to table row nodes[i].  rule: UPDATE_SGD (w -= lr * g) or
+    UPDATE_ADAGRAD (state += g * g; w -= lr * g / (sqrt(state) + eps), `state` shaped like the table), each operation
+    one float32 operation.  nodes must be pairwise distinct; EMPTY_KEY entries are skipped.  With num_dev (device
+    int64[1]) the count is read on the device and num is its upper bound."""
+    _require_gpu(table)
+    _i32(nodes)
+    assert table.dtype == torch.float32 and table.stride(-1) == 1 and (table.dim() < 2 or table.stride(0) == _dim_of(table)), \
+        "update_rows: the table is float32 with rows dim elements apart"
+    assert grad.dtype == torch.float32 and grad.is_contiguous() and _dim_of(grad) == _dim_of(table), \
+        f"update_rows: grad is a contiguous float32 (count, {_dim_of(table)}) tensor, not {grad.dtype} {tuple(grad.shape)}"
+    if state is not None:
+        assert state.dtype == torch.float32 and state.shape == table.shape and state.stride() == table.stride(), \
+            "update_rows: state is shaped like the table"
+    n = nodes.numel() if num is None else int(num)
+    assert n <= nodes.numel() and n <= grad.shape[0], "update_rows: num beyond nodes / grad"
+    check(lib().ggms_update_rows(_ptr(table), _ptr(state), _ptr(nodes), n, _ptr(num_dev), _ptr(grad), _dim_of(table),
+                                 rule, lr, eps, _stream()), "ggms_update_rows")
+    return table
+
+
 def quantize_rows(src, out_dtype, out=None, first_row=0, check=True):
     """ggms_quantize_rows: the 2-D float32 / float16 device tensor `src` encoded into out_dtype -- torch.float16,
     torch.bfloat16, torch.float8_e4m3fn, torch.float8_e5m2, or Q8ROW (returned as the uint8 (rows, row_bytes(Q8ROW, dim))

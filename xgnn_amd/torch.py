@@ -128,6 +128,36 @@ def get_graph_link_pairs(batch_key):
     return pos_src, pos_dst, pos_src.unsqueeze(1).expand(b, k), ids[2 * b:].view(b, k)
 
 
+def update_graph_feat(batch_key, grad):
+    """Config key feat_learnable: the gradient of get_graph_feat(batch_key) -- row i for row i -- moves the learnable
+    table's rows of the batch's input nodes (SGD or Adagrad, include/ggms.h ggms_update_rows).  `grad` is a contiguous
+    float32 CUDA tensor of the delivered shape on the trainer device, produced on the current stream; the call enqueues
+    and returns, and `grad` may be dropped right after it.  Batches enqueued by a LATER sample_once see the update."""
+    if not (torch.is_tensor(grad) and grad.is_cuda and grad.dtype == torch.float32 and grad.is_contiguous()):
+        raise ValueError("update_graph_feat: grad must be a contiguous float32 CUDA tensor, got "
+                         f"{getattr(grad, 'dtype', type(grad))} on {getattr(grad, 'device', '?')}"
+                         f"{'' if not torch.is_tensor(grad) or grad.is_contiguous() else ' (not contiguous)'}")
+    t = _CTensor()
+    _basics.C_LIB_CTYPES.samgraph_get_graph_feat(batch_key, C.byref(t))
+    if grad.device.index != t.device_id:
+        raise ValueError(f"update_graph_feat: grad is on {grad.device}, the trainer device is cuda:{t.device_id}")
+    delivered = (int(t.shape[0]), int(t.shape[1]))
+    if tuple(grad.shape) != delivered:  # (the engine checks again for callers of the C entry, and aborts)
+        raise ValueError(f"update_graph_feat: grad of shape {tuple(grad.shape)}, batch {batch_key} delivered {delivered}")
+    _basics.C_LIB_CTYPES.samgraph_update_graph_feat(batch_key, grad.data_ptr(), grad.shape[0], grad.shape[1],
+                                                    torch.cuda.current_stream(grad.device).cuda_stream)
+
+
+def get_store_feat():
+    """The live learnable table (config key feat_learnable): a zero-copy (num_node, feat_dim) float32 device view."""
+    return _get("samgraph_get_store_feat", None)
+
+
+def get_store_state():
+    """The Adagrad accumulator of the learnable table (feat_learnable = adagrad), shaped like get_store_feat()."""
+    return _get("samgraph_get_store_state", None)
+
+
 def _create_dgl_block(data, num_src_nodes, num_dst_nodes):
     import dgl  # DGL-on-ROCm is needed only here, exactly where the reference needs it (adapter.py:131-136)
     from dgl.heterograph import DGLBlock
