@@ -124,11 +124,18 @@ void ggms_debug_delay_next_scan(uint32_t sleeps);
  *                                 place by the generating lanes)
  *   GGMS_DEBUG_OWNER_SCAN_CHUNKS  workgroups of the chunked owner scan (small: chunks too long for registers are read
  *                                 twice)
- *   GGMS_DEBUG_OWNER_SCAN_TILES   != 0: the tile-chained owner scan (by default only beyond 65 M items per fill) */
+ *   GGMS_DEBUG_OWNER_SCAN_TILES   != 0: the tile-chained owner scan (by default only beyond 65 M items per fill)
+ *   GGMS_DEBUG_GRID_CAP           1..2048: no size-dependent launch gets more workgroups of 256 threads than this
+ *                                 (default 2048; a larger value is the default: the knob can only shrink a grid), so
+ *                                 that a few thousand items take every grid-stride kernel through its later rounds --
+ *                                 next-tile prefetch hand-over, LDS reuse behind the closing barrier, the ticketed
+ *                                 forms taken when there are fewer workgroups than tiles.  Read on the host, once per
+ *                                 launch.  Launches of a fixed shape do not look at it (DESIGN.md lists them). */
 #define GGMS_DEBUG_KHOP0_DRAW_CAP 0
 #define GGMS_DEBUG_OWNER_SCAN_CHUNKS 1
 #define GGMS_DEBUG_OWNER_SCAN_TILES 2
-#define GGMS_DEBUG_NUM_KNOBS 3
+#define GGMS_DEBUG_GRID_CAP 3
+#define GGMS_DEBUG_NUM_KNOBS 4
 void ggms_debug_set_knob(int knob, long long value);
 size_t ggms_dtype_bytes(int dtype);
 /* bytes from one stored row of `dim` elements to the next: dim x ggms_dtype_bytes(dtype) for the element types,

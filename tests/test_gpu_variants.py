@@ -12,7 +12,8 @@ from xgnn_amd._lib import COUNT_DST, COUNT_EDGES, COUNT_INPUT, COUNT_SRC, COUNT_
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-KHOP0_DRAW_CAP, OWNER_SCAN_CHUNKS, OWNER_SCAN_TILES = 0, 1, 2
+KHOP0_DRAW_CAP, OWNER_SCAN_CHUNKS, OWNER_SCAN_TILES, GRID_CAP = 0, 1, 2, 3  # GGMS_DEBUG_* (GRID_CAP: test_gpu_grid_rounds.py)
+NUM_KNOBS = 4
 P_dev, P_u32 = P.dev, P.host_u32
 
 
@@ -33,7 +34,8 @@ def knob():
         used.append(which)
         lib().ggms_debug_set_knob(which, value)
     yield set_knob
-    for w in used:
+    assert all(0 <= w < NUM_KNOBS for w in used)
+    for w in range(NUM_KNOBS):  # every knob back to its default, the ones a called test set by itself included
         lib().ggms_debug_set_knob(w, -1)
 
 

@@ -82,7 +82,7 @@ bool host_readable_table(const void *table, const char *what) {
 }
 
 std::atomic<long long> &debug_knob_word(int knob) {
-  static std::atomic<long long> v[GGMS_DEBUG_NUM_KNOBS] = {{-1}, {-1}, {-1}};
+  static std::atomic<long long> v[GGMS_DEBUG_NUM_KNOBS] = {{-1}, {-1}, {-1}, {-1}};
   return v[knob];
 }
 long long debug_knob(int knob) { return debug_knob_word(knob).load(std::memory_order_relaxed); }

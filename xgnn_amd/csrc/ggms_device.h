@@ -36,12 +36,28 @@ void set_error(const char *fmt, ...);
 inline hipStream_t to_stream(ggms_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 // Grid for a grid-stride kernel over n items, capped at every wave slot of the device (256 CUs x 32 waves =
-// 2048 blocks x 256 threads).
-inline size_t grid_cap() { return (size_t)kMaxGridBlocks; }
+// 2048 blocks x 256 threads).  ggms_debug_set_knob(GGMS_DEBUG_GRID_CAP) (tests) lowers the cap, never raises it:
+// every launch whose grid follows the input size takes it from here (or clamps grid_cap() itself), so a few thousand
+// items reach the rounds that otherwise need hundreds of thousands.  One relaxed load per launch.
+// NOT capped, by design -- launches of a fixed shape, whose kernels have no round loop over workgroups to reach, or whose
+// grid is part of the result:
+//   dim3(1): k_record, k_status_copy, k_closure_mark, k_prefetch_cap, k_small_scan / k_small_scan2, k_sort_small,
+//            k_tile_prefix_t;
+//   k_drop_prefix (one workgroup per layer), k_batch_handoff (one workgroup per 16 KiB of each segment, no loop),
+//   k_map_rest_all's grid.y (one row of workgroups per deferred job; grid.x is capped);
+//   k_copy_prefix (256 workgroups whatever the count), k_probe_copy16 and k_fabric_probe (measuring tools);
+//   k_weighted_draw: its thread count IS the reference's task -> RNG stream map (min(tasks, 512 K) threads, stride
+//            `span`, not gridDim); fewer threads would draw other numbers.
+long long debug_knob(int knob); // common.hip: ggms_debug_set_knob's value, -1 = default
+inline size_t grid_cap() {
+  const long long v = debug_knob(GGMS_DEBUG_GRID_CAP);
+  return v >= 1 && v < (long long)kMaxGridBlocks ? (size_t)v : (size_t)kMaxGridBlocks;
+}
 inline int grid_for(size_t n, size_t per_block) {
   size_t g = (n + per_block - 1) / per_block;
+  const size_t cap = grid_cap();
   if (g < 1) g = 1;
-  if (g > grid_cap()) g = grid_cap();
+  if (g > cap) g = cap;
   return (int)g;
 }
 
@@ -54,7 +70,6 @@ inline int grid_for(size_t n, size_t per_block) {
 constexpr uint32_t kErrScanSpin = 1u;    // decoupled look-back gave up waiting for a predecessor tile
 constexpr uint32_t kErrTableFull = 2u;   // hashed dedup table: probing found no free bucket
 uint32_t *device_status_word();          // common.hip; NULL if it cannot be allocated
-long long debug_knob(int knob);          // common.hip: ggms_debug_set_knob's value, -1 = default
 
 // ---- a count that lives either in an argument or in device memory ---------
 // Lets a whole mini-batch be enqueued without a host round trip: the size of

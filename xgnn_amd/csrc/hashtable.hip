@@ -804,7 +804,8 @@ int ht_fill_impl(const ggms_hashtable_t *ht, const uint32_t *input, size_t n_max
   // items, and fewer chunks than kChunkGrid (chunks too long for registers take the two-pass form)
   const bool force_tiles = debug_knob(GGMS_DEBUG_OWNER_SCAN_TILES) > 0;
   const long long knob_chunks = debug_knob(GGMS_DEBUG_OWNER_SCAN_CHUNKS);
-  const size_t chunk_grid = knob_chunks > 0 && knob_chunks < (long long)kChunkGrid ? (size_t)knob_chunks : (size_t)kChunkGrid;
+  const size_t chunk_grid = std::min(knob_chunks > 0 && knob_chunks < (long long)kChunkGrid ? (size_t)knob_chunks : (size_t)kChunkGrid,
+                                     grid_cap()); // GGMS_DEBUG_GRID_CAP counts here too: a chunk is a workgroup
   const int cgrid = (int)std::min<size_t>(std::max<size_t>(owner_scan_tiles(n_max), 1), chunk_grid);
   // a chunk's owner count travels in 16 bits: at most kChunkMaxTiles tiles per chunk (65 M items at the full grid);
   // beyond that the tile-chained kernel runs

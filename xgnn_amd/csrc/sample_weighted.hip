@@ -420,7 +420,8 @@ int sample_weighted_hash_dedup_impl(const SampleLayer &l) {
   // each (a quarter of the generator instructions per stream) were built and measured slower too (a wave then waits
   // for the slowest of 16 streams instead of 4), as were 8 and 32 lanes per stream
   // (profiles/r03_ab_hash_dedup_lanes_per_stream.txt).  Only <16, 1> is built.
-  hipLaunchKernelGGL((k_weighted_hash_dedup<16, 1>), dim3((unsigned)std::min<size_t>((256 / (64 / 16)) * blocks, 8192)),
+  // one-wave workgroups: four of them to a 256-thread workgroup of grid_cap() (8192 = every wave slot)
+  hipLaunchKernelGGL((k_weighted_hash_dedup<16, 1>), dim3((unsigned)std::min<size_t>((256 / (64 / 16)) * blocks, 4 * grid_cap())),
                      dim3(kWave), 0, l.s, l.graph->indptr, l.graph->indices, l.prob, l.alias, l.input, l.n, fanout, offset,
                      l.out_src, l.out_dst, l.states, l.src, di);
   GGMS_LAUNCH_CHECK();
