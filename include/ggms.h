@@ -548,6 +548,35 @@ int ggms_drop_pair_edges(const ggms_id_t *pair_src, const ggms_id_t *pair_dst, s
                          void *workspace, size_t workspace_bytes, ggms_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Edge ids of a sampled batch (an extension; DGL hands them out as dgl.EID, PyG as e_id): for every edge of every layer
+ * the position of that edge in the graph's CSR -- the index edge data (weights, attributes, labels, timestamps) is
+ * stored under, and the id space of ggms_link_seeds' edge ids.  A post-pass over a finished batch, behind any sampler
+ * and behind ggms_drop_pair_edges: no sampler emits anything for it.
+ *   per edge    for layer i and edge k < n_i: s = id_map ? id_map[col[i][k]] : col[i][k] (the node whose list was read),
+ *               t = id_map ? id_map[row[i][k]] : row[i][k] (the sampled neighbour); eid[i][k] = the smallest p with
+ *               indptr[s] <= p < indptr[s + 1] and indices[p] == t.  No such p, or s or t equal to GGMS_EMPTY_KEY or
+ *               >= graph->num_node: eid[i][k] = GGMS_EMPTY_KEY.  A row / col entry >= num_id_map (id_map's length;
+ *               ignored without id_map) maps to GGMS_EMPTY_KEY.  A pure function of (graph, s, t): parallel edges all get
+ *               the first copy's position, repeated picks of one neighbour the same id.
+ *   per layer i n_i = counts_dev[GGMS_COUNT_EDGES(i)] is read on the device; max_edges[i] (>= n_i) only sizes launches
+ *               and workspace.  Entries of eid[i] behind n_i are not written.  row / col / eid are HOST arrays of
+ *               num_layer device pointers; nothing but eid and the workspace is written.
+ *   arguments   a sharded graph (num_part != 0), num_edge = indptr[num_node] >= 2^32 - 1 (GGMS_EMPTY_KEY would be a
+ *               position), num_layer == 0 or > 16, a null array, a workspace below ggms_edge_positions_workspace_bytes
+ *               (0 for arguments out of range): GGMS_ERR_INVALID with a message, before any device call.
+ * Like every entry point: no allocation, no synchronisation, every size stays on the device.  One 16-byte memset and TWO
+ * launches per call, whatever num_layer and the n_i are: a wave takes 64 consecutive edges, finds the runs of equal s
+ * among them and streams each run's list once, matching 64 entries at a time against the run's targets; lists longer
+ * than 1024 entries are queued in the workspace and spread over 16 waves each by the second launch, which combines with
+ * a minimum.  Nothing survives the call.
+ * ------------------------------------------------------------------------- */
+size_t ggms_edge_positions_workspace_bytes(const size_t *max_edges, uint32_t num_layer);
+int ggms_edge_positions(const ggms_graph_t *graph, uint64_t num_edge, const ggms_id_t *id_map /* may be NULL */,
+                        size_t num_id_map, const ggms_id_t *const *row, const ggms_id_t *const *col,
+                        ggms_id_t *const *eid, const size_t *max_edges, uint32_t num_layer, const uint64_t *counts_dev,
+                        void *workspace, size_t workspace_bytes, ggms_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * arch4's batch with early feature prefetch -- DoGPUSampleDyCache (cuda/cuda_loops.cc:294-524).  The layers of
  * ggms_sample_batch, except:
  *   - after the second-to-last layer's table fill, every neighbour of every node entered so far (n2o[0, k)) is

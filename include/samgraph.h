@@ -138,6 +138,23 @@ size_t samgraph_get_graph_num_excluded(uint64_t key);
 void samgraph_update_graph_feat(uint64_t key, const void *grad, size_t num_rows, size_t dim, void *caller_stream);
 void samgraph_get_store_feat(samgraph_tensor_t *out);
 void samgraph_get_store_state(samgraph_tensor_t *out);
+/* Extensions for config keys edge_ids = on and edge_feat = on (arch1, one CSR; refused by name with every other
+ * deployment, use_dist_graph, random_walk and khop2; edge_feat implies edge_ids).  Behind the sampler -- and behind
+ * exclude_seed_edges' filter -- ggms_edge_positions (include/ggms.h) computes for every edge of every layer its position
+ * in indices.bin: the id edge data is stored under, and the id space of train_edge_set.bin.
+ *   samgraph_get_graph_edge_ids(key, layer)    num_edge(layer) positions, uint32 bits in samgraph_get_graph_row's dtype;
+ *     indices[id] is the global id of the edge's row node, the edge lies in the list of its col node.  Parallel edges all
+ *     carry the first copy's position.
+ *   samgraph_get_graph_edge_feat(key, layer)   with edge_feat: (num_edge(layer), EDGE_FEAT_DIM) rows of edge_feat.bin
+ *     (NUM_EDGE rows in CSR order, uploaded to the GPU at init; meta.txt: EDGE_FEAT_DIM and, optionally,
+ *     EDGE_FEAT_DATA_TYPE -- F32 without it, any element type, not Q8ROW), row k = table[edge_ids[k]], in the table's
+ *     dtype: feat_out_dtype does not apply.  A missing file or meta key and a file of another size are fatal at init.
+ *   samgraph_get_graph_link_edge_ids(key)      task = link_prediction (no other key needed): the batch's B positive
+ *     edge ids, what a rating or label per positive is looked up with.
+ * Without the keys nothing runs and nothing is allocated; the first two accessors are then fatal. */
+void samgraph_get_graph_edge_ids(uint64_t key, int layer_idx, samgraph_tensor_t *out);
+void samgraph_get_graph_edge_feat(uint64_t key, int layer_idx, samgraph_tensor_t *out);
+void samgraph_get_graph_link_edge_ids(uint64_t key, samgraph_tensor_t *out);
 /* a batch's buffers stay valid while its retain count is > 0 */
 void samgraph_batch_retain(uint64_t key);
 void samgraph_batch_release(uint64_t key);

@@ -12,12 +12,17 @@ batch_size counts positive EDGES; the batch's seed list is their B (2 + K) endpo
 num_dst is B (2 + K) while the distinct endpoints are the first max(id) + 1 nodes of the batch.
 
     python tools/example_link_prediction.py <dataset_dir> [--epochs 2] [--batch-size 512] [--num-negative 3]
-        [--exclude-seed-edges none|self|both] [--learn-features sgd|adagrad --feat-lr 0.05]
+        [--exclude-seed-edges none|self|both] [--learn-features sgd|adagrad --feat-lr 0.05] [--edge-weight]
 
 --learn-features makes the engine's feature table the model's trainable input embedding (config keys feat_learnable,
 feat_lr): the batch's rows become a leaf that requires grad, and after backward() their gradient goes back with
 sam.update_graph_feat(key, h.grad) -- the table moves on the device, no copy of it lives in torch.  The rows are used
 as they are (no 1 / 65536): give such a dataset a feat.bin that is an embedding's initial value, small random numbers.
+
+--edge-weight reads the dataset's edge table (config key edge_feat; datagen.write_dataset(..., edge_feat=...)): column 0
+of sam.get_graph_edge_feat(key, i), the row of every sampled edge of layer i, scales that edge's message, and the mean
+becomes the weighted mean.  sam.get_graph_edge_ids(key, i) are the ids the rows were gathered under -- what a model with
+its own per-edge parameters would index them with -- and sam.get_graph_link_edge_ids(key) those of the positives.
 """
 import argparse
 import os
@@ -29,6 +34,17 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import samgraph.torch as sam  # noqa: E402
 from example_train_sage import SageLayer  # noqa: E402
+
+
+class WeightedSageLayer(SageLayer):
+    """SageLayer whose neighbour term is the mean weighted by a scalar per edge."""
+
+    def forward(self, h, row, col, num_dst, weight):
+        agg = torch.zeros((num_dst, h.shape[1]), dtype=h.dtype, device=h.device)
+        total = torch.zeros(num_dst, dtype=h.dtype, device=h.device)
+        agg.index_add_(0, col, h[row] * weight.unsqueeze(1))
+        total.index_add_(0, col, weight)
+        return self.w_self(h[:num_dst]) + self.w_nbr(agg / total.clamp(min=1e-12).unsqueeze(1))
 
 
 def main():
@@ -47,10 +63,13 @@ def main():
     ap.add_argument("--learn-features", choices=["sgd", "adagrad"],
                     help="train the feature table itself with this rule (config key feat_learnable)")
     ap.add_argument("--feat-lr", type=float, default=0.05, help="learning rate of the feature table (feat_lr)")
+    ap.add_argument("--edge-weight", action="store_true",
+                    help="scale every message by column 0 of the edge's row of the dataset's edge table (edge_feat)")
     args = ap.parse_args()
     L = len(args.fanout)
+    edge = {"edge_feat": "on"} if args.edge_weight else {}
     learn = {"feat_learnable": args.learn_features, "feat_lr": args.feat_lr} if args.learn_features else {}
-    sam.config({**learn, "dataset_path": args.dataset, "_arch": sam.builtin_archs["arch1"]["arch"],
+    sam.config({**learn, **edge, "dataset_path": args.dataset, "_arch": sam.builtin_archs["arch1"]["arch"],
                 "_sample_type": sam.sample_types[args.sample_type], "batch_size": args.batch_size,
                 "num_epoch": args.epochs, "_cache_policy": sam.cache_policies["degree"], "cache_percentage": 0.0,
                 "max_sampling_jobs": 10, "max_copying_jobs": 1, "omp_thread_num": 4, "num_layer": L,
@@ -62,7 +81,7 @@ def main():
     dev = torch.device("cuda", 0)
     torch.manual_seed(args.seed)
     dims = [sam.feat_dim()] + [args.hidden] * L
-    layers = torch.nn.ModuleList([SageLayer(dims[i], dims[i + 1]) for i in range(L)]).to(dev)
+    layers = torch.nn.ModuleList([(WeightedSageLayer if edge else SageLayer)(dims[i], dims[i + 1]) for i in range(L)]).to(dev)
     opt = torch.optim.Adam(layers.parameters(), lr=0.003)
     steps = sam.steps_per_epoch()
     for epoch in range(args.epochs):
@@ -80,7 +99,9 @@ def main():
             for i in range(L):
                 row, col, num_src, num_dst = coo[i]
                 assert h.shape[0] == num_src
-                h = layers[i](h, row.long(), col.long(), num_dst if i + 1 < L else num_out)
+                # (edge k of the layer is CSR position sam.get_graph_edge_ids(key, i)[k]; its row was gathered under that id)
+                w = (sam.get_graph_edge_feat(key, i)[:, 0].float().abs(),) if edge else ()
+                h = layers[i](h, row.long(), col.long(), num_dst if i + 1 < L else num_out, *w)
                 if i + 1 < L:
                     h = torch.relu(h)
             pos = (h[pos_src] * h[pos_dst]).sum(1)

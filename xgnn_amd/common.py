@@ -112,6 +112,8 @@ SAMGRAPH_SYMBOLS = {
     "samgraph_get_graph_output_nodes": (None, [_u64, _TP]),
     "samgraph_get_graph_seed_ids": (None, [_u64, _TP]), "samgraph_num_negative": (_sz, []),
     "samgraph_get_graph_num_excluded": (_sz, [_u64]),
+    "samgraph_get_graph_edge_ids": (None, [_u64, _i, _TP]), "samgraph_get_graph_edge_feat": (None, [_u64, _i, _TP]),
+    "samgraph_get_graph_link_edge_ids": (None, [_u64, _TP]),
     "samgraph_update_graph_feat": (None, [_u64, C.c_void_p, _sz, _sz, C.c_void_p]),
     "samgraph_get_store_feat": (None, [_TP]), "samgraph_get_store_state": (None, [_TP]),
     "samgraph_batch_retain": (None, [_u64]), "samgraph_batch_release": (None, [_u64]),

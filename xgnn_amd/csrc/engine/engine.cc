@@ -333,6 +333,29 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
     // enqueued before its gather was
     cfg.extract_streams = 1;
   }
+  if (kv.count("edge_ids") || kv.count("edge_feat")) { // extension: CSR positions (and edge-table rows) of the sampled edges
+    for (const char *key : {"edge_ids", "edge_feat"})
+      if (kv.count(key) && kv[key] != "on" && kv[key] != "off")
+        fatal(__FILE__, __LINE__, std::string(key) + " = " + kv[key] + ": on or off (the default)");
+    cfg.edge_feat = kv.count("edge_feat") && kv["edge_feat"] == "on";
+    cfg.edge_ids = cfg.edge_feat || (kv.count("edge_ids") && kv["edge_ids"] == "on");
+  }
+  if (cfg.edge_ids) {
+    static const char *const arch_names[] = {"arch0", "arch1", "arch2", "arch3", "arch4", "arch5", "arch6", "arch7"};
+    const std::string key = cfg.edge_feat ? "edge_feat" : "edge_ids";
+    if (cfg.arch != kArch1)
+      fatal(__FILE__, __LINE__, std::string(arch_names[cfg.arch]) + ": " + key + " is not built: the edge positions are "
+                                "computed behind arch1's sampling chain and travel through no hand-off or queue");
+    if (cfg.use_dist_graph)
+      fatal(__FILE__, __LINE__, key + " with use_dist_graph: an edge id is a position in ONE CSR, a sharded topology has "
+                                "none");
+    if (cfg.sample_type == GGMS_RANDOM_WALK)
+      fatal(__FILE__, __LINE__, key + " with _sample_type 3 (random_walk) is not built: its edges join a node and a node "
+                                "it visited, they are not edges of the graph");
+    if (cfg.sample_type == GGMS_KHOP2)
+      fatal(__FILE__, __LINE__, key + " with _sample_type 5 (khop2) is not built: khop2 permutes indices in place, a "
+                                "position names another edge after every batch");
+  }
   if (cfg.arch == kArch4) { // DoGPUSampleDyCache's switch (cuda/cuda_loops.cc:347-377) and what it needs
     if (cfg.sample_type != GGMS_KHOP0 && cfg.sample_type != GGMS_KHOP1 && cfg.sample_type != GGMS_WEIGHTED_KHOP)
       fatal(__FILE__, __LINE__, "arch4: _sample_type " + std::to_string(cfg.sample_type) + " is not supported: the "
@@ -418,6 +441,12 @@ void Engine::LoadDataset() {
                                   "F8E4M3, F8E5M2 and Q8ROW tables only");
       // a row-scaled table has no element type to hand out raw: only the converting gather can deliver its rows
       if (ds.feat_dtype == GGMS_Q8ROW && cfg.feat_out_dtype < 0) fatal(__FILE__, __LINE__, kQ8RowNeedsOutDtype);
+    } else if (k == "EDGE_FEAT_DATA_TYPE") { // (read whatever the config says: the file describes the dataset)
+      SAM_CHECK(kFeatDtypeNames.count(v), "unknown EDGE_FEAT_DATA_TYPE " + v);
+      ds.edge_feat_dtype = kFeatDtypeNames.at(v);
+      if (cfg.edge_feat && ds.edge_feat_dtype == GGMS_Q8ROW)
+        fatal(__FILE__, __LINE__, "edge_feat with EDGE_FEAT_DATA_TYPE Q8ROW: the edge rows are moved by the plain gather, "
+                                  "which takes element types only; a row-scaled edge table is not built");
     } else {
       meta[k] = std::stoull(v);
     }
@@ -525,6 +554,23 @@ void Engine::LoadDataset() {
       ds.num_train_edge = ds.num_edge;
     }
     SAM_CHECK(ds.num_train_edge > 0, "task = link_prediction: the train edge set is empty");
+  }
+  if (cfg.edge_ids && ds.num_edge >= 0xffffffffull)
+    fatal(__FILE__, __LINE__, std::string(cfg.edge_feat ? "edge_feat" : "edge_ids") + ": " + std::to_string(ds.num_edge) +
+                                  " edges: edge ids are 32-bit positions, at most 2^32 - 2 of them");
+  if (cfg.edge_feat) { // the edge table: NUM_EDGE rows in CSR order
+    if (!meta.count("EDGE_FEAT_DIM") || meta["EDGE_FEAT_DIM"] == 0)
+      fatal(__FILE__, __LINE__, "edge_feat: meta.txt lacks EDGE_FEAT_DIM (elements per row of edge_feat.bin)");
+    ds.edge_feat_dim = meta["EDGE_FEAT_DIM"];
+    const std::string name = cfg.dataset_path + "edge_feat.bin";
+    struct stat st;
+    if (stat(name.c_str(), &st) != 0)
+      fatal(__FILE__, __LINE__, "edge_feat: " + name + " is missing (NUM_EDGE rows of EDGE_FEAT_DIM elements, CSR order)");
+    const size_t want = ds.num_edge * ds.edge_feat_row_bytes();
+    if ((size_t)st.st_size != want)
+      fatal(__FILE__, __LINE__, "edge_feat: edge_feat.bin has " + std::to_string((size_t)st.st_size) + " bytes, NUM_EDGE x "
+                                    "EDGE_FEAT_DIM x the element size is " + std::to_string(want));
+    ds.edge_feat = MapFile("edge_feat.bin", want, false);
   }
   if (cfg.sample_type == GGMS_WEIGHTED_KHOP || cfg.sample_type == GGMS_WEIGHTED_KHOP_HASH_DEDUP) { // engine.cc:372-384
     ds.prob_table = MapFile("prob_table.bin", ds.num_edge * 4, false);
@@ -1044,6 +1090,11 @@ void Engine::SampleInit(int worker_id, const std::string &ctx) {
     SAM_CHECK(drop_ws_bytes_ > 0, "exclude_seed_edges: the batch bounds are out of ggms_drop_pair_edges' range");
     for (Pipe &P : pipes_) SAM_HIP(hipMalloc(&P.drop_ws, drop_ws_bytes_));
   }
+  if (cfg.edge_ids) { // the long-list queue of ggms_edge_positions, one per pipeline
+    eid_ws_bytes_ = ggms_edge_positions_workspace_bytes(max_edges_.data(), L);
+    SAM_CHECK(eid_ws_bytes_ > 0, "edge_ids: the batch bounds are out of ggms_edge_positions' range");
+    for (Pipe &P : pipes_) SAM_HIP(hipMalloc(&P.eid_ws, eid_ws_bytes_));
+  }
   SAM_HIP(hipStreamSynchronize(stream_));
   prof.Resize(cfg.num_epoch, num_global_step_);
   if (cfg.UsePresample()) { // dist_engine.cc:455-466: worker 0 ranks the nodes, everybody waits
@@ -1253,6 +1304,7 @@ void Engine::BuildCache() {
       // arch1: the whole table lives in HBM and is gathered directly (cuda_loops_arch1.cc:61)
       d_feat_ = dev_upload(feat, ds.feat.bytes, bs);
       feat_src_ = d_feat_;
+      if (cfg.edge_feat) d_edge_feat_ = dev_upload(ds.edge_feat.ptr, ds.edge_feat.bytes, bs); // the edge table, beside it
       if (cfg.feat_learnable >= 0) { // the upload is the learnable table's initial value; Adagrad's accumulator starts at 0
         if (cfg.feat_learnable == GGMS_UPDATE_ADAGRAD) {
           SAM_HIP(hipMalloc(&d_feat_state_, std::max<size_t>(ds.feat.bytes, 16)));
@@ -1432,6 +1484,14 @@ void Engine::TrainInit(int worker_id, const std::string &ctx) {
         SAM_HIP(hipMalloc((void **)&b->excluded_dev, L * 8));
         SAM_HIP(hipHostMalloc((void **)&b->excluded, L * 8));
         std::memset(b->excluded, 0, L * 8);
+      }
+    }
+    if (cfg.edge_ids) { // per layer: the edges' CSR positions and, with edge_feat, the edge table's rows under them
+      b->eid.assign(L, nullptr);
+      b->efeat.assign(L, nullptr);
+      for (uint32_t i = 0; i < L; ++i) {
+        SAM_HIP(hipMalloc((void **)&b->eid[i], std::max<size_t>(max_edges_[i], 4) * 4));
+        if (cfg.edge_feat) SAM_HIP(hipMalloc(&b->efeat[i], std::max<size_t>(max_edges_[i] * ds.edge_feat_row_bytes(), 16)));
       }
     }
     if (StagedHostTier()) { // index arrays of GetMissCacheIndex + pinned / device staging of the miss rows
@@ -1632,6 +1692,13 @@ void Engine::SampleInto(Batch *b, Pipe &P) {
       SAM_HIP(hipMemcpyAsync(b->excluded, b->excluded_dev, L * 8, hipMemcpyDeviceToHost, P.stream));
     }
   }
+  if (cfg.edge_ids) {
+    // Which edge of the graph every sampled edge is: a post-pass over the finished layers (behind the filter: the ids of
+    // the edges that are left), with the batch's own input nodes as the local -> global map.  Same stream, no new one
+    // (EnqueueGather's note on the four hardware queues), in front of ev_sampled like everything that writes the batch.
+    SAM_GGMS(ggms_edge_positions(&graph_, ds.num_edge, s.input_nodes, max_unique_, s.row.data(), s.col.data(),
+                                 b->eid.data(), max_edges_.data(), L, s.counts_dev, P.eid_ws, eid_ws_bytes_, P.stream));
+  }
   SAM_HIP(hipMemsetAsync(s.counts_dev + GGMS_COUNT_MISS(L), 0, 8, P.stream)); // the trainer's miss count starts at 0
   SAM_HIP(hipEventRecord(b->ev_sampled, P.stream));
 }
@@ -1682,6 +1749,13 @@ void Engine::EnqueueGather(Batch *b, hipStream_t ss) {
     }
     SAM_GGMS(ggms_extract(b->label, label_src_, b->trainer.output_nodes, b->num_seeds, 1, GGMS_I64, xs));
   }
+  // edge_feat: the edge table's rows under the layers' edge ids, table[eid], with the plain row gather and the device
+  // edge count.  On the node rows' stream and IN FRONT of their gather: a lean batch is complete when that gather's
+  // own packet says so (gather_timer), and stream order then covers these.
+  if (cfg.edge_feat)
+    for (uint32_t i = 0; i < L; ++i)
+      SAM_GGMS(ggms_gather_scatter(b->efeat[i], d_edge_feat_, b->eid[i], nullptr, max_edges_[i],
+                                   b->trainer.counts_dev + GGMS_COUNT_EDGES(i), ds.edge_feat_dim, ds.edge_feat_dtype, xs));
   if (b->lean) SAM_GGMS(ggms_launch_timer_arm(b->gather_timer));
   else SAM_HIP(hipEventRecord(b->ev_xstart, xs)); // the extract's own start: behind the previous batch's extract on xs
   // the rows are delivered in the batch's dtype (config key feat_out_dtype; the table's own without the key, which is

@@ -109,6 +109,10 @@ struct RunConfig {
   // (ggms_update_rows' rule; -1: key absent, the table is read-only).  The other two keys are read with the first only
   int feat_learnable = -1;
   float feat_lr = 0.0f, feat_eps = 1e-10f;
+  // extension (config keys `edge_ids` = on, `edge_feat` = on; arch1, one CSR, not random_walk / khop2): every layer of a
+  // batch comes with its edges' CSR positions (ggms_edge_positions behind the sampler), and with edge_feat -- which
+  // implies edge_ids -- with the rows of edge_feat.bin those positions name
+  bool edge_ids = false, edge_feat = false;
   size_t staged_serial_epochs = 0; // host-staged path: the first N epochs run the reference's serial, per-phase-timed sequence
   size_t staged_serial_steps = 0;  // ... or this worker's first N batches
   // worker 0 ranks the nodes at init: pre_sample (sampled input nodes) or presample_static (L-hop closures)
@@ -143,6 +147,12 @@ struct Dataset {
   // bytes from one STORED row of the table to the next: what sizes and strides the table, the cache, its shards and
   // replicas and the staging buffers (feat_dim x element bytes; a Q8ROW row is its codes, pad and scale / bias trailer)
   size_t feat_row_bytes() const { return ggms_row_bytes(feat_dtype, feat_dim); }
+  // edge_feat: edge_feat.bin, NUM_EDGE rows of EDGE_FEAT_DIM elements of EDGE_FEAT_DATA_TYPE (F32 without the key) in CSR
+  // order
+  size_t edge_feat_dim = 0;
+  int edge_feat_dtype = GGMS_F32;
+  HostArray edge_feat;
+  size_t edge_feat_row_bytes() const { return edge_feat_dim * ggms_dtype_bytes(edge_feat_dtype); }
 };
 
 // ---- Profiler log store: profiler.h:166-215 ------------------------------------
@@ -210,6 +220,10 @@ struct Batch {
   // exclude_seed_edges: the edges ggms_drop_pair_edges took out of each layer -- device words (zeroed per batch) and
   // their pinned host copy, valid with the counts.  Null without the key: the batch then carries no extra packet.
   uint64_t *excluded_dev = nullptr, *excluded = nullptr;
+  // edge_ids / edge_feat: per layer, the CSR positions of the layer's edges (max_edges words) and the edge table's rows
+  // under them.  Empty without the keys.
+  std::vector<uint32_t *> eid;
+  std::vector<void *> efeat;
   uint64_t num_miss = 0;
   hipEvent_t ev_seeds = nullptr, ev_start = nullptr, ev_sampled = nullptr, ev_xstart = nullptr, ev_done = nullptr;
   // arch6 with `gpu_extract` off: the host-staged miss path (dist_loops.cc:1015-1207)
@@ -382,8 +396,11 @@ class Engine {
     hipEvent_t rng_done = nullptr;
     void *drop_ws = nullptr; // exclude_seed_edges: ggms_drop_pair_edges' workspace, a piece of its own (the seed ids it
                              // reads lie in `ws`)
+    void *eid_ws = nullptr;  // edge_ids: ggms_edge_positions' workspace
   };
   size_t drop_ws_bytes_ = 0;
+  size_t eid_ws_bytes_ = 0;    // edge_ids: ggms_edge_positions' workspace (Pipe::eid_ws)
+  void *d_edge_feat_ = nullptr; // edge_feat: the edge table in HBM
   uint64_t link_excluded_ = 0; // exclude_seed_edges: edges dropped from the batches handed out so far in this epoch
   std::vector<Pipe> pipes_;
   size_t enq_count_ = 0;

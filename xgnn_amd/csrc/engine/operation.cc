@@ -149,6 +149,30 @@ size_t samgraph_get_graph_num_excluded(uint64_t key) {
   for (size_t i = 0; b->excluded && i < E.cfg.fanout.size(); ++i) total += b->excluded[i];
   return total;
 }
+// config keys edge_ids / edge_feat: layer l's edge ids (CSR positions; the uint32 bits in get_graph_row's dtype) and the
+// edge table's rows under them, (num_edge(l), EDGE_FEAT_DIM) in the table's dtype
+void samgraph_get_graph_edge_ids(uint64_t key, int l, samgraph_tensor_t *out) {
+  auto &E = Engine::Get();
+  if (!E.cfg.edge_ids) sam::fatal(__FILE__, __LINE__, "samgraph_get_graph_edge_ids needs the config key edge_ids = on (or edge_feat = on)");
+  auto *b = E.Current(key);
+  SAM_CHECK(l >= 0 && (size_t)l < b->eid.size(), "samgraph_get_graph_edge_ids: no such layer");
+  fill(out, b->eid[l], (int64_t)b->counts[GGMS_COUNT_EDGES(l)], 1, 1, GGMS_I32, E.batch_device_type(), E.trainer_device());
+}
+void samgraph_get_graph_edge_feat(uint64_t key, int l, samgraph_tensor_t *out) {
+  auto &E = Engine::Get();
+  if (!E.cfg.edge_feat) sam::fatal(__FILE__, __LINE__, "samgraph_get_graph_edge_feat needs the config key edge_feat = on");
+  auto *b = E.Current(key);
+  SAM_CHECK(l >= 0 && (size_t)l < b->efeat.size(), "samgraph_get_graph_edge_feat: no such layer");
+  fill(out, b->efeat[l], (int64_t)b->counts[GGMS_COUNT_EDGES(l)], (int64_t)E.ds.edge_feat_dim, 2, E.ds.edge_feat_dtype,
+       E.batch_device_type(), E.trainer_device());
+}
+// task = link_prediction: the batch's positive edge ids (CSR positions, the id space of the edge ids above)
+void samgraph_get_graph_link_edge_ids(uint64_t key, samgraph_tensor_t *out) {
+  auto &E = Engine::Get();
+  if (!E.cfg.link_prediction) sam::fatal(__FILE__, __LINE__, "samgraph_get_graph_link_edge_ids needs task = link_prediction");
+  auto *b = E.Current(key);
+  fill(out, b->edge_ids, (int64_t)b->num_pos, 1, 1, GGMS_I32, E.batch_device_type(), E.trainer_device());
+}
 // config key feat_learnable: the gradient of the current batch's rows moves the table; the live table and its state
 void samgraph_update_graph_feat(uint64_t key, const void *grad, size_t num_rows, size_t dim, void *caller_stream) {
   Engine::Get().UpdateGraphFeat(key, grad, num_rows, dim, (hipStream_t)caller_stream);

@@ -143,7 +143,7 @@ def build_prob_prefix_table(indptr, weights, num_threads=8):
 
 
 def write_dataset(path, graph, feat=None, label=None, valid_frac=0.02, test_frac=0.05, feat_dtype="F32", weights=None,
-                  minimal=False, train_edges=None):
+                  minimal=False, train_edges=None, edge_feat=None, edge_feat_dtype="F32"):
     """Write a dataset directory in the reference's on-disk format (datagen/README.md:37-51,
     samgraph/common/constant.cc:23-51, engine.cc:109-443): meta.txt (tab separated) + raw little-endian
     arrays: indptr/indices/train_set/test_set/valid_set/cache_by_* uint32, feat row-major, label int64;
@@ -152,6 +152,9 @@ def write_dataset(path, graph, feat=None, label=None, valid_frac=0.02, test_frac
     weights (one float per edge) adds prob_table.bin / alias_table.bin / prob_prefix_table.bin.
     train_edges (uint32 positions in indices, each below the edge count) adds train_edge_set.bin, the set a
     link_prediction run shuffles (config key `task`); without it such a run takes every edge.
+    edge_feat (one row per edge, in the order of indices; a 1-d array is dim 1) adds edge_feat.bin and the meta keys
+    EDGE_FEAT_DIM / EDGE_FEAT_DATA_TYPE, the table of config key `edge_feat`; edge_feat_dtype names an element type
+    (FP8: as for feat), not Q8ROW.
     minimal: what a sampling + extract run needs and nothing that costs minutes at papers100M size -- one-node
     valid / test sets instead of random slices of the complement, no cache_by_random.bin."""
     import os
@@ -183,6 +186,14 @@ def write_dataset(path, graph, feat=None, label=None, valid_frac=0.02, test_frac
             assert feat.dtype == np.uint8 and feat.shape == (n, q8row_stride(meta["feat_dim"])), \
                 f"a Q8ROW table is the packed uint8 rows ({n}, {q8row_stride(meta['feat_dim'])}), not {feat.dtype} {feat.shape}"
         np.ascontiguousarray(feat).tofile(os.path.join(path, "feat.bin"))
+    if edge_feat is not None:
+        assert edge_feat_dtype != "Q8ROW", "edge_feat_dtype: an element type; a row-scaled edge table is not built"
+        if edge_feat_dtype in FP8_FORMATS:
+            edge_feat = _fp8_bytes(edge_feat, edge_feat_dtype)
+        edge_feat = np.ascontiguousarray(edge_feat)
+        edge_feat = edge_feat.reshape(edge_feat.shape[0], -1)
+        assert edge_feat.shape[0] == ix.size, f"edge_feat: one row per edge ({ix.size}), not {edge_feat.shape[0]}"
+        edge_feat.tofile(os.path.join(path, "edge_feat.bin"))
     if label is not None:
         np.ascontiguousarray(label, dtype=np.int64).tofile(os.path.join(path, "label.bin"))
     if weights is not None:  # tables of the weighted samplers (engine.cc:372-384 loads them by these names)
@@ -200,6 +211,9 @@ def write_dataset(path, graph, feat=None, label=None, valid_frac=0.02, test_frac
             f.write(f"{k}\t{v}\n")
         if feat_dtype != "F32":
             f.write(f"FEAT_DATA_TYPE\t{feat_dtype}\n")
+        if edge_feat is not None:
+            f.write(f"EDGE_FEAT_DIM\t{edge_feat.shape[1]}\n")
+            f.write(f"EDGE_FEAT_DATA_TYPE\t{edge_feat_dtype}\n")
     return path
 
 

@@ -208,6 +208,39 @@ def drop_pair_edges(pair_src, pair_dst, which, rows, cols, counts, max_edges=Non
     return num_dropped
 
 
+def edge_positions(graph, rows, cols, counts, id_map=None, max_edges=None, eids=None, num_edge=None):
+    """ggms_edge_positions: for every edge k < counts[COUNT_EDGES(i)] of every layer (rows[i], cols[i]) the CSR position of
+    the edge (s -> t), s = id_map[cols[i][k]], t = id_map[rows[i][k]] (the ids themselves without id_map): the smallest p
+    in s's list with indices[p] == t, EMPTY_KEY (-1 as int32) where there is none or an id is no node.  counts: a device
+    int64 tensor in the batch counts layout.  max_edges: the layers' bounds (default: the tensors' lengths).  eids: the
+    output tensors (entries behind the count are left alone; fresh ones unless given).  num_edge: indptr[-1] (default:
+    indices' length).  Returns eids."""
+    L = len(rows)
+    _require_gpu(counts)
+    dev = counts.device
+    assert counts.dtype == torch.int64 and counts.is_contiguous()
+    for t in list(rows) + list(cols):
+        _require_gpu(_i32(t))
+    me = [int(x) for x in max_edges] if max_edges is not None else [min(r.numel(), c.numel()) for r, c in zip(rows, cols)]
+    if eids is None:
+        eids = [torch.empty(max(1, m), dtype=torch.int32, device=dev) for m in me]
+    for t, m in zip(eids, me):
+        _require_gpu(_i32(t))
+        assert t.numel() >= m, "edge_positions: an eid tensor is shorter than its layer's bound"
+    if id_map is not None:
+        _require_gpu(_i32(id_map))
+    c_me = (C.c_size_t * max(1, L))(*me)
+    ws = _workspace(lib().ggms_edge_positions_workspace_bytes(c_me, L), dev)
+    c_rows = (C.c_void_p * max(1, L))(*[t.data_ptr() for t in rows])
+    c_cols = (C.c_void_p * max(1, L))(*[t.data_ptr() for t in cols])
+    c_eids = (C.c_void_p * max(1, L))(*[t.data_ptr() for t in eids])
+    ne = int(num_edge) if num_edge is not None else graph.indices.numel()
+    check(lib().ggms_edge_positions(C.byref(graph.c), ne, _ptr(id_map), id_map.numel() if id_map is not None else 0,
+                                    c_rows, c_cols, c_eids, c_me, L, _ptr(counts), _ptr(ws), ws.numel() * 4, _stream()),
+          "ggms_edge_positions")
+    return eids
+
+
 def sample_weighted_khop_prefix(graph, prob_prefix_table, inp, fanout, states):
     """GPUSampleWeightedKHopPrefix (cuda_sampling_weighted_khop_prefix.cu:145-246)."""
     return _sample("ggms_sample_weighted_khop_prefix", WEIGHTED_KHOP_PREFIX, graph, inp, fanout, states,

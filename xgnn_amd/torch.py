@@ -116,6 +116,23 @@ def get_graph_output_nodes(batch_key): return _get("samgraph_get_graph_output_no
 def get_graph_seed_ids(batch_key): return _get("samgraph_get_graph_seed_ids", batch_key)
 
 
+def get_graph_edge_ids(batch_key, layer_idx):
+    """Config key edge_ids (or edge_feat): the CSR position of every edge of the layer (DGL's dgl.EID, PyG's e_id), int32
+    holding the uint32 bits -- the index edge data is stored under, and the id space of get_graph_link_edge_ids."""
+    return _get("samgraph_get_graph_edge_ids", batch_key, layer_idx)
+
+
+def get_graph_edge_feat(batch_key, layer_idx):
+    """Config key edge_feat: (num_edge, EDGE_FEAT_DIM) rows of the dataset's edge table, row k that of edge k of the
+    layer, in the table's dtype."""
+    return _get("samgraph_get_graph_edge_feat", batch_key, layer_idx)
+
+
+def get_graph_link_edge_ids(batch_key):
+    """The positive edge ids (CSR positions) of a link_prediction batch, in the order of get_graph_link_pairs."""
+    return _get("samgraph_get_graph_link_edge_ids", batch_key)
+
+
 def get_graph_link_pairs(batch_key):
     """(pos_src, pos_dst, neg_src, neg_dst) of a link_prediction batch: views of the batch's one id tensor
     (get_graph_seed_ids), B positives and K negatives each -- pos_src, pos_dst of shape (B,), neg_src (pos_src expanded)
