@@ -117,6 +117,12 @@ void ggms_debug_set_scan_patience(uint32_t polls);
  * patience the others compute its word themselves and the last one replaces the table's item count by the total before
  * that workgroup starts: the "owner arrives late" case of the self-serve look-back.  One shot. */
 void ggms_debug_delay_next_scan(uint32_t sleeps);
+/* Test aid: every ordered scan of this process tags its descriptors with an epoch drawn from ONE launch counter --
+ * the next scan takes (counter + 1) mod 2^30, skipping 0; the chunked owner scan's 16-bit descriptors carry
+ * epoch % 65535 + 1.  This sets the counter and returns its previous value, so that a test reaches the 30-bit wrap
+ * and the 16-bit wrap (every 65535 scans: a few thousand batches) in a handful of launches.  Put the returned value
+ * back afterwards: later scans then never repeat an epoch already left behind in device memory. */
+uint32_t ggms_debug_set_scan_epoch(uint32_t counter);
 /* Test aids (this process): force a slower, result-identical form of a kernel that default sizes rarely or never
  * reach.  value < 0 restores the default.  The library reads NO environment variable for any of this (the one it
  * reads is GGMS_EXTRACT_BLOCKS, the gather's grid cap).

@@ -99,6 +99,7 @@ SYMBOLS = {
     "ggms_debug_poison_next_scan": (None, []),
     "ggms_debug_set_scan_patience": (None, [C.c_uint32]),
     "ggms_debug_delay_next_scan": (None, [C.c_uint32]),
+    "ggms_debug_set_scan_epoch": (C.c_uint32, [C.c_uint32]),
     "ggms_debug_set_knob": (None, [_i, C.c_longlong]),
     "ggms_fabric_probe": (_i, [_i, _vp, _sz, _sz, _u32, _vp, _vp]),
     "ggms_dtype_bytes": (_sz, [_i]),

@@ -862,6 +862,7 @@ extern "C" {
 void ggms_debug_poison_next_scan(void) { g_poison_next_scan.store(true); }
 void ggms_debug_set_scan_patience(uint32_t polls) { scan_patience_word().store(polls); }
 void ggms_debug_delay_next_scan(uint32_t sleeps) { scan_delay_word().store(sleeps); }
+uint32_t ggms_debug_set_scan_epoch(uint32_t counter) { return scan_epoch_counter().exchange(counter); }
 
 size_t ggms_hashtable_num_buckets(size_t capacity) {
   size_t half = capacity >> 1;

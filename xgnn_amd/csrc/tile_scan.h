@@ -82,8 +82,13 @@ inline uint32_t *take_ticket_set(ScanArea *a) {
   return a->tickets + (size_t)kTicketWords * a->next_ticket_set++;
 }
 
-inline uint32_t next_scan_epoch() {
+// the process-wide launch counter behind the epochs (ggms_debug_set_scan_epoch moves it: tests of the wraps below)
+inline std::atomic<uint32_t> &scan_epoch_counter() {
   static std::atomic<uint32_t> g{0};
+  return g;
+}
+inline uint32_t next_scan_epoch() {
+  std::atomic<uint32_t> &g = scan_epoch_counter();
   uint32_t e;
   do { e = (g.fetch_add(1) + 1) & 0x3fffffffu; } while (e == 0);
   return e;
