@@ -200,7 +200,8 @@ enum ggms_sample_type {
   GGMS_KHOP2 = 5,
   GGMS_WEIGHTED_KHOP_HASH_DEDUP = 6,
   GGMS_KHOP3 = 7,
-  GGMS_KHOP_LABOR = 8 /* an extension: ggms_sample_khop_labor below */
+  GGMS_KHOP_LABOR = 8, /* an extension: ggms_sample_khop_labor below */
+  GGMS_KHOP_TEMPORAL = 9 /* an extension: ggms_sample_khop_temporal / ggms_sample_batch_temporal below */
 };
 
 /* Workspace of every leaf sampler below but random walk, whose size depends on
@@ -242,6 +243,35 @@ int ggms_sample_khop_labor(const ggms_graph_t *graph, const ggms_id_t *input,
                            ggms_id_t *out_src, ggms_id_t *out_dst,
                            uint64_t *num_out_dev, void *workspace,
                            size_t workspace_bytes, ggms_stream_t stream);
+
+/* khop_temporal (an extension; the reference has no such sampler; DGL: temporal_sample_neighbors, PyG: NeighborLoader's
+ * time_attr): fixed-fanout sampling among the edges that lie strictly BEFORE a per-seed cut-off time.
+ *   edge_time   one uint32 per position of graph->indices.  PRECONDITION: inside every node's list the times are
+ *               non-decreasing (a time-sorted CSR), so the eligible edges of a seed are a prefix of its list.
+ *   eligible    seed i is node s = input[i] with cut-off c = input_cut[i]; its list is the positions
+ *               [indptr[s], indptr[s + 1]); e = the number of its entries with edge_time[p] < c (strict) -- under the
+ *               precondition the first e positions.  c = 0: nothing is eligible; c = 0xffffffff: every edge with a time
+ *               below 2^32 - 1.  A list that violates the precondition: WHICH edges come out is unspecified, but nothing
+ *               is read or written out of bounds and every emitted position lies in the seed's list.
+ *   GGMS_PICK_UNIFORM  khop_labor's rule on the prefix: the min(fanout, e) positions p of [0, e) with the smallest keys
+ *               (fmix32(t_p ^ layer_salt) << 32) | p, ascending position.  Each seed gets a uniform sample without
+ *               replacement of its past; seeds that share neighbours share picks; multi-edges tie on the hash and break
+ *               by position.
+ *   GGMS_PICK_RECENT   the last min(fanout, e) positions of the prefix, ascending ("most recent neighbours").
+ *   output      seeds in input order; out_src / out_dst as khop_labor writes them; out_pos[k] = the edge's position in
+ *               graph->indices, indptr[s] + p -- the index of its time and of every other per-edge array.  Duplicate
+ *               seeds with different cuts are independent.  All three outputs hold num_input * fanout entries.
+ *   arguments   refused with GGMS_ERR_INVALID before any device call: a sharded graph (positions are those of ONE CSR),
+ *               fanout 0 or >= 128, a pick other than the two, a null array, a short workspace.  Positions are 32-bit:
+ *               a CSR of 2^32 - 1 edges or more cannot be expressed in ggms_id_t offsets in the first place.
+ * Stateless: a pure function of (graph, edge_time, input, input_cut, fanout, pick, layer_salt).  No allocation, no
+ * synchronisation, every size stays on the device.  Workspace: ggms_sample_workspace_bytes(GGMS_KHOP_TEMPORAL, ...). */
+#define GGMS_PICK_UNIFORM 0
+#define GGMS_PICK_RECENT 1
+int ggms_sample_khop_temporal(const ggms_graph_t *graph, const uint32_t *edge_time, const ggms_id_t *input,
+                              const uint32_t *input_cut, size_t num_input, size_t fanout, int pick,
+                              uint32_t layer_salt, ggms_id_t *out_src, ggms_id_t *out_dst, ggms_id_t *out_pos,
+                              uint64_t *num_out_dev, void *workspace, size_t workspace_bytes, ggms_stream_t stream);
 
 /* GPUSampleWeightedKHopPrefix, cuda/cuda_sampling_weighted_khop_prefix.cu:145-246:
  * prob_prefix_table = per-list inclusive prefix sums of the edge weights; one
@@ -488,6 +518,60 @@ int ggms_sample_batch(int sample_type, const ggms_graph_t *graph,
 int ggms_sample_batch_seed_ids(int sample_type, size_t num_seeds, const size_t *fanouts, uint32_t num_layer,
                                const ggms_sample_extra_t *extra, const void *workspace,
                                const ggms_id_t **seed_ids_dev);
+
+/* ---------------------------------------------------------------------------
+ * The temporal batch (an extension): ggms_sample_batch's layers with khop_temporal as the sampler.  A batch dedups by
+ * NODE, but a node can be reached from seeds with different times; the rule keeps the node-level dedup and never leaks:
+ * a node's cut-off is the minimum of the times of the seeds that reach it.
+ *   cut[v] = +inf (0xffffffff) for all v
+ *   for raw seed position j:  cut[seeds[j]] = min(cut[seeds[j]], seed_time[j])
+ *   frontier = the raw seeds                      (layer L-1; later layers: n2o[0, num_dst(i)))
+ *   for i = L-1 .. 0:
+ *     c_f = cut[f] for every frontier entry f, AS IT STANDS WHEN THE LAYER STARTS
+ *     sample f with cut c_f (ggms_sample_khop_temporal's rule, layer_salt = fmix32(labor_salt + 0x9e3779b9 * (i + 1)))
+ *     for every emitted edge (f -> t):  cut[t] = min(cut[t], c_f)
+ *     dedup / numbering exactly as ggms_sample_batch does it
+ *   no leak     every sampled edge has edge_time[eid] < cut[col] as the cut stood when the layer started, and every root
+ *               that a node's layer-i sample feeds has a time >= that cut.  (node_cut holds the FINAL cuts, which later
+ *               layers may have lowered further: edge_time[eid] < node_cut[col] holds for the layer that last lowered
+ *               col's cut and every layer after it.)
+ *   duplicates  a raw seed that occurs twice with different times is sampled with the smaller one both times.
+ *   elsewhere   the result equals per-seed temporal sampling (DGL, PyG) whenever no node is reached under two
+ *               different times; it is conservative (an older cut) otherwise.
+ *   purity      a pure function of (graph, times, seeds, seed_time, fanouts, pick, salt): a minimum does not care about
+ *               arrival order.
+ * State: cut_table, num_node 64-bit words owned by the caller and zeroed ONCE; every batch on a table passes a `stamp`
+ * larger than any used on it before (1, 2, 3, ...; ggms_khop_closure's `visit` convention; after 0xffffffff the table
+ * is zeroed again).  A word is (stamp << 32) | (0xffffffff - cut) under a 64-bit atomic maximum: a newer stamp beats a
+ * stale word, within a stamp the smaller cut wins, a word with another stamp reads as absent.  The seeds' cuts are
+ * entered by one small launch, the neighbours' by the sampler as it emits (one atomic per sampled edge, nothing
+ * returned); a layer reads the table only in its first launch, in front of the launches that write it.
+ *   eid         HOST array of L device pointers, capacities max_edges[i]: eid[i][k] = CSR position of edge k of layer i
+ *               (the table fills never reorder edges)
+ *   node_cut    device, max_unique words: node_cut[local id] = the final cut of that input node
+ *   counts_dev, row, col, both table layouts, the numbering: ggms_sample_batch's.  extra->labor_salt is the batch salt
+ *   (NULL: 0); rng_wait / rng_done and seeds_distinct are ignored.  ggms_sample_batch_seed_ids(GGMS_KHOP_TEMPORAL, ...)
+ *   gives the raw seeds' local ids.  ggms_sample_batch(GGMS_KHOP_TEMPORAL, ...) is GGMS_ERR_INVALID.
+ * ------------------------------------------------------------------------- */
+typedef struct {
+  const uint32_t *edge_time; /* device, one per CSR position */
+  uint64_t *cut_table;       /* device, graph->num_node words */
+  uint32_t stamp;            /* != 0, larger than any used on cut_table since it was zeroed */
+  uint32_t pick;             /* GGMS_PICK_UNIFORM | GGMS_PICK_RECENT */
+} ggms_temporal_t;
+size_t ggms_sample_batch_temporal_workspace_bytes(size_t num_seeds, const size_t *fanouts, uint32_t num_layer,
+                                                  const ggms_sample_extra_t *extra);
+int ggms_sample_batch_temporal(const ggms_graph_t *graph, const ggms_id_t *seeds, const uint32_t *seed_time,
+                               size_t num_seeds, const size_t *fanouts, uint32_t num_layer, ggms_hashtable_t *ht,
+                               ggms_id_t *const *row, ggms_id_t *const *col, ggms_id_t *const *eid, uint32_t *node_cut,
+                               uint64_t *counts_dev, const ggms_temporal_t *t, const ggms_sample_extra_t *extra,
+                               void *workspace, size_t workspace_bytes, ggms_stream_t stream);
+/* The seed times of a link batch: out_time[q] = edge_time[edge_ids[i]] for every position q of ggms_link_seeds'
+ * endpoint layout that belongs to positive i (its source, its destination and its num_negative negatives).  num_edge is
+ * the length of edge_time; an id >= num_edge gives 0 (nothing is eligible).  One launch. */
+int ggms_link_seed_times(const uint32_t *edge_time, uint64_t num_edge, const ggms_id_t *edge_ids, size_t num_pos,
+                         uint32_t num_negative, uint32_t *out_time /* num_pos * (2 + num_negative) */,
+                         ggms_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Link-prediction seeds (an extension; the reference has no such operator): a batch of positive EDGE ids becomes the

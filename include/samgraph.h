@@ -155,6 +155,21 @@ void samgraph_get_store_state(samgraph_tensor_t *out);
 void samgraph_get_graph_edge_ids(uint64_t key, int layer_idx, samgraph_tensor_t *out);
 void samgraph_get_graph_edge_feat(uint64_t key, int layer_idx, samgraph_tensor_t *out);
 void samgraph_get_graph_link_edge_ids(uint64_t key, samgraph_tensor_t *out);
+/* Extensions for _sample_type 9 (khop_temporal; config key temporal_pick = uniform | recent; arch1 with task =
+ * link_prediction and one CSR -- every other deployment, task = node_classification, use_dist_graph and
+ * exclude_seed_edges other than none are refused by name).  The dataset carries edge_time.bin: NUM_EDGE uint32, one per
+ * position of indices.bin, non-decreasing inside every node's list (size and order are checked at init, fatal with the
+ * node).  Every entry of a batch's seed list is sampled strictly BEFORE the time of its positive edge, a node reached
+ * under several times before the smallest of them (ggms_sample_batch_temporal, include/ggms.h).  edge_ids is implied:
+ * the sampler emits the positions itself -- parallel edges carry their OWN position -- and edge_feat gathers under them.
+ *   samgraph_get_graph_edge_time(key, layer)   num_edge(layer) times, edge_time[edge_ids[k]]
+ *   samgraph_get_graph_node_cut(key)           one cut-off per input node (the final one): what a time encoding of an
+ *                                              edge, cut[col] - edge_time, is taken against
+ *   samgraph_get_graph_link_time(key)          the times of the batch's B positive edges
+ * All three: uint32 bits in samgraph_get_graph_row's dtype; fatal with every other sample type. */
+void samgraph_get_graph_edge_time(uint64_t key, int layer_idx, samgraph_tensor_t *out);
+void samgraph_get_graph_node_cut(uint64_t key, samgraph_tensor_t *out);
+void samgraph_get_graph_link_time(uint64_t key, samgraph_tensor_t *out);
 /* a batch's buffers stay valid while its retain count is > 0 */
 void samgraph_batch_retain(uint64_t key);
 void samgraph_batch_release(uint64_t key);

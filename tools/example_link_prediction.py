@@ -13,6 +13,7 @@ num_dst is B (2 + K) while the distinct endpoints are the first max(id) + 1 node
 
     python tools/example_link_prediction.py <dataset_dir> [--epochs 2] [--batch-size 512] [--num-negative 3]
         [--exclude-seed-edges none|self|both] [--learn-features sgd|adagrad --feat-lr 0.05] [--edge-weight]
+        [--temporal [--temporal-pick uniform|recent]]
 
 --learn-features makes the engine's feature table the model's trainable input embedding (config keys feat_learnable,
 feat_lr): the batch's rows become a leaf that requires grad, and after backward() their gradient goes back with
@@ -23,6 +24,11 @@ as they are (no 1 / 65536): give such a dataset a feat.bin that is an embedding'
 of sam.get_graph_edge_feat(key, i), the row of every sampled edge of layer i, scales that edge's message, and the mean
 becomes the weighted mean.  sam.get_graph_edge_ids(key, i) are the ids the rows were gathered under -- what a model with
 its own per-edge parameters would index them with -- and sam.get_graph_link_edge_ids(key) those of the positives.
+
+--temporal samples with sample_type khop_temporal on a dataset that carries edge_time.bin (datagen.write_dataset(...,
+edge_time=...)): every endpoint of a positive is sampled strictly before the positive's time, so exclude_seed_edges is
+none.  The age of every sampled edge, dt = sam.get_graph_node_cut(key)[col] - sam.get_graph_edge_time(key, i), is the
+model's edge input: a message is scaled by 1 / (1 + log(1 + dt)), recent interactions count more.
 """
 import argparse
 import os
@@ -65,9 +71,15 @@ def main():
     ap.add_argument("--feat-lr", type=float, default=0.05, help="learning rate of the feature table (feat_lr)")
     ap.add_argument("--edge-weight", action="store_true",
                     help="scale every message by column 0 of the edge's row of the dataset's edge table (edge_feat)")
+    ap.add_argument("--temporal", action="store_true",
+                    help="sample_type khop_temporal: neighbours from strictly before each positive's time (edge_time.bin)")
+    ap.add_argument("--temporal-pick", default="uniform", choices=["uniform", "recent"])
     args = ap.parse_args()
     L = len(args.fanout)
     edge = {"edge_feat": "on"} if args.edge_weight else {}
+    if args.temporal:  # strictly-before already removes the positive, its mirror at the same time, and everything later
+        args.sample_type, args.exclude_seed_edges = "khop_temporal", "none"
+        edge["temporal_pick"] = args.temporal_pick
     learn = {"feat_learnable": args.learn_features, "feat_lr": args.feat_lr} if args.learn_features else {}
     sam.config({**learn, **edge, "dataset_path": args.dataset, "_arch": sam.builtin_archs["arch1"]["arch"],
                 "_sample_type": sam.sample_types[args.sample_type], "batch_size": args.batch_size,
@@ -100,7 +112,14 @@ def main():
                 row, col, num_src, num_dst = coo[i]
                 assert h.shape[0] == num_src
                 # (edge k of the layer is CSR position sam.get_graph_edge_ids(key, i)[k]; its row was gathered under that id)
-                w = (sam.get_graph_edge_feat(key, i)[:, 0].float().abs(),) if edge else ()
+                w = ()
+                if args.edge_weight:
+                    w = (sam.get_graph_edge_feat(key, i)[:, 0].float().abs(),)
+                if args.temporal:  # the edge's age against the cut-off of the node it was sampled for (uint32 bits)
+                    cut = sam.get_graph_node_cut(key).long() & 0xFFFFFFFF
+                    dt = (cut[col.long()] - (sam.get_graph_edge_time(key, i).long() & 0xFFFFFFFF)).clamp(min=0).float()
+                    decay = 1.0 / (1.0 + torch.log1p(dt))
+                    w = (w[0] * decay if w else decay,)
                 h = layers[i](h, row.long(), col.long(), num_dst if i + 1 < L else num_out, *w)
                 if i + 1 < L:
                     h = torch.relu(h)

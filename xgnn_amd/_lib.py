@@ -27,6 +27,11 @@ class SampleExtra(C.Structure):
                 ("seeds_distinct", C.c_uint32), ("labor_salt", C.c_uint32)]
 
 
+class Temporal(C.Structure):
+    """ggms_temporal_t"""
+    _fields_ = [("edge_time", C.c_void_p), ("cut_table", C.c_void_p), ("stamp", C.c_uint32), ("pick", C.c_uint32)]
+
+
 class FeatureTiers(C.Structure):
     """ggms_feature_tiers_t"""
     _fields_ = [("table", C.c_void_p), ("replica", C.c_void_p), ("num_replica", C.c_uint64),
@@ -110,6 +115,8 @@ SYMBOLS = {
     "ggms_sample_khop3": (_i, [C.POINTER(Graph), _vp, _sz, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "ggms_sample_khop0": (_i, [C.POINTER(Graph), _vp, _sz, _sz, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ggms_sample_khop_labor": (_i, [C.POINTER(Graph), _vp, _sz, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ggms_sample_khop_temporal": (_i, [C.POINTER(Graph), _vp, _vp, _vp, _sz, _sz, _i, C.c_uint32, _vp, _vp, _vp, _vp, _vp,
+                                       _sz, _vp]),
     "ggms_sample_khop1": (_i, [C.POINTER(Graph), _vp, _sz, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "ggms_sample_khop2": (_i, [C.POINTER(Graph), _vp, _sz, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "ggms_sample_weighted_workspace_bytes": (_sz, [_sz, _sz]),
@@ -137,6 +144,11 @@ SYMBOLS = {
     "ggms_sample_batch": (_i, [_i, C.POINTER(Graph), _vp, _sz, C.POINTER(_sz), _u32, C.POINTER(HashTable), _vp, _sz,
                                C.POINTER(_vp), C.POINTER(_vp), _vp, C.POINTER(SampleExtra), _vp, _sz, _vp]),
     "ggms_sample_batch_seed_ids": (_i, [_i, _sz, C.POINTER(_sz), _u32, C.POINTER(SampleExtra), _vp, C.POINTER(_vp)]),
+    "ggms_sample_batch_temporal_workspace_bytes": (_sz, [_sz, C.POINTER(_sz), _u32, C.POINTER(SampleExtra)]),
+    "ggms_sample_batch_temporal": (_i, [C.POINTER(Graph), _vp, _vp, _sz, C.POINTER(_sz), _u32, C.POINTER(HashTable),
+                                        C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, C.POINTER(Temporal),
+                                        C.POINTER(SampleExtra), _vp, _sz, _vp]),
+    "ggms_link_seed_times": (_i, [_vp, _u64, _vp, _sz, _u32, _vp, _vp]),
     "ggms_link_seeds": (_i, [C.POINTER(Graph), _vp, _sz, _u32, _i, _u32, _vp, _vp, _vp]),
     "ggms_drop_pair_edges_workspace_bytes": (_sz, [_sz, C.POINTER(_sz), _u32]),
     "ggms_drop_pair_edges": (_i, [_vp, _vp, _sz, _u32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz), _u32, _vp, _vp,

@@ -11,6 +11,7 @@ from . import _lib
 kCPU, kMMAP, kGPU = 0, 1, 2
 kKHop0, kKHop1, kWeightedKHop, kRandomWalk, kWeightedKHopPrefix, kKHop2, kWeightedKHopHashDedup, kKHop3 = range(8)
 kKHopLabor = 8  # an extension: fixed-fanout LABOR sampling (include/ggms.h, GGMS_KHOP_LABOR)
+kKHopTemporal = 9  # an extension: sampling strictly before the seed's time (include/ggms.h, GGMS_KHOP_TEMPORAL)
 kArch0, kArch1, kArch2, kArch3, kArch4, kArch5, kArch6, kArch7 = range(8)
 (kCacheByDegree, kCacheByHeuristic, kCacheByPreSample, kCacheByDegreeHop, kCacheByPreSampleStatic,
  kCacheByFakeOptimal, kDynamicCache, kCacheByRandom) = range(8)
@@ -27,7 +28,7 @@ def gpu(device_id=0):
 sample_types = {
     'khop0': kKHop0, 'khop1': kKHop1, 'khop2': kKHop2, 'khop3': kKHop3, 'random_walk': kRandomWalk,
     'weighted_khop': kWeightedKHop, 'weighted_khop_prefix': kWeightedKHopPrefix,
-    'weighted_khop_hash_dedup': kWeightedKHopHashDedup, 'khop_labor': kKHopLabor,
+    'weighted_khop_hash_dedup': kWeightedKHopHashDedup, 'khop_labor': kKHopLabor, 'khop_temporal': kKHopTemporal,
 }
 builtin_archs = {
     'arch0': {'arch': kArch0, 'sampler_ctx': cpu(), 'trainer_ctx': gpu(0)},
@@ -114,6 +115,8 @@ SAMGRAPH_SYMBOLS = {
     "samgraph_get_graph_num_excluded": (_sz, [_u64]),
     "samgraph_get_graph_edge_ids": (None, [_u64, _i, _TP]), "samgraph_get_graph_edge_feat": (None, [_u64, _i, _TP]),
     "samgraph_get_graph_link_edge_ids": (None, [_u64, _TP]),
+    "samgraph_get_graph_edge_time": (None, [_u64, _i, _TP]), "samgraph_get_graph_node_cut": (None, [_u64, _TP]),
+    "samgraph_get_graph_link_time": (None, [_u64, _TP]),
     "samgraph_update_graph_feat": (None, [_u64, C.c_void_p, _sz, _sz, C.c_void_p]),
     "samgraph_get_store_feat": (None, [_TP]), "samgraph_get_store_state": (None, [_TP]),
     "samgraph_batch_retain": (None, [_u64]), "samgraph_batch_release": (None, [_u64]),

@@ -227,7 +227,12 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
     cfg.lookahead = 0;
     cfg.pipelines = 1;
   }
-  SAM_CHECK(cfg.sample_type >= GGMS_KHOP0 && cfg.sample_type <= GGMS_KHOP_LABOR, "unknown sample type");
+  SAM_CHECK(cfg.sample_type >= GGMS_KHOP0 && cfg.sample_type <= GGMS_KHOP_TEMPORAL, "unknown sample type");
+  if (cfg.Temporal() && cfg.arch != kArch1) {
+    static const char *const arch_names[] = {"arch0", "arch1", "arch2", "arch3", "arch4", "arch5", "arch6", "arch7"};
+    fatal(__FILE__, __LINE__, std::string(arch_names[cfg.arch]) + ": _sample_type 9 (khop_temporal) is not built: the seed "
+                              "times, the cut table and the edge positions run in arch1's sampling chain only");
+  }
   if (cfg.sample_type == GGMS_KHOP_LABOR && cfg.arch == kArch0)
     fatal(__FILE__, __LINE__, "arch0: _sample_type 8 (khop_labor) is not supported: the CPU engine has no sampler for "
                               "it; it samples with khop0 or khop2");
@@ -333,6 +338,24 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
     // enqueued before its gather was
     cfg.extract_streams = 1;
   }
+  if (cfg.Temporal()) { // extension: sampling strictly before the positive edge's time
+    const std::string who = "_sample_type 9 (khop_temporal)";
+    if (!cfg.link_prediction)
+      fatal(__FILE__, __LINE__, who + " needs task = link_prediction: a seed's time is the time of its positive edge; "
+                                "task = node_classification has no time for a node");
+    if (cfg.use_dist_graph)
+      fatal(__FILE__, __LINE__, who + " with use_dist_graph: edge times are stored by position in ONE CSR, a sharded "
+                                "topology has none");
+    if (cfg.exclude_seed_edges)
+      fatal(__FILE__, __LINE__, who + " with exclude_seed_edges = " + kv["exclude_seed_edges"] + ": strictly-before already "
+                                "removes the positive, its mirror at the same time, and everything later.");
+    if (kv.count("temporal_pick")) {
+      const std::string v = kv["temporal_pick"];
+      if (v != "uniform" && v != "recent")
+        fatal(__FILE__, __LINE__, "temporal_pick = " + v + ": uniform (the default) or recent");
+      cfg.temporal_pick = v == "recent" ? GGMS_PICK_RECENT : GGMS_PICK_UNIFORM;
+    }
+  }
   if (kv.count("edge_ids") || kv.count("edge_feat")) { // extension: CSR positions (and edge-table rows) of the sampled edges
     for (const char *key : {"edge_ids", "edge_feat"})
       if (kv.count(key) && kv[key] != "on" && kv[key] != "off")
@@ -340,6 +363,7 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
     cfg.edge_feat = kv.count("edge_feat") && kv["edge_feat"] == "on";
     cfg.edge_ids = cfg.edge_feat || (kv.count("edge_ids") && kv["edge_ids"] == "on");
   }
+  if (cfg.Temporal()) cfg.edge_ids = true; // implied: the sampler emits the positions itself
   if (cfg.edge_ids) {
     static const char *const arch_names[] = {"arch0", "arch1", "arch2", "arch3", "arch4", "arch5", "arch6", "arch7"};
     const std::string key = cfg.edge_feat ? "edge_feat" : "edge_ids";
@@ -571,6 +595,24 @@ void Engine::LoadDataset() {
       fatal(__FILE__, __LINE__, "edge_feat: edge_feat.bin has " + std::to_string((size_t)st.st_size) + " bytes, NUM_EDGE x "
                                     "EDGE_FEAT_DIM x the element size is " + std::to_string(want));
     ds.edge_feat = MapFile("edge_feat.bin", want, false);
+  }
+  if (cfg.Temporal()) { // the edge times: NUM_EDGE uint32 in CSR order, sorted inside every list
+    const std::string name = cfg.dataset_path + "edge_time.bin";
+    struct stat st;
+    if (stat(name.c_str(), &st) != 0)
+      fatal(__FILE__, __LINE__, "khop_temporal: " + name + " is missing (NUM_EDGE uint32 times, one per position of "
+                                    "indices.bin; datagen.write_dataset(edge_time=...))");
+    if ((size_t)st.st_size != ds.num_edge * 4)
+      fatal(__FILE__, __LINE__, "khop_temporal: edge_time.bin has " + std::to_string((size_t)st.st_size) + " bytes, NUM_EDGE x 4 is " +
+                                    std::to_string(ds.num_edge * 4));
+    ds.edge_time = MapFile("edge_time.bin", ds.num_edge * 4, false);
+    const uint32_t *ip = (const uint32_t *)ds.indptr.ptr, *t = (const uint32_t *)ds.edge_time.ptr;
+    for (size_t v = 0; v < ds.num_node; ++v)
+      for (size_t p = (size_t)ip[v] + 1; p < ip[v + 1]; ++p)
+        if (t[p] < t[p - 1])
+          fatal(__FILE__, __LINE__, "khop_temporal: edge_time.bin: the times of node " + std::to_string(v) + "'s list are not "
+                                        "non-decreasing (position " + std::to_string(p) + "); datagen.sort_lists_by_time "
+                                        "re-sorts a graph");
   }
   if (cfg.sample_type == GGMS_WEIGHTED_KHOP || cfg.sample_type == GGMS_WEIGHTED_KHOP_HASH_DEDUP) { // engine.cc:372-384
     ds.prob_table = MapFile("prob_table.bin", ds.num_edge * 4, false);
@@ -1046,7 +1088,7 @@ void Engine::SampleInit(int worker_id, const std::string &ctx) {
   extra_.random_walk_restart_prob = cfg.random_walk_restart_prob;
   extra_.num_random_walk = cfg.num_random_walk;
   // GPURandomStates dist_engine.cc:432-433; seed = wall clock unless the "seed" key is given
-  if (cfg.sample_type == GGMS_KHOP_LABOR) { // stateless: its variates are hashes of (node id, salt) -- no RNG pool
+  if (cfg.sample_type == GGMS_KHOP_LABOR || cfg.Temporal()) { // stateless: their variates are hashes of (node id, salt) -- no RNG pool
     num_states_ = 0;
     states_ = nullptr;
   } else {
@@ -1090,7 +1132,13 @@ void Engine::SampleInit(int worker_id, const std::string &ctx) {
     SAM_CHECK(drop_ws_bytes_ > 0, "exclude_seed_edges: the batch bounds are out of ggms_drop_pair_edges' range");
     for (Pipe &P : pipes_) SAM_HIP(hipMalloc(&P.drop_ws, drop_ws_bytes_));
   }
-  if (cfg.edge_ids) { // the long-list queue of ggms_edge_positions, one per pipeline
+  if (cfg.Temporal()) { // one cut table per pipeline: 8 B x num_node, zeroed once; stamps 1, 2, 3, ... per batch
+    for (Pipe &P : pipes_) {
+      SAM_HIP(hipMalloc((void **)&P.cut_table, std::max<size_t>(ds.num_node, 1) * 8));
+      SAM_HIP(hipMemsetAsync(P.cut_table, 0, std::max<size_t>(ds.num_node, 1) * 8, stream_));
+    }
+  }
+  if (cfg.edge_ids && !cfg.Temporal()) { // the long-list queue of ggms_edge_positions, one per pipeline
     eid_ws_bytes_ = ggms_edge_positions_workspace_bytes(max_edges_.data(), L);
     SAM_CHECK(eid_ws_bytes_ > 0, "edge_ids: the batch bounds are out of ggms_edge_positions' range");
     for (Pipe &P : pipes_) SAM_HIP(hipMalloc(&P.eid_ws, eid_ws_bytes_));
@@ -1305,6 +1353,7 @@ void Engine::BuildCache() {
       d_feat_ = dev_upload(feat, ds.feat.bytes, bs);
       feat_src_ = d_feat_;
       if (cfg.edge_feat) d_edge_feat_ = dev_upload(ds.edge_feat.ptr, ds.edge_feat.bytes, bs); // the edge table, beside it
+      if (cfg.Temporal()) d_edge_time_ = (uint32_t *)dev_upload(ds.edge_time.ptr, ds.edge_time.bytes, bs); // and the times
       if (cfg.feat_learnable >= 0) { // the upload is the learnable table's initial value; Adagrad's accumulator starts at 0
         if (cfg.feat_learnable == GGMS_UPDATE_ADAGRAD) {
           SAM_HIP(hipMalloc(&d_feat_state_, std::max<size_t>(ds.feat.bytes, 16)));
@@ -1494,6 +1543,12 @@ void Engine::TrainInit(int worker_id, const std::string &ctx) {
         if (cfg.edge_feat) SAM_HIP(hipMalloc(&b->efeat[i], std::max<size_t>(max_edges_[i] * ds.edge_feat_row_bytes(), 16)));
       }
     }
+    if (cfg.Temporal()) {
+      SAM_HIP(hipMalloc((void **)&b->seed_time, std::max<size_t>(max_seeds_, 4) * 4));
+      SAM_HIP(hipMalloc((void **)&b->node_cut, std::max<size_t>(max_unique_, 4) * 4));
+      b->etime.assign(L, nullptr);
+      for (uint32_t i = 0; i < L; ++i) SAM_HIP(hipMalloc((void **)&b->etime[i], std::max<size_t>(max_edges_[i], 4) * 4));
+    }
     if (StagedHostTier()) { // index arrays of GetMissCacheIndex + pinned / device staging of the miss rows
       if (cache_table_) { // (no cache: no split, and the rows land in the batch's feature buffer directly)
         for (uint32_t **p : {&b->miss_src, &b->miss_dst, &b->hit_src, &b->hit_dst}) SAM_HIP(hipMalloc((void **)p, max_unique_ * 4));
@@ -1656,8 +1711,12 @@ void Engine::SampleInto(Batch *b, Pipe &P) {
     SAM_GGMS(ggms_link_seeds(&graph_, b->edge_ids, b->num_pos, cfg.num_negative, cfg.negative_mode, salt, s.output_nodes,
                              forced, P.stream));
     extra.seeds_distinct = 0;
+    // khop_temporal: every entry of the seed list is sampled before the time of its positive edge
+    if (cfg.Temporal())
+      SAM_GGMS(ggms_link_seed_times(d_edge_time_, ds.num_edge, b->edge_ids, b->num_pos, cfg.num_negative, b->seed_time,
+                                    P.stream));
   }
-  if (pipes_.size() > 1 && cfg.sample_type != GGMS_KHOP0 && cfg.sample_type != GGMS_KHOP_LABOR) {
+  if (pipes_.size() > 1 && cfg.sample_type != GGMS_KHOP0 && cfg.sample_type != GGMS_KHOP_LABOR && !cfg.Temporal()) {
     extra.rng_wait = last_rng_done_;
     extra.rng_done = P.rng_done;
     last_rng_done_ = P.rng_done;
@@ -1672,7 +1731,18 @@ void Engine::SampleInto(Batch *b, Pipe &P) {
                                         states_, num_states_, s.row.data(), s.col.data(), s.counts_dev, &extra,
                                         max_prefetch_edges_, (ggms_event_t)b->ev_expand, (ggms_event_t)b->ev_final, P.ws,
                                         ws_bytes_, P.stream));
-  else
+  else if (cfg.Temporal()) {
+    // the pipeline's own cut table and stamp counter; a wrapped stamp zeroes the table on the pipeline's stream, in
+    // front of the batch that starts again from 1.  The sampler fills the batch's eid buffers itself.
+    if (P.stamp == 0xffffffffu) {
+      SAM_HIP(hipMemsetAsync(P.cut_table, 0, std::max<size_t>(ds.num_node, 1) * 8, P.stream));
+      P.stamp = 0;
+    }
+    const ggms_temporal_t t{d_edge_time_, P.cut_table, ++P.stamp, (uint32_t)cfg.temporal_pick};
+    SAM_GGMS(ggms_sample_batch_temporal(&graph_, s.output_nodes, b->seed_time, b->num_seeds, cfg.fanout.data(), L, &ht,
+                                        s.row.data(), s.col.data(), b->eid.data(), b->node_cut, s.counts_dev, &t, &extra, P.ws,
+                                        ws_bytes_, P.stream));
+  } else
     SAM_GGMS(ggms_sample_batch(cfg.sample_type, &graph_, s.output_nodes, b->num_seeds, cfg.fanout.data(), L, &ht, states_,
                                num_states_, s.row.data(), s.col.data(), s.counts_dev, &extra, P.ws, ws_bytes_, P.stream));
   P.ht.version = ht.version; // the batch bumped the table's version stamp
@@ -1692,7 +1762,7 @@ void Engine::SampleInto(Batch *b, Pipe &P) {
       SAM_HIP(hipMemcpyAsync(b->excluded, b->excluded_dev, L * 8, hipMemcpyDeviceToHost, P.stream));
     }
   }
-  if (cfg.edge_ids) {
+  if (cfg.edge_ids && !cfg.Temporal()) {
     // Which edge of the graph every sampled edge is: a post-pass over the finished layers (behind the filter: the ids of
     // the edges that are left), with the batch's own input nodes as the local -> global map.  Same stream, no new one
     // (EnqueueGather's note on the four hardware queues), in front of ev_sampled like everything that writes the batch.
@@ -1756,6 +1826,11 @@ void Engine::EnqueueGather(Batch *b, hipStream_t ss) {
     for (uint32_t i = 0; i < L; ++i)
       SAM_GGMS(ggms_gather_scatter(b->efeat[i], d_edge_feat_, b->eid[i], nullptr, max_edges_[i],
                                    b->trainer.counts_dev + GGMS_COUNT_EDGES(i), ds.edge_feat_dim, ds.edge_feat_dtype, xs));
+  // khop_temporal: the sampled edges' times, edge_time[eid], beside the edge rows (dim 1, the device edge count)
+  if (cfg.Temporal())
+    for (uint32_t i = 0; i < L; ++i)
+      SAM_GGMS(ggms_gather_scatter(b->etime[i], d_edge_time_, b->eid[i], nullptr, max_edges_[i],
+                                   b->trainer.counts_dev + GGMS_COUNT_EDGES(i), 1, GGMS_I32, xs));
   if (b->lean) SAM_GGMS(ggms_launch_timer_arm(b->gather_timer));
   else SAM_HIP(hipEventRecord(b->ev_xstart, xs)); // the extract's own start: behind the previous batch's extract on xs
   // the rows are delivered in the batch's dtype (config key feat_out_dtype; the table's own without the key, which is

@@ -113,6 +113,11 @@ struct RunConfig {
   // batch comes with its edges' CSR positions (ggms_edge_positions behind the sampler), and with edge_feat -- which
   // implies edge_ids -- with the rows of edge_feat.bin those positions name
   bool edge_ids = false, edge_feat = false;
+  // extension (`_sample_type` 9 = khop_temporal, config key `temporal_pick` = uniform | recent; arch1, link_prediction,
+  // one CSR): every seed is sampled strictly before the time of its positive edge (ggms_sample_batch_temporal).  Implies
+  // edge_ids -- the sampler itself emits the positions, ggms_edge_positions is not enqueued
+  int temporal_pick = GGMS_PICK_UNIFORM;
+  bool Temporal() const { return sample_type == GGMS_KHOP_TEMPORAL; }
   size_t staged_serial_epochs = 0; // host-staged path: the first N epochs run the reference's serial, per-phase-timed sequence
   size_t staged_serial_steps = 0;  // ... or this worker's first N batches
   // worker 0 ranks the nodes at init: pre_sample (sampled input nodes) or presample_static (L-hop closures)
@@ -152,6 +157,8 @@ struct Dataset {
   size_t edge_feat_dim = 0;
   int edge_feat_dtype = GGMS_F32;
   HostArray edge_feat;
+  // khop_temporal: edge_time.bin, NUM_EDGE uint32 in CSR order, non-decreasing inside every node's list (checked at load)
+  HostArray edge_time;
   size_t edge_feat_row_bytes() const { return edge_feat_dim * ggms_dtype_bytes(edge_feat_dtype); }
 };
 
@@ -224,6 +231,10 @@ struct Batch {
   // under them.  Empty without the keys.
   std::vector<uint32_t *> eid;
   std::vector<void *> efeat;
+  // khop_temporal: the seed list's times (ggms_link_seed_times; the first num_pos are the positives'), the final cut of
+  // every input node, and per layer edge_time[eid].  Null / empty with every other sampler.
+  uint32_t *seed_time = nullptr, *node_cut = nullptr;
+  std::vector<uint32_t *> etime;
   uint64_t num_miss = 0;
   hipEvent_t ev_seeds = nullptr, ev_start = nullptr, ev_sampled = nullptr, ev_xstart = nullptr, ev_done = nullptr;
   // arch6 with `gpu_extract` off: the host-staged miss path (dist_loops.cc:1015-1207)
@@ -397,10 +408,13 @@ class Engine {
     void *drop_ws = nullptr; // exclude_seed_edges: ggms_drop_pair_edges' workspace, a piece of its own (the seed ids it
                              // reads lie in `ws`)
     void *eid_ws = nullptr;  // edge_ids: ggms_edge_positions' workspace
+    uint64_t *cut_table = nullptr; // khop_temporal: the pipeline's cut table (8 B x num_node, zeroed once) and the stamp of
+    uint32_t stamp = 0;            // its last batch
   };
   size_t drop_ws_bytes_ = 0;
   size_t eid_ws_bytes_ = 0;    // edge_ids: ggms_edge_positions' workspace (Pipe::eid_ws)
   void *d_edge_feat_ = nullptr; // edge_feat: the edge table in HBM
+  uint32_t *d_edge_time_ = nullptr; // khop_temporal: the edge times in HBM
   uint64_t link_excluded_ = 0; // exclude_seed_edges: edges dropped from the batches handed out so far in this epoch
   std::vector<Pipe> pipes_;
   size_t enq_count_ = 0;

@@ -173,6 +173,30 @@ void samgraph_get_graph_link_edge_ids(uint64_t key, samgraph_tensor_t *out) {
   auto *b = E.Current(key);
   fill(out, b->edge_ids, (int64_t)b->num_pos, 1, 1, GGMS_I32, E.batch_device_type(), E.trainer_device());
 }
+// _sample_type 9 (khop_temporal): the time of every edge of layer l (edge_time[edge_ids]), the final cut-off of every input
+// node, the times of the batch's positive edges -- uint32 bits in get_graph_row's dtype
+static sam::Batch *temporal_batch(uint64_t key, const char *who) {
+  auto &E = Engine::Get();
+  if (!E.cfg.Temporal()) sam::fatal(__FILE__, __LINE__, std::string(who) + " needs _sample_type 9 (khop_temporal)");
+  return E.Current(key);
+}
+void samgraph_get_graph_edge_time(uint64_t key, int l, samgraph_tensor_t *out) {
+  auto &E = Engine::Get();
+  auto *b = temporal_batch(key, "samgraph_get_graph_edge_time");
+  SAM_CHECK(l >= 0 && (size_t)l < b->etime.size(), "samgraph_get_graph_edge_time: no such layer");
+  fill(out, b->etime[l], (int64_t)b->counts[GGMS_COUNT_EDGES(l)], 1, 1, GGMS_I32, E.batch_device_type(), E.trainer_device());
+}
+void samgraph_get_graph_node_cut(uint64_t key, samgraph_tensor_t *out) {
+  auto &E = Engine::Get();
+  auto *b = temporal_batch(key, "samgraph_get_graph_node_cut");
+  fill(out, b->node_cut, (int64_t)b->counts[GGMS_COUNT_INPUT(E.cfg.fanout.size())], 1, 1, GGMS_I32, E.batch_device_type(),
+       E.trainer_device());
+}
+void samgraph_get_graph_link_time(uint64_t key, samgraph_tensor_t *out) {
+  auto &E = Engine::Get();
+  auto *b = temporal_batch(key, "samgraph_get_graph_link_time");
+  fill(out, b->seed_time, (int64_t)b->num_pos, 1, 1, GGMS_I32, E.batch_device_type(), E.trainer_device());
+}
 // config key feat_learnable: the gradient of the current batch's rows moves the table; the live table and its state
 void samgraph_update_graph_feat(uint64_t key, const void *grad, size_t num_rows, size_t dim, void *caller_stream) {
   Engine::Get().UpdateGraphFeat(key, grad, num_rows, dim, (hipStream_t)caller_stream);

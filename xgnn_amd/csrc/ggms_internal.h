@@ -84,7 +84,14 @@ struct SampleLayer {
   uint32_t *out_data = nullptr;         // random walk: visit counts
   size_t walk_length = 0, num_walk = 0;
   double restart_prob = 0;
-  uint32_t salt = 0;                    // khop_labor: the layer salt
+  uint32_t salt = 0;                    // khop_labor, khop_temporal: the layer salt
+  // khop_temporal: per-position times; the seeds' cuts (leaf) or the batch's cut table + stamp; the positions' output
+  const uint32_t *edge_time = nullptr;
+  const uint32_t *input_cut = nullptr;
+  uint64_t *cut_table = nullptr;
+  uint32_t stamp = 0;
+  int pick = 0;
+  uint32_t *out_pos = nullptr;
 };
 
 // sample_khop.hip
@@ -105,6 +112,14 @@ size_t walk_scan_tiles(size_t num_input);
 // sample_labor.hip
 size_t labor_ws_words(size_t num_input);
 int sample_khop_labor_impl(const SampleLayer &l);
+
+// sample_temporal.hip
+size_t temporal_ws_words(size_t num_input);
+int sample_khop_temporal_impl(const SampleLayer &l);
+int temporal_seed_cut_impl(const uint32_t *seeds, const uint32_t *seed_time, size_t num_seeds, uint64_t *cut_table,
+                           uint32_t stamp, hipStream_t s); // cut[seed] = min(cut[seed], seed_time), under `stamp`
+int temporal_node_cut_impl(const uint32_t *n2o, size_t n_max, Count n, const uint64_t *cut_table, uint32_t stamp,
+                           uint32_t *node_cut, hipStream_t s); // node_cut[local id] = cut[n2o[local id]]
 
 // sample_batch.hip: the per-sampler rules, one copy for the leaf entry points and ggms_sample_batch
 size_t layer_ws_words(int type, size_t n, size_t fanout, size_t walk_length, size_t num_walk);

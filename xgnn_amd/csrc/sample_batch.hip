@@ -76,6 +76,7 @@ size_t layer_ws_words(int type, size_t n, size_t fanout, size_t walk_length, siz
   case GGMS_WEIGHTED_KHOP_PREFIX: return weighted_ws_words(n, fanout);
   case GGMS_RANDOM_WALK: return random_walk_ws_words(n, walk_length, num_walk, fanout);
   case GGMS_KHOP_LABOR: return labor_ws_words(n);
+  case GGMS_KHOP_TEMPORAL: return temporal_ws_words(n);
   default: return sample_ws_words(n); // khop3, khop2, weighted_khop_hash_dedup
   }
 }
@@ -86,6 +87,7 @@ static int layer_shape_check(int type, const SampleLayer &l) {
   if (type == GGMS_KHOP3) GGMS_CHECK_ARG(l.fanout < 128);                            // khop3.cu:85
   if (type == GGMS_WEIGHTED_KHOP_HASH_DEDUP) GGMS_CHECK_ARG(l.fanout < kDedupSlots); // hash_dedup.cu:42
   if (type == GGMS_KHOP_LABOR) GGMS_CHECK_ARG(l.fanout < 128); // the hub route ranks its selection in LDS
+  if (type == GGMS_KHOP_TEMPORAL) GGMS_CHECK_ARG(l.fanout < 128); // khop_labor's selection on a prefix
   if (type == GGMS_RANDOM_WALK) GGMS_CHECK_ARG(l.walk_length > 0 && l.num_walk > 0);
   // "this algorithm not support DistGraph engine", dist_loops.cc:167-228
   if (type != GGMS_KHOP3 && type != GGMS_KHOP0 && type != GGMS_RANDOM_WALK && type != GGMS_KHOP_LABOR)
@@ -98,13 +100,16 @@ static int layer_check(int type, const SampleLayer &l, size_t num_states) {
   const int rc = layer_shape_check(type, l);
   if (rc != GGMS_OK) return rc;
   const uint64_t n = l.n_max;
-  if (type == GGMS_KHOP1 || type == GGMS_KHOP2) GGMS_CHECK_ARG(l.graph->indptr && l.graph->indices);
+  if (type == GGMS_KHOP1 || type == GGMS_KHOP2 || type == GGMS_KHOP_TEMPORAL)
+    GGMS_CHECK_ARG(l.graph->indptr && l.graph->indices);
+  if (type == GGMS_KHOP_TEMPORAL) GGMS_CHECK_ARG(l.edge_time && l.out_pos && (l.input_cut || l.cut_table));
   if (type == GGMS_WEIGHTED_KHOP || type == GGMS_WEIGHTED_KHOP_HASH_DEDUP) GGMS_CHECK_ARG(l.prob && l.alias);
   if (type == GGMS_WEIGHTED_KHOP_PREFIX) GGMS_CHECK_ARG(l.prob);
   // the RNG pool: assert(i < num_random_states) in every sampler of the reference but khop0
   switch (type) {
   case GGMS_KHOP0:
-  case GGMS_KHOP_LABOR: return GGMS_OK; // stateless
+  case GGMS_KHOP_LABOR:
+  case GGMS_KHOP_TEMPORAL: return GGMS_OK; // stateless
   case GGMS_KHOP3: GGMS_CHECK_ARG(l.states && (n + 127) / 128 * 8 <= num_states); return GGMS_OK; // khop3.cu:89
   case GGMS_KHOP2:                                                                                   // khop2.cu:57
   case GGMS_WEIGHTED_KHOP_HASH_DEDUP: // hash_dedup.cu:70
@@ -131,6 +136,7 @@ static int sample_layer(int type, const SampleLayer &l) {
   case GGMS_WEIGHTED_KHOP_HASH_DEDUP: return sample_weighted_hash_dedup_impl(l);
   case GGMS_RANDOM_WALK: return sample_random_walk_impl(l);
   case GGMS_KHOP_LABOR: return sample_khop_labor_impl(l);
+  case GGMS_KHOP_TEMPORAL: return sample_khop_temporal_impl(l);
   default: return sample_weighted_impl(l, type); // khop1, weighted_khop, weighted_khop_prefix
   }
 }
@@ -142,7 +148,10 @@ static int sample_layer(int type, const SampleLayer &l) {
 // separate insert launch of ht_fill_impl follows).  khop_labor does not either: its selection writes each edge from
 // the lane that held the key, after a search that is all ballots -- a returning atomic per edge there would serialise
 // behind the search of the seed's whole wave, and the sampler stays a pure function of its inputs.
-static bool layer_enters_output(int type) { return type != GGMS_KHOP2 && type != GGMS_KHOP_LABOR; }
+// khop_temporal is khop_labor's selection: the same holds.
+static bool layer_enters_output(int type) {
+  return type != GGMS_KHOP2 && type != GGMS_KHOP_LABOR && type != GGMS_KHOP_TEMPORAL;
+}
 
 // a leaf entry point: shape checks; nothing to sample -> a zero count (null pointers allowed); pointers, workspace and
 // RNG pool; the sampler
@@ -264,11 +273,21 @@ struct Prefetch {
   hipEvent_t start, final;
 };
 
-// the body of ggms_sample_batch and ggms_sample_batch_prefetch; every argument check is the caller's
+// ggms_sample_batch_temporal's part of a batch (NULL: any other batch)
+struct TemporalBatch {
+  const ggms_temporal_t *t;
+  const uint32_t *seed_time;
+  ggms_id_t *const *eid;
+  uint32_t *node_cut;
+};
+
+// the body of ggms_sample_batch, ggms_sample_batch_prefetch and ggms_sample_batch_temporal; every argument check is the
+// caller's
 static int sample_batch_impl(int sample_type, const ggms_graph_t *graph, const ggms_id_t *seeds, size_t num_seeds,
                              const size_t *fanouts, uint32_t num_layer, ggms_hashtable_t *ht, void *states,
                              size_t num_states, ggms_id_t *const *row, ggms_id_t *const *col, uint64_t *counts_dev,
-                             const ggms_sample_extra_t *extra, void *workspace, const Prefetch *pf, hipStream_t s) {
+                             const ggms_sample_extra_t *extra, void *workspace, const Prefetch *pf, hipStream_t s,
+                             const TemporalBatch *tb = nullptr) {
   const BatchCaps c = caps_of(num_seeds, fanouts, num_layer);
   // what every layer's sampler call shares; the loop below fills in the rest
   SampleLayer L{graph, nullptr, 0, 0, nullptr, nullptr, nullptr, (uint32_t *)states, nullptr, s};
@@ -279,7 +298,15 @@ static int sample_batch_impl(int sample_type, const ggms_graph_t *graph, const g
     L.num_walk = extra->num_random_walk;
     L.restart_prob = extra->random_walk_restart_prob;
   }
-  const bool ordered_rng = sample_type != GGMS_KHOP_LABOR; // a stateless sampler has nothing to order between batches
+  // a stateless sampler has nothing to order between batches
+  const bool ordered_rng = sample_type != GGMS_KHOP_LABOR && sample_type != GGMS_KHOP_TEMPORAL;
+  if (tb) {
+    L.edge_time = tb->t->edge_time;
+    L.cut_table = tb->t->cut_table;
+    L.stamp = tb->t->stamp;
+    L.pick = (int)tb->t->pick;
+    L.out_pos = tb->eid[0]; // layer_check's non-null test; every layer sets its own below
+  }
   for (uint32_t i = 0; i < num_layer; ++i) {
     L.n_max = c.max_input[i];
     L.fanout = fanouts[i];
@@ -369,6 +396,9 @@ static int sample_batch_impl(int sample_type, const ggms_graph_t *graph, const g
                       kRestNow, pro.record_n);
   }
   if (rc != GGMS_OK) return rc;
+  // khop_temporal: cut[seed] = min over the raw seeds' times, entered before the first layer's snapshot of the table
+  if (tb) rc = temporal_seed_cut_impl(seeds, tb->seed_time, num_seeds, L.cut_table, L.stamp, s);
+  if (rc != GGMS_OK) return rc;
   uint32_t next_base = (uint32_t)num_seeds;
 
   MapRestJobs jobs{};
@@ -435,6 +465,7 @@ static int sample_batch_impl(int sample_type, const ggms_graph_t *graph, const g
       L.first = first && fuse_seeds ? &first_layer : nullptr;
       L.enter = first && khop0_enters ? &seed_enter : nullptr;
       if (sample_type == GGMS_RANDOM_WALK) L.out_data = extra->data[i];
+      if (tb) L.out_pos = tb->eid[i];
       rc = sample_layer(sample_type, L);
     }
     if (rc != GGMS_OK) return rc;
@@ -472,6 +503,13 @@ static int sample_batch_impl(int sample_type, const ggms_graph_t *graph, const g
       job_items = std::max(job_items, e_max);
     }
   }
+  // khop_temporal: the final cut of every input node, by local id (the table keeps changing with the next batch)
+  if (tb) {
+    rc = temporal_node_cut_impl(ht->n2o, c.max_input[0] + c.max_edges[0],
+                                count_of32(c.max_input[0] + c.max_edges[0], ht->num_items_dev), L.cut_table, L.stamp,
+                                tb->node_cut, s);
+    if (rc != GGMS_OK) return rc;
+  }
   // the rest of GPUMapEdges' dst half for every layer + the batch's status word (GGMS_COUNT_STATUS)
   return launch_map_rest_all(ht, jobs, num_jobs, job_items, di.map, counts_dev + GGMS_COUNT_STATUS(num_layer), s);
 }
@@ -483,6 +521,11 @@ int ggms_sample_batch(int sample_type, const ggms_graph_t *graph, const ggms_id_
                       ggms_stream_t stream) {
   GGMS_CHECK_ARG(graph && fanouts && ht && row && col && counts_dev);
   GGMS_CHECK_ARG(num_layer >= 1 && num_layer <= 16);
+  if (sample_type == GGMS_KHOP_TEMPORAL) {
+    set_error("ggms_sample_batch: sample type %d (khop_temporal) takes edge times, seed times and a cut table: call "
+              "ggms_sample_batch_temporal", sample_type);
+    return GGMS_ERR_INVALID;
+  }
   GGMS_CHECK_ARG(sample_type >= GGMS_KHOP0 && sample_type <= GGMS_KHOP_LABOR);
   GGMS_CHECK_ARG(num_seeds == 0 || seeds);
   GGMS_CHECK_ARG(workspace && workspace_bytes >= ggms_sample_batch_workspace_bytes(sample_type, num_seeds, fanouts,
@@ -501,12 +544,44 @@ int ggms_sample_batch_seed_ids(int sample_type, size_t num_seeds, const size_t *
                                const ggms_sample_extra_t *extra, const void *workspace, const ggms_id_t **seed_ids_dev) {
   GGMS_CHECK_ARG(fanouts && workspace && seed_ids_dev);
   GGMS_CHECK_ARG(num_layer >= 1 && num_layer <= 16);
-  GGMS_CHECK_ARG(sample_type >= GGMS_KHOP0 && sample_type <= GGMS_KHOP_LABOR);
+  GGMS_CHECK_ARG(sample_type >= GGMS_KHOP0 && sample_type <= GGMS_KHOP_TEMPORAL);
   const BatchCaps c = caps_of(num_seeds, fanouts, num_layer);
   const BatchLayout lay = layout_of(sample_type, num_seeds, fanouts, num_layer, c, extra);
   const uint32_t *w = (const uint32_t *)(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
   *seed_ids_dev = w + lay.seed_local;
   return GGMS_OK;
+}
+
+// ---- khop_temporal: the batch with per-seed times and a cut table --------------------------------------------------
+size_t ggms_sample_batch_temporal_workspace_bytes(size_t num_seeds, const size_t *fanouts, uint32_t num_layer,
+                                                  const ggms_sample_extra_t *extra) {
+  return ggms_sample_batch_workspace_bytes(GGMS_KHOP_TEMPORAL, num_seeds, fanouts, num_layer, extra);
+}
+
+int ggms_sample_batch_temporal(const ggms_graph_t *graph, const ggms_id_t *seeds, const uint32_t *seed_time,
+                               size_t num_seeds, const size_t *fanouts, uint32_t num_layer, ggms_hashtable_t *ht,
+                               ggms_id_t *const *row, ggms_id_t *const *col, ggms_id_t *const *eid, uint32_t *node_cut,
+                               uint64_t *counts_dev, const ggms_temporal_t *t, const ggms_sample_extra_t *extra,
+                               void *workspace, size_t workspace_bytes, ggms_stream_t stream) {
+  GGMS_CHECK_ARG(graph && fanouts && ht && row && col && eid && node_cut && counts_dev && t);
+  GGMS_CHECK_ARG(num_layer >= 1 && num_layer <= 16);
+  GGMS_CHECK_ARG(graph->num_part == 0); // edge positions are those of one CSR
+  GGMS_CHECK_ARG(t->edge_time && t->cut_table && t->stamp != 0);
+  GGMS_CHECK_ARG(t->pick == GGMS_PICK_UNIFORM || t->pick == GGMS_PICK_RECENT);
+  GGMS_CHECK_ARG(num_seeds == 0 || (seeds && seed_time));
+  for (uint32_t i = 0; i < num_layer; ++i) GGMS_CHECK_ARG(row[i] && col[i] && eid[i]);
+  GGMS_CHECK_ARG(workspace && workspace_bytes >= ggms_sample_batch_temporal_workspace_bytes(num_seeds, fanouts,
+                                                                                            num_layer, extra));
+  const BatchCaps c = caps_of(num_seeds, fanouts, num_layer);
+  GGMS_CHECK_ARG(c.max_input[0] + c.max_edges[0] <= ht->n2o_size);
+  GGMS_CHECK_ARG(c.max_input[0] + c.max_edges[0] < (1ull << 32) - 4); // indices and 2 + local id fit 32 bits
+  // the seeds may repeat with different times: never the distinct-seeds path, whatever the caller promises
+  ggms_sample_extra_t ex{};
+  if (extra) ex = *extra;
+  ex.seeds_distinct = 0;
+  const TemporalBatch tb{t, seed_time, eid, node_cut};
+  return sample_batch_impl(GGMS_KHOP_TEMPORAL, graph, seeds, num_seeds, fanouts, num_layer, ht, nullptr, 0, row, col,
+                           counts_dev, &ex, workspace, nullptr, to_stream(stream), &tb);
 }
 
 // ---- arch4: the prefetching batch ----------------------------------------------------------------------------------

@@ -143,7 +143,7 @@ def build_prob_prefix_table(indptr, weights, num_threads=8):
 
 
 def write_dataset(path, graph, feat=None, label=None, valid_frac=0.02, test_frac=0.05, feat_dtype="F32", weights=None,
-                  minimal=False, train_edges=None, edge_feat=None, edge_feat_dtype="F32"):
+                  minimal=False, train_edges=None, edge_feat=None, edge_feat_dtype="F32", edge_time=None):
     """Write a dataset directory in the reference's on-disk format (datagen/README.md:37-51,
     samgraph/common/constant.cc:23-51, engine.cc:109-443): meta.txt (tab separated) + raw little-endian
     arrays: indptr/indices/train_set/test_set/valid_set/cache_by_* uint32, feat row-major, label int64;
@@ -155,6 +155,8 @@ def write_dataset(path, graph, feat=None, label=None, valid_frac=0.02, test_frac
     edge_feat (one row per edge, in the order of indices; a 1-d array is dim 1) adds edge_feat.bin and the meta keys
     EDGE_FEAT_DIM / EDGE_FEAT_DATA_TYPE, the table of config key `edge_feat`; edge_feat_dtype names an element type
     (FP8: as for feat), not Q8ROW.
+    edge_time (one uint32 per edge, in the order of indices, non-decreasing inside every node's list -- see
+    sort_lists_by_time) adds edge_time.bin, the times `sample_type khop_temporal` samples before.
     minimal: what a sampling + extract run needs and nothing that costs minutes at papers100M size -- one-node
     valid / test sets instead of random slices of the complement, no cache_by_random.bin."""
     import os
@@ -194,6 +196,13 @@ def write_dataset(path, graph, feat=None, label=None, valid_frac=0.02, test_frac
         edge_feat = edge_feat.reshape(edge_feat.shape[0], -1)
         assert edge_feat.shape[0] == ix.size, f"edge_feat: one row per edge ({ix.size}), not {edge_feat.shape[0]}"
         edge_feat.tofile(os.path.join(path, "edge_feat.bin"))
+    if edge_time is not None:
+        edge_time = np.ascontiguousarray(edge_time, dtype=np.uint32)
+        assert edge_time.shape == (ix.size,), f"edge_time: one time per edge ({ix.size}), not {edge_time.shape}"
+        bad = first_unsorted_list(ip, edge_time)
+        assert bad is None, (f"edge_time: the times of node {bad}'s list are not non-decreasing "
+                             "(datagen.sort_lists_by_time re-sorts a graph)")
+        edge_time.tofile(os.path.join(path, "edge_time.bin"))
     if label is not None:
         np.ascontiguousarray(label, dtype=np.int64).tofile(os.path.join(path, "label.bin"))
     if weights is not None:  # tables of the weighted samplers (engine.cc:372-384 loads them by these names)
@@ -215,6 +224,34 @@ def write_dataset(path, graph, feat=None, label=None, valid_frac=0.02, test_frac
             f.write(f"EDGE_FEAT_DIM\t{edge_feat.shape[1]}\n")
             f.write(f"EDGE_FEAT_DATA_TYPE\t{edge_feat_dtype}\n")
     return path
+
+
+def first_unsorted_list(indptr, edge_time):
+    """The first node whose list's times are not non-decreasing (khop_temporal's precondition), or None."""
+    ip = np.asarray(indptr, dtype=np.int64)
+    t = np.asarray(edge_time, dtype=np.int64)
+    if t.size < 2:
+        return None
+    drop = np.flatnonzero(t[1:] < t[:-1]) + 1  # positions whose time is below their predecessor's
+    starts = np.zeros(t.size + 1, bool)
+    starts[ip[:-1]] = True  # a list's first position has no predecessor in its list
+    drop = drop[~starts[drop]]
+    return None if drop.size == 0 else int(np.searchsorted(ip, drop[0], side="right") - 1)
+
+
+def sort_lists_by_time(indptr, indices, edge_time, *edge_arrays):
+    """A time-sorted CSR for khop_temporal: every node's list stably re-sorted by time (equal times keep their order).
+    Returns (indices, edge_time, *edge_arrays, perm), all permuted alike -- new[p] = old[perm[p]]; every other per-edge
+    array (edge_feat rows, weights) must be permuted with `perm` too, and positions kept elsewhere (train_edges) are
+    re-mapped by the caller: new position = inverse[old position], inverse[perm] = arange.
+    Times are uint32.  Float or 64-bit times are rank-transformed first (np.unique(t, return_inverse=True)[1]): only
+    their order matters to the sampler."""
+    ip = np.asarray(indptr, dtype=np.int64)
+    t = np.ascontiguousarray(edge_time, dtype=np.uint32)
+    assert t.shape == (int(ip[-1]),), "edge_time: one time per edge"
+    owner = np.repeat(np.arange(ip.size - 1), np.diff(ip))
+    perm = np.lexsort((np.arange(t.size), t, owner))  # by list, then time, then old position
+    return (np.asarray(indices)[perm], t[perm], *[np.asarray(a)[perm] for a in edge_arrays], perm)
 
 
 # FEAT_DATA_TYPE names of the OCP 8-bit float tables (include/ggms.h: GGMS_F8E4M3 = 16, GGMS_F8E5M2 = 17)

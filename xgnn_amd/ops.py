@@ -49,7 +49,9 @@ def _check_q8row(src, src_dtype, dim):
 
 KHOP0, KHOP1, WEIGHTED_KHOP, RANDOM_WALK, WEIGHTED_KHOP_PREFIX, KHOP2, WEIGHTED_KHOP_HASH_DEDUP, KHOP3 = range(8)
 KHOP_LABOR = 8  # an extension: per-node shared randomness (include/ggms.h)
-_STATELESS = (KHOP0, KHOP_LABOR)  # samplers without an RNG pool
+KHOP_TEMPORAL = 9  # an extension: sampling strictly before a per-seed cut-off time (include/ggms.h)
+PICK_UNIFORM, PICK_RECENT = 0, 1  # khop_temporal's picks
+_STATELESS = (KHOP0, KHOP_LABOR, KHOP_TEMPORAL)  # samplers without an RNG pool
 
 
 def _require_gpu(t):
@@ -156,6 +158,37 @@ def sample_khop0(graph, inp, fanout):
 def sample_khop_labor(graph, inp, fanout, layer_salt):
     """ggms_sample_khop_labor: the min(fanout, degree) neighbours with the smallest fmix32(id ^ layer_salt), per seed."""
     return _sample("ggms_sample_khop_labor", KHOP_LABOR, graph, inp, fanout, None, salt=layer_salt)
+
+
+def sample_khop_temporal(graph, edge_time, inp, inp_cut, fanout, layer_salt, pick=PICK_UNIFORM):
+    """ggms_sample_khop_temporal: per seed, among the list entries with edge_time < inp_cut[i] (a prefix of the
+    time-sorted list), khop_labor's selection (PICK_UNIFORM) or the last min(fanout, e) of them (PICK_RECENT).
+    Returns (out_src, out_dst, out_pos, num_out[1] on device); out_pos = the edges' positions in graph.indices."""
+    _require_gpu(inp)
+    _i32(inp), _i32(inp_cut), _i32(edge_time)
+    n = inp.numel()
+    assert inp_cut.numel() == n
+    dev = inp.device
+    out = [torch.empty(max(1, n * fanout), dtype=torch.int32, device=dev) for _ in range(3)]
+    num_out = torch.zeros(1, dtype=torch.int64, device=dev)
+    ws = _workspace(lib().ggms_sample_workspace_bytes(KHOP_TEMPORAL, n, fanout), dev)
+    check(lib().ggms_sample_khop_temporal(C.byref(graph.c), _ptr(edge_time), _ptr(inp), _ptr(inp_cut), n, fanout, pick,
+                                          layer_salt & 0xFFFFFFFF, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
+                                          _ptr(num_out), _ptr(ws), ws.numel() * 4, _stream()),
+          "ggms_sample_khop_temporal")
+    return out[0], out[1], out[2], num_out
+
+
+def link_seed_times(edge_time, edge_ids, num_negative):
+    """ggms_link_seed_times: edge_time[edge_ids[i]] for the source, the destination and every negative of positive i,
+    in ggms_link_seeds' endpoint layout (an id past edge_time's end: 0)."""
+    _require_gpu(edge_ids)
+    _i32(edge_ids), _i32(edge_time)
+    n = edge_ids.numel()
+    out = torch.empty(max(1, n * (2 + max(0, num_negative))), dtype=torch.int32, device=edge_ids.device)
+    check(lib().ggms_link_seed_times(_ptr(edge_time), edge_time.numel(), _ptr(edge_ids), n, num_negative, _ptr(out),
+                                     _stream()), "ggms_link_seed_times")
+    return out[: n * (2 + num_negative)]
 
 
 NEG_UNIFORM, NEG_EXCLUDE = 0, 1  # ggms_link_seeds modes
@@ -1026,6 +1059,65 @@ class PrefetchBatchSampler(_BatchBuffers):
         c, layers = self._sliced("ggms_sample_batch_prefetch", lambda c: f" (expansion needed {c[needed]} edges, "
                                                                          f"capacity {self.max_prefetch_edges})")
         return dict(layers=layers, input_nodes=self.ht.n2o[: c[COUNT_INPUT(self.L)]], expansion_edges=c[needed])
+
+
+class TemporalBatchSampler(_BatchBuffers):
+    """ggms_sample_batch_temporal: BatchSampler's layers with khop_temporal as the sampler.  One slot, one pipeline, one
+    cut table (8 bytes per node, zeroed here) whose stamp goes up by one per batch."""
+
+    def __init__(self, graph, edge_time, fanouts, batch_size, pick=PICK_UNIFORM, device="cuda", direct_table=True,
+                 max_seeds=None):
+        self._init_capacity(graph, fanouts, KHOP_TEMPORAL, int(batch_size * 1.25) + 1 if max_seeds is None else int(max_seeds),
+                            None, None)
+        _require_gpu(_i32(edge_time))
+        self.edge_time, self.pick = edge_time, pick
+        self.ht = OrderedHashTable(self.max_unique, device, num_node=graph.c.num_node if direct_table else None)
+        self.states = None
+        (self.row, self._rows), (self.col, self._cols) = self._layer_buffers(1, device), self._layer_buffers(1, device)
+        self.eid, self._eids = self._layer_buffers(1, device)
+        self.node_cut = torch.empty(max(1, self.max_unique), dtype=torch.int32, device=device)
+        self.counts = torch.zeros(COUNTS_SAMPLE_WORDS(self.L), dtype=torch.int64, device=device)
+        self.cut_table = torch.zeros(max(1, graph.c.num_node), dtype=torch.int64, device=device)
+        self.stamp = 0
+        wsb = lib().ggms_sample_batch_temporal_workspace_bytes(self.max_seeds, self._f, self.L, C.byref(self._extra))
+        self.ws = _workspace(wsb, device)
+        self._n = 0
+
+    def sample(self, seeds, seed_time, salt=0, stamp=None):
+        """Enqueue one batch: seeds[j] is sampled strictly before min(seed_time over the occurrences of that node).
+        stamp: the batch's stamp on the cut table (default: the last one + 1; after 0xffffffff the table is zeroed)."""
+        _i32(seeds), _i32(seed_time)
+        n = self._n = seeds.numel()
+        assert n <= self.max_seeds and seed_time.numel() == n
+        if stamp is None:
+            if self.stamp == 0xFFFFFFFF:
+                self.cut_table.zero_()
+                self.stamp = 0
+            stamp = self.stamp + 1
+        self.stamp = stamp
+        t = _lib.Temporal(self.edge_time.data_ptr(), self.cut_table.data_ptr(), stamp, self.pick)
+        self._extra.labor_salt = salt & 0xFFFFFFFF
+        check(lib().ggms_sample_batch_temporal(C.byref(self.graph.c), _ptr(seeds), _ptr(seed_time), n, self._f, self.L,
+                                               C.byref(self.ht.c), self._rows, self._cols, self._eids,
+                                               _ptr(self.node_cut), _ptr(self.counts), C.byref(t), C.byref(self._extra),
+                                               _ptr(self.ws), self.ws.numel() * 4, _stream()),
+              "ggms_sample_batch_temporal")
+
+    def seed_ids(self):
+        """Local ids of the raw seeds of the last batch (ggms_sample_batch_seed_ids)."""
+        p = C.c_void_p()
+        check(lib().ggms_sample_batch_seed_ids(KHOP_TEMPORAL, self._n, self._f, self.L, C.byref(self._extra),
+                                               _ptr(self.ws), C.byref(p)), "ggms_sample_batch_seed_ids")
+        off = (p.value - self.ws.data_ptr()) // 4
+        return self.ws[off: off + self._n]
+
+    def result(self):
+        """Sync and slice the outputs: BatchSampler.result()'s, each layer with its `eid`, and `node_cut`."""
+        c, layers = self._sliced("ggms_sample_batch_temporal")
+        for i, lay in enumerate(layers):
+            lay["eid"] = self.eid[i][:c[COUNT_EDGES(i)]]
+        n_in = c[COUNT_INPUT(self.L)]
+        return dict(layers=layers, input_nodes=self.ht.n2o[:n_in], node_cut=self.node_cut[:n_in])
 
 
 def dynamic_cache_reset(stamps):

@@ -128,6 +128,23 @@ def get_graph_edge_feat(batch_key, layer_idx):
     return _get("samgraph_get_graph_edge_feat", batch_key, layer_idx)
 
 
+def get_graph_edge_time(batch_key, layer_idx):
+    """sample_type khop_temporal: the time of every edge of the layer, edge_time[get_graph_edge_ids] (int32 holding the
+    uint32 bits)."""
+    return _get("samgraph_get_graph_edge_time", batch_key, layer_idx)
+
+
+def get_graph_node_cut(batch_key):
+    """sample_type khop_temporal: the cut-off time of every input node -- the smallest time among the positives it
+    serves; node_cut[col] - edge_time is an edge's age for a time encoding (int32 holding the uint32 bits)."""
+    return _get("samgraph_get_graph_node_cut", batch_key)
+
+
+def get_graph_link_time(batch_key):
+    """sample_type khop_temporal: the times of the batch's positive edges, in the order of get_graph_link_edge_ids."""
+    return _get("samgraph_get_graph_link_time", batch_key)
+
+
 def get_graph_link_edge_ids(batch_key):
     """The positive edge ids (CSR positions) of a link_prediction batch, in the order of get_graph_link_pairs."""
     return _get("samgraph_get_graph_link_edge_ids", batch_key)
