@@ -201,7 +201,8 @@ enum ggms_sample_type {
   GGMS_WEIGHTED_KHOP_HASH_DEDUP = 6,
   GGMS_KHOP3 = 7,
   GGMS_KHOP_LABOR = 8, /* an extension: ggms_sample_khop_labor below */
-  GGMS_KHOP_TEMPORAL = 9 /* an extension: ggms_sample_khop_temporal / ggms_sample_batch_temporal below */
+  GGMS_KHOP_TEMPORAL = 9, /* an extension: ggms_sample_khop_temporal / ggms_sample_batch_temporal below */
+  GGMS_KHOP_TYPED = 10 /* an extension: ggms_sample_khop_typed / ggms_sample_batch_typed below */
 };
 
 /* Workspace of every leaf sampler below but random walk, whose size depends on
@@ -272,6 +273,41 @@ int ggms_sample_khop_temporal(const ggms_graph_t *graph, const uint32_t *edge_ti
                               const uint32_t *input_cut, size_t num_input, size_t fanout, int pick,
                               uint32_t layer_salt, ggms_id_t *out_src, ggms_id_t *out_dst, ggms_id_t *out_pos,
                               uint64_t *num_out_dev, void *workspace, size_t workspace_bytes, ggms_stream_t stream);
+
+/* khop_typed (an extension; the reference has no such sampler; DGL: sample_etype_neighbors(etype_sorted=True), PyG:
+ * NeighborLoader(num_neighbors={edge_type: [...]})): a fanout per EDGE TYPE, so a rare relation is sampled next to a
+ * common one.
+ *   edge_type   one uint8 per position of graph->indices, every value < num_type = R, 1 <= R <= GGMS_MAX_EDGE_TYPES.
+ *               PRECONDITION: inside every node's list the types are non-decreasing (a type-sorted CSR), so the edges of
+ *               type r of a node are one contiguous segment of its list.
+ *   segments    seed i is node s = input[i]; its list is the positions [indptr[s], indptr[s + 1]), d of them.
+ *               b_r = the number of entries of the list with type < r, r = 0 .. R (b_0 = 0; b_R counts the entries with
+ *               type < R).  Segment r is the list positions [b_r, b_{r+1}), e_r of them.
+ *   fanouts     type_fanout[r] = k_r in 0 .. 127, a HOST array of R; 0: the relation is not sampled.  K = their sum >= 1.
+ *   selected    from segment r, khop_labor's rule on the segment: the min(k_r, e_r) positions p of [b_r, b_{r+1}) with the
+ *               smallest keys (fmix32(t_p ^ layer_salt) << 32) | p; all of them if e_r <= k_r.  The salt is THE SAME FOR
+ *               EVERY TYPE: the variate belongs to the node, not to the relation -- a node picked under two relations is
+ *               one row of the batch, so khop_labor's sharing extends across relations.
+ *   output      seeds in input order; inside a seed ascending position, hence ascending type.  out_src / out_dst as
+ *               khop_labor writes them; out_pos[k] = indptr[s] + p, the edge's position in graph->indices (parallel edges
+ *               of different relations have their own); out_type[k] = r.  All four hold num_input * K entries.  Duplicate
+ *               seeds get the same edges.  With R = 1 the edges are exactly khop_labor's with fanout k_0.
+ *   unsorted    a list that violates the precondition: WHICH edges come out is unspecified.  The boundaries are made
+ *               monotone (b_{r+1} = max(b_{r+1}, b_r)) before anything is counted; nothing is read or written out of
+ *               bounds, every emitted position lies in the seed's list, no seed emits more than K edges.
+ *   arguments   refused with GGMS_ERR_INVALID before any device call: a sharded graph (positions are those of ONE CSR),
+ *               R outside 1 .. GGMS_MAX_EDGE_TYPES, a k_r >= 128, K = 0, a null array, a short workspace.
+ * Stateless: a pure function of (graph, edge_type, type_fanout, input, layer_salt).  No allocation, no synchronisation,
+ * every size stays on the device.  Workspace: the boundaries take R words per seed, which the generic sizing function
+ * cannot know: ggms_sample_workspace_bytes(GGMS_KHOP_TYPED, num_input, K) is sized for R = GGMS_MAX_EDGE_TYPES and
+ * serves every R; ggms_sample_khop_typed_workspace_bytes(num_input, R) is what the call needs for its R. */
+#define GGMS_MAX_EDGE_TYPES 32
+size_t ggms_sample_khop_typed_workspace_bytes(size_t num_input, uint32_t num_type);
+int ggms_sample_khop_typed(const ggms_graph_t *graph, const uint8_t *edge_type, uint32_t num_type,
+                           const uint32_t *type_fanout /* host, num_type */, const ggms_id_t *input, size_t num_input,
+                           uint32_t layer_salt, ggms_id_t *out_src, ggms_id_t *out_dst, ggms_id_t *out_pos,
+                           uint8_t *out_type, uint64_t *num_out_dev, void *workspace, size_t workspace_bytes,
+                           ggms_stream_t stream);
 
 /* GPUSampleWeightedKHopPrefix, cuda/cuda_sampling_weighted_khop_prefix.cu:145-246:
  * prob_prefix_table = per-list inclusive prefix sums of the edge weights; one
@@ -572,6 +608,33 @@ int ggms_sample_batch_temporal(const ggms_graph_t *graph, const ggms_id_t *seeds
 int ggms_link_seed_times(const uint32_t *edge_time, uint64_t num_edge, const ggms_id_t *edge_ids, size_t num_pos,
                          uint32_t num_negative, uint32_t *out_time /* num_pos * (2 + num_negative) */,
                          ggms_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * The typed batch (an extension): ggms_sample_batch's layers with khop_typed as the sampler -- R-GCN-style models and
+ * typed link prediction want a fanout per relation and need to know which relation a sampled edge belongs to.
+ *   t->type_fanout  HOST, num_layer x num_type, row i = the k_r of layer i (indexed by layer id like `fanouts`).
+ *               fanouts[i] must equal row i's sum (checked); capacities and workspace arithmetic are
+ *               ggms_sample_batch_capacity's with those sums.
+ *   layer i     ggms_sample_khop_typed's rule with row i and layer_salt = fmix32(labor_salt + 0x9e3779b9 * (i + 1)).
+ *   eid, etype  HOST arrays of L device pointers, capacities max_edges[i]: eid[i][k] = the CSR position of edge k of
+ *               layer i, etype[i][k] = its type = edge_type[eid[i][k]] (the table fills never reorder edges).
+ *   counts_dev, row, col, both table layouts, the numbering: ggms_sample_batch's.  extra->labor_salt is the batch salt
+ *   (NULL: 0); rng_wait / rng_done are ignored (stateless).  ggms_sample_batch_seed_ids(GGMS_KHOP_TYPED, ...) gives the
+ *   raw seeds' local ids.  ggms_sample_batch(GGMS_KHOP_TYPED, ...) is GGMS_ERR_INVALID and names this call.
+ *   With num_type = 1 the batch equals ggms_sample_batch(GGMS_KHOP_LABOR, ...) with the same fanouts and salt.
+ * ------------------------------------------------------------------------- */
+typedef struct {
+  const uint8_t *edge_type;    /* device, one per CSR position */
+  uint32_t num_type;           /* R, 1 .. GGMS_MAX_EDGE_TYPES */
+  const uint32_t *type_fanout; /* HOST, num_layer x num_type, layer-major */
+} ggms_typed_t;
+size_t ggms_sample_batch_typed_workspace_bytes(size_t num_seeds, const size_t *fanouts, uint32_t num_layer,
+                                               uint32_t num_type, const ggms_sample_extra_t *extra);
+int ggms_sample_batch_typed(const ggms_graph_t *graph, const ggms_id_t *seeds, size_t num_seeds, const size_t *fanouts,
+                            uint32_t num_layer, ggms_hashtable_t *ht, ggms_id_t *const *row, ggms_id_t *const *col,
+                            ggms_id_t *const *eid, uint8_t *const *etype, uint64_t *counts_dev, const ggms_typed_t *t,
+                            const ggms_sample_extra_t *extra, void *workspace, size_t workspace_bytes,
+                            ggms_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Link-prediction seeds (an extension; the reference has no such operator): a batch of positive EDGE ids becomes the

@@ -170,6 +170,18 @@ void samgraph_get_graph_link_edge_ids(uint64_t key, samgraph_tensor_t *out);
 void samgraph_get_graph_edge_time(uint64_t key, int layer_idx, samgraph_tensor_t *out);
 void samgraph_get_graph_node_cut(uint64_t key, samgraph_tensor_t *out);
 void samgraph_get_graph_link_time(uint64_t key, samgraph_tensor_t *out);
+/* Extension for _sample_type 10 (khop_typed; config key type_fanout = num_layer x NUM_EDGE_TYPE integers, layer-major, each
+ * 0 .. 127, no all-zero row; `fanout` must hold the rows' sums -- the Python front-end fills it in from a list of lists).
+ * arch1 with one CSR, task = node_classification or link_prediction, 1 or 2 pipelines; every other deployment,
+ * use_dist_graph and exclude_seed_edges other than none are refused by name.  The dataset carries edge_type.bin
+ * (NUM_EDGE uint8, one per position of indices.bin, non-decreasing inside every node's list) and the meta key
+ * NUM_EDGE_TYPE (1 .. 32); size, order and range are checked at init, fatal with the node.  Every layer samples
+ * min(k_r, e_r) edges of every relation r per node (ggms_sample_batch_typed, include/ggms.h).  edge_ids is implied: the
+ * sampler emits the positions itself -- parallel edges of different relations carry their OWN position -- and edge_feat
+ * gathers under them.
+ *   samgraph_get_graph_edge_type(key, layer)   num_edge(layer) types (uint8), edge_type[edge_ids[k]]
+ * Fatal with every other sample type. */
+void samgraph_get_graph_edge_type(uint64_t key, int layer_idx, samgraph_tensor_t *out);
 /* a batch's buffers stay valid while its retain count is > 0 */
 void samgraph_batch_retain(uint64_t key);
 void samgraph_batch_release(uint64_t key);

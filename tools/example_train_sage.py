@@ -7,6 +7,11 @@ index_add_.  Everything up to the model -- config keys, init, sample_once / get_
 label -- is the reference's own loop.
 
     python tools/example_train_sage.py <dataset_dir> [--epochs 2] [--batch-size 1024] [--fanout 10 5] [--sample-type khop3]
+    python tools/example_train_sage.py <dataset_dir> --typed 6,3,1/3,1,1
+
+--typed: sample_type khop_typed on a data set with edge_type.bin -- a fanout per relation and layer (rows by layer id) --
+and a relation-wise mean (R-GCN's aggregation: one weight per relation over the mean of that relation's sampled
+neighbours) on the types sam.get_graph_edge_type hands out, in plain torch.
 """
 import argparse
 import os
@@ -34,6 +39,25 @@ class SageLayer(torch.nn.Module):
         return self.w_self(h[:num_dst]) + self.w_nbr(agg / deg.clamp(min=1).unsqueeze(1))
 
 
+class TypedSageLayer(torch.nn.Module):
+    """w_self h_v + sum_r w_r mean{h_u : u sampled for v under relation r}"""
+
+    def __init__(self, d_in, d_out, num_type):
+        super().__init__()
+        self.w_self = torch.nn.Linear(d_in, d_out)
+        self.w_rel = torch.nn.ModuleList([torch.nn.Linear(d_in, d_out, bias=False) for _ in range(num_type)])
+
+    def forward(self, h, row, col, etype, num_dst):
+        R = len(self.w_rel)
+        slot = col * R + etype  # one mean per (node, relation)
+        agg = torch.zeros((num_dst * R, h.shape[1]), dtype=h.dtype, device=h.device)
+        deg = torch.zeros(num_dst * R, dtype=h.dtype, device=h.device)
+        agg.index_add_(0, slot, h[row])
+        deg.index_add_(0, slot, torch.ones_like(slot, dtype=h.dtype))
+        mean = (agg / deg.clamp(min=1).unsqueeze(1)).view(num_dst, R, -1)
+        return self.w_self(h[:num_dst]) + sum(w(mean[:, r]) for r, w in enumerate(self.w_rel))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("dataset")
@@ -43,9 +67,15 @@ def main():
     ap.add_argument("--sample-type", default="khop3")
     ap.add_argument("--hidden", type=int, default=64)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--typed", default=None, metavar="K,K,../K,K,..",
+                    help="khop_typed: the fanouts of every relation, a row per layer id")
     args = ap.parse_args()
+    type_fanout = [[int(k) for k in row.split(",")] for row in args.typed.split("/")] if args.typed else None
+    if type_fanout:
+        args.sample_type, args.fanout = "khop_typed", [sum(row) for row in type_fanout]
     L = len(args.fanout)
-    sam.config({"dataset_path": args.dataset, "_arch": sam.builtin_archs["arch1"]["arch"],
+    typed_keys = {"type_fanout": type_fanout} if type_fanout else {}
+    sam.config({**typed_keys, "dataset_path": args.dataset, "_arch": sam.builtin_archs["arch1"]["arch"],
                 "_sample_type": sam.sample_types[args.sample_type], "batch_size": args.batch_size,
                 "num_epoch": args.epochs, "_cache_policy": sam.cache_policies["degree"], "cache_percentage": 0.0,
                 "max_sampling_jobs": 10, "max_copying_jobs": 1, "omp_thread_num": 4, "num_layer": L,
@@ -55,7 +85,10 @@ def main():
     dev = torch.device("cuda", 0)
     torch.manual_seed(args.seed)
     dims = [sam.feat_dim()] + [args.hidden] * (L - 1) + [sam.num_class()]
-    layers = torch.nn.ModuleList([SageLayer(dims[i], dims[i + 1]) for i in range(L)]).to(dev)
+    if type_fanout:
+        layers = torch.nn.ModuleList([TypedSageLayer(dims[i], dims[i + 1], len(type_fanout[0])) for i in range(L)]).to(dev)
+    else:
+        layers = torch.nn.ModuleList([SageLayer(dims[i], dims[i + 1]) for i in range(L)]).to(dev)
     opt = torch.optim.Adam(layers.parameters(), lr=0.003)
     steps = sam.steps_per_epoch()
     for epoch in range(args.epochs):
@@ -69,7 +102,10 @@ def main():
             for i in range(L):
                 row, col, num_src, num_dst = coo[i]
                 assert h.shape[0] == num_src
-                h = layers[i](h, row.long(), col.long(), num_dst)
+                if type_fanout:
+                    h = layers[i](h, row.long(), col.long(), sam.get_graph_edge_type(key, i).long(), num_dst)
+                else:
+                    h = layers[i](h, row.long(), col.long(), num_dst)
                 if i + 1 < L:
                     h = torch.relu(h)
             loss = torch.nn.functional.cross_entropy(h, label)

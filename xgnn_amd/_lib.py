@@ -32,6 +32,11 @@ class Temporal(C.Structure):
     _fields_ = [("edge_time", C.c_void_p), ("cut_table", C.c_void_p), ("stamp", C.c_uint32), ("pick", C.c_uint32)]
 
 
+class Typed(C.Structure):
+    """ggms_typed_t"""
+    _fields_ = [("edge_type", C.c_void_p), ("num_type", C.c_uint32), ("type_fanout", C.POINTER(C.c_uint32))]
+
+
 class FeatureTiers(C.Structure):
     """ggms_feature_tiers_t"""
     _fields_ = [("table", C.c_void_p), ("replica", C.c_void_p), ("num_replica", C.c_uint64),
@@ -149,6 +154,13 @@ SYMBOLS = {
                                         C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, C.POINTER(Temporal),
                                         C.POINTER(SampleExtra), _vp, _sz, _vp]),
     "ggms_link_seed_times": (_i, [_vp, _u64, _vp, _sz, _u32, _vp, _vp]),
+    "ggms_sample_khop_typed_workspace_bytes": (_sz, [_sz, _u32]),
+    "ggms_sample_khop_typed": (_i, [C.POINTER(Graph), _vp, _u32, C.POINTER(C.c_uint32), _vp, _sz, C.c_uint32, _vp, _vp,
+                                    _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ggms_sample_batch_typed_workspace_bytes": (_sz, [_sz, C.POINTER(_sz), _u32, _u32, C.POINTER(SampleExtra)]),
+    "ggms_sample_batch_typed": (_i, [C.POINTER(Graph), _vp, _sz, C.POINTER(_sz), _u32, C.POINTER(HashTable),
+                                     C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp,
+                                     C.POINTER(Typed), C.POINTER(SampleExtra), _vp, _sz, _vp]),
     "ggms_link_seeds": (_i, [C.POINTER(Graph), _vp, _sz, _u32, _i, _u32, _vp, _vp, _vp]),
     "ggms_drop_pair_edges_workspace_bytes": (_sz, [_sz, C.POINTER(_sz), _u32]),
     "ggms_drop_pair_edges": (_i, [_vp, _vp, _sz, _u32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz), _u32, _vp, _vp,

@@ -12,6 +12,7 @@ kCPU, kMMAP, kGPU = 0, 1, 2
 kKHop0, kKHop1, kWeightedKHop, kRandomWalk, kWeightedKHopPrefix, kKHop2, kWeightedKHopHashDedup, kKHop3 = range(8)
 kKHopLabor = 8  # an extension: fixed-fanout LABOR sampling (include/ggms.h, GGMS_KHOP_LABOR)
 kKHopTemporal = 9  # an extension: sampling strictly before the seed's time (include/ggms.h, GGMS_KHOP_TEMPORAL)
+kKHopTyped = 10  # an extension: a fanout per edge type on a type-sorted CSR (include/ggms.h, GGMS_KHOP_TYPED)
 kArch0, kArch1, kArch2, kArch3, kArch4, kArch5, kArch6, kArch7 = range(8)
 (kCacheByDegree, kCacheByHeuristic, kCacheByPreSample, kCacheByDegreeHop, kCacheByPreSampleStatic,
  kCacheByFakeOptimal, kDynamicCache, kCacheByRandom) = range(8)
@@ -29,6 +30,7 @@ sample_types = {
     'khop0': kKHop0, 'khop1': kKHop1, 'khop2': kKHop2, 'khop3': kKHop3, 'random_walk': kRandomWalk,
     'weighted_khop': kWeightedKHop, 'weighted_khop_prefix': kWeightedKHopPrefix,
     'weighted_khop_hash_dedup': kWeightedKHopHashDedup, 'khop_labor': kKHopLabor, 'khop_temporal': kKHopTemporal,
+    'khop_typed': kKHopTyped,
 }
 builtin_archs = {
     'arch0': {'arch': kArch0, 'sampler_ctx': cpu(), 'trainer_ctx': gpu(0)},
@@ -117,6 +119,7 @@ SAMGRAPH_SYMBOLS = {
     "samgraph_get_graph_link_edge_ids": (None, [_u64, _TP]),
     "samgraph_get_graph_edge_time": (None, [_u64, _i, _TP]), "samgraph_get_graph_node_cut": (None, [_u64, _TP]),
     "samgraph_get_graph_link_time": (None, [_u64, _TP]),
+    "samgraph_get_graph_edge_type": (None, [_u64, _i, _TP]),
     "samgraph_update_graph_feat": (None, [_u64, C.c_void_p, _sz, _sz, C.c_void_p]),
     "samgraph_get_store_feat": (None, [_TP]), "samgraph_get_store_state": (None, [_TP]),
     "samgraph_batch_retain": (None, [_u64]), "samgraph_batch_release": (None, [_u64]),
@@ -141,6 +144,14 @@ class SamGraphBasics(object):
         return self._h
 
     def config(self, run_config: dict):
+        tf = run_config.get("type_fanout")
+        if isinstance(tf, (list, tuple)) and tf and isinstance(tf[0], (list, tuple)):
+            # sample_type khop_typed: num_layer rows of NUM_EDGE_TYPE fanouts, layer-major; a layer's fanout is its
+            # row's sum (the engine refuses a `fanout` that says otherwise)
+            run_config = dict(run_config)
+            run_config["type_fanout"] = [int(k) for row in tf for k in row]
+            run_config.setdefault("fanout", [sum(int(k) for k in row) for row in tf])
+            run_config.setdefault("num_fanout", len(tf))
         keys = [str(k).encode() for k in run_config.keys()]
         vals = []
         for value in run_config.values():

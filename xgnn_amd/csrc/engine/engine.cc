@@ -227,7 +227,12 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
     cfg.lookahead = 0;
     cfg.pipelines = 1;
   }
-  SAM_CHECK(cfg.sample_type >= GGMS_KHOP0 && cfg.sample_type <= GGMS_KHOP_TEMPORAL, "unknown sample type");
+  SAM_CHECK(cfg.sample_type >= GGMS_KHOP0 && cfg.sample_type <= GGMS_KHOP_TYPED, "unknown sample type");
+  if (cfg.Typed() && cfg.arch != kArch1) {
+    static const char *const arch_names[] = {"arch0", "arch1", "arch2", "arch3", "arch4", "arch5", "arch6", "arch7"};
+    fatal(__FILE__, __LINE__, std::string(arch_names[cfg.arch]) + ": _sample_type 10 (khop_typed) is not built: the edge "
+                              "types and the edge positions run in arch1's sampling chain only");
+  }
   if (cfg.Temporal() && cfg.arch != kArch1) {
     static const char *const arch_names[] = {"arch0", "arch1", "arch2", "arch3", "arch4", "arch5", "arch6", "arch7"};
     fatal(__FILE__, __LINE__, std::string(arch_names[cfg.arch]) + ": _sample_type 9 (khop_temporal) is not built: the seed "
@@ -356,6 +361,41 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
       cfg.temporal_pick = v == "recent" ? GGMS_PICK_RECENT : GGMS_PICK_UNIFORM;
     }
   }
+  if (cfg.Typed()) { // extension: a fanout per edge type
+    const std::string who = "_sample_type 10 (khop_typed)";
+    if (cfg.use_dist_graph)
+      fatal(__FILE__, __LINE__, who + " with use_dist_graph: edge types are stored by position in ONE CSR, a sharded "
+                                "topology has none");
+    if (cfg.exclude_seed_edges)
+      fatal(__FILE__, __LINE__, who + " with exclude_seed_edges = " + kv["exclude_seed_edges"] + " is not built: the filter "
+                                "compacts row / col and knows nothing of the position and type streams the sampler wrote "
+                                "beside them");
+    if (!kv.count("type_fanout"))
+      fatal(__FILE__, __LINE__, who + " needs the config key type_fanout: num_layer x NUM_EDGE_TYPE fanouts, layer-major");
+    std::stringstream ss(kv["type_fanout"]);
+    long long v;
+    while (ss >> v) {
+      if (v < 0 || v >= 128)
+        fatal(__FILE__, __LINE__, "type_fanout: the value " + std::to_string(v) + " is out of range: a relation's fanout is "
+                                  "0 (not sampled) .. 127");
+      cfg.type_fanout.push_back((uint32_t)v);
+    }
+    const size_t L = cfg.fanout.size(), nv = cfg.type_fanout.size();
+    if (!ss.eof() || nv == 0 || nv % L != 0 || nv / L > GGMS_MAX_EDGE_TYPES)
+      fatal(__FILE__, __LINE__, "type_fanout has " + std::to_string(nv) + " values: num_layer (" + std::to_string(L) +
+                                ") rows of NUM_EDGE_TYPE (1 .. " + std::to_string(GGMS_MAX_EDGE_TYPES) + ") integers");
+    cfg.num_edge_type = (uint32_t)(nv / L);
+    for (size_t i = 0; i < L; ++i) {
+      size_t sum = 0;
+      for (uint32_t r = 0; r < cfg.num_edge_type; ++r) sum += cfg.type_fanout[i * cfg.num_edge_type + r];
+      if (sum == 0)
+        fatal(__FILE__, __LINE__, "type_fanout: row " + std::to_string(i) + " is all zero: a layer that samples no relation");
+      if (sum != cfg.fanout[i])
+        fatal(__FILE__, __LINE__, "fanout[" + std::to_string(i) + "] = " + std::to_string(cfg.fanout[i]) + " disagrees with "
+                                  "type_fanout: row " + std::to_string(i) + " sums to " + std::to_string(sum) +
+                                  " (leave fanout to the Python front-end, or give the rows' sums)");
+    }
+  }
   if (kv.count("edge_ids") || kv.count("edge_feat")) { // extension: CSR positions (and edge-table rows) of the sampled edges
     for (const char *key : {"edge_ids", "edge_feat"})
       if (kv.count(key) && kv[key] != "on" && kv[key] != "off")
@@ -363,7 +403,7 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
     cfg.edge_feat = kv.count("edge_feat") && kv["edge_feat"] == "on";
     cfg.edge_ids = cfg.edge_feat || (kv.count("edge_ids") && kv["edge_ids"] == "on");
   }
-  if (cfg.Temporal()) cfg.edge_ids = true; // implied: the sampler emits the positions itself
+  if (cfg.SamplerEmitsEdgeIds()) cfg.edge_ids = true; // implied: the sampler emits the positions itself
   if (cfg.edge_ids) {
     static const char *const arch_names[] = {"arch0", "arch1", "arch2", "arch3", "arch4", "arch5", "arch6", "arch7"};
     const std::string key = cfg.edge_feat ? "edge_feat" : "edge_ids";
@@ -613,6 +653,38 @@ void Engine::LoadDataset() {
           fatal(__FILE__, __LINE__, "khop_temporal: edge_time.bin: the times of node " + std::to_string(v) + "'s list are not "
                                         "non-decreasing (position " + std::to_string(p) + "); datagen.sort_lists_by_time "
                                         "re-sorts a graph");
+  }
+  if (cfg.Typed()) { // the edge types: NUM_EDGE uint8 in CSR order, sorted inside every list, below NUM_EDGE_TYPE
+    if (!meta.count("NUM_EDGE_TYPE"))
+      fatal(__FILE__, __LINE__, "khop_typed: meta.txt lacks NUM_EDGE_TYPE (datagen.write_dataset(edge_type=, num_edge_type=))");
+    const size_t R = meta["NUM_EDGE_TYPE"];
+    if (R < 1 || R > GGMS_MAX_EDGE_TYPES)
+      fatal(__FILE__, __LINE__, "khop_typed: NUM_EDGE_TYPE = " + std::to_string(R) + ": 1 .. " + std::to_string(GGMS_MAX_EDGE_TYPES));
+    if (R != cfg.num_edge_type)
+      fatal(__FILE__, __LINE__, "type_fanout has " + std::to_string(cfg.type_fanout.size()) + " values, num_layer x "
+                                    "NUM_EDGE_TYPE is " + std::to_string(cfg.fanout.size()) + " x " + std::to_string(R));
+    const std::string name = cfg.dataset_path + "edge_type.bin";
+    struct stat st;
+    if (stat(name.c_str(), &st) != 0)
+      fatal(__FILE__, __LINE__, "khop_typed: " + name + " is missing (NUM_EDGE uint8 types, one per position of "
+                                    "indices.bin; datagen.write_dataset(edge_type=...))");
+    if ((size_t)st.st_size != ds.num_edge)
+      fatal(__FILE__, __LINE__, "khop_typed: edge_type.bin has " + std::to_string((size_t)st.st_size) + " bytes, NUM_EDGE is " +
+                                    std::to_string(ds.num_edge));
+    ds.edge_type = MapFile("edge_type.bin", ds.num_edge, false);
+    const uint32_t *ip = (const uint32_t *)ds.indptr.ptr;
+    const uint8_t *t = (const uint8_t *)ds.edge_type.ptr;
+    for (size_t v = 0; v < ds.num_node; ++v) // order and range in one pass: a sorted list's largest type is its last
+      for (size_t p = ip[v]; p < ip[v + 1]; ++p) {
+        if (p > ip[v] && t[p] < t[p - 1])
+          fatal(__FILE__, __LINE__, "khop_typed: edge_type.bin: the types of node " + std::to_string(v) + "'s list are not "
+                                        "non-decreasing (position " + std::to_string(p) + "); datagen.sort_lists_by_type "
+                                        "re-sorts a graph");
+        if (t[p] >= R)
+          fatal(__FILE__, __LINE__, "khop_typed: edge_type.bin: node " + std::to_string(v) + "'s list holds the type " +
+                                        std::to_string((unsigned)t[p]) + " (position " + std::to_string(p) +
+                                        "), NUM_EDGE_TYPE is " + std::to_string(R));
+      }
   }
   if (cfg.sample_type == GGMS_WEIGHTED_KHOP || cfg.sample_type == GGMS_WEIGHTED_KHOP_HASH_DEDUP) { // engine.cc:372-384
     ds.prob_table = MapFile("prob_table.bin", ds.num_edge * 4, false);
@@ -1088,7 +1160,7 @@ void Engine::SampleInit(int worker_id, const std::string &ctx) {
   extra_.random_walk_restart_prob = cfg.random_walk_restart_prob;
   extra_.num_random_walk = cfg.num_random_walk;
   // GPURandomStates dist_engine.cc:432-433; seed = wall clock unless the "seed" key is given
-  if (cfg.sample_type == GGMS_KHOP_LABOR || cfg.Temporal()) { // stateless: their variates are hashes of (node id, salt) -- no RNG pool
+  if (cfg.sample_type == GGMS_KHOP_LABOR || cfg.Temporal() || cfg.Typed()) { // stateless: their variates are hashes of (node id, salt) -- no RNG pool
     num_states_ = 0;
     states_ = nullptr;
   } else {
@@ -1107,6 +1179,8 @@ void Engine::SampleInit(int worker_id, const std::string &ctx) {
   ws_bytes_ = cfg.arch == kArch4 ? ggms_sample_batch_prefetch_workspace_bytes(cfg.sample_type, max_seeds_, cfg.fanout.data(),
                                                                           L, &extra_, max_prefetch_edges_)
                                  : ggms_sample_batch_workspace_bytes(cfg.sample_type, max_seeds_, cfg.fanout.data(), L, &extra_);
+  if (cfg.Typed()) // the boundary words follow NUM_EDGE_TYPE, which the generic function sizes at its maximum
+    ws_bytes_ = ggms_sample_batch_typed_workspace_bytes(max_seeds_, cfg.fanout.data(), L, cfg.num_edge_type, &extra_);
   SAM_HIP(hipMalloc(&ws_, ws_bytes_));
   // pipeline 0 = {stream_, ht_, ws_}; the others get their own stream, table and workspace
   pipes_.assign(cfg.pipelines, Pipe{});
@@ -1138,7 +1212,12 @@ void Engine::SampleInit(int worker_id, const std::string &ctx) {
       SAM_HIP(hipMemsetAsync(P.cut_table, 0, std::max<size_t>(ds.num_node, 1) * 8, stream_));
     }
   }
-  if (cfg.edge_ids && !cfg.Temporal()) { // the long-list queue of ggms_edge_positions, one per pipeline
+  if (cfg.Typed()) { // the edge types in HBM, beside the topology the sampler reads
+    SAM_HIP(hipMalloc((void **)&d_edge_type_, std::max<size_t>(ds.num_edge, 16)));
+    SAM_HIP(hipMemcpyAsync(d_edge_type_, ds.edge_type.ptr, ds.num_edge, hipMemcpyHostToDevice, stream_));
+    SAM_HIP(hipStreamSynchronize(stream_));
+  }
+  if (cfg.edge_ids && !cfg.SamplerEmitsEdgeIds()) { // the long-list queue of ggms_edge_positions, one per pipeline
     eid_ws_bytes_ = ggms_edge_positions_workspace_bytes(max_edges_.data(), L);
     SAM_CHECK(eid_ws_bytes_ > 0, "edge_ids: the batch bounds are out of ggms_edge_positions' range");
     for (Pipe &P : pipes_) SAM_HIP(hipMalloc(&P.eid_ws, eid_ws_bytes_));
@@ -1549,6 +1628,10 @@ void Engine::TrainInit(int worker_id, const std::string &ctx) {
       b->etime.assign(L, nullptr);
       for (uint32_t i = 0; i < L; ++i) SAM_HIP(hipMalloc((void **)&b->etime[i], std::max<size_t>(max_edges_[i], 4) * 4));
     }
+    if (cfg.Typed()) {
+      b->etype.assign(L, nullptr);
+      for (uint32_t i = 0; i < L; ++i) SAM_HIP(hipMalloc((void **)&b->etype[i], std::max<size_t>(max_edges_[i], 16)));
+    }
     if (StagedHostTier()) { // index arrays of GetMissCacheIndex + pinned / device staging of the miss rows
       if (cache_table_) { // (no cache: no split, and the rows land in the batch's feature buffer directly)
         for (uint32_t **p : {&b->miss_src, &b->miss_dst, &b->hit_src, &b->hit_dst}) SAM_HIP(hipMalloc((void **)p, max_unique_ * 4));
@@ -1716,7 +1799,8 @@ void Engine::SampleInto(Batch *b, Pipe &P) {
       SAM_GGMS(ggms_link_seed_times(d_edge_time_, ds.num_edge, b->edge_ids, b->num_pos, cfg.num_negative, b->seed_time,
                                     P.stream));
   }
-  if (pipes_.size() > 1 && cfg.sample_type != GGMS_KHOP0 && cfg.sample_type != GGMS_KHOP_LABOR && !cfg.Temporal()) {
+  if (pipes_.size() > 1 && cfg.sample_type != GGMS_KHOP0 && cfg.sample_type != GGMS_KHOP_LABOR && !cfg.Temporal() &&
+      !cfg.Typed()) {
     extra.rng_wait = last_rng_done_;
     extra.rng_done = P.rng_done;
     last_rng_done_ = P.rng_done;
@@ -1742,6 +1826,12 @@ void Engine::SampleInto(Batch *b, Pipe &P) {
     SAM_GGMS(ggms_sample_batch_temporal(&graph_, s.output_nodes, b->seed_time, b->num_seeds, cfg.fanout.data(), L, &ht,
                                         s.row.data(), s.col.data(), b->eid.data(), b->node_cut, s.counts_dev, &t, &extra, P.ws,
                                         ws_bytes_, P.stream));
+  } else if (cfg.Typed()) {
+    // the sampler fills the batch's eid and etype buffers itself, on the pipeline's stream like everything else here
+    const ggms_typed_t t{d_edge_type_, cfg.num_edge_type, cfg.type_fanout.data()};
+    SAM_GGMS(ggms_sample_batch_typed(&graph_, s.output_nodes, b->num_seeds, cfg.fanout.data(), L, &ht, s.row.data(),
+                                     s.col.data(), b->eid.data(), b->etype.data(), s.counts_dev, &t, &extra, P.ws, ws_bytes_,
+                                     P.stream));
   } else
     SAM_GGMS(ggms_sample_batch(cfg.sample_type, &graph_, s.output_nodes, b->num_seeds, cfg.fanout.data(), L, &ht, states_,
                                num_states_, s.row.data(), s.col.data(), s.counts_dev, &extra, P.ws, ws_bytes_, P.stream));
@@ -1762,7 +1852,7 @@ void Engine::SampleInto(Batch *b, Pipe &P) {
       SAM_HIP(hipMemcpyAsync(b->excluded, b->excluded_dev, L * 8, hipMemcpyDeviceToHost, P.stream));
     }
   }
-  if (cfg.edge_ids && !cfg.Temporal()) {
+  if (cfg.edge_ids && !cfg.SamplerEmitsEdgeIds()) {
     // Which edge of the graph every sampled edge is: a post-pass over the finished layers (behind the filter: the ids of
     // the edges that are left), with the batch's own input nodes as the local -> global map.  Same stream, no new one
     // (EnqueueGather's note on the four hardware queues), in front of ev_sampled like everything that writes the batch.

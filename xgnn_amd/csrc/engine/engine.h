@@ -118,6 +118,13 @@ struct RunConfig {
   // edge_ids -- the sampler itself emits the positions, ggms_edge_positions is not enqueued
   int temporal_pick = GGMS_PICK_UNIFORM;
   bool Temporal() const { return sample_type == GGMS_KHOP_TEMPORAL; }
+  // extension (`_sample_type` 10 = khop_typed, config key `type_fanout` = num_layer x NUM_EDGE_TYPE integers, layer-major;
+  // arch1, one CSR, both tasks): a fanout per edge type (ggms_sample_batch_typed); `fanout` holds the rows' sums.  Implies
+  // edge_ids like khop_temporal
+  std::vector<uint32_t> type_fanout;
+  uint32_t num_edge_type = 0; // type_fanout.size() / num_layer; LoadDataset checks it against meta.txt's NUM_EDGE_TYPE
+  bool Typed() const { return sample_type == GGMS_KHOP_TYPED; }
+  bool SamplerEmitsEdgeIds() const { return Temporal() || Typed(); } // ggms_edge_positions is not enqueued
   size_t staged_serial_epochs = 0; // host-staged path: the first N epochs run the reference's serial, per-phase-timed sequence
   size_t staged_serial_steps = 0;  // ... or this worker's first N batches
   // worker 0 ranks the nodes at init: pre_sample (sampled input nodes) or presample_static (L-hop closures)
@@ -159,6 +166,9 @@ struct Dataset {
   HostArray edge_feat;
   // khop_temporal: edge_time.bin, NUM_EDGE uint32 in CSR order, non-decreasing inside every node's list (checked at load)
   HostArray edge_time;
+  // khop_typed: edge_type.bin, NUM_EDGE uint8 in CSR order, non-decreasing inside every node's list and below NUM_EDGE_TYPE
+  // (checked at load)
+  HostArray edge_type;
   size_t edge_feat_row_bytes() const { return edge_feat_dim * ggms_dtype_bytes(edge_feat_dtype); }
 };
 
@@ -235,6 +245,8 @@ struct Batch {
   // every input node, and per layer edge_time[eid].  Null / empty with every other sampler.
   uint32_t *seed_time = nullptr, *node_cut = nullptr;
   std::vector<uint32_t *> etime;
+  // khop_typed: per layer the sampled edges' types, written by the sampler beside eid.  Empty with every other sampler.
+  std::vector<uint8_t *> etype;
   uint64_t num_miss = 0;
   hipEvent_t ev_seeds = nullptr, ev_start = nullptr, ev_sampled = nullptr, ev_xstart = nullptr, ev_done = nullptr;
   // arch6 with `gpu_extract` off: the host-staged miss path (dist_loops.cc:1015-1207)
@@ -415,6 +427,7 @@ class Engine {
   size_t eid_ws_bytes_ = 0;    // edge_ids: ggms_edge_positions' workspace (Pipe::eid_ws)
   void *d_edge_feat_ = nullptr; // edge_feat: the edge table in HBM
   uint32_t *d_edge_time_ = nullptr; // khop_temporal: the edge times in HBM
+  uint8_t *d_edge_type_ = nullptr;  // khop_typed: the edge types in HBM
   uint64_t link_excluded_ = 0; // exclude_seed_edges: edges dropped from the batches handed out so far in this epoch
   std::vector<Pipe> pipes_;
   size_t enq_count_ = 0;

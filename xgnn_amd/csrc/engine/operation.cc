@@ -197,6 +197,14 @@ void samgraph_get_graph_link_time(uint64_t key, samgraph_tensor_t *out) {
   auto *b = temporal_batch(key, "samgraph_get_graph_link_time");
   fill(out, b->seed_time, (int64_t)b->num_pos, 1, 1, GGMS_I32, E.batch_device_type(), E.trainer_device());
 }
+// _sample_type 10 (khop_typed): the type of every edge of layer l, edge_type[edge_ids], as the sampler wrote it -- uint8
+void samgraph_get_graph_edge_type(uint64_t key, int l, samgraph_tensor_t *out) {
+  auto &E = Engine::Get();
+  if (!E.cfg.Typed()) sam::fatal(__FILE__, __LINE__, "samgraph_get_graph_edge_type needs _sample_type 10 (khop_typed)");
+  auto *b = E.Current(key);
+  SAM_CHECK(l >= 0 && (size_t)l < b->etype.size(), "samgraph_get_graph_edge_type: no such layer");
+  fill(out, b->etype[l], (int64_t)b->counts[GGMS_COUNT_EDGES(l)], 1, 1, GGMS_U8, E.batch_device_type(), E.trainer_device());
+}
 // config key feat_learnable: the gradient of the current batch's rows moves the table; the live table and its state
 void samgraph_update_graph_feat(uint64_t key, const void *grad, size_t num_rows, size_t dim, void *caller_stream) {
   Engine::Get().UpdateGraphFeat(key, grad, num_rows, dim, (hipStream_t)caller_stream);

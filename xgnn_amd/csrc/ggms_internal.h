@@ -92,6 +92,12 @@ struct SampleLayer {
   uint32_t stamp = 0;
   int pick = 0;
   uint32_t *out_pos = nullptr;
+  // khop_typed: per-position types, their number R, the R type fanouts of this layer (host; `fanout` is their sum), the
+  // types' output.  Shares out_pos with khop_temporal
+  const uint8_t *edge_type = nullptr;
+  uint32_t num_type = 0;
+  const uint32_t *type_fanout = nullptr;
+  uint8_t *out_type = nullptr;
 };
 
 // sample_khop.hip
@@ -121,8 +127,13 @@ int temporal_seed_cut_impl(const uint32_t *seeds, const uint32_t *seed_time, siz
 int temporal_node_cut_impl(const uint32_t *n2o, size_t n_max, Count n, const uint64_t *cut_table, uint32_t stamp,
                            uint32_t *node_cut, hipStream_t s); // node_cut[local id] = cut[n2o[local id]]
 
+// sample_typed.hip
+size_t typed_ws_words(size_t num_input, size_t num_type); // num_type 0: sized for GGMS_MAX_EDGE_TYPES
+int typed_fanout_sum(const uint32_t *type_fanout, uint32_t num_type, size_t *sum); // refuses R, a null row, a k_r >= 128
+int sample_khop_typed_impl(const SampleLayer &l);
+
 // sample_batch.hip: the per-sampler rules, one copy for the leaf entry points and ggms_sample_batch
-size_t layer_ws_words(int type, size_t n, size_t fanout, size_t walk_length, size_t num_walk);
+size_t layer_ws_words(int type, size_t n, size_t fanout, size_t walk_length, size_t num_walk, size_t num_type = 0);
 int sample_leaf(int type, SampleLayer l, size_t num_states, size_t workspace_bytes); // a leaf entry point's body
 
 // hashtable.hip

@@ -68,8 +68,9 @@ static BatchCaps caps_of(size_t num_seeds, const size_t *fanouts, uint32_t L) {
 
 // ---- the per-sampler rules: one copy for the leaf entry points and ggms_sample_batch --------------------------
 
-size_t layer_ws_words(int type, size_t n, size_t fanout, size_t walk_length, size_t num_walk) {
+size_t layer_ws_words(int type, size_t n, size_t fanout, size_t walk_length, size_t num_walk, size_t num_type) {
   switch (type) {
+  case GGMS_KHOP_TYPED: return typed_ws_words(n, num_type);
   case GGMS_KHOP0: return khop0_ws_words(n, fanout);
   case GGMS_KHOP1:
   case GGMS_WEIGHTED_KHOP:
@@ -88,6 +89,12 @@ static int layer_shape_check(int type, const SampleLayer &l) {
   if (type == GGMS_WEIGHTED_KHOP_HASH_DEDUP) GGMS_CHECK_ARG(l.fanout < kDedupSlots); // hash_dedup.cu:42
   if (type == GGMS_KHOP_LABOR) GGMS_CHECK_ARG(l.fanout < 128); // the hub route ranks its selection in LDS
   if (type == GGMS_KHOP_TEMPORAL) GGMS_CHECK_ARG(l.fanout < 128); // khop_labor's selection on a prefix
+  if (type == GGMS_KHOP_TYPED) { // khop_labor's selection per segment: every k_r < 128; `fanout` is the row's sum
+    size_t sum = 0;
+    const int rc = typed_fanout_sum(l.type_fanout, l.num_type, &sum);
+    if (rc != GGMS_OK) return rc;
+    GGMS_CHECK_ARG(sum == l.fanout);
+  }
   if (type == GGMS_RANDOM_WALK) GGMS_CHECK_ARG(l.walk_length > 0 && l.num_walk > 0);
   // "this algorithm not support DistGraph engine", dist_loops.cc:167-228
   if (type != GGMS_KHOP3 && type != GGMS_KHOP0 && type != GGMS_RANDOM_WALK && type != GGMS_KHOP_LABOR)
@@ -100,8 +107,9 @@ static int layer_check(int type, const SampleLayer &l, size_t num_states) {
   const int rc = layer_shape_check(type, l);
   if (rc != GGMS_OK) return rc;
   const uint64_t n = l.n_max;
-  if (type == GGMS_KHOP1 || type == GGMS_KHOP2 || type == GGMS_KHOP_TEMPORAL)
+  if (type == GGMS_KHOP1 || type == GGMS_KHOP2 || type == GGMS_KHOP_TEMPORAL || type == GGMS_KHOP_TYPED)
     GGMS_CHECK_ARG(l.graph->indptr && l.graph->indices);
+  if (type == GGMS_KHOP_TYPED) GGMS_CHECK_ARG(l.edge_type && l.out_pos && l.out_type);
   if (type == GGMS_KHOP_TEMPORAL) GGMS_CHECK_ARG(l.edge_time && l.out_pos && (l.input_cut || l.cut_table));
   if (type == GGMS_WEIGHTED_KHOP || type == GGMS_WEIGHTED_KHOP_HASH_DEDUP) GGMS_CHECK_ARG(l.prob && l.alias);
   if (type == GGMS_WEIGHTED_KHOP_PREFIX) GGMS_CHECK_ARG(l.prob);
@@ -109,7 +117,8 @@ static int layer_check(int type, const SampleLayer &l, size_t num_states) {
   switch (type) {
   case GGMS_KHOP0:
   case GGMS_KHOP_LABOR:
-  case GGMS_KHOP_TEMPORAL: return GGMS_OK; // stateless
+  case GGMS_KHOP_TEMPORAL:
+  case GGMS_KHOP_TYPED: return GGMS_OK; // stateless
   case GGMS_KHOP3: GGMS_CHECK_ARG(l.states && (n + 127) / 128 * 8 <= num_states); return GGMS_OK; // khop3.cu:89
   case GGMS_KHOP2:                                                                                   // khop2.cu:57
   case GGMS_WEIGHTED_KHOP_HASH_DEDUP: // hash_dedup.cu:70
@@ -137,6 +146,7 @@ static int sample_layer(int type, const SampleLayer &l) {
   case GGMS_RANDOM_WALK: return sample_random_walk_impl(l);
   case GGMS_KHOP_LABOR: return sample_khop_labor_impl(l);
   case GGMS_KHOP_TEMPORAL: return sample_khop_temporal_impl(l);
+  case GGMS_KHOP_TYPED: return sample_khop_typed_impl(l);
   default: return sample_weighted_impl(l, type); // khop1, weighted_khop, weighted_khop_prefix
   }
 }
@@ -148,9 +158,9 @@ static int sample_layer(int type, const SampleLayer &l) {
 // separate insert launch of ht_fill_impl follows).  khop_labor does not either: its selection writes each edge from
 // the lane that held the key, after a search that is all ballots -- a returning atomic per edge there would serialise
 // behind the search of the seed's whole wave, and the sampler stays a pure function of its inputs.
-// khop_temporal is khop_labor's selection: the same holds.
+// khop_temporal and khop_typed are khop_labor's selection: the same holds.
 static bool layer_enters_output(int type) {
-  return type != GGMS_KHOP2 && type != GGMS_KHOP_LABOR && type != GGMS_KHOP_TEMPORAL;
+  return type != GGMS_KHOP2 && type != GGMS_KHOP_LABOR && type != GGMS_KHOP_TEMPORAL && type != GGMS_KHOP_TYPED;
 }
 
 // a leaf entry point: shape checks; nothing to sample -> a zero count (null pointers allowed); pointers, workspace and
@@ -164,7 +174,8 @@ int sample_leaf(int type, SampleLayer l, size_t num_states, size_t workspace_byt
     return GGMS_OK;
   }
   GGMS_CHECK_ARG(l.input && l.out_src && l.out_dst && l.workspace && (type != GGMS_RANDOM_WALK || l.out_data));
-  GGMS_CHECK_ARG(workspace_bytes >= layer_ws_words(type, l.n_max, l.fanout, l.walk_length, l.num_walk) * sizeof(uint32_t));
+  GGMS_CHECK_ARG(workspace_bytes >=
+                 layer_ws_words(type, l.n_max, l.fanout, l.walk_length, l.num_walk, l.num_type) * sizeof(uint32_t));
   // 32-bit output positions; a random walk's are bounded by walk_length * num_walk < 2^31 instead
   GGMS_CHECK_ARG(type == GGMS_RANDOM_WALK || (uint64_t)l.n_max * l.fanout < (1ull << 32));
   rc = layer_check(type, l, num_states);
@@ -206,12 +217,12 @@ int ggms_sample_batch_capacity(size_t num_seeds, const size_t *fanouts, uint32_t
 }
 
 static size_t sampler_ws_words(int sample_type, const BatchCaps &c, const size_t *fanouts, uint32_t L,
-                               const ggms_sample_extra_t *extra) {
+                               const ggms_sample_extra_t *extra, size_t num_type) {
   size_t w = sample_ws_words(c.max_in_all);
   if (sample_type == GGMS_RANDOM_WALK && !extra) return w; // no walk: ggms_sample_batch refuses the call
   for (uint32_t i = 0; i < L; ++i)
     w = std::max(w, layer_ws_words(sample_type, c.max_input[i], fanouts[i], extra ? extra->random_walk_length : 0,
-                                   extra ? extra->num_random_walk : 0));
+                                   extra ? extra->num_random_walk : 0, num_type));
   return w;
 }
 
@@ -225,12 +236,14 @@ struct BatchLayout {
 static inline size_t up4(size_t w) { return (w + 3) & ~(size_t)3; }
 
 // pf_edges: the prefetching batch's expansion capacity (its keys are one more fill of the batch); 0 = none
+// num_type: khop_typed's R (its boundary words); 0 = sized for GGMS_MAX_EDGE_TYPES.  seed_local is the first piece
+// whatever it is
 static BatchLayout layout_of(int sample_type, size_t num_seeds, const size_t *fanouts, uint32_t L, const BatchCaps &c,
-                             const ggms_sample_extra_t *extra, size_t pf_edges = 0) {
+                             const ggms_sample_extra_t *extra, size_t pf_edges = 0, size_t num_type = 0) {
   BatchLayout l{};
   size_t w = 0;
   l.seed_local = w;  w += up4(num_seeds + 16);
-  l.samp_ws = w;     w += up4(sampler_ws_words(sample_type, c, fanouts, L, extra));
+  l.samp_ws = w;     w += up4(sampler_ws_words(sample_type, c, fanouts, L, extra, num_type));
   for (uint32_t i = 0; i < L; ++i) { // global neighbour ids of every layer: kept for the end-of-batch id look-ups
     l.tmp_dst[i] = w;
     w += up4(c.max_edges[i] + 16);
@@ -273,6 +286,13 @@ struct Prefetch {
   hipEvent_t start, final;
 };
 
+// ggms_sample_batch_typed's part of a batch (NULL: any other batch)
+struct TypedBatch {
+  const ggms_typed_t *t;
+  ggms_id_t *const *eid;
+  uint8_t *const *etype;
+};
+
 // ggms_sample_batch_temporal's part of a batch (NULL: any other batch)
 struct TemporalBatch {
   const ggms_temporal_t *t;
@@ -281,13 +301,13 @@ struct TemporalBatch {
   uint32_t *node_cut;
 };
 
-// the body of ggms_sample_batch, ggms_sample_batch_prefetch and ggms_sample_batch_temporal; every argument check is the
-// caller's
+// the body of ggms_sample_batch, ggms_sample_batch_prefetch, ggms_sample_batch_temporal and ggms_sample_batch_typed;
+// every argument check is the caller's
 static int sample_batch_impl(int sample_type, const ggms_graph_t *graph, const ggms_id_t *seeds, size_t num_seeds,
                              const size_t *fanouts, uint32_t num_layer, ggms_hashtable_t *ht, void *states,
                              size_t num_states, ggms_id_t *const *row, ggms_id_t *const *col, uint64_t *counts_dev,
                              const ggms_sample_extra_t *extra, void *workspace, const Prefetch *pf, hipStream_t s,
-                             const TemporalBatch *tb = nullptr) {
+                             const TemporalBatch *tb = nullptr, const TypedBatch *yb = nullptr) {
   const BatchCaps c = caps_of(num_seeds, fanouts, num_layer);
   // what every layer's sampler call shares; the loop below fills in the rest
   SampleLayer L{graph, nullptr, 0, 0, nullptr, nullptr, nullptr, (uint32_t *)states, nullptr, s};
@@ -299,7 +319,8 @@ static int sample_batch_impl(int sample_type, const ggms_graph_t *graph, const g
     L.restart_prob = extra->random_walk_restart_prob;
   }
   // a stateless sampler has nothing to order between batches
-  const bool ordered_rng = sample_type != GGMS_KHOP_LABOR && sample_type != GGMS_KHOP_TEMPORAL;
+  const bool ordered_rng = sample_type != GGMS_KHOP_LABOR && sample_type != GGMS_KHOP_TEMPORAL &&
+                           sample_type != GGMS_KHOP_TYPED;
   if (tb) {
     L.edge_time = tb->t->edge_time;
     L.cut_table = tb->t->cut_table;
@@ -307,15 +328,22 @@ static int sample_batch_impl(int sample_type, const ggms_graph_t *graph, const g
     L.pick = (int)tb->t->pick;
     L.out_pos = tb->eid[0]; // layer_check's non-null test; every layer sets its own below
   }
+  if (yb) {
+    L.edge_type = yb->t->edge_type;
+    L.num_type = yb->t->num_type;
+    L.out_pos = yb->eid[0]; // layer_check's non-null tests; every layer sets its own below
+    L.out_type = yb->etype[0];
+  }
   for (uint32_t i = 0; i < num_layer; ++i) {
     L.n_max = c.max_input[i];
     L.fanout = fanouts[i];
+    if (yb) L.type_fanout = yb->t->type_fanout + (size_t)i * L.num_type; // fanouts[i] must be this row's sum
     const int rc = layer_check(sample_type, L, num_states);
     if (rc != GGMS_OK) return rc;
   }
 
   const BatchLayout lay = layout_of(sample_type, num_seeds, fanouts, num_layer, c, extra,
-                                    pf ? std::max<size_t>(pf->max_edges, 1) : 0);
+                                    pf ? std::max<size_t>(pf->max_edges, 1) : 0, L.num_type);
   uint32_t *w = (uint32_t *)(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
   uint32_t *seed_local = w + lay.seed_local;
   uint32_t *samp_ws = w + lay.samp_ws;
@@ -466,6 +494,11 @@ static int sample_batch_impl(int sample_type, const ggms_graph_t *graph, const g
       L.enter = first && khop0_enters ? &seed_enter : nullptr;
       if (sample_type == GGMS_RANDOM_WALK) L.out_data = extra->data[i];
       if (tb) L.out_pos = tb->eid[i];
+      if (yb) {
+        L.type_fanout = yb->t->type_fanout + (size_t)i * L.num_type;
+        L.out_pos = yb->eid[i];
+        L.out_type = yb->etype[i];
+      }
       rc = sample_layer(sample_type, L);
     }
     if (rc != GGMS_OK) return rc;
@@ -526,6 +559,11 @@ int ggms_sample_batch(int sample_type, const ggms_graph_t *graph, const ggms_id_
               "ggms_sample_batch_temporal", sample_type);
     return GGMS_ERR_INVALID;
   }
+  if (sample_type == GGMS_KHOP_TYPED) {
+    set_error("ggms_sample_batch: sample type %d (khop_typed) takes edge types and a fanout per type and layer: call "
+              "ggms_sample_batch_typed", sample_type);
+    return GGMS_ERR_INVALID;
+  }
   GGMS_CHECK_ARG(sample_type >= GGMS_KHOP0 && sample_type <= GGMS_KHOP_LABOR);
   GGMS_CHECK_ARG(num_seeds == 0 || seeds);
   GGMS_CHECK_ARG(workspace && workspace_bytes >= ggms_sample_batch_workspace_bytes(sample_type, num_seeds, fanouts,
@@ -544,7 +582,7 @@ int ggms_sample_batch_seed_ids(int sample_type, size_t num_seeds, const size_t *
                                const ggms_sample_extra_t *extra, const void *workspace, const ggms_id_t **seed_ids_dev) {
   GGMS_CHECK_ARG(fanouts && workspace && seed_ids_dev);
   GGMS_CHECK_ARG(num_layer >= 1 && num_layer <= 16);
-  GGMS_CHECK_ARG(sample_type >= GGMS_KHOP0 && sample_type <= GGMS_KHOP_TEMPORAL);
+  GGMS_CHECK_ARG(sample_type >= GGMS_KHOP0 && sample_type <= GGMS_KHOP_TYPED);
   const BatchCaps c = caps_of(num_seeds, fanouts, num_layer);
   const BatchLayout lay = layout_of(sample_type, num_seeds, fanouts, num_layer, c, extra);
   const uint32_t *w = (const uint32_t *)(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
@@ -582,6 +620,42 @@ int ggms_sample_batch_temporal(const ggms_graph_t *graph, const ggms_id_t *seeds
   const TemporalBatch tb{t, seed_time, eid, node_cut};
   return sample_batch_impl(GGMS_KHOP_TEMPORAL, graph, seeds, num_seeds, fanouts, num_layer, ht, nullptr, 0, row, col,
                            counts_dev, &ex, workspace, nullptr, to_stream(stream), &tb);
+}
+
+// ---- khop_typed: the batch with a fanout per edge type and layer ---------------------------------------------------
+size_t ggms_sample_batch_typed_workspace_bytes(size_t num_seeds, const size_t *fanouts, uint32_t num_layer,
+                                               uint32_t num_type, const ggms_sample_extra_t *extra) {
+  if (!fanouts || num_layer < 1 || num_layer > 16 || num_type < 1 || num_type > GGMS_MAX_EDGE_TYPES) return 0;
+  const BatchCaps c = caps_of(num_seeds, fanouts, num_layer);
+  return layout_of(GGMS_KHOP_TYPED, num_seeds, fanouts, num_layer, c, extra, 0, num_type).total * sizeof(uint32_t) + 16;
+}
+
+int ggms_sample_batch_typed(const ggms_graph_t *graph, const ggms_id_t *seeds, size_t num_seeds, const size_t *fanouts,
+                            uint32_t num_layer, ggms_hashtable_t *ht, ggms_id_t *const *row, ggms_id_t *const *col,
+                            ggms_id_t *const *eid, uint8_t *const *etype, uint64_t *counts_dev, const ggms_typed_t *t,
+                            const ggms_sample_extra_t *extra, void *workspace, size_t workspace_bytes,
+                            ggms_stream_t stream) {
+  GGMS_CHECK_ARG(graph && fanouts && ht && row && col && eid && etype && counts_dev && t);
+  GGMS_CHECK_ARG(num_layer >= 1 && num_layer <= 16);
+  GGMS_CHECK_ARG(graph->num_part == 0); // edge positions are those of one CSR
+  GGMS_CHECK_ARG(t->edge_type && t->type_fanout);
+  GGMS_CHECK_ARG(t->num_type >= 1 && t->num_type <= GGMS_MAX_EDGE_TYPES);
+  for (uint32_t i = 0; i < num_layer; ++i) { // every row: k_r < 128, and fanouts[i] is its sum (>= 1)
+    size_t sum = 0;
+    const int rc = typed_fanout_sum(t->type_fanout + (size_t)i * t->num_type, t->num_type, &sum);
+    if (rc != GGMS_OK) return rc;
+    GGMS_CHECK_ARG(sum >= 1 && sum == fanouts[i]);
+  }
+  GGMS_CHECK_ARG(num_seeds == 0 || seeds);
+  for (uint32_t i = 0; i < num_layer; ++i) GGMS_CHECK_ARG(row[i] && col[i] && eid[i] && etype[i]);
+  GGMS_CHECK_ARG(workspace && workspace_bytes >= ggms_sample_batch_typed_workspace_bytes(num_seeds, fanouts, num_layer,
+                                                                                         t->num_type, extra));
+  const BatchCaps c = caps_of(num_seeds, fanouts, num_layer);
+  GGMS_CHECK_ARG(c.max_input[0] + c.max_edges[0] <= ht->n2o_size);
+  GGMS_CHECK_ARG(c.max_input[0] + c.max_edges[0] < (1ull << 32) - 4); // indices and 2 + local id fit 32 bits
+  const TypedBatch yb{t, eid, etype};
+  return sample_batch_impl(GGMS_KHOP_TYPED, graph, seeds, num_seeds, fanouts, num_layer, ht, nullptr, 0, row, col,
+                           counts_dev, extra, workspace, nullptr, to_stream(stream), nullptr, &yb);
 }
 
 // ---- arch4: the prefetching batch ----------------------------------------------------------------------------------

@@ -143,7 +143,8 @@ def build_prob_prefix_table(indptr, weights, num_threads=8):
 
 
 def write_dataset(path, graph, feat=None, label=None, valid_frac=0.02, test_frac=0.05, feat_dtype="F32", weights=None,
-                  minimal=False, train_edges=None, edge_feat=None, edge_feat_dtype="F32", edge_time=None):
+                  minimal=False, train_edges=None, edge_feat=None, edge_feat_dtype="F32", edge_time=None, edge_type=None,
+                  num_edge_type=None):
     """Write a dataset directory in the reference's on-disk format (datagen/README.md:37-51,
     samgraph/common/constant.cc:23-51, engine.cc:109-443): meta.txt (tab separated) + raw little-endian
     arrays: indptr/indices/train_set/test_set/valid_set/cache_by_* uint32, feat row-major, label int64;
@@ -157,6 +158,9 @@ def write_dataset(path, graph, feat=None, label=None, valid_frac=0.02, test_frac
     (FP8: as for feat), not Q8ROW.
     edge_time (one uint32 per edge, in the order of indices, non-decreasing inside every node's list -- see
     sort_lists_by_time) adds edge_time.bin, the times `sample_type khop_temporal` samples before.
+    edge_type (one uint8 per edge, in the order of indices, non-decreasing inside every node's list -- see
+    sort_lists_by_type -- and below num_edge_type, 1 .. 32) adds edge_type.bin and the meta key NUM_EDGE_TYPE, the
+    relations `sample_type khop_typed` has a fanout for.
     minimal: what a sampling + extract run needs and nothing that costs minutes at papers100M size -- one-node
     valid / test sets instead of random slices of the complement, no cache_by_random.bin."""
     import os
@@ -203,6 +207,22 @@ def write_dataset(path, graph, feat=None, label=None, valid_frac=0.02, test_frac
         assert bad is None, (f"edge_time: the times of node {bad}'s list are not non-decreasing "
                              "(datagen.sort_lists_by_time re-sorts a graph)")
         edge_time.tofile(os.path.join(path, "edge_time.bin"))
+    if edge_type is not None:
+        assert num_edge_type is not None and 1 <= int(num_edge_type) <= 32, \
+            f"num_edge_type: 1 .. 32 (GGMS_MAX_EDGE_TYPES), not {num_edge_type}"
+        assert np.asarray(edge_type).size == 0 or (0 <= int(np.min(edge_type)) and int(np.max(edge_type)) < 256), \
+            "edge_type: uint8 values"
+        edge_type = np.ascontiguousarray(edge_type, dtype=np.uint8)
+        assert edge_type.shape == (ix.size,), f"edge_type: one type per edge ({ix.size}), not {edge_type.shape}"
+        bad = first_unsorted_list(ip, edge_type)
+        assert bad is None, (f"edge_type: the types of node {bad}'s list are not non-decreasing "
+                             "(datagen.sort_lists_by_type re-sorts a graph)")
+        over = np.flatnonzero(edge_type >= int(num_edge_type))
+        assert over.size == 0, (f"edge_type: node {int(np.searchsorted(ip, over[0], side='right') - 1) if over.size else 0}"
+                                f"'s list holds a type >= num_edge_type = {num_edge_type}")
+        edge_type.tofile(os.path.join(path, "edge_type.bin"))
+    else:
+        assert num_edge_type is None, "num_edge_type without edge_type"
     if label is not None:
         np.ascontiguousarray(label, dtype=np.int64).tofile(os.path.join(path, "label.bin"))
     if weights is not None:  # tables of the weighted samplers (engine.cc:372-384 loads them by these names)
@@ -223,11 +243,14 @@ def write_dataset(path, graph, feat=None, label=None, valid_frac=0.02, test_frac
         if edge_feat is not None:
             f.write(f"EDGE_FEAT_DIM\t{edge_feat.shape[1]}\n")
             f.write(f"EDGE_FEAT_DATA_TYPE\t{edge_feat_dtype}\n")
+        if edge_type is not None:
+            f.write(f"NUM_EDGE_TYPE\t{int(num_edge_type)}\n")
     return path
 
 
 def first_unsorted_list(indptr, edge_time):
-    """The first node whose list's times are not non-decreasing (khop_temporal's precondition), or None."""
+    """The first node whose list's values (times, types) are not non-decreasing -- the precondition of khop_temporal and
+    khop_typed -- or None."""
     ip = np.asarray(indptr, dtype=np.int64)
     t = np.asarray(edge_time, dtype=np.int64)
     if t.size < 2:
@@ -246,12 +269,23 @@ def sort_lists_by_time(indptr, indices, edge_time, *edge_arrays):
     re-mapped by the caller: new position = inverse[old position], inverse[perm] = arange.
     Times are uint32.  Float or 64-bit times are rank-transformed first (np.unique(t, return_inverse=True)[1]): only
     their order matters to the sampler."""
+    return _sort_lists_by(indptr, indices, np.ascontiguousarray(edge_time, dtype=np.uint32), "edge_time", edge_arrays)
+
+
+def sort_lists_by_type(indptr, indices, edge_type, *edge_arrays):
+    """A type-sorted CSR for khop_typed: every node's list stably re-sorted by edge type (a relation's edges keep their
+    order), so the edges of one type of a node are one contiguous segment.  Returns (indices, edge_type, *edge_arrays,
+    perm), sort_lists_by_time's convention: new[p] = old[perm[p]]."""
+    return _sort_lists_by(indptr, indices, np.ascontiguousarray(edge_type, dtype=np.uint8), "edge_type", edge_arrays)
+
+
+def _sort_lists_by(indptr, indices, key, what, edge_arrays):
+    """Every list stably re-sorted by a per-edge key: (indices, key, *edge_arrays, perm), all permuted alike."""
     ip = np.asarray(indptr, dtype=np.int64)
-    t = np.ascontiguousarray(edge_time, dtype=np.uint32)
-    assert t.shape == (int(ip[-1]),), "edge_time: one time per edge"
+    assert key.shape == (int(ip[-1]),), f"{what}: one value per edge"
     owner = np.repeat(np.arange(ip.size - 1), np.diff(ip))
-    perm = np.lexsort((np.arange(t.size), t, owner))  # by list, then time, then old position
-    return (np.asarray(indices)[perm], t[perm], *[np.asarray(a)[perm] for a in edge_arrays], perm)
+    perm = np.lexsort((np.arange(key.size), key, owner))  # by list, then key, then old position
+    return (np.asarray(indices)[perm], key[perm], *[np.asarray(a)[perm] for a in edge_arrays], perm)
 
 
 # FEAT_DATA_TYPE names of the OCP 8-bit float tables (include/ggms.h: GGMS_F8E4M3 = 16, GGMS_F8E5M2 = 17)

@@ -51,7 +51,9 @@ KHOP0, KHOP1, WEIGHTED_KHOP, RANDOM_WALK, WEIGHTED_KHOP_PREFIX, KHOP2, WEIGHTED_
 KHOP_LABOR = 8  # an extension: per-node shared randomness (include/ggms.h)
 KHOP_TEMPORAL = 9  # an extension: sampling strictly before a per-seed cut-off time (include/ggms.h)
 PICK_UNIFORM, PICK_RECENT = 0, 1  # khop_temporal's picks
-_STATELESS = (KHOP0, KHOP_LABOR, KHOP_TEMPORAL)  # samplers without an RNG pool
+KHOP_TYPED = 10  # an extension: a fanout per edge type on a type-sorted CSR (include/ggms.h)
+MAX_EDGE_TYPES = 32  # GGMS_MAX_EDGE_TYPES
+_STATELESS = (KHOP0, KHOP_LABOR, KHOP_TEMPORAL, KHOP_TYPED)  # samplers without an RNG pool
 
 
 def _require_gpu(t):
@@ -177,6 +179,32 @@ def sample_khop_temporal(graph, edge_time, inp, inp_cut, fanout, layer_salt, pic
                                           _ptr(num_out), _ptr(ws), ws.numel() * 4, _stream()),
           "ggms_sample_khop_temporal")
     return out[0], out[1], out[2], num_out
+
+
+def _u8(t):
+    assert t.dtype == torch.uint8 and t.dim() == 1 and t.stride(0) == 1, "edge types: a dense 1-d uint8 tensor"
+    return t
+
+
+def sample_khop_typed(graph, edge_type, type_fanout, inp, layer_salt):
+    """ggms_sample_khop_typed: per seed and edge type r (a contiguous segment of the type-sorted list), khop_labor's
+    selection with fanout type_fanout[r] on the segment, one salt for all types.
+    Returns (out_src, out_dst, out_pos, out_type, num_out[1] on device); out_pos = the edges' positions in
+    graph.indices, out_type (uint8) their types."""
+    _require_gpu(inp)
+    _i32(inp), _u8(edge_type)
+    n, R = inp.numel(), len(type_fanout)
+    K = sum(int(k) for k in type_fanout)
+    dev = inp.device
+    out = [torch.empty(max(1, n * K), dtype=torch.int32, device=dev) for _ in range(3)]
+    out_type = torch.empty(max(1, n * K), dtype=torch.uint8, device=dev)
+    num_out = torch.zeros(1, dtype=torch.int64, device=dev)
+    ws = _workspace(lib().ggms_sample_khop_typed_workspace_bytes(n, R), dev)
+    f = (C.c_uint32 * max(R, 1))(*[int(k) for k in type_fanout])
+    check(lib().ggms_sample_khop_typed(C.byref(graph.c), _ptr(edge_type), R, f, _ptr(inp), n, layer_salt & 0xFFFFFFFF,
+                                       _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out_type), _ptr(num_out),
+                                       _ptr(ws), ws.numel() * 4, _stream()), "ggms_sample_khop_typed")
+    return out[0], out[1], out[2], out_type, num_out
 
 
 def link_seed_times(edge_time, edge_ids, num_negative):
@@ -1118,6 +1146,61 @@ class TemporalBatchSampler(_BatchBuffers):
             lay["eid"] = self.eid[i][:c[COUNT_EDGES(i)]]
         n_in = c[COUNT_INPUT(self.L)]
         return dict(layers=layers, input_nodes=self.ht.n2o[:n_in], node_cut=self.node_cut[:n_in])
+
+
+class TypedBatchSampler(_BatchBuffers):
+    """ggms_sample_batch_typed: BatchSampler's layers with khop_typed as the sampler.  One slot, one pipeline.
+    type_fanouts: num_layer rows of num_type fanouts, indexed by layer id like `fanouts`; the batch's fanouts are the
+    rows' sums."""
+
+    def __init__(self, graph, edge_type, type_fanouts, batch_size, device="cuda", direct_table=True, max_seeds=None):
+        rows = [[int(k) for k in row] for row in type_fanouts]
+        self.num_type = len(rows[0])
+        assert all(len(row) == self.num_type for row in rows), "type_fanouts: every layer has one fanout per edge type"
+        self._init_capacity(graph, [sum(row) for row in rows], KHOP_TYPED,
+                            int(batch_size * 1.25) + 1 if max_seeds is None else int(max_seeds), None, None)
+        _require_gpu(_u8(edge_type))
+        self.edge_type, self.type_fanouts = edge_type, rows
+        self._tf = (C.c_uint32 * (self.L * self.num_type))(*[k for row in rows for k in row])
+        self._typed = _lib.Typed(edge_type.data_ptr(), self.num_type, self._tf)
+        self.ht = OrderedHashTable(self.max_unique, device, num_node=graph.c.num_node if direct_table else None)
+        self.states = None
+        (self.row, self._rows), (self.col, self._cols) = self._layer_buffers(1, device), self._layer_buffers(1, device)
+        self.eid, self._eids = self._layer_buffers(1, device)
+        self.etype = [torch.empty(max(1, e), dtype=torch.uint8, device=device) for e in self.max_edges]
+        self._etypes = (C.c_void_p * self.L)(*[t.data_ptr() for t in self.etype])
+        self.counts = torch.zeros(COUNTS_SAMPLE_WORDS(self.L), dtype=torch.int64, device=device)
+        wsb = lib().ggms_sample_batch_typed_workspace_bytes(self.max_seeds, self._f, self.L, self.num_type,
+                                                            C.byref(self._extra))
+        self.ws = _workspace(wsb, device)
+        self._n = 0
+
+    def sample(self, seeds, salt=0):
+        """Enqueue one batch; salt: the batch salt (layer i samples under fmix32(salt + 0x9e3779b9 * (i + 1)))."""
+        _i32(seeds)
+        n = self._n = seeds.numel()
+        assert n <= self.max_seeds
+        self._extra.labor_salt = salt & 0xFFFFFFFF
+        check(lib().ggms_sample_batch_typed(C.byref(self.graph.c), _ptr(seeds), n, self._f, self.L, C.byref(self.ht.c),
+                                            self._rows, self._cols, self._eids, self._etypes, _ptr(self.counts),
+                                            C.byref(self._typed), C.byref(self._extra), _ptr(self.ws),
+                                            self.ws.numel() * 4, _stream()), "ggms_sample_batch_typed")
+
+    def seed_ids(self):
+        """Local ids of the raw seeds of the last batch (ggms_sample_batch_seed_ids)."""
+        p = C.c_void_p()
+        check(lib().ggms_sample_batch_seed_ids(KHOP_TYPED, self._n, self._f, self.L, C.byref(self._extra),
+                                               _ptr(self.ws), C.byref(p)), "ggms_sample_batch_seed_ids")
+        off = (p.value - self.ws.data_ptr()) // 4
+        return self.ws[off: off + self._n]
+
+    def result(self):
+        """Sync and slice the outputs: BatchSampler.result()'s, each layer with its `eid` and `etype`."""
+        c, layers = self._sliced("ggms_sample_batch_typed")
+        for i, lay in enumerate(layers):
+            lay["eid"] = self.eid[i][:c[COUNT_EDGES(i)]]
+            lay["etype"] = self.etype[i][:c[COUNT_EDGES(i)]]
+        return dict(layers=layers, input_nodes=self.ht.n2o[:c[COUNT_INPUT(self.L)]])
 
 
 def dynamic_cache_reset(stamps):

@@ -145,6 +145,11 @@ def get_graph_link_time(batch_key):
     return _get("samgraph_get_graph_link_time", batch_key)
 
 
+def get_graph_edge_type(batch_key, layer_idx):
+    """sample_type khop_typed: the relation of every edge of the layer, edge_type[get_graph_edge_ids] (uint8)."""
+    return _get("samgraph_get_graph_edge_type", batch_key, layer_idx)
+
+
 def get_graph_link_edge_ids(batch_key):
     """The positive edge ids (CSR positions) of a link_prediction batch, in the order of get_graph_link_pairs."""
     return _get("samgraph_get_graph_link_edge_ids", batch_key)
