@@ -730,6 +730,45 @@ int ggms_edge_positions(const ggms_graph_t *graph, uint64_t num_edge, const ggms
                         void *workspace, size_t workspace_bytes, ggms_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Induced subgraph of a node set (an extension; DGL / PyG: ShaDowKHopSampler, GraphSAINT's node sampler, Cluster-GCN):
+ * every edge of the graph with BOTH ends in the set, as one COO over the set's local ids.  A post-pass behind a finished
+ * batch (nodes = the batch's n2o, num_nodes_dev = counts_dev + GGMS_COUNT_INPUT(L)), behind any sampler.
+ *   nodes[0, n)     n = num_nodes_dev ? *num_nodes_dev : max_nodes (n <= max_nodes; a larger count is read as max_nodes)
+ *   loc(v)          = min { j : nodes[j] == v } for ids v < graph->num_node; an entry that is GGMS_EMPTY_KEY or >= num_node
+ *                   owns nothing and is nobody's target
+ *   owners          the positions j with loc(nodes[j]) == j (a repeated id: only its first position owns the list)
+ *   edges, in order for owner j ascending, for p = indptr[u] .. indptr[u + 1] - 1 ascending (u = nodes[j]): if
+ *                   w = indices[p] has a loc, the edge (row = loc(w), col = j, eid = p) -- row is the neighbour, col the
+ *                   node whose list was read, as ggms_sample_batch writes them.  Parallel edges are each kept, with their
+ *                   own position; self-loops are kept.
+ *   outputs         row, col, eid (eid may be NULL): the first min(M, max_edges) edges of that order; nothing is written
+ *                   behind them and nothing past max_edges.  out_counts_dev[0] = M, the number of induced edges that
+ *                   exist (M > max_edges: the caller's overflow test -- no status bit); [1] = the list entries walked.
+ *   local_of        graph->num_node 32-bit words owned by the caller, GGMS_EMPTY_KEY everywhere on entry (once:
+ *                   ggms_induced_map_init) and again on return: the call marks with atomicMin(local_of[nodes[j]], j) and
+ *                   restores the words of its nodes in its last launch.  One map serves one call at a time.
+ *   arguments       refused with GGMS_ERR_INVALID and a message, before any device call: a null array, a workspace below
+ *                   ggms_induced_edges_workspace_bytes(max_nodes, num_edge), num_edge (= indptr[num_node]) >= 2^32 - 1,
+ *                   max_nodes >= 2^32 - 1024, eid != NULL on a sharded graph (a position is an index into ONE CSR; with
+ *                   eid == NULL a sharded graph is read through its view, like ggms_khop_closure).  max_nodes == 0:
+ *                   GGMS_OK, both count words zeroed.
+ * A pure function of (graph, nodes[0, n)): the result does not depend on the grid.  No allocation, no synchronisation,
+ * no host round trip; the number of launches and memsets depends on (max_nodes, num_edge) only.  Two edge-tiled walks
+ * over the owners' lists (a hub is cut by edge), one random 4-byte read of local_of per list entry in each.
+ * ------------------------------------------------------------------------- */
+size_t ggms_induced_edges_workspace_bytes(size_t max_nodes, uint64_t num_edge);
+int ggms_induced_map_init(uint32_t *local_of, size_t num_node, ggms_stream_t stream);
+int ggms_induced_edges(const ggms_graph_t *graph, uint64_t num_edge, const ggms_id_t *nodes, size_t max_nodes,
+                       const uint64_t *num_nodes_dev /* may be NULL */, uint32_t *local_of, ggms_id_t *row,
+                       ggms_id_t *col, ggms_id_t *eid /* may be NULL */, size_t max_edges,
+                       uint64_t *out_counts_dev /* 2 words */, void *workspace, size_t workspace_bytes,
+                       ggms_stream_t stream);
+/* *kept_dev = min(counts_dev[0], max_edges): the number of entries a call with these count words wrote, for a consumer
+ * that walks them on the device (a row gather over eid takes its count from device memory and does not clamp it).  One
+ * launch of one wave, not capped by GGMS_DEBUG_GRID_CAP. */
+int ggms_induced_kept(const uint64_t *counts_dev, size_t max_edges, uint64_t *kept_dev, ggms_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * arch4's batch with early feature prefetch -- DoGPUSampleDyCache (cuda/cuda_loops.cc:294-524).  The layers of
  * ggms_sample_batch, except:
  *   - after the second-to-last layer's table fill, every neighbour of every node entered so far (n2o[0, k)) is

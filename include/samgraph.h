@@ -155,6 +155,25 @@ void samgraph_get_store_state(samgraph_tensor_t *out);
 void samgraph_get_graph_edge_ids(uint64_t key, int layer_idx, samgraph_tensor_t *out);
 void samgraph_get_graph_edge_feat(uint64_t key, int layer_idx, samgraph_tensor_t *out);
 void samgraph_get_graph_link_edge_ids(uint64_t key, samgraph_tensor_t *out);
+/* Extensions for config key induced_subgraph = on (arch1, one CSR, both tasks, any number of pipelines, both table
+ * layouts; refused by name with every other deployment, use_dist_graph, khop2, khop_temporal and exclude_seed_edges other
+ * than none).  Behind the sampler, ggms_induced_edges (include/ggms.h) computes the subgraph the batch's input nodes
+ * induce: EVERY edge of the graph with both ends among them (ShaDow-GNN, GraphSAINT's node sampler, Cluster-GCN), one COO
+ * over the batch's local ids -- rows of samgraph_get_graph_feat, like every layer's -- in (col, CSR position) order.
+ *   samgraph_get_graph_num_induced(key)          M, the number of induced edges
+ *   samgraph_get_graph_induced_row / _col(key)   M local ids each: row = the neighbour, col = the node whose list holds
+ *     the edge (samgraph_get_graph_row's convention and dtype).  Parallel edges are each there, self-loops too.
+ *   samgraph_get_graph_induced_edge_ids(key)     M CSR positions (each edge its own), the id space of edge_ids
+ *   samgraph_get_graph_induced_edge_feat(key)    with edge_feat = on as well: (M, EDGE_FEAT_DIM), row k = table[ids[k]]
+ * induced_max_edges (optional, 1 .. 2^32 - 1025): the capacity of a batch's induced arrays.  Default: the sum of the
+ * layers' edge capacities (what the sampled layers could hold at most), capped at NUM_EDGE -- a capacity, not a
+ * measurement.  A batch that induces more is fatal, with the key and the count it needed.
+ * Without the key nothing runs and nothing is allocated; the accessors are then fatal. */
+size_t samgraph_get_graph_num_induced(uint64_t key);
+void samgraph_get_graph_induced_row(uint64_t key, samgraph_tensor_t *out);
+void samgraph_get_graph_induced_col(uint64_t key, samgraph_tensor_t *out);
+void samgraph_get_graph_induced_edge_ids(uint64_t key, samgraph_tensor_t *out);
+void samgraph_get_graph_induced_edge_feat(uint64_t key, samgraph_tensor_t *out);
 /* Extensions for _sample_type 9 (khop_temporal; config key temporal_pick = uniform | recent; arch1 with task =
  * link_prediction and one CSR -- every other deployment, task = node_classification, use_dist_graph and
  * exclude_seed_edges other than none are refused by name).  The dataset carries edge_time.bin: NUM_EDGE uint32, one per

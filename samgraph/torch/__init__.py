@@ -11,4 +11,6 @@ from xgnn_amd.torch import (config, init, start, num_class, feat_dim, num_epoch,
                             get_dataset_label, get_graph_input_nodes, get_graph_output_nodes, load_subtensor,
                             notify_sampler_ready, wait_for_sampler_ready, get_graph_coo,
                             update_graph_feat, get_store_feat, get_store_state,
-                            get_graph_edge_ids, get_graph_edge_feat, get_graph_link_edge_ids)
+                            get_graph_edge_ids, get_graph_edge_feat, get_graph_link_edge_ids,
+                            get_graph_induced_row, get_graph_induced_col, get_graph_induced_edge_ids,
+                            get_graph_induced_edge_feat, get_graph_num_induced)

@@ -168,6 +168,10 @@ SYMBOLS = {
     "ggms_edge_positions_workspace_bytes": (_sz, [C.POINTER(_sz), _u32]),
     "ggms_edge_positions": (_i, [C.POINTER(Graph), _u64, _vp, _sz, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
                                  C.POINTER(_sz), _u32, _vp, _vp, _sz, _vp]),
+    "ggms_induced_edges_workspace_bytes": (_sz, [_sz, _u64]),
+    "ggms_induced_map_init": (_i, [_vp, _sz, _vp]),
+    "ggms_induced_edges": (_i, [C.POINTER(Graph), _u64, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "ggms_induced_kept": (_i, [_vp, _sz, _vp, _vp]),
     "ggms_hashtable_num_buckets": (_sz, [_sz]),
     "ggms_hashtable_init": (_i, [C.POINTER(HashTable), _vp]),
     "ggms_hashtable_reset": (_i, [C.POINTER(HashTable), _vp]),

@@ -117,6 +117,10 @@ SAMGRAPH_SYMBOLS = {
     "samgraph_get_graph_num_excluded": (_sz, [_u64]),
     "samgraph_get_graph_edge_ids": (None, [_u64, _i, _TP]), "samgraph_get_graph_edge_feat": (None, [_u64, _i, _TP]),
     "samgraph_get_graph_link_edge_ids": (None, [_u64, _TP]),
+    "samgraph_get_graph_num_induced": (_sz, [_u64]),
+    "samgraph_get_graph_induced_row": (None, [_u64, _TP]), "samgraph_get_graph_induced_col": (None, [_u64, _TP]),
+    "samgraph_get_graph_induced_edge_ids": (None, [_u64, _TP]),
+    "samgraph_get_graph_induced_edge_feat": (None, [_u64, _TP]),
     "samgraph_get_graph_edge_time": (None, [_u64, _i, _TP]), "samgraph_get_graph_node_cut": (None, [_u64, _TP]),
     "samgraph_get_graph_link_time": (None, [_u64, _TP]),
     "samgraph_get_graph_edge_type": (None, [_u64, _i, _TP]),
@@ -180,6 +184,7 @@ class SamGraphBasics(object):
         return self.C_LIB_CTYPES.samgraph_feat_row_bytes(1 if delivered else 0)
     def num_negative(self): return self.C_LIB_CTYPES.samgraph_num_negative()
     def get_graph_num_excluded(self, key): return self.C_LIB_CTYPES.samgraph_get_graph_num_excluded(key)
+    def get_graph_num_induced(self, key): return self.C_LIB_CTYPES.samgraph_get_graph_num_induced(key)
     def num_epoch(self): return self.C_LIB_CTYPES.samgraph_num_epoch()
     def steps_per_epoch(self): return self.C_LIB_CTYPES.samgraph_steps_per_epoch()
     def get_next_batch(self): return self.C_LIB_CTYPES.samgraph_get_next_batch()

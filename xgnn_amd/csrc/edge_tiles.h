@@ -60,9 +60,19 @@ __device__ __forceinline__ uint64_t wave_find_node(const uint32_t *pre, uint64_t
 // elsewhere).  The sink may use barriers and LDS of its own; the LDS staged here is not rewritten before every lane
 // has returned from it (each round ends with the walk's own barrier).
 // Precondition: E < 2^32 -- pre and the staged copies are 32-bit, edge positions 64-bit.
-template <typename Sink>
-__device__ __forceinline__ void walk_edge_tiles(const GraphView &g, const uint32_t *nodes, uint64_t F,
-                                                const uint32_t *__restrict__ pre, uint64_t E, Sink sink) {
+//
+// Two sink flavours, one body (walk_edge_tiles_any; kWhere is a compile-time switch, so the plain flavour compiles to
+// what it did before the second one existed):
+//   walk_edge_tiles        sink(v, have, cur) as above; every list node is a valid id.
+//   walk_edge_tiles_where  sink(v, have, cur, own, ent): own[k] = the index i of the edge's owner in `nodes`, ent[k] = the
+//                          address the neighbour id was loaded from -- its list offset is ent[k] minus the list's start,
+//                          its CSR position ent[k] - g.indices on an unsharded graph, with no further load.  The list may
+//                          hold ids that own no edges (pre[i + 1] == pre[i]): an id >= num_node among them (a padding
+//                          word, GGMS_EMPTY_KEY) is never looked up in indptr.
+template <bool kWhere, typename Sink>
+__device__ __forceinline__ void walk_edge_tiles_any(const GraphView &g, const uint32_t *nodes, uint64_t F,
+                                                    const uint32_t *__restrict__ pre, uint64_t E, uint32_t num_node,
+                                                    Sink sink) {
   __shared__ uint32_t s_pre[kWin + 1];
   __shared__ const uint32_t *s_ptr[kWin];
   __shared__ uint64_t s_lo;
@@ -85,7 +95,12 @@ __device__ __forceinline__ void walk_edge_tiles(const GraphView &g, const uint32
         s_pre[j] = (uint32_t)p;
         if (p < e1) {
           uint32_t len;
-          s_ptr[j] = g.neighbours(nodes[i], len);
+          if constexpr (kWhere) {
+            const uint32_t u = nodes[i];
+            s_ptr[j] = u < num_node ? g.neighbours(u, len) : nullptr; // (an id out of range owns no edge: never read)
+          } else {
+            s_ptr[j] = g.neighbours(nodes[i], len);
+          }
         }
         wlen += kBlock;
         if (__syncthreads_or(p >= e1) || wlen == kWin) break;
@@ -95,10 +110,16 @@ __device__ __forceinline__ void walk_edge_tiles(const GraphView &g, const uint32
       const uint64_t s_end = s_pre[wlen];
       const uint64_t stop = s_end < e1 ? s_end : e1;
       uint32_t v[kPerThread], have = 0;
+      [[maybe_unused]] uint32_t own[kPerThread];
+      [[maybe_unused]] const uint32_t *ent[kPerThread];
 #pragma unroll
       for (uint32_t k = 0; k < kPerThread; ++k) {
         const uint64_t e = cur + k * kBlock + threadIdx.x;
         v[k] = 0;
+        if constexpr (kWhere) {
+          own[k] = 0;
+          ent[k] = nullptr;
+        }
         if (e < stop) {
           uint32_t lo = 0, len = wlen; // the last staged node that starts at or before e (s_pre[0] <= cur <= e)
           while (len > 1) {
@@ -107,15 +128,33 @@ __device__ __forceinline__ void walk_edge_tiles(const GraphView &g, const uint32
             len -= half;
           }
           v[k] = s_ptr[lo][(uint32_t)e - s_pre[lo]];
+          if constexpr (kWhere) {
+            own[k] = (uint32_t)nw + lo;
+            ent[k] = s_ptr[lo] + ((uint32_t)e - s_pre[lo]);
+          }
           have |= 1u << k;
         }
       }
-      sink(v, have, cur);
+      if constexpr (kWhere) sink(v, have, cur, own, ent);
+      else sink(v, have, cur);
       __syncthreads(); // every read of s_pre / s_ptr / s_lo is done before the next round restages them
       cur = stop;
       nw += wlen;
     }
   }
+}
+
+template <typename Sink>
+__device__ __forceinline__ void walk_edge_tiles(const GraphView &g, const uint32_t *nodes, uint64_t F,
+                                                const uint32_t *__restrict__ pre, uint64_t E, Sink sink) {
+  walk_edge_tiles_any<false>(g, nodes, F, pre, E, 0u, sink);
+}
+// F < 2^32 (own is 32-bit)
+template <typename Sink>
+__device__ __forceinline__ void walk_edge_tiles_where(const GraphView &g, const uint32_t *nodes, uint64_t F,
+                                                      const uint32_t *__restrict__ pre, uint64_t E, uint32_t num_node,
+                                                      Sink sink) {
+  walk_edge_tiles_any<true>(g, nodes, F, pre, E, num_node, sink);
 }
 
 } // namespace ggms

@@ -420,6 +420,44 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
       fatal(__FILE__, __LINE__, key + " with _sample_type 5 (khop2) is not built: khop2 permutes indices in place, a "
                                 "position names another edge after every batch");
   }
+  if (kv.count("induced_subgraph") || kv.count("induced_max_edges")) { // extension: the subgraph a batch's input nodes induce
+    if (kv.count("induced_subgraph") && kv["induced_subgraph"] != "on" && kv["induced_subgraph"] != "off")
+      fatal(__FILE__, __LINE__, "induced_subgraph = " + kv["induced_subgraph"] + ": on or off (the default)");
+    cfg.induced = kv.count("induced_subgraph") && kv["induced_subgraph"] == "on";
+    if (kv.count("induced_max_edges") && !cfg.induced)
+      fatal(__FILE__, __LINE__, "induced_max_edges without induced_subgraph = on: the key sizes the induced arrays only");
+  }
+  if (cfg.induced) {
+    static const char *const arch_names[] = {"arch0", "arch1", "arch2", "arch3", "arch4", "arch5", "arch6", "arch7"};
+    if (cfg.arch != kArch1)
+      fatal(__FILE__, __LINE__, std::string(arch_names[cfg.arch]) + ": induced_subgraph is not built: the induced edges are "
+                                "computed behind arch1's sampling chain and travel through no hand-off or queue");
+    if (cfg.use_dist_graph)
+      fatal(__FILE__, __LINE__, "induced_subgraph with use_dist_graph is not built: the induced edges come with their "
+                                "positions in ONE CSR, a sharded topology has none");
+    if (cfg.sample_type == GGMS_KHOP2)
+      fatal(__FILE__, __LINE__, "induced_subgraph with _sample_type 5 (khop2) is not built: khop2 permutes indices in "
+                                "place, a position names another edge after every batch");
+    if (cfg.Temporal())
+      fatal(__FILE__, __LINE__, "induced_subgraph with _sample_type 9 (khop_temporal) is not built: an induced edge may lie "
+                                "after a node's cut-off, which leaks the future into the batch");
+    if (cfg.exclude_seed_edges)
+      fatal(__FILE__, __LINE__, "induced_subgraph with exclude_seed_edges = " + kv["exclude_seed_edges"] + " is not built: "
+                                "the filter does not compact an id stream, and the induced subgraph of a link batch holds "
+                                "its positive edges; take exclude_seed_edges = none and drop them in the trainer");
+    if (kv.count("induced_max_edges")) {
+      unsigned long long v = 0;
+      try {
+        size_t used = 0;
+        v = std::stoull(kv["induced_max_edges"], &used);
+        if (used != kv["induced_max_edges"].size() || kv["induced_max_edges"][0] == '-') v = 0;
+      } catch (...) { v = 0; }
+      if (v == 0 || v >= 0xffffffffull - 1023ull)
+        fatal(__FILE__, __LINE__, "induced_max_edges = " + kv["induced_max_edges"] + ": the capacity of a batch's induced "
+                                  "arrays, 1 .. 2^32 - 1025 edges");
+      cfg.induced_max_edges = (size_t)v;
+    }
+  }
   if (cfg.arch == kArch4) { // DoGPUSampleDyCache's switch (cuda/cuda_loops.cc:347-377) and what it needs
     if (cfg.sample_type != GGMS_KHOP0 && cfg.sample_type != GGMS_KHOP1 && cfg.sample_type != GGMS_WEIGHTED_KHOP)
       fatal(__FILE__, __LINE__, "arch4: _sample_type " + std::to_string(cfg.sample_type) + " is not supported: the "
@@ -622,6 +660,9 @@ void Engine::LoadDataset() {
   if (cfg.edge_ids && ds.num_edge >= 0xffffffffull)
     fatal(__FILE__, __LINE__, std::string(cfg.edge_feat ? "edge_feat" : "edge_ids") + ": " + std::to_string(ds.num_edge) +
                                   " edges: edge ids are 32-bit positions, at most 2^32 - 2 of them");
+  if (cfg.induced && ds.num_edge >= 0xffffffffull)
+    fatal(__FILE__, __LINE__, "induced_subgraph: " + std::to_string(ds.num_edge) + " edges: the induced edges come with "
+                                  "32-bit positions, at most 2^32 - 2 of them");
   if (cfg.edge_feat) { // the edge table: NUM_EDGE rows in CSR order
     if (!meta.count("EDGE_FEAT_DIM") || meta["EDGE_FEAT_DIM"] == 0)
       fatal(__FILE__, __LINE__, "edge_feat: meta.txt lacks EDGE_FEAT_DIM (elements per row of edge_feat.bin)");
@@ -736,8 +777,24 @@ void Engine::DataInit() {
     ComputeBounds();
     QueueInit();
   }
+  if (cfg.induced) ResolveInducedCapacity();
   prof.LogInit(/*kLogInitL2LoadDataset*/ 6, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
   data_ready_ = true;
+}
+
+// induced_subgraph: how many edges a batch's induced arrays hold.  Without the key `induced_max_edges`: the sum of the
+// layers' edge capacities, capped at NUM_EDGE -- a CAPACITY default, not a measurement: the sampled layers hold at most
+// that many edges among the same nodes, the induced subgraph holds every edge among them and may hold more (a dense
+// neighbourhood; the batch then dies by name, with the count it needed).  Host arithmetic, known after data_init.
+void Engine::ResolveInducedCapacity() {
+  ComputeBounds();
+  size_t sum = 0;
+  for (size_t m : max_edges_) sum += m;
+  const size_t dflt = std::max<size_t>(std::min<size_t>(std::min(sum, ds.num_edge), 0xffffffffull - 1025ull), 1);
+  induced_max_edges_ = cfg.induced_max_edges ? cfg.induced_max_edges : dflt;
+  log_info("induced_subgraph: induced_max_edges = " + std::to_string(induced_max_edges_) +
+           (cfg.induced_max_edges ? " (config)" : " (default: the layers' edge capacities, " + std::to_string(sum) +
+                                                      ", capped at NUM_EDGE = " + std::to_string(ds.num_edge) + ")"));
 }
 
 static double ipc_timeout_s();
@@ -1222,6 +1279,14 @@ void Engine::SampleInit(int worker_id, const std::string &ctx) {
     SAM_CHECK(eid_ws_bytes_ > 0, "edge_ids: the batch bounds are out of ggms_edge_positions' range");
     for (Pipe &P : pipes_) SAM_HIP(hipMalloc(&P.eid_ws, eid_ws_bytes_));
   }
+  if (cfg.induced) { // one membership map (4 B x num_node, filled once: every call restores it) and one workspace per pipeline
+    induced_ws_bytes_ = ggms_induced_edges_workspace_bytes(max_unique_, ds.num_edge);
+    for (Pipe &P : pipes_) {
+      SAM_HIP(hipMalloc((void **)&P.induced_map, std::max<size_t>(ds.num_node, 1) * 4));
+      SAM_GGMS(ggms_induced_map_init(P.induced_map, ds.num_node, stream_));
+      SAM_HIP(hipMalloc(&P.induced_ws, induced_ws_bytes_));
+    }
+  }
   SAM_HIP(hipStreamSynchronize(stream_));
   prof.Resize(cfg.num_epoch, num_global_step_);
   if (cfg.UsePresample()) { // dist_engine.cc:455-466: worker 0 ranks the nodes, everybody waits
@@ -1622,6 +1687,18 @@ void Engine::TrainInit(int worker_id, const std::string &ctx) {
         if (cfg.edge_feat) SAM_HIP(hipMalloc(&b->efeat[i], std::max<size_t>(max_edges_[i] * ds.edge_feat_row_bytes(), 16)));
       }
     }
+    if (cfg.induced) { // the induced COO, its positions, with edge_feat its rows; the count words and their host copy
+      const size_t cap = std::max<size_t>(induced_max_edges_, 4);
+      for (uint32_t **p : {&b->ind_row, &b->ind_col, &b->ind_eid}) {
+        SAM_HIP(hipMalloc((void **)p, cap * 4));
+        SAM_HIP(hipMemset(*p, 0, cap * 4));
+      }
+      if (cfg.edge_feat) SAM_HIP(hipMalloc(&b->ind_efeat, std::max<size_t>(cap * ds.edge_feat_row_bytes(), 16)));
+      SAM_HIP(hipMalloc((void **)&b->ind_counts_dev, 4 * 8));
+      SAM_HIP(hipMemset(b->ind_counts_dev, 0, 4 * 8));
+      SAM_HIP(hipHostMalloc((void **)&b->ind_counts, 2 * 8));
+      std::memset(b->ind_counts, 0, 2 * 8);
+    }
     if (cfg.Temporal()) {
       SAM_HIP(hipMalloc((void **)&b->seed_time, std::max<size_t>(max_seeds_, 4) * 4));
       SAM_HIP(hipMalloc((void **)&b->node_cut, std::max<size_t>(max_unique_, 4) * 4));
@@ -1859,6 +1936,17 @@ void Engine::SampleInto(Batch *b, Pipe &P) {
     SAM_GGMS(ggms_edge_positions(&graph_, ds.num_edge, s.input_nodes, max_unique_, s.row.data(), s.col.data(),
                                  b->eid.data(), max_edges_.data(), L, s.counts_dev, P.eid_ws, eid_ws_bytes_, P.stream));
   }
+  if (cfg.induced) {
+    // Every edge of the graph among the batch's input nodes: a post-pass over the finished node list, on the pipeline's
+    // map and workspace, same stream, in front of ev_sampled like everything that writes the batch.  The two counts go to
+    // the host here, behind the call: whichever stream completes the batch (ev_done) is ordered behind ev_sampled.
+    SAM_GGMS(ggms_induced_edges(&graph_, ds.num_edge, s.input_nodes, max_unique_, s.counts_dev + GGMS_COUNT_INPUT(L),
+                                P.induced_map, b->ind_row, b->ind_col, b->ind_eid, induced_max_edges_, b->ind_counts_dev,
+                                P.induced_ws, induced_ws_bytes_, P.stream));
+    SAM_HIP(hipMemcpyAsync(b->ind_counts, b->ind_counts_dev, 2 * 8, hipMemcpyDeviceToHost, P.stream));
+    if (cfg.edge_feat) // the rows the gather may read: never more than were written, whatever M says
+      SAM_GGMS(ggms_induced_kept(b->ind_counts_dev, induced_max_edges_, b->ind_counts_dev + 2, P.stream));
+  }
   SAM_HIP(hipMemsetAsync(s.counts_dev + GGMS_COUNT_MISS(L), 0, 8, P.stream)); // the trainer's miss count starts at 0
   SAM_HIP(hipEventRecord(b->ev_sampled, P.stream));
 }
@@ -1916,6 +2004,9 @@ void Engine::EnqueueGather(Batch *b, hipStream_t ss) {
     for (uint32_t i = 0; i < L; ++i)
       SAM_GGMS(ggms_gather_scatter(b->efeat[i], d_edge_feat_, b->eid[i], nullptr, max_edges_[i],
                                    b->trainer.counts_dev + GGMS_COUNT_EDGES(i), ds.edge_feat_dim, ds.edge_feat_dtype, xs));
+  if (cfg.edge_feat && cfg.induced) // ... and once more over the induced edges' ids (the count: min(M, capacity))
+    SAM_GGMS(ggms_gather_scatter(b->ind_efeat, d_edge_feat_, b->ind_eid, nullptr, induced_max_edges_, b->ind_counts_dev + 2,
+                                 ds.edge_feat_dim, ds.edge_feat_dtype, xs));
   // khop_temporal: the sampled edges' times, edge_time[eid], beside the edge rows (dim 1, the device edge count)
   if (cfg.Temporal())
     for (uint32_t i = 0; i < L; ++i)
@@ -2080,6 +2171,11 @@ void Engine::Finish(Batch *b, Batch *prev) {
     fatal(__FILE__, __LINE__, "arch4: batch " + std::to_string(b->key) + ": the expansion needed " +
                                   std::to_string(b->counts[GGMS_COUNT_EXPANSION(L)]) + " edges, capacity " +
                                   std::to_string(max_prefetch_edges_) + " (config key prefetch_max_edges)");
+  if (cfg.induced && b->ind_counts[0] > induced_max_edges_)
+    fatal(__FILE__, __LINE__, "induced_subgraph: batch " + std::to_string(b->key) + ": its " + std::to_string(b->num_input) +
+                                  " input nodes induce " + std::to_string(b->ind_counts[0]) + " edges, capacity " +
+                                  std::to_string(induced_max_edges_) + " (config key induced_max_edges: at least " +
+                                  std::to_string(b->ind_counts[0]) + ")");
   CheckBatchStatus(b->counts[GGMS_COUNT_STATUS(L)], b->key);
   if (cfg.link_prediction) { // negatives whose eight candidates were all rejected, per epoch
     link_forced_ += b->counts[GGMS_COUNT_LINK_FORCED(L)];

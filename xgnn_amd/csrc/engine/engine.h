@@ -125,6 +125,13 @@ struct RunConfig {
   uint32_t num_edge_type = 0; // type_fanout.size() / num_layer; LoadDataset checks it against meta.txt's NUM_EDGE_TYPE
   bool Typed() const { return sample_type == GGMS_KHOP_TYPED; }
   bool SamplerEmitsEdgeIds() const { return Temporal() || Typed(); } // ggms_edge_positions is not enqueued
+  // extension (config keys `induced_subgraph` = on, `induced_max_edges`; arch1, one CSR, not khop2 / khop_temporal, no
+  // exclude_seed_edges): every batch also carries the subgraph its input nodes induce -- every edge of the graph with
+  // both ends among them, one COO over the batch's local ids with the edges' CSR positions (ggms_induced_edges behind
+  // the sampler), and with edge_feat the edge table's rows under those.  induced_max_edges 0: the default, the sum of the
+  // layers' edge capacities capped at NUM_EDGE (Engine::ResolveInducedCapacity)
+  bool induced = false;
+  size_t induced_max_edges = 0;
   size_t staged_serial_epochs = 0; // host-staged path: the first N epochs run the reference's serial, per-phase-timed sequence
   size_t staged_serial_steps = 0;  // ... or this worker's first N batches
   // worker 0 ranks the nodes at init: pre_sample (sampled input nodes) or presample_static (L-hop closures)
@@ -247,6 +254,13 @@ struct Batch {
   std::vector<uint32_t *> etime;
   // khop_typed: per layer the sampled edges' types, written by the sampler beside eid.  Empty with every other sampler.
   std::vector<uint8_t *> etype;
+  // induced_subgraph: the induced COO and its edges' CSR positions (induced_max_edges words each), with edge_feat the edge
+  // table's rows under them; three device words -- ggms_induced_edges' two counts [M, list entries walked] and
+  // min(M, induced_max_edges), the gather's row count -- and the pinned host copy of the first two, valid with the
+  // counts.  Null without the key.
+  uint32_t *ind_row = nullptr, *ind_col = nullptr, *ind_eid = nullptr;
+  void *ind_efeat = nullptr;
+  uint64_t *ind_counts_dev = nullptr, *ind_counts = nullptr;
   uint64_t num_miss = 0;
   hipEvent_t ev_seeds = nullptr, ev_start = nullptr, ev_sampled = nullptr, ev_xstart = nullptr, ev_done = nullptr;
   // arch6 with `gpu_extract` off: the host-staged miss path (dist_loops.cc:1015-1207)
@@ -422,7 +436,12 @@ class Engine {
     void *eid_ws = nullptr;  // edge_ids: ggms_edge_positions' workspace
     uint64_t *cut_table = nullptr; // khop_temporal: the pipeline's cut table (8 B x num_node, zeroed once) and the stamp of
     uint32_t stamp = 0;            // its last batch
+    uint32_t *induced_map = nullptr; // induced_subgraph: the pipeline's membership map (4 B x num_node, all EMPTY between
+    void *induced_ws = nullptr;      // batches) and ggms_induced_edges' workspace
   };
+  size_t induced_ws_bytes_ = 0;
+  size_t induced_max_edges_ = 0; // induced_subgraph: the capacity of a batch's induced arrays (ResolveInducedCapacity)
+  void ResolveInducedCapacity();
   size_t drop_ws_bytes_ = 0;
   size_t eid_ws_bytes_ = 0;    // edge_ids: ggms_edge_positions' workspace (Pipe::eid_ws)
   void *d_edge_feat_ = nullptr; // edge_feat: the edge table in HBM

@@ -166,6 +166,40 @@ void samgraph_get_graph_edge_feat(uint64_t key, int l, samgraph_tensor_t *out) {
   fill(out, b->efeat[l], (int64_t)b->counts[GGMS_COUNT_EDGES(l)], (int64_t)E.ds.edge_feat_dim, 2, E.ds.edge_feat_dtype,
        E.batch_device_type(), E.trainer_device());
 }
+// config key induced_subgraph: the subgraph the batch's input nodes induce -- num_induced edges (row = the neighbour,
+// col = the node whose list was read; local ids, rows of get_graph_feat), their CSR positions, and with edge_feat the edge
+// table's rows under those
+static sam::Batch *induced_batch(uint64_t key, const char *who, bool need_feat = false) {
+  auto &E = Engine::Get();
+  if (!E.cfg.induced) sam::fatal(__FILE__, __LINE__, std::string(who) + " needs the config key induced_subgraph = on");
+  if (need_feat && !E.cfg.edge_feat)
+    sam::fatal(__FILE__, __LINE__, std::string(who) + " needs the config key edge_feat = on (beside induced_subgraph = on)");
+  return E.Current(key);
+}
+size_t samgraph_get_graph_num_induced(uint64_t key) {
+  return induced_batch(key, "samgraph_get_graph_num_induced")->ind_counts[0];
+}
+void samgraph_get_graph_induced_row(uint64_t key, samgraph_tensor_t *out) {
+  auto *b = induced_batch(key, "samgraph_get_graph_induced_row");
+  auto &E = Engine::Get();
+  fill(out, b->ind_row, (int64_t)b->ind_counts[0], 1, 1, GGMS_I32, E.batch_device_type(), E.trainer_device());
+}
+void samgraph_get_graph_induced_col(uint64_t key, samgraph_tensor_t *out) {
+  auto *b = induced_batch(key, "samgraph_get_graph_induced_col");
+  auto &E = Engine::Get();
+  fill(out, b->ind_col, (int64_t)b->ind_counts[0], 1, 1, GGMS_I32, E.batch_device_type(), E.trainer_device());
+}
+void samgraph_get_graph_induced_edge_ids(uint64_t key, samgraph_tensor_t *out) {
+  auto *b = induced_batch(key, "samgraph_get_graph_induced_edge_ids");
+  auto &E = Engine::Get();
+  fill(out, b->ind_eid, (int64_t)b->ind_counts[0], 1, 1, GGMS_I32, E.batch_device_type(), E.trainer_device());
+}
+void samgraph_get_graph_induced_edge_feat(uint64_t key, samgraph_tensor_t *out) {
+  auto *b = induced_batch(key, "samgraph_get_graph_induced_edge_feat", true);
+  auto &E = Engine::Get();
+  fill(out, b->ind_efeat, (int64_t)b->ind_counts[0], (int64_t)E.ds.edge_feat_dim, 2, E.ds.edge_feat_dtype,
+       E.batch_device_type(), E.trainer_device());
+}
 // task = link_prediction: the batch's positive edge ids (CSR positions, the id space of the edge ids above)
 void samgraph_get_graph_link_edge_ids(uint64_t key, samgraph_tensor_t *out) {
   auto &E = Engine::Get();

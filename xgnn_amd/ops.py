@@ -302,6 +302,49 @@ def edge_positions(graph, rows, cols, counts, id_map=None, max_edges=None, eids=
     return eids
 
 
+def induced_map(num_node, device="cuda"):
+    """The membership map of ggms_induced_edges: num_node int32 words, all EMPTY_KEY (ggms_induced_map_init).  Every
+    call leaves it as it found it, so one map serves every call on a graph (one call at a time)."""
+    m = torch.empty(max(1, num_node), dtype=torch.int32, device=device)
+    _require_gpu(m)
+    check(lib().ggms_induced_map_init(_ptr(m), m.numel(), _stream()), "ggms_induced_map_init")
+    return m
+
+
+def induced_edges(graph, nodes, local_of, max_edges, num_nodes_dev=None, want_eid=True, num_edge=None, out=None,
+                  counts=None, max_nodes=None):
+    """ggms_induced_edges: every edge of the graph with both ends among nodes[0, n), as (row, col, eid) over positions of
+    `nodes` (row: the neighbour, col: the node whose list was read, eid: the CSR position) in (col, position) order; a
+    repeated id counts at its first position only.  n = num_nodes_dev[0] (a device int64 tensor) or len(nodes).  Returns
+    (row, col, eid, counts): the first min(M, max_edges) entries are written, counts (device int64[2]) = [M, list entries
+    walked]; eid is None without want_eid.  num_edge: indptr[-1] (default: indices' length).  out: (row, col, eid)
+    tensors to write into (fresh ones unless given); counts: the count words' tensor."""
+    _require_gpu(_i32(nodes))
+    _require_gpu(_i32(local_of))
+    dev = nodes.device
+    mn = int(max_nodes) if max_nodes is not None else nodes.numel()
+    if out is None:
+        out = tuple(torch.empty(max(1, max_edges), dtype=torch.int32, device=dev) for _ in range(3))
+    row, col, eid = out
+    if not want_eid:
+        eid = None
+    for t in (row, col, eid):
+        if t is not None:
+            _require_gpu(_i32(t))
+            assert t.numel() >= max_edges, "induced_edges: an output tensor is shorter than max_edges"
+    if counts is None:
+        counts = torch.empty(2, dtype=torch.int64, device=dev)
+    assert counts.dtype == torch.int64 and counts.is_contiguous() and counts.numel() >= 2
+    if num_nodes_dev is not None:
+        assert num_nodes_dev.dtype == torch.int64 and num_nodes_dev.is_cuda
+    ne = int(num_edge) if num_edge is not None else graph.indices.numel()
+    ws = _workspace(lib().ggms_induced_edges_workspace_bytes(mn, ne), dev)
+    check(lib().ggms_induced_edges(C.byref(graph.c), ne, _ptr(nodes), mn, _ptr(num_nodes_dev), _ptr(local_of),
+                                   _ptr(row), _ptr(col), _ptr(eid), max_edges, _ptr(counts), _ptr(ws), ws.numel() * 4,
+                                   _stream()), "ggms_induced_edges")
+    return row, col, eid, counts
+
+
 def sample_weighted_khop_prefix(graph, prob_prefix_table, inp, fanout, states):
     """GPUSampleWeightedKHopPrefix (cuda_sampling_weighted_khop_prefix.cu:145-246)."""
     return _sample("ggms_sample_weighted_khop_prefix", WEIGHTED_KHOP_PREFIX, graph, inp, fanout, states,

@@ -19,7 +19,8 @@ for _name in ("init start num_class feat_dim num_epoch steps_per_epoch get_next_
               "report_epoch report_epoch_average report_node_access trace_step_begin trace_step_end "
               "trace_step_begin_now trace_step_end_now dump_trace forward_barrier wait_one_child log_step_by_key "
               "get_log_step_value_by_key data_init sample_init train_init extract_start num_local_step "
-              "um_sample_init switch_init feat_row_bytes num_negative get_graph_num_excluded").split():
+              "um_sample_init switch_init feat_row_bytes num_negative get_graph_num_excluded "
+              "get_graph_num_induced").split():
     globals()[_name] = getattr(_basics, _name)
 
 # DataType code -> (numpy typestr, torch dtype); common/common.h:38-46, adapter.cc:33-53
@@ -126,6 +127,29 @@ def get_graph_edge_feat(batch_key, layer_idx):
     """Config key edge_feat: (num_edge, EDGE_FEAT_DIM) rows of the dataset's edge table, row k that of edge k of the
     layer, in the table's dtype."""
     return _get("samgraph_get_graph_edge_feat", batch_key, layer_idx)
+
+
+def get_graph_induced_row(batch_key):
+    """Config key induced_subgraph: the neighbour end of every edge the batch's input nodes induce -- every edge of the
+    graph with both ends among them -- as a local id (a row of get_graph_feat), get_graph_num_induced of them."""
+    return _get("samgraph_get_graph_induced_row", batch_key)
+
+
+def get_graph_induced_col(batch_key):
+    """Config key induced_subgraph: the local id of the node whose list holds the induced edge (get_graph_col's side)."""
+    return _get("samgraph_get_graph_induced_col", batch_key)
+
+
+def get_graph_induced_edge_ids(batch_key):
+    """Config key induced_subgraph: the CSR position of every induced edge (int32 holding the uint32 bits); parallel
+    edges carry their own."""
+    return _get("samgraph_get_graph_induced_edge_ids", batch_key)
+
+
+def get_graph_induced_edge_feat(batch_key):
+    """Config keys induced_subgraph and edge_feat: (num_induced, EDGE_FEAT_DIM) rows of the edge table, row k that of
+    induced edge k."""
+    return _get("samgraph_get_graph_induced_edge_feat", batch_key)
 
 
 def get_graph_edge_time(batch_key, layer_idx):
