@@ -168,8 +168,41 @@ typedef struct {
   uint32_t num_part;
   uint32_t num_cache_node;
   uint32_t num_node;
-  uint32_t _pad;
+  uint32_t heads_id; /* 0: none; else the handle ggms_list_heads_attach wrote ("Inline list heads" below).  It took the
+                        place of the struct's pad word: same layout, same size */
 } ggms_graph_t;
+
+/* ---------------------------------------------------------------------------
+ * Inline list heads (an extension; the reference has no such table): a one-time table over a STATIC, unsharded CSR with
+ * one 64-byte, 64-byte-aligned record of 16 uint32 words per node, so that a sampler input costs one memory-side
+ * request and one round trip where indptr -> indices costs two or three requests and two dependent trips.
+ *   deg <= GGMS_LIST_HEAD_INLINE (15):  word 0 = deg, words 1 .. deg = the neighbours in CSR order, the rest 0
+ *   deg >  GGMS_LIST_HEAD_INLINE:       word 0 = deg, word 1 = indptr[v], the rest 0
+ *   ggms_list_heads_bytes   64 x num_node (0 nodes: 0)
+ *   ggms_list_heads_build   one streaming kernel over the CSR; like every entry point it allocates nothing and does not
+ *               synchronise.  heads: device memory, 64-byte aligned, `bytes` >= ggms_list_heads_bytes(num_node).
+ *               Unsharded graphs only (num_part != 0: GGMS_ERR_INVALID).  The table is valid once `stream` has run it
+ *               and for as long as indptr / indices keep their contents.
+ *   ggms_list_heads_attach  registers (heads, indptr, indices, num_node) in a small host-side registry of this process
+ *               and writes the handle into graph->heads_id (a graph that had one is detached first).  The caller keeps
+ *               `heads` alive until the detach.  GGMS_ERR_INVALID: null / misaligned pointer, sharded graph, registry
+ *               full (GGMS_LIST_HEADS_MAX handles).
+ *   ggms_list_heads_detach  releases the handle and zeroes graph->heads_id; a graph without one: nothing happens.
+ *   ggms_list_heads_of      the table a call on `graph` would use right now, or NULL (host arithmetic only).
+ * A call uses the heads only if graph->heads_id is a live handle AND the registry's indptr, indices and num_node equal
+ * the struct's: a stale id, a copied struct whose arrays were replaced, or garbage in the word (it used to be padding)
+ * is ignored, never trusted.  Which calls look: khop3 (ggms_sample_khop3, ggms_sample_batch[_prefetch] with
+ * GGMS_KHOP3).  Results are byte-identical with and without heads: edges, order, RNG pool, counts.  Every other call
+ * reads the CSR as before.
+ * ------------------------------------------------------------------------- */
+#define GGMS_LIST_HEAD_BYTES 64
+#define GGMS_LIST_HEAD_INLINE 15
+#define GGMS_LIST_HEADS_MAX 255
+size_t ggms_list_heads_bytes(size_t num_node);
+int ggms_list_heads_build(const ggms_graph_t *graph, void *heads, size_t bytes, ggms_stream_t stream);
+int ggms_list_heads_attach(ggms_graph_t *graph, const void *heads);
+int ggms_list_heads_detach(ggms_graph_t *graph);
+const void *ggms_list_heads_of(const ggms_graph_t *graph);
 
 /* ---------------------------------------------------------------------------
  * XORWOW state pool -- GPURandomStates, cuda/cuda_random_states.cu:36-109.

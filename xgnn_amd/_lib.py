@@ -16,7 +16,7 @@ class Graph(C.Structure):
     _fields_ = [("indptr", C.c_void_p), ("indices", C.c_void_p),
                 ("part_indptr", C.c_void_p), ("part_indices", C.c_void_p),
                 ("num_part", C.c_uint32), ("num_cache_node", C.c_uint32),
-                ("num_node", C.c_uint32), ("_pad", C.c_uint32)]
+                ("num_node", C.c_uint32), ("heads_id", C.c_uint32)]
 
 
 class SampleExtra(C.Structure):
@@ -114,6 +114,11 @@ SYMBOLS = {
     "ggms_fabric_probe": (_i, [_i, _vp, _sz, _sz, _u32, _vp, _vp]),
     "ggms_dtype_bytes": (_sz, [_i]),
     "ggms_row_bytes": (_sz, [_i, _sz]),
+    "ggms_list_heads_bytes": (_sz, [_sz]),
+    "ggms_list_heads_build": (_i, [C.POINTER(Graph), _vp, _sz, _vp]),
+    "ggms_list_heads_attach": (_i, [C.POINTER(Graph), _vp]),
+    "ggms_list_heads_detach": (_i, [C.POINTER(Graph)]),
+    "ggms_list_heads_of": (_vp, [C.POINTER(Graph)]),
     "ggms_random_states_init": (_i, [_vp, _sz, _u64, _vp]),
     "ggms_random_states_count": (_sz, [_i, C.POINTER(_sz), _sz, _sz, _sz]),
     "ggms_sample_workspace_bytes": (_sz, [_i, _sz, _sz]),

@@ -274,6 +274,14 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
     // the batch dtype rule of a table of that type (the table's side of it is checked in LoadDataset)
     if (cfg.feat_store_dtype == GGMS_Q8ROW && cfg.feat_out_dtype < 0) fatal(__FILE__, __LINE__, kQ8RowNeedsOutDtype);
   }
+  if (kv.count("inline_heads")) { // extension: inline list heads for khop3 (include/ggms.h), built at graph load
+    const std::string v = kv["inline_heads"];
+    if (v != "auto" && v != "0" && v != "1") fatal(__FILE__, __LINE__, "inline_heads = " + v + ": auto (the default), 0 or 1");
+    cfg.inline_heads = v == "auto" ? -1 : (v == "1" ? 1 : 0);
+    if (cfg.inline_heads == 1 && (cfg.arch != kArch1 || cfg.use_dist_graph || cfg.sample_type == GGMS_KHOP2))
+      fatal(__FILE__, __LINE__, "inline_heads = 1: built for arch1 with the whole CSR on the GPU, and not beside khop2, "
+                                "which permutes the neighbour lists the table copies");
+  }
   if (kv.count("task")) { // extension: what a batch is made of
     const std::string v = kv["task"];
     if (v != "node_classification" && v != "link_prediction")
@@ -1096,6 +1104,7 @@ void Engine::UploadGraph() {
     graph_.indptr = d_indptr_;
     graph_.indices = d_indices_;
     SAM_HIP(hipStreamSynchronize(stream_));
+    AttachListHeads();
     return;
   }
   // DistGraph::GraphLoad, cuda/dist_graph.cu:309-385
@@ -1149,6 +1158,30 @@ void Engine::UploadGraph() {
   graph_.part_indices = (const ggms_id_t *const *)part_indices_.data();
   graph_.num_part = P;
   graph_.num_cache_node = num_cache_node;
+}
+
+// Config key inline_heads: one 64-byte record per node (degree + the whole list up to degree 15, include/ggms.h), built by
+// one streaming kernel over the CSR that was just uploaded and attached to graph_; khop3 reads it where it read indptr.
+// The CSR is static for the engine's life, so the table is too.  The decision is logged once.
+void Engine::AttachListHeads() {
+  if (cfg.arch != kArch1 || cfg.inline_heads == 0 || ds.num_node == 0) return;
+  const size_t bytes = ggms_list_heads_bytes(ds.num_node);
+  if (cfg.inline_heads < 0) {
+    if (cfg.sample_type != GGMS_KHOP3) return; // the other samplers do not look at it
+    size_t free_b = 0, total_b = 0;
+    SAM_HIP(hipMemGetInfo(&free_b, &total_b));
+    if (bytes > free_b / 4) {
+      std::fprintf(stderr, "[samgraph-amd] inline_heads = auto: not built (%zu bytes needed, %zu free: more than a quarter)\n",
+                   bytes, free_b);
+      return;
+    }
+  }
+  SAM_HIP(hipMalloc(&d_heads_, bytes));
+  SAM_GGMS(ggms_list_heads_build(&graph_, d_heads_, bytes, stream_));
+  SAM_HIP(hipStreamSynchronize(stream_));
+  SAM_GGMS(ggms_list_heads_attach(&graph_, d_heads_));
+  std::fprintf(stderr, "[samgraph-amd] inline_heads = %s: %zu bytes of list heads for %zu nodes attached\n",
+               cfg.inline_heads < 0 ? "auto" : "1", bytes, (size_t)ds.num_node);
 }
 
 // ------------------------------------------------------------------ init
@@ -1773,6 +1806,7 @@ void Engine::Shutdown() {
   if (stream_) (void)hipStreamSynchronize(stream_);
   if (stream_extract_) (void)hipStreamSynchronize(stream_extract_);
   if (stream_extract2_) (void)hipStreamSynchronize(stream_extract2_);
+  if (d_heads_) (void)ggms_list_heads_detach(&graph_); // the handle goes back; device memory stays until the process ends
 }
 
 // ------------------------------------------------------------------ hot loop

@@ -95,6 +95,11 @@ struct RunConfig {
   // encoded into this type by the trainer GPU before the cache is built (Engine::QuantizeStore); from then on the
   // dataset is what a meta.txt naming the type would have loaded.  -1: key absent, the table stays as it is on disk
   int feat_store_dtype = -1;
+  // extension (config key `inline_heads` = auto | 0 | 1; arch1, whole CSR on the GPU): the 64-byte-per-node table of
+  // include/ggms.h ("Inline list heads"), built once at graph load and attached to the graph; khop3 then finds a
+  // frontier node's list with one request.  -1 = auto: khop3, and 64 x num_node bytes at most a quarter of the free
+  // device memory at that point.  1: build it or stop with a message.  0: never
+  int inline_heads = -1;
   // extension (config keys `task` = node_classification | link_prediction, `num_negative` = 1 .. 64, `negative_mode` =
   // uniform | exclude; arch1): a batch is batch_size positive EDGES of the shuffled train edge set; its seed list is
   // their endpoints and num_negative negative destinations each (ggms_link_seeds), batch_size x (2 + num_negative) ids
@@ -348,6 +353,7 @@ class Engine {
   ggms_topology_t topo_{};
   bool topo_valid_ = false;
   void UploadGraph();
+  void AttachListHeads(); // config key inline_heads
   void Presample();
   void QuantizeStore(); // config key feat_store_dtype: ds.feat re-encoded by ggms_quantize_rows, before BuildCache
   void BuildCache();
@@ -415,6 +421,7 @@ class Engine {
   hipStream_t stream_extract2_ = nullptr;
   // device graph
   uint32_t *d_indptr_ = nullptr, *d_indices_ = nullptr;
+  void *d_heads_ = nullptr; // inline list heads (config key inline_heads), attached to graph_
   std::vector<void *> part_indptr_, part_indices_; // P+1 entries (slot P = host CSR)
   ggms_graph_t graph_{};
   // sampler state

@@ -128,6 +128,9 @@ struct GraphView {
   Divisor part;                                   // d = num_part
   uint32_t num_part;
   uint32_t num_cache_node;
+  // inline list heads (list_heads.hip; NULL: none attached): 16 words per node, word 0 = degree, then the whole list
+  // (degree <= kHeadInline) or indptr[v].  Only the unsharded view ever carries them, and only khop3 reads them.
+  const uint32_t *heads;
 
   // indptr[v], indptr[v + 1] with ONE 8-byte load (4-byte aligned: global_load_dwordx2 only needs dword alignment):
   // one request at the memory side instead of two -- the sampler is bounded by requests, not bytes
@@ -164,6 +167,11 @@ struct GraphView {
 // call (host side) turns that into an argument error.  common.hip
 bool host_readable_table(const void *table, const char *what);
 
+// The heads table registered under g->heads_id, if that handle is live and was attached to exactly this CSR (indptr,
+// indices, num_node); else NULL -- a stale or garbage id is ignored.  list_heads.hip
+constexpr uint32_t kHeadWords = GGMS_LIST_HEAD_BYTES / 4, kHeadInline = GGMS_LIST_HEAD_INLINE;
+const uint32_t *list_heads_of(const ggms_graph_t *g);
+
 // host side: NULL + an error message if the graph has more shards than the kernels carry
 inline bool view_of(const ggms_graph_t *g, GraphView &v) {
   v = GraphView{};
@@ -172,7 +180,10 @@ inline bool view_of(const ggms_graph_t *g, GraphView &v) {
   v.num_part = g->num_part;
   v.num_cache_node = g->num_cache_node;
   v.part = divisor_of(g->num_part ? g->num_part : 1);
-  if (g->num_part == 0) return true;
+  if (g->num_part == 0) {
+    if (g->heads_id != 0) v.heads = list_heads_of(g);
+    return true;
+  }
   if (g->num_part > kMaxParts || !g->part_indptr || !g->part_indices) {
     set_error("graph view: num_part %u (at most %u shards; part_indptr / part_indices are HOST arrays of num_part + 1 device pointers)",
               g->num_part, kMaxParts);

@@ -85,6 +85,7 @@ __device__ __forceinline__ uint32_t row_shr(uint32_t v) {
 // (profiles/r04_ab_vs_r03_same_box.txt, r04_ab_khop3_waves_per_simd.txt).
 // what tile t's descriptor holds -- the edges its 128 seeds will produce -- computed by one wave from the kernel's input
 // (scan_lookback's Help: a look-back that has waited long enough no longer depends on tile t's workgroup running)
+template <bool HEADS>
 struct Khop3TileHelp {
   static constexpr bool kCan = true;
   const GraphView &g;
@@ -98,7 +99,8 @@ struct Khop3TileHelp {
       const uint64_t i = 128 * t + 64 * k + (threadIdx.x & 63u);
       if (i < n) {
         uint32_t len;
-        (void)g.neighbours(input[i], len);
+        if constexpr (HEADS) len = g.heads[(uint64_t)input[i] * kHeadWords]; // word 0 of the record
+        else (void)g.neighbours(input[i], len);
         acc += len < fanout ? len : fanout;
       }
     }
@@ -112,7 +114,16 @@ struct Khop3TileHelp {
 // list, table word {pending, position}.  A seed's word is smaller than any neighbour instance's, so it wins whenever it
 // arrives; if a neighbour instance of this launch got there first the seed tells it so through `lost`, exactly as any
 // smaller arrival does (DedupInsert) -- the owner scan and the end-of-batch look-ups need nothing new.
-template <int GPW, bool INSERT, bool FIRST>
+//
+// HEADS (inline list heads attached to the graph, list_heads.hip): phase 1 reads the seed's 64-byte record where it
+// read the indptr pair -- the lane that owns the seed issues four 16-byte loads of the one line (the group's 16 lanes
+// fetching a dword each measured 4 % slower and spilled: profiles/list_heads_ab.txt).  Degree <= 15: the record IS the
+// list; its 15 words go to LDS and the sweep takes `nbr` from there: no second, dependent trip to `indices`, one
+// memory-side request per input instead of two or three.  Longer lists: word 1 is indptr[v], the rest as without heads.
+// Where the 15 words live: a seed with degree <= 15 <= fanout never draws, so its `fanout` words of s_pos are free and
+// hold them (no LDS added: fanout >= 15 is where LDS is tightest); with fanout < 15 a seed of degree fanout + 1 .. 15
+// needs both: the words go behind s_pos (128 x 15 more words).  Same bytes either way; !HEADS is the kernel as it was.
+template <int GPW, bool INSERT, bool FIRST, bool HEADS>
 __global__ __launch_bounds__(128 * (4 / GPW), 6) void k_khop3_fused(GraphView g, const uint32_t *__restrict__ input,
                                                                  Count n_arg, uint32_t fanout, uint32_t fanout_magic,
                                                                  uint32_t *__restrict__ out_src,
@@ -138,6 +149,9 @@ __global__ __launch_bounds__(128 * (4 / GPW), 6) void k_khop3_fused(GraphView g,
   uint32_t *const tab = set_tab[active ? y : 0];
   const uint64_t num_tiles = (n + 127) / 128;
   const uint32_t my_s = y + 8u * lig; // my seed of the tile (as a group lane)
+  // HEADS: seed s keeps its inline list at s_nbr[s * nbr_stride .. + 15)
+  uint32_t *const s_nbr = fanout >= kHeadInline ? s_pos : s_pos + 128u * fanout;
+  const uint32_t nbr_stride = fanout >= kHeadInline ? fanout : kHeadInline;
 
   if (active)
     for (uint32_t s = lig; s <= set_mask; s += 16) tab[s] = HASH_EMPTY;
@@ -169,7 +183,23 @@ __global__ __launch_bounds__(128 * (4 / GPW), 6) void k_khop3_fused(GraphView g,
           fl.n2o[my_index] = rid;
           seed_old = atomicMin(di.w + rid, make_w1(di.version, 1u, (uint32_t)my_index));
         }
-        ptr = g.neighbours(rid, my_len);
+        if constexpr (HEADS) {
+          // all four quarters at once (one line): waiting for word 0 before asking for the rest would be the second trip
+          const uint4 *rec = reinterpret_cast<const uint4 *>(g.heads + (uint64_t)rid * kHeadWords);
+          const uint4 q0 = rec[0], q1 = rec[1], q2 = rec[2], q3 = rec[3];
+          my_len = q0.x;
+          if (my_len > kHeadInline) {
+            ptr = g.indices + q0.y;
+          } else if (my_len != 0) { // words past the degree are zero and never read
+            uint32_t *d = s_nbr + my_s * nbr_stride;
+            d[0] = q0.y; d[1] = q0.z; d[2] = q0.w;
+            d[3] = q1.x; d[4] = q1.y; d[5] = q1.z; d[6] = q1.w;
+            d[7] = q2.x; d[8] = q2.y; d[9] = q2.z; d[10] = q2.w;
+            d[11] = q3.x; d[12] = q3.y; d[13] = q3.z; d[14] = q3.w;
+          }
+        } else {
+          ptr = g.neighbours(rid, my_len);
+        }
         if (my_len > fanout) my_magic = (uint32_t)(4294967296.0 / (double)my_len); // floor(2^32 / len), exact
       }
       s_ptr[my_s] = ptr;
@@ -312,7 +342,7 @@ __global__ __launch_bounds__(128 * (4 / GPW), 6) void k_khop3_fused(GraphView g,
     if (threadIdx.x < kWave) {
       uint32_t prefix = 0;
       if (b != 0) {
-        prefix = scan_lookback(fs.desc, b, fs.epoch, fs.err, fs.patience, Khop3TileHelp{g, input, n, fanout});
+        prefix = scan_lookback(fs.desc, b, fs.epoch, fs.err, fs.patience, Khop3TileHelp<HEADS>{g, input, n, fanout});
         if (lane == 0)
           __hip_atomic_store(&fs.desc[b], scan_desc(fs.epoch, FLAG_P, prefix + s_off[128]), __ATOMIC_RELAXED,
                              __HIP_MEMORY_SCOPE_AGENT);
@@ -327,7 +357,7 @@ __global__ __launch_bounds__(128 * (4 / GPW), 6) void k_khop3_fused(GraphView g,
     // for a "take them all" seed and the sampler's pick otherwise; written out as (src value, neighbour id)
     const uint32_t prefix = s_prefix;
     const uint32_t slots = 128u * fanout;
-    const auto slot_of = [&](uint32_t t, uint32_t &sd, uint32_t &e, uint32_t &pos) -> bool {
+    const auto slot_of = [&](uint32_t t, uint32_t &sd, uint32_t &e, uint32_t &pos, bool &inl) -> bool {
       // s = t / fanout (t < 2^14): mulhi by ceil(2^32 / fanout), one fix-up
       sd = fanout == 1 ? t : __umulhi(t, fanout_magic);
       if (sd * fanout > t) --sd;
@@ -336,19 +366,26 @@ __global__ __launch_bounds__(128 * (4 / GPW), 6) void k_khop3_fused(GraphView g,
       if (j >= (len < fanout ? len : fanout)) return false;
       e = prefix + s_off[sd] + j;
       pos = len <= fanout ? j : s_pos[t];
+      inl = HEADS && len <= kHeadInline; // the list is in LDS (phase 1)
       return true;
+    };
+    const auto nbr_of = [&](uint32_t sd, uint32_t pos, bool inl) -> uint32_t {
+      if constexpr (HEADS) {
+        if (inl) return s_nbr[sd * nbr_stride + pos];
+      }
+      return s_ptr[sd][pos];
     };
     if (multi) {
       // a frontier that fits the chip at once (every workgroup has ONE tile): the sweep runs at latency, so a lane keeps
       // four slots in flight -- loads together, then the atomics together, then their bookkeeping
       for (uint32_t t0 = threadIdx.x; t0 < slots; t0 += 4 * NT) {
         uint32_t sd[4], e[4], pos[4], nbr[4];
-        bool ok[4];
+        bool ok[4], inl[4];
 #pragma unroll
         for (uint32_t u = 0; u < 4; ++u) {
           const uint32_t t = t0 + u * NT;
-          ok[u] = t < slots && slot_of(t, sd[u], e[u], pos[u]);
-          nbr[u] = ok[u] ? s_ptr[sd[u]][pos[u]] : 0u;
+          ok[u] = t < slots && slot_of(t, sd[u], e[u], pos[u], inl[u]);
+          nbr[u] = ok[u] ? nbr_of(sd[u], pos[u], inl[u]) : 0u;
         }
         unsigned long long old[4];
 #pragma unroll
@@ -370,8 +407,9 @@ __global__ __launch_bounds__(128 * (4 / GPW), 6) void k_khop3_fused(GraphView g,
       // sampling on papers100M when applied everywhere -- those launches are bounded by requests, not by latency)
       for (uint32_t t = threadIdx.x; t < slots; t += NT) {
         uint32_t sd, e, pos;
-        if (!slot_of(t, sd, e, pos)) continue;
-        const uint32_t nbr = s_ptr[sd][pos];
+        bool inl;
+        if (!slot_of(t, sd, e, pos, inl)) continue;
+        const uint32_t nbr = nbr_of(sd, pos, inl);
         out_src[e] = sm.value(s_rid[sd], 128 * b + sd);
         out_dst[e] = nbr;
         if (INSERT) di.enter(nbr, e);
@@ -762,19 +800,31 @@ size_t sample_ws_words(size_t num_input) {
   return num_input + tile_scan_words(num_input) + 16 + 2 * (num_input / 128 + 2) + kTicketWords + 16;
 }
 
-template <int GPW, bool INSERT, bool FIRST>
-static int launch_khop3_fused(int grid, size_t lds, const SampleLayer &l, uint32_t set_mask, uint32_t multi,
-                               FusedScan fs, DedupInsert di, FirstLayer fl) {
+template <int GPW, bool INSERT, bool FIRST, bool HEADS>
+static int launch_khop3_fused_h(int grid, size_t lds, const SampleLayer &l, uint32_t set_mask, uint32_t multi,
+                                 FusedScan fs, DedupInsert di, FirstLayer fl) {
   const uint32_t fanout = (uint32_t)l.fanout;
   const uint32_t fanout_magic = (uint32_t)((0x100000000ull + fanout - 1) / fanout); // ceil(2^32 / fanout)
   if (lds > (48u << 10)) { // large fan-outs: more dynamic LDS than the default per-kernel limit (gfx950 has 160 KB)
-    static const int raised = raise_dynamic_lds(reinterpret_cast<const void *>(&k_khop3_fused<GPW, INSERT, FIRST>),
+    static const int raised = raise_dynamic_lds(reinterpret_cast<const void *>(&k_khop3_fused<GPW, INSERT, FIRST, HEADS>),
                                                 128 * 127 * 4, "k_khop3_fused (fanout >= 96)");
     if (raised != GGMS_OK) return raised;
   }
-  hipLaunchKernelGGL((k_khop3_fused<GPW, INSERT, FIRST>), dim3(grid), dim3(128 * (4 / GPW)), lds, l.s, l.g, l.input, l.n,
-                     fanout, fanout_magic, l.out_src, l.out_dst, l.src, l.states, set_mask, multi, fs, di, fl);
+  hipLaunchKernelGGL((k_khop3_fused<GPW, INSERT, FIRST, HEADS>), dim3(grid), dim3(128 * (4 / GPW)), lds, l.s, l.g, l.input,
+                     l.n, fanout, fanout_magic, l.out_src, l.out_dst, l.src, l.states, set_mask, multi, fs, di, fl);
   return GGMS_OK;
+}
+
+// the graph's inline list heads, where attached, pick the HEADS form of the kernel (a uniform choice per launch)
+template <int GPW, bool INSERT, bool FIRST>
+static int launch_khop3_fused(int grid, size_t lds, const SampleLayer &l, uint32_t set_mask, uint32_t multi,
+                               FusedScan fs, DedupInsert di, FirstLayer fl) {
+  if (l.g.heads) {
+    // fanout < 15: the inline lists need room of their own behind the positions (k_khop3_fused)
+    if (l.fanout < kHeadInline) lds += 128 * kHeadInline * sizeof(uint32_t);
+    return launch_khop3_fused_h<GPW, INSERT, FIRST, true>(grid, lds, l, set_mask, multi, fs, di, fl);
+  }
+  return launch_khop3_fused_h<GPW, INSERT, FIRST, false>(grid, lds, l, set_mask, multi, fs, di, fl);
 }
 
 bool khop3_can_fuse_seeds(size_t num_seeds) { return (num_seeds + 127) / 128 <= grid_cap(); }

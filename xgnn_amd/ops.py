@@ -75,10 +75,17 @@ def _i32(t):
 
 
 class DeviceGraph:
-    """ggms_graph_t over device tensors: DeviceNormalGraph or DeviceDistGraph (dist_graph.h:114-180)."""
+    """ggms_graph_t over device tensors: DeviceNormalGraph or DeviceDistGraph (dist_graph.h:114-180).
 
-    def __init__(self, indptr, indices, part_indptr=None, part_indices=None, num_cache_node=0):
+    inline_heads: the 64-byte-per-node table of include/ggms.h ("Inline list heads"), built once here and attached to
+    the struct; khop3 then finds a frontier node's list with one request.  None (default): build it if the graph is an
+    unsharded CSR on a GPU and 64 x num_node bytes are at most a quarter of the device's free memory; True: build it or
+    raise; False: never.  The CSR must keep its contents while the heads are attached (khop2, which permutes `indices`,
+    detaches them)."""
+
+    def __init__(self, indptr, indices, part_indptr=None, part_indices=None, num_cache_node=0, inline_heads=None):
         self.indptr, self.indices = indptr, indices
+        self.heads = None
         self._keep = [indptr, indices]
         num_node = (indptr.numel() - 1) if indptr is not None else 0
         self.c = _CGraph()
@@ -98,6 +105,39 @@ class DeviceGraph:
             self.c.num_part = len(part_indptr) - 1
             self.c.num_cache_node = num_cache_node
             self.c.num_node = part_indptr[-1].numel() - 1
+        if inline_heads or inline_heads is None:
+            self._build_heads(required=bool(inline_heads))
+
+    def _build_heads(self, required):
+        on_gpu = (self.c.num_part == 0 and self.indptr is not None and self.indices is not None
+                  and getattr(self.indptr, "is_cuda", False) and getattr(self.indices, "is_cuda", False)
+                  and self.c.num_node > 0)
+        if not on_gpu:
+            if required:
+                raise _lib.GgmsError("inline_heads=True needs an unsharded CSR in device memory")
+            return
+        nbytes = lib().ggms_list_heads_bytes(self.c.num_node)
+        with torch.cuda.device(self.indptr.device):
+            if not required and 4 * nbytes > torch.cuda.mem_get_info()[0]:
+                return
+            heads = torch.empty(nbytes // 4, dtype=torch.int32, device=self.indptr.device)
+            check(lib().ggms_list_heads_build(C.byref(self.c), _ptr(heads), nbytes, _stream()), "ggms_list_heads_build")
+            # samplers run on streams of their own: the table is complete before anyone can look
+            torch.cuda.current_stream().synchronize()
+        check(lib().ggms_list_heads_attach(C.byref(self.c), _ptr(heads)), "ggms_list_heads_attach")
+        self.heads = heads
+
+    def detach_heads(self):
+        """Release the handle and the table (nothing happens without one)."""
+        if self.heads is not None:
+            lib().ggms_list_heads_detach(C.byref(self.c))
+            self.heads = None
+
+    def __del__(self):
+        try:
+            self.detach_heads()
+        except Exception:  # interpreter shutdown: the library may be gone already
+            pass
 
 
 def random_states(num_states, seed, device="cuda"):
@@ -364,6 +404,7 @@ def sample_khop1(graph, inp, fanout, states):
 
 def sample_khop2(graph, inp, fanout, states):
     """GPUSampleKHop2 (cuda_sampling_khop2.cu:196-262).  Permutes graph.indices in place, like the reference."""
+    graph.detach_heads()  # the draws permute graph.indices: inline list heads would go stale
     return _sample("ggms_sample_khop2", KHOP2, graph, inp, fanout, states)
 
 
@@ -904,6 +945,8 @@ class _BatchBuffers:
 
     def _init_capacity(self, graph, fanouts, sample_type, max_seeds, prob_table, alias_table):
         self.graph, self.fanouts, self.sample_type = graph, [int(f) for f in fanouts], sample_type
+        if sample_type == KHOP2:
+            graph.detach_heads()  # the draws permute graph.indices: inline list heads would go stale
         L = self.L = len(self.fanouts)
         self._f = (C.c_size_t * L)(*self.fanouts)
         self.max_seeds = max_seeds
