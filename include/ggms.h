@@ -802,6 +802,66 @@ int ggms_induced_edges(const ggms_graph_t *graph, uint64_t num_edge, const ggms_
 int ggms_induced_kept(const uint64_t *counts_dev, size_t max_edges, uint64_t *kept_dev, ggms_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Heterogeneous view of a sampled batch (an extension; DGL: to_block over a heterograph, PyG: HeteroData): per node type
+ * a node list, per relation an edge list whose ids are local to their type's list.  Two post-passes behind a finished
+ * batch (behind ggms_sample_batch_typed in the engine); no sampler emits anything for them.  Both are ONE stable
+ * multi-way partition with at most 32 buckets: an item's output position is a function of its index alone -- no atomic
+ * decides an order -- so the bytes written do not depend on the grid.
+ *
+ * ggms_hetero_nodes
+ *   node_type       one byte per node id of the graph (num_node of them), values below num_type = T (1 .. 32)
+ *   nodes[0, n)     n = num_nodes_dev ? min(*num_nodes_dev, max_nodes) : max_nodes -- the batch's n2o
+ *   valid           an entry i with nodes[i] < num_node and node_type[nodes[i]] < T.  Any other entry (GGMS_EMPTY_KEY
+ *                   included) is never used to index node_type, gets ntype = 0xFF and local = slot = GGMS_EMPTY_KEY, and
+ *                   is in no count and in no group
+ *   ntype[i]        = node_type[nodes[i]]
+ *   local[i]        = |{ j < i : ntype[j] == ntype[i] }|: the entry's rank inside its type
+ *   base_dev[t]     = |{ i < n : ntype[i] < t }| for t = 0 .. T (T + 1 words; base_dev[T] = the valid entries)
+ *   slot[i]         = base_dev[ntype[i]] + local[i]
+ *   typed_nodes     typed_nodes[slot[i]] = nodes[i]: the ids grouped by type, every group in batch order
+ *   cuts            num_cut <= GGMS_HETERO_MAX_CUTS values c_k = cut_base_dev[cut_words_host[k]] (a device base pointer
+ *                   and a HOST array of word indices, so that a caller points at its counts words):
+ *                   cut_counts_dev[k * T + t] = |{ i < min(c_k, n) : ntype[i] == t }|.  The source sets of a batch's
+ *                   layers are nested prefixes of n2o, so ONE local array serves every layer and the cuts give each
+ *                   layer's per-type source and destination counts.  num_cut == 0: nothing is read or written for them
+ *   nothing is written behind n in ntype / local / slot, and behind base_dev[T] in typed_nodes.
+ *
+ * ggms_hetero_edges: all num_layer layers in one call (HOST arrays of num_layer device pointers, capacities as
+ * ggms_sample_batch_capacity gives them, like ggms_edge_positions).  Per layer i, with R = num_rel (1 .. 32):
+ *   E               = min(counts_dev[GGMS_COUNT_EDGES(i)], max_edges[i])
+ *   off[r]          = |{ e < E : etype[i][e] < r }| for r = 0 .. R; off = rel_offsets_dev + i * (R + 1).  An entry with
+ *                   etype >= R is left out of every count and every output
+ *   entry e of relation r goes to q = off[r] + |{ e' < e : etype[i][e'] == r }| (stable: the sampler's order within a
+ *                   relation survives), where out_row[i][q] = local[row[i][e]], out_col[i][q] = local[col[i][e]] and
+ *                   out_eid[i][q] = eid[i][e]; a row / col entry >= num_local (local's length) maps to GGMS_EMPTY_KEY.
+ *                   eid and out_eid may both be NULL.  Direction as everywhere: col is the node whose list was read (the
+ *                   edge's destination), row the sampled neighbour (its source)
+ *   nothing is written behind off[R] in any output, no counts word is written.
+ *
+ * Both: argument errors -- a null pointer, T or R of 0 or above 32, num_cut above GGMS_HETERO_MAX_CUTS, num_layer of 0 or
+ * above 16, a bound of 2^32 - 1024 items or more, a workspace below ggms_hetero_*_workspace_bytes (0 for arguments out of
+ * range) -- return GGMS_ERR_INVALID with a message that names the argument, before any device call.  No allocation, no
+ * synchronisation, no host round trip; one memset at most and a fixed number of launches whatever the sizes are: the
+ * tiles' bucket counts, one scan over buckets x tiles, the emit (and, for the nodes, the cut counts).
+ * ------------------------------------------------------------------------- */
+#define GGMS_MAX_NODE_TYPES 32
+#define GGMS_HETERO_MAX_CUTS 17
+size_t ggms_hetero_nodes_workspace_bytes(size_t max_nodes, uint32_t num_type);
+int ggms_hetero_nodes(const uint8_t *node_type, size_t num_node, uint32_t num_type, const ggms_id_t *nodes,
+                      size_t max_nodes, const uint64_t *num_nodes_dev /* may be NULL */, const uint64_t *cut_base_dev,
+                      const uint32_t *cut_words_host, uint32_t num_cut, uint8_t *ntype, uint32_t *local, uint32_t *slot,
+                      ggms_id_t *typed_nodes, uint32_t *base_dev /* T + 1 words */,
+                      uint32_t *cut_counts_dev /* num_cut * T words */, void *workspace, size_t workspace_bytes,
+                      ggms_stream_t stream);
+size_t ggms_hetero_edges_workspace_bytes(const size_t *max_edges, uint32_t num_layer, uint32_t num_rel);
+int ggms_hetero_edges(const ggms_id_t *const *row, const ggms_id_t *const *col,
+                      const ggms_id_t *const *eid /* may be NULL */, const uint8_t *const *etype, const size_t *max_edges,
+                      uint32_t num_layer, uint32_t num_rel, const uint64_t *counts_dev, const uint32_t *local,
+                      size_t num_local, ggms_id_t *const *out_row, ggms_id_t *const *out_col,
+                      ggms_id_t *const *out_eid /* NULL iff eid is */, uint32_t *rel_offsets_dev /* L * (R + 1) words */,
+                      void *workspace, size_t workspace_bytes, ggms_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * arch4's batch with early feature prefetch -- DoGPUSampleDyCache (cuda/cuda_loops.cc:294-524).  The layers of
  * ggms_sample_batch, except:
  *   - after the second-to-last layer's table fill, every neighbour of every node entered so far (n2o[0, k)) is

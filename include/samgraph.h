@@ -201,6 +201,45 @@ void samgraph_get_graph_link_time(uint64_t key, samgraph_tensor_t *out);
  *   samgraph_get_graph_edge_type(key, layer)   num_edge(layer) types (uint8), edge_type[edge_ids[k]]
  * Fatal with every other sample type. */
 void samgraph_get_graph_edge_type(uint64_t key, int layer_idx, samgraph_tensor_t *out);
+/* Extensions for config key hetero_batch = on (arch1 with _sample_type 10, both tasks, 1 or 2 pipelines, both table
+ * layouts; refused by name with every other deployment, every other sample type, edge_feat, induced_subgraph,
+ * feat_learnable and use_dist_graph).  The dataset carries node_type.bin (NUM_NODE uint8, one per node id) and the meta key
+ * NUM_NODE_TYPE = T (1 .. 32); a missing file, another size and a value >= T are fatal at init, and so is a relation whose
+ * edges disagree about (source type, destination type) -- named with both signatures.  Behind the sampler,
+ * ggms_hetero_nodes and ggms_hetero_edges (include/ggms.h) group the batch's input nodes by type and every layer's edges
+ * by relation; an edge's ends become ranks inside their types' groups.  Direction as everywhere: col is the edge's
+ * destination (the node whose list was read), row its source.
+ * THE FEATURE ROWS FOLLOW THE GROUPED ORDER: with the key, row s of samgraph_get_graph_feat belongs to
+ * typed_nodes[s] -- the gather is handed the grouped list in place of the input nodes, same count, same kernel, no second
+ * pass over the rows -- so a type's rows are one contiguous slice.  Labels, pair ids and the homogeneous row / col /
+ * edge_ids / edge_type are untouched and keep indexing the input nodes; node_slot maps an input-node index to its feature
+ * row, node_local to its rank inside its type.
+ *   samgraph_get_graph_node_type(key)             one uint8 per input node
+ *   samgraph_get_graph_node_local / _slot(key)    one id per input node: the rank inside its type; base[type] + that rank
+ *   samgraph_get_graph_typed_nodes(key, t)        the global ids of type t, in batch order (a slice of the grouped list)
+ *   samgraph_get_graph_feat_of_type(key, t)       their rows: a VIEW of samgraph_get_graph_feat's buffer, not a copy
+ *   samgraph_get_graph_num_src_of_type / _num_dst_of_type(key, layer, t)   how many of the layer's source / destination
+ *     nodes have type t: they are the first that many of the type's group (the layers' node sets are nested prefixes)
+ *   samgraph_get_graph_rel_row / _rel_col / _rel_edge_ids(key, layer, r)   relation r's edges of the layer in the
+ *     sampler's order: source ranks, destination ranks, CSR positions (slices of the partitioned arrays)
+ *   samgraph_get_graph_rel_num_edges(key, layer, r)
+ *   samgraph_num_node_type(), samgraph_relation_src_type(r), samgraph_relation_dst_type(r)   T and the relation table
+ *     derived at init (255 / 255 for a relation without an edge)
+ * Without the key nothing runs and nothing is allocated; every accessor above is then fatal. */
+void samgraph_get_graph_node_type(uint64_t key, samgraph_tensor_t *out);
+void samgraph_get_graph_node_local(uint64_t key, samgraph_tensor_t *out);
+void samgraph_get_graph_node_slot(uint64_t key, samgraph_tensor_t *out);
+void samgraph_get_graph_typed_nodes(uint64_t key, int node_type, samgraph_tensor_t *out);
+void samgraph_get_graph_feat_of_type(uint64_t key, int node_type, samgraph_tensor_t *out);
+size_t samgraph_get_graph_num_src_of_type(uint64_t key, int layer_idx, int node_type);
+size_t samgraph_get_graph_num_dst_of_type(uint64_t key, int layer_idx, int node_type);
+void samgraph_get_graph_rel_row(uint64_t key, int layer_idx, int relation, samgraph_tensor_t *out);
+void samgraph_get_graph_rel_col(uint64_t key, int layer_idx, int relation, samgraph_tensor_t *out);
+void samgraph_get_graph_rel_edge_ids(uint64_t key, int layer_idx, int relation, samgraph_tensor_t *out);
+size_t samgraph_get_graph_rel_num_edges(uint64_t key, int layer_idx, int relation);
+size_t samgraph_num_node_type(void);
+int samgraph_relation_src_type(int relation);
+int samgraph_relation_dst_type(int relation);
 /* a batch's buffers stay valid while its retain count is > 0 */
 void samgraph_batch_retain(uint64_t key);
 void samgraph_batch_release(uint64_t key);

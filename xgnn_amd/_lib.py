@@ -177,6 +177,12 @@ SYMBOLS = {
     "ggms_induced_map_init": (_i, [_vp, _sz, _vp]),
     "ggms_induced_edges": (_i, [C.POINTER(Graph), _u64, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp]),
     "ggms_induced_kept": (_i, [_vp, _sz, _vp, _vp]),
+    "ggms_hetero_nodes_workspace_bytes": (_sz, [_sz, _u32]),
+    "ggms_hetero_nodes": (_i, [_vp, _sz, _u32, _vp, _sz, _vp, _vp, C.POINTER(_u32), _u32, _vp, _vp, _vp, _vp, _vp, _vp,
+                               _vp, _sz, _vp]),
+    "ggms_hetero_edges_workspace_bytes": (_sz, [C.POINTER(_sz), _u32, _u32]),
+    "ggms_hetero_edges": (_i, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz), _u32, _u32,
+                               _vp, _vp, _sz, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _sz, _vp]),
     "ggms_hashtable_num_buckets": (_sz, [_sz]),
     "ggms_hashtable_init": (_i, [C.POINTER(HashTable), _vp]),
     "ggms_hashtable_reset": (_i, [C.POINTER(HashTable), _vp]),

@@ -121,6 +121,14 @@ SAMGRAPH_SYMBOLS = {
     "samgraph_get_graph_induced_row": (None, [_u64, _TP]), "samgraph_get_graph_induced_col": (None, [_u64, _TP]),
     "samgraph_get_graph_induced_edge_ids": (None, [_u64, _TP]),
     "samgraph_get_graph_induced_edge_feat": (None, [_u64, _TP]),
+    "samgraph_get_graph_node_type": (None, [_u64, _TP]), "samgraph_get_graph_node_local": (None, [_u64, _TP]),
+    "samgraph_get_graph_node_slot": (None, [_u64, _TP]),
+    "samgraph_get_graph_typed_nodes": (None, [_u64, _i, _TP]), "samgraph_get_graph_feat_of_type": (None, [_u64, _i, _TP]),
+    "samgraph_get_graph_num_src_of_type": (_sz, [_u64, _i, _i]), "samgraph_get_graph_num_dst_of_type": (_sz, [_u64, _i, _i]),
+    "samgraph_get_graph_rel_row": (None, [_u64, _i, _i, _TP]), "samgraph_get_graph_rel_col": (None, [_u64, _i, _i, _TP]),
+    "samgraph_get_graph_rel_edge_ids": (None, [_u64, _i, _i, _TP]),
+    "samgraph_get_graph_rel_num_edges": (_sz, [_u64, _i, _i]),
+    "samgraph_num_node_type": (_sz, []), "samgraph_relation_src_type": (_i, [_i]), "samgraph_relation_dst_type": (_i, [_i]),
     "samgraph_get_graph_edge_time": (None, [_u64, _i, _TP]), "samgraph_get_graph_node_cut": (None, [_u64, _TP]),
     "samgraph_get_graph_link_time": (None, [_u64, _TP]),
     "samgraph_get_graph_edge_type": (None, [_u64, _i, _TP]),
@@ -185,6 +193,12 @@ class SamGraphBasics(object):
     def num_negative(self): return self.C_LIB_CTYPES.samgraph_num_negative()
     def get_graph_num_excluded(self, key): return self.C_LIB_CTYPES.samgraph_get_graph_num_excluded(key)
     def get_graph_num_induced(self, key): return self.C_LIB_CTYPES.samgraph_get_graph_num_induced(key)
+    def get_graph_num_src_of_type(self, key, layer, t): return self.C_LIB_CTYPES.samgraph_get_graph_num_src_of_type(key, layer, t)
+    def get_graph_num_dst_of_type(self, key, layer, t): return self.C_LIB_CTYPES.samgraph_get_graph_num_dst_of_type(key, layer, t)
+    def get_graph_rel_num_edges(self, key, layer, r): return self.C_LIB_CTYPES.samgraph_get_graph_rel_num_edges(key, layer, r)
+    def num_node_type(self): return self.C_LIB_CTYPES.samgraph_num_node_type()
+    def relation_src_type(self, r): return self.C_LIB_CTYPES.samgraph_relation_src_type(r)
+    def relation_dst_type(self, r): return self.C_LIB_CTYPES.samgraph_relation_dst_type(r)
     def num_epoch(self): return self.C_LIB_CTYPES.samgraph_num_epoch()
     def steps_per_epoch(self): return self.C_LIB_CTYPES.samgraph_steps_per_epoch()
     def get_next_batch(self): return self.C_LIB_CTYPES.samgraph_get_next_batch()

@@ -228,6 +228,15 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
     cfg.pipelines = 1;
   }
   SAM_CHECK(cfg.sample_type >= GGMS_KHOP0 && cfg.sample_type <= GGMS_KHOP_TYPED, "unknown sample type");
+  if (kv.count("hetero_batch")) { // extension: the batch's heterogeneous view (node types, per-relation blocks)
+    if (kv["hetero_batch"] != "on" && kv["hetero_batch"] != "off")
+      fatal(__FILE__, __LINE__, "hetero_batch = " + kv["hetero_batch"] + ": on or off (the default)");
+    cfg.hetero = kv["hetero_batch"] == "on";
+    static const char *const arch_names[] = {"arch0", "arch1", "arch2", "arch3", "arch4", "arch5", "arch6", "arch7"};
+    if (cfg.hetero && cfg.arch != kArch1)
+      fatal(__FILE__, __LINE__, std::string(arch_names[cfg.arch]) + ": hetero_batch is not built: the typed view is computed "
+                                "behind arch1's sampling chain and travels through no hand-off or queue");
+  }
   if (cfg.Typed() && cfg.arch != kArch1) {
     static const char *const arch_names[] = {"arch0", "arch1", "arch2", "arch3", "arch4", "arch5", "arch6", "arch7"};
     fatal(__FILE__, __LINE__, std::string(arch_names[cfg.arch]) + ": _sample_type 10 (khop_typed) is not built: the edge "
@@ -466,6 +475,21 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
       cfg.induced_max_edges = (size_t)v;
     }
   }
+  if (cfg.hetero) { // (the key itself and the deployment: above, in front of khop_typed's own refusals)
+    if (!cfg.Typed())
+      fatal(__FILE__, __LINE__, "hetero_batch with _sample_type " + std::to_string(cfg.sample_type) + " is not built: the "
+                                "relation of every sampled edge comes from _sample_type 10 (khop_typed) only");
+    if (cfg.use_dist_graph) // (khop_typed refuses it first; kept for the day it does not)
+      fatal(__FILE__, __LINE__, "hetero_batch with use_dist_graph is not built: relations are stored by position in ONE CSR");
+    if (cfg.edge_feat)
+      fatal(__FILE__, __LINE__, "hetero_batch with edge_feat is not built: the edge rows are gathered in the layers' "
+                                "homogeneous order, not per relation");
+    if (cfg.induced)
+      fatal(__FILE__, __LINE__, "hetero_batch with induced_subgraph is not built: the induced edges carry no relation");
+    if (cfg.feat_learnable >= 0)
+      fatal(__FILE__, __LINE__, "hetero_batch with feat_learnable is not built: the gradient rows come back in the grouped "
+                                "order, the update scatters them by input_nodes");
+  }
   if (cfg.arch == kArch4) { // DoGPUSampleDyCache's switch (cuda/cuda_loops.cc:347-377) and what it needs
     if (cfg.sample_type != GGMS_KHOP0 && cfg.sample_type != GGMS_KHOP1 && cfg.sample_type != GGMS_WEIGHTED_KHOP)
       fatal(__FILE__, __LINE__, "arch4: _sample_type " + std::to_string(cfg.sample_type) + " is not supported: the "
@@ -703,6 +727,28 @@ void Engine::LoadDataset() {
                                         "non-decreasing (position " + std::to_string(p) + "); datagen.sort_lists_by_time "
                                         "re-sorts a graph");
   }
+  if (cfg.hetero) { // the node types: NUM_NODE uint8 below NUM_NODE_TYPE
+    if (!meta.count("NUM_NODE_TYPE"))
+      fatal(__FILE__, __LINE__, "hetero_batch: meta.txt lacks NUM_NODE_TYPE (datagen.write_dataset(node_type=, num_node_type=))");
+    const size_t T = meta["NUM_NODE_TYPE"];
+    if (T < 1 || T > GGMS_MAX_NODE_TYPES)
+      fatal(__FILE__, __LINE__, "hetero_batch: NUM_NODE_TYPE = " + std::to_string(T) + ": 1 .. " + std::to_string(GGMS_MAX_NODE_TYPES));
+    const std::string name = cfg.dataset_path + "node_type.bin";
+    struct stat st;
+    if (stat(name.c_str(), &st) != 0)
+      fatal(__FILE__, __LINE__, "hetero_batch: " + name + " is missing (NUM_NODE uint8 types, one per node id; "
+                                    "datagen.write_dataset(node_type=...))");
+    if ((size_t)st.st_size != ds.num_node)
+      fatal(__FILE__, __LINE__, "hetero_batch: node_type.bin has " + std::to_string((size_t)st.st_size) + " bytes, NUM_NODE is " +
+                                    std::to_string(ds.num_node));
+    ds.node_type = MapFile("node_type.bin", ds.num_node, false);
+    ds.num_node_type = (uint32_t)T;
+    const uint8_t *nt = (const uint8_t *)ds.node_type.ptr;
+    for (size_t v = 0; v < ds.num_node; ++v)
+      if (nt[v] >= T)
+        fatal(__FILE__, __LINE__, "hetero_batch: node_type.bin: node " + std::to_string(v) + " has the type " +
+                                      std::to_string((unsigned)nt[v]) + ", NUM_NODE_TYPE is " + std::to_string(T));
+  }
   if (cfg.Typed()) { // the edge types: NUM_EDGE uint8 in CSR order, sorted inside every list, below NUM_EDGE_TYPE
     if (!meta.count("NUM_EDGE_TYPE"))
       fatal(__FILE__, __LINE__, "khop_typed: meta.txt lacks NUM_EDGE_TYPE (datagen.write_dataset(edge_type=, num_edge_type=))");
@@ -723,8 +769,31 @@ void Engine::LoadDataset() {
     ds.edge_type = MapFile("edge_type.bin", ds.num_edge, false);
     const uint32_t *ip = (const uint32_t *)ds.indptr.ptr;
     const uint8_t *t = (const uint8_t *)ds.edge_type.ptr;
+    // hetero_batch: the same pass derives every relation's (source type, destination type) -- the list's owner is the
+    // edge's destination, the entry its source -- and fails on the first edge that disagrees with its relation's others
+    const uint8_t *nt = cfg.hetero ? (const uint8_t *)ds.node_type.ptr : nullptr;
+    const uint32_t *ix = (const uint32_t *)ds.indices.ptr;
+    if (cfg.hetero) {
+      ds.rel_src_type.assign(R, 255);
+      ds.rel_dst_type.assign(R, 255);
+    }
+    const auto pass_t0 = std::chrono::steady_clock::now();
     for (size_t v = 0; v < ds.num_node; ++v) // order and range in one pass: a sorted list's largest type is its last
       for (size_t p = ip[v]; p < ip[v + 1]; ++p) {
+        if (nt && t[p] < R && ix[p] < ds.num_node) {
+          const uint8_t src = nt[ix[p]], dst = nt[v];
+          uint8_t &rs = ds.rel_src_type[t[p]], &rd = ds.rel_dst_type[t[p]];
+          if (rs == 255) {
+            rs = src;
+            rd = dst;
+          } else if (rs != src || rd != dst) {
+            fatal(__FILE__, __LINE__, "hetero_batch: relation " + std::to_string((unsigned)t[p]) + " has two signatures: (source "
+                                          "type " + std::to_string((unsigned)rs) + ", destination type " + std::to_string((unsigned)rd) +
+                                          ") and (source type " + std::to_string((unsigned)src) + ", destination type " +
+                                          std::to_string((unsigned)dst) + ") at position " + std::to_string(p) + " of node " +
+                                          std::to_string(v) + "'s list; datagen.relation_types derives consistent relations");
+          }
+        }
         if (p > ip[v] && t[p] < t[p - 1])
           fatal(__FILE__, __LINE__, "khop_typed: edge_type.bin: the types of node " + std::to_string(v) + "'s list are not "
                                         "non-decreasing (position " + std::to_string(p) + "); datagen.sort_lists_by_type "
@@ -734,6 +803,10 @@ void Engine::LoadDataset() {
                                         std::to_string((unsigned)t[p]) + " (position " + std::to_string(p) +
                                         "), NUM_EDGE_TYPE is " + std::to_string(R));
       }
+    if (cfg.hetero)
+      log_info("hetero_batch: " + std::to_string(ds.num_node_type) + " node types, " + std::to_string(R) + " relations; the "
+               "pass over edge_type.bin with the relations' signatures took " +
+               std::to_string(std::chrono::duration<double>(std::chrono::steady_clock::now() - pass_t0).count()) + " s");
   }
   if (cfg.sample_type == GGMS_WEIGHTED_KHOP || cfg.sample_type == GGMS_WEIGHTED_KHOP_HASH_DEDUP) { // engine.cc:372-384
     ds.prob_table = MapFile("prob_table.bin", ds.num_edge * 4, false);
@@ -1312,6 +1385,17 @@ void Engine::SampleInit(int worker_id, const std::string &ctx) {
     SAM_CHECK(eid_ws_bytes_ > 0, "edge_ids: the batch bounds are out of ggms_edge_positions' range");
     for (Pipe &P : pipes_) SAM_HIP(hipMalloc(&P.eid_ws, eid_ws_bytes_));
   }
+  if (cfg.hetero) { // the node types in HBM; one workspace per pipeline, shared by the two calls (they follow each other)
+    SAM_HIP(hipMalloc((void **)&d_node_type_, std::max<size_t>(ds.num_node, 16)));
+    SAM_HIP(hipMemcpyAsync(d_node_type_, ds.node_type.ptr, ds.num_node, hipMemcpyHostToDevice, stream_));
+    SAM_HIP(hipStreamSynchronize(stream_));
+    hetero_ws_bytes_ = std::max(ggms_hetero_nodes_workspace_bytes(max_unique_, ds.num_node_type),
+                                ggms_hetero_edges_workspace_bytes(max_edges_.data(), L, cfg.num_edge_type));
+    SAM_CHECK(ggms_hetero_nodes_workspace_bytes(max_unique_, ds.num_node_type) > 0 &&
+                  ggms_hetero_edges_workspace_bytes(max_edges_.data(), L, cfg.num_edge_type) > 0,
+              "hetero_batch: the batch bounds are out of ggms_hetero_nodes' / ggms_hetero_edges' range");
+    for (Pipe &P : pipes_) SAM_HIP(hipMalloc(&P.hetero_ws, hetero_ws_bytes_));
+  }
   if (cfg.induced) { // one membership map (4 B x num_node, filled once: every call restores it) and one workspace per pipeline
     induced_ws_bytes_ = ggms_induced_edges_workspace_bytes(max_unique_, ds.num_edge);
     for (Pipe &P : pipes_) {
@@ -1732,6 +1816,21 @@ void Engine::TrainInit(int worker_id, const std::string &ctx) {
       SAM_HIP(hipHostMalloc((void **)&b->ind_counts, 2 * 8));
       std::memset(b->ind_counts, 0, 2 * 8);
     }
+    if (cfg.hetero) { // the typed view: four node arrays, three arrays per layer, the small words and their host copy
+      const size_t nu = std::max<size_t>(max_unique_, 4);
+      SAM_HIP(hipMalloc((void **)&b->het_ntype, std::max<size_t>(nu, 16)));
+      for (uint32_t **p : {&b->het_local, &b->het_slot, &b->het_typed}) SAM_HIP(hipMalloc((void **)p, nu * 4));
+      b->het_row.assign(L, nullptr);
+      b->het_col.assign(L, nullptr);
+      b->het_eid.assign(L, nullptr);
+      for (uint32_t i = 0; i < L; ++i)
+        for (uint32_t **p : {&b->het_row[i], &b->het_col[i], &b->het_eid[i]})
+          SAM_HIP(hipMalloc((void **)p, std::max<size_t>(max_edges_[i], 4) * 4));
+      SAM_HIP(hipMalloc((void **)&b->het_words_dev, HetWords() * 4));
+      SAM_HIP(hipMemset(b->het_words_dev, 0, HetWords() * 4));
+      SAM_HIP(hipHostMalloc((void **)&b->het_words, HetWords() * 4));
+      std::memset(b->het_words, 0, HetWords() * 4);
+    }
     if (cfg.Temporal()) {
       SAM_HIP(hipMalloc((void **)&b->seed_time, std::max<size_t>(max_seeds_, 4) * 4));
       SAM_HIP(hipMalloc((void **)&b->node_cut, std::max<size_t>(max_unique_, 4) * 4));
@@ -1981,6 +2080,25 @@ void Engine::SampleInto(Batch *b, Pipe &P) {
     if (cfg.edge_feat) // the rows the gather may read: never more than were written, whatever M says
       SAM_GGMS(ggms_induced_kept(b->ind_counts_dev, induced_max_edges_, b->ind_counts_dev + 2, P.stream));
   }
+  if (cfg.hetero) {
+    // The typed view of the finished batch: the nodes grouped by type -- one `local` array serves every layer, the
+    // layers' source sets being nested prefixes of the input nodes; the cuts are the layers' source counts and the last
+    // layer's destination count -- then every layer's edges grouped by relation and renumbered through it.  Same stream,
+    // the pipeline's workspace, in front of ev_sampled like everything that writes the batch; the small words go to the
+    // host behind the calls, as the induced counts do.
+    uint32_t cut_words[GGMS_HETERO_MAX_CUTS];
+    for (uint32_t i = 0; i < L; ++i) cut_words[i] = GGMS_COUNT_SRC(i);
+    cut_words[L] = GGMS_COUNT_DST(L - 1);
+    SAM_GGMS(ggms_hetero_nodes(d_node_type_, ds.num_node, ds.num_node_type, s.input_nodes, max_unique_,
+                               s.counts_dev + GGMS_COUNT_INPUT(L), s.counts_dev, cut_words, L + 1, b->het_ntype, b->het_local,
+                               b->het_slot, b->het_typed, b->het_words_dev + HetBaseAt(), b->het_words_dev + HetCutsAt(),
+                               P.hetero_ws, hetero_ws_bytes_, P.stream));
+    SAM_GGMS(ggms_hetero_edges(s.row.data(), s.col.data(), b->eid.data(), b->etype.data(), max_edges_.data(), L,
+                               cfg.num_edge_type, s.counts_dev, b->het_local, max_unique_, b->het_row.data(),
+                               b->het_col.data(), b->het_eid.data(), b->het_words_dev + HetOffsetsAt(), P.hetero_ws,
+                               hetero_ws_bytes_, P.stream));
+    SAM_HIP(hipMemcpyAsync(b->het_words, b->het_words_dev, HetWords() * 4, hipMemcpyDeviceToHost, P.stream));
+  }
   SAM_HIP(hipMemsetAsync(s.counts_dev + GGMS_COUNT_MISS(L), 0, 8, P.stream)); // the trainer's miss count starts at 0
   SAM_HIP(hipEventRecord(b->ev_sampled, P.stream));
 }
@@ -2051,6 +2169,9 @@ void Engine::EnqueueGather(Batch *b, hipStream_t ss) {
   // the rows are delivered in the batch's dtype (config key feat_out_dtype; the table's own without the key, which is
   // the plain gather: a *_convert call with one dtype IS its plain namesake)
   const int out_dtype = batch_feat_dtype();
+  // hetero_batch: the rows are gathered in the grouped order -- the same count, the same kernel, another id list -- so a
+  // type's rows are one contiguous slice of the batch's feature buffer and there is no second pass over the rows
+  const uint32_t *const gather_nodes = cfg.hetero ? b->het_typed : b->trainer.input_nodes;
   uint32_t dyn_seq = 0;
   if (cfg.dynamic_cache) { // batch order on one extract stream; seq wraps: the table starts again from zero
     if (++dyn_seq_ == 0) {
@@ -2075,18 +2196,18 @@ void Engine::EnqueueGather(Batch *b, hipStream_t ss) {
     tiers.my_part = cfg.part_cache ? (uint32_t)worker_id_ : 0;
     tiers.host_feat = feat_src_;
     tiers.host_row_mask = mock ? ds.feat_mask : 0;
-    SAM_GGMS(ggms_extract_tiered_convert(b->feat, b->trainer.input_nodes, max_unique_, n_in, &tiers, ds.feat_dim,
+    SAM_GGMS(ggms_extract_tiered_convert(b->feat, gather_nodes, max_unique_, n_in, &tiers, ds.feat_dim,
                                          ds.feat_dtype, out_dtype, gather_counts ? n_miss : nullptr, xs));
   } else if (cfg.UseGPUCache()) {
     // DoArch6GetCacheMissIndex + DoArch6GPUCacheFeatureCopy (dist_loops.cc:1015-1285) in one pass; everything cached in
     // node order (no table): no row can miss, the count stays the zero the sampling stream wrote
-    SAM_GGMS(ggms_extract_cached_convert(b->feat, b->trainer.input_nodes, max_unique_, n_in, cache_table_,
+    SAM_GGMS(ggms_extract_cached_convert(b->feat, gather_nodes, max_unique_, n_in, cache_table_,
                                          (const void *const *)cache_parts_.data(), num_cache_part_, feat_src_, ds.feat_dim,
                                          ds.feat_dtype, out_dtype, (cache_table_ && can_miss) ? n_miss : nullptr, xs));
   } else {
     // DoGPUFeatureExtract (cuda/cuda_loops.cc, dist_loops.cc:585-634); with SAMGRAPH_EMPTY_FEAT GPUMockExtract
     // (cuda_loops.cc:692-700 / dist_loops.cc:608-616): row = node & mask (all ones otherwise)
-    SAM_GGMS(ggms_gather_scatter_convert(b->feat, feat_src_, b->trainer.input_nodes, nullptr, max_unique_, n_in,
+    SAM_GGMS(ggms_gather_scatter_convert(b->feat, feat_src_, gather_nodes, nullptr, max_unique_, n_in,
                                          ds.feat_dim, ds.feat_dtype, out_dtype, ds.feat_mask, xs));
   }
   if (cfg.dynamic_cache) { // the next batch finds these rows in b->feat; b holds the batch it read until it is finished

@@ -137,6 +137,11 @@ struct RunConfig {
   // layers' edge capacities capped at NUM_EDGE (Engine::ResolveInducedCapacity)
   bool induced = false;
   size_t induced_max_edges = 0;
+  // extension (config key `hetero_batch` = on; arch1 with _sample_type 10 (khop_typed), one CSR): every batch also carries
+  // its heterogeneous view -- the input nodes grouped by node type, every layer's edges grouped by relation with ids local
+  // to their types' lists (ggms_hetero_nodes / ggms_hetero_edges behind the sampler) -- and the feature rows are gathered
+  // in the grouped order
+  bool hetero = false;
   size_t staged_serial_epochs = 0; // host-staged path: the first N epochs run the reference's serial, per-phase-timed sequence
   size_t staged_serial_steps = 0;  // ... or this worker's first N batches
   // worker 0 ranks the nodes at init: pre_sample (sampled input nodes) or presample_static (L-hop closures)
@@ -181,6 +186,11 @@ struct Dataset {
   // khop_typed: edge_type.bin, NUM_EDGE uint8 in CSR order, non-decreasing inside every node's list and below NUM_EDGE_TYPE
   // (checked at load)
   HostArray edge_type;
+  // hetero_batch: node_type.bin, NUM_NODE uint8 below NUM_NODE_TYPE, and every relation's (source type, destination type)
+  // as its edges have them -- 255 / 255 for a relation without an edge
+  HostArray node_type;
+  uint32_t num_node_type = 0;
+  std::vector<uint8_t> rel_src_type, rel_dst_type;
   size_t edge_feat_row_bytes() const { return edge_feat_dim * ggms_dtype_bytes(edge_feat_dtype); }
 };
 
@@ -266,6 +276,14 @@ struct Batch {
   uint32_t *ind_row = nullptr, *ind_col = nullptr, *ind_eid = nullptr;
   void *ind_efeat = nullptr;
   uint64_t *ind_counts_dev = nullptr, *ind_counts = nullptr;
+  // hetero_batch: per input node its type, its rank inside the type and its slot in the grouped list, the grouped list
+  // itself (max_unique entries each); per layer the edges grouped by relation (row / col as ranks inside their types, the
+  // CSR positions; the layer's edge capacity each); the small words [base: T + 1 | cuts: (L + 1) x T | offsets: L x (R + 1)]
+  // on the device and their pinned host copy, valid with the counts.  Null / empty without the key.
+  uint8_t *het_ntype = nullptr;
+  uint32_t *het_local = nullptr, *het_slot = nullptr, *het_typed = nullptr;
+  std::vector<uint32_t *> het_row, het_col, het_eid;
+  uint32_t *het_words_dev = nullptr, *het_words = nullptr;
   uint64_t num_miss = 0;
   hipEvent_t ev_seeds = nullptr, ev_start = nullptr, ev_sampled = nullptr, ev_xstart = nullptr, ev_done = nullptr;
   // arch6 with `gpu_extract` off: the host-staged miss path (dist_loops.cc:1015-1207)
@@ -445,7 +463,17 @@ class Engine {
     uint32_t stamp = 0;            // its last batch
     uint32_t *induced_map = nullptr; // induced_subgraph: the pipeline's membership map (4 B x num_node, all EMPTY between
     void *induced_ws = nullptr;      // batches) and ggms_induced_edges' workspace
+    void *hetero_ws = nullptr;       // hetero_batch: the one workspace of ggms_hetero_nodes and ggms_hetero_edges
   };
+  size_t hetero_ws_bytes_ = 0;
+  uint8_t *d_node_type_ = nullptr; // hetero_batch: the node types in HBM
+ public:
+  // hetero_batch: where the three groups of Batch::het_words start
+  size_t HetBaseAt() const { return 0; }
+  size_t HetCutsAt() const { return ds.num_node_type + 1; }
+  size_t HetOffsetsAt() const { return HetCutsAt() + (cfg.fanout.size() + 1) * ds.num_node_type; }
+  size_t HetWords() const { return HetOffsetsAt() + cfg.fanout.size() * (cfg.num_edge_type + 1); }
+ private:
   size_t induced_ws_bytes_ = 0;
   size_t induced_max_edges_ = 0; // induced_subgraph: the capacity of a batch's induced arrays (ResolveInducedCapacity)
   void ResolveInducedCapacity();

@@ -239,6 +239,91 @@ void samgraph_get_graph_edge_type(uint64_t key, int l, samgraph_tensor_t *out) {
   SAM_CHECK(l >= 0 && (size_t)l < b->etype.size(), "samgraph_get_graph_edge_type: no such layer");
   fill(out, b->etype[l], (int64_t)b->counts[GGMS_COUNT_EDGES(l)], 1, 1, GGMS_U8, E.batch_device_type(), E.trainer_device());
 }
+// config key hetero_batch: the batch's heterogeneous view.  The small words (Batch::het_words: base | cuts | offsets) are
+// on the host with the counts; every tensor below is a zero-copy view, the per-type and per-relation ones slices
+static sam::Batch *hetero_batch(uint64_t key, const char *who) {
+  auto &E = Engine::Get();
+  if (!E.cfg.hetero) sam::fatal(__FILE__, __LINE__, std::string(who) + " needs the config key hetero_batch = on");
+  return E.Current(key);
+}
+static void hetero_need(const char *who) {
+  if (!Engine::Get().cfg.hetero) sam::fatal(__FILE__, __LINE__, std::string(who) + " needs the config key hetero_batch = on");
+}
+static uint32_t hetero_type(int t, const char *who) {
+  SAM_CHECK(t >= 0 && (size_t)t < Engine::Get().ds.num_node_type, std::string(who) + ": no such node type");
+  return (uint32_t)t;
+}
+static const uint32_t *hetero_offsets(sam::Batch *b, int l, int r, const char *who) { // &off[l][r]
+  auto &E = Engine::Get();
+  SAM_CHECK(l >= 0 && (size_t)l < E.cfg.fanout.size(), std::string(who) + ": no such layer");
+  SAM_CHECK(r >= 0 && (uint32_t)r < E.cfg.num_edge_type, std::string(who) + ": no such relation");
+  return b->het_words + E.HetOffsetsAt() + (size_t)l * (E.cfg.num_edge_type + 1) + (size_t)r;
+}
+static void hetero_nodes_tensor(uint64_t key, const char *who, int which, samgraph_tensor_t *out) {
+  auto &E = Engine::Get();
+  auto *b = hetero_batch(key, who);
+  void *p = which == 0 ? (void *)b->het_ntype : which == 1 ? (void *)b->het_local : (void *)b->het_slot;
+  fill(out, p, (int64_t)b->num_input, 1, 1, which == 0 ? GGMS_U8 : GGMS_I32, E.batch_device_type(), E.trainer_device());
+}
+void samgraph_get_graph_node_type(uint64_t key, samgraph_tensor_t *out) { hetero_nodes_tensor(key, "samgraph_get_graph_node_type", 0, out); }
+void samgraph_get_graph_node_local(uint64_t key, samgraph_tensor_t *out) { hetero_nodes_tensor(key, "samgraph_get_graph_node_local", 1, out); }
+void samgraph_get_graph_node_slot(uint64_t key, samgraph_tensor_t *out) { hetero_nodes_tensor(key, "samgraph_get_graph_node_slot", 2, out); }
+void samgraph_get_graph_typed_nodes(uint64_t key, int t, samgraph_tensor_t *out) {
+  auto &E = Engine::Get();
+  auto *b = hetero_batch(key, "samgraph_get_graph_typed_nodes");
+  const uint32_t *base = b->het_words + E.HetBaseAt() + hetero_type(t, "samgraph_get_graph_typed_nodes");
+  fill(out, b->het_typed + base[0], (int64_t)(base[1] - base[0]), 1, 1, GGMS_I32, E.batch_device_type(), E.trainer_device());
+}
+void samgraph_get_graph_feat_of_type(uint64_t key, int t, samgraph_tensor_t *out) {
+  auto &E = Engine::Get();
+  auto *b = hetero_batch(key, "samgraph_get_graph_feat_of_type");
+  const uint32_t *base = b->het_words + E.HetBaseAt() + hetero_type(t, "samgraph_get_graph_feat_of_type");
+  fill(out, (char *)b->feat + (size_t)base[0] * E.batch_feat_row_bytes(), (int64_t)(base[1] - base[0]), (int64_t)E.ds.feat_dim, 2,
+       E.batch_feat_dtype(), E.batch_device_type(), E.trainer_device());
+}
+size_t samgraph_get_graph_num_src_of_type(uint64_t key, int l, int t) {
+  auto &E = Engine::Get();
+  auto *b = hetero_batch(key, "samgraph_get_graph_num_src_of_type");
+  SAM_CHECK(l >= 0 && (size_t)l < E.cfg.fanout.size(), "samgraph_get_graph_num_src_of_type: no such layer");
+  return b->het_words[E.HetCutsAt() + (size_t)l * E.ds.num_node_type + hetero_type(t, "samgraph_get_graph_num_src_of_type")];
+}
+size_t samgraph_get_graph_num_dst_of_type(uint64_t key, int l, int t) { // num_dst(l) = num_src(l + 1); the last: its own cut
+  auto &E = Engine::Get();
+  auto *b = hetero_batch(key, "samgraph_get_graph_num_dst_of_type");
+  SAM_CHECK(l >= 0 && (size_t)l < E.cfg.fanout.size(), "samgraph_get_graph_num_dst_of_type: no such layer");
+  return b->het_words[E.HetCutsAt() + (size_t)(l + 1) * E.ds.num_node_type + hetero_type(t, "samgraph_get_graph_num_dst_of_type")];
+}
+static void hetero_rel_tensor(uint64_t key, int l, int r, const char *who, int which, samgraph_tensor_t *out) {
+  auto &E = Engine::Get();
+  auto *b = hetero_batch(key, who);
+  const uint32_t *off = hetero_offsets(b, l, r, who);
+  uint32_t *p = (which == 0 ? b->het_row : which == 1 ? b->het_col : b->het_eid)[l];
+  fill(out, p + off[0], (int64_t)(off[1] - off[0]), 1, 1, GGMS_I32, E.batch_device_type(), E.trainer_device());
+}
+void samgraph_get_graph_rel_row(uint64_t key, int l, int r, samgraph_tensor_t *out) { hetero_rel_tensor(key, l, r, "samgraph_get_graph_rel_row", 0, out); }
+void samgraph_get_graph_rel_col(uint64_t key, int l, int r, samgraph_tensor_t *out) { hetero_rel_tensor(key, l, r, "samgraph_get_graph_rel_col", 1, out); }
+void samgraph_get_graph_rel_edge_ids(uint64_t key, int l, int r, samgraph_tensor_t *out) { hetero_rel_tensor(key, l, r, "samgraph_get_graph_rel_edge_ids", 2, out); }
+size_t samgraph_get_graph_rel_num_edges(uint64_t key, int l, int r) {
+  auto *b = hetero_batch(key, "samgraph_get_graph_rel_num_edges");
+  const uint32_t *off = hetero_offsets(b, l, r, "samgraph_get_graph_rel_num_edges");
+  return off[1] - off[0];
+}
+size_t samgraph_num_node_type(void) {
+  hetero_need("samgraph_num_node_type");
+  return Engine::Get().ds.num_node_type;
+}
+int samgraph_relation_src_type(int r) {
+  hetero_need("samgraph_relation_src_type");
+  auto &E = Engine::Get();
+  SAM_CHECK(r >= 0 && (size_t)r < E.ds.rel_src_type.size(), "samgraph_relation_src_type: no such relation");
+  return E.ds.rel_src_type[r];
+}
+int samgraph_relation_dst_type(int r) {
+  hetero_need("samgraph_relation_dst_type");
+  auto &E = Engine::Get();
+  SAM_CHECK(r >= 0 && (size_t)r < E.ds.rel_dst_type.size(), "samgraph_relation_dst_type: no such relation");
+  return E.ds.rel_dst_type[r];
+}
 // config key feat_learnable: the gradient of the current batch's rows moves the table; the live table and its state
 void samgraph_update_graph_feat(uint64_t key, const void *grad, size_t num_rows, size_t dim, void *caller_stream) {
   Engine::Get().UpdateGraphFeat(key, grad, num_rows, dim, (hipStream_t)caller_stream);

@@ -43,7 +43,7 @@ inline hipStream_t to_stream(ggms_stream_t s) { return reinterpret_cast<hipStrea
 // grid is part of the result:
 //   dim3(1): k_record, k_status_copy, k_closure_mark, k_prefetch_cap, k_small_scan / k_small_scan2, k_sort_small,
 //            k_tile_prefix_t, k_induced_kept;
-//   k_drop_prefix (one workgroup per layer), k_batch_handoff (one workgroup per 16 KiB of each segment, no loop),
+//   k_hetero_cuts (one workgroup per cut), k_drop_prefix (one workgroup per layer), k_batch_handoff (one workgroup per 16 KiB of each segment, no loop),
 //   k_map_rest_all's grid.y (one row of workgroups per deferred job; grid.x is capped);
 //   k_copy_prefix (256 workgroups whatever the count), k_probe_copy16 and k_fabric_probe (measuring tools);
 //   k_weighted_draw: its thread count IS the reference's task -> RNG stream map (min(tasks, 512 K) threads, stride

@@ -144,7 +144,7 @@ def build_prob_prefix_table(indptr, weights, num_threads=8):
 
 def write_dataset(path, graph, feat=None, label=None, valid_frac=0.02, test_frac=0.05, feat_dtype="F32", weights=None,
                   minimal=False, train_edges=None, edge_feat=None, edge_feat_dtype="F32", edge_time=None, edge_type=None,
-                  num_edge_type=None):
+                  num_edge_type=None, node_type=None, num_node_type=None):
     """Write a dataset directory in the reference's on-disk format (datagen/README.md:37-51,
     samgraph/common/constant.cc:23-51, engine.cc:109-443): meta.txt (tab separated) + raw little-endian
     arrays: indptr/indices/train_set/test_set/valid_set/cache_by_* uint32, feat row-major, label int64;
@@ -161,6 +161,8 @@ def write_dataset(path, graph, feat=None, label=None, valid_frac=0.02, test_frac
     edge_type (one uint8 per edge, in the order of indices, non-decreasing inside every node's list -- see
     sort_lists_by_type -- and below num_edge_type, 1 .. 32) adds edge_type.bin and the meta key NUM_EDGE_TYPE, the
     relations `sample_type khop_typed` has a fanout for.
+    node_type (one uint8 per node id, below num_node_type, 1 .. 32) adds node_type.bin and the meta key NUM_NODE_TYPE,
+    the types a heterogeneous batch groups its nodes by (relation_types derives consistent relations from them).
     minimal: what a sampling + extract run needs and nothing that costs minutes at papers100M size -- one-node
     valid / test sets instead of random slices of the complement, no cache_by_random.bin."""
     import os
@@ -223,6 +225,11 @@ def write_dataset(path, graph, feat=None, label=None, valid_frac=0.02, test_frac
         edge_type.tofile(os.path.join(path, "edge_type.bin"))
     else:
         assert num_edge_type is None, "num_edge_type without edge_type"
+    if node_type is not None:
+        node_type = _checked_node_types(node_type, num_node_type, n)
+        node_type.tofile(os.path.join(path, "node_type.bin"))
+    else:
+        assert num_node_type is None, "num_node_type without node_type"
     if label is not None:
         np.ascontiguousarray(label, dtype=np.int64).tofile(os.path.join(path, "label.bin"))
     if weights is not None:  # tables of the weighted samplers (engine.cc:372-384 loads them by these names)
@@ -245,7 +252,37 @@ def write_dataset(path, graph, feat=None, label=None, valid_frac=0.02, test_frac
             f.write(f"EDGE_FEAT_DATA_TYPE\t{edge_feat_dtype}\n")
         if edge_type is not None:
             f.write(f"NUM_EDGE_TYPE\t{int(num_edge_type)}\n")
+        if node_type is not None:
+            f.write(f"NUM_NODE_TYPE\t{int(num_node_type)}\n")
     return path
+
+
+MAX_NODE_TYPES = 32  # GGMS_MAX_NODE_TYPES
+
+
+def _checked_node_types(node_type, num_node_type, num_node):
+    """node_type as the uint8 array the dataset stores, or an AssertionError that names what is wrong with it."""
+    assert num_node_type is not None and 1 <= int(num_node_type) <= MAX_NODE_TYPES, \
+        f"num_node_type: 1 .. {MAX_NODE_TYPES} (GGMS_MAX_NODE_TYPES), not {num_node_type}"
+    a = np.asarray(node_type)
+    assert a.shape == (num_node,), f"node_type: one type per node ({num_node}), not {a.shape}"
+    over = np.flatnonzero((a < 0) | (a >= int(num_node_type)))
+    assert over.size == 0, (f"node_type: node {int(over[0]) if over.size else 0} has type "
+                            f"{int(a[over[0]]) if over.size else 0}, not below num_node_type = {num_node_type}")
+    return np.ascontiguousarray(a, dtype=np.uint8)
+
+
+def relation_types(indptr, indices, node_type, num_node_type):
+    """Relations that are consistent with the node types by construction: for a list entry p of owner v (the edge's
+    destination; indices[p] is its source) etype[p] = type(v) * T + type(indices[p]), T = num_node_type, so relation r
+    joins source type r % T to destination type r // T and there are T * T of them (T * T <= 32: the sampler's bound on
+    NUM_EDGE_TYPE).  The result is in the order of `indices`; sort_lists_by_type makes the CSR khop_typed wants of it."""
+    T = int(num_node_type) if num_node_type is not None else 0
+    ip = np.asarray(indptr, dtype=np.int64)
+    nt = _checked_node_types(node_type, num_node_type, ip.size - 1)
+    assert T * T <= 32, f"relation_types: {T} node types give {T * T} relations, above 32 (GGMS_MAX_EDGE_TYPES)"
+    owner = np.repeat(np.arange(ip.size - 1), np.diff(ip))
+    return (nt[owner].astype(np.uint32) * T + nt[np.asarray(indices, dtype=np.int64)]).astype(np.uint8)
 
 
 def first_unsorted_list(indptr, edge_time):

@@ -385,6 +385,96 @@ def induced_edges(graph, nodes, local_of, max_edges, num_nodes_dev=None, want_ei
     return row, col, eid, counts
 
 
+MAX_NODE_TYPES = 32   # GGMS_MAX_NODE_TYPES
+HETERO_MAX_CUTS = 17  # GGMS_HETERO_MAX_CUTS
+
+
+def hetero_nodes(node_type, num_type, nodes, num_nodes_dev=None, cut_base=None, cut_words=(), max_nodes=None, out=None,
+                 workspace=None):
+    """ggms_hetero_nodes: the nodes of a batch grouped by node type.  node_type: a device uint8 tensor, one byte per node
+    id, values below num_type; nodes: the batch's ids (int32), the first n = min(num_nodes_dev[0], max_nodes) count
+    (num_nodes_dev: a device int64 tensor; without it n = max_nodes, default len(nodes)).  cut_base: a device int64
+    tensor, cut_words: indices into it -- cut k is cut_base[cut_words[k]].  Returns a dict: ntype (uint8; 255 for an id
+    that is no node), local (rank inside the type), slot (= base[ntype] + local), typed_nodes (typed_nodes[slot[i]] =
+    nodes[i]), base (int32, num_type + 1 words: base[t] = entries of a type below t), cut_counts (int32,
+    (len(cut_words), num_type): the types of nodes[0, min(cut, n))).  Entries behind n are left alone.  out: a dict of
+    tensors to write into (fresh ones unless given); workspace: an int32 tensor of at least
+    ggms_hetero_nodes_workspace_bytes (a fresh one unless given)."""
+    _require_gpu(_i32(nodes))
+    _require_gpu(node_type)
+    assert node_type.dtype == torch.uint8 and node_type.is_contiguous()
+    dev = nodes.device
+    T, B = int(num_type), len(cut_words)
+    mn = int(max_nodes) if max_nodes is not None else nodes.numel()
+    assert mn <= nodes.numel()
+    o = dict(out) if out is not None else {}
+    o.setdefault("ntype", torch.empty(max(1, mn), dtype=torch.uint8, device=dev))
+    for name in ("local", "slot", "typed_nodes"):
+        o.setdefault(name, torch.empty(max(1, mn), dtype=torch.int32, device=dev))
+    o.setdefault("base", torch.empty(max(1, T + 1), dtype=torch.int32, device=dev))
+    o.setdefault("cut_counts", torch.empty((B, max(1, T)), dtype=torch.int32, device=dev))
+    for name in ("ntype", "local", "slot", "typed_nodes"):
+        _require_gpu(o[name])
+        assert o[name].is_contiguous() and o[name].numel() >= mn, f"hetero_nodes: {name} is shorter than max_nodes"
+    assert o["ntype"].dtype == torch.uint8 and o["base"].numel() >= T + 1 and o["cut_counts"].numel() >= B * T
+    for name in ("local", "slot", "typed_nodes", "base", "cut_counts"):
+        assert o[name].dtype == torch.int32 and o[name].is_contiguous()
+    if num_nodes_dev is not None:
+        assert num_nodes_dev.dtype == torch.int64 and num_nodes_dev.is_cuda
+    if B:
+        assert cut_base is not None and cut_base.dtype == torch.int64 and cut_base.is_cuda and cut_base.is_contiguous()
+        assert all(0 <= int(w) < cut_base.numel() for w in cut_words)
+    need = lib().ggms_hetero_nodes_workspace_bytes(mn, T)
+    ws = workspace if workspace is not None else _workspace(need, dev)
+    c_words = (C.c_uint32 * max(1, B))(*[int(w) for w in cut_words])
+    check(lib().ggms_hetero_nodes(_ptr(node_type), node_type.numel(), T, _ptr(nodes), mn, _ptr(num_nodes_dev),
+                                  _ptr(cut_base), c_words, B, _ptr(o["ntype"]), _ptr(o["local"]), _ptr(o["slot"]),
+                                  _ptr(o["typed_nodes"]), _ptr(o["base"]), _ptr(o["cut_counts"]), _ptr(ws),
+                                  ws.numel() * 4, _stream()), "ggms_hetero_nodes")
+    return o
+
+
+def hetero_edges(rows, cols, etypes, num_rel, counts, local, eids=None, max_edges=None, out=None, rel_offsets=None,
+                 workspace=None):
+    """ggms_hetero_edges: every layer's edges grouped by relation (stable) and renumbered through `local`
+    (hetero_nodes): per layer i the first E = min(counts[COUNT_EDGES(i)], max_edges[i]) entries of rows[i] / cols[i] /
+    etypes[i] (uint8) / eids[i] count; entry e of relation r goes to q = off[r] + its rank among the layer's entries of r,
+    out_row[q] = local[rows[i][e]], out_col[q] = local[cols[i][e]], out_eid[q] = eids[i][e].  counts: a device int64
+    tensor in the batch counts layout.  Returns (out_rows, out_cols, out_eids or None, rel_offsets): rel_offsets is int32
+    of shape (L, num_rel + 1).  out: (out_rows, out_cols, out_eids) lists to write into; workspace as in hetero_nodes."""
+    L, R = len(rows), int(num_rel)
+    _require_gpu(counts)
+    dev = counts.device
+    assert counts.dtype == torch.int64 and counts.is_contiguous()
+    _require_gpu(_i32(local))
+    for t in list(rows) + list(cols) + (list(eids) if eids is not None else []):
+        _require_gpu(_i32(t))
+    for t in etypes:
+        _require_gpu(t)
+        assert t.dtype == torch.uint8  # (any byte offset: a slice of a larger tensor is fine)
+    me = [int(x) for x in max_edges] if max_edges is not None else [min(r.numel(), c.numel()) for r, c in zip(rows, cols)]
+    if out is None:
+        fresh = lambda: [torch.empty(max(1, m), dtype=torch.int32, device=dev) for m in me]  # noqa: E731
+        out = (fresh(), fresh(), fresh() if eids is not None else None)
+    out_rows, out_cols, out_eids = out
+    assert (out_eids is None) == (eids is None)
+    for ts in (out_rows, out_cols, out_eids):
+        for t, m in zip(ts or [], me):
+            _require_gpu(_i32(t))
+            assert t.numel() >= m, "hetero_edges: an output tensor is shorter than its layer's bound"
+    if rel_offsets is None:
+        rel_offsets = torch.empty((max(1, L), R + 1), dtype=torch.int32, device=dev)
+    assert rel_offsets.dtype == torch.int32 and rel_offsets.is_contiguous() and rel_offsets.numel() >= L * (R + 1)
+    c_me = (C.c_size_t * max(1, L))(*me)
+    arr = lambda ts: (C.c_void_p * max(1, L))(*[t.data_ptr() for t in ts]) if ts is not None else None  # noqa: E731
+    need = lib().ggms_hetero_edges_workspace_bytes(c_me, L, R)
+    ws = workspace if workspace is not None else _workspace(need, dev)
+    check(lib().ggms_hetero_edges(arr(rows), arr(cols), arr(eids), arr(etypes), c_me, L, R, _ptr(counts), _ptr(local),
+                                  local.numel(), arr(out_rows), arr(out_cols), arr(out_eids), _ptr(rel_offsets), _ptr(ws),
+                                  ws.numel() * 4, _stream()), "ggms_hetero_edges")
+    return out_rows, out_cols, out_eids, rel_offsets
+
+
 def sample_weighted_khop_prefix(graph, prob_prefix_table, inp, fanout, states):
     """GPUSampleWeightedKHopPrefix (cuda_sampling_weighted_khop_prefix.cu:145-246)."""
     return _sample("ggms_sample_weighted_khop_prefix", WEIGHTED_KHOP_PREFIX, graph, inp, fanout, states,

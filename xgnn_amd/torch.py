@@ -20,7 +20,8 @@ for _name in ("init start num_class feat_dim num_epoch steps_per_epoch get_next_
               "trace_step_begin_now trace_step_end_now dump_trace forward_barrier wait_one_child log_step_by_key "
               "get_log_step_value_by_key data_init sample_init train_init extract_start num_local_step "
               "um_sample_init switch_init feat_row_bytes num_negative get_graph_num_excluded "
-              "get_graph_num_induced").split():
+              "get_graph_num_induced get_graph_num_src_of_type get_graph_num_dst_of_type get_graph_rel_num_edges "
+              "num_node_type relation_src_type relation_dst_type").split():
     globals()[_name] = getattr(_basics, _name)
 
 # DataType code -> (numpy typestr, torch dtype); common/common.h:38-46, adapter.cc:33-53
@@ -150,6 +151,50 @@ def get_graph_induced_edge_feat(batch_key):
     """Config keys induced_subgraph and edge_feat: (num_induced, EDGE_FEAT_DIM) rows of the edge table, row k that of
     induced edge k."""
     return _get("samgraph_get_graph_induced_edge_feat", batch_key)
+
+
+def get_graph_node_type(batch_key):
+    """Config key hetero_batch: the node type of every input node (uint8)."""
+    return _get("samgraph_get_graph_node_type", batch_key)
+
+
+def get_graph_node_local(batch_key):
+    """Config key hetero_batch: per input node its rank inside its type -- the id the per-relation blocks use."""
+    return _get("samgraph_get_graph_node_local", batch_key)
+
+
+def get_graph_node_slot(batch_key):
+    """Config key hetero_batch: per input node the row of get_graph_feat that holds its features (with the key the rows
+    are grouped by type): base[type] + node_local.  Labels, seed ids and the homogeneous row / col index input nodes;
+    this maps them to the typed view."""
+    return _get("samgraph_get_graph_node_slot", batch_key)
+
+
+def get_graph_typed_nodes(batch_key, node_type):
+    """Config key hetero_batch: the global ids of the batch's nodes of one type, in batch order."""
+    return _get("samgraph_get_graph_typed_nodes", batch_key, node_type)
+
+
+def get_graph_feat_of_type(batch_key, node_type):
+    """Config key hetero_batch: the feature rows of get_graph_typed_nodes(key, t), a view of get_graph_feat's buffer (a
+    type's rows are one contiguous slice), in the dtype the gather delivered."""
+    return _get("samgraph_get_graph_feat_of_type", batch_key, node_type)
+
+
+def get_graph_rel_row(batch_key, layer_idx, relation):
+    """Config key hetero_batch: the source end of every edge of one relation of the layer, as a rank inside the
+    relation's source type (relation_src_type), in the sampler's order."""
+    return _get("samgraph_get_graph_rel_row", batch_key, layer_idx, relation)
+
+
+def get_graph_rel_col(batch_key, layer_idx, relation):
+    """Config key hetero_batch: the destination end, a rank inside the relation's destination type."""
+    return _get("samgraph_get_graph_rel_col", batch_key, layer_idx, relation)
+
+
+def get_graph_rel_edge_ids(batch_key, layer_idx, relation):
+    """Config key hetero_batch: the CSR positions of the relation's edges of the layer."""
+    return _get("samgraph_get_graph_rel_edge_ids", batch_key, layer_idx, relation)
 
 
 def get_graph_edge_time(batch_key, layer_idx):
