@@ -862,6 +862,56 @@ int ggms_hetero_edges(const ggms_id_t *const *row, const ggms_id_t *const *col,
                       void *workspace, size_t workspace_bytes, ggms_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Typed feature tables (an extension; DGL / PyG keep one feature tensor per node type): one table per node type, each
+ * with its own row width and element type, gathered for a heterogeneous batch into ONE buffer of per-type blocks.
+ *
+ * ggms_gather_typed
+ *   tables          a HOST array of T = num_type entries (1 .. GGMS_MAX_NODE_TYPES)
+ *   typed_nodes, base_dev   exactly as ggms_hetero_nodes writes them: the batch's ids grouped by type and the T + 1 words
+ *                   that say where each group starts.  The groups are clamped so that nothing behind max_nodes is read
+ *                   and no two overlap: b[t] = max over u <= t of min(base_dev[u], max_nodes)
+ *   cnt_t           = b[t + 1] - b[t]
+ *   rb_t            = dim_t x ggms_dtype_bytes(out_dtype_t): the bytes of an output row of type t
+ *   out_offset_dev  written by the kernel: off[0] = 0, off[t + 1] = round_up(off[t] + cnt_t x rb_t, 16) -- every type's
+ *                   block starts 16-byte aligned, whatever the other types' widths are
+ *   block t         cnt_t dense rows at out + off[t].  Block row j comes from slot s = b[t] + j and node
+ *                   v = typed_nodes[s]; its table row is row_of_node[v], or v - first_node_t with row_of_node == NULL
+ *   conversion      that of ggms_gather_scatter_convert for the same dtype pair: equal types move the bits, widening is
+ *                   exact, narrowing rounds to nearest even
+ *   zero rows       an entry with v >= num_node, or whose table row is >= num_rows_t (or, without row_of_node, lies
+ *                   before first_node_t), never indexes a table; its output row is zero bytes
+ *   dim == 0        the type has no table: it occupies no bytes (off[t + 1] = off[t]), nothing is read or written for it
+ *   nothing is written behind off[T]; between a block's last row and the next block's start lie only the pad bytes,
+ *   which are written as zero.
+ * ggms_gather_typed_out_bytes = max_nodes x max_t rb_t + 16 x T (host arithmetic; 0 for arguments out of range).
+ *
+ * Argument errors -- a null pointer, T of 0 or above GGMS_MAX_NODE_TYPES, a dtype outside F32 / F16 / BF16, a table base
+ * or `out` that is not aligned to its element, out_bytes below ggms_gather_typed_out_bytes, a row of 8192 chunks or more
+ * (a chunk is the widest of 16 / 8 / 4 / 2 / 1 bytes -- elements, when the gather converts -- that divides the row and
+ * keeps both sides aligned), max_nodes >= 2^32 - 1024 -- return GGMS_ERR_INVALID with a message that names the argument,
+ * before any device call.  max_nodes == 0 is GGMS_OK with `off` written as zeros.  No allocation, no synchronisation, no
+ * host round trip, no atomics; the bytes do not depend on the grid.  One launch per (source dtype, output dtype, chunk
+ * width) combination present among the tables -- fixed by the table set, not by the batch; the launches honour
+ * GGMS_DEBUG_GRID_CAP and GGMS_EXTRACT_BLOCKS like the other gathers, and a timer armed with ggms_launch_timer_arm
+ * rides on the first of them.
+ * ------------------------------------------------------------------------- */
+typedef struct {
+  const void *table;   /* device (or device-mapped host) base; ignored when dim == 0 */
+  uint64_t num_rows;   /* rows of the table */
+  uint32_t dim;        /* elements per row; 0: the type has no table, nothing is read or written for it */
+  int32_t src_dtype;   /* GGMS_F32 | GGMS_F16 | GGMS_BF16 */
+  int32_t out_dtype;   /* one of the three; == src_dtype is the plain copy */
+  uint32_t first_node; /* used when row_of_node == NULL: row = node - first_node */
+} ggms_typed_table_t;
+
+size_t ggms_gather_typed_out_bytes(const ggms_typed_table_t *tables, uint32_t num_type, size_t max_nodes);
+
+int ggms_gather_typed(void *out, size_t out_bytes, const ggms_typed_table_t *tables /* HOST, T entries */,
+                      uint32_t num_type, const ggms_id_t *typed_nodes, const uint32_t *base_dev /* T + 1 */,
+                      size_t max_nodes, const uint32_t *row_of_node /* device, num_node words, or NULL */,
+                      size_t num_node, uint64_t *out_offset_dev /* T + 1 words */, ggms_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * arch4's batch with early feature prefetch -- DoGPUSampleDyCache (cuda/cuda_loops.cc:294-524).  The layers of
  * ggms_sample_batch, except:
  *   - after the second-to-last layer's table fill, every neighbour of every node entered so far (n2o[0, k)) is

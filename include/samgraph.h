@@ -240,6 +240,23 @@ size_t samgraph_get_graph_rel_num_edges(uint64_t key, int layer_idx, int relatio
 size_t samgraph_num_node_type(void);
 int samgraph_relation_src_type(int relation);
 int samgraph_relation_dst_type(int relation);
+/* Extensions for config key typed_feat = on (needs hetero_batch = on, and through it arch1 with _sample_type 10): the
+ * feature store is one table PER NODE TYPE.  The dataset carries, for every type t below NUM_NODE_TYPE, the meta keys
+ * NODE_FEAT_DIM_<t> (0: the type has no features) and NODE_FEAT_DATA_TYPE_<t> (F32, F16 or BF16), and node_feat_<t>.bin
+ * for every type with a table: one row per node of the type, row k that of the type's k-th node in ascending node id
+ * (datagen.write_dataset(node_feat=[...])).  A missing key or file and a file of another size than (nodes of type t) x
+ * dim x element size are fatal at init, by name and with both numbers.  feat.bin is neither mapped nor uploaded.  Refused
+ * by name: typed_feat without hetero_batch, with feat_learnable, with feat_store_dtype, with SAMGRAPH_EMPTY_FEAT /
+ * SAMGRAPH_FAKE_FEAT_DIM, and a table type outside the three.  A batch's rows are gathered by ggms_gather_typed
+ * (include/ggms.h) over the grouped node list into per-type blocks of ONE buffer, every block 16-byte aligned;
+ * feat_out_dtype sets every type's delivered dtype, without it every type arrives in its own.
+ *   samgraph_get_graph_feat_of_type(key, t)   (nodes of type t in the batch, dim_t) in type t's delivered dtype: a VIEW of
+ *     the batch's buffer at the type's offset word, not a copy; (cnt_t, 0) for a type without a table
+ *   samgraph_feat_dim_of_type(t), samgraph_feat_dtype_of_type(t)   the type's row width; its delivered ggms_dtype code
+ *   samgraph_get_graph_feat(key)              fatal by name: there is no single matrix
+ * Without the key nothing is allocated, enqueued or changed, and the two new entry points are fatal. */
+size_t samgraph_feat_dim_of_type(int node_type);
+int samgraph_feat_dtype_of_type(int node_type);
 /* a batch's buffers stay valid while its retain count is > 0 */
 void samgraph_batch_retain(uint64_t key);
 void samgraph_batch_release(uint64_t key);

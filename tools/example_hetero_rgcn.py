@@ -14,6 +14,10 @@ views of one buffer), the blocks with ids local to their types (get_graph_rel_ro
 destination counts of every layer.  A layer's destination nodes are the first num_dst_of_type nodes of each type's
 group, so the next layer's input is the head of this layer's output -- no re-indexing between layers.  The seeds' logits
 are read back through get_graph_node_type / get_graph_node_local of the first num_seeds input nodes.
+--typed-feat: the dataset gets one feature table PER NODE TYPE (config key typed_feat): type 0 keeps the 16 float32
+columns, type 1 gets 8 of them as float16, type 2 has no features at all.  The model then starts with a linear input
+projection per type that has features -- get_graph_feat_of_type(key, t) is (nodes of the type, feat_dim_of_type(t)) in
+feat_dtype_of_type(t) -- and an nn.Embedding indexed by typed_nodes for the type that has none.
 Prints the loss of every epoch; it falls.
 """
 import argparse
@@ -34,7 +38,7 @@ T = 3
 TYPE_FANOUT = [[2] * 9, [2] * 9]  # by layer id: every relation, two neighbours each
 
 
-def make_dataset(path, seed=5):
+def make_dataset(path, seed=5, typed_feat=False):
     g = datagen.make_graph("tiny", seed=seed)
     ip, ix, n = g["indptr"], g["indices"], g["meta"]["num_node"]
     rng = np.random.RandomState(seed)
@@ -48,9 +52,22 @@ def make_dataset(path, seed=5):
     mean = np.bincount(owner, weights=feat[ix, 1], minlength=n) / np.maximum(np.diff(ip.astype(np.int64)), 1)
     label = nt.astype(np.int64) * 4 + (feat[:, 0] > 0.5) * 2 + (mean > 0.5)
     g["meta"] = dict(g["meta"], feat_dim=dim, num_class=4 * T)
+    node_feat = [feat[nt == 0], feat[nt == 1][:, :8].astype(np.float16), None] if typed_feat else None
     datagen.write_dataset(path, g, feat=feat, label=label, minimal=True, edge_type=et, num_edge_type=T * T, node_type=nt,
-                          num_node_type=T)
+                          num_node_type=T, node_feat=node_feat)
     return path
+
+
+class TypedInput(torch.nn.Module):
+    """typed_feat: a linear projection per type that has features, an embedding per node for a type that has none."""
+
+    def __init__(self, dims, num_nodes, d_out):
+        super().__init__()
+        self.proj = torch.nn.ModuleList([torch.nn.Linear(d, d_out) if d else torch.nn.Embedding(num_nodes, d_out) for d in dims])
+        self.dims = dims
+
+    def forward(self, rows, typed_nodes):
+        return [self.proj[t](rows[t].float()) if d else self.proj[t](typed_nodes[t].long()) for t, d in enumerate(self.dims)]
 
 
 class RelLayer(torch.nn.Module):
@@ -80,27 +97,33 @@ def main():
     ap.add_argument("--batch-size", type=int, default=256)
     ap.add_argument("--hidden", type=int, default=64)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--typed-feat", action="store_true")
     args = ap.parse_args()
     tmp = None
     if args.dataset is None:
         tmp = tempfile.TemporaryDirectory()
-        args.dataset = make_dataset(tmp.name)
+        args.dataset = make_dataset(tmp.name, typed_feat=args.typed_feat)
     L, R = len(TYPE_FANOUT), len(TYPE_FANOUT[0])
     sam.config({"dataset_path": args.dataset, "_arch": sam.builtin_archs["arch1"]["arch"],
                 "_sample_type": sam.sample_types["khop_typed"], "type_fanout": TYPE_FANOUT, "hetero_batch": "on",
                 "batch_size": args.batch_size, "num_epoch": args.epochs, "_cache_policy": sam.cache_policies["degree"],
                 "cache_percentage": 0.0, "max_sampling_jobs": 10, "max_copying_jobs": 1, "omp_thread_num": 4,
                 "num_layer": L, "num_hidden": args.hidden, "lr": 0.003, "dropout": 0.0, "sampler_ctx": "cuda:0",
-                "trainer_ctx": "cuda:0", "seed": args.seed})
+                "trainer_ctx": "cuda:0", "seed": args.seed, **({"typed_feat": "on"} if args.typed_feat else {})})
     sam.init()
     dev = torch.device("cuda", 0)
     torch.manual_seed(args.seed)
     num_type = sam.num_node_type()
     rel = [(r, sam.relation_src_type(r), sam.relation_dst_type(r)) for r in range(R)]
     rel = [x for x in rel if x[1] != 255]  # a relation without an edge has no signature
-    dims = [sam.feat_dim()] + [args.hidden] * (L - 1) + [sam.num_class()]
+    dims = [args.hidden if args.typed_feat else sam.feat_dim()] + [args.hidden] * (L - 1) + [sam.num_class()]
     layers = torch.nn.ModuleList([RelLayer(dims[i], dims[i + 1], R, num_type) for i in range(L)]).to(dev)
-    opt = torch.optim.Adam(layers.parameters(), lr=0.01)
+    params = list(layers.parameters())
+    if args.typed_feat:
+        num_node = sam.get_dataset_label().numel()
+        inp = TypedInput([sam.feat_dim_of_type(t) for t in range(num_type)], num_node, args.hidden).to(dev)
+        params += list(inp.parameters())
+    opt = torch.optim.Adam(params, lr=0.01)
     steps = sam.steps_per_epoch()
     losses = []
     for epoch in range(args.epochs):
@@ -109,6 +132,8 @@ def main():
             sam.sample_once()
             key = sam.get_next_batch()
             h = [sam.get_graph_feat_of_type(key, t) for t in range(num_type)]  # views: a type's rows are one slice
+            if args.typed_feat:
+                h = [torch.relu(x) for x in inp(h, [sam.get_graph_typed_nodes(key, t) for t in range(num_type)])]
             for i in range(L):  # layer 0 = the outermost hop
                 assert all(h[t].shape[0] >= sam.get_graph_num_src_of_type(key, i, t) for t in range(num_type))
                 blocks = [(r, s, d, sam.get_graph_rel_row(key, i, r).long(), sam.get_graph_rel_col(key, i, r).long())

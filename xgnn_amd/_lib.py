@@ -37,6 +37,12 @@ class Typed(C.Structure):
     _fields_ = [("edge_type", C.c_void_p), ("num_type", C.c_uint32), ("type_fanout", C.POINTER(C.c_uint32))]
 
 
+class TypedTable(C.Structure):
+    """ggms_typed_table_t"""
+    _fields_ = [("table", C.c_void_p), ("num_rows", C.c_uint64), ("dim", C.c_uint32), ("src_dtype", C.c_int32),
+                ("out_dtype", C.c_int32), ("first_node", C.c_uint32)]
+
+
 class FeatureTiers(C.Structure):
     """ggms_feature_tiers_t"""
     _fields_ = [("table", C.c_void_p), ("replica", C.c_void_p), ("num_replica", C.c_uint64),
@@ -183,6 +189,8 @@ SYMBOLS = {
     "ggms_hetero_edges_workspace_bytes": (_sz, [C.POINTER(_sz), _u32, _u32]),
     "ggms_hetero_edges": (_i, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz), _u32, _u32,
                                _vp, _vp, _sz, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _sz, _vp]),
+    "ggms_gather_typed_out_bytes": (_sz, [C.POINTER(TypedTable), _u32, _sz]),
+    "ggms_gather_typed": (_i, [_vp, _sz, C.POINTER(TypedTable), _u32, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
     "ggms_hashtable_num_buckets": (_sz, [_sz]),
     "ggms_hashtable_init": (_i, [C.POINTER(HashTable), _vp]),
     "ggms_hashtable_reset": (_i, [C.POINTER(HashTable), _vp]),

@@ -128,6 +128,7 @@ SAMGRAPH_SYMBOLS = {
     "samgraph_get_graph_rel_row": (None, [_u64, _i, _i, _TP]), "samgraph_get_graph_rel_col": (None, [_u64, _i, _i, _TP]),
     "samgraph_get_graph_rel_edge_ids": (None, [_u64, _i, _i, _TP]),
     "samgraph_get_graph_rel_num_edges": (_sz, [_u64, _i, _i]),
+    "samgraph_feat_dim_of_type": (_sz, [_i]), "samgraph_feat_dtype_of_type": (_i, [_i]),
     "samgraph_num_node_type": (_sz, []), "samgraph_relation_src_type": (_i, [_i]), "samgraph_relation_dst_type": (_i, [_i]),
     "samgraph_get_graph_edge_time": (None, [_u64, _i, _TP]), "samgraph_get_graph_node_cut": (None, [_u64, _TP]),
     "samgraph_get_graph_link_time": (None, [_u64, _TP]),
@@ -197,6 +198,8 @@ class SamGraphBasics(object):
     def get_graph_num_dst_of_type(self, key, layer, t): return self.C_LIB_CTYPES.samgraph_get_graph_num_dst_of_type(key, layer, t)
     def get_graph_rel_num_edges(self, key, layer, r): return self.C_LIB_CTYPES.samgraph_get_graph_rel_num_edges(key, layer, r)
     def num_node_type(self): return self.C_LIB_CTYPES.samgraph_num_node_type()
+    def feat_dim_of_type(self, t): return self.C_LIB_CTYPES.samgraph_feat_dim_of_type(t)
+    def feat_dtype_code_of_type(self, t): return self.C_LIB_CTYPES.samgraph_feat_dtype_of_type(t)
     def relation_src_type(self, r): return self.C_LIB_CTYPES.samgraph_relation_src_type(r)
     def relation_dst_type(self, r): return self.C_LIB_CTYPES.samgraph_relation_dst_type(r)
     def num_epoch(self): return self.C_LIB_CTYPES.samgraph_num_epoch()

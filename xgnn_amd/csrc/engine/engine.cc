@@ -475,6 +475,26 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
       cfg.induced_max_edges = (size_t)v;
     }
   }
+  if (kv.count("typed_feat")) { // extension: one feature table per node type (in front of hetero_batch's own refusals)
+    if (kv["typed_feat"] != "on" && kv["typed_feat"] != "off")
+      fatal(__FILE__, __LINE__, "typed_feat = " + kv["typed_feat"] + ": on or off (the default)");
+    cfg.typed_feat = kv["typed_feat"] == "on";
+  }
+  if (cfg.typed_feat) {
+    if (!cfg.hetero)
+      fatal(__FILE__, __LINE__, "typed_feat without hetero_batch = on is not built: the typed tables are gathered over the "
+                                "batch's nodes grouped by type, which hetero_batch computes");
+    if (cfg.feat_learnable >= 0)
+      fatal(__FILE__, __LINE__, "typed_feat with feat_learnable is not built: the update moves rows of ONE F32 table; "
+                                "per-type learnable tables are a follow-up");
+    if (cfg.feat_store_dtype >= 0)
+      fatal(__FILE__, __LINE__, "typed_feat with feat_store_dtype is not built: the quantiser re-encodes ONE table; FP8 and "
+                                "Q8ROW typed tables are a follow-up");
+    for (const char *e : {"SAMGRAPH_EMPTY_FEAT", "SAMGRAPH_FAKE_FEAT_DIM"})
+      if (getenv(e))
+        fatal(__FILE__, __LINE__, std::string("typed_feat with ") + e + " is not built: the stand-in is ONE table of one "
+                                  "width; the typed tables are the dataset's own node_feat_<t>.bin");
+  }
   if (cfg.hetero) { // (the key itself and the deployment: above, in front of khop_typed's own refusals)
     if (!cfg.Typed())
       fatal(__FILE__, __LINE__, "hetero_batch with _sample_type " + std::to_string(cfg.sample_type) + " is not built: the "
@@ -561,12 +581,17 @@ void Engine::LoadDataset() {
   std::ifstream meta_file(cfg.dataset_path + "meta.txt");
   SAM_CHECK(meta_file.good(), "cannot read " + cfg.dataset_path + "meta.txt");
   std::unordered_map<std::string, size_t> meta;
+  std::unordered_map<std::string, std::string> meta_text; // NODE_FEAT_DATA_TYPE_<t>: names, read by typed_feat only
   std::string line;
   while (std::getline(meta_file, line)) {
     std::istringstream iss(line);
     std::string k, v;
     if (!(iss >> k >> v)) break;
-    if (k == "FEAT_DATA_TYPE") {
+    if (k.rfind("NODE_FEAT_DATA_TYPE_", 0) == 0) {
+      meta_text[k] = v;
+    } else if (k == "FEAT_DATA_TYPE" && cfg.typed_feat) {
+      // (the one table is neither mapped nor uploaded: whatever type it has concerns nobody)
+    } else if (k == "FEAT_DATA_TYPE") {
       SAM_CHECK(kFeatDtypeNames.count(v), "unknown FEAT_DATA_TYPE " + v);
       ds.feat_dtype = kFeatDtypeNames.at(v);
       // (an FP8 table is a source of the converting gather only: without the key its rows are moved as bytes)
@@ -620,7 +645,10 @@ void Engine::LoadDataset() {
   size_t empty_bits = 0; // SAMGRAPH_EMPTY_FEAT = k (run_config.cc:137-139, engine.cc:205-207): a 2^k-row stand-in table,
                          // node v reads row v & (2^k - 1) (gpu_mock_extract / cpu_mock_extract)
   if (const char *e = getenv("SAMGRAPH_EMPTY_FEAT")) empty_bits = std::strtoull(e, nullptr, 10);
-  if (empty_bits) {
+  if (cfg.typed_feat) {
+    // typed_feat: feat.bin is neither mapped nor uploaded; the tables are node_feat_<t>.bin (LoadTypedFeat, below)
+    ds.feat_rows = 0;
+  } else if (empty_bits) {
     SAM_CHECK(empty_bits < 32, "SAMGRAPH_EMPTY_FEAT out of range");
     ds.feat_rows = (size_t)1 << empty_bits;
     ds.feat_mask = (uint32_t)(ds.feat_rows - 1);
@@ -748,6 +776,7 @@ void Engine::LoadDataset() {
       if (nt[v] >= T)
         fatal(__FILE__, __LINE__, "hetero_batch: node_type.bin: node " + std::to_string(v) + " has the type " +
                                       std::to_string((unsigned)nt[v]) + ", NUM_NODE_TYPE is " + std::to_string(T));
+    if (cfg.typed_feat) LoadTypedFeat(meta, meta_text);
   }
   if (cfg.Typed()) { // the edge types: NUM_EDGE uint8 in CSR order, sorted inside every list, below NUM_EDGE_TYPE
     if (!meta.count("NUM_EDGE_TYPE"))
@@ -1147,6 +1176,62 @@ bool Engine::ShufflerNext(Batch *b, hipStream_t copy_stream) {
   if (sanity && (cfg.arch == kArch1 || Dedicated())) SanityCheckBatch(shuf_host_.data() + global_data_offset_ + offset, size);
   SAM_HIP(hipMemcpyAsync(b->sampler.output_nodes, shuf_dev_ + offset, size * 4, hipMemcpyDeviceToDevice, copy_stream)); // Copy1D
   return true;
+}
+
+// typed_feat: NODE_FEAT_DIM_<t> / NODE_FEAT_DATA_TYPE_<t> and node_feat_<t>.bin for every node type; every node's rank
+// inside its type (row k of a table belongs to the type's k-th node in ascending id).  Behind the node types' own check.
+void Engine::LoadTypedFeat(const std::unordered_map<std::string, size_t> &meta,
+                           const std::unordered_map<std::string, std::string> &meta_text) {
+  const size_t T = ds.num_node_type;
+  const uint8_t *nt = (const uint8_t *)ds.node_type.ptr;
+  ds.node_feat.assign(T, Dataset::NodeFeat{});
+  // one pass: the types' sizes and first ids, every node's rank, and whether the types lie one behind the other
+  std::vector<uint32_t> rank(ds.num_node);
+  std::vector<size_t> seen(T, 0);
+  bool sorted = true;
+  for (size_t v = 0; v < ds.num_node; ++v) {
+    const uint8_t t = nt[v];
+    if (seen[t] == 0) ds.node_feat[t].first_node = (uint32_t)v;
+    if (v > 0 && t < nt[v - 1]) sorted = false;
+    rank[v] = (uint32_t)seen[t]++;
+  }
+  size_t table_bytes = 0;
+  for (size_t t = 0; t < T; ++t) {
+    Dataset::NodeFeat &nf = ds.node_feat[t];
+    nf.rows = seen[t];
+    const std::string ts = std::to_string(t), dim_key = "NODE_FEAT_DIM_" + ts, dt_key = "NODE_FEAT_DATA_TYPE_" + ts;
+    if (!meta.count(dim_key))
+      fatal(__FILE__, __LINE__, "typed_feat: meta.txt lacks " + dim_key + " (datagen.write_dataset(node_feat=[...]); 0 for a "
+                                "type without features)");
+    if (!meta_text.count(dt_key))
+      fatal(__FILE__, __LINE__, "typed_feat: meta.txt lacks " + dt_key + " (F32, F16 or BF16)");
+    nf.dim = meta.at(dim_key);
+    const std::string &name = meta_text.at(dt_key);
+    if (!kFeatDtypeNames.count(name) || !ggms::is_float_dtype(kFeatDtypeNames.at(name)))
+      fatal(__FILE__, __LINE__, "typed_feat with " + dt_key + " = " + name + " is not built: a typed table is F32, F16 or "
+                                "BF16; FP8 and Q8ROW typed tables are a follow-up");
+    nf.dtype = kFeatDtypeNames.at(name);
+    if (nf.dim == 0) continue;
+    const std::string file = "node_feat_" + ts + ".bin";
+    struct stat st;
+    if (stat((cfg.dataset_path + file).c_str(), &st) != 0)
+      fatal(__FILE__, __LINE__, "typed_feat: " + cfg.dataset_path + file + " is missing (" + std::to_string(nf.rows) +
+                                " rows of " + dim_key + " = " + std::to_string(nf.dim) + " " + name + " elements, one per "
+                                "node of type " + ts + " in ascending node id)");
+    const size_t want = nf.rows * nf.row_bytes();
+    if ((size_t)st.st_size != want)
+      fatal(__FILE__, __LINE__, "typed_feat: " + file + " has " + std::to_string((size_t)st.st_size) + " bytes, (nodes of type " +
+                                ts + ") x " + dim_key + " x the element size is " + std::to_string(nf.rows) + " x " +
+                                std::to_string(nf.dim) + " x " + std::to_string(ggms_dtype_bytes(nf.dtype)) + " = " +
+                                std::to_string(want));
+    if (want) nf.file = MapFile(file, want, false);
+    table_bytes += want;
+  }
+  if (!sorted) ds.node_rank.swap(rank);
+  log_info("typed_feat: " + std::to_string(T) + " tables, " + std::to_string(table_bytes) + " bytes of HBM; " +
+           (sorted ? std::string("node_type.bin is non-decreasing in the node id: no rank table (row = node - the type's "
+                                 "first id)")
+                   : "a rank table of 4 x NUM_NODE = " + std::to_string(4 * ds.num_node) + " bytes is uploaded"));
 }
 
 // ------------------------------------------------------------------ device graph (GGMS topology)
@@ -1611,8 +1696,23 @@ void Engine::BuildCache() {
       feat_src_ = nullptr;
     } else if (cfg.arch == kArch1) {
       // arch1: the whole table lives in HBM and is gathered directly (cuda_loops_arch1.cc:61)
-      d_feat_ = dev_upload(feat, ds.feat.bytes, bs);
-      feat_src_ = d_feat_;
+      if (cfg.typed_feat) { // one table per node type in place of the one table, and the rank table where one is needed
+        const size_t T = ds.num_node_type;
+        d_node_feat_.assign(T, nullptr);
+        typed_tables_.assign(T, ggms_typed_table_t{});
+        for (size_t t = 0; t < T; ++t) {
+          const Dataset::NodeFeat &nf = ds.node_feat[t];
+          // (a type that has a width but no node: dev_upload of 0 bytes is still an allocation, so the leaf gets a table
+          // base and 0 rows -- every rank lies beyond it -- and not the null pointer it refuses)
+          if (nf.dim) d_node_feat_[t] = dev_upload(nf.file.ptr, nf.file.bytes, bs);
+          typed_tables_[t] = ggms_typed_table_t{d_node_feat_[t], nf.rows, (uint32_t)nf.dim, nf.dtype,
+                                                typed_feat_dtype(t), nf.first_node};
+        }
+        if (!ds.node_rank.empty()) d_node_rank_ = (uint32_t *)dev_upload(ds.node_rank.data(), ds.node_rank.size() * 4, bs);
+      } else {
+        d_feat_ = dev_upload(feat, ds.feat.bytes, bs);
+        feat_src_ = d_feat_;
+      }
       if (cfg.edge_feat) d_edge_feat_ = dev_upload(ds.edge_feat.ptr, ds.edge_feat.bytes, bs); // the edge table, beside it
       if (cfg.Temporal()) d_edge_time_ = (uint32_t *)dev_upload(ds.edge_time.ptr, ds.edge_time.bytes, bs); // and the times
       if (cfg.feat_learnable >= 0) { // the upload is the learnable table's initial value; Adagrad's accumulator starts at 0
@@ -1785,7 +1885,17 @@ void Engine::TrainInit(int worker_id, const std::string &ctx) {
     auto b = std::make_unique<Batch>();
     b->slot = (int)s;
     b->trainer.Alloc(max_edges_, max_unique_, max_seeds_, cfg.sample_type == GGMS_RANDOM_WALK);
-    SAM_HIP(hipMalloc(&b->feat, max_unique_ * batch_feat_row_bytes())); // rows as delivered
+    if (cfg.typed_feat) { // per-type blocks, every one 16-byte aligned; the T + 1 offsets and their host copy
+      typed_feat_bytes_ = ggms_gather_typed_out_bytes(typed_tables_.data(), ds.num_node_type, max_unique_);
+      SAM_CHECK(typed_feat_bytes_ > 0, "typed_feat: the batch bound is out of ggms_gather_typed's range");
+      SAM_HIP(hipMalloc(&b->feat, typed_feat_bytes_));
+      SAM_HIP(hipMalloc((void **)&b->het_off_dev, (ds.num_node_type + 1) * 8));
+      SAM_HIP(hipMemset(b->het_off_dev, 0, (ds.num_node_type + 1) * 8));
+      SAM_HIP(hipHostMalloc((void **)&b->het_off, (ds.num_node_type + 1) * 8));
+      std::memset(b->het_off, 0, (ds.num_node_type + 1) * 8);
+    } else {
+      SAM_HIP(hipMalloc(&b->feat, max_unique_ * batch_feat_row_bytes())); // rows as delivered
+    }
     SAM_HIP(hipMalloc((void **)&b->label, max_seeds_ * 8));
     if (cfg.link_prediction) {
       SAM_HIP(hipMalloc((void **)&b->edge_ids, cfg.batch_size * 4));
@@ -2127,7 +2237,9 @@ void Engine::EnqueueGather(Batch *b, hipStream_t ss) {
   const bool can_miss = num_cached_nodes_ < ds.num_node;
   const bool gather_counts = cfg.UseGPUCache() && (mock || ((num_replica_ || cache_table_) && can_miss));
   static const bool lean_off = [] { const char *e = getenv("SAMGRAPH_LEAN_EXTRACT"); return e && e[0] == '0'; }(); // A/B hook
-  b->lean = !lean_off && !StagedHostTier() && !gather_counts && !node_access_dev_;
+  // (typed_feat: the gather is one launch per chunk class and writes offset words the host reads -- a timer on its first
+  // launch does not say "the rows are out", so such a batch takes the event sequence)
+  b->lean = !lean_off && !StagedHostTier() && !gather_counts && !node_access_dev_ && !cfg.typed_feat;
   if (!remote && b->lean) {
     SAM_HIP(hipMemcpyAsync(b->counts, b->trainer.counts_dev, CountsBytes(L), hipMemcpyDeviceToHost, ss));
     SAM_HIP(hipEventRecord(b->ev_done, ss)); // labels and counts are out; the rows: gather_timer
@@ -2180,7 +2292,13 @@ void Engine::EnqueueGather(Batch *b, hipStream_t ss) {
     }
     dyn_seq = dyn_seq_;
   }
-  if (StagedHostTier()) {
+  if (cfg.typed_feat) {
+    // one table per node type: the grouped list and its base words, as ggms_hetero_nodes wrote them, in place of the
+    // one-table gather; the blocks' offsets go to the host behind it
+    SAM_GGMS(ggms_gather_typed(b->feat, typed_feat_bytes_, typed_tables_.data(), ds.num_node_type, b->het_typed,
+                               b->het_words_dev + HetBaseAt(), max_unique_, d_node_rank_, ds.num_node, b->het_off_dev, xs));
+    SAM_HIP(hipMemcpyAsync(b->het_off, b->het_off_dev, (ds.num_node_type + 1) * 8, hipMemcpyDeviceToHost, xs));
+  } else if (StagedHostTier()) {
     StagedExtract(b, ss, xs);
   } else if (cfg.dynamic_cache) { // DoDynamicCacheFeatureCopy (cuda/cuda_loops.cc:1073-1215) as one gather
     SAM_GGMS(ggms_extract_dynamic(b->feat, b->trainer.input_nodes, max_unique_, n_in, dyn_stamps_, dyn_seq,
@@ -2357,6 +2475,8 @@ void Engine::Finish(Batch *b, Batch *prev) {
   // feature bytes: what the gather wrote to the batch (rows in the delivered dtype); miss bytes: what it read from the
   // host tier (rows in the table's dtype)
   const double out_row_bytes = (double)batch_feat_row_bytes();
+  // (typed_feat: the rows differ in width by type; what the gather wrote is the end of the last block)
+  const double feature_bytes = cfg.typed_feat ? (double)b->het_off[ds.num_node_type] : b->num_input * out_row_bytes;
   const double row_bytes = (double)ds.feat_row_bytes();
   // item codes: profiler.h:58-140 (kLogL1NumSample = 0, kLogL1NumNode = 1, kLogL1SampleTime = 3,
   // kLogL1CopyTime = 6, kLogL1FeatureBytes = 9, kLogL1MissBytes = 13; epoch items :119-137)
@@ -2364,11 +2484,11 @@ void Engine::Finish(Batch *b, Batch *prev) {
   prof.LogStep(b->key, 1, (double)b->num_input);
   prof.LogStep(b->key, 3, ms_sample * 1e-3);
   prof.LogStep(b->key, 6, ms_copy * 1e-3);
-  prof.LogStep(b->key, 9, b->num_input * out_row_bytes);
+  prof.LogStep(b->key, 9, feature_bytes);
   prof.LogStep(b->key, 13, b->num_miss * row_bytes);
   prof.LogEpochAdd(b->key, 0 /*kLogEpochSampleTime*/, ms_sample * 1e-3);
   prof.LogEpochAdd(b->key, 8 /*kLogEpochCopyTime*/, s_copy_epoch);
-  prof.LogEpochAdd(b->key, 12 /*kLogEpochFeatureBytes*/, b->num_input * out_row_bytes);
+  prof.LogEpochAdd(b->key, 12 /*kLogEpochFeatureBytes*/, feature_bytes);
   prof.LogEpochAdd(b->key, 13 /*kLogEpochMissBytes*/, b->num_miss * row_bytes);
   prof.LogEpochAdd(b->key, 15 /*kLogEpochNumSample*/, (double)edges);
   if (BatchSampledElsewhere()) { // what the hand-off (arch5: the unpack) moved and its time

@@ -142,6 +142,10 @@ struct RunConfig {
   // to their types' lists (ggms_hetero_nodes / ggms_hetero_edges behind the sampler) -- and the feature rows are gathered
   // in the grouped order
   bool hetero = false;
+  // extension (config key `typed_feat` = on; needs hetero_batch = on): the feature store is one table PER NODE TYPE, each
+  // with its own width and element type (node_feat_<t>.bin, NODE_FEAT_DIM_<t>, NODE_FEAT_DATA_TYPE_<t>); a batch's rows are
+  // gathered by ggms_gather_typed into per-type blocks of one buffer.  feat.bin is then neither mapped nor uploaded
+  bool typed_feat = false;
   size_t staged_serial_epochs = 0; // host-staged path: the first N epochs run the reference's serial, per-phase-timed sequence
   size_t staged_serial_steps = 0;  // ... or this worker's first N batches
   // worker 0 ranks the nodes at init: pre_sample (sampled input nodes) or presample_static (L-hop closures)
@@ -191,6 +195,19 @@ struct Dataset {
   HostArray node_type;
   uint32_t num_node_type = 0;
   std::vector<uint8_t> rel_src_type, rel_dst_type;
+  // typed_feat: per node type its table (the mapped node_feat_<t>.bin; dim 0: the type has none), the number of nodes of
+  // the type (= the table's rows) and its first node id.  Row k of a table belongs to the type's k-th node in ascending
+  // id.  node_rank: every node's rank inside its type -- empty where node_type.bin is non-decreasing in the node id (the
+  // rank is then node - first_node)
+  struct NodeFeat {
+    HostArray file;
+    size_t dim = 0, rows = 0;
+    int dtype = GGMS_F32;
+    uint32_t first_node = 0;
+    size_t row_bytes() const { return dim * ggms_dtype_bytes(dtype); }
+  };
+  std::vector<NodeFeat> node_feat;
+  std::vector<uint32_t> node_rank;
   size_t edge_feat_row_bytes() const { return edge_feat_dim * ggms_dtype_bytes(edge_feat_dtype); }
 };
 
@@ -284,6 +301,9 @@ struct Batch {
   uint32_t *het_local = nullptr, *het_slot = nullptr, *het_typed = nullptr;
   std::vector<uint32_t *> het_row, het_col, het_eid;
   uint32_t *het_words_dev = nullptr, *het_words = nullptr;
+  // typed_feat: the T + 1 byte offsets of the types' blocks in `feat`, as ggms_gather_typed wrote them, and their pinned
+  // host copy, valid with the counts.  Null without the key.
+  uint64_t *het_off_dev = nullptr, *het_off = nullptr;
   uint64_t num_miss = 0;
   hipEvent_t ev_seeds = nullptr, ev_start = nullptr, ev_sampled = nullptr, ev_xstart = nullptr, ev_done = nullptr;
   // arch6 with `gpu_extract` off: the host-staged miss path (dist_loops.cc:1015-1207)
@@ -350,6 +370,8 @@ class Engine {
   int batch_feat_dtype() const { return cfg.feat_out_dtype < 0 ? ds.feat_dtype : cfg.feat_out_dtype; }
   // bytes of one row of a batch's feature buffer: always dim x batch dtype, whatever the table stores per row
   size_t batch_feat_row_bytes() const { return ds.feat_dim * ggms_dtype_bytes(batch_feat_dtype()); }
+  // typed_feat: the dtype type t's rows are delivered in (feat_out_dtype, else the table's own)
+  int typed_feat_dtype(size_t t) const { return cfg.feat_out_dtype < 0 ? ds.node_feat[t].dtype : cfg.feat_out_dtype; }
   int batch_device_type() const { return (cfg.arch == kArch0 && cfg.trainer_on_host) ? 0 : 2; } // DeviceType, common.h:48
   void Barrier(const char *what = "step");
   void *OpenPeer(const hipIpcMemHandle_t &handle, uint32_t peer, size_t bytes, const char *what);
@@ -467,6 +489,14 @@ class Engine {
   };
   size_t hetero_ws_bytes_ = 0;
   uint8_t *d_node_type_ = nullptr; // hetero_batch: the node types in HBM
+  // typed_feat: the tables in HBM (null for a type without one), the rank table (null: ranks are node - first_node), the
+  // leaf's table array and the bytes of a batch's feature buffer
+  std::vector<void *> d_node_feat_;
+  uint32_t *d_node_rank_ = nullptr;
+  std::vector<ggms_typed_table_t> typed_tables_;
+  size_t typed_feat_bytes_ = 0;
+  void LoadTypedFeat(const std::unordered_map<std::string, size_t> &meta,
+                     const std::unordered_map<std::string, std::string> &meta_text);
  public:
   // hetero_batch: where the three groups of Batch::het_words start
   size_t HetBaseAt() const { return 0; }

@@ -89,6 +89,9 @@ void samgraph_dump_trace(void) { Engine::Get().prof.DumpTrace(); }
 // ---- tensor hand-off (adapter.cc:62-193) ------------------------------------------------------
 void samgraph_get_graph_feat(uint64_t key, samgraph_tensor_t *out) {
   auto &E = Engine::Get();
+  if (E.cfg.typed_feat)
+    sam::fatal(__FILE__, __LINE__, "samgraph_get_graph_feat with typed_feat = on: there is no single feature matrix, the types' "
+                                   "rows differ in width and dtype; samgraph_get_graph_feat_of_type(key, t) hands out each block");
   auto *b = E.Current(key);
   fill(out, b->feat, (int64_t)b->num_input, (int64_t)E.ds.feat_dim, 2, E.batch_feat_dtype(), E.batch_device_type(), E.trainer_device());
 }
@@ -278,6 +281,11 @@ void samgraph_get_graph_feat_of_type(uint64_t key, int t, samgraph_tensor_t *out
   auto &E = Engine::Get();
   auto *b = hetero_batch(key, "samgraph_get_graph_feat_of_type");
   const uint32_t *base = b->het_words + E.HetBaseAt() + hetero_type(t, "samgraph_get_graph_feat_of_type");
+  if (E.cfg.typed_feat) { // the type's block of the buffer, at its offset word: (cnt_t, dim_t) in the type's delivered dtype
+    fill(out, (char *)b->feat + b->het_off[t], (int64_t)(base[1] - base[0]), (int64_t)E.ds.node_feat[t].dim, 2,
+         E.typed_feat_dtype((size_t)t), E.batch_device_type(), E.trainer_device());
+    return;
+  }
   fill(out, (char *)b->feat + (size_t)base[0] * E.batch_feat_row_bytes(), (int64_t)(base[1] - base[0]), (int64_t)E.ds.feat_dim, 2,
        E.batch_feat_dtype(), E.batch_device_type(), E.trainer_device());
 }
@@ -308,6 +316,15 @@ size_t samgraph_get_graph_rel_num_edges(uint64_t key, int l, int r) {
   const uint32_t *off = hetero_offsets(b, l, r, "samgraph_get_graph_rel_num_edges");
   return off[1] - off[0];
 }
+// config key typed_feat: one feature table per node type
+static size_t typed_feat_type(int t, const char *who) {
+  auto &E = Engine::Get();
+  if (!E.cfg.typed_feat) sam::fatal(__FILE__, __LINE__, std::string(who) + " needs the config key typed_feat = on");
+  SAM_CHECK(t >= 0 && (size_t)t < E.ds.node_feat.size(), std::string(who) + ": no such node type");
+  return (size_t)t;
+}
+size_t samgraph_feat_dim_of_type(int t) { return Engine::Get().ds.node_feat[typed_feat_type(t, "samgraph_feat_dim_of_type")].dim; }
+int samgraph_feat_dtype_of_type(int t) { return Engine::Get().typed_feat_dtype(typed_feat_type(t, "samgraph_feat_dtype_of_type")); }
 size_t samgraph_num_node_type(void) {
   hetero_need("samgraph_num_node_type");
   return Engine::Get().ds.num_node_type;

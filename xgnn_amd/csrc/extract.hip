@@ -23,88 +23,10 @@
 #include <hip/hip_ext.h>
 
 #include "ggms_device.h"
-#include "row_formats.h"
+#include "row_chunks.h"
 
 namespace ggms {
 
-template <int BYTES> struct ChunkT;
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-template <> struct ChunkT<16> { using type = u32x4_t; };
-template <> struct ChunkT<8> { using type = u32x2_t; };
-template <> struct ChunkT<4> { using type = uint32_t; };
-template <> struct ChunkT<2> { using type = uint16_t; };
-template <> struct ChunkT<1> { using type = uint8_t; };
-
-// ---- what a chunk is ----------------------------------------------------------------------------------------------
-// The sweep moves CHUNKS: a fixed number of elements of a row, read as Src and written as Dst.  The plain gather's
-// chunk is CB bytes on both sides.  A converting gather (ggms_*_convert: an F16 / BF16 / F32 table delivered in
-// another of the three types, or an FP8 table delivered in one of them) has chunks of EPC elements: EPC x source element bytes in, EPC x output element bytes
-// out, converted at store time -- the registers a lane holds between its loads and its first store are the SOURCE
-// chunks only, whichever side is the wider one.
-template <int CB> struct CopyChunk {
-  static constexpr bool kScaled = false; // (ScaledChunk below)
-  static constexpr int kSrcBytes = CB, kDstBytes = CB;
-  using Src = typename ChunkT<CB>::type;
-  using Dst = Src;
-  static __device__ __forceinline__ Dst convert(Src v) { return v; }
-};
-
-template <int EPC, int SRC_DT, int DST_DT> struct ConvertChunk {
-  using S = Elem<SRC_DT>;
-  using D = Elem<DST_DT>;
-  static constexpr bool kScaled = false;
-  static constexpr int kSrcBytes = EPC * (int)sizeof(typename S::bits), kDstBytes = EPC * (int)sizeof(typename D::bits);
-  using Src = typename VecT<typename S::bits, EPC>::type;
-  using Dst = typename VecT<typename D::bits, EPC>::type;
-  // every FP8 value is a bf16 number (at most 3 mantissa bits): the upper half of its f32, no rounding step
-  static constexpr bool kTruncates = (SRC_DT == GGMS_F8E4M3 || SRC_DT == GGMS_F8E5M2) && DST_DT == GGMS_BF16;
-  static __device__ __forceinline__ typename D::bits one(typename S::bits b) {
-    if constexpr (kTruncates) return (typename D::bits)(__builtin_bit_cast(uint32_t, S::to_f32(b)) >> 16);
-    else return D::from_f32(S::to_f32(b));
-  }
-  static __device__ __forceinline__ Dst convert(Src v) {
-    if constexpr (EPC == 1) {
-      return one(v);
-    } else {
-      Dst o;
-#pragma unroll
-      for (int e = 0; e < EPC; ++e) o[e] = one(v[e]);
-      return o;
-    }
-  }
-};
-
-// A row-scaled 8-bit table (GGMS_Q8ROW, include/ggms.h): a row is `dim` unsigned codes, zero bytes up to the next
-// multiple of 8, then the row's f32 scale and f32 bias.  The chunk is EPC code bytes; its value needs the two numbers
-// that belong to the ROW, so convert takes them beside the chunk's bits: the sweep loads a row's 8-byte trailer with
-// the row's pointer (the lane that resolves the row keeps both) and hands scale and bias to the chunk's lane the way
-// it hands out the pointer.  value = fl32(fl32(float(code) * scale) + bias), two IEEE operations: NOT an FMA, whose
-// single rounding gives other bits (hipcc contracts a * b + c by default, through __fmul_rn / __fadd_rn too, which
-// are plain operators in its headers; the pragma takes the licence away for these two operations).
-template <int EPC, int DST_DT> struct ScaledChunk {
-  using D = Elem<DST_DT>;
-  static constexpr bool kScaled = true;
-  static constexpr int kSrcBytes = EPC, kDstBytes = EPC * (int)sizeof(typename D::bits);
-  using Src = typename VecT<uint8_t, EPC>::type;
-  using Dst = typename VecT<typename D::bits, EPC>::type;
-  static __device__ __forceinline__ typename D::bits one(uint8_t code, float scale, float bias) {
-#pragma clang fp contract(off)
-    const float scaled = (float)code * scale;
-    const float value = scaled + bias;
-    return D::from_f32(value);
-  }
-  static __device__ __forceinline__ Dst convert(Src v, uint32_t scale_bits, uint32_t bias_bits) {
-    const float scale = __builtin_bit_cast(float, scale_bits), bias = __builtin_bit_cast(float, bias_bits);
-    if constexpr (EPC == 1) {
-      return one(v, scale, bias);
-    } else {
-      Dst o;
-#pragma unroll
-      for (int e = 0; e < EPC; ++e) o[e] = one(v[e], scale, bias);
-      return o;
-    }
-  }
-};
 // which tier served a row (0 = not counted); counters[tier - 1] in ggms_extract_tiered
 constexpr uint32_t kTierHost = 1, kTierRemote = 2, kTierLocal = 3, kTierReplica = 4;
 
@@ -428,6 +350,12 @@ bool take_armed_timer(hipEvent_t *start, hipEvent_t *stop) {
   return true;
 }
 
+// GGMS_EXTRACT_BLOCKS (default 256): the most workgroups any row gather is launched with (launch_chunks has the story)
+int gather_max_blocks() {
+  static const int max_blocks = [] { const char *e = getenv("GGMS_EXTRACT_BLOCKS"); int v = e ? atoi(e) : 256; return v > 0 ? v : 256; }();
+  return max_blocks;
+}
+
 // One row-gather launch: with a timer armed on this thread the kernel goes out through hipExtLaunchKernel carrying
 // the timer's events (start = the dispatch's own begin timestamp, stop = its completion signal) -- no marker packet
 // before or behind it; otherwise the plain launch.
@@ -465,7 +393,7 @@ static int launch_chunks(char *out, Rows rows, const uint32_t *dst_index, size_t
   // gather and the sampler beside it, profiles/r03_ab_gather_grid.txt): with 16 x 16-B loads per lane in flight that
   // already streams at the rate of a full-occupancy launch, and the free wave slots let the next batch's
   // latency-bound sampling kernels run beside the gather on another stream.
-  static const int max_blocks = [] { const char *e = getenv("GGMS_EXTRACT_BLOCKS"); int v = e ? atoi(e) : 256; return v > 0 ? v : 256; }();
+  const int max_blocks = gather_max_blocks();
   int grid = grid_for(n_max, kBlock);
   if (grid > max_blocks) grid = max_blocks;
   // 16 independent chunk loads per lane once a row has >= 8 chunks, else 8 (measured: 0.58 -> 0.60 of peak at 400-B
@@ -533,14 +461,7 @@ static bool row_move(int src_dt, int dst_dt, size_t dim, RowMove &m) {
   return true;
 }
 
-// A chunk's wider side is at most 16 bytes (one load or store instruction per chunk and side, consecutive lanes on
-// consecutive addresses): 8 elements between the 16-bit types, 4 when one side is f32.  Measured against 8-element
-// chunks for those (a 16-B load with two 16-B stores, two 16-B loads with a 16-B store): profiles/feat_convert_ab.txt.
-// An FP8 source follows the same rule: 8 elements into a 16-bit type (8-B load, 16-B store), 4 into f32 (4-B load,
-// 16-B store); profiles/fp8_table_ab.txt.
-constexpr int convert_max_epc(size_t src_es, size_t dst_es) { return (int)(16 / (src_es > dst_es ? src_es : dst_es)); }
-
-// A chunk FAMILY: one converting pair in every chunk width it is built in (kMaxEpc: the rule above)
+// A chunk FAMILY: one converting pair in every chunk width it is built in (kMaxEpc: convert_max_epc, row_chunks.h)
 template <int SRC_DT, int DST_DT> struct ConvertFamily {
   static constexpr int kSrcDt = SRC_DT, kDstDt = DST_DT;
   static constexpr int kMaxEpc = convert_max_epc(sizeof(typename Elem<SRC_DT>::bits), sizeof(typename Elem<DST_DT>::bits));

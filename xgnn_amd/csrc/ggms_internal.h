@@ -173,5 +173,7 @@ int prefetch_list_impl(const GraphView &g, const uint32_t *nodes, size_t max_nod
 // extract.hip: hands the launch timer armed on this thread (include/ggms.h) to the launch about to be issued -- its
 // start / stop events for hipExtLaunchKernel -- and disarms it; false if none is armed
 bool take_armed_timer(hipEvent_t *start, hipEvent_t *stop);
+// extract.hip: GGMS_EXTRACT_BLOCKS, the cap on a row gather's workgroups (read once)
+int gather_max_blocks();
 
 } // namespace ggms

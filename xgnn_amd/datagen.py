@@ -144,7 +144,7 @@ def build_prob_prefix_table(indptr, weights, num_threads=8):
 
 def write_dataset(path, graph, feat=None, label=None, valid_frac=0.02, test_frac=0.05, feat_dtype="F32", weights=None,
                   minimal=False, train_edges=None, edge_feat=None, edge_feat_dtype="F32", edge_time=None, edge_type=None,
-                  num_edge_type=None, node_type=None, num_node_type=None):
+                  num_edge_type=None, node_type=None, num_node_type=None, node_feat=None):
     """Write a dataset directory in the reference's on-disk format (datagen/README.md:37-51,
     samgraph/common/constant.cc:23-51, engine.cc:109-443): meta.txt (tab separated) + raw little-endian
     arrays: indptr/indices/train_set/test_set/valid_set/cache_by_* uint32, feat row-major, label int64;
@@ -163,6 +163,10 @@ def write_dataset(path, graph, feat=None, label=None, valid_frac=0.02, test_frac
     relations `sample_type khop_typed` has a fanout for.
     node_type (one uint8 per node id, below num_node_type, 1 .. 32) adds node_type.bin and the meta key NUM_NODE_TYPE,
     the types a heterogeneous batch groups its nodes by (relation_types derives consistent relations from them).
+    node_feat (needs node_type; one entry per node type: a 2-d float32 / float16 numpy array, a 2-d float32 / float16 /
+    bfloat16 torch tensor, or None for a type without features) adds node_feat_<t>.bin for every type that has a table
+    and the meta keys NODE_FEAT_DIM_<t> (0 without a table) / NODE_FEAT_DATA_TYPE_<t>, the tables of config key
+    `typed_feat`.  Entry t has one row per node of type t; row k belongs to the k-th such node in ascending node id.
     minimal: what a sampling + extract run needs and nothing that costs minutes at papers100M size -- one-node
     valid / test sets instead of random slices of the complement, no cache_by_random.bin."""
     import os
@@ -230,6 +234,10 @@ def write_dataset(path, graph, feat=None, label=None, valid_frac=0.02, test_frac
         node_type.tofile(os.path.join(path, "node_type.bin"))
     else:
         assert num_node_type is None, "num_node_type without node_type"
+    typed = _checked_node_feat(node_feat, node_type, num_node_type) if node_feat is not None else None
+    for t, (table, _) in enumerate(typed or []):
+        if table is not None:
+            table.tofile(os.path.join(path, f"node_feat_{t}.bin"))
     if label is not None:
         np.ascontiguousarray(label, dtype=np.int64).tofile(os.path.join(path, "label.bin"))
     if weights is not None:  # tables of the weighted samplers (engine.cc:372-384 loads them by these names)
@@ -254,6 +262,9 @@ def write_dataset(path, graph, feat=None, label=None, valid_frac=0.02, test_frac
             f.write(f"NUM_EDGE_TYPE\t{int(num_edge_type)}\n")
         if node_type is not None:
             f.write(f"NUM_NODE_TYPE\t{int(num_node_type)}\n")
+        for t, (table, dtype_name) in enumerate(typed or []):
+            f.write(f"NODE_FEAT_DIM_{t}\t{0 if table is None else table.shape[1]}\n")
+            f.write(f"NODE_FEAT_DATA_TYPE_{t}\t{dtype_name}\n")
     return path
 
 
@@ -270,6 +281,37 @@ def _checked_node_types(node_type, num_node_type, num_node):
     assert over.size == 0, (f"node_type: node {int(over[0]) if over.size else 0} has type "
                             f"{int(a[over[0]]) if over.size else 0}, not below num_node_type = {num_node_type}")
     return np.ascontiguousarray(a, dtype=np.uint8)
+
+
+def _checked_node_feat(node_feat, node_type, num_node_type):
+    """node_feat as [(the (rows, dim) array a file stores -- bfloat16 as its uint16 bits -- or None, dtype name)], one
+    per node type, or an AssertionError that names the type and what is wrong with its entry."""
+    assert node_type is not None, "node_feat: needs node_type / num_node_type (one table per node type)"
+    T = int(num_node_type)
+    assert len(node_feat) == T, f"node_feat: one entry per node type ({T}), not {len(node_feat)}"
+    counts = np.bincount(node_type, minlength=T)
+    out = []
+    for t, a in enumerate(node_feat):
+        if a is None:
+            out.append((None, "F32"))
+            continue
+        if hasattr(a, "detach"):  # a torch tensor
+            import torch
+            names = {torch.float32: "F32", torch.float16: "F16", torch.bfloat16: "BF16"}
+            assert a.dtype in names, f"node_feat[{t}]: dtype {a.dtype} (F32, F16 or BF16)"
+            name = names[a.dtype]
+            a = a.detach().cpu().contiguous()
+            a = a.view(torch.int16).numpy().view(np.uint16) if name == "BF16" else a.numpy()
+        else:
+            a = np.asarray(a)
+            names = {np.dtype(np.float32): "F32", np.dtype(np.float16): "F16"}
+            assert a.dtype in names, f"node_feat[{t}]: dtype {a.dtype} (F32, F16 or BF16)"
+            name = names[a.dtype]
+        assert a.ndim == 2, f"node_feat[{t}]: a 2-d (rows, dim) array, not rank {a.ndim}"
+        assert a.shape[0] == counts[t], f"node_feat[{t}]: one row per node of type {t} ({int(counts[t])}), not {a.shape[0]}"
+        assert a.shape[1] >= 1, f"node_feat[{t}]: rows of dim 0 (None is a type without features)"
+        out.append((np.ascontiguousarray(a), name))
+    return out
 
 
 def relation_types(indptr, indices, node_type, num_node_type):

@@ -475,6 +475,61 @@ def hetero_edges(rows, cols, etypes, num_rel, counts, local, eids=None, max_edge
     return out_rows, out_cols, out_eids, rel_offsets
 
 
+def typed_tables(tables, out_dtypes=None, first_nodes=None):
+    """The ggms_typed_table_t array of a table set.  tables: one entry per node type, a contiguous 2-D device tensor
+    (float32, float16 or bfloat16) or None for a type without features; out_dtypes: the delivered dtype per type (None,
+    or a None entry: the table's own); first_nodes: the first node id of every type, for calls without a rank table."""
+    T = len(tables)
+    arr = (_lib.TypedTable * max(1, T))()
+    for t, tab in enumerate(tables):
+        if tab is None:
+            continue
+        _require_gpu(tab)
+        assert tab.dim() == 2 and tab.is_contiguous(), f"typed_tables: table {t} is not a contiguous 2-D tensor"
+        od = out_dtypes[t] if out_dtypes is not None and out_dtypes[t] is not None else tab.dtype
+        arr[t] = _lib.TypedTable(tab.data_ptr(), tab.shape[0], tab.shape[1], _dtype_code(tab.dtype), _dtype_code(od),
+                                 int(first_nodes[t]) if first_nodes is not None else 0)
+    return arr
+
+
+def gather_typed_out_bytes(c_tables, num_type, max_nodes):
+    """ggms_gather_typed_out_bytes (0 for arguments out of range)."""
+    return lib().ggms_gather_typed_out_bytes(c_tables, num_type, max_nodes)
+
+
+def gather_typed(c_tables, num_type, typed_nodes, base, row_of_node=None, num_node=None, max_nodes=None, out=None,
+                 offsets=None):
+    """ggms_gather_typed: the feature rows of a heterogeneous batch, one table per node type (c_tables: typed_tables()),
+    into one uint8 buffer of per-type blocks.  typed_nodes / base: as hetero_nodes returns them; row_of_node: a device
+    int32 tensor, a node's row in its type's table (None: row = node - first_node of the type); num_node: ids at or above
+    it give zero rows (default: len(row_of_node); without a rank table no bound: every id is taken for a node, and a
+    type's table alone decides which rows exist).  Returns (out, offsets): block t is out[offsets[t]:] as
+    (base[t + 1] - base[t], dim_t) rows of the type's delivered dtype; offsets is a device int64 tensor of num_type + 1
+    words.  out / offsets: tensors to write into (fresh ones unless given)."""
+    _require_gpu(_i32(typed_nodes))
+    _require_gpu(_i32(base))
+    dev = typed_nodes.device
+    T = int(num_type)
+    mn = int(max_nodes) if max_nodes is not None else typed_nodes.numel()
+    assert mn <= typed_nodes.numel() and base.numel() >= T + 1
+    if row_of_node is not None:
+        _require_gpu(_i32(row_of_node))
+        num_node = row_of_node.numel() if num_node is None else num_node
+        assert num_node <= row_of_node.numel()
+    elif num_node is None:
+        num_node = 1 << 32  # no bound: ids are 32-bit
+    if out is None:
+        out = torch.empty(max(16, gather_typed_out_bytes(c_tables, T, mn)), dtype=torch.uint8, device=dev)
+    if offsets is None:
+        offsets = torch.empty(T + 1, dtype=torch.int64, device=dev)
+    _require_gpu(out)
+    assert out.dtype == torch.uint8 and out.is_contiguous()
+    assert offsets.dtype == torch.int64 and offsets.is_cuda and offsets.is_contiguous() and offsets.numel() >= T + 1
+    check(lib().ggms_gather_typed(_ptr(out), out.numel(), c_tables, T, _ptr(typed_nodes), _ptr(base), mn,
+                                  _ptr(row_of_node), int(num_node), _ptr(offsets), _stream()), "ggms_gather_typed")
+    return out, offsets
+
+
 def sample_weighted_khop_prefix(graph, prob_prefix_table, inp, fanout, states):
     """GPUSampleWeightedKHopPrefix (cuda_sampling_weighted_khop_prefix.cu:145-246)."""
     return _sample("ggms_sample_weighted_khop_prefix", WEIGHTED_KHOP_PREFIX, graph, inp, fanout, states,

@@ -21,7 +21,7 @@ for _name in ("init start num_class feat_dim num_epoch steps_per_epoch get_next_
               "get_log_step_value_by_key data_init sample_init train_init extract_start num_local_step "
               "um_sample_init switch_init feat_row_bytes num_negative get_graph_num_excluded "
               "get_graph_num_induced get_graph_num_src_of_type get_graph_num_dst_of_type get_graph_rel_num_edges "
-              "num_node_type relation_src_type relation_dst_type").split():
+              "num_node_type relation_src_type relation_dst_type feat_dim_of_type").split():
     globals()[_name] = getattr(_basics, _name)
 
 # DataType code -> (numpy typestr, torch dtype); common/common.h:38-46, adapter.cc:33-53
@@ -177,8 +177,15 @@ def get_graph_typed_nodes(batch_key, node_type):
 
 def get_graph_feat_of_type(batch_key, node_type):
     """Config key hetero_batch: the feature rows of get_graph_typed_nodes(key, t), a view of get_graph_feat's buffer (a
-    type's rows are one contiguous slice), in the dtype the gather delivered."""
+    type's rows are one contiguous slice), in the dtype the gather delivered.  With typed_feat = on: the type's own block,
+    (nodes of the type, feat_dim_of_type(t)) in feat_dtype_of_type(t), a view of the batch's buffer; (n, 0) for a type
+    without a table."""
     return _get("samgraph_get_graph_feat_of_type", batch_key, node_type)
+
+
+def feat_dtype_of_type(node_type):
+    """Config key typed_feat: the torch dtype type t's rows are delivered in (feat_out_dtype, else the table's own)."""
+    return _DT[_basics.feat_dtype_code_of_type(node_type)][1]
 
 
 def get_graph_rel_row(batch_key, layer_idx, relation):
