@@ -1227,7 +1227,7 @@ int ggms_batch_handoff(const ggms_copy_seg_t *segs, uint32_t num_segs, ggms_stre
  *                       on the device from the batch's counts words (the output nodes': num_output, from the host).
  *   ggms_queue_unpack:  ONE launch on a stream of the TRAINER's device reads the lengths from the slot's header and
  *                       copies the arrays and the counts words into the trainer's buffers.
- * `slot` is a device address of the slot (host memory registered with hipHostRegister(..., Mapped) and translated by
+ * `slot` is a device address of the slot (pinned host memory from hipHostMalloc(..., Mapped), translated by
  * hipHostGetDevicePointer, or any device memory), 16-byte aligned.  Every length is clamped to the layout's bound,
  * so neither launch writes past a slot or a buffer the bounds describe.  The header's `seq` word is never written by
  * a launch: it belongs to the host's ticket protocol.  A launch timer armed on the calling thread rides on the launch.

@@ -421,10 +421,39 @@ def test_configs3_papers100m_graphsage_feature_shards_full_size():
     assert 0.45 < st["remote_row_fraction"] < 0.55 and st["rows_by_tier"]["host"] == 0
 
 
+_PIN_PROBE = """
+import ctypes as C, sys
+hip = C.CDLL("libamdhip64.so")
+blocks = []
+for _ in range(int(sys.argv[2])):
+    p = C.c_void_p()
+    rc = hip.hipHostMalloc(C.byref(p), C.c_size_t(int(sys.argv[1])), C.c_uint(0))
+    if rc != 0:
+        sys.exit(3 if rc == 2 else "hipHostMalloc -> %d" % rc)  # 2: hipErrorOutOfMemory
+    blocks.append(p)
+for p in blocks:
+    hip.hipHostFree(p)
+"""
+
+
+def _can_pin(nbytes, blocks):
+    """Whether this machine lets `blocks` allocations of `nbytes` pinned host memory exist at once (hipHostMalloc in a
+    child process, freed again): what a machine may pin can be far less than its RAM, and nothing the machine publishes
+    says how much it is."""
+    r = subprocess.run([sys.executable, "-c", _PIN_PROBE, str(nbytes), str(blocks)], capture_output=True, text=True, timeout=300)
+    assert r.returncode in (0, 3), r.stderr[-2000:]
+    return r.returncode == 0
+
+
 def test_configs4_friendster_pinsage_hybrid_store_full_size():
     """BASELINE configs[4] at its real size on two ranks: Friendster-scale CSR (N 65.6 M, 256-dim rows), PinSAGE random
     walks, hybrid GGMS -- the hotter half of the rows in HBM (a quarter of those replicated on both ranks, the rest
-    sharded), every row also in pinned host DRAM; one gather serves replica, local shard, peer shard and host rows."""
+    sharded), every row also in pinned host DRAM; one gather serves replica, local shard, peer shard and host rows.
+    Each of the two ranks pins the whole table, 2 x 67.2 GB on one machine: a machine that cannot pin that much cannot
+    hold this configuration, and the test skips there before it starts anything."""
+    table_bytes = 65_608_366 * 256 * 4
+    if not _can_pin(table_bytes, 2):
+        pytest.skip(f"this machine cannot pin 2 x {table_bytes / 1e9:.1f} GB of host memory (hipHostMalloc: out of memory)")
     d = _two_ranks_full_size(["--preset", "friendster", "--sample-type", "random_walk", "--fanout", "5,5,5",
                               "--store", "hybrid", "--cache-ratio", "0.5", "--replicate-frac", "0.25"], timeout=1200)
     assert d["rows_verified"] and d["n_gpus"] == 2 and "N=65608366" in d["config"]["workload"]

@@ -3,7 +3,6 @@ trainer processes unpack it onto their GPU and gather its rows.  On a one-GPU bo
 (SAMGRAPH_FORCE_DEVICE=0); a case that needs two real devices skips when fewer are visible."""
 import ctypes as C
 import json
-import mmap
 import os
 import subprocess
 import sys
@@ -173,7 +172,7 @@ def _hip():
 
 @pytest.mark.gpu
 def test_queue_pack_unpack_leaf_against_numpy():
-    """ggms_queue_pack into a slot of registered (mapped) host memory, then ggms_queue_unpack out of it: random lengths
+    """ggms_queue_pack into a slot of pinned (mapped) host memory, then ggms_queue_unpack out of it: random lengths
     with 0 and byte sizes that are not a multiple of 16, every length read from device words (the pack: the batch's
     counts; the unpack: the slot's header), a length beyond its bound clamped to it.  The header carries key,
     num_output, num_layer and the counts words verbatim; the slot's seq word and every byte past each length (in the
@@ -186,12 +185,10 @@ def test_queue_pack_unpack_leaf_against_numpy():
     lay = ops.queue_layout(max_edges, max_input, max_output, has_data=True)
     assert lay.slot_bytes % 4096 == 0 and lay.off_row[0] == 512
     size = lay.slot_bytes
-    mm = mmap.mmap(-1, size)  # MAP_SHARED | MAP_ANONYMOUS, as the engine's queue
-    host = np.frombuffer(mm, dtype=np.uint8)
-    addr = C.addressof(C.c_char.from_buffer(mm))
-    assert hip.hipHostRegister(C.c_void_p(addr), C.c_size_t(size), C.c_uint(2)) == 0  # hipHostRegisterMapped
+    pinned = torch.empty(size, dtype=torch.uint8, pin_memory=True)  # hipHostMalloc, as the engine's mirror of its queue
+    host = pinned.numpy()
     dptr = C.c_void_p()
-    assert hip.hipHostGetDevicePointer(C.byref(dptr), C.c_void_p(addr), C.c_uint(0)) == 0
+    assert hip.hipHostGetDevicePointer(C.byref(dptr), C.c_void_p(pinned.data_ptr()), C.c_uint(0)) == 0
     try:
         segs = [(f"row{i}", lay.off_row[i], max_edges[i]) for i in range(L)] + \
                [(f"col{i}", lay.off_col[i], max_edges[i]) for i in range(L)] + \
@@ -238,5 +235,4 @@ def test_queue_pack_unpack_leaf_against_numpy():
                 assert np.array_equal(got[:n], src[name].cpu().numpy()[:n]), (trial, name)
                 assert (got[n:] == -7).all(), (trial, name)
     finally:
-        torch.cuda.synchronize()
-        assert hip.hipHostUnregister(C.c_void_p(addr)) == 0
+        torch.cuda.synchronize()  # before the pinned pages go

@@ -49,6 +49,19 @@ def ops():
     return _ops
 
 
+@pytest.fixture(scope="module", autouse=True)
+def caches_emptied_after_the_module():
+    """The module's tables (57 and 67 GB pinned, as much HBM) stay in torch's caches when their tensors go, and pinned
+    memory counts against what every process on the machine may pin: the engine runs that later tests start would find
+    none.  Both caches are given back when the module is done."""
+    yield
+    import gc
+    gc.collect()
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    torch._C._host_emptyCache()
+
+
 @pytest.fixture(scope="module")
 def papers():
     """The papers100M-shaped CSR (N 111,059,956, E 1.62e9), generated once for the module."""

@@ -197,8 +197,7 @@ def test_closure_through_topology_shards(ops, P):
         torch.cuda.synchronize()
         ops.check_device_status("khop_closure shards")
     finally:
-        # this process goes on: the registration must not outlive the pages it pins (a later allocation at the same
-        # address would be taken for registered memory by the runtime's copies)
+        # this process goes on: the pinned pages are given back once nothing on the device reads them
         torch.cuda.synchronize()
         g = None
         host_ix.close()

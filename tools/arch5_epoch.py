@@ -3,7 +3,7 @@ queue slot and the per-step time against arch1.  Nothing here is part of bench.p
 printed as one JSON line.
 
     python tools/arch5_epoch.py rate [--preset-bounds 8000 25 10] [--fill 1.0 0.5] [--reps 20] [--rounds 3]
-        One slot of registered (mapped) host memory sized for batch 8000, fanout [25, 10].  ggms_queue_pack (the
+        One slot of pinned (mapped) host memory sized for batch 8000, fanout [25, 10].  ggms_queue_pack (the
         sampler GPU's stores into the slot, zero-copy) against hipMemcpyAsync D2H of the slot's bound size, and
         ggms_queue_unpack (the trainer GPU's loads from the slot) against hipMemcpyAsync H2D of the bound size,
         alternating, on cuda:0.  --fill: the fraction of every bound the batch uses (1.0: the same bytes as the DMA).
@@ -28,7 +28,6 @@ sys.path.insert(0, ROOT)
 
 
 def rate(a):
-    import mmap
     import numpy as np
     import torch
     from xgnn_amd import _lib, ops
@@ -42,10 +41,9 @@ def rate(a):
     _lib.check(lib.ggms_sample_batch_capacity(max_seeds, (C.c_size_t * L)(*fan), L, mi, me, C.byref(mu)), "capacity")
     lay = ops.queue_layout(list(me), mu.value, max_seeds)
     size = lay.slot_bytes
-    mm, mm_dma = mmap.mmap(-1, size), mmap.mmap(-1, size)  # the slot; the DMA copies' host side (keeps the slot intact)
-    addr, addr_dma = C.addressof(C.c_char.from_buffer(mm)), C.addressof(C.c_char.from_buffer(mm_dma))
-    for x in (addr, addr_dma):
-        assert hip.hipHostRegister(C.c_void_p(x), C.c_size_t(size), C.c_uint(2)) == 0
+    # the slot; the DMA copies' host side (keeps the slot intact): pinned, as the engine's mirror of its queue
+    mm, mm_dma = (torch.empty(size, dtype=torch.uint8, pin_memory=True) for _ in range(2))
+    addr, addr_dma = mm.data_ptr(), mm_dma.data_ptr()
     dptr = C.c_void_p()
     assert hip.hipHostGetDevicePointer(C.byref(dptr), C.c_void_p(addr), C.c_uint(0)) == 0
     dev = torch.device("cuda", 0)
@@ -116,8 +114,6 @@ def rate(a):
             "pack_over_dma_time": med["pack"] / med["dma_d2h_bound"],
             "unpack_over_dma_time": med["unpack"] / med["dma_h2d_bound"]})
     torch.cuda.synchronize()
-    for x in (addr, addr_dma):
-        assert hip.hipHostUnregister(C.c_void_p(x)) == 0
     print(json.dumps(out), flush=True)
 
 

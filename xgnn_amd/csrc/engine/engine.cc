@@ -1243,12 +1243,15 @@ static void *dev_upload(const void *host, size_t bytes, hipStream_t s) {
   return d;
 }
 
-static const void *map_host(void *host, size_t bytes) {
-  // cudaHostRegister(..., ReadOnly) + zero-copy reads (dist_engine.cc:217-241)
+static const void *map_host(const void *host, size_t bytes) {
+  // zero-copy reads of host memory (cudaHostRegister(..., ReadOnly), dist_engine.cc:217-241).  Pages a process already
+  // has cannot be registered on every machine (a GPU passed through to a virtual machine refuses hipHostRegister), so
+  // the device reads a pinned copy of them that this process allocates; the host goes on reading `host`.
   if (bytes == 0) return nullptr;
-  SAM_HIP(hipHostRegister(host, bytes, hipHostRegisterMapped));
-  void *d = nullptr;
-  SAM_HIP(hipHostGetDevicePointer(&d, host, 0));
+  void *pinned = nullptr, *d = nullptr;
+  SAM_HIP(hipHostMalloc(&pinned, bytes, hipHostMallocMapped));
+  std::memcpy(pinned, host, bytes);
+  SAM_HIP(hipHostGetDevicePointer(&d, pinned, 0));
   return d;
 }
 

@@ -434,13 +434,15 @@ class Engine {
   struct QueueCtl;
   QueueCtl *queue_ = nullptr;
   char *queue_slots_ = nullptr;     // host address of slot 0
-  char *queue_slots_dev_ = nullptr; // ... the same memory as this process's device sees it (hipHostRegister, Mapped)
+  char *queue_mirror_ = nullptr;     // this process's pinned mirror of the slots (hipHostMalloc, Mapped; QueueMap) ...
+  char *queue_mirror_dev_ = nullptr; // ... as its device sees it: what the pack / unpack launches write / read
   size_t queue_depth_ = 0;
   ggms_queue_layout_t qlay_{};
   std::unique_ptr<Batch> sbatch_; // the sampler's own batch buffers (it packs each batch before it samples the next)
   void ComputeBounds();
   void QueueInit();
   void QueueMap();
+  void CopySlot(char *dst, const char *src) const; // a message, shared slot <-> mirror slot
   ggms_queue_header_t *QueueHeader(uint64_t pos) const;
   bool QueueWait(const uint64_t *word, uint64_t want, const char *what, bool stoppable);
   void PublishRanking();   // pre_sample: sampler 0's ranking is written ...

@@ -12,8 +12,10 @@
 #include <sys/mman.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
+#include <cstring>
 #include <string>
 
 namespace sam {
@@ -25,7 +27,7 @@ struct Engine::QueueCtl {
   alignas(64) uint64_t ranking_ready; // pre_sample: sampler 0 has written ds.ranking_nodes
 };
 
-// the parent, before the fork: no GPU is touched (every process registers the slots itself, QueueMap)
+// the parent, before the fork: no GPU is touched (every process allocates its pinned mirror of the slots itself, QueueMap)
 void Engine::QueueInit() {
   static_assert(sizeof(QueueCtl) <= 4096, "the control block fits its page");
   const auto t0 = std::chrono::steady_clock::now();
@@ -44,12 +46,34 @@ void Engine::QueueInit() {
   log_info("arch5: batch queue of " + std::to_string(queue_depth_) + " slots x " + std::to_string(qlay_.slot_bytes) + " bytes");
 }
 
-// this process's device reads / writes the slots in place: pinned and mapped (cudaHostRegister, dist_engine.cc:217-241)
+// The reference pins the shared slots themselves (cudaHostRegister, dist_engine.cc:217-241).  Pages a process already
+// has cannot be registered on every machine (a GPU passed through to a virtual machine refuses hipHostRegister), and
+// pinned memory a process allocates is its own.  So every process has a pinned, mapped mirror of the ring: its device
+// packs into / unpacks out of the mirror's slot, and the host carries the message between that slot and the shared one
+// (CopySlot).  Whoever holds a ticket owns the shared slot and, with it, the same slot of its mirror.
 void Engine::QueueMap() {
-  SAM_HIP(hipHostRegister(queue_slots_, queue_depth_ * qlay_.slot_bytes, hipHostRegisterMapped));
+  SAM_HIP(hipHostMalloc((void **)&queue_mirror_, queue_depth_ * qlay_.slot_bytes, hipHostMallocMapped));
   void *d = nullptr;
-  SAM_HIP(hipHostGetDevicePointer(&d, queue_slots_, 0));
-  queue_slots_dev_ = (char *)d;
+  SAM_HIP(hipHostGetDevicePointer(&d, queue_mirror_, 0));
+  queue_mirror_dev_ = (char *)d;
+}
+
+// One slot's message from `src` to `dst`: the header behind its seq word (which only the ticket protocol writes), and
+// every array at the length the header gives, clamped to the layout's bound as the launches clamp it
+void Engine::CopySlot(char *dst, const char *src) const {
+  const ggms_queue_header_t *h = (const ggms_queue_header_t *)src;
+  const uint32_t L = qlay_.num_layer;
+  const size_t seq_bytes = sizeof(h->seq);
+  std::memcpy(dst + seq_bytes, src + seq_bytes, sizeof(*h) - seq_bytes);
+  auto copy = [&](uint64_t off, uint64_t n, uint64_t bound) { std::memcpy(dst + off, src + off, std::min(n, bound) * 4); };
+  for (uint32_t i = 0; i < L; ++i) {
+    const uint64_t n = h->counts[GGMS_COUNT_EDGES(i)];
+    copy(qlay_.off_row[i], n, qlay_.max_edges[i]);
+    copy(qlay_.off_col[i], n, qlay_.max_edges[i]);
+    if (qlay_.has_data) copy(qlay_.off_data[i], n, qlay_.max_edges[i]);
+  }
+  copy(qlay_.off_input, h->counts[GGMS_COUNT_INPUT(L)], qlay_.max_input);
+  copy(qlay_.off_output, h->num_output, qlay_.max_output);
 }
 
 ggms_queue_header_t *Engine::QueueHeader(uint64_t pos) const {
@@ -124,16 +148,18 @@ void Engine::SendOne() {
   SampleInto(b, pipes_[0]); // (pipeline 0: stream_)
   SAM_HIP(hipEventSynchronize(b->ev_sampled)); // DoGPUSample ends with a stream sync too
   const double t_sample = since(t0);
-  // send: a free slot (the ticket's), the pack, its completion, then the slot is published
+  // send: a free slot (the ticket's), the pack into its mirror, its completion, the copy, then the slot is published
   const auto t1 = clk::now();
   const uint64_t pos = __atomic_fetch_add(&queue_->enqueue_pos, 1, __ATOMIC_ACQ_REL);
   ggms_queue_header_t *h = QueueHeader(pos);
   const std::string what = "a free queue slot from the trainers (ticket " + std::to_string(pos) + ")";
   QueueWait(&h->seq, pos, what.c_str(), false);
   const ggms_queue_batch_t src = b->sampler.View();
-  SAM_GGMS(ggms_queue_pack(queue_slots_dev_ + (pos % queue_depth_) * qlay_.slot_bytes, &qlay_, &src, b->key, b->num_seeds, ss));
+  const size_t slot_off = (pos % queue_depth_) * qlay_.slot_bytes;
+  SAM_GGMS(ggms_queue_pack(queue_mirror_dev_ + slot_off, &qlay_, &src, b->key, b->num_seeds, ss));
   SAM_HIP(hipEventRecord(b->ev_done, ss));
   SAM_HIP(hipEventSynchronize(b->ev_done));
+  CopySlot((char *)h, queue_mirror_ + slot_off);
   const uint64_t status = h->counts[GGMS_COUNT_STATUS(L)], num_input = h->counts[GGMS_COUNT_INPUT(L)];
   uint64_t edges = 0;
   for (uint32_t i = 0; i < L; ++i) edges += h->counts[GGMS_COUNT_EDGES(i)];
@@ -172,8 +198,10 @@ bool Engine::Receive(Batch *b) {
 // slot goes back to the samplers as soon as that launch has completed (the timer's end: the host waits for it)
 void Engine::Unpack(Batch *b, hipStream_t xs) {
   const ggms_queue_batch_t dst = b->trainer.View();
+  const size_t slot_off = (b->queue_pos % queue_depth_) * qlay_.slot_bytes;
+  CopySlot(queue_mirror_ + slot_off, (const char *)QueueHeader(b->queue_pos));
   SAM_GGMS(ggms_launch_timer_arm(b->handoff_timer));
-  SAM_GGMS(ggms_queue_unpack(&dst, queue_slots_dev_ + (b->queue_pos % queue_depth_) * qlay_.slot_bytes, &qlay_, xs));
+  SAM_GGMS(ggms_queue_unpack(&dst, queue_mirror_dev_ + slot_off, &qlay_, xs));
   double us = 0;
   SAM_GGMS(ggms_launch_timer_elapsed_us(b->handoff_timer, &us)); // blocks until the unpack has completed
   __atomic_store_n(&QueueHeader(b->queue_pos)->seq, b->queue_pos + queue_depth_, __ATOMIC_RELEASE); // free

@@ -1014,33 +1014,38 @@ _TYPESTR = {torch.float32: "<f4", torch.float64: "<f8", torch.float16: "<f2", to
 
 
 class RegisteredHost:
-    """A host array registered for device access (hipHostRegister, mapped): what DistGraph keeps in its last slot --
-    the whole CSR in host memory, read by the sampling kernels over PCIe (dist_graph.cu:367-381) -- and what the
-    `gpu_extract` miss tier is (dist_engine.cc:217-241).  `.tensor` aliases the host pages as a device tensor."""
+    """A host array for device access: what DistGraph keeps in its last slot -- the whole CSR in host memory, read by
+    the sampling kernels over PCIe (dist_graph.cu:367-381) -- and what the `gpu_extract` miss tier is
+    (dist_engine.cc:217-241).  The reference registers the array's own pages (cudaHostRegister); pages a process already
+    has cannot be registered on every machine (a GPU passed through to a virtual machine refuses hipHostRegister), so
+    the device reads a pinned copy of the array (hipHostMalloc, mapped; not torch's pinned pool, which would keep the
+    pages after close()).  `.array` is that copy on the host, `.tensor` aliases its pages as a device tensor."""
 
     def __init__(self, array, device="cuda"):
-        self.array = np.ascontiguousarray(array)  # kept alive: the registration pins THESE pages
+        array = np.ascontiguousarray(array)
         hip = C.CDLL("libamdhip64.so")
         self._hip = hip
-        nbytes = self.array.nbytes
-        self._host = C.c_void_p(self.array.ctypes.data)
+        self._host = C.c_void_p()
         with torch.cuda.device(torch.device(device)):
-            rc = hip.hipHostRegister(self._host, C.c_size_t(nbytes), C.c_uint(2))  # hipHostRegisterMapped
+            rc = hip.hipHostMalloc(C.byref(self._host), C.c_size_t(array.nbytes), C.c_uint(2))  # hipHostMallocMapped
             if rc != 0:
-                raise _lib.GgmsError(f"hipHostRegister({nbytes} bytes) -> {rc}")
+                raise _lib.GgmsError(f"hipHostMalloc({array.nbytes} bytes) -> {rc}")
+            self.array = np.ctypeslib.as_array(C.cast(self._host, C.POINTER(C.c_uint8)), (array.nbytes,)) \
+                .view(array.dtype).reshape(array.shape)
+            self.array[...] = array
             dp = C.c_void_p()
             rc = hip.hipHostGetDevicePointer(C.byref(dp), self._host, C.c_uint(0))
             if rc != 0:
-                hip.hipHostUnregister(self._host)
+                hip.hipHostFree(self._host)
                 raise _lib.GgmsError(f"hipHostGetDevicePointer -> {rc}")
-        kind = {4: "<i4", 8: "<i8", 1: "|u1", 2: "<i2"}[self.array.dtype.itemsize]
+        kind = {4: "<i4", 8: "<i8", 1: "|u1", 2: "<i2"}[array.dtype.itemsize]
         self.ptr = dp.value
-        self.tensor = torch.as_tensor(_RawDevice(self.ptr, self.array.shape, kind), device=torch.device(device))
+        self.tensor = torch.as_tensor(_RawDevice(self.ptr, array.shape, kind), device=torch.device(device))
 
     def close(self):
         if self._host is not None:
-            self.tensor = None
-            self._hip.hipHostUnregister(self._host)
+            self.tensor = self.array = None
+            self._hip.hipHostFree(self._host)
             self._host = None
 
 
