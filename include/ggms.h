@@ -235,7 +235,8 @@ enum ggms_sample_type {
   GGMS_KHOP3 = 7,
   GGMS_KHOP_LABOR = 8, /* an extension: ggms_sample_khop_labor below */
   GGMS_KHOP_TEMPORAL = 9, /* an extension: ggms_sample_khop_temporal / ggms_sample_batch_temporal below */
-  GGMS_KHOP_TYPED = 10 /* an extension: ggms_sample_khop_typed / ggms_sample_batch_typed below */
+  GGMS_KHOP_TYPED = 10, /* an extension: ggms_sample_khop_typed / ggms_sample_batch_typed below */
+  GGMS_KHOP_LABOR_WEIGHTED = 11 /* an extension: ggms_sample_khop_labor_weighted / ggms_sample_batch_labor_weighted */
 };
 
 /* Workspace of every leaf sampler below but random walk, whose size depends on
@@ -341,6 +342,38 @@ int ggms_sample_khop_typed(const ggms_graph_t *graph, const uint8_t *edge_type, 
                            uint32_t layer_salt, ggms_id_t *out_src, ggms_id_t *out_dst, ggms_id_t *out_pos,
                            uint8_t *out_type, uint64_t *num_out_dev, void *workspace, size_t workspace_bytes,
                            ggms_stream_t stream);
+
+/* khop_labor_weighted (an extension; the reference has no such sampler; DGL: sample_neighbors(prob=..., replace=False),
+ * PyG: a weighted NeighborLoader): fixed-fanout sampling WITHOUT replacement in which an edge's chance grows with its
+ * weight (Efraimidis-Spirakis / exponential clocks), with khop_labor's shared randomness: the variate belongs to the
+ * NODE, the weight only rescales it per edge, so seeds that share a neighbour share its variate.  With fanout 1 the
+ * edge at position p is picked with probability w_p / sum of the list's weights (distinct neighbour ids).
+ *   edge_weight one float32 per position of graph->indices.
+ *   hash        for seed s with list t_0 .. t_{d-1} and position p: h = fmix32(t_p ^ layer_salt) (khop_labor's fmix32);
+ *               v = 2 h + 1 as uint64 (33 bits); e = floor(log2 v); m = v << (63 - e); f = (m >> 31) & 0xffffffff;
+ *               i = f >> 24; r = f & 0xffffff
+ *   logarithm   L = (e << 32) + T[i] + (((T[i + 1] - T[i]) * r) >> 24), all uint64, with the table
+ *               T[i] = round(2^32 log2(1 + i / 256)), i = 0 .. 256, T[256] = 2^32: 257 literal constants
+ *               (xgnn_amd/csrc/labor_log2_table.h)
+ *   variate     E = (33 << 32) - L, a uint64 with E >= 1 for every h and strictly decreasing in h; E / 2^32 * ln 2 is
+ *               Exp(1) to within 3e-6 in log2
+ *   clamp       w' = fminf(fmaxf(w_p, 2^-40), 2^40); a NaN becomes 2^-40.  Nothing is out of range: the key is a
+ *               normal float
+ *   key         key32 = the bits of float32(E) / w': float32(E) the round-to-nearest-even conversion of the uint64, the
+ *               quotient ONE correctly rounded binary32 division (positive floats order like their bit patterns).  The
+ *               64-bit key is (key32 << 32) | p
+ *   selected    the min(fanout, d) positions with the smallest keys; seeds in input order, within a seed ascending
+ *               position (d <= fanout: the whole list in order); duplicate seeds get the same edges
+ *   output      out_src / out_dst as khop_labor writes them; out_pos[k] = indptr[s] + p, the edge's position in
+ *               graph->indices (parallel edges carry their own weights).  All three hold num_input * fanout entries.
+ *   arguments   refused with GGMS_ERR_INVALID before any device call: a sharded graph (positions and weights are those
+ *               of ONE CSR), fanout 0 or >= 128, a null array, a short workspace.
+ * Stateless: a pure function of (graph, edge_weight, input, fanout, layer_salt).  No allocation, no synchronisation,
+ * every size stays on the device.  Workspace: ggms_sample_workspace_bytes(GGMS_KHOP_LABOR_WEIGHTED, ...). */
+int ggms_sample_khop_labor_weighted(const ggms_graph_t *graph, const float *edge_weight, const ggms_id_t *input,
+                                    size_t num_input, size_t fanout, uint32_t layer_salt, ggms_id_t *out_src,
+                                    ggms_id_t *out_dst, ggms_id_t *out_pos, uint64_t *num_out_dev, void *workspace,
+                                    size_t workspace_bytes, ggms_stream_t stream);
 
 /* GPUSampleWeightedKHopPrefix, cuda/cuda_sampling_weighted_khop_prefix.cu:145-246:
  * prob_prefix_table = per-list inclusive prefix sums of the edge weights; one
@@ -668,6 +701,27 @@ int ggms_sample_batch_typed(const ggms_graph_t *graph, const ggms_id_t *seeds, s
                             ggms_id_t *const *eid, uint8_t *const *etype, uint64_t *counts_dev, const ggms_typed_t *t,
                             const ggms_sample_extra_t *extra, void *workspace, size_t workspace_bytes,
                             ggms_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * The weighted LABOR batch (an extension): ggms_sample_batch's chain with khop_labor_weighted as the sampler.
+ *   edge_weight device, one float32 per CSR position (ggms_sample_khop_labor_weighted's).  ggms_sample_extra_t is full,
+ *               hence an entry point of its own.
+ *   layer i     ggms_sample_khop_labor_weighted's rule with layer_salt = fmix32(labor_salt + 0x9e3779b9 * (i + 1)).
+ *   eid         HOST array of L device pointers, capacities max_edges[i]: eid[i][k] = the CSR position of edge k of
+ *               layer i (the table fills never reorder edges); edge_weight[eid[i][k]] is its weight.
+ *   counts_dev, row, col, both table layouts, the numbering, seeds_distinct: ggms_sample_batch's.  extra->labor_salt is
+ *   the batch salt (NULL: 0); rng_wait / rng_done are ignored (stateless).
+ *   ggms_sample_batch_seed_ids(GGMS_KHOP_LABOR_WEIGHTED, ...) gives the raw seeds' local ids.
+ *   ggms_sample_batch(GGMS_KHOP_LABOR_WEIGHTED, ...) is GGMS_ERR_INVALID and names this call.  Sharded graphs are
+ *   refused (GGMS_ERR_INVALID).
+ * ------------------------------------------------------------------------- */
+size_t ggms_sample_batch_labor_weighted_workspace_bytes(size_t num_seeds, const size_t *fanouts, uint32_t num_layer,
+                                                        const ggms_sample_extra_t *extra);
+int ggms_sample_batch_labor_weighted(const ggms_graph_t *graph, const ggms_id_t *seeds, size_t num_seeds,
+                                     const size_t *fanouts, uint32_t num_layer, ggms_hashtable_t *ht,
+                                     ggms_id_t *const *row, ggms_id_t *const *col, ggms_id_t *const *eid,
+                                     uint64_t *counts_dev, const float *edge_weight, const ggms_sample_extra_t *extra,
+                                     void *workspace, size_t workspace_bytes, ggms_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Link-prediction seeds (an extension; the reference has no such operator): a batch of positive EDGE ids becomes the

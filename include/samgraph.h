@@ -201,6 +201,16 @@ void samgraph_get_graph_link_time(uint64_t key, samgraph_tensor_t *out);
  *   samgraph_get_graph_edge_type(key, layer)   num_edge(layer) types (uint8), edge_type[edge_ids[k]]
  * Fatal with every other sample type. */
 void samgraph_get_graph_edge_type(uint64_t key, int layer_idx, samgraph_tensor_t *out);
+/* Extension for _sample_type 11 (khop_labor_weighted): weighted sampling without replacement (ggms_sample_batch_labor_weighted,
+ * include/ggms.h).  arch1 with one CSR, task = node_classification or link_prediction, 1 or 2 pipelines, both table layouts;
+ * every other deployment, use_dist_graph, exclude_seed_edges other than none, induced_subgraph, hetero_batch and
+ * inline_heads = 1 are refused by name (inline_heads = auto means off).  The dataset carries edge_weight.bin: NUM_EDGE
+ * float32, one per position of indices.bin; a missing file, another size, and the first weight that is not finite or lies
+ * outside [2^-40, 2^40] (named by its position) are fatal at init.  The batch salt follows the batch's key as khop_labor's;
+ * no RNG pool.  edge_ids is implied: the sampler emits the positions itself, and edge_feat gathers under them.
+ *   samgraph_get_graph_edge_weight(key, layer)   num_edge(layer) weights (float32), edge_weight[edge_ids[k]]
+ * Fatal with every other sample type. */
+void samgraph_get_graph_edge_weight(uint64_t key, int layer_idx, samgraph_tensor_t *out);
 /* Extensions for config key hetero_batch = on (arch1 with _sample_type 10, both tasks, 1 or 2 pipelines, both table
  * layouts; refused by name with every other deployment, every other sample type, edge_feat, induced_subgraph,
  * feat_learnable and use_dist_graph).  The dataset carries node_type.bin (NUM_NODE uint8, one per node id) and the meta key

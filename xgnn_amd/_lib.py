@@ -172,6 +172,12 @@ SYMBOLS = {
     "ggms_sample_batch_typed": (_i, [C.POINTER(Graph), _vp, _sz, C.POINTER(_sz), _u32, C.POINTER(HashTable),
                                      C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp,
                                      C.POINTER(Typed), C.POINTER(SampleExtra), _vp, _sz, _vp]),
+    "ggms_sample_khop_labor_weighted": (_i, [C.POINTER(Graph), _vp, _vp, _sz, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp,
+                                             _sz, _vp]),
+    "ggms_sample_batch_labor_weighted_workspace_bytes": (_sz, [_sz, C.POINTER(_sz), _u32, C.POINTER(SampleExtra)]),
+    "ggms_sample_batch_labor_weighted": (_i, [C.POINTER(Graph), _vp, _sz, C.POINTER(_sz), _u32, C.POINTER(HashTable),
+                                              C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp, _vp,
+                                              C.POINTER(SampleExtra), _vp, _sz, _vp]),
     "ggms_link_seeds": (_i, [C.POINTER(Graph), _vp, _sz, _u32, _i, _u32, _vp, _vp, _vp]),
     "ggms_drop_pair_edges_workspace_bytes": (_sz, [_sz, C.POINTER(_sz), _u32]),
     "ggms_drop_pair_edges": (_i, [_vp, _vp, _sz, _u32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz), _u32, _vp, _vp,

@@ -13,6 +13,7 @@ kKHop0, kKHop1, kWeightedKHop, kRandomWalk, kWeightedKHopPrefix, kKHop2, kWeight
 kKHopLabor = 8  # an extension: fixed-fanout LABOR sampling (include/ggms.h, GGMS_KHOP_LABOR)
 kKHopTemporal = 9  # an extension: sampling strictly before the seed's time (include/ggms.h, GGMS_KHOP_TEMPORAL)
 kKHopTyped = 10  # an extension: a fanout per edge type on a type-sorted CSR (include/ggms.h, GGMS_KHOP_TYPED)
+kKHopLaborWeighted = 11  # an extension: weighted sampling without replacement (include/ggms.h, GGMS_KHOP_LABOR_WEIGHTED)
 kArch0, kArch1, kArch2, kArch3, kArch4, kArch5, kArch6, kArch7 = range(8)
 (kCacheByDegree, kCacheByHeuristic, kCacheByPreSample, kCacheByDegreeHop, kCacheByPreSampleStatic,
  kCacheByFakeOptimal, kDynamicCache, kCacheByRandom) = range(8)
@@ -30,7 +31,7 @@ sample_types = {
     'khop0': kKHop0, 'khop1': kKHop1, 'khop2': kKHop2, 'khop3': kKHop3, 'random_walk': kRandomWalk,
     'weighted_khop': kWeightedKHop, 'weighted_khop_prefix': kWeightedKHopPrefix,
     'weighted_khop_hash_dedup': kWeightedKHopHashDedup, 'khop_labor': kKHopLabor, 'khop_temporal': kKHopTemporal,
-    'khop_typed': kKHopTyped,
+    'khop_typed': kKHopTyped, 'khop_labor_weighted': kKHopLaborWeighted,
 }
 builtin_archs = {
     'arch0': {'arch': kArch0, 'sampler_ctx': cpu(), 'trainer_ctx': gpu(0)},
@@ -132,7 +133,7 @@ SAMGRAPH_SYMBOLS = {
     "samgraph_num_node_type": (_sz, []), "samgraph_relation_src_type": (_i, [_i]), "samgraph_relation_dst_type": (_i, [_i]),
     "samgraph_get_graph_edge_time": (None, [_u64, _i, _TP]), "samgraph_get_graph_node_cut": (None, [_u64, _TP]),
     "samgraph_get_graph_link_time": (None, [_u64, _TP]),
-    "samgraph_get_graph_edge_type": (None, [_u64, _i, _TP]),
+    "samgraph_get_graph_edge_type": (None, [_u64, _i, _TP]), "samgraph_get_graph_edge_weight": (None, [_u64, _i, _TP]),
     "samgraph_update_graph_feat": (None, [_u64, C.c_void_p, _sz, _sz, C.c_void_p]),
     "samgraph_get_store_feat": (None, [_TP]), "samgraph_get_store_state": (None, [_TP]),
     "samgraph_batch_retain": (None, [_u64]), "samgraph_batch_release": (None, [_u64]),

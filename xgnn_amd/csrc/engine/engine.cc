@@ -227,7 +227,12 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
     cfg.lookahead = 0;
     cfg.pipelines = 1;
   }
-  SAM_CHECK(cfg.sample_type >= GGMS_KHOP0 && cfg.sample_type <= GGMS_KHOP_TYPED, "unknown sample type");
+  SAM_CHECK(cfg.sample_type >= GGMS_KHOP0 && cfg.sample_type <= GGMS_KHOP_LABOR_WEIGHTED, "unknown sample type");
+  if (cfg.Weighted() && cfg.arch != kArch1) {
+    static const char *const arch_names[] = {"arch0", "arch1", "arch2", "arch3", "arch4", "arch5", "arch6", "arch7"};
+    fatal(__FILE__, __LINE__, std::string(arch_names[cfg.arch]) + ": _sample_type 11 (khop_labor_weighted) is not built: the "
+                              "edge weights and the edge positions run in arch1's sampling chain only");
+  }
   if (kv.count("hetero_batch")) { // extension: the batch's heterogeneous view (node types, per-relation blocks)
     if (kv["hetero_batch"] != "on" && kv["hetero_batch"] != "off")
       fatal(__FILE__, __LINE__, "hetero_batch = " + kv["hetero_batch"] + ": on or off (the default)");
@@ -412,6 +417,21 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
                                   "type_fanout: row " + std::to_string(i) + " sums to " + std::to_string(sum) +
                                   " (leave fanout to the Python front-end, or give the rows' sums)");
     }
+  }
+  if (cfg.Weighted()) { // extension: weighted sampling without replacement on edge_weight.bin
+    const std::string who = "_sample_type 11 (khop_labor_weighted)";
+    if (cfg.use_dist_graph)
+      fatal(__FILE__, __LINE__, who + " with use_dist_graph: edge weights are stored by position in ONE CSR, a sharded "
+                                "topology has none");
+    if (cfg.exclude_seed_edges)
+      fatal(__FILE__, __LINE__, who + " with exclude_seed_edges = " + kv["exclude_seed_edges"] + " is not built: the filter "
+                                "compacts row / col and knows nothing of the position stream the sampler wrote beside them");
+    if (kv.count("induced_subgraph") && kv["induced_subgraph"] == "on")
+      fatal(__FILE__, __LINE__, who + " with induced_subgraph is not built: the induced edges carry no weight");
+    if (cfg.inline_heads == 1)
+      fatal(__FILE__, __LINE__, who + " with inline_heads = 1: only khop3 reads the list heads; the weighted sampler reads "
+                                "whole lists and their weights");
+    cfg.inline_heads = 0; // auto means off
   }
   if (kv.count("edge_ids") || kv.count("edge_feat")) { // extension: CSR positions (and edge-table rows) of the sampled edges
     for (const char *key : {"edge_ids", "edge_feat"})
@@ -754,6 +774,22 @@ void Engine::LoadDataset() {
           fatal(__FILE__, __LINE__, "khop_temporal: edge_time.bin: the times of node " + std::to_string(v) + "'s list are not "
                                         "non-decreasing (position " + std::to_string(p) + "); datagen.sort_lists_by_time "
                                         "re-sorts a graph");
+  }
+  if (cfg.Weighted()) { // the edge weights: NUM_EDGE float32 in CSR order, finite and within the sampler's clamp range
+    const std::string name = cfg.dataset_path + "edge_weight.bin";
+    struct stat st;
+    if (stat(name.c_str(), &st) != 0)
+      fatal(__FILE__, __LINE__, "khop_labor_weighted: " + name + " is missing (NUM_EDGE float32 weights, one per position of "
+                                    "indices.bin; datagen.write_dataset(edge_weight=...))");
+    if ((size_t)st.st_size != ds.num_edge * 4)
+      fatal(__FILE__, __LINE__, "khop_labor_weighted: edge_weight.bin has " + std::to_string((size_t)st.st_size) +
+                                    " bytes, NUM_EDGE x 4 is " + std::to_string(ds.num_edge * 4));
+    ds.edge_weight = MapFile("edge_weight.bin", ds.num_edge * 4, false);
+    const float *w = (const float *)ds.edge_weight.ptr;
+    for (size_t p = 0; p < ds.num_edge; ++p)
+      if (!(w[p] >= 0x1p-40f && w[p] <= 0x1p40f)) // a NaN fails both comparisons
+        fatal(__FILE__, __LINE__, "khop_labor_weighted: edge_weight.bin: position " + std::to_string(p) + " holds " +
+                                      std::to_string(w[p]) + ", not a finite weight in [2^-40, 2^40]");
   }
   if (cfg.hetero) { // the node types: NUM_NODE uint8 below NUM_NODE_TYPE
     if (!meta.count("NUM_NODE_TYPE"))
@@ -1411,7 +1447,7 @@ void Engine::SampleInit(int worker_id, const std::string &ctx) {
   extra_.random_walk_restart_prob = cfg.random_walk_restart_prob;
   extra_.num_random_walk = cfg.num_random_walk;
   // GPURandomStates dist_engine.cc:432-433; seed = wall clock unless the "seed" key is given
-  if (cfg.sample_type == GGMS_KHOP_LABOR || cfg.Temporal() || cfg.Typed()) { // stateless: their variates are hashes of (node id, salt) -- no RNG pool
+  if (cfg.sample_type == GGMS_KHOP_LABOR || cfg.Temporal() || cfg.Typed() || cfg.Weighted()) { // stateless: their variates are hashes of (node id, salt) -- no RNG pool
     num_states_ = 0;
     states_ = nullptr;
   } else {
@@ -1466,6 +1502,11 @@ void Engine::SampleInit(int worker_id, const std::string &ctx) {
   if (cfg.Typed()) { // the edge types in HBM, beside the topology the sampler reads
     SAM_HIP(hipMalloc((void **)&d_edge_type_, std::max<size_t>(ds.num_edge, 16)));
     SAM_HIP(hipMemcpyAsync(d_edge_type_, ds.edge_type.ptr, ds.num_edge, hipMemcpyHostToDevice, stream_));
+    SAM_HIP(hipStreamSynchronize(stream_));
+  }
+  if (cfg.Weighted()) { // the edge weights in HBM, beside the topology the sampler reads
+    SAM_HIP(hipMalloc((void **)&d_edge_weight_, std::max<size_t>(ds.num_edge, 4) * 4));
+    SAM_HIP(hipMemcpyAsync(d_edge_weight_, ds.edge_weight.ptr, ds.num_edge * 4, hipMemcpyHostToDevice, stream_));
     SAM_HIP(hipStreamSynchronize(stream_));
   }
   if (cfg.edge_ids && !cfg.SamplerEmitsEdgeIds()) { // the long-list queue of ggms_edge_positions, one per pipeline
@@ -1954,6 +1995,10 @@ void Engine::TrainInit(int worker_id, const std::string &ctx) {
       b->etype.assign(L, nullptr);
       for (uint32_t i = 0; i < L; ++i) SAM_HIP(hipMalloc((void **)&b->etype[i], std::max<size_t>(max_edges_[i], 16)));
     }
+    if (cfg.Weighted()) {
+      b->eweight.assign(L, nullptr);
+      for (uint32_t i = 0; i < L; ++i) SAM_HIP(hipMalloc((void **)&b->eweight[i], std::max<size_t>(max_edges_[i], 4) * 4));
+    }
     if (StagedHostTier()) { // index arrays of GetMissCacheIndex + pinned / device staging of the miss rows
       if (cache_table_) { // (no cache: no split, and the rows land in the batch's feature buffer directly)
         for (uint32_t **p : {&b->miss_src, &b->miss_dst, &b->hit_src, &b->hit_dst}) SAM_HIP(hipMalloc((void **)p, max_unique_ * 4));
@@ -2123,7 +2168,7 @@ void Engine::SampleInto(Batch *b, Pipe &P) {
                                     P.stream));
   }
   if (pipes_.size() > 1 && cfg.sample_type != GGMS_KHOP0 && cfg.sample_type != GGMS_KHOP_LABOR && !cfg.Temporal() &&
-      !cfg.Typed()) {
+      !cfg.Typed() && !cfg.Weighted()) {
     extra.rng_wait = last_rng_done_;
     extra.rng_done = P.rng_done;
     last_rng_done_ = P.rng_done;
@@ -2155,6 +2200,11 @@ void Engine::SampleInto(Batch *b, Pipe &P) {
     SAM_GGMS(ggms_sample_batch_typed(&graph_, s.output_nodes, b->num_seeds, cfg.fanout.data(), L, &ht, s.row.data(),
                                      s.col.data(), b->eid.data(), b->etype.data(), s.counts_dev, &t, &extra, P.ws, ws_bytes_,
                                      P.stream));
+  } else if (cfg.Weighted()) {
+    // the sampler fills the batch's eid buffers itself
+    SAM_GGMS(ggms_sample_batch_labor_weighted(&graph_, s.output_nodes, b->num_seeds, cfg.fanout.data(), L, &ht, s.row.data(),
+                                              s.col.data(), b->eid.data(), s.counts_dev, d_edge_weight_, &extra, P.ws,
+                                              ws_bytes_, P.stream));
   } else
     SAM_GGMS(ggms_sample_batch(cfg.sample_type, &graph_, s.output_nodes, b->num_seeds, cfg.fanout.data(), L, &ht, states_,
                                num_states_, s.row.data(), s.col.data(), s.counts_dev, &extra, P.ws, ws_bytes_, P.stream));
@@ -2279,6 +2329,11 @@ void Engine::EnqueueGather(Batch *b, hipStream_t ss) {
     for (uint32_t i = 0; i < L; ++i)
       SAM_GGMS(ggms_gather_scatter(b->etime[i], d_edge_time_, b->eid[i], nullptr, max_edges_[i],
                                    b->trainer.counts_dev + GGMS_COUNT_EDGES(i), 1, GGMS_I32, xs));
+  // khop_labor_weighted: the sampled edges' weights, edge_weight[eid], the same way
+  if (cfg.Weighted())
+    for (uint32_t i = 0; i < L; ++i)
+      SAM_GGMS(ggms_gather_scatter(b->eweight[i], d_edge_weight_, b->eid[i], nullptr, max_edges_[i],
+                                   b->trainer.counts_dev + GGMS_COUNT_EDGES(i), 1, GGMS_F32, xs));
   if (b->lean) SAM_GGMS(ggms_launch_timer_arm(b->gather_timer));
   else SAM_HIP(hipEventRecord(b->ev_xstart, xs)); // the extract's own start: behind the previous batch's extract on xs
   // the rows are delivered in the batch's dtype (config key feat_out_dtype; the table's own without the key, which is

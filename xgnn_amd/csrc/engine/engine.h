@@ -129,7 +129,10 @@ struct RunConfig {
   std::vector<uint32_t> type_fanout;
   uint32_t num_edge_type = 0; // type_fanout.size() / num_layer; LoadDataset checks it against meta.txt's NUM_EDGE_TYPE
   bool Typed() const { return sample_type == GGMS_KHOP_TYPED; }
-  bool SamplerEmitsEdgeIds() const { return Temporal() || Typed(); } // ggms_edge_positions is not enqueued
+  // extension (_sample_type 11, khop_labor_weighted; arch1, one CSR, both tasks): weighted sampling without replacement
+  // on edge_weight.bin (ggms_sample_batch_labor_weighted).  Implies edge_ids like khop_temporal
+  bool Weighted() const { return sample_type == GGMS_KHOP_LABOR_WEIGHTED; }
+  bool SamplerEmitsEdgeIds() const { return Temporal() || Typed() || Weighted(); } // ggms_edge_positions is not enqueued
   // extension (config keys `induced_subgraph` = on, `induced_max_edges`; arch1, one CSR, not khop2 / khop_temporal, no
   // exclude_seed_edges): every batch also carries the subgraph its input nodes induce -- every edge of the graph with
   // both ends among them, one COO over the batch's local ids with the edges' CSR positions (ggms_induced_edges behind
@@ -190,6 +193,8 @@ struct Dataset {
   // khop_typed: edge_type.bin, NUM_EDGE uint8 in CSR order, non-decreasing inside every node's list and below NUM_EDGE_TYPE
   // (checked at load)
   HostArray edge_type;
+  // khop_labor_weighted: edge_weight.bin, NUM_EDGE float32 in CSR order, finite and within [2^-40, 2^40] (checked at load)
+  HostArray edge_weight;
   // hetero_batch: node_type.bin, NUM_NODE uint8 below NUM_NODE_TYPE, and every relation's (source type, destination type)
   // as its edges have them -- 255 / 255 for a relation without an edge
   HostArray node_type;
@@ -286,6 +291,8 @@ struct Batch {
   std::vector<uint32_t *> etime;
   // khop_typed: per layer the sampled edges' types, written by the sampler beside eid.  Empty with every other sampler.
   std::vector<uint8_t *> etype;
+  // khop_labor_weighted: per layer edge_weight[eid].  Empty with every other sampler.
+  std::vector<float *> eweight;
   // induced_subgraph: the induced COO and its edges' CSR positions (induced_max_edges words each), with edge_feat the edge
   // table's rows under them; three device words -- ggms_induced_edges' two counts [M, list entries walked] and
   // min(M, induced_max_edges), the gather's row count -- and the pinned host copy of the first two, valid with the
@@ -513,6 +520,7 @@ class Engine {
   size_t eid_ws_bytes_ = 0;    // edge_ids: ggms_edge_positions' workspace (Pipe::eid_ws)
   void *d_edge_feat_ = nullptr; // edge_feat: the edge table in HBM
   uint32_t *d_edge_time_ = nullptr; // khop_temporal: the edge times in HBM
+  float *d_edge_weight_ = nullptr;  // khop_labor_weighted: the edge weights in HBM
   uint8_t *d_edge_type_ = nullptr;  // khop_typed: the edge types in HBM
   uint64_t link_excluded_ = 0; // exclude_seed_edges: edges dropped from the batches handed out so far in this epoch
   std::vector<Pipe> pipes_;

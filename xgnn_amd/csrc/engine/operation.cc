@@ -242,6 +242,15 @@ void samgraph_get_graph_edge_type(uint64_t key, int l, samgraph_tensor_t *out) {
   SAM_CHECK(l >= 0 && (size_t)l < b->etype.size(), "samgraph_get_graph_edge_type: no such layer");
   fill(out, b->etype[l], (int64_t)b->counts[GGMS_COUNT_EDGES(l)], 1, 1, GGMS_U8, E.batch_device_type(), E.trainer_device());
 }
+// _sample_type 11 (khop_labor_weighted): the weight of every edge of layer l, edge_weight[edge_ids] -- float32
+void samgraph_get_graph_edge_weight(uint64_t key, int l, samgraph_tensor_t *out) {
+  auto &E = Engine::Get();
+  if (!E.cfg.Weighted())
+    sam::fatal(__FILE__, __LINE__, "samgraph_get_graph_edge_weight needs _sample_type 11 (khop_labor_weighted)");
+  auto *b = E.Current(key);
+  SAM_CHECK(l >= 0 && (size_t)l < b->eweight.size(), "samgraph_get_graph_edge_weight: no such layer");
+  fill(out, b->eweight[l], (int64_t)b->counts[GGMS_COUNT_EDGES(l)], 1, 1, GGMS_F32, E.batch_device_type(), E.trainer_device());
+}
 // config key hetero_batch: the batch's heterogeneous view.  The small words (Batch::het_words: base | cuts | offsets) are
 // on the host with the counts; every tensor below is a zero-copy view, the per-type and per-relation ones slices
 static sam::Batch *hetero_batch(uint64_t key, const char *who) {

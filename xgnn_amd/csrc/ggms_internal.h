@@ -98,6 +98,8 @@ struct SampleLayer {
   uint32_t num_type = 0;
   const uint32_t *type_fanout = nullptr;
   uint8_t *out_type = nullptr;
+  // khop_labor_weighted: per-position weights.  Shares out_pos with khop_temporal
+  const float *edge_weight = nullptr;
 };
 
 // sample_khop.hip
@@ -118,6 +120,9 @@ size_t walk_scan_tiles(size_t num_input);
 // sample_labor.hip
 size_t labor_ws_words(size_t num_input);
 int sample_khop_labor_impl(const SampleLayer &l);
+
+// sample_labor_weighted.hip (workspace: labor_ws_words)
+int sample_khop_labor_weighted_impl(const SampleLayer &l);
 
 // sample_temporal.hip
 size_t temporal_ws_words(size_t num_input);

@@ -1,6 +1,7 @@
 // labor_select.h -- the bottom-k selection of khop_labor (include/ggms.h), one copy for the samplers that use it:
 // khop_labor over a seed's whole list (sample_labor.hip) and khop_temporal over the list's eligible prefix
-// (sample_temporal.hip).  The callers differ in where the length comes from and in what an emitted edge writes, so both
+// (sample_temporal.hip); khop_labor_weighted (sample_labor_weighted.hip) shares the constants, the count and
+// labor_block_sum and runs the same searches over its own key.  The callers differ in where the length comes from and in what an emitted edge writes, so both
 // are the caller's: `d` is an argument and every selected position leaves through emit(o, p, t) -- o its rank among the
 // seed's selected positions (ascending position), p the position in the list, t = list[p].
 //   labor_wave_select<R>  one WAVE, k < d <= 64 R: the hashes of the whole list sit in registers, the k-th smallest is
@@ -18,7 +19,25 @@ constexpr uint32_t kLaborWaveMax = 1024; // 16 keys; longer lists take a workgro
 constexpr uint32_t kLaborCand = 1024;    // keys the hub pre-filter's LDS buffer holds (8 KB)
 constexpr uint32_t kLaborMaxFanout = 127;
 
+// tile_scan's pieces of a layer over whole lists (khop_labor, khop_labor_weighted): the count of seed i is
+// min(fanout, d), its exclusive sum the seed's offset into the outputs
+struct LaborCount {
+  GraphView g;
+  const uint32_t *input;
+  uint32_t fanout;
+  __device__ __forceinline__ uint32_t operator()(uint64_t i) const {
+    uint32_t len;
+    g.neighbours(input[i], len);
+    return len < fanout ? len : fanout;
+  }
+};
+struct LaborOffset {
+  uint32_t *offset;
+  __device__ __forceinline__ void operator()(uint64_t i, uint32_t, uint32_t excl) const { offset[i] = excl; }
+};
+
 // fanout < d <= 64 R: the whole list in the wave's registers, position p = 64 r + lane
+// (sample_labor_weighted.hip's weighted_wave_select is a copy over another key: fix both)
 template <int R, typename Emit>
 __device__ __forceinline__ void labor_wave_select(const uint32_t *__restrict__ list, uint32_t d, uint32_t k, uint32_t salt,
                                                   const Emit &emit) {
@@ -90,6 +109,7 @@ __device__ __forceinline__ uint32_t labor_count_below(const uint32_t *__restrict
 // over LDS, and the k selected positions are ranked by position.  Fewer than k survivors, or more than the buffer
 // holds: the exact route -- the bitwise search over the list itself and an ordered emit with block scans.  Ends with a
 // barrier: the next call may rewrite the LDS at once.
+// (sample_labor_weighted.hip's weighted_hub_list copies the LDS search, the ranking and the exact route: fix both)
 template <typename Emit>
 __device__ __forceinline__ void labor_hub_list(const uint32_t *__restrict__ list, uint32_t d, uint32_t k, uint32_t salt,
                                                const Emit &emit) {

@@ -76,7 +76,8 @@ size_t layer_ws_words(int type, size_t n, size_t fanout, size_t walk_length, siz
   case GGMS_WEIGHTED_KHOP:
   case GGMS_WEIGHTED_KHOP_PREFIX: return weighted_ws_words(n, fanout);
   case GGMS_RANDOM_WALK: return random_walk_ws_words(n, walk_length, num_walk, fanout);
-  case GGMS_KHOP_LABOR: return labor_ws_words(n);
+  case GGMS_KHOP_LABOR:
+  case GGMS_KHOP_LABOR_WEIGHTED: return labor_ws_words(n);
   case GGMS_KHOP_TEMPORAL: return temporal_ws_words(n);
   default: return sample_ws_words(n); // khop3, khop2, weighted_khop_hash_dedup
   }
@@ -89,6 +90,7 @@ static int layer_shape_check(int type, const SampleLayer &l) {
   if (type == GGMS_WEIGHTED_KHOP_HASH_DEDUP) GGMS_CHECK_ARG(l.fanout < kDedupSlots); // hash_dedup.cu:42
   if (type == GGMS_KHOP_LABOR) GGMS_CHECK_ARG(l.fanout < 128); // the hub route ranks its selection in LDS
   if (type == GGMS_KHOP_TEMPORAL) GGMS_CHECK_ARG(l.fanout < 128); // khop_labor's selection on a prefix
+  if (type == GGMS_KHOP_LABOR_WEIGHTED) GGMS_CHECK_ARG(l.fanout < 128); // khop_labor's selection over another key
   if (type == GGMS_KHOP_TYPED) { // khop_labor's selection per segment: every k_r < 128; `fanout` is the row's sum
     size_t sum = 0;
     const int rc = typed_fanout_sum(l.type_fanout, l.num_type, &sum);
@@ -107,10 +109,12 @@ static int layer_check(int type, const SampleLayer &l, size_t num_states) {
   const int rc = layer_shape_check(type, l);
   if (rc != GGMS_OK) return rc;
   const uint64_t n = l.n_max;
-  if (type == GGMS_KHOP1 || type == GGMS_KHOP2 || type == GGMS_KHOP_TEMPORAL || type == GGMS_KHOP_TYPED)
+  if (type == GGMS_KHOP1 || type == GGMS_KHOP2 || type == GGMS_KHOP_TEMPORAL || type == GGMS_KHOP_TYPED ||
+      type == GGMS_KHOP_LABOR_WEIGHTED)
     GGMS_CHECK_ARG(l.graph->indptr && l.graph->indices);
   if (type == GGMS_KHOP_TYPED) GGMS_CHECK_ARG(l.edge_type && l.out_pos && l.out_type);
   if (type == GGMS_KHOP_TEMPORAL) GGMS_CHECK_ARG(l.edge_time && l.out_pos && (l.input_cut || l.cut_table));
+  if (type == GGMS_KHOP_LABOR_WEIGHTED) GGMS_CHECK_ARG(l.edge_weight && l.out_pos);
   if (type == GGMS_WEIGHTED_KHOP || type == GGMS_WEIGHTED_KHOP_HASH_DEDUP) GGMS_CHECK_ARG(l.prob && l.alias);
   if (type == GGMS_WEIGHTED_KHOP_PREFIX) GGMS_CHECK_ARG(l.prob);
   // the RNG pool: assert(i < num_random_states) in every sampler of the reference but khop0
@@ -118,7 +122,8 @@ static int layer_check(int type, const SampleLayer &l, size_t num_states) {
   case GGMS_KHOP0:
   case GGMS_KHOP_LABOR:
   case GGMS_KHOP_TEMPORAL:
-  case GGMS_KHOP_TYPED: return GGMS_OK; // stateless
+  case GGMS_KHOP_TYPED:
+  case GGMS_KHOP_LABOR_WEIGHTED: return GGMS_OK; // stateless
   case GGMS_KHOP3: GGMS_CHECK_ARG(l.states && (n + 127) / 128 * 8 <= num_states); return GGMS_OK; // khop3.cu:89
   case GGMS_KHOP2:                                                                                   // khop2.cu:57
   case GGMS_WEIGHTED_KHOP_HASH_DEDUP: // hash_dedup.cu:70
@@ -147,6 +152,7 @@ static int sample_layer(int type, const SampleLayer &l) {
   case GGMS_KHOP_LABOR: return sample_khop_labor_impl(l);
   case GGMS_KHOP_TEMPORAL: return sample_khop_temporal_impl(l);
   case GGMS_KHOP_TYPED: return sample_khop_typed_impl(l);
+  case GGMS_KHOP_LABOR_WEIGHTED: return sample_khop_labor_weighted_impl(l);
   default: return sample_weighted_impl(l, type); // khop1, weighted_khop, weighted_khop_prefix
   }
 }
@@ -158,9 +164,10 @@ static int sample_layer(int type, const SampleLayer &l) {
 // separate insert launch of ht_fill_impl follows).  khop_labor does not either: its selection writes each edge from
 // the lane that held the key, after a search that is all ballots -- a returning atomic per edge there would serialise
 // behind the search of the seed's whole wave, and the sampler stays a pure function of its inputs.
-// khop_temporal and khop_typed are khop_labor's selection: the same holds.
+// khop_temporal, khop_typed and khop_labor_weighted are khop_labor's selection: the same holds.
 static bool layer_enters_output(int type) {
-  return type != GGMS_KHOP2 && type != GGMS_KHOP_LABOR && type != GGMS_KHOP_TEMPORAL && type != GGMS_KHOP_TYPED;
+  return type != GGMS_KHOP2 && type != GGMS_KHOP_LABOR && type != GGMS_KHOP_TEMPORAL && type != GGMS_KHOP_TYPED &&
+         type != GGMS_KHOP_LABOR_WEIGHTED;
 }
 
 // a leaf entry point: shape checks; nothing to sample -> a zero count (null pointers allowed); pointers, workspace and
@@ -301,13 +308,20 @@ struct TemporalBatch {
   uint32_t *node_cut;
 };
 
-// the body of ggms_sample_batch, ggms_sample_batch_prefetch, ggms_sample_batch_temporal and ggms_sample_batch_typed;
-// every argument check is the caller's
+// ggms_sample_batch_labor_weighted's part of a batch (NULL: any other batch)
+struct WeightedBatch {
+  const float *edge_weight;
+  ggms_id_t *const *eid;
+};
+
+// the body of ggms_sample_batch, ggms_sample_batch_prefetch, ggms_sample_batch_temporal, ggms_sample_batch_typed and
+// ggms_sample_batch_labor_weighted; every argument check is the caller's
 static int sample_batch_impl(int sample_type, const ggms_graph_t *graph, const ggms_id_t *seeds, size_t num_seeds,
                              const size_t *fanouts, uint32_t num_layer, ggms_hashtable_t *ht, void *states,
                              size_t num_states, ggms_id_t *const *row, ggms_id_t *const *col, uint64_t *counts_dev,
                              const ggms_sample_extra_t *extra, void *workspace, const Prefetch *pf, hipStream_t s,
-                             const TemporalBatch *tb = nullptr, const TypedBatch *yb = nullptr) {
+                             const TemporalBatch *tb = nullptr, const TypedBatch *yb = nullptr,
+                             const WeightedBatch *wb = nullptr) {
   const BatchCaps c = caps_of(num_seeds, fanouts, num_layer);
   // what every layer's sampler call shares; the loop below fills in the rest
   SampleLayer L{graph, nullptr, 0, 0, nullptr, nullptr, nullptr, (uint32_t *)states, nullptr, s};
@@ -320,7 +334,7 @@ static int sample_batch_impl(int sample_type, const ggms_graph_t *graph, const g
   }
   // a stateless sampler has nothing to order between batches
   const bool ordered_rng = sample_type != GGMS_KHOP_LABOR && sample_type != GGMS_KHOP_TEMPORAL &&
-                           sample_type != GGMS_KHOP_TYPED;
+                           sample_type != GGMS_KHOP_TYPED && sample_type != GGMS_KHOP_LABOR_WEIGHTED;
   if (tb) {
     L.edge_time = tb->t->edge_time;
     L.cut_table = tb->t->cut_table;
@@ -333,6 +347,10 @@ static int sample_batch_impl(int sample_type, const ggms_graph_t *graph, const g
     L.num_type = yb->t->num_type;
     L.out_pos = yb->eid[0]; // layer_check's non-null tests; every layer sets its own below
     L.out_type = yb->etype[0];
+  }
+  if (wb) {
+    L.edge_weight = wb->edge_weight;
+    L.out_pos = wb->eid[0]; // layer_check's non-null test; every layer sets its own below
   }
   for (uint32_t i = 0; i < num_layer; ++i) {
     L.n_max = c.max_input[i];
@@ -494,6 +512,7 @@ static int sample_batch_impl(int sample_type, const ggms_graph_t *graph, const g
       L.enter = first && khop0_enters ? &seed_enter : nullptr;
       if (sample_type == GGMS_RANDOM_WALK) L.out_data = extra->data[i];
       if (tb) L.out_pos = tb->eid[i];
+      if (wb) L.out_pos = wb->eid[i];
       if (yb) {
         L.type_fanout = yb->t->type_fanout + (size_t)i * L.num_type;
         L.out_pos = yb->eid[i];
@@ -564,6 +583,11 @@ int ggms_sample_batch(int sample_type, const ggms_graph_t *graph, const ggms_id_
               "ggms_sample_batch_typed", sample_type);
     return GGMS_ERR_INVALID;
   }
+  if (sample_type == GGMS_KHOP_LABOR_WEIGHTED) {
+    set_error("ggms_sample_batch: sample type %d (khop_labor_weighted) takes edge weights and returns edge positions: "
+              "call ggms_sample_batch_labor_weighted", sample_type);
+    return GGMS_ERR_INVALID;
+  }
   GGMS_CHECK_ARG(sample_type >= GGMS_KHOP0 && sample_type <= GGMS_KHOP_LABOR);
   GGMS_CHECK_ARG(num_seeds == 0 || seeds);
   GGMS_CHECK_ARG(workspace && workspace_bytes >= ggms_sample_batch_workspace_bytes(sample_type, num_seeds, fanouts,
@@ -582,7 +606,7 @@ int ggms_sample_batch_seed_ids(int sample_type, size_t num_seeds, const size_t *
                                const ggms_sample_extra_t *extra, const void *workspace, const ggms_id_t **seed_ids_dev) {
   GGMS_CHECK_ARG(fanouts && workspace && seed_ids_dev);
   GGMS_CHECK_ARG(num_layer >= 1 && num_layer <= 16);
-  GGMS_CHECK_ARG(sample_type >= GGMS_KHOP0 && sample_type <= GGMS_KHOP_TYPED);
+  GGMS_CHECK_ARG(sample_type >= GGMS_KHOP0 && sample_type <= GGMS_KHOP_LABOR_WEIGHTED);
   const BatchCaps c = caps_of(num_seeds, fanouts, num_layer);
   const BatchLayout lay = layout_of(sample_type, num_seeds, fanouts, num_layer, c, extra);
   const uint32_t *w = (const uint32_t *)(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
@@ -656,6 +680,32 @@ int ggms_sample_batch_typed(const ggms_graph_t *graph, const ggms_id_t *seeds, s
   const TypedBatch yb{t, eid, etype};
   return sample_batch_impl(GGMS_KHOP_TYPED, graph, seeds, num_seeds, fanouts, num_layer, ht, nullptr, 0, row, col,
                            counts_dev, extra, workspace, nullptr, to_stream(stream), nullptr, &yb);
+}
+
+// ---- khop_labor_weighted: the batch with per-position weights -------------------------------------------------------
+size_t ggms_sample_batch_labor_weighted_workspace_bytes(size_t num_seeds, const size_t *fanouts, uint32_t num_layer,
+                                                        const ggms_sample_extra_t *extra) {
+  return ggms_sample_batch_workspace_bytes(GGMS_KHOP_LABOR_WEIGHTED, num_seeds, fanouts, num_layer, extra);
+}
+
+int ggms_sample_batch_labor_weighted(const ggms_graph_t *graph, const ggms_id_t *seeds, size_t num_seeds,
+                                     const size_t *fanouts, uint32_t num_layer, ggms_hashtable_t *ht,
+                                     ggms_id_t *const *row, ggms_id_t *const *col, ggms_id_t *const *eid,
+                                     uint64_t *counts_dev, const float *edge_weight, const ggms_sample_extra_t *extra,
+                                     void *workspace, size_t workspace_bytes, ggms_stream_t stream) {
+  GGMS_CHECK_ARG(graph && fanouts && ht && row && col && eid && counts_dev && edge_weight);
+  GGMS_CHECK_ARG(num_layer >= 1 && num_layer <= 16);
+  GGMS_CHECK_ARG(graph->num_part == 0); // edge positions and the weights are those of one CSR
+  GGMS_CHECK_ARG(num_seeds == 0 || seeds);
+  for (uint32_t i = 0; i < num_layer; ++i) GGMS_CHECK_ARG(row[i] && col[i] && eid[i]);
+  GGMS_CHECK_ARG(workspace && workspace_bytes >= ggms_sample_batch_labor_weighted_workspace_bytes(num_seeds, fanouts,
+                                                                                                  num_layer, extra));
+  const BatchCaps c = caps_of(num_seeds, fanouts, num_layer);
+  GGMS_CHECK_ARG(c.max_input[0] + c.max_edges[0] <= ht->n2o_size);
+  GGMS_CHECK_ARG(c.max_input[0] + c.max_edges[0] < (1ull << 32) - 4); // indices and 2 + local id fit 32 bits
+  const WeightedBatch wb{edge_weight, eid};
+  return sample_batch_impl(GGMS_KHOP_LABOR_WEIGHTED, graph, seeds, num_seeds, fanouts, num_layer, ht, nullptr, 0, row,
+                           col, counts_dev, extra, workspace, nullptr, to_stream(stream), nullptr, nullptr, &wb);
 }
 
 // ---- arch4: the prefetching batch ----------------------------------------------------------------------------------

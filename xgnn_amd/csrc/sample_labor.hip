@@ -31,21 +31,6 @@
 
 namespace ggms {
 
-struct LaborCount {
-  GraphView g;
-  const uint32_t *input;
-  uint32_t fanout;
-  __device__ __forceinline__ uint32_t operator()(uint64_t i) const {
-    uint32_t len;
-    g.neighbours(input[i], len);
-    return len < fanout ? len : fanout;
-  }
-};
-struct LaborOffset {
-  uint32_t *offset;
-  __device__ __forceinline__ void operator()(uint64_t i, uint32_t, uint32_t excl) const { offset[i] = excl; }
-};
-
 // an edge of khop_labor: (seed's value, neighbour id) at the seed's offset + the rank inside the seed
 struct LaborEmit {
   uint32_t *__restrict__ src, *__restrict__ dst; // out_src / out_dst + the seed's offset

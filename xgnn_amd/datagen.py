@@ -144,7 +144,7 @@ def build_prob_prefix_table(indptr, weights, num_threads=8):
 
 def write_dataset(path, graph, feat=None, label=None, valid_frac=0.02, test_frac=0.05, feat_dtype="F32", weights=None,
                   minimal=False, train_edges=None, edge_feat=None, edge_feat_dtype="F32", edge_time=None, edge_type=None,
-                  num_edge_type=None, node_type=None, num_node_type=None, node_feat=None):
+                  num_edge_type=None, node_type=None, num_node_type=None, node_feat=None, edge_weight=None):
     """Write a dataset directory in the reference's on-disk format (datagen/README.md:37-51,
     samgraph/common/constant.cc:23-51, engine.cc:109-443): meta.txt (tab separated) + raw little-endian
     arrays: indptr/indices/train_set/test_set/valid_set/cache_by_* uint32, feat row-major, label int64;
@@ -167,6 +167,9 @@ def write_dataset(path, graph, feat=None, label=None, valid_frac=0.02, test_frac
     bfloat16 torch tensor, or None for a type without features) adds node_feat_<t>.bin for every type that has a table
     and the meta keys NODE_FEAT_DIM_<t> (0 without a table) / NODE_FEAT_DATA_TYPE_<t>, the tables of config key
     `typed_feat`.  Entry t has one row per node of type t; row k belongs to the k-th such node in ascending node id.
+    edge_weight (one float32 per edge, in the order of indices) adds edge_weight.bin, the weights of
+    ggms_sample_khop_labor_weighted, which clamps them to [2^-40, 2^40] (`weights` keeps writing its tables and nothing
+    else).
     minimal: what a sampling + extract run needs and nothing that costs minutes at papers100M size -- one-node
     valid / test sets instead of random slices of the complement, no cache_by_random.bin."""
     import os
@@ -213,6 +216,10 @@ def write_dataset(path, graph, feat=None, label=None, valid_frac=0.02, test_frac
         assert bad is None, (f"edge_time: the times of node {bad}'s list are not non-decreasing "
                              "(datagen.sort_lists_by_time re-sorts a graph)")
         edge_time.tofile(os.path.join(path, "edge_time.bin"))
+    if edge_weight is not None:
+        edge_weight = np.ascontiguousarray(edge_weight, dtype=np.float32)
+        assert edge_weight.shape == (ix.size,), f"edge_weight: one weight per edge ({ix.size}), not {edge_weight.shape}"
+        edge_weight.tofile(os.path.join(path, "edge_weight.bin"))
     if edge_type is not None:
         assert num_edge_type is not None and 1 <= int(num_edge_type) <= 32, \
             f"num_edge_type: 1 .. 32 (GGMS_MAX_EDGE_TYPES), not {num_edge_type}"

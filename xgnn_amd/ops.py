@@ -53,7 +53,8 @@ KHOP_TEMPORAL = 9  # an extension: sampling strictly before a per-seed cut-off t
 PICK_UNIFORM, PICK_RECENT = 0, 1  # khop_temporal's picks
 KHOP_TYPED = 10  # an extension: a fanout per edge type on a type-sorted CSR (include/ggms.h)
 MAX_EDGE_TYPES = 32  # GGMS_MAX_EDGE_TYPES
-_STATELESS = (KHOP0, KHOP_LABOR, KHOP_TEMPORAL, KHOP_TYPED)  # samplers without an RNG pool
+KHOP_LABOR_WEIGHTED = 11  # an extension: weighted sampling without replacement, khop_labor's sharing (include/ggms.h)
+_STATELESS = (KHOP0, KHOP_LABOR, KHOP_TEMPORAL, KHOP_TYPED, KHOP_LABOR_WEIGHTED)  # samplers without an RNG pool
 
 
 def _require_gpu(t):
@@ -218,6 +219,31 @@ def sample_khop_temporal(graph, edge_time, inp, inp_cut, fanout, layer_salt, pic
                                           layer_salt & 0xFFFFFFFF, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
                                           _ptr(num_out), _ptr(ws), ws.numel() * 4, _stream()),
           "ggms_sample_khop_temporal")
+    return out[0], out[1], out[2], num_out
+
+
+def _f32(t):
+    assert t.dtype == torch.float32 and t.dim() == 1 and t.stride(0) == 1, "edge weights: a dense 1-d float32 tensor"
+    return t
+
+
+def sample_khop_labor_weighted(graph, edge_weight, inp, fanout, layer_salt):
+    """ggms_sample_khop_labor_weighted: per seed, the min(fanout, degree) list positions with the smallest
+    E(neighbour id, layer_salt) / weight -- a weighted sample without replacement, the variate shared per node.
+    Returns (out_src, out_dst, out_pos, num_out[1] on device); out_pos = the edges' positions in graph.indices."""
+    _require_gpu(inp)
+    _i32(inp)
+    if edge_weight is not None:
+        _require_gpu(_f32(edge_weight))
+    n = inp.numel()
+    dev = inp.device
+    out = [torch.empty(max(1, n * fanout), dtype=torch.int32, device=dev) for _ in range(3)]
+    num_out = torch.zeros(1, dtype=torch.int64, device=dev)
+    ws = _workspace(lib().ggms_sample_workspace_bytes(KHOP_LABOR_WEIGHTED, n, fanout), dev)
+    check(lib().ggms_sample_khop_labor_weighted(C.byref(graph.c), _ptr(edge_weight), _ptr(inp), n, fanout,
+                                                layer_salt & 0xFFFFFFFF, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
+                                                _ptr(num_out), _ptr(ws), ws.numel() * 4, _stream()),
+          "ggms_sample_khop_labor_weighted")
     return out[0], out[1], out[2], num_out
 
 
@@ -1436,6 +1462,46 @@ class TypedBatchSampler(_BatchBuffers):
         for i, lay in enumerate(layers):
             lay["eid"] = self.eid[i][:c[COUNT_EDGES(i)]]
             lay["etype"] = self.etype[i][:c[COUNT_EDGES(i)]]
+        return dict(layers=layers, input_nodes=self.ht.n2o[:c[COUNT_INPUT(self.L)]])
+
+
+class LaborWeightedBatchSampler(_BatchBuffers):
+    """ggms_sample_batch_labor_weighted: BatchSampler's layers with khop_labor_weighted as the sampler.  One slot, one
+    pipeline."""
+
+    def __init__(self, graph, edge_weight, fanouts, batch_size, device="cuda", direct_table=True, max_seeds=None):
+        self._init_capacity(graph, fanouts, KHOP_LABOR_WEIGHTED,
+                            int(batch_size * 1.25) + 1 if max_seeds is None else int(max_seeds), None, None)
+        _require_gpu(_f32(edge_weight))
+        self.edge_weight = edge_weight
+        self.ht = OrderedHashTable(self.max_unique, device, num_node=graph.c.num_node if direct_table else None)
+        self.states = None
+        (self.row, self._rows), (self.col, self._cols) = self._layer_buffers(1, device), self._layer_buffers(1, device)
+        self.eid, self._eids = self._layer_buffers(1, device)
+        self.counts = torch.zeros(COUNTS_SAMPLE_WORDS(self.L), dtype=torch.int64, device=device)
+        wsb = lib().ggms_sample_batch_labor_weighted_workspace_bytes(self.max_seeds, self._f, self.L,
+                                                                     C.byref(self._extra))
+        self.ws = _workspace(wsb, device)
+
+    def sample(self, seeds, salt=0, distinct=False):
+        """Enqueue one batch; salt: the batch salt (layer i samples under fmix32(salt + 0x9e3779b9 * (i + 1)));
+        distinct: the caller promises pairwise distinct seeds (ggms_sample_extra_t.seeds_distinct)."""
+        _i32(seeds)
+        n = seeds.numel()
+        assert n <= self.max_seeds
+        self._extra.labor_salt = salt & 0xFFFFFFFF
+        self._extra.seeds_distinct = 1 if distinct else 0
+        check(lib().ggms_sample_batch_labor_weighted(C.byref(self.graph.c), _ptr(seeds), n, self._f, self.L,
+                                                     C.byref(self.ht.c), self._rows, self._cols, self._eids,
+                                                     _ptr(self.counts), _ptr(self.edge_weight), C.byref(self._extra),
+                                                     _ptr(self.ws), self.ws.numel() * 4, _stream()),
+              "ggms_sample_batch_labor_weighted")
+
+    def result(self):
+        """Sync and slice the outputs: BatchSampler.result()'s, each layer with its `eid`."""
+        c, layers = self._sliced("ggms_sample_batch_labor_weighted")
+        for i, lay in enumerate(layers):
+            lay["eid"] = self.eid[i][:c[COUNT_EDGES(i)]]
         return dict(layers=layers, input_nodes=self.ht.n2o[:c[COUNT_INPUT(self.L)]])
 
 

@@ -221,6 +221,11 @@ def get_graph_link_time(batch_key):
     return _get("samgraph_get_graph_link_time", batch_key)
 
 
+def get_graph_edge_weight(batch_key, layer_idx):
+    """sample_type khop_labor_weighted: the weight of every edge of the layer, edge_weight[get_graph_edge_ids] (float32)."""
+    return _get("samgraph_get_graph_edge_weight", batch_key, layer_idx)
+
+
 def get_graph_edge_type(batch_key, layer_idx):
     """sample_type khop_typed: the relation of every edge of the layer, edge_type[get_graph_edge_ids] (uint8)."""
     return _get("samgraph_get_graph_edge_type", batch_key, layer_idx)
