@@ -754,6 +754,40 @@ int ggms_link_seeds(const ggms_graph_t *graph, const ggms_id_t *edge_ids, size_t
                     uint64_t *num_forced_dev /* zeroed by the caller; may be NULL */, ggms_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Typed link-prediction seeds (an extension): ggms_link_seeds on a heterogeneous graph -- a negative of a positive
+ * (u, r, v) is a node of v's type, and only u's edges under r reject.  Stateless: a pure function of the inputs.
+ *   edge_type   device, one uint8 per position of graph->indices, non-decreasing inside every list (ggms_sample_khop_typed's
+ *               precondition).  node_type: device, one uint8 per node, every value < num_node_type = T, 1 <= T <=
+ *               GGMS_MAX_NODE_TYPES.
+ *   type lists  type_nodes[num_node]: the node ids grouped by type, ascending inside a type; type_base[T + 1]: the
+ *               groups' starts (type_base[0] = 0, type_base[T] = num_node).  Built once per data set.
+ *   positive e  u and v as ggms_link_seeds finds them; r = edge_type[e]; t = node_type[v]; n_t = type_base[t + 1] -
+ *               type_base[t] (>= 1: v is of type t).  On a data set whose relations join fixed node types, t is the type of
+ *               every destination of r: no relation table is read.
+ *   candidates  cand_t(e, j, a) = type_nodes[type_base[t] + mulhi32(fmix32(fmix32(e ^ salt) + 0x9e3779b9 * (8 j + a + 1)),
+ *               n_t)]: ggms_link_seeds' hash, scaled to the type instead of to num_node.
+ *   modes       GGMS_NEG_TYPED_UNIFORM: negative j = cand_t(e, j, 0).
+ *               GGMS_NEG_TYPED_EXCLUDE: a candidate w is rejected if w == u or w occurs in u's SEGMENT of r -- the
+ *               contiguous positions of u's list whose type is r; it holds e.  An edge (u, r', w) of another relation
+ *               does not reject: it is no positive of r.  First accepted attempt of a = 0 .. 7; all eight rejected:
+ *               attempt 7, counted in *num_forced_dev as ggms_link_seeds counts.
+ *   outputs     endpoints: ggms_link_seeds' layout.  out_rel (uint8[num_pos], may be NULL): r of every positive.
+ *               An edge id >= E -- and a positive whose destination is no node, has a type >= T or a type list without
+ *               nodes -- reads nothing further: GGMS_EMPTY_KEY in its 2 + K positions, 0xff in out_rel.
+ * GGMS_ERR_INVALID, before the device is touched: a sharded graph, T outside 1 .. GGMS_MAX_NODE_TYPES, num_negative
+ * outside 1 .. 64, a mode that is neither typed mode, a null array (out_rel and num_forced_dev may be NULL).
+ * ggms_link_seeds refuses the typed modes.  num_pos == 0 is GGMS_OK with nothing launched.  One launch: no workspace, no
+ * allocation, no synchronisation; only the segment is read, at most twice.
+ * ------------------------------------------------------------------------- */
+#define GGMS_NEG_TYPED_UNIFORM 2
+#define GGMS_NEG_TYPED_EXCLUDE 3
+int ggms_link_seeds_typed(const ggms_graph_t *graph, const uint8_t *edge_type, const uint8_t *node_type,
+                          const ggms_id_t *type_nodes, const uint32_t *type_base, uint32_t num_node_type,
+                          const ggms_id_t *edge_ids, size_t num_pos, uint32_t num_negative, int mode, uint32_t salt,
+                          ggms_id_t *endpoints /* num_pos * (2 + num_negative) ids */, uint8_t *out_rel /* may be NULL */,
+                          uint64_t *num_forced_dev /* zeroed by the caller; may be NULL */, ggms_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Positive edges out of the sampled layers (an extension; the reference has no such operator): a link-prediction batch
  * samples the neighbourhood of its positives' endpoints from the graph that holds the positives, so (u, v) itself shows
  * up among u's sampled neighbours.  This call removes every such edge from the layers of a sampled batch, in place.

@@ -119,6 +119,12 @@ void samgraph_get_graph_output_nodes(uint64_t key, samgraph_tensor_t *out);     
  * (0 without the key). */
 void samgraph_get_graph_seed_ids(uint64_t key, samgraph_tensor_t *out);
 size_t samgraph_num_negative(void);
+/* negative_mode = typed_uniform | typed_exclude (with sample_type khop_typed and hetero_batch = on; anything else is fatal
+ * by name): ggms_link_seeds_typed draws the negatives -- nodes of the positive destination's type, rejected only by the
+ * source's edges of the positive's relation -- with the same salt and the same forced word.
+ *   samgraph_get_graph_link_rel(key)   the relation of each of the B positives, edge_type[link_edge_ids], uint8: which
+ *     decoder scores pair i.  Fatal with the other modes. */
+void samgraph_get_graph_link_rel(uint64_t key, samgraph_tensor_t *out);
 size_t samgraph_get_graph_num_excluded(uint64_t key);
 /* Extensions for config key feat_learnable = sgd | adagrad (arch1, FEAT_DATA_TYPE F32; with it feat_lr: required,
  * finite; feat_eps: Adagrad only, default 1e-10, > 0).  The table on the device is LEARNABLE: it starts as feat.bin, and

@@ -118,6 +118,7 @@ SAMGRAPH_SYMBOLS = {
     "samgraph_get_graph_num_excluded": (_sz, [_u64]),
     "samgraph_get_graph_edge_ids": (None, [_u64, _i, _TP]), "samgraph_get_graph_edge_feat": (None, [_u64, _i, _TP]),
     "samgraph_get_graph_link_edge_ids": (None, [_u64, _TP]),
+    "samgraph_get_graph_link_rel": (None, [_u64, _TP]),
     "samgraph_get_graph_num_induced": (_sz, [_u64]),
     "samgraph_get_graph_induced_row": (None, [_u64, _TP]), "samgraph_get_graph_induced_col": (None, [_u64, _TP]),
     "samgraph_get_graph_induced_edge_ids": (None, [_u64, _TP]),

@@ -302,6 +302,10 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
       fatal(__FILE__, __LINE__, "task = " + v + ": node_classification (the default) or link_prediction");
     cfg.link_prediction = v == "link_prediction";
   }
+  if (!cfg.link_prediction && kv.count("negative_mode") &&
+      (kv["negative_mode"] == "typed_uniform" || kv["negative_mode"] == "typed_exclude"))
+    fatal(__FILE__, __LINE__, "negative_mode = " + kv["negative_mode"] + " needs task = link_prediction: only a batch of "
+                              "positive edges has negatives");
   if (cfg.link_prediction) {
     static const char *const arch_names[] = {"arch0", "arch1", "arch2", "arch3", "arch4", "arch5", "arch6", "arch7"};
     if (cfg.arch != kArch1)
@@ -319,10 +323,15 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
     }
     if (kv.count("negative_mode")) {
       const std::string v = kv["negative_mode"];
-      if (v != "uniform" && v != "exclude")
-        fatal(__FILE__, __LINE__, "negative_mode = " + v + ": uniform or exclude (the default)");
-      cfg.negative_mode = v == "uniform" ? GGMS_NEG_UNIFORM : GGMS_NEG_EXCLUDE;
+      if (v != "uniform" && v != "exclude" && v != "typed_uniform" && v != "typed_exclude")
+        fatal(__FILE__, __LINE__, "negative_mode = " + v + ": uniform, exclude (the default), typed_uniform or typed_exclude");
+      cfg.negative_mode = v == "uniform" ? GGMS_NEG_UNIFORM : v == "exclude" ? GGMS_NEG_EXCLUDE
+                          : v == "typed_uniform" ? GGMS_NEG_TYPED_UNIFORM : GGMS_NEG_TYPED_EXCLUDE;
     }
+    if (cfg.TypedNegatives() && !(cfg.Typed() && cfg.hetero))
+      fatal(__FILE__, __LINE__, "negative_mode = " + kv["negative_mode"] + " needs sample_type = khop_typed (_sample_type 10) "
+                                "and hetero_batch = on: they load edge_type.bin and node_type.bin, which say what a "
+                                "positive's relation and its destination's type are");
     if (kv.count("exclude_seed_edges")) {
       const std::string v = kv["exclude_seed_edges"];
       if (v != "none" && v != "self" && v != "both")
@@ -808,10 +817,19 @@ void Engine::LoadDataset() {
     ds.node_type = MapFile("node_type.bin", ds.num_node, false);
     ds.num_node_type = (uint32_t)T;
     const uint8_t *nt = (const uint8_t *)ds.node_type.ptr;
-    for (size_t v = 0; v < ds.num_node; ++v)
+    if (cfg.TypedNegatives()) ds.type_base.assign(T + 1, 0);
+    for (size_t v = 0; v < ds.num_node; ++v) {
       if (nt[v] >= T)
         fatal(__FILE__, __LINE__, "hetero_batch: node_type.bin: node " + std::to_string(v) + " has the type " +
                                       std::to_string((unsigned)nt[v]) + ", NUM_NODE_TYPE is " + std::to_string(T));
+      if (cfg.TypedNegatives()) ++ds.type_base[nt[v] + 1];
+    }
+    if (cfg.TypedNegatives()) { // the type lists of ggms_link_seeds_typed: counts -> starts, then the ids in ascending order
+      for (size_t t = 0; t < T; ++t) ds.type_base[t + 1] += ds.type_base[t];
+      std::vector<uint32_t> at(ds.type_base.begin(), ds.type_base.end() - 1);
+      ds.type_nodes.resize(ds.num_node);
+      for (size_t v = 0; v < ds.num_node; ++v) ds.type_nodes[at[nt[v]]++] = (uint32_t)v;
+    }
     if (cfg.typed_feat) LoadTypedFeat(meta, meta_text);
   }
   if (cfg.Typed()) { // the edge types: NUM_EDGE uint8 in CSR order, sorted inside every list, below NUM_EDGE_TYPE
@@ -1517,6 +1535,12 @@ void Engine::SampleInit(int worker_id, const std::string &ctx) {
   if (cfg.hetero) { // the node types in HBM; one workspace per pipeline, shared by the two calls (they follow each other)
     SAM_HIP(hipMalloc((void **)&d_node_type_, std::max<size_t>(ds.num_node, 16)));
     SAM_HIP(hipMemcpyAsync(d_node_type_, ds.node_type.ptr, ds.num_node, hipMemcpyHostToDevice, stream_));
+    if (cfg.TypedNegatives()) { // the type lists, once per data set
+      SAM_HIP(hipMalloc((void **)&d_type_nodes_, std::max<size_t>(ds.num_node, 4) * 4));
+      SAM_HIP(hipMalloc((void **)&d_type_base_, ds.type_base.size() * 4));
+      SAM_HIP(hipMemcpyAsync(d_type_nodes_, ds.type_nodes.data(), ds.num_node * 4, hipMemcpyHostToDevice, stream_));
+      SAM_HIP(hipMemcpyAsync(d_type_base_, ds.type_base.data(), ds.type_base.size() * 4, hipMemcpyHostToDevice, stream_));
+    }
     SAM_HIP(hipStreamSynchronize(stream_));
     hetero_ws_bytes_ = std::max(ggms_hetero_nodes_workspace_bytes(max_unique_, ds.num_node_type),
                                 ggms_hetero_edges_workspace_bytes(max_edges_.data(), L, cfg.num_edge_type));
@@ -1944,6 +1968,7 @@ void Engine::TrainInit(int worker_id, const std::string &ctx) {
     if (cfg.link_prediction) {
       SAM_HIP(hipMalloc((void **)&b->edge_ids, cfg.batch_size * 4));
       SAM_HIP(hipMalloc((void **)&b->seed_ids, max_seeds_ * 4));
+      if (cfg.TypedNegatives()) SAM_HIP(hipMalloc((void **)&b->link_rel, std::max<size_t>(cfg.batch_size, 16)));
       if (cfg.exclude_seed_edges) { // the dropped count of every layer: its own words, not counts words
         SAM_HIP(hipMalloc((void **)&b->excluded_dev, L * 8));
         SAM_HIP(hipHostMalloc((void **)&b->excluded, L * 8));
@@ -2159,8 +2184,13 @@ void Engine::SampleInto(Batch *b, Pipe &P) {
     uint64_t *forced = s.counts_dev + GGMS_COUNT_LINK_FORCED(L);
     SAM_HIP(hipMemsetAsync(forced, 0, 8, P.stream));
     const uint32_t salt = ggms::fmix32(extra.labor_salt ^ 0x6c696e6bu);
-    SAM_GGMS(ggms_link_seeds(&graph_, b->edge_ids, b->num_pos, cfg.num_negative, cfg.negative_mode, salt, s.output_nodes,
-                             forced, P.stream));
+    if (cfg.TypedNegatives()) // negatives of the destination's type, the relation's segment rejects; out_rel rides along
+      SAM_GGMS(ggms_link_seeds_typed(&graph_, d_edge_type_, d_node_type_, d_type_nodes_, d_type_base_, ds.num_node_type,
+                                     b->edge_ids, b->num_pos, cfg.num_negative, cfg.negative_mode, salt, s.output_nodes,
+                                     b->link_rel, forced, P.stream));
+    else
+      SAM_GGMS(ggms_link_seeds(&graph_, b->edge_ids, b->num_pos, cfg.num_negative, cfg.negative_mode, salt, s.output_nodes,
+                               forced, P.stream));
     extra.seeds_distinct = 0;
     // khop_temporal: every entry of the seed list is sampled before the time of its positive edge
     if (cfg.Temporal())

@@ -106,6 +106,12 @@ struct RunConfig {
   bool link_prediction = false;
   uint32_t num_negative = 1;
   int negative_mode = GGMS_NEG_EXCLUDE;
+  // extension (`negative_mode` = typed_uniform | typed_exclude; needs _sample_type 10 (khop_typed) and hetero_batch = on,
+  // which load edge_type.bin and node_type.bin): the negatives of a positive are nodes of its destination's type, only the
+  // source's edges of the positive's relation reject (ggms_link_seeds_typed), and a batch carries its positives' relations
+  bool TypedNegatives() const {
+    return link_prediction && (negative_mode == GGMS_NEG_TYPED_UNIFORM || negative_mode == GGMS_NEG_TYPED_EXCLUDE);
+  }
   // extension (config key `exclude_seed_edges` = none | self | both; read with task = link_prediction only): the batch's
   // positive edges (self), and their mirrors (both), leave its sampled layers (ggms_drop_pair_edges' `which`; 0 = none)
   uint32_t exclude_seed_edges = 0;
@@ -200,6 +206,9 @@ struct Dataset {
   HostArray node_type;
   uint32_t num_node_type = 0;
   std::vector<uint8_t> rel_src_type, rel_dst_type;
+  // typed negatives: the node ids grouped by type, ascending inside a type, and the T + 1 group starts -- built in the
+  // load's pass over node_type.bin; empty with every other negative_mode
+  std::vector<uint32_t> type_nodes, type_base;
   // typed_feat: per node type its table (the mapped node_feat_<t>.bin; dim 0: the type has none), the number of nodes of
   // the type (= the table's rows) and its first node id.  Row k of a table belongs to the type's k-th node in ascending
   // id.  node_rank: every node's rank inside its type -- empty where node_type.bin is non-decreasing in the node id (the
@@ -278,6 +287,8 @@ struct Batch {
   // entry of the seed list -- the pair ids -- copied out of the sampling workspace before the next batch reuses it
   uint32_t *edge_ids = nullptr, *seed_ids = nullptr;
   size_t num_pos = 0;
+  // typed negatives: the relation of every positive (ggms_link_seeds_typed's out_rel).  Null with every other negative_mode
+  uint8_t *link_rel = nullptr;
   // exclude_seed_edges: the edges ggms_drop_pair_edges took out of each layer -- device words (zeroed per batch) and
   // their pinned host copy, valid with the counts.  Null without the key: the batch then carries no extra packet.
   uint64_t *excluded_dev = nullptr, *excluded = nullptr;
@@ -498,6 +509,7 @@ class Engine {
   };
   size_t hetero_ws_bytes_ = 0;
   uint8_t *d_node_type_ = nullptr; // hetero_batch: the node types in HBM
+  uint32_t *d_type_nodes_ = nullptr, *d_type_base_ = nullptr; // typed negatives: the type lists in HBM, 4 N + 4 (T + 1) bytes
   // typed_feat: the tables in HBM (null for a type without one), the rank table (null: ranks are node - first_node), the
   // leaf's table array and the bytes of a batch's feature buffer
   std::vector<void *> d_node_feat_;

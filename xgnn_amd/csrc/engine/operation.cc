@@ -210,6 +210,14 @@ void samgraph_get_graph_link_edge_ids(uint64_t key, samgraph_tensor_t *out) {
   auto *b = E.Current(key);
   fill(out, b->edge_ids, (int64_t)b->num_pos, 1, 1, GGMS_I32, E.batch_device_type(), E.trainer_device());
 }
+// negative_mode = typed_uniform | typed_exclude: the relation of every positive edge (edge_type[link_edge_ids]) -- uint8
+void samgraph_get_graph_link_rel(uint64_t key, samgraph_tensor_t *out) {
+  auto &E = Engine::Get();
+  if (!E.cfg.TypedNegatives())
+    sam::fatal(__FILE__, __LINE__, "samgraph_get_graph_link_rel needs negative_mode = typed_uniform or typed_exclude");
+  auto *b = E.Current(key);
+  fill(out, b->link_rel, (int64_t)b->num_pos, 1, 1, GGMS_U8, E.batch_device_type(), E.trainer_device());
+}
 // _sample_type 9 (khop_temporal): the time of every edge of layer l (edge_time[edge_ids]), the final cut-off of every input
 // node, the times of the batch's positive edges -- uint32 bits in get_graph_row's dtype
 static sam::Batch *temporal_batch(uint64_t key, const char *who) {

@@ -302,6 +302,39 @@ def link_seeds(graph, edge_ids, num_negative, mode=NEG_EXCLUDE, salt=0, count_fo
     return out[: n * (2 + num_negative)], forced
 
 
+NEG_TYPED_UNIFORM, NEG_TYPED_EXCLUDE = 2, 3  # ggms_link_seeds_typed modes
+
+
+def type_lists(node_type, num_node_type):
+    """The type lists of ggms_link_seeds_typed: (type_nodes int32[N]: the node ids grouped by type, ascending inside a
+    type; type_base int32[T + 1]: the groups' starts), on node_type's device.  Once per data set, not per batch."""
+    _u8(node_type)
+    nodes = torch.argsort(node_type.to(torch.int16), stable=True).to(torch.int32)
+    count = torch.bincount(node_type.to(torch.int64), minlength=num_node_type)
+    assert count.numel() == num_node_type, "node_type holds a value >= num_node_type"
+    base = torch.zeros(num_node_type + 1, dtype=torch.int64, device=node_type.device)
+    base[1:] = torch.cumsum(count, 0)
+    return nodes.contiguous(), base.to(torch.int32)
+
+
+def link_seeds_typed(graph, edge_type, node_type, type_nodes, type_base, edge_ids, num_negative,
+                     mode=NEG_TYPED_EXCLUDE, salt=0, count_forced=True):
+    """ggms_link_seeds_typed: ops.link_seeds on a heterogeneous graph -- the negatives of positive (u, r, v) are nodes of
+    v's type, and only u's edges under r reject (include/ggms.h).  type_nodes, type_base: ops.type_lists(node_type, T).
+    Returns (endpoints, rel uint8[B]: r of every positive, num_forced[1] on device or None)."""
+    _require_gpu(edge_ids)
+    _i32(edge_ids), _u8(edge_type), _u8(node_type), _i32(type_nodes), _i32(type_base)
+    n, dev = edge_ids.numel(), edge_ids.device
+    out = torch.empty(max(1, n * (2 + max(0, num_negative))), dtype=torch.int32, device=dev)
+    rel = torch.empty(max(1, n), dtype=torch.uint8, device=dev)
+    forced = torch.zeros(1, dtype=torch.int64, device=dev) if count_forced else None
+    check(lib().ggms_link_seeds_typed(C.byref(graph.c), _ptr(edge_type), _ptr(node_type), _ptr(type_nodes),
+                                      _ptr(type_base), type_base.numel() - 1, _ptr(edge_ids), n, num_negative, mode,
+                                      salt & 0xFFFFFFFF, _ptr(out), _ptr(rel), _ptr(forced), _stream()),
+          "ggms_link_seeds_typed")
+    return out[: n * (2 + num_negative)], rel[:n], forced
+
+
 DROP_FORWARD, DROP_REVERSE = 1, 2  # ggms_drop_pair_edges' `which` bits
 
 

@@ -236,6 +236,12 @@ def get_graph_link_edge_ids(batch_key):
     return _get("samgraph_get_graph_link_edge_ids", batch_key)
 
 
+def get_graph_link_rel(batch_key):
+    """negative_mode typed_uniform / typed_exclude: the relation of every positive edge of the batch (uint8), in the order
+    of get_graph_link_edge_ids -- the decoder that scores pair i and its negatives."""
+    return _get("samgraph_get_graph_link_rel", batch_key)
+
+
 def get_graph_link_pairs(batch_key):
     """(pos_src, pos_dst, neg_src, neg_dst) of a link_prediction batch: views of the batch's one id tensor
     (get_graph_seed_ids), B positives and K negatives each -- pos_src, pos_dst of shape (B,), neg_src (pos_src expanded)
