@@ -236,7 +236,8 @@ enum ggms_sample_type {
   GGMS_KHOP_LABOR = 8, /* an extension: ggms_sample_khop_labor below */
   GGMS_KHOP_TEMPORAL = 9, /* an extension: ggms_sample_khop_temporal / ggms_sample_batch_temporal below */
   GGMS_KHOP_TYPED = 10, /* an extension: ggms_sample_khop_typed / ggms_sample_batch_typed below */
-  GGMS_KHOP_LABOR_WEIGHTED = 11 /* an extension: ggms_sample_khop_labor_weighted / ggms_sample_batch_labor_weighted */
+  GGMS_KHOP_LABOR_WEIGHTED = 11, /* an extension: ggms_sample_khop_labor_weighted / ggms_sample_batch_labor_weighted */
+  GGMS_RANDOM_WALK_METAPATH = 12 /* an extension: ggms_sample_walk_metapath / ggms_sample_batch_walk_metapath below */
 };
 
 /* Workspace of every leaf sampler below but random walk, whose size depends on
@@ -454,6 +455,45 @@ int ggms_sample_random_walk(const ggms_graph_t *graph, const ggms_id_t *input,
                             ggms_id_t *out_data, uint64_t *num_out_dev,
                             void *states, size_t num_states, void *workspace,
                             size_t workspace_bytes, ggms_stream_t stream);
+
+/* random_walk_metapath (an extension; the reference has no such sampler; DGL: PinSAGESampler /
+ * RandomWalkNeighborSampler(metapath=[...])): PinSAGE's neighbourhood on a heterogeneous graph.  A walk follows a path of
+ * relations over and over (item -> user -> item); only the node at the END of a full traversal is a visit, so the
+ * neighbours of an item are items.
+ *   inputs      graph: one CSR, unsharded.  edge_type: one uint8 per position of graph->indices, every value < num_type = R,
+ *               1 <= R <= GGMS_MAX_EDGE_TYPES, non-decreasing inside every list (khop_typed's type-sorted CSR).
+ *               metapath[0 .. M), a HOST array, 1 <= M <= GGMS_MAX_METAPATH, every entry < R.  num_traversal T >= 1,
+ *               num_walk W >= 1, K >= 1, restart_prob p in [0, 1], a 32-bit layer_salt, input[0 .. num_input).
+ *   randomness  stateless, no RNG pool.  All arithmetic is uint32 mod 2^32; fmix32 is khop_labor's (above).
+ *               base = fmix32(s ^ layer_salt) for the seed's node id s;  wk = fmix32(base + 0x9E3779B9 * (w + 1)) for walk w;
+ *               draw(x) = fmix32(wk + 0x85EBCA6B * (x + 1)).  Step j of traversal t uses x = 2 * (t * M + j); the restart
+ *               test after traversal t uses x = 2 * t + 1.  The walks are keyed by node id: equal seeds walk identically.
+ *   step        from node u under relation r = metapath[j]: [b, b + e) is r's segment of u's list, b = the number of its
+ *               entries with type < r, e = the number with type r.  e = 0 (degree 0 included): the walk ends.  Else
+ *               u <- indices[indptr[u] + b + mulhi32(draw(x), e)]  (mulhi32(a, b) = (a * b) >> 32 in 64 bits).
+ *   traversal   after the M steps of traversal t the node reached is visit number t * W + w of the seed (random walk's
+ *               [step][walk] order, a traversal in the place of a step).  Then the walk ends if (uint64)draw(2 t + 1) < thr,
+ *               thr = min(2^32, floor(p * 2^32)) computed on the host in double.  A walk that ended visits nothing more.
+ *   output      exactly ggms_sample_random_walk's: per seed, in input order, the distinct visited nodes by count
+ *               descending, ties by the smaller first visit number, cut at K; (out_src = seed, out_dst = visited,
+ *               out_data = count), *num_out_dev = their number; all three hold num_input * K entries.  An input entry
+ *               equal to GGMS_EMPTY_KEY yields nothing.  The seed itself may appear among its neighbours.
+ *   unsorted    a list whose type bytes are not sorted gets SOME segment inside [0, d): which edge is followed is
+ *               unspecified, nothing outside the list is read.
+ *   arguments   refused with GGMS_ERR_INVALID and a message, before any device call: a sharded graph, a null edge_type,
+ *               R outside 1 .. GGMS_MAX_EDGE_TYPES, M outside 1 .. GGMS_MAX_METAPATH, a metapath entry >= R, T, W or K = 0,
+ *               p outside [0, 1] or not finite, a short workspace.  num_input == 0: GGMS_OK, *num_out_dev = 0, no kernel
+ *               is launched.
+ * Up to 128 visits per seed (T * W) are ranked in LDS, more in the visit scratch itself, like random walk's.  No
+ * allocation, no synchronisation, every size stays on the device. */
+#define GGMS_MAX_METAPATH 8
+size_t ggms_sample_walk_metapath_workspace_bytes(size_t num_input, size_t num_traversal, size_t num_walk, size_t K);
+int ggms_sample_walk_metapath(const ggms_graph_t *graph, const uint8_t *edge_type, uint32_t num_type,
+                              const uint32_t *metapath /* host, metapath_len */, uint32_t metapath_len,
+                              const ggms_id_t *input, size_t num_input, size_t num_traversal, double restart_prob,
+                              size_t num_walk, size_t K, uint32_t layer_salt, ggms_id_t *out_src, ggms_id_t *out_dst,
+                              ggms_id_t *out_data, uint64_t *num_out_dev, void *workspace, size_t workspace_bytes,
+                              ggms_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Ordered hash table -- OrderedHashTable, cuda/cuda_hashtable.h:103-153,
@@ -701,6 +741,27 @@ int ggms_sample_batch_typed(const ggms_graph_t *graph, const ggms_id_t *seeds, s
                             ggms_id_t *const *eid, uint8_t *const *etype, uint64_t *counts_dev, const ggms_typed_t *t,
                             const ggms_sample_extra_t *extra, void *workspace, size_t workspace_bytes,
                             ggms_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * The metapath walk batch (an extension): ggms_sample_batch's layers with random_walk_metapath as the sampler.
+ *   t           the edge types (ggms_typed_t's edge_type and num_type; type_fanout is not read and may be NULL).
+ *   metapath    HOST, metapath_len relation ids, the same path for every layer.
+ *   extra       required: random_walk_length = the number of traversals T, random_walk_restart_prob, num_random_walk = W,
+ *               data = HOST array of L device pointers, the visit counts of every layer.  fanouts[i] = K.
+ *   layer i     ggms_sample_walk_metapath's rule with layer_salt = fmix32(labor_salt + 0x9e3779b9 * (i + 1)).
+ *   counts_dev, row, col, both table layouts, the numbering, seeds_distinct: ggms_sample_batch's.  rng_wait / rng_done
+ *   are ignored (stateless).  ggms_sample_batch_seed_ids(GGMS_RANDOM_WALK_METAPATH, ...) gives the raw seeds' local ids.
+ *   ggms_sample_batch(GGMS_RANDOM_WALK_METAPATH, ...) is GGMS_ERR_INVALID and names this call.  The walk's refusals are
+ *   ggms_sample_walk_metapath's.
+ * ------------------------------------------------------------------------- */
+size_t ggms_sample_batch_walk_metapath_workspace_bytes(size_t num_seeds, const size_t *fanouts, uint32_t num_layer,
+                                                       const ggms_sample_extra_t *extra);
+int ggms_sample_batch_walk_metapath(const ggms_graph_t *graph, const ggms_id_t *seeds, size_t num_seeds,
+                                    const size_t *fanouts, uint32_t num_layer, ggms_hashtable_t *ht, ggms_id_t *const *row,
+                                    ggms_id_t *const *col, uint64_t *counts_dev, const ggms_typed_t *t,
+                                    const uint32_t *metapath /* host, metapath_len */, uint32_t metapath_len,
+                                    const ggms_sample_extra_t *extra, void *workspace, size_t workspace_bytes,
+                                    ggms_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * The weighted LABOR batch (an extension): ggms_sample_batch's chain with khop_labor_weighted as the sampler.

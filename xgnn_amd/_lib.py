@@ -178,6 +178,13 @@ SYMBOLS = {
     "ggms_sample_batch_labor_weighted": (_i, [C.POINTER(Graph), _vp, _sz, C.POINTER(_sz), _u32, C.POINTER(HashTable),
                                               C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp, _vp,
                                               C.POINTER(SampleExtra), _vp, _sz, _vp]),
+    "ggms_sample_walk_metapath_workspace_bytes": (_sz, [_sz, _sz, _sz, _sz]),
+    "ggms_sample_walk_metapath": (_i, [C.POINTER(Graph), _vp, _u32, C.POINTER(C.c_uint32), _u32, _vp, _sz, _sz,
+                                       C.c_double, _sz, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ggms_sample_batch_walk_metapath_workspace_bytes": (_sz, [_sz, C.POINTER(_sz), _u32, C.POINTER(SampleExtra)]),
+    "ggms_sample_batch_walk_metapath": (_i, [C.POINTER(Graph), _vp, _sz, C.POINTER(_sz), _u32, C.POINTER(HashTable),
+                                             C.POINTER(_vp), C.POINTER(_vp), _vp, C.POINTER(Typed),
+                                             C.POINTER(C.c_uint32), _u32, C.POINTER(SampleExtra), _vp, _sz, _vp]),
     "ggms_link_seeds": (_i, [C.POINTER(Graph), _vp, _sz, _u32, _i, _u32, _vp, _vp, _vp]),
     "ggms_link_seeds_typed": (_i, [C.POINTER(Graph), _vp, _vp, _vp, _vp, _u32, _vp, _sz, _u32, _i, _u32, _vp, _vp, _vp,
                                    _vp]),

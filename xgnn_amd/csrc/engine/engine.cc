@@ -182,7 +182,7 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
       fatal(__FILE__, __LINE__, "only arch0 (CPU), arch1 (standalone), arch3 (dedicated), arch4 (dedicated with prefetch), "
                                 "arch5 (factored) and arch6 (SGNN/XGNN) are built; see DESIGN.md");
   }
-  if (cfg.sample_type != GGMS_RANDOM_WALK) { // operation.cc:150-163
+  if (!cfg.Walk()) { // operation.cc:150-163
     SAM_CHECK(kv.count("num_fanout") && kv.count("fanout"), "khop sampling needs num_fanout/fanout");
     size_t nf = std::stoull(kv["num_fanout"]);
     std::stringstream ss(kv["fanout"]);
@@ -227,7 +227,12 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
     cfg.lookahead = 0;
     cfg.pipelines = 1;
   }
-  SAM_CHECK(cfg.sample_type >= GGMS_KHOP0 && cfg.sample_type <= GGMS_KHOP_LABOR_WEIGHTED, "unknown sample type");
+  SAM_CHECK(cfg.sample_type >= GGMS_KHOP0 && cfg.sample_type <= GGMS_RANDOM_WALK_METAPATH, "unknown sample type");
+  if (cfg.Metapath() && cfg.arch != kArch1) {
+    static const char *const arch_names[] = {"arch0", "arch1", "arch2", "arch3", "arch4", "arch5", "arch6", "arch7"};
+    fatal(__FILE__, __LINE__, std::string(arch_names[cfg.arch]) + ": _sample_type 12 (random_walk_metapath) is not built: "
+                              "the edge types are read in arch1's sampling chain only");
+  }
   if (cfg.Weighted() && cfg.arch != kArch1) {
     static const char *const arch_names[] = {"arch0", "arch1", "arch2", "arch3", "arch4", "arch5", "arch6", "arch7"};
     fatal(__FILE__, __LINE__, std::string(arch_names[cfg.arch]) + ": _sample_type 11 (khop_labor_weighted) is not built: the "
@@ -311,9 +316,10 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
     if (cfg.arch != kArch1)
       fatal(__FILE__, __LINE__, std::string(arch_names[cfg.arch]) + ": task = link_prediction is not built: edge seeds, "
                                 "negative sampling and the pair ids run in arch1's sampling chain only");
-    if (cfg.sample_type == GGMS_RANDOM_WALK)
-      fatal(__FILE__, __LINE__, "task = link_prediction with _sample_type 3 (random_walk) is not built: the pair ids are "
-                                "the k-hop batch's seed ids");
+    if (cfg.Walk())
+      fatal(__FILE__, __LINE__, "task = link_prediction with _sample_type " + std::to_string(cfg.sample_type) +
+                                    (cfg.Metapath() ? " (random_walk_metapath)" : " (random_walk)") +
+                                    " is not built: the pair ids are the k-hop batch's seed ids");
     if (kv.count("num_negative")) {
       long long k = 0;
       try { k = std::stoll(kv["num_negative"]); } catch (...) { k = 0; }
@@ -427,6 +433,32 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
                                   " (leave fanout to the Python front-end, or give the rows' sums)");
     }
   }
+  if (cfg.Metapath()) { // extension: PinSAGE's walks along a relation path
+    const std::string who = "_sample_type 12 (random_walk_metapath)";
+    if (cfg.use_dist_graph)
+      fatal(__FILE__, __LINE__, who + " with use_dist_graph: edge types are stored by position in ONE CSR, a sharded "
+                                "topology has none");
+    if (cfg.inline_heads == 1)
+      fatal(__FILE__, __LINE__, who + " with inline_heads = 1: only khop3 reads the list heads; a walk step reads a "
+                                "relation's segment of the list");
+    cfg.inline_heads = 0; // auto means off
+    if (!kv.count("metapath"))
+      fatal(__FILE__, __LINE__, who + " needs the config key metapath: 1 .. " + std::to_string(GGMS_MAX_METAPATH) +
+                                    " relation ids, the path one traversal follows");
+    std::stringstream ss(kv["metapath"]);
+    long long v;
+    while (ss >> v) {
+      if (v < 0 || v >= GGMS_MAX_EDGE_TYPES)
+        fatal(__FILE__, __LINE__, "metapath: the value " + std::to_string(v) + " is out of range: a relation id is 0 .. "
+                                  "NUM_EDGE_TYPE - 1, at most " + std::to_string(GGMS_MAX_EDGE_TYPES - 1));
+      cfg.metapath.push_back((uint32_t)v);
+    }
+    if (!ss.eof() || cfg.metapath.empty() || cfg.metapath.size() > GGMS_MAX_METAPATH)
+      fatal(__FILE__, __LINE__, "metapath has " + std::to_string(cfg.metapath.size()) + " relation ids: 1 .. " +
+                                    std::to_string(GGMS_MAX_METAPATH) + " integers");
+    if (!(cfg.random_walk_restart_prob >= 0.0 && cfg.random_walk_restart_prob <= 1.0))
+      fatal(__FILE__, __LINE__, "random_walk_restart_prob = " + kv["random_walk_restart_prob"] + ": a probability, 0 .. 1");
+  }
   if (cfg.Weighted()) { // extension: weighted sampling without replacement on edge_weight.bin
     const std::string who = "_sample_type 11 (khop_labor_weighted)";
     if (cfg.use_dist_graph)
@@ -459,9 +491,11 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
     if (cfg.use_dist_graph)
       fatal(__FILE__, __LINE__, key + " with use_dist_graph: an edge id is a position in ONE CSR, a sharded topology has "
                                 "none");
-    if (cfg.sample_type == GGMS_RANDOM_WALK)
-      fatal(__FILE__, __LINE__, key + " with _sample_type 3 (random_walk) is not built: its edges join a node and a node "
-                                "it visited, they are not edges of the graph");
+    if (cfg.Walk())
+      fatal(__FILE__, __LINE__, key + " with _sample_type " + std::to_string(cfg.sample_type) +
+                                    (cfg.Metapath() ? " (random_walk_metapath)" : " (random_walk)") +
+                                    " is not built: its edges join a node and a node it visited, they are not edges of "
+                                    "the graph");
     if (cfg.sample_type == GGMS_KHOP2)
       fatal(__FILE__, __LINE__, key + " with _sample_type 5 (khop2) is not built: khop2 permutes indices in place, a "
                                 "position names another edge after every batch");
@@ -832,22 +866,30 @@ void Engine::LoadDataset() {
     }
     if (cfg.typed_feat) LoadTypedFeat(meta, meta_text);
   }
-  if (cfg.Typed()) { // the edge types: NUM_EDGE uint8 in CSR order, sorted inside every list, below NUM_EDGE_TYPE
+  if (cfg.Typed() || cfg.Metapath()) { // the edge types: NUM_EDGE uint8 in CSR order, sorted inside every list, below NUM_EDGE_TYPE
+    const std::string who = cfg.Typed() ? "khop_typed" : "random_walk_metapath";
     if (!meta.count("NUM_EDGE_TYPE"))
-      fatal(__FILE__, __LINE__, "khop_typed: meta.txt lacks NUM_EDGE_TYPE (datagen.write_dataset(edge_type=, num_edge_type=))");
+      fatal(__FILE__, __LINE__, who + ": meta.txt lacks NUM_EDGE_TYPE (datagen.write_dataset(edge_type=, num_edge_type=))");
     const size_t R = meta["NUM_EDGE_TYPE"];
     if (R < 1 || R > GGMS_MAX_EDGE_TYPES)
-      fatal(__FILE__, __LINE__, "khop_typed: NUM_EDGE_TYPE = " + std::to_string(R) + ": 1 .. " + std::to_string(GGMS_MAX_EDGE_TYPES));
-    if (R != cfg.num_edge_type)
+      fatal(__FILE__, __LINE__, who + ": NUM_EDGE_TYPE = " + std::to_string(R) + ": 1 .. " + std::to_string(GGMS_MAX_EDGE_TYPES));
+    if (cfg.Typed() && R != cfg.num_edge_type)
       fatal(__FILE__, __LINE__, "type_fanout has " + std::to_string(cfg.type_fanout.size()) + " values, num_layer x "
                                     "NUM_EDGE_TYPE is " + std::to_string(cfg.fanout.size()) + " x " + std::to_string(R));
+    if (cfg.Metapath()) {
+      cfg.num_edge_type = (uint32_t)R;
+      for (size_t j = 0; j < cfg.metapath.size(); ++j)
+        if (cfg.metapath[j] >= R)
+          fatal(__FILE__, __LINE__, "metapath: entry " + std::to_string(j) + " is the relation " + std::to_string(cfg.metapath[j]) +
+                                        ", NUM_EDGE_TYPE is " + std::to_string(R));
+    }
     const std::string name = cfg.dataset_path + "edge_type.bin";
     struct stat st;
     if (stat(name.c_str(), &st) != 0)
-      fatal(__FILE__, __LINE__, "khop_typed: " + name + " is missing (NUM_EDGE uint8 types, one per position of "
+      fatal(__FILE__, __LINE__, who + ": " + name + " is missing (NUM_EDGE uint8 types, one per position of "
                                     "indices.bin; datagen.write_dataset(edge_type=...))");
     if ((size_t)st.st_size != ds.num_edge)
-      fatal(__FILE__, __LINE__, "khop_typed: edge_type.bin has " + std::to_string((size_t)st.st_size) + " bytes, NUM_EDGE is " +
+      fatal(__FILE__, __LINE__, who + ": edge_type.bin has " + std::to_string((size_t)st.st_size) + " bytes, NUM_EDGE is " +
                                     std::to_string(ds.num_edge));
     ds.edge_type = MapFile("edge_type.bin", ds.num_edge, false);
     const uint32_t *ip = (const uint32_t *)ds.indptr.ptr;
@@ -878,11 +920,11 @@ void Engine::LoadDataset() {
           }
         }
         if (p > ip[v] && t[p] < t[p - 1])
-          fatal(__FILE__, __LINE__, "khop_typed: edge_type.bin: the types of node " + std::to_string(v) + "'s list are not "
+          fatal(__FILE__, __LINE__, who + ": edge_type.bin: the types of node " + std::to_string(v) + "'s list are not "
                                         "non-decreasing (position " + std::to_string(p) + "); datagen.sort_lists_by_type "
                                         "re-sorts a graph");
         if (t[p] >= R)
-          fatal(__FILE__, __LINE__, "khop_typed: edge_type.bin: node " + std::to_string(v) + "'s list holds the type " +
+          fatal(__FILE__, __LINE__, who + ": edge_type.bin: node " + std::to_string(v) + "'s list holds the type " +
                                         std::to_string((unsigned)t[p]) + " (position " + std::to_string(p) +
                                         "), NUM_EDGE_TYPE is " + std::to_string(R));
       }
@@ -1465,7 +1507,7 @@ void Engine::SampleInit(int worker_id, const std::string &ctx) {
   extra_.random_walk_restart_prob = cfg.random_walk_restart_prob;
   extra_.num_random_walk = cfg.num_random_walk;
   // GPURandomStates dist_engine.cc:432-433; seed = wall clock unless the "seed" key is given
-  if (cfg.sample_type == GGMS_KHOP_LABOR || cfg.Temporal() || cfg.Typed() || cfg.Weighted()) { // stateless: their variates are hashes of (node id, salt) -- no RNG pool
+  if (cfg.sample_type == GGMS_KHOP_LABOR || cfg.Temporal() || cfg.Typed() || cfg.Weighted() || cfg.Metapath()) { // stateless: their variates are hashes of (node id, salt) -- no RNG pool
     num_states_ = 0;
     states_ = nullptr;
   } else {
@@ -1517,7 +1559,7 @@ void Engine::SampleInit(int worker_id, const std::string &ctx) {
       SAM_HIP(hipMemsetAsync(P.cut_table, 0, std::max<size_t>(ds.num_node, 1) * 8, stream_));
     }
   }
-  if (cfg.Typed()) { // the edge types in HBM, beside the topology the sampler reads
+  if (cfg.Typed() || cfg.Metapath()) { // the edge types in HBM, beside the topology the sampler reads
     SAM_HIP(hipMalloc((void **)&d_edge_type_, std::max<size_t>(ds.num_edge, 16)));
     SAM_HIP(hipMemcpyAsync(d_edge_type_, ds.edge_type.ptr, ds.num_edge, hipMemcpyHostToDevice, stream_));
     SAM_HIP(hipStreamSynchronize(stream_));
@@ -1573,7 +1615,7 @@ void Engine::SampleInit(int worker_id, const std::string &ctx) {
   if (cfg.arch == kArch5) { // the sampler's own batch buffers: it samples into them and packs them into a queue slot
     sbatch_ = std::make_unique<Batch>();
     Batch *b = sbatch_.get();
-    b->sampler.Alloc(max_edges_, max_unique_, max_seeds_, cfg.sample_type == GGMS_RANDOM_WALK);
+    b->sampler.Alloc(max_edges_, max_unique_, max_seeds_, cfg.Walk());
     SAM_HIP(hipEventCreateWithFlags(&b->ev_sampled, hipEventDisableTiming));
     SAM_HIP(hipEventCreateWithFlags(&b->ev_done, hipEventDisableTiming));
     QueueMap();
@@ -1630,7 +1672,7 @@ void Engine::Presample() {
   for (uint32_t i = 0; i < row.size(); ++i) {
     SAM_HIP(hipMalloc((void **)&row[i], std::max<size_t>(max_edges_[i], 4) * 4));
     SAM_HIP(hipMalloc((void **)&col[i], std::max<size_t>(max_edges_[i], 4) * 4));
-    if (cfg.sample_type == GGMS_RANDOM_WALK) SAM_HIP(hipMalloc((void **)&dat[i], std::max<size_t>(max_edges_[i], 4) * 4));
+    if (cfg.Walk()) SAM_HIP(hipMalloc((void **)&dat[i], std::max<size_t>(max_edges_[i], 4) * 4));
   }
   uint32_t stamp = 0; // closure k of the presample: stamp k, so `visit` is zeroed once
   for (size_t e = 0; e < cfg.presample_epoch; ++e) {
@@ -1654,6 +1696,12 @@ void Engine::Presample() {
       extra.seeds_distinct = train_distinct_ ? 1u : 0u; // slices of a permutation of the train set
       extra.labor_salt = ggms::labor_batch_salt(cfg.labor_seed, e, s); // the training rule, on the presample's own epochs
       // pipeline 0's table: its version stamp keeps counting when the training batches follow
+      if (cfg.Metapath()) {
+        const ggms_typed_t t{d_edge_type_, cfg.num_edge_type, nullptr};
+        SAM_GGMS(ggms_sample_batch_walk_metapath(&graph_, d_train + off, size, cfg.fanout.data(), L, &pipes_[0].ht,
+                                                 row.data(), col.data(), d_counts, &t, cfg.metapath.data(),
+                                                 (uint32_t)cfg.metapath.size(), &extra, ws_, ws_bytes_, stream_));
+      } else
       SAM_GGMS(ggms_sample_batch(cfg.sample_type, &graph_, d_train + off, size, cfg.fanout.data(), L, &pipes_[0].ht,
                                  states_, num_states_, row.data(), col.data(), d_counts, &extra, ws_, ws_bytes_, stream_));
       SAM_GGMS(ggms_count_nodes(d_freq, pipes_[0].ht.n2o, max_unique_, d_counts + GGMS_COUNT_INPUT(L), stream_));
@@ -1952,7 +2000,7 @@ void Engine::TrainInit(int worker_id, const std::string &ctx) {
   for (size_t s = 0; s < nslots; ++s) {
     auto b = std::make_unique<Batch>();
     b->slot = (int)s;
-    b->trainer.Alloc(max_edges_, max_unique_, max_seeds_, cfg.sample_type == GGMS_RANDOM_WALK);
+    b->trainer.Alloc(max_edges_, max_unique_, max_seeds_, cfg.Walk());
     if (cfg.typed_feat) { // per-type blocks, every one 16-byte aligned; the T + 1 offsets and their host copy
       typed_feat_bytes_ = ggms_gather_typed_out_bytes(typed_tables_.data(), ds.num_node_type, max_unique_);
       SAM_CHECK(typed_feat_bytes_ > 0, "typed_feat: the batch bound is out of ggms_gather_typed's range");
@@ -2044,7 +2092,7 @@ void Engine::TrainInit(int worker_id, const std::string &ctx) {
     if (BatchSampledElsewhere()) SAM_GGMS(ggms_launch_timer_create(&b->handoff_timer));
     if (Dedicated()) { // the sampler's side of the slot, on the sampler GPU (GetGraphFileCtx, cuda_engine.cc:437-481)
       SAM_HIP(hipSetDevice(device_));
-      b->sampler.Alloc(max_edges_, max_unique_, max_seeds_, cfg.sample_type == GGMS_RANDOM_WALK);
+      b->sampler.Alloc(max_edges_, max_unique_, max_seeds_, cfg.Walk());
     } else {
       b->sampler = b->trainer;
     }
@@ -2198,7 +2246,7 @@ void Engine::SampleInto(Batch *b, Pipe &P) {
                                     P.stream));
   }
   if (pipes_.size() > 1 && cfg.sample_type != GGMS_KHOP0 && cfg.sample_type != GGMS_KHOP_LABOR && !cfg.Temporal() &&
-      !cfg.Typed() && !cfg.Weighted()) {
+      !cfg.Typed() && !cfg.Weighted() && !cfg.Metapath()) {
     extra.rng_wait = last_rng_done_;
     extra.rng_done = P.rng_done;
     last_rng_done_ = P.rng_done;
@@ -2235,6 +2283,12 @@ void Engine::SampleInto(Batch *b, Pipe &P) {
     SAM_GGMS(ggms_sample_batch_labor_weighted(&graph_, s.output_nodes, b->num_seeds, cfg.fanout.data(), L, &ht, s.row.data(),
                                               s.col.data(), b->eid.data(), s.counts_dev, d_edge_weight_, &extra, P.ws,
                                               ws_bytes_, P.stream));
+  } else if (cfg.Metapath()) {
+    // random walk's batch with the edge types and the path; the visit counts land in the batch's data buffers
+    const ggms_typed_t t{d_edge_type_, cfg.num_edge_type, nullptr};
+    SAM_GGMS(ggms_sample_batch_walk_metapath(&graph_, s.output_nodes, b->num_seeds, cfg.fanout.data(), L, &ht, s.row.data(),
+                                             s.col.data(), s.counts_dev, &t, cfg.metapath.data(),
+                                             (uint32_t)cfg.metapath.size(), &extra, P.ws, ws_bytes_, P.stream));
   } else
     SAM_GGMS(ggms_sample_batch(cfg.sample_type, &graph_, s.output_nodes, b->num_seeds, cfg.fanout.data(), L, &ht, states_,
                                num_states_, s.row.data(), s.col.data(), s.counts_dev, &extra, P.ws, ws_bytes_, P.stream));
@@ -2582,7 +2636,7 @@ void Engine::Finish(Batch *b, Batch *prev) {
   if (BatchSampledElsewhere()) { // what the hand-off (arch5: the unpack) moved and its time
     double us_handoff = 0;       // (DoGraphCopy / DoIdCopy, cuda/cuda_loops.cc:629,653)
     SAM_GGMS(ggms_launch_timer_elapsed_us(b->handoff_timer, &us_handoff));
-    const double per_edge = cfg.sample_type == GGMS_RANDOM_WALK ? 12.0 : 8.0; // row + col (+ data)
+    const double per_edge = cfg.Walk() ? 12.0 : 8.0; // row + col (+ data)
     prof.LogStep(b->key, 12 /*kLogL1GraphBytes*/, edges * per_edge);
     prof.LogStep(b->key, 11 /*kLogL1IdBytes*/, (b->num_input + b->num_seeds) * 4.0);
     prof.LogStep(b->key, 22 /*kLogL2GraphCopyTime*/, us_handoff * 1e-6);

@@ -139,6 +139,12 @@ struct RunConfig {
   // on edge_weight.bin (ggms_sample_batch_labor_weighted).  Implies edge_ids like khop_temporal
   bool Weighted() const { return sample_type == GGMS_KHOP_LABOR_WEIGHTED; }
   bool SamplerEmitsEdgeIds() const { return Temporal() || Typed() || Weighted(); } // ggms_edge_positions is not enqueued
+  // extension (`_sample_type` 12 = random_walk_metapath, config key `metapath` = relation ids; arch1, one CSR): random
+  // walk's keys with random_walk_length as the number of traversals of the path (ggms_sample_batch_walk_metapath);
+  // num_edge_type is meta.txt's NUM_EDGE_TYPE.  Walk(): either walk sampler -- visit counts ride with the batch
+  std::vector<uint32_t> metapath;
+  bool Metapath() const { return sample_type == GGMS_RANDOM_WALK_METAPATH; }
+  bool Walk() const { return sample_type == GGMS_RANDOM_WALK || Metapath(); }
   // extension (config keys `induced_subgraph` = on, `induced_max_edges`; arch1, one CSR, not khop2 / khop_temporal, no
   // exclude_seed_edges): every batch also carries the subgraph its input nodes induce -- every edge of the graph with
   // both ends among them, one COO over the batch's local ids with the edges' CSR positions (ggms_induced_edges behind

@@ -33,7 +33,7 @@ void Engine::QueueInit() {
   const auto t0 = std::chrono::steady_clock::now();
   const uint32_t L = (uint32_t)cfg.fanout.size();
   SAM_CHECK(L <= GGMS_QUEUE_MAX_LAYERS, "arch5: at most GGMS_QUEUE_MAX_LAYERS layers");
-  SAM_GGMS(ggms_queue_layout(&qlay_, L, max_edges_.data(), max_unique_, max_seeds_, cfg.sample_type == GGMS_RANDOM_WALK));
+  SAM_GGMS(ggms_queue_layout(&qlay_, L, max_edges_.data(), max_unique_, max_seeds_, cfg.Walk()));
   queue_depth_ = cfg.queue_depth;
   const size_t bytes = 4096 + queue_depth_ * qlay_.slot_bytes;
   void *m = mmap(nullptr, bytes, PROT_READ | PROT_WRITE, MAP_SHARED | MAP_ANONYMOUS, -1, 0);

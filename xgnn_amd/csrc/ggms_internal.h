@@ -100,6 +100,10 @@ struct SampleLayer {
   uint8_t *out_type = nullptr;
   // khop_labor_weighted: per-position weights.  Shares out_pos with khop_temporal
   const float *edge_weight = nullptr;
+  // random_walk_metapath: the relation path (host, 1 .. GGMS_MAX_METAPATH entries < num_type).  Shares edge_type /
+  // num_type with khop_typed, walk_length (the traversals) / num_walk / restart_prob / out_data with random walk, salt
+  const uint32_t *metapath = nullptr;
+  uint32_t metapath_len = 0;
 };
 
 // sample_khop.hip
@@ -116,6 +120,12 @@ int sample_weighted_hash_dedup_impl(const SampleLayer &l);
 size_t random_walk_ws_words(size_t num_input, size_t walk_length, size_t num_walk, size_t K);
 int sample_random_walk_impl(const SampleLayer &l);
 size_t walk_scan_tiles(size_t num_input);
+int walk_topk_impl(const SampleLayer &l, uint32_t *tmp_src, uint32_t *tmp_dst, uint32_t per, uint32_t *w);
+
+// sample_walk_metapath.hip (workspace: random_walk_ws_words)
+int walk_metapath_check(uint32_t num_type, const uint32_t *metapath, uint32_t metapath_len, size_t num_traversal,
+                        double restart_prob, size_t num_walk, size_t K, const char *who); // the refusals of include/ggms.h
+int sample_walk_metapath_impl(const SampleLayer &l);
 
 // sample_labor.hip
 size_t labor_ws_words(size_t num_input);

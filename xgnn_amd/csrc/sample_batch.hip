@@ -75,7 +75,8 @@ size_t layer_ws_words(int type, size_t n, size_t fanout, size_t walk_length, siz
   case GGMS_KHOP1:
   case GGMS_WEIGHTED_KHOP:
   case GGMS_WEIGHTED_KHOP_PREFIX: return weighted_ws_words(n, fanout);
-  case GGMS_RANDOM_WALK: return random_walk_ws_words(n, walk_length, num_walk, fanout);
+  case GGMS_RANDOM_WALK:
+  case GGMS_RANDOM_WALK_METAPATH: return random_walk_ws_words(n, walk_length, num_walk, fanout);
   case GGMS_KHOP_LABOR:
   case GGMS_KHOP_LABOR_WEIGHTED: return labor_ws_words(n);
   case GGMS_KHOP_TEMPORAL: return temporal_ws_words(n);
@@ -98,6 +99,11 @@ static int layer_shape_check(int type, const SampleLayer &l) {
     GGMS_CHECK_ARG(sum == l.fanout);
   }
   if (type == GGMS_RANDOM_WALK) GGMS_CHECK_ARG(l.walk_length > 0 && l.num_walk > 0);
+  if (type == GGMS_RANDOM_WALK_METAPATH) { // the walk's own refusals, with their messages
+    const int rc = walk_metapath_check(l.num_type, l.metapath, l.metapath_len, l.walk_length, l.restart_prob, l.num_walk,
+                                       l.fanout, "random_walk_metapath");
+    if (rc != GGMS_OK) return rc;
+  }
   // "this algorithm not support DistGraph engine", dist_loops.cc:167-228
   if (type != GGMS_KHOP3 && type != GGMS_KHOP0 && type != GGMS_RANDOM_WALK && type != GGMS_KHOP_LABOR)
     GGMS_CHECK_ARG(l.graph->num_part == 0);
@@ -110,8 +116,9 @@ static int layer_check(int type, const SampleLayer &l, size_t num_states) {
   if (rc != GGMS_OK) return rc;
   const uint64_t n = l.n_max;
   if (type == GGMS_KHOP1 || type == GGMS_KHOP2 || type == GGMS_KHOP_TEMPORAL || type == GGMS_KHOP_TYPED ||
-      type == GGMS_KHOP_LABOR_WEIGHTED)
+      type == GGMS_KHOP_LABOR_WEIGHTED || type == GGMS_RANDOM_WALK_METAPATH)
     GGMS_CHECK_ARG(l.graph->indptr && l.graph->indices);
+  if (type == GGMS_RANDOM_WALK_METAPATH) GGMS_CHECK_ARG(l.edge_type && l.out_data);
   if (type == GGMS_KHOP_TYPED) GGMS_CHECK_ARG(l.edge_type && l.out_pos && l.out_type);
   if (type == GGMS_KHOP_TEMPORAL) GGMS_CHECK_ARG(l.edge_time && l.out_pos && (l.input_cut || l.cut_table));
   if (type == GGMS_KHOP_LABOR_WEIGHTED) GGMS_CHECK_ARG(l.edge_weight && l.out_pos);
@@ -123,7 +130,8 @@ static int layer_check(int type, const SampleLayer &l, size_t num_states) {
   case GGMS_KHOP_LABOR:
   case GGMS_KHOP_TEMPORAL:
   case GGMS_KHOP_TYPED:
-  case GGMS_KHOP_LABOR_WEIGHTED: return GGMS_OK; // stateless
+  case GGMS_KHOP_LABOR_WEIGHTED:
+  case GGMS_RANDOM_WALK_METAPATH: return GGMS_OK; // stateless
   case GGMS_KHOP3: GGMS_CHECK_ARG(l.states && (n + 127) / 128 * 8 <= num_states); return GGMS_OK; // khop3.cu:89
   case GGMS_KHOP2:                                                                                   // khop2.cu:57
   case GGMS_WEIGHTED_KHOP_HASH_DEDUP: // hash_dedup.cu:70
@@ -149,6 +157,7 @@ static int sample_layer(int type, const SampleLayer &l) {
   case GGMS_KHOP2: return sample_khop2_impl(l);
   case GGMS_WEIGHTED_KHOP_HASH_DEDUP: return sample_weighted_hash_dedup_impl(l);
   case GGMS_RANDOM_WALK: return sample_random_walk_impl(l);
+  case GGMS_RANDOM_WALK_METAPATH: return sample_walk_metapath_impl(l);
   case GGMS_KHOP_LABOR: return sample_khop_labor_impl(l);
   case GGMS_KHOP_TEMPORAL: return sample_khop_temporal_impl(l);
   case GGMS_KHOP_TYPED: return sample_khop_typed_impl(l);
@@ -180,11 +189,12 @@ int sample_leaf(int type, SampleLayer l, size_t num_states, size_t workspace_byt
     GGMS_HIP(hipMemsetAsync(l.num_out, 0, sizeof(uint64_t), l.s));
     return GGMS_OK;
   }
-  GGMS_CHECK_ARG(l.input && l.out_src && l.out_dst && l.workspace && (type != GGMS_RANDOM_WALK || l.out_data));
+  const bool walk = type == GGMS_RANDOM_WALK || type == GGMS_RANDOM_WALK_METAPATH;
+  GGMS_CHECK_ARG(l.input && l.out_src && l.out_dst && l.workspace && (!walk || l.out_data));
   GGMS_CHECK_ARG(workspace_bytes >=
                  layer_ws_words(type, l.n_max, l.fanout, l.walk_length, l.num_walk, l.num_type) * sizeof(uint32_t));
   // 32-bit output positions; a random walk's are bounded by walk_length * num_walk < 2^31 instead
-  GGMS_CHECK_ARG(type == GGMS_RANDOM_WALK || (uint64_t)l.n_max * l.fanout < (1ull << 32));
+  GGMS_CHECK_ARG(walk || (uint64_t)l.n_max * l.fanout < (1ull << 32));
   rc = layer_check(type, l, num_states);
   if (rc != GGMS_OK) return rc;
   if (!view_of(l.graph, l.g)) return GGMS_ERR_INVALID; // after layer_check's refusal of a sharded graph
@@ -226,7 +236,8 @@ int ggms_sample_batch_capacity(size_t num_seeds, const size_t *fanouts, uint32_t
 static size_t sampler_ws_words(int sample_type, const BatchCaps &c, const size_t *fanouts, uint32_t L,
                                const ggms_sample_extra_t *extra, size_t num_type) {
   size_t w = sample_ws_words(c.max_in_all);
-  if (sample_type == GGMS_RANDOM_WALK && !extra) return w; // no walk: ggms_sample_batch refuses the call
+  const bool walk = sample_type == GGMS_RANDOM_WALK || sample_type == GGMS_RANDOM_WALK_METAPATH;
+  if (walk && !extra) return w; // no walk: ggms_sample_batch refuses the call
   for (uint32_t i = 0; i < L; ++i)
     w = std::max(w, layer_ws_words(sample_type, c.max_input[i], fanouts[i], extra ? extra->random_walk_length : 0,
                                    extra ? extra->num_random_walk : 0, num_type));
@@ -261,7 +272,8 @@ static BatchLayout layout_of(int sample_type, size_t num_seeds, const size_t *fa
   // ONE scan area for the batch: sampler offsets (tiles of 128 seeds), owner scans (tiles of 2048 items), the
   // generic tile scans of the other samplers (<= kSinglePassTiles descriptors, else three launches)
   l.scan_tiles = std::max<size_t>({c.max_in_all / 128 + 2, owner_scan_tiles(l.dedup_items) + 2, kSinglePassTiles + 2});
-  if (sample_type == GGMS_RANDOM_WALK) l.scan_tiles = std::max(l.scan_tiles, walk_scan_tiles(c.max_in_all));
+  if (sample_type == GGMS_RANDOM_WALK || sample_type == GGMS_RANDOM_WALK_METAPATH)
+    l.scan_tiles = std::max(l.scan_tiles, walk_scan_tiles(c.max_in_all));
   if (sample_type == GGMS_KHOP0) l.scan_tiles = std::max<size_t>(l.scan_tiles, 2 * (kSinglePassTiles + 2)); // two sums per pass
   l.scan = w;
   w += up4(std::max(tile_scan_words(std::max(c.max_e_all, c.max_in_all)), 8 + 2 * l.scan_tiles + 4) + 16);
@@ -314,14 +326,21 @@ struct WeightedBatch {
   ggms_id_t *const *eid;
 };
 
-// the body of ggms_sample_batch, ggms_sample_batch_prefetch, ggms_sample_batch_temporal, ggms_sample_batch_typed and
-// ggms_sample_batch_labor_weighted; every argument check is the caller's
+// ggms_sample_batch_walk_metapath's part of a batch (NULL: any other batch)
+struct MetapathBatch {
+  const ggms_typed_t *t;
+  const uint32_t *metapath;
+  uint32_t metapath_len;
+};
+
+// the body of ggms_sample_batch, ggms_sample_batch_prefetch, ggms_sample_batch_temporal, ggms_sample_batch_typed,
+// ggms_sample_batch_labor_weighted and ggms_sample_batch_walk_metapath; every argument check is the caller's
 static int sample_batch_impl(int sample_type, const ggms_graph_t *graph, const ggms_id_t *seeds, size_t num_seeds,
                              const size_t *fanouts, uint32_t num_layer, ggms_hashtable_t *ht, void *states,
                              size_t num_states, ggms_id_t *const *row, ggms_id_t *const *col, uint64_t *counts_dev,
                              const ggms_sample_extra_t *extra, void *workspace, const Prefetch *pf, hipStream_t s,
                              const TemporalBatch *tb = nullptr, const TypedBatch *yb = nullptr,
-                             const WeightedBatch *wb = nullptr) {
+                             const WeightedBatch *wb = nullptr, const MetapathBatch *mb = nullptr) {
   const BatchCaps c = caps_of(num_seeds, fanouts, num_layer);
   // what every layer's sampler call shares; the loop below fills in the rest
   SampleLayer L{graph, nullptr, 0, 0, nullptr, nullptr, nullptr, (uint32_t *)states, nullptr, s};
@@ -334,7 +353,16 @@ static int sample_batch_impl(int sample_type, const ggms_graph_t *graph, const g
   }
   // a stateless sampler has nothing to order between batches
   const bool ordered_rng = sample_type != GGMS_KHOP_LABOR && sample_type != GGMS_KHOP_TEMPORAL &&
-                           sample_type != GGMS_KHOP_TYPED && sample_type != GGMS_KHOP_LABOR_WEIGHTED;
+                           sample_type != GGMS_KHOP_TYPED && sample_type != GGMS_KHOP_LABOR_WEIGHTED &&
+                           sample_type != GGMS_RANDOM_WALK_METAPATH;
+  const bool walk = sample_type == GGMS_RANDOM_WALK || sample_type == GGMS_RANDOM_WALK_METAPATH;
+  if (mb) {
+    L.edge_type = mb->t->edge_type;
+    L.num_type = mb->t->num_type;
+    L.metapath = mb->metapath;
+    L.metapath_len = mb->metapath_len;
+    L.out_data = extra->data[0]; // layer_check's non-null test; every layer sets its own below
+  }
   if (tb) {
     L.edge_time = tb->t->edge_time;
     L.cut_table = tb->t->cut_table;
@@ -510,7 +538,7 @@ static int sample_batch_impl(int sample_type, const ggms_graph_t *graph, const g
       L.insert = inserted ? &di : nullptr;
       L.first = first && fuse_seeds ? &first_layer : nullptr;
       L.enter = first && khop0_enters ? &seed_enter : nullptr;
-      if (sample_type == GGMS_RANDOM_WALK) L.out_data = extra->data[i];
+      if (walk) L.out_data = extra->data[i];
       if (tb) L.out_pos = tb->eid[i];
       if (wb) L.out_pos = wb->eid[i];
       if (yb) {
@@ -588,6 +616,11 @@ int ggms_sample_batch(int sample_type, const ggms_graph_t *graph, const ggms_id_
               "call ggms_sample_batch_labor_weighted", sample_type);
     return GGMS_ERR_INVALID;
   }
+  if (sample_type == GGMS_RANDOM_WALK_METAPATH) {
+    set_error("ggms_sample_batch: sample type %d (random_walk_metapath) takes edge types and a relation path: call "
+              "ggms_sample_batch_walk_metapath", sample_type);
+    return GGMS_ERR_INVALID;
+  }
   GGMS_CHECK_ARG(sample_type >= GGMS_KHOP0 && sample_type <= GGMS_KHOP_LABOR);
   GGMS_CHECK_ARG(num_seeds == 0 || seeds);
   GGMS_CHECK_ARG(workspace && workspace_bytes >= ggms_sample_batch_workspace_bytes(sample_type, num_seeds, fanouts,
@@ -606,7 +639,7 @@ int ggms_sample_batch_seed_ids(int sample_type, size_t num_seeds, const size_t *
                                const ggms_sample_extra_t *extra, const void *workspace, const ggms_id_t **seed_ids_dev) {
   GGMS_CHECK_ARG(fanouts && workspace && seed_ids_dev);
   GGMS_CHECK_ARG(num_layer >= 1 && num_layer <= 16);
-  GGMS_CHECK_ARG(sample_type >= GGMS_KHOP0 && sample_type <= GGMS_KHOP_LABOR_WEIGHTED);
+  GGMS_CHECK_ARG(sample_type >= GGMS_KHOP0 && sample_type <= GGMS_RANDOM_WALK_METAPATH);
   const BatchCaps c = caps_of(num_seeds, fanouts, num_layer);
   const BatchLayout lay = layout_of(sample_type, num_seeds, fanouts, num_layer, c, extra);
   const uint32_t *w = (const uint32_t *)(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
@@ -706,6 +739,53 @@ int ggms_sample_batch_labor_weighted(const ggms_graph_t *graph, const ggms_id_t 
   const WeightedBatch wb{edge_weight, eid};
   return sample_batch_impl(GGMS_KHOP_LABOR_WEIGHTED, graph, seeds, num_seeds, fanouts, num_layer, ht, nullptr, 0, row,
                            col, counts_dev, extra, workspace, nullptr, to_stream(stream), nullptr, nullptr, &wb);
+}
+
+// ---- random_walk_metapath: the batch with edge types and a relation path --------------------------------------------
+size_t ggms_sample_batch_walk_metapath_workspace_bytes(size_t num_seeds, const size_t *fanouts, uint32_t num_layer,
+                                                       const ggms_sample_extra_t *extra) {
+  return ggms_sample_batch_workspace_bytes(GGMS_RANDOM_WALK_METAPATH, num_seeds, fanouts, num_layer, extra);
+}
+
+int ggms_sample_batch_walk_metapath(const ggms_graph_t *graph, const ggms_id_t *seeds, size_t num_seeds,
+                                    const size_t *fanouts, uint32_t num_layer, ggms_hashtable_t *ht, ggms_id_t *const *row,
+                                    ggms_id_t *const *col, uint64_t *counts_dev, const ggms_typed_t *t,
+                                    const uint32_t *metapath, uint32_t metapath_len, const ggms_sample_extra_t *extra,
+                                    void *workspace, size_t workspace_bytes, ggms_stream_t stream) {
+  static const char *const who = "ggms_sample_batch_walk_metapath";
+  GGMS_CHECK_ARG(graph && fanouts && ht && row && col && counts_dev && t);
+  GGMS_CHECK_ARG(num_layer >= 1 && num_layer <= 16);
+  if (graph->num_part != 0) {
+    set_error("%s: num_part %u: edge types are stored by position in ONE CSR, the call takes unsharded graphs only", who,
+              graph->num_part);
+    return GGMS_ERR_INVALID;
+  }
+  if (!t->edge_type) {
+    set_error("%s: edge_type is NULL (one uint8 per position of graph->indices)", who);
+    return GGMS_ERR_INVALID;
+  }
+  if (!extra || !extra->data) {
+    set_error("%s: extra is required: the walk's shape and data, the visit counts of every layer", who);
+    return GGMS_ERR_INVALID;
+  }
+  for (uint32_t i = 0; i < num_layer; ++i) { // fanouts[i] = K of layer i
+    const int rc = walk_metapath_check(t->num_type, metapath, metapath_len, extra->random_walk_length,
+                                       extra->random_walk_restart_prob, extra->num_random_walk, fanouts[i], who);
+    if (rc != GGMS_OK) return rc;
+  }
+  GGMS_CHECK_ARG(num_seeds == 0 || seeds);
+  for (uint32_t i = 0; i < num_layer; ++i) GGMS_CHECK_ARG(row[i] && col[i] && extra->data[i]);
+  if (!workspace || workspace_bytes < ggms_sample_batch_walk_metapath_workspace_bytes(num_seeds, fanouts, num_layer, extra)) {
+    set_error("%s: workspace_bytes %zu, ggms_sample_batch_walk_metapath_workspace_bytes gives %zu", who, workspace_bytes,
+              ggms_sample_batch_walk_metapath_workspace_bytes(num_seeds, fanouts, num_layer, extra));
+    return GGMS_ERR_INVALID;
+  }
+  const BatchCaps c = caps_of(num_seeds, fanouts, num_layer);
+  GGMS_CHECK_ARG(c.max_input[0] + c.max_edges[0] <= ht->n2o_size);
+  GGMS_CHECK_ARG(c.max_input[0] + c.max_edges[0] < (1ull << 32) - 4); // indices and 2 + local id fit 32 bits
+  const MetapathBatch mb{t, metapath, metapath_len};
+  return sample_batch_impl(GGMS_RANDOM_WALK_METAPATH, graph, seeds, num_seeds, fanouts, num_layer, ht, nullptr, 0, row, col,
+                           counts_dev, extra, workspace, nullptr, to_stream(stream), nullptr, nullptr, nullptr, &mb);
 }
 
 // ---- arch4: the prefetching batch ----------------------------------------------------------------------------------

@@ -296,10 +296,8 @@ static int launch_topk_emit(int grid, size_t lds, hipStream_t s, uint32_t *tmp_s
 int sample_random_walk_impl(const SampleLayer &l) {
   const size_t n_max = l.n_max;
   const Count n = l.n;
-  const uint32_t walk_length = (uint32_t)l.walk_length, num_walk = (uint32_t)l.num_walk, K = (uint32_t)l.fanout;
+  const uint32_t walk_length = (uint32_t)l.walk_length, num_walk = (uint32_t)l.num_walk;
   const hipStream_t s = l.s;
-  ScanArea *shared_scan = l.scan;
-  const DedupInsert *insert = l.insert;
   const uint32_t per = walk_length * num_walk;
   uint32_t *w = l.workspace;
   uint32_t *tmp_src = w; w += n_max * per;
@@ -307,6 +305,18 @@ int sample_random_walk_impl(const SampleLayer &l) {
   int rc = random_walk_raw_impl(l.g, l.input, n_max, n, walk_length, l.restart_prob, num_walk, tmp_src, tmp_dst,
                                 l.states, s);
   if (rc != GGMS_OK) return rc;
+  return walk_topk_impl(l, tmp_src, tmp_dst, per, w);
+}
+
+// the top-K of every seed's `per` visits (tmp_src / tmp_dst, visit-major, stride l.n_max) -> the layer's output;
+// w: the workspace words behind the visit scratch
+int walk_topk_impl(const SampleLayer &l, uint32_t *tmp_src, uint32_t *tmp_dst, uint32_t per, uint32_t *w) {
+  const size_t n_max = l.n_max;
+  const Count n = l.n;
+  const uint32_t K = (uint32_t)l.fanout;
+  const hipStream_t s = l.s;
+  ScanArea *shared_scan = l.scan;
+  const DedupInsert *insert = l.insert;
   const uint32_t Kc = K < per ? K : per;
   const uint32_t T = per > kLdsVisits ? 64u : walk_tile(per, Kc);
   const size_t tiles = (n_max + T - 1) / T;

@@ -54,7 +54,10 @@ PICK_UNIFORM, PICK_RECENT = 0, 1  # khop_temporal's picks
 KHOP_TYPED = 10  # an extension: a fanout per edge type on a type-sorted CSR (include/ggms.h)
 MAX_EDGE_TYPES = 32  # GGMS_MAX_EDGE_TYPES
 KHOP_LABOR_WEIGHTED = 11  # an extension: weighted sampling without replacement, khop_labor's sharing (include/ggms.h)
-_STATELESS = (KHOP0, KHOP_LABOR, KHOP_TEMPORAL, KHOP_TYPED, KHOP_LABOR_WEIGHTED)  # samplers without an RNG pool
+RANDOM_WALK_METAPATH = 12  # an extension: PinSAGE's walks along a relation path (include/ggms.h)
+MAX_METAPATH = 8  # GGMS_MAX_METAPATH
+# samplers without an RNG pool
+_STATELESS = (KHOP0, KHOP_LABOR, KHOP_TEMPORAL, KHOP_TYPED, KHOP_LABOR_WEIGHTED, RANDOM_WALK_METAPATH)
 
 
 def _require_gpu(t):
@@ -630,6 +633,29 @@ def sample_random_walk(graph, inp, walk_length, restart_prob, num_walk, K, state
                                         _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), _ptr(num_out), _ptr(states),
                                         states.shape[0], _ptr(ws), ws.numel() * 4, _stream()),
           "ggms_sample_random_walk")
+    return outs[0], outs[1], outs[2], num_out
+
+
+def sample_walk_metapath(graph, edge_type, num_type, metapath, inp, num_traversal, restart_prob, num_walk, K,
+                         layer_salt, num_out=None):
+    """ggms_sample_walk_metapath: per seed, num_walk stateless walks of num_traversal traversals of the relation path
+    `metapath` on a type-sorted CSR, with restart; the K most visited traversal ends per seed.
+    Returns (out_src, out_dst, out_data = visit counts, num_out[1] on device), like sample_random_walk.
+    num_out: the caller's own int64 word for the count (a view of one element)."""
+    _require_gpu(inp)
+    _i32(inp), _u8(edge_type)
+    n, M = inp.numel(), len(metapath)
+    dev = inp.device
+    outs = [torch.empty(max(1, n * K), dtype=torch.int32, device=dev) for _ in range(3)]
+    if num_out is None:
+        num_out = torch.zeros(1, dtype=torch.int64, device=dev)
+    assert num_out.dtype == torch.int64 and num_out.numel() == 1
+    ws = _workspace(lib().ggms_sample_walk_metapath_workspace_bytes(n, num_traversal, num_walk, K), dev)
+    mp = (C.c_uint32 * max(M, 1))(*[int(r) for r in metapath])
+    check(lib().ggms_sample_walk_metapath(C.byref(graph.c), _ptr(edge_type), num_type, mp, M, _ptr(inp), n,
+                                          num_traversal, restart_prob, num_walk, K, layer_salt & 0xFFFFFFFF,
+                                          _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), _ptr(num_out), _ptr(ws),
+                                          ws.numel() * 4, _stream()), "ggms_sample_walk_metapath")
     return outs[0], outs[1], outs[2], num_out
 
 
@@ -1495,6 +1521,53 @@ class TypedBatchSampler(_BatchBuffers):
         for i, lay in enumerate(layers):
             lay["eid"] = self.eid[i][:c[COUNT_EDGES(i)]]
             lay["etype"] = self.etype[i][:c[COUNT_EDGES(i)]]
+        return dict(layers=layers, input_nodes=self.ht.n2o[:c[COUNT_INPUT(self.L)]])
+
+
+class WalkMetapathBatchSampler(_BatchBuffers):
+    """ggms_sample_batch_walk_metapath: BatchSampler's layers with random_walk_metapath as the sampler: every layer
+    walks `metapath` num_traversal times per walk and keeps the K most visited ends.  One slot, one pipeline."""
+
+    def __init__(self, graph, edge_type, num_type, metapath, num_layer, K, num_traversal, restart_prob, num_walk,
+                 batch_size, device="cuda", direct_table=True, max_seeds=None):
+        self._init_capacity(graph, [int(K)] * num_layer, RANDOM_WALK_METAPATH,
+                            int(batch_size * 1.25) + 1 if max_seeds is None else int(max_seeds), None, None)
+        _require_gpu(_u8(edge_type))
+        self.edge_type, self.metapath = edge_type, [int(r) for r in metapath]
+        self._mp = (C.c_uint32 * max(len(self.metapath), 1))(*self.metapath)
+        self._typed = _lib.Typed(edge_type.data_ptr(), num_type, None)
+        self.ht = OrderedHashTable(self.max_unique, device, num_node=graph.c.num_node if direct_table else None)
+        self.states = None
+        (self.row, self._rows), (self.col, self._cols) = self._layer_buffers(1, device), self._layer_buffers(1, device)
+        self.data, self._datas = self._layer_buffers(1, device)
+        self.counts = torch.zeros(COUNTS_SAMPLE_WORDS(self.L), dtype=torch.int64, device=device)
+        self._extra.random_walk_length = num_traversal
+        self._extra.random_walk_restart_prob = restart_prob
+        self._extra.num_random_walk = num_walk
+        self._extra.data = C.cast(self._datas, C.c_void_p)
+        wsb = lib().ggms_sample_batch_walk_metapath_workspace_bytes(self.max_seeds, self._f, self.L,
+                                                                    C.byref(self._extra))
+        self.ws = _workspace(wsb, device)
+
+    def sample(self, seeds, salt=0, distinct=False):
+        """Enqueue one batch; salt: the batch salt (layer i walks under fmix32(salt + 0x9e3779b9 * (i + 1)));
+        distinct: the caller promises pairwise distinct seeds (ggms_sample_extra_t.seeds_distinct)."""
+        _i32(seeds)
+        n = seeds.numel()
+        assert n <= self.max_seeds
+        self._extra.labor_salt = salt & 0xFFFFFFFF
+        self._extra.seeds_distinct = 1 if distinct else 0
+        check(lib().ggms_sample_batch_walk_metapath(C.byref(self.graph.c), _ptr(seeds), n, self._f, self.L,
+                                                    C.byref(self.ht.c), self._rows, self._cols, _ptr(self.counts),
+                                                    C.byref(self._typed), self._mp, len(self.metapath),
+                                                    C.byref(self._extra), _ptr(self.ws), self.ws.numel() * 4,
+                                                    _stream()), "ggms_sample_batch_walk_metapath")
+
+    def result(self):
+        """Sync and slice the outputs: BatchSampler.result()'s, each layer with its visit counts `data`."""
+        c, layers = self._sliced("ggms_sample_batch_walk_metapath")
+        for i, lay in enumerate(layers):
+            lay["data"] = self.data[i][:c[COUNT_EDGES(i)]]
         return dict(layers=layers, input_nodes=self.ht.n2o[:c[COUNT_INPUT(self.L)]])
 
 
