@@ -237,7 +237,8 @@ enum ggms_sample_type {
   GGMS_KHOP_TEMPORAL = 9, /* an extension: ggms_sample_khop_temporal / ggms_sample_batch_temporal below */
   GGMS_KHOP_TYPED = 10, /* an extension: ggms_sample_khop_typed / ggms_sample_batch_typed below */
   GGMS_KHOP_LABOR_WEIGHTED = 11, /* an extension: ggms_sample_khop_labor_weighted / ggms_sample_batch_labor_weighted */
-  GGMS_RANDOM_WALK_METAPATH = 12 /* an extension: ggms_sample_walk_metapath / ggms_sample_batch_walk_metapath below */
+  GGMS_RANDOM_WALK_METAPATH = 12, /* an extension: ggms_sample_walk_metapath / ggms_sample_batch_walk_metapath below */
+  GGMS_KHOP_TYPED_TEMPORAL = 13 /* an extension: ggms_sample_khop_typed_temporal / ggms_sample_batch_typed_temporal */
 };
 
 /* Workspace of every leaf sampler below but random walk, whose size depends on
@@ -343,6 +344,45 @@ int ggms_sample_khop_typed(const ggms_graph_t *graph, const uint8_t *edge_type, 
                            uint32_t layer_salt, ggms_id_t *out_src, ggms_id_t *out_dst, ggms_id_t *out_pos,
                            uint8_t *out_type, uint64_t *num_out_dev, void *workspace, size_t workspace_bytes,
                            ggms_stream_t stream);
+
+/* khop_typed_temporal (an extension; the reference has no such sampler; PyG: LinkNeighborLoader(num_neighbors={edge_type:
+ * [...]}, time_attr=...), DGL: temporal sampling per canonical edge type): khop_typed's fanout per EDGE TYPE among the
+ * edges strictly BEFORE khop_temporal's per-seed cut-off -- interaction logs and temporal knowledge graphs carry a
+ * relation and a time on every edge.
+ *   edge_type   one uint8 per position of graph->indices, every value < num_type = R, 1 <= R <= GGMS_MAX_EDGE_TYPES;
+ *   edge_time   one uint32 per position.  PRECONDITION: inside every node's list the pairs (type, time) are
+ *               non-decreasing lexicographically (a (type, time)-sorted CSR): the types are khop_typed's sorted bytes,
+ *               and inside a type's segment the times are non-decreasing.
+ *   prefixes    seed i is node s = input[i] with cut-off c = input_cut[i]; its list is the d positions
+ *               [indptr[s], indptr[s + 1]).  A_r = the first list position whose type is >= r; Z_r = the first whose
+ *               (type, time) is >= (r, c); e_r = Z_r - A_r.  Under the precondition [A_r, Z_r) are exactly the edges of
+ *               type r with edge_time < c (strict).  c = 0: nothing is eligible.
+ *   fanouts     type_fanout[r] = k_r in 0 .. 127, a HOST array of R; K = their sum >= 1 (khop_typed's).
+ *   GGMS_PICK_UNIFORM  from relation r the min(k_r, e_r) positions p of [A_r, Z_r) with the smallest keys
+ *               (fmix32(t_p ^ layer_salt) << 32) | p; the salt is the same for every type, as in khop_typed.
+ *   GGMS_PICK_RECENT   the last min(k_r, e_r) positions of [A_r, Z_r).
+ *   output      seeds in input order; inside a seed ascending type, inside a type ascending position.  out_src /
+ *               out_dst as khop_labor writes them, out_pos[k] = indptr[s] + p, out_type[k] = r.  All four hold
+ *               num_input * K entries.  Duplicate seeds with different cuts are independent.
+ *   identities  R = 1: the edges are exactly ggms_sample_khop_temporal's with fanout k_0.  Every cut = 0xffffffff (and
+ *               every time below it): exactly ggms_sample_khop_typed's.
+ *   unsorted    a list that violates the precondition: WHICH edges come out is unspecified.  A is made monotone
+ *               (A_r = max(A_r, A_{r-1})) and Z_r is clamped into [A_r, A_{r+1}], A_R = d, before anything is counted:
+ *               nothing is read or written out of bounds, every emitted position lies in the seed's list, the ranges
+ *               of two relations never overlap, no seed emits more than K edges.
+ *   arguments   refused with GGMS_ERR_INVALID before any device call: a sharded graph, R outside
+ *               1 .. GGMS_MAX_EDGE_TYPES, a k_r >= 128, K = 0, a pick other than the two, a null array, a short workspace.
+ * Stateless: a pure function of (graph, edge_type, edge_time, type_fanout, input, input_cut, pick, layer_salt).  No
+ * allocation, no synchronisation, every size stays on the device.  Workspace: a record of 2 R words per seed;
+ * ggms_sample_workspace_bytes(GGMS_KHOP_TYPED_TEMPORAL, num_input, K) is sized for R = GGMS_MAX_EDGE_TYPES,
+ * ggms_sample_khop_typed_temporal_workspace_bytes(num_input, R) is what the call needs for its R (0: R out of range). */
+size_t ggms_sample_khop_typed_temporal_workspace_bytes(size_t num_input, uint32_t num_type);
+int ggms_sample_khop_typed_temporal(const ggms_graph_t *graph, const uint8_t *edge_type, const uint32_t *edge_time,
+                                    uint32_t num_type, const uint32_t *type_fanout /* host, num_type */,
+                                    const ggms_id_t *input, const uint32_t *input_cut, size_t num_input, int pick,
+                                    uint32_t layer_salt, ggms_id_t *out_src, ggms_id_t *out_dst, ggms_id_t *out_pos,
+                                    uint8_t *out_type, uint64_t *num_out_dev, void *workspace, size_t workspace_bytes,
+                                    ggms_stream_t stream);
 
 /* khop_labor_weighted (an extension; the reference has no such sampler; DGL: sample_neighbors(prob=..., replace=False),
  * PyG: a weighted NeighborLoader): fixed-fanout sampling WITHOUT replacement in which an edge's chance grows with its
@@ -741,6 +781,30 @@ int ggms_sample_batch_typed(const ggms_graph_t *graph, const ggms_id_t *seeds, s
                             ggms_id_t *const *eid, uint8_t *const *etype, uint64_t *counts_dev, const ggms_typed_t *t,
                             const ggms_sample_extra_t *extra, void *workspace, size_t workspace_bytes,
                             ggms_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * The typed temporal batch (an extension): the temporal batch above, chain and cut rule unchanged, with
+ * khop_typed_temporal as the sampler and the typed batch's fanout row per layer.
+ *   tt          the temporal batch's ggms_temporal_t: edge times, cut table, stamp, pick.
+ *   ty          the typed batch's ggms_typed_t: edge types, R, type_fanout (HOST, num_layer x num_type); fanouts[i] must
+ *               equal row i's sum (checked).
+ *   layer i     c_f = cut[f] as it stands when the layer starts; ggms_sample_khop_typed_temporal's rule with row i, cut
+ *               c_f and layer_salt = fmix32(labor_salt + 0x9e3779b9 * (i + 1)); every emitted edge (f -> t) lowers cut[t]
+ *               to c_f.  A node reached under several times is sampled before the smallest.
+ *   eid, etype, node_cut   as in the two batches above.  seeds_distinct is ignored: seeds may repeat with different times.
+ *   counts_dev, row, col, both table layouts, the numbering: ggms_sample_batch's.
+ *   ggms_sample_batch_seed_ids(GGMS_KHOP_TYPED_TEMPORAL, ...) gives the raw seeds' local ids.
+ *   ggms_sample_batch(GGMS_KHOP_TYPED_TEMPORAL, ...) is GGMS_ERR_INVALID and names this call.  The argument checks are
+ *   those of both batches above.
+ * ------------------------------------------------------------------------- */
+size_t ggms_sample_batch_typed_temporal_workspace_bytes(size_t num_seeds, const size_t *fanouts, uint32_t num_layer,
+                                                        uint32_t num_type, const ggms_sample_extra_t *extra);
+int ggms_sample_batch_typed_temporal(const ggms_graph_t *graph, const ggms_id_t *seeds, const uint32_t *seed_time,
+                                     size_t num_seeds, const size_t *fanouts, uint32_t num_layer, ggms_hashtable_t *ht,
+                                     ggms_id_t *const *row, ggms_id_t *const *col, ggms_id_t *const *eid,
+                                     uint8_t *const *etype, uint32_t *node_cut, uint64_t *counts_dev,
+                                     const ggms_temporal_t *tt, const ggms_typed_t *ty, const ggms_sample_extra_t *extra,
+                                     void *workspace, size_t workspace_bytes, ggms_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * The metapath walk batch (an extension): ggms_sample_batch's layers with random_walk_metapath as the sampler.

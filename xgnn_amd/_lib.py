@@ -172,6 +172,14 @@ SYMBOLS = {
     "ggms_sample_batch_typed": (_i, [C.POINTER(Graph), _vp, _sz, C.POINTER(_sz), _u32, C.POINTER(HashTable),
                                      C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp,
                                      C.POINTER(Typed), C.POINTER(SampleExtra), _vp, _sz, _vp]),
+    "ggms_sample_khop_typed_temporal_workspace_bytes": (_sz, [_sz, _u32]),
+    "ggms_sample_khop_typed_temporal": (_i, [C.POINTER(Graph), _vp, _vp, _u32, C.POINTER(C.c_uint32), _vp, _vp, _sz, _i,
+                                             C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ggms_sample_batch_typed_temporal_workspace_bytes": (_sz, [_sz, C.POINTER(_sz), _u32, _u32, C.POINTER(SampleExtra)]),
+    "ggms_sample_batch_typed_temporal": (_i, [C.POINTER(Graph), _vp, _vp, _sz, C.POINTER(_sz), _u32, C.POINTER(HashTable),
+                                              C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp, _vp,
+                                              C.POINTER(Temporal), C.POINTER(Typed), C.POINTER(SampleExtra), _vp, _sz,
+                                              _vp]),
     "ggms_sample_khop_labor_weighted": (_i, [C.POINTER(Graph), _vp, _vp, _sz, _sz, C.c_uint32, _vp, _vp, _vp, _vp, _vp,
                                              _sz, _vp]),
     "ggms_sample_batch_labor_weighted_workspace_bytes": (_sz, [_sz, C.POINTER(_sz), _u32, C.POINTER(SampleExtra)]),

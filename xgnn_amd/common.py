@@ -15,6 +15,7 @@ kKHopTemporal = 9  # an extension: sampling strictly before the seed's time (inc
 kKHopTyped = 10  # an extension: a fanout per edge type on a type-sorted CSR (include/ggms.h, GGMS_KHOP_TYPED)
 kKHopLaborWeighted = 11  # an extension: weighted sampling without replacement (include/ggms.h, GGMS_KHOP_LABOR_WEIGHTED)
 kRandomWalkMetapath = 12  # an extension: PinSAGE's walks along a relation path (include/ggms.h, GGMS_RANDOM_WALK_METAPATH)
+kKHopTypedTemporal = 13  # an extension: a fanout per edge type before the seed's time (include/ggms.h, GGMS_KHOP_TYPED_TEMPORAL)
 kArch0, kArch1, kArch2, kArch3, kArch4, kArch5, kArch6, kArch7 = range(8)
 (kCacheByDegree, kCacheByHeuristic, kCacheByPreSample, kCacheByDegreeHop, kCacheByPreSampleStatic,
  kCacheByFakeOptimal, kDynamicCache, kCacheByRandom) = range(8)
@@ -33,6 +34,7 @@ sample_types = {
     'weighted_khop': kWeightedKHop, 'weighted_khop_prefix': kWeightedKHopPrefix,
     'weighted_khop_hash_dedup': kWeightedKHopHashDedup, 'khop_labor': kKHopLabor, 'khop_temporal': kKHopTemporal,
     'khop_typed': kKHopTyped, 'khop_labor_weighted': kKHopLaborWeighted, 'random_walk_metapath': kRandomWalkMetapath,
+    'khop_typed_temporal': kKHopTypedTemporal,
 }
 builtin_archs = {
     'arch0': {'arch': kArch0, 'sampler_ctx': cpu(), 'trainer_ctx': gpu(0)},

@@ -227,7 +227,7 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
     cfg.lookahead = 0;
     cfg.pipelines = 1;
   }
-  SAM_CHECK(cfg.sample_type >= GGMS_KHOP0 && cfg.sample_type <= GGMS_RANDOM_WALK_METAPATH, "unknown sample type");
+  SAM_CHECK(cfg.sample_type >= GGMS_KHOP0 && cfg.sample_type <= GGMS_KHOP_TYPED_TEMPORAL, "unknown sample type");
   if (cfg.Metapath() && cfg.arch != kArch1) {
     static const char *const arch_names[] = {"arch0", "arch1", "arch2", "arch3", "arch4", "arch5", "arch6", "arch7"};
     fatal(__FILE__, __LINE__, std::string(arch_names[cfg.arch]) + ": _sample_type 12 (random_walk_metapath) is not built: "
@@ -251,6 +251,12 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
     static const char *const arch_names[] = {"arch0", "arch1", "arch2", "arch3", "arch4", "arch5", "arch6", "arch7"};
     fatal(__FILE__, __LINE__, std::string(arch_names[cfg.arch]) + ": _sample_type 10 (khop_typed) is not built: the edge "
                               "types and the edge positions run in arch1's sampling chain only");
+  }
+  if (cfg.TypedTemporal() && cfg.arch != kArch1) {
+    static const char *const arch_names[] = {"arch0", "arch1", "arch2", "arch3", "arch4", "arch5", "arch6", "arch7"};
+    fatal(__FILE__, __LINE__, std::string(arch_names[cfg.arch]) + ": _sample_type 13 (khop_typed_temporal) is not built: the "
+                              "edge types, the seed times, the cut table and the edge positions run in arch1's sampling "
+                              "chain only");
   }
   if (cfg.Temporal() && cfg.arch != kArch1) {
     static const char *const arch_names[] = {"arch0", "arch1", "arch2", "arch3", "arch4", "arch5", "arch6", "arch7"};
@@ -334,7 +340,7 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
       cfg.negative_mode = v == "uniform" ? GGMS_NEG_UNIFORM : v == "exclude" ? GGMS_NEG_EXCLUDE
                           : v == "typed_uniform" ? GGMS_NEG_TYPED_UNIFORM : GGMS_NEG_TYPED_EXCLUDE;
     }
-    if (cfg.TypedNegatives() && !(cfg.Typed() && cfg.hetero))
+    if (cfg.TypedNegatives() && !(cfg.Relational() && cfg.hetero))
       fatal(__FILE__, __LINE__, "negative_mode = " + kv["negative_mode"] + " needs sample_type = khop_typed (_sample_type 10) "
                                 "and hetero_batch = on: they load edge_type.bin and node_type.bin, which say what a "
                                 "positive's relation and its destination's type are");
@@ -380,8 +386,8 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
     // enqueued before its gather was
     cfg.extract_streams = 1;
   }
-  if (cfg.Temporal()) { // extension: sampling strictly before the positive edge's time
-    const std::string who = "_sample_type 9 (khop_temporal)";
+  if (cfg.Timed()) { // extension: sampling strictly before the positive edge's time
+    const std::string who = cfg.Temporal() ? "_sample_type 9 (khop_temporal)" : "_sample_type 13 (khop_typed_temporal)";
     if (!cfg.link_prediction)
       fatal(__FILE__, __LINE__, who + " needs task = link_prediction: a seed's time is the time of its positive edge; "
                                 "task = node_classification has no time for a node");
@@ -398,8 +404,14 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
       cfg.temporal_pick = v == "recent" ? GGMS_PICK_RECENT : GGMS_PICK_UNIFORM;
     }
   }
-  if (cfg.Typed()) { // extension: a fanout per edge type
-    const std::string who = "_sample_type 10 (khop_typed)";
+  if (cfg.TypedTemporal()) { // (its other refusals: khop_temporal's above, khop_typed's below)
+    if (cfg.inline_heads == 1)
+      fatal(__FILE__, __LINE__, "_sample_type 13 (khop_typed_temporal) with inline_heads = 1: only khop3 reads the list heads; "
+                                "this sampler reads a relation's prefix of the list");
+    cfg.inline_heads = 0; // auto means off
+  }
+  if (cfg.Relational()) { // extension: a fanout per edge type
+    const std::string who = cfg.Typed() ? "_sample_type 10 (khop_typed)" : "_sample_type 13 (khop_typed_temporal)";
     if (cfg.use_dist_graph)
       fatal(__FILE__, __LINE__, who + " with use_dist_graph: edge types are stored by position in ONE CSR, a sharded "
                                 "topology has none");
@@ -518,9 +530,11 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
     if (cfg.sample_type == GGMS_KHOP2)
       fatal(__FILE__, __LINE__, "induced_subgraph with _sample_type 5 (khop2) is not built: khop2 permutes indices in "
                                 "place, a position names another edge after every batch");
-    if (cfg.Temporal())
-      fatal(__FILE__, __LINE__, "induced_subgraph with _sample_type 9 (khop_temporal) is not built: an induced edge may lie "
-                                "after a node's cut-off, which leaks the future into the batch");
+    if (cfg.Timed())
+      fatal(__FILE__, __LINE__, std::string("induced_subgraph with ") +
+                                    (cfg.Temporal() ? "_sample_type 9 (khop_temporal)" : "_sample_type 13 (khop_typed_temporal)") +
+                                    " is not built: an induced edge may lie after a node's cut-off, which leaks the future "
+                                    "into the batch");
     if (cfg.exclude_seed_edges)
       fatal(__FILE__, __LINE__, "induced_subgraph with exclude_seed_edges = " + kv["exclude_seed_edges"] + " is not built: "
                                 "the filter does not compact an id stream, and the induced subgraph of a link batch holds "
@@ -559,7 +573,7 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
                                   "width; the typed tables are the dataset's own node_feat_<t>.bin");
   }
   if (cfg.hetero) { // (the key itself and the deployment: above, in front of khop_typed's own refusals)
-    if (!cfg.Typed())
+    if (!cfg.Relational())
       fatal(__FILE__, __LINE__, "hetero_batch with _sample_type " + std::to_string(cfg.sample_type) + " is not built: the "
                                 "relation of every sampled edge comes from _sample_type 10 (khop_typed) only");
     if (cfg.use_dist_graph) // (khop_typed refuses it first; kept for the day it does not)
@@ -800,18 +814,20 @@ void Engine::LoadDataset() {
                                     "EDGE_FEAT_DIM x the element size is " + std::to_string(want));
     ds.edge_feat = MapFile("edge_feat.bin", want, false);
   }
-  if (cfg.Temporal()) { // the edge times: NUM_EDGE uint32 in CSR order, sorted inside every list
+  if (cfg.Timed()) { // the edge times: NUM_EDGE uint32 in CSR order, sorted inside every list (khop_typed_temporal: inside
+                     // every (node, type) segment -- checked with the types, below)
+    const std::string who = cfg.Temporal() ? "khop_temporal" : "khop_typed_temporal";
     const std::string name = cfg.dataset_path + "edge_time.bin";
     struct stat st;
     if (stat(name.c_str(), &st) != 0)
-      fatal(__FILE__, __LINE__, "khop_temporal: " + name + " is missing (NUM_EDGE uint32 times, one per position of "
+      fatal(__FILE__, __LINE__, who + ": " + name + " is missing (NUM_EDGE uint32 times, one per position of "
                                     "indices.bin; datagen.write_dataset(edge_time=...))");
     if ((size_t)st.st_size != ds.num_edge * 4)
-      fatal(__FILE__, __LINE__, "khop_temporal: edge_time.bin has " + std::to_string((size_t)st.st_size) + " bytes, NUM_EDGE x 4 is " +
+      fatal(__FILE__, __LINE__, who + ": edge_time.bin has " + std::to_string((size_t)st.st_size) + " bytes, NUM_EDGE x 4 is " +
                                     std::to_string(ds.num_edge * 4));
     ds.edge_time = MapFile("edge_time.bin", ds.num_edge * 4, false);
     const uint32_t *ip = (const uint32_t *)ds.indptr.ptr, *t = (const uint32_t *)ds.edge_time.ptr;
-    for (size_t v = 0; v < ds.num_node; ++v)
+    for (size_t v = 0; cfg.Temporal() && v < ds.num_node; ++v)
       for (size_t p = (size_t)ip[v] + 1; p < ip[v + 1]; ++p)
         if (t[p] < t[p - 1])
           fatal(__FILE__, __LINE__, "khop_temporal: edge_time.bin: the times of node " + std::to_string(v) + "'s list are not "
@@ -866,14 +882,14 @@ void Engine::LoadDataset() {
     }
     if (cfg.typed_feat) LoadTypedFeat(meta, meta_text);
   }
-  if (cfg.Typed() || cfg.Metapath()) { // the edge types: NUM_EDGE uint8 in CSR order, sorted inside every list, below NUM_EDGE_TYPE
-    const std::string who = cfg.Typed() ? "khop_typed" : "random_walk_metapath";
+  if (cfg.Relational() || cfg.Metapath()) { // the edge types: NUM_EDGE uint8 in CSR order, sorted inside every list, below NUM_EDGE_TYPE
+    const std::string who = cfg.Typed() ? "khop_typed" : cfg.TypedTemporal() ? "khop_typed_temporal" : "random_walk_metapath";
     if (!meta.count("NUM_EDGE_TYPE"))
       fatal(__FILE__, __LINE__, who + ": meta.txt lacks NUM_EDGE_TYPE (datagen.write_dataset(edge_type=, num_edge_type=))");
     const size_t R = meta["NUM_EDGE_TYPE"];
     if (R < 1 || R > GGMS_MAX_EDGE_TYPES)
       fatal(__FILE__, __LINE__, who + ": NUM_EDGE_TYPE = " + std::to_string(R) + ": 1 .. " + std::to_string(GGMS_MAX_EDGE_TYPES));
-    if (cfg.Typed() && R != cfg.num_edge_type)
+    if (cfg.Relational() && R != cfg.num_edge_type)
       fatal(__FILE__, __LINE__, "type_fanout has " + std::to_string(cfg.type_fanout.size()) + " values, num_layer x "
                                     "NUM_EDGE_TYPE is " + std::to_string(cfg.fanout.size()) + " x " + std::to_string(R));
     if (cfg.Metapath()) {
@@ -898,6 +914,8 @@ void Engine::LoadDataset() {
     // edge's destination, the entry its source -- and fails on the first edge that disagrees with its relation's others
     const uint8_t *nt = cfg.hetero ? (const uint8_t *)ds.node_type.ptr : nullptr;
     const uint32_t *ix = (const uint32_t *)ds.indices.ptr;
+    // khop_typed_temporal: the same pass checks the times inside every (node, type) segment
+    const uint32_t *tm = cfg.TypedTemporal() ? (const uint32_t *)ds.edge_time.ptr : nullptr;
     if (cfg.hetero) {
       ds.rel_src_type.assign(R, 255);
       ds.rel_dst_type.assign(R, 255);
@@ -923,6 +941,11 @@ void Engine::LoadDataset() {
           fatal(__FILE__, __LINE__, who + ": edge_type.bin: the types of node " + std::to_string(v) + "'s list are not "
                                         "non-decreasing (position " + std::to_string(p) + "); datagen.sort_lists_by_type "
                                         "re-sorts a graph");
+        if (tm && p > ip[v] && t[p] == t[p - 1] && tm[p] < tm[p - 1])
+          fatal(__FILE__, __LINE__, who + ": edge_time.bin: the times of node " + std::to_string(v) + "'s list are not "
+                                        "non-decreasing inside the segment of type " + std::to_string((unsigned)t[p]) +
+                                        " (position " + std::to_string(p) + "); datagen.sort_lists_by_type_time re-sorts a "
+                                        "graph");
         if (t[p] >= R)
           fatal(__FILE__, __LINE__, who + ": edge_type.bin: node " + std::to_string(v) + "'s list holds the type " +
                                         std::to_string((unsigned)t[p]) + " (position " + std::to_string(p) +
@@ -1507,7 +1530,7 @@ void Engine::SampleInit(int worker_id, const std::string &ctx) {
   extra_.random_walk_restart_prob = cfg.random_walk_restart_prob;
   extra_.num_random_walk = cfg.num_random_walk;
   // GPURandomStates dist_engine.cc:432-433; seed = wall clock unless the "seed" key is given
-  if (cfg.sample_type == GGMS_KHOP_LABOR || cfg.Temporal() || cfg.Typed() || cfg.Weighted() || cfg.Metapath()) { // stateless: their variates are hashes of (node id, salt) -- no RNG pool
+  if (cfg.sample_type == GGMS_KHOP_LABOR || cfg.Timed() || cfg.Typed() || cfg.Weighted() || cfg.Metapath()) { // stateless: their variates are hashes of (node id, salt) -- no RNG pool
     num_states_ = 0;
     states_ = nullptr;
   } else {
@@ -1528,6 +1551,8 @@ void Engine::SampleInit(int worker_id, const std::string &ctx) {
                                  : ggms_sample_batch_workspace_bytes(cfg.sample_type, max_seeds_, cfg.fanout.data(), L, &extra_);
   if (cfg.Typed()) // the boundary words follow NUM_EDGE_TYPE, which the generic function sizes at its maximum
     ws_bytes_ = ggms_sample_batch_typed_workspace_bytes(max_seeds_, cfg.fanout.data(), L, cfg.num_edge_type, &extra_);
+  if (cfg.TypedTemporal()) // likewise its records
+    ws_bytes_ = ggms_sample_batch_typed_temporal_workspace_bytes(max_seeds_, cfg.fanout.data(), L, cfg.num_edge_type, &extra_);
   SAM_HIP(hipMalloc(&ws_, ws_bytes_));
   // pipeline 0 = {stream_, ht_, ws_}; the others get their own stream, table and workspace
   pipes_.assign(cfg.pipelines, Pipe{});
@@ -1553,13 +1578,13 @@ void Engine::SampleInit(int worker_id, const std::string &ctx) {
     SAM_CHECK(drop_ws_bytes_ > 0, "exclude_seed_edges: the batch bounds are out of ggms_drop_pair_edges' range");
     for (Pipe &P : pipes_) SAM_HIP(hipMalloc(&P.drop_ws, drop_ws_bytes_));
   }
-  if (cfg.Temporal()) { // one cut table per pipeline: 8 B x num_node, zeroed once; stamps 1, 2, 3, ... per batch
+  if (cfg.Timed()) { // one cut table per pipeline: 8 B x num_node, zeroed once; stamps 1, 2, 3, ... per batch
     for (Pipe &P : pipes_) {
       SAM_HIP(hipMalloc((void **)&P.cut_table, std::max<size_t>(ds.num_node, 1) * 8));
       SAM_HIP(hipMemsetAsync(P.cut_table, 0, std::max<size_t>(ds.num_node, 1) * 8, stream_));
     }
   }
-  if (cfg.Typed() || cfg.Metapath()) { // the edge types in HBM, beside the topology the sampler reads
+  if (cfg.Relational() || cfg.Metapath()) { // the edge types in HBM, beside the topology the sampler reads
     SAM_HIP(hipMalloc((void **)&d_edge_type_, std::max<size_t>(ds.num_edge, 16)));
     SAM_HIP(hipMemcpyAsync(d_edge_type_, ds.edge_type.ptr, ds.num_edge, hipMemcpyHostToDevice, stream_));
     SAM_HIP(hipStreamSynchronize(stream_));
@@ -1830,7 +1855,7 @@ void Engine::BuildCache() {
         feat_src_ = d_feat_;
       }
       if (cfg.edge_feat) d_edge_feat_ = dev_upload(ds.edge_feat.ptr, ds.edge_feat.bytes, bs); // the edge table, beside it
-      if (cfg.Temporal()) d_edge_time_ = (uint32_t *)dev_upload(ds.edge_time.ptr, ds.edge_time.bytes, bs); // and the times
+      if (cfg.Timed()) d_edge_time_ = (uint32_t *)dev_upload(ds.edge_time.ptr, ds.edge_time.bytes, bs); // and the times
       if (cfg.feat_learnable >= 0) { // the upload is the learnable table's initial value; Adagrad's accumulator starts at 0
         if (cfg.feat_learnable == GGMS_UPDATE_ADAGRAD) {
           SAM_HIP(hipMalloc(&d_feat_state_, std::max<size_t>(ds.feat.bytes, 16)));
@@ -2058,13 +2083,13 @@ void Engine::TrainInit(int worker_id, const std::string &ctx) {
       SAM_HIP(hipHostMalloc((void **)&b->het_words, HetWords() * 4));
       std::memset(b->het_words, 0, HetWords() * 4);
     }
-    if (cfg.Temporal()) {
+    if (cfg.Timed()) {
       SAM_HIP(hipMalloc((void **)&b->seed_time, std::max<size_t>(max_seeds_, 4) * 4));
       SAM_HIP(hipMalloc((void **)&b->node_cut, std::max<size_t>(max_unique_, 4) * 4));
       b->etime.assign(L, nullptr);
       for (uint32_t i = 0; i < L; ++i) SAM_HIP(hipMalloc((void **)&b->etime[i], std::max<size_t>(max_edges_[i], 4) * 4));
     }
-    if (cfg.Typed()) {
+    if (cfg.Relational()) {
       b->etype.assign(L, nullptr);
       for (uint32_t i = 0; i < L; ++i) SAM_HIP(hipMalloc((void **)&b->etype[i], std::max<size_t>(max_edges_[i], 16)));
     }
@@ -2241,11 +2266,11 @@ void Engine::SampleInto(Batch *b, Pipe &P) {
                                forced, P.stream));
     extra.seeds_distinct = 0;
     // khop_temporal: every entry of the seed list is sampled before the time of its positive edge
-    if (cfg.Temporal())
+    if (cfg.Timed())
       SAM_GGMS(ggms_link_seed_times(d_edge_time_, ds.num_edge, b->edge_ids, b->num_pos, cfg.num_negative, b->seed_time,
                                     P.stream));
   }
-  if (pipes_.size() > 1 && cfg.sample_type != GGMS_KHOP0 && cfg.sample_type != GGMS_KHOP_LABOR && !cfg.Temporal() &&
+  if (pipes_.size() > 1 && cfg.sample_type != GGMS_KHOP0 && cfg.sample_type != GGMS_KHOP_LABOR && !cfg.Timed() &&
       !cfg.Typed() && !cfg.Weighted() && !cfg.Metapath()) {
     extra.rng_wait = last_rng_done_;
     extra.rng_done = P.rng_done;
@@ -2261,7 +2286,7 @@ void Engine::SampleInto(Batch *b, Pipe &P) {
                                         states_, num_states_, s.row.data(), s.col.data(), s.counts_dev, &extra,
                                         max_prefetch_edges_, (ggms_event_t)b->ev_expand, (ggms_event_t)b->ev_final, P.ws,
                                         ws_bytes_, P.stream));
-  else if (cfg.Temporal()) {
+  else if (cfg.Timed()) {
     // the pipeline's own cut table and stamp counter; a wrapped stamp zeroes the table on the pipeline's stream, in
     // front of the batch that starts again from 1.  The sampler fills the batch's eid buffers itself.
     if (P.stamp == 0xffffffffu) {
@@ -2269,6 +2294,12 @@ void Engine::SampleInto(Batch *b, Pipe &P) {
       P.stamp = 0;
     }
     const ggms_temporal_t t{d_edge_time_, P.cut_table, ++P.stamp, (uint32_t)cfg.temporal_pick};
+    if (cfg.TypedTemporal()) { // ... and the etype buffers, under the fanout rows
+      const ggms_typed_t y{d_edge_type_, cfg.num_edge_type, cfg.type_fanout.data()};
+      SAM_GGMS(ggms_sample_batch_typed_temporal(&graph_, s.output_nodes, b->seed_time, b->num_seeds, cfg.fanout.data(), L, &ht,
+                                                s.row.data(), s.col.data(), b->eid.data(), b->etype.data(), b->node_cut,
+                                                s.counts_dev, &t, &y, &extra, P.ws, ws_bytes_, P.stream));
+    } else
     SAM_GGMS(ggms_sample_batch_temporal(&graph_, s.output_nodes, b->seed_time, b->num_seeds, cfg.fanout.data(), L, &ht,
                                         s.row.data(), s.col.data(), b->eid.data(), b->node_cut, s.counts_dev, &t, &extra, P.ws,
                                         ws_bytes_, P.stream));
@@ -2409,7 +2440,7 @@ void Engine::EnqueueGather(Batch *b, hipStream_t ss) {
     SAM_GGMS(ggms_gather_scatter(b->ind_efeat, d_edge_feat_, b->ind_eid, nullptr, induced_max_edges_, b->ind_counts_dev + 2,
                                  ds.edge_feat_dim, ds.edge_feat_dtype, xs));
   // khop_temporal: the sampled edges' times, edge_time[eid], beside the edge rows (dim 1, the device edge count)
-  if (cfg.Temporal())
+  if (cfg.Timed())
     for (uint32_t i = 0; i < L; ++i)
       SAM_GGMS(ggms_gather_scatter(b->etime[i], d_edge_time_, b->eid[i], nullptr, max_edges_[i],
                                    b->trainer.counts_dev + GGMS_COUNT_EDGES(i), 1, GGMS_I32, xs));

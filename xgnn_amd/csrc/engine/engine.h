@@ -138,7 +138,13 @@ struct RunConfig {
   // extension (_sample_type 11, khop_labor_weighted; arch1, one CSR, both tasks): weighted sampling without replacement
   // on edge_weight.bin (ggms_sample_batch_labor_weighted).  Implies edge_ids like khop_temporal
   bool Weighted() const { return sample_type == GGMS_KHOP_LABOR_WEIGHTED; }
-  bool SamplerEmitsEdgeIds() const { return Temporal() || Typed() || Weighted(); } // ggms_edge_positions is not enqueued
+  // extension (`_sample_type` 13 = khop_typed_temporal; arch1, link_prediction, one CSR): khop_typed's fanout per edge type
+  // before khop_temporal's cut (ggms_sample_batch_typed_temporal) -- both samplers' keys, files, tables and hand-outs.
+  // Timed(): the batch has seed times, a cut table and edge times; Relational(): it has edge types and type fanouts
+  bool TypedTemporal() const { return sample_type == GGMS_KHOP_TYPED_TEMPORAL; }
+  bool Timed() const { return Temporal() || TypedTemporal(); }
+  bool Relational() const { return Typed() || TypedTemporal(); }
+  bool SamplerEmitsEdgeIds() const { return Timed() || Typed() || Weighted(); } // ggms_edge_positions is not enqueued
   // extension (`_sample_type` 12 = random_walk_metapath, config key `metapath` = relation ids; arch1, one CSR): random
   // walk's keys with random_walk_length as the number of traversals of the path (ggms_sample_batch_walk_metapath);
   // num_edge_type is meta.txt's NUM_EDGE_TYPE.  Walk(): either walk sampler -- visit counts ride with the batch

@@ -218,11 +218,11 @@ void samgraph_get_graph_link_rel(uint64_t key, samgraph_tensor_t *out) {
   auto *b = E.Current(key);
   fill(out, b->link_rel, (int64_t)b->num_pos, 1, 1, GGMS_U8, E.batch_device_type(), E.trainer_device());
 }
-// _sample_type 9 (khop_temporal): the time of every edge of layer l (edge_time[edge_ids]), the final cut-off of every input
+// _sample_type 9 (khop_temporal) and 13 (khop_typed_temporal): the time of every edge of layer l (edge_time[edge_ids]), the final cut-off of every input
 // node, the times of the batch's positive edges -- uint32 bits in get_graph_row's dtype
 static sam::Batch *temporal_batch(uint64_t key, const char *who) {
   auto &E = Engine::Get();
-  if (!E.cfg.Temporal()) sam::fatal(__FILE__, __LINE__, std::string(who) + " needs _sample_type 9 (khop_temporal)");
+  if (!E.cfg.Timed()) sam::fatal(__FILE__, __LINE__, std::string(who) + " needs _sample_type 9 (khop_temporal)");
   return E.Current(key);
 }
 void samgraph_get_graph_edge_time(uint64_t key, int l, samgraph_tensor_t *out) {
@@ -242,10 +242,10 @@ void samgraph_get_graph_link_time(uint64_t key, samgraph_tensor_t *out) {
   auto *b = temporal_batch(key, "samgraph_get_graph_link_time");
   fill(out, b->seed_time, (int64_t)b->num_pos, 1, 1, GGMS_I32, E.batch_device_type(), E.trainer_device());
 }
-// _sample_type 10 (khop_typed): the type of every edge of layer l, edge_type[edge_ids], as the sampler wrote it -- uint8
+// _sample_type 10 (khop_typed) and 13 (khop_typed_temporal): the type of every edge of layer l, edge_type[edge_ids], as the sampler wrote it -- uint8
 void samgraph_get_graph_edge_type(uint64_t key, int l, samgraph_tensor_t *out) {
   auto &E = Engine::Get();
-  if (!E.cfg.Typed()) sam::fatal(__FILE__, __LINE__, "samgraph_get_graph_edge_type needs _sample_type 10 (khop_typed)");
+  if (!E.cfg.Relational()) sam::fatal(__FILE__, __LINE__, "samgraph_get_graph_edge_type needs _sample_type 10 (khop_typed)");
   auto *b = E.Current(key);
   SAM_CHECK(l >= 0 && (size_t)l < b->etype.size(), "samgraph_get_graph_edge_type: no such layer");
   fill(out, b->etype[l], (int64_t)b->counts[GGMS_COUNT_EDGES(l)], 1, 1, GGMS_U8, E.batch_device_type(), E.trainer_device());

@@ -147,6 +147,10 @@ size_t typed_ws_words(size_t num_input, size_t num_type); // num_type 0: sized f
 int typed_fanout_sum(const uint32_t *type_fanout, uint32_t num_type, size_t *sum); // refuses R, a null row, a k_r >= 128
 int sample_khop_typed_impl(const SampleLayer &l);
 
+// sample_typed_temporal.hip: khop_typed's and khop_temporal's fields of SampleLayer together
+size_t typed_temporal_ws_words(size_t num_input, size_t num_type); // num_type 0: sized for GGMS_MAX_EDGE_TYPES
+int sample_khop_typed_temporal_impl(const SampleLayer &l);
+
 // sample_batch.hip: the per-sampler rules, one copy for the leaf entry points and ggms_sample_batch
 size_t layer_ws_words(int type, size_t n, size_t fanout, size_t walk_length, size_t num_walk, size_t num_type = 0);
 int sample_leaf(int type, SampleLayer l, size_t num_states, size_t workspace_bytes); // a leaf entry point's body

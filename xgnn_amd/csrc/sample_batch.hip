@@ -71,6 +71,7 @@ static BatchCaps caps_of(size_t num_seeds, const size_t *fanouts, uint32_t L) {
 size_t layer_ws_words(int type, size_t n, size_t fanout, size_t walk_length, size_t num_walk, size_t num_type) {
   switch (type) {
   case GGMS_KHOP_TYPED: return typed_ws_words(n, num_type);
+  case GGMS_KHOP_TYPED_TEMPORAL: return typed_temporal_ws_words(n, num_type);
   case GGMS_KHOP0: return khop0_ws_words(n, fanout);
   case GGMS_KHOP1:
   case GGMS_WEIGHTED_KHOP:
@@ -92,7 +93,8 @@ static int layer_shape_check(int type, const SampleLayer &l) {
   if (type == GGMS_KHOP_LABOR) GGMS_CHECK_ARG(l.fanout < 128); // the hub route ranks its selection in LDS
   if (type == GGMS_KHOP_TEMPORAL) GGMS_CHECK_ARG(l.fanout < 128); // khop_labor's selection on a prefix
   if (type == GGMS_KHOP_LABOR_WEIGHTED) GGMS_CHECK_ARG(l.fanout < 128); // khop_labor's selection over another key
-  if (type == GGMS_KHOP_TYPED) { // khop_labor's selection per segment: every k_r < 128; `fanout` is the row's sum
+  // khop_labor's selection per segment (khop_typed_temporal: per prefix): every k_r < 128; `fanout` is the row's sum
+  if (type == GGMS_KHOP_TYPED || type == GGMS_KHOP_TYPED_TEMPORAL) {
     size_t sum = 0;
     const int rc = typed_fanout_sum(l.type_fanout, l.num_type, &sum);
     if (rc != GGMS_OK) return rc;
@@ -116,11 +118,12 @@ static int layer_check(int type, const SampleLayer &l, size_t num_states) {
   if (rc != GGMS_OK) return rc;
   const uint64_t n = l.n_max;
   if (type == GGMS_KHOP1 || type == GGMS_KHOP2 || type == GGMS_KHOP_TEMPORAL || type == GGMS_KHOP_TYPED ||
-      type == GGMS_KHOP_LABOR_WEIGHTED || type == GGMS_RANDOM_WALK_METAPATH)
+      type == GGMS_KHOP_LABOR_WEIGHTED || type == GGMS_RANDOM_WALK_METAPATH || type == GGMS_KHOP_TYPED_TEMPORAL)
     GGMS_CHECK_ARG(l.graph->indptr && l.graph->indices);
   if (type == GGMS_RANDOM_WALK_METAPATH) GGMS_CHECK_ARG(l.edge_type && l.out_data);
-  if (type == GGMS_KHOP_TYPED) GGMS_CHECK_ARG(l.edge_type && l.out_pos && l.out_type);
-  if (type == GGMS_KHOP_TEMPORAL) GGMS_CHECK_ARG(l.edge_time && l.out_pos && (l.input_cut || l.cut_table));
+  if (type == GGMS_KHOP_TYPED || type == GGMS_KHOP_TYPED_TEMPORAL) GGMS_CHECK_ARG(l.edge_type && l.out_pos && l.out_type);
+  if (type == GGMS_KHOP_TEMPORAL || type == GGMS_KHOP_TYPED_TEMPORAL)
+    GGMS_CHECK_ARG(l.edge_time && l.out_pos && (l.input_cut || l.cut_table));
   if (type == GGMS_KHOP_LABOR_WEIGHTED) GGMS_CHECK_ARG(l.edge_weight && l.out_pos);
   if (type == GGMS_WEIGHTED_KHOP || type == GGMS_WEIGHTED_KHOP_HASH_DEDUP) GGMS_CHECK_ARG(l.prob && l.alias);
   if (type == GGMS_WEIGHTED_KHOP_PREFIX) GGMS_CHECK_ARG(l.prob);
@@ -130,6 +133,7 @@ static int layer_check(int type, const SampleLayer &l, size_t num_states) {
   case GGMS_KHOP_LABOR:
   case GGMS_KHOP_TEMPORAL:
   case GGMS_KHOP_TYPED:
+  case GGMS_KHOP_TYPED_TEMPORAL:
   case GGMS_KHOP_LABOR_WEIGHTED:
   case GGMS_RANDOM_WALK_METAPATH: return GGMS_OK; // stateless
   case GGMS_KHOP3: GGMS_CHECK_ARG(l.states && (n + 127) / 128 * 8 <= num_states); return GGMS_OK; // khop3.cu:89
@@ -161,6 +165,7 @@ static int sample_layer(int type, const SampleLayer &l) {
   case GGMS_KHOP_LABOR: return sample_khop_labor_impl(l);
   case GGMS_KHOP_TEMPORAL: return sample_khop_temporal_impl(l);
   case GGMS_KHOP_TYPED: return sample_khop_typed_impl(l);
+  case GGMS_KHOP_TYPED_TEMPORAL: return sample_khop_typed_temporal_impl(l);
   case GGMS_KHOP_LABOR_WEIGHTED: return sample_khop_labor_weighted_impl(l);
   default: return sample_weighted_impl(l, type); // khop1, weighted_khop, weighted_khop_prefix
   }
@@ -173,10 +178,10 @@ static int sample_layer(int type, const SampleLayer &l) {
 // separate insert launch of ht_fill_impl follows).  khop_labor does not either: its selection writes each edge from
 // the lane that held the key, after a search that is all ballots -- a returning atomic per edge there would serialise
 // behind the search of the seed's whole wave, and the sampler stays a pure function of its inputs.
-// khop_temporal, khop_typed and khop_labor_weighted are khop_labor's selection: the same holds.
+// khop_temporal, khop_typed, khop_typed_temporal and khop_labor_weighted are khop_labor's selection: the same holds.
 static bool layer_enters_output(int type) {
   return type != GGMS_KHOP2 && type != GGMS_KHOP_LABOR && type != GGMS_KHOP_TEMPORAL && type != GGMS_KHOP_TYPED &&
-         type != GGMS_KHOP_LABOR_WEIGHTED;
+         type != GGMS_KHOP_LABOR_WEIGHTED && type != GGMS_KHOP_TYPED_TEMPORAL;
 }
 
 // a leaf entry point: shape checks; nothing to sample -> a zero count (null pointers allowed); pointers, workspace and
@@ -254,7 +259,7 @@ struct BatchLayout {
 static inline size_t up4(size_t w) { return (w + 3) & ~(size_t)3; }
 
 // pf_edges: the prefetching batch's expansion capacity (its keys are one more fill of the batch); 0 = none
-// num_type: khop_typed's R (its boundary words); 0 = sized for GGMS_MAX_EDGE_TYPES.  seed_local is the first piece
+// num_type: khop_typed's / khop_typed_temporal's R (their boundary words); 0 = sized for GGMS_MAX_EDGE_TYPES.  seed_local is the first piece
 // whatever it is
 static BatchLayout layout_of(int sample_type, size_t num_seeds, const size_t *fanouts, uint32_t L, const BatchCaps &c,
                              const ggms_sample_extra_t *extra, size_t pf_edges = 0, size_t num_type = 0) {
@@ -334,7 +339,8 @@ struct MetapathBatch {
 };
 
 // the body of ggms_sample_batch, ggms_sample_batch_prefetch, ggms_sample_batch_temporal, ggms_sample_batch_typed,
-// ggms_sample_batch_labor_weighted and ggms_sample_batch_walk_metapath; every argument check is the caller's
+// ggms_sample_batch_labor_weighted, ggms_sample_batch_walk_metapath and ggms_sample_batch_typed_temporal (tb and yb
+// together); every argument check is the caller's
 static int sample_batch_impl(int sample_type, const ggms_graph_t *graph, const ggms_id_t *seeds, size_t num_seeds,
                              const size_t *fanouts, uint32_t num_layer, ggms_hashtable_t *ht, void *states,
                              size_t num_states, ggms_id_t *const *row, ggms_id_t *const *col, uint64_t *counts_dev,
@@ -354,7 +360,7 @@ static int sample_batch_impl(int sample_type, const ggms_graph_t *graph, const g
   // a stateless sampler has nothing to order between batches
   const bool ordered_rng = sample_type != GGMS_KHOP_LABOR && sample_type != GGMS_KHOP_TEMPORAL &&
                            sample_type != GGMS_KHOP_TYPED && sample_type != GGMS_KHOP_LABOR_WEIGHTED &&
-                           sample_type != GGMS_RANDOM_WALK_METAPATH;
+                           sample_type != GGMS_RANDOM_WALK_METAPATH && sample_type != GGMS_KHOP_TYPED_TEMPORAL;
   const bool walk = sample_type == GGMS_RANDOM_WALK || sample_type == GGMS_RANDOM_WALK_METAPATH;
   if (mb) {
     L.edge_type = mb->t->edge_type;
@@ -621,6 +627,11 @@ int ggms_sample_batch(int sample_type, const ggms_graph_t *graph, const ggms_id_
               "ggms_sample_batch_walk_metapath", sample_type);
     return GGMS_ERR_INVALID;
   }
+  if (sample_type == GGMS_KHOP_TYPED_TEMPORAL) {
+    set_error("ggms_sample_batch: sample type %d (khop_typed_temporal) takes edge types, edge times, seed times, a cut "
+              "table and a fanout per type and layer: call ggms_sample_batch_typed_temporal", sample_type);
+    return GGMS_ERR_INVALID;
+  }
   GGMS_CHECK_ARG(sample_type >= GGMS_KHOP0 && sample_type <= GGMS_KHOP_LABOR);
   GGMS_CHECK_ARG(num_seeds == 0 || seeds);
   GGMS_CHECK_ARG(workspace && workspace_bytes >= ggms_sample_batch_workspace_bytes(sample_type, num_seeds, fanouts,
@@ -639,7 +650,7 @@ int ggms_sample_batch_seed_ids(int sample_type, size_t num_seeds, const size_t *
                                const ggms_sample_extra_t *extra, const void *workspace, const ggms_id_t **seed_ids_dev) {
   GGMS_CHECK_ARG(fanouts && workspace && seed_ids_dev);
   GGMS_CHECK_ARG(num_layer >= 1 && num_layer <= 16);
-  GGMS_CHECK_ARG(sample_type >= GGMS_KHOP0 && sample_type <= GGMS_RANDOM_WALK_METAPATH);
+  GGMS_CHECK_ARG(sample_type >= GGMS_KHOP0 && sample_type <= GGMS_KHOP_TYPED_TEMPORAL);
   const BatchCaps c = caps_of(num_seeds, fanouts, num_layer);
   const BatchLayout lay = layout_of(sample_type, num_seeds, fanouts, num_layer, c, extra);
   const uint32_t *w = (const uint32_t *)(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
@@ -713,6 +724,51 @@ int ggms_sample_batch_typed(const ggms_graph_t *graph, const ggms_id_t *seeds, s
   const TypedBatch yb{t, eid, etype};
   return sample_batch_impl(GGMS_KHOP_TYPED, graph, seeds, num_seeds, fanouts, num_layer, ht, nullptr, 0, row, col,
                            counts_dev, extra, workspace, nullptr, to_stream(stream), nullptr, &yb);
+}
+
+// ---- khop_typed_temporal: khop_temporal's chain with a fanout row per layer -----------------------------------------
+size_t ggms_sample_batch_typed_temporal_workspace_bytes(size_t num_seeds, const size_t *fanouts, uint32_t num_layer,
+                                                        uint32_t num_type, const ggms_sample_extra_t *extra) {
+  if (!fanouts || num_layer < 1 || num_layer > 16 || num_type < 1 || num_type > GGMS_MAX_EDGE_TYPES) return 0;
+  const BatchCaps c = caps_of(num_seeds, fanouts, num_layer);
+  return layout_of(GGMS_KHOP_TYPED_TEMPORAL, num_seeds, fanouts, num_layer, c, extra, 0, num_type).total *
+             sizeof(uint32_t) + 16;
+}
+
+int ggms_sample_batch_typed_temporal(const ggms_graph_t *graph, const ggms_id_t *seeds, const uint32_t *seed_time,
+                                     size_t num_seeds, const size_t *fanouts, uint32_t num_layer, ggms_hashtable_t *ht,
+                                     ggms_id_t *const *row, ggms_id_t *const *col, ggms_id_t *const *eid,
+                                     uint8_t *const *etype, uint32_t *node_cut, uint64_t *counts_dev,
+                                     const ggms_temporal_t *tt, const ggms_typed_t *ty, const ggms_sample_extra_t *extra,
+                                     void *workspace, size_t workspace_bytes, ggms_stream_t stream) {
+  GGMS_CHECK_ARG(graph && fanouts && ht && row && col && eid && etype && node_cut && counts_dev && tt && ty);
+  GGMS_CHECK_ARG(num_layer >= 1 && num_layer <= 16);
+  GGMS_CHECK_ARG(graph->num_part == 0); // edge positions are those of one CSR
+  GGMS_CHECK_ARG(tt->edge_time && tt->cut_table && tt->stamp != 0);
+  GGMS_CHECK_ARG(tt->pick == GGMS_PICK_UNIFORM || tt->pick == GGMS_PICK_RECENT);
+  GGMS_CHECK_ARG(ty->edge_type && ty->type_fanout);
+  GGMS_CHECK_ARG(ty->num_type >= 1 && ty->num_type <= GGMS_MAX_EDGE_TYPES);
+  for (uint32_t i = 0; i < num_layer; ++i) { // every row: k_r < 128, and fanouts[i] is its sum (>= 1)
+    size_t sum = 0;
+    const int rc = typed_fanout_sum(ty->type_fanout + (size_t)i * ty->num_type, ty->num_type, &sum);
+    if (rc != GGMS_OK) return rc;
+    GGMS_CHECK_ARG(sum >= 1 && sum == fanouts[i]);
+  }
+  GGMS_CHECK_ARG(num_seeds == 0 || (seeds && seed_time));
+  for (uint32_t i = 0; i < num_layer; ++i) GGMS_CHECK_ARG(row[i] && col[i] && eid[i] && etype[i]);
+  GGMS_CHECK_ARG(workspace && workspace_bytes >= ggms_sample_batch_typed_temporal_workspace_bytes(
+                                                     num_seeds, fanouts, num_layer, ty->num_type, extra));
+  const BatchCaps c = caps_of(num_seeds, fanouts, num_layer);
+  GGMS_CHECK_ARG(c.max_input[0] + c.max_edges[0] <= ht->n2o_size);
+  GGMS_CHECK_ARG(c.max_input[0] + c.max_edges[0] < (1ull << 32) - 4); // indices and 2 + local id fit 32 bits
+  // the seeds may repeat with different times: never the distinct-seeds path, whatever the caller promises
+  ggms_sample_extra_t ex{};
+  if (extra) ex = *extra;
+  ex.seeds_distinct = 0;
+  const TemporalBatch tb{tt, seed_time, eid, node_cut};
+  const TypedBatch yb{ty, eid, etype};
+  return sample_batch_impl(GGMS_KHOP_TYPED_TEMPORAL, graph, seeds, num_seeds, fanouts, num_layer, ht, nullptr, 0, row,
+                           col, counts_dev, &ex, workspace, nullptr, to_stream(stream), &tb, &yb);
 }
 
 // ---- khop_labor_weighted: the batch with per-position weights -------------------------------------------------------

@@ -21,20 +21,12 @@
 // In a batch (ggms_sample_batch_temporal) every emitted edge f -> t also lowers t's cut-off to f's: one 64-bit atomicMax
 // on the cut table per edge, no value returned.  The table is only READ by k_temporal_prefix, which is a launch in front
 // of the ones that write it: stream order separates a layer's snapshot from its updates.
+#include "cut_word.h"
 #include "ggms_internal.h"
 #include "labor_select.h"
 #include "tile_scan.h"
 
 namespace ggms {
-
-// a cut-table word: (stamp << 32) | (0xffffffff - cut) under unsigned 64-bit max -- a newer stamp beats a stale word,
-// within a stamp the smaller cut wins; a word with another stamp reads as absent (cut = +inf = 0xffffffff)
-__device__ __forceinline__ unsigned long long cut_word(uint32_t stamp, uint32_t cut) {
-  return ((unsigned long long)stamp << 32) | (0xffffffffu - cut);
-}
-__device__ __forceinline__ uint32_t cut_of_word(unsigned long long w, uint32_t stamp) {
-  return (uint32_t)(w >> 32) == stamp ? 0xffffffffu - (uint32_t)w : 0xffffffffu;
-}
 
 __global__ __launch_bounds__(kBlock) void k_temporal_prefix(const uint32_t *__restrict__ indptr,
                                                             const uint32_t *__restrict__ edge_time,

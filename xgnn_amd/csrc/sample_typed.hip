@@ -29,19 +29,9 @@
 #include "ggms_internal.h"
 #include "labor_select.h"
 #include "tile_scan.h"
+#include "type_fanouts.h"
 
 namespace ggms {
-
-// k_r, r < GGMS_MAX_EDGE_TYPES, one byte each
-struct TypeFanouts {
-  uint32_t w[GGMS_MAX_EDGE_TYPES / 4];
-  __device__ __forceinline__ uint32_t get(uint32_t r) const {
-    uint32_t v = w[0];
-#pragma unroll
-    for (uint32_t j = 1; j < GGMS_MAX_EDGE_TYPES / 4; ++j) v = (r >> 2) == j ? w[j] : v;
-    return (v >> ((r & 3u) * 8u)) & 0xffu;
-  }
-};
 
 __global__ __launch_bounds__(kBlock) void k_typed_bounds(const uint32_t *__restrict__ indptr,
                                                          const uint8_t *__restrict__ edge_type,
@@ -228,8 +218,7 @@ int sample_khop_typed_impl(const SampleLayer &l) {
   uint32_t *heavy_count = bounds + (size_t)R * n_max;
   uint32_t *scan_scr = heavy_count + 16;
   const ScanArea sa = l.scan ? *l.scan : ScanArea{scan_scr, false};
-  TypeFanouts f{};
-  for (uint32_t r = 0; r < R; ++r) f.w[r >> 2] |= (l.type_fanout[r] & 0xffu) << ((r & 3u) * 8u);
+  const TypeFanouts f = type_fanouts_of(l.type_fanout, R);
   uint32_t gshift = 0;
   while ((1u << gshift) < R) ++gshift;
   GGMS_HIP(hipMemsetAsync(heavy_count, 0, sizeof(uint32_t), l.s));

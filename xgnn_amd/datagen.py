@@ -160,7 +160,9 @@ def write_dataset(path, graph, feat=None, label=None, valid_frac=0.02, test_frac
     sort_lists_by_time) adds edge_time.bin, the times `sample_type khop_temporal` samples before.
     edge_type (one uint8 per edge, in the order of indices, non-decreasing inside every node's list -- see
     sort_lists_by_type -- and below num_edge_type, 1 .. 32) adds edge_type.bin and the meta key NUM_EDGE_TYPE, the
-    relations `sample_type khop_typed` has a fanout for.
+    relations `sample_type khop_typed` has a fanout for.  With both edge_type and edge_time the times need only be
+    non-decreasing inside every (node, type) segment -- see sort_lists_by_type_time -- the CSR of
+    `sample_type khop_typed_temporal`.
     node_type (one uint8 per node id, below num_node_type, 1 .. 32) adds node_type.bin and the meta key NUM_NODE_TYPE,
     the types a heterogeneous batch groups its nodes by (relation_types derives consistent relations from them).
     node_feat (needs node_type; one entry per node type: a 2-d float32 / float16 numpy array, a 2-d float32 / float16 /
@@ -212,9 +214,14 @@ def write_dataset(path, graph, feat=None, label=None, valid_frac=0.02, test_frac
     if edge_time is not None:
         edge_time = np.ascontiguousarray(edge_time, dtype=np.uint32)
         assert edge_time.shape == (ix.size,), f"edge_time: one time per edge ({ix.size}), not {edge_time.shape}"
-        bad = first_unsorted_list(ip, edge_time)
-        assert bad is None, (f"edge_time: the times of node {bad}'s list are not non-decreasing "
-                             "(datagen.sort_lists_by_time re-sorts a graph)")
+        if edge_type is None:
+            bad = first_unsorted_list(ip, edge_time)
+            assert bad is None, (f"edge_time: the times of node {bad}'s list are not non-decreasing "
+                                 "(datagen.sort_lists_by_time re-sorts a graph)")
+        else:  # with types the times need only be sorted inside every (node, type) segment: khop_typed_temporal's CSR
+            bad = first_unsorted_segment(ip, edge_type, edge_time)
+            assert bad is None, (f"edge_time: the times of node {bad[0]}'s list are not non-decreasing inside its type "
+                                 f"segment at position {bad[1]} (datagen.sort_lists_by_type_time re-sorts a graph)")
         edge_time.tofile(os.path.join(path, "edge_time.bin"))
     if edge_weight is not None:
         edge_weight = np.ascontiguousarray(edge_weight, dtype=np.float32)
@@ -346,6 +353,34 @@ def first_unsorted_list(indptr, edge_time):
     starts[ip[:-1]] = True  # a list's first position has no predecessor in its list
     drop = drop[~starts[drop]]
     return None if drop.size == 0 else int(np.searchsorted(ip, drop[0], side="right") - 1)
+
+
+def first_unsorted_segment(indptr, edge_type, edge_time):
+    """(node, position) of the first edge whose time is below its predecessor's although both lie in the same list and
+    have the same type -- a violation of khop_typed_temporal's precondition on the times -- or None."""
+    ip = np.asarray(indptr, dtype=np.int64)
+    t = np.asarray(edge_time, dtype=np.int64)
+    y = np.asarray(edge_type)
+    if t.size < 2:
+        return None
+    drop = np.flatnonzero((t[1:] < t[:-1]) & (y[1:] == y[:-1])) + 1
+    starts = np.zeros(t.size + 1, bool)
+    starts[ip[:-1]] = True
+    drop = drop[~starts[drop]]
+    return None if drop.size == 0 else (int(np.searchsorted(ip, drop[0], side="right") - 1), int(drop[0]))
+
+
+def sort_lists_by_type_time(indptr, indices, edge_type, edge_time, *edge_arrays):
+    """A (type, time)-sorted CSR for khop_typed_temporal: every node's list stably re-sorted by edge type, then by time
+    inside a type.  Returns (indices, edge_type, edge_time, *edge_arrays, perm), sort_lists_by_time's convention:
+    new[p] = old[perm[p]]."""
+    ip = np.asarray(indptr, dtype=np.int64)
+    y = np.ascontiguousarray(edge_type, dtype=np.uint8)
+    t = np.ascontiguousarray(edge_time, dtype=np.uint32)
+    assert y.shape == (int(ip[-1]),) and t.shape == y.shape, "edge_type, edge_time: one value per edge"
+    owner = np.repeat(np.arange(ip.size - 1), np.diff(ip))
+    perm = np.lexsort((np.arange(y.size), t, y, owner))  # by list, then type, then time, then old position
+    return (np.asarray(indices)[perm], y[perm], t[perm], *[np.asarray(a)[perm] for a in edge_arrays], perm)
 
 
 def sort_lists_by_time(indptr, indices, edge_time, *edge_arrays):

@@ -56,8 +56,10 @@ MAX_EDGE_TYPES = 32  # GGMS_MAX_EDGE_TYPES
 KHOP_LABOR_WEIGHTED = 11  # an extension: weighted sampling without replacement, khop_labor's sharing (include/ggms.h)
 RANDOM_WALK_METAPATH = 12  # an extension: PinSAGE's walks along a relation path (include/ggms.h)
 MAX_METAPATH = 8  # GGMS_MAX_METAPATH
+KHOP_TYPED_TEMPORAL = 13  # an extension: a fanout per edge type before a per-seed cut-off time (include/ggms.h)
 # samplers without an RNG pool
-_STATELESS = (KHOP0, KHOP_LABOR, KHOP_TEMPORAL, KHOP_TYPED, KHOP_LABOR_WEIGHTED, RANDOM_WALK_METAPATH)
+_STATELESS = (KHOP0, KHOP_LABOR, KHOP_TEMPORAL, KHOP_TYPED, KHOP_LABOR_WEIGHTED, RANDOM_WALK_METAPATH,
+              KHOP_TYPED_TEMPORAL)
 
 
 def _require_gpu(t):
@@ -273,6 +275,29 @@ def sample_khop_typed(graph, edge_type, type_fanout, inp, layer_salt):
     check(lib().ggms_sample_khop_typed(C.byref(graph.c), _ptr(edge_type), R, f, _ptr(inp), n, layer_salt & 0xFFFFFFFF,
                                        _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out_type), _ptr(num_out),
                                        _ptr(ws), ws.numel() * 4, _stream()), "ggms_sample_khop_typed")
+    return out[0], out[1], out[2], out_type, num_out
+
+
+def sample_khop_typed_temporal(graph, edge_type, edge_time, type_fanout, inp, inp_cut, layer_salt, pick=PICK_UNIFORM):
+    """ggms_sample_khop_typed_temporal: per seed and edge type r, among the entries of r's segment with
+    edge_time < inp_cut[i] (a prefix of the segment on a (type, time)-sorted list), khop_labor's selection with fanout
+    type_fanout[r] (PICK_UNIFORM) or the last min(type_fanout[r], e_r) of them (PICK_RECENT).
+    Returns (out_src, out_dst, out_pos, out_type, num_out[1] on device), as sample_khop_typed does."""
+    _require_gpu(inp)
+    _i32(inp), _i32(inp_cut), _u8(edge_type), _i32(edge_time)
+    n, R = inp.numel(), len(type_fanout)
+    assert inp_cut.numel() == n
+    K = sum(int(k) for k in type_fanout)
+    dev = inp.device
+    out = [torch.empty(max(1, n * K), dtype=torch.int32, device=dev) for _ in range(3)]
+    out_type = torch.empty(max(1, n * K), dtype=torch.uint8, device=dev)
+    num_out = torch.zeros(1, dtype=torch.int64, device=dev)
+    ws = _workspace(lib().ggms_sample_khop_typed_temporal_workspace_bytes(n, R), dev)
+    f = (C.c_uint32 * max(R, 1))(*[int(k) for k in type_fanout])
+    check(lib().ggms_sample_khop_typed_temporal(C.byref(graph.c), _ptr(edge_type), _ptr(edge_time), R, f, _ptr(inp),
+                                                _ptr(inp_cut), n, pick, layer_salt & 0xFFFFFFFF, _ptr(out[0]),
+                                                _ptr(out[1]), _ptr(out[2]), _ptr(out_type), _ptr(num_out), _ptr(ws),
+                                                ws.numel() * 4, _stream()), "ggms_sample_khop_typed_temporal")
     return out[0], out[1], out[2], out_type, num_out
 
 
@@ -1522,6 +1547,57 @@ class TypedBatchSampler(_BatchBuffers):
             lay["eid"] = self.eid[i][:c[COUNT_EDGES(i)]]
             lay["etype"] = self.etype[i][:c[COUNT_EDGES(i)]]
         return dict(layers=layers, input_nodes=self.ht.n2o[:c[COUNT_INPUT(self.L)]])
+
+
+class TypedTemporalBatchSampler(TypedBatchSampler):
+    """ggms_sample_batch_typed_temporal: TemporalBatchSampler's chain (cut table, stamps, node_cut) with
+    khop_typed_temporal as the sampler and TypedBatchSampler's fanout rows.  One slot, one pipeline."""
+
+    def __init__(self, graph, edge_type, edge_time, type_fanouts, batch_size, pick=PICK_UNIFORM, device="cuda",
+                 direct_table=True, max_seeds=None):
+        super().__init__(graph, edge_type, type_fanouts, batch_size, device, direct_table, max_seeds)
+        self.sample_type = KHOP_TYPED_TEMPORAL
+        _require_gpu(_i32(edge_time))
+        self.edge_time, self.pick = edge_time, pick
+        self.node_cut = torch.empty(max(1, self.max_unique), dtype=torch.int32, device=device)
+        self.cut_table = torch.zeros(max(1, graph.c.num_node), dtype=torch.int64, device=device)
+        self.stamp = 0
+        wsb = lib().ggms_sample_batch_typed_temporal_workspace_bytes(self.max_seeds, self._f, self.L, self.num_type,
+                                                                     C.byref(self._extra))
+        self.ws = _workspace(wsb, device)
+
+    def sample(self, seeds, seed_time, salt=0, stamp=None):
+        """Enqueue one batch, as TemporalBatchSampler.sample does."""
+        _i32(seeds), _i32(seed_time)
+        n = self._n = seeds.numel()
+        assert n <= self.max_seeds and seed_time.numel() == n
+        if stamp is None:
+            if self.stamp == 0xFFFFFFFF:
+                self.cut_table.zero_()
+                self.stamp = 0
+            stamp = self.stamp + 1
+        self.stamp = stamp
+        t = _lib.Temporal(self.edge_time.data_ptr(), self.cut_table.data_ptr(), stamp, self.pick)
+        self._extra.labor_salt = salt & 0xFFFFFFFF
+        check(lib().ggms_sample_batch_typed_temporal(C.byref(self.graph.c), _ptr(seeds), _ptr(seed_time), n, self._f,
+                                                     self.L, C.byref(self.ht.c), self._rows, self._cols, self._eids,
+                                                     self._etypes, _ptr(self.node_cut), _ptr(self.counts), C.byref(t),
+                                                     C.byref(self._typed), C.byref(self._extra), _ptr(self.ws),
+                                                     self.ws.numel() * 4, _stream()), "ggms_sample_batch_typed_temporal")
+
+    def seed_ids(self):
+        """Local ids of the raw seeds of the last batch (ggms_sample_batch_seed_ids)."""
+        p = C.c_void_p()
+        check(lib().ggms_sample_batch_seed_ids(KHOP_TYPED_TEMPORAL, self._n, self._f, self.L, C.byref(self._extra),
+                                               _ptr(self.ws), C.byref(p)), "ggms_sample_batch_seed_ids")
+        off = (p.value - self.ws.data_ptr()) // 4
+        return self.ws[off: off + self._n]
+
+    def result(self):
+        """Sync and slice the outputs: TypedBatchSampler.result()'s and `node_cut`."""
+        res = super().result()
+        res["node_cut"] = self.node_cut[:res["input_nodes"].numel()]
+        return res
 
 
 class WalkMetapathBatchSampler(_BatchBuffers):
