@@ -56,7 +56,20 @@ enum ggms_status {
  *   - a SOURCE of the converting gathers only (into F32, F16, BF16; every base 8-byte aligned).  It has no element
  *     size: ggms_dtype_bytes(GGMS_Q8ROW) = 0, so every plain entry point refuses the code as it refuses an unknown
  *     one.  A Q8ROW table that has to move as bytes (cache fill, shards, replicas, the host table, IPC) moves as a
- *     GGMS_U8 table of dim = ggms_row_bytes(GGMS_Q8ROW, dim) through the plain calls. */
+ *     GGMS_U8 table of dim = ggms_row_bytes(GGMS_Q8ROW, dim) through the plain calls.
+ * GGMS_MXFP4 (an extension) is a ROW format too: OCP Microscaling FP4, a 4-bit E2M1 element and one power-of-two E8M0
+ * scale per block of 32 elements.  `dim` must be even.
+ *   - a row of `dim` elements is nb = ceil(dim / 32) blocks of 16 code bytes (element 2j of a block is the low nibble
+ *     of its byte j, element 2j + 1 the high nibble; a partial last block is padded with zero nibbles), then nb scale
+ *     bytes in block order, then zero bytes up to the stride: rows lie round_up(17 * nb, 8) bytes apart
+ *     (ggms_row_bytes) -- 72 at dim 128, 408 at dim 768, 544 at dim 1024;
+ *   - element: sign in bit 3, magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6 in bits 2..0; +-0 are distinct, no inf, no NaN.
+ *     Scale byte x means 2^(x - 127); x = 255 means NaN, and every element of that block decodes to NaN;
+ *   - element value = element x 2^(x - 127): for x in [2, 252] a normal f32 or +-0, exactly, so the decode into F32 is
+ *     exact and the decodes into F16 / BF16 are the narrowing of an F32 table's values (x in {0, 1, 253, 254}, where
+ *     the product may be subnormal or overflow: unspecified);
+ *   - a SOURCE of the converting gathers only, exactly as GGMS_Q8ROW (every base 8-byte aligned, ggms_dtype_bytes = 0,
+ *     moved as bytes as a GGMS_U8 table of dim = ggms_row_bytes(GGMS_MXFP4, dim)). */
 enum ggms_dtype {
   GGMS_F32 = 0,
   GGMS_F64 = 1,
@@ -68,7 +81,8 @@ enum ggms_dtype {
   GGMS_BF16 = 7,
   GGMS_F8E4M3 = 16,
   GGMS_F8E5M2 = 17,
-  GGMS_Q8ROW = 18
+  GGMS_Q8ROW = 18,
+  GGMS_MXFP4 = 20
 };
 
 int ggms_abi_version(void);
@@ -145,7 +159,7 @@ uint32_t ggms_debug_set_scan_epoch(uint32_t counter);
 void ggms_debug_set_knob(int knob, long long value);
 size_t ggms_dtype_bytes(int dtype);
 /* bytes from one stored row of `dim` elements to the next: dim x ggms_dtype_bytes(dtype) for the element types,
- * round_up(dim, 8) + 8 for GGMS_Q8ROW, 0 for an unknown code */
+ * round_up(dim, 8) + 8 for GGMS_Q8ROW, round_up(17 * ceil(dim / 32), 8) for GGMS_MXFP4, 0 for an unknown code */
 size_t ggms_row_bytes(int dtype, size_t dim);
 
 /* ---------------------------------------------------------------------------
@@ -1310,6 +1324,11 @@ int ggms_extract_tiered(void *out, const ggms_id_t *nodes, size_t num_nodes,
  *     (GGMS_ERR_INVALID with a message).  Its source rows lie ggms_row_bytes(GGMS_Q8ROW, dim) apart, every source
  *     base (src, shards, replica, host_feat) must be 8-byte aligned (else GGMS_ERR_INVALID, nothing launched;
  *     hipMalloc, pinned and IPC bases always are), and a chunk is 8, 4, 2 or 1 codes by the same 16-byte rule;
+ *   - GGMS_MXFP4 stands where GGMS_Q8ROW stands: a legal src_dtype with out_dtype in {F32, F16, BF16} and in no other
+ *     pair, every source base 8-byte aligned.  dim must be even (GGMS_ERR_INVALID with a message).  A chunk is 8, 4 or 2
+ *     elements by the same 16-byte rule (4 .. 1 code bytes and the block's scale byte in): the widest that divides
+ *     dim with `out` aligned to chunk x output element bytes; an `out` not aligned to two elements is
+ *     GGMS_ERR_INVALID.  A NaN scale gives NaNs, -0 stays -0;
  *   - widening (F16, BF16 -> F32) is exact, subnormals included; narrowing (F32 -> F16, BF16) rounds to nearest
  *     even, overflows to +-inf and produces subnormals; F16 <-> BF16 goes through f32; NaN stays NaN (payload
  *     unspecified);
@@ -1334,7 +1353,7 @@ int ggms_extract_tiered_convert(void *out, const ggms_id_t *nodes, size_t num_no
 /* ---------------------------------------------------------------------------
  * Row quantiser (an extension): the WRITE side of the narrow tables the converting gathers read.  `num_rows` dense
  * rows of `dim` elements of src_dtype (GGMS_F32 or GGMS_F16) are encoded into out_dtype -- GGMS_F16, GGMS_BF16,
- * GGMS_F8E4M3, GGMS_F8E5M2 or GGMS_Q8ROW -- with output rows ggms_row_bytes(out_dtype, dim) apart.  One streaming
+ * GGMS_F8E4M3, GGMS_F8E5M2, GGMS_Q8ROW or GGMS_MXFP4 -- with output rows ggms_row_bytes(out_dtype, dim) apart.  One streaming
  * pass; bit for bit what the CPU tools of xgnn_amd/datagen.py (quantize_features) compute:
  *   - F16 / BF16: round to nearest even, overflow to +-inf, subnormals kept (the converting gather's narrowing);
  *   - F8E4M3: round to nearest even after a clamp to +-448 (no infinity: +-inf and everything beyond saturate);
@@ -1346,9 +1365,15 @@ int ggms_extract_tiered_convert(void *out, const ggms_id_t *nodes, size_t num_no
  *     A row that holds NaN or +-inf has no codes: its whole output row is written as zero bytes and first_row + its
  *     index is folded into *bad_row with a 64-bit atomic minimum -- the caller sets the word to UINT64_MAX before the
  *     call and reads the smallest bad row after it; bad_row == NULL: no report.  The other formats never report.
+ *   - MXFP4 (dim even), per block of 32 elements (a partial last block: the elements that exist): amax = max |v|,
+ *     scale byte x = clamp(biased f32 exponent of amax - 2, 2, 252) (amax 0 or subnormal: 2), code = v x 2^(127 - x)
+ *     (an exact scaling) rounded to the nearest E2M1 magnitude, a tie to the code with an even low bit (0.25 -> 0,
+ *     0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4), magnitudes above 6 saturate to 6, the sign is kept
+ *     (-0.0 stays -0.0); pad nibbles and pad bytes zero.  A row that holds NaN or +-inf is a zero row reported through
+ *     *bad_row, as for Q8ROW.
  * GGMS_ERR_INVALID (nothing launched) for any other pair of dtypes, src_dtype == out_dtype, dim == 0, a `src` that is
  * not 4-byte aligned, or an `out` that is not aligned to its element (Q8ROW: to 8 bytes, every row's trailer is one
- * store).  Loads are up to 16 bytes wide where `src` and dim allow it.  num_rows == 0 is GGMS_OK.
+ * store; MXFP4: to 8 bytes, and an odd dim).  Loads are up to 16 bytes wide where `src` and dim allow it.  num_rows == 0 is GGMS_OK.
  * ------------------------------------------------------------------------- */
 int ggms_quantize_rows(void *out, int out_dtype, const void *src, int src_dtype, size_t num_rows, size_t dim,
                        uint64_t first_row, uint64_t *bad_row /* device, may be NULL */, ggms_stream_t stream);

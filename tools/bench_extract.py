@@ -19,7 +19,11 @@ the parent's f16 -> X gather of the same output beyond the 3.5 % drift of a sess
 the comparison behind the row quantiser (ggms_quantize_rows): F32 rows encoded into each of F16, BF16, F8E4M3, F8E5M2
 and Q8ROW beside the plain F32 gather of the same rows through an identity index (ggms_gather_scatter; of the parent
 build's library with --parent-lib) and a straight device copy of the input bytes; condition: no encode is slower than
-that gather beyond the 3.5 % drift of a session."""
+that gather beyond the 3.5 % drift of a session, and
+    python tools/bench_extract.py --mxfp4-ab [--dim 128 --rows N --table-rows N] [--parent-lib SO] [--alt-lib SO] [--out FILE]
+the comparison behind MXFP4 (block-scaled 4-bit) tables: the MXFP4 -> bf16 / f32 gathers (of a trial build with another
+chunk width too: --alt-lib) beside the F8E4M3 -> bf16 / f32 gathers (of the parent build with --parent-lib) and the
+Q8ROW -> bf16 gather, then the row quantiser into MXFP4 beside Q8ROW on the same F32 rows, as GB/s of source read."""
 import argparse
 import ctypes as C
 import os, sys
@@ -37,6 +41,7 @@ ap.add_argument("--ab", action="store_true")
 ap.add_argument("--fp8-ab", action="store_true")
 ap.add_argument("--q8row-ab", action="store_true")
 ap.add_argument("--quantize-ab", action="store_true")
+ap.add_argument("--mxfp4-ab", action="store_true")
 ap.add_argument("--parent-lib", help="--fp8-ab / --q8row-ab: a libggms_hip.so of another build, timed beside this one")
 ap.add_argument("--alt-lib", help="--fp8-ab: a trial build whose FP8 gathers are timed too")
 ap.add_argument("--alt-name", default="trial build")
@@ -319,6 +324,77 @@ def run_quantize_ab():
             f.write(text + "\n")
 
 
+def run_mxfp4_ab():
+    """Gathers: one ggms_gather_scatter_convert launch on the same index, algorithmic bytes = rows x (4 + stored row bytes
+    + dim x output element bytes); encodes: one ggms_quantize_rows launch, source bytes read.  5 rounds x 30 launches per
+    case in alternating order."""
+    idx = torch.randint(0, args.table_rows, (args.rows,), device=dev, dtype=torch.int32)
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def entry(path):
+        fn = C.CDLL(path).ggms_gather_scatter_convert
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_uint32, C.c_void_p]
+        return fn
+
+    from xgnn_amd import _lib
+    this = entry(_lib.LIB_PATH)
+    src = torch.randn(args.table_rows, args.dim, device=dev)
+    tables = {"mxfp4": (ops.quantize_rows(src, ops.MXFP4), ops.MXFP4), "q8row": (ops.quantize_rows(src, ops.Q8ROW), ops.Q8ROW),
+              "f8e4m3": (ops.quantize_rows(src, torch.float8_e4m3fn), 16)}
+    outs = {k: torch.empty((args.rows, args.dim), dtype=DT[k], device=dev) for k in ("f32", "bf16")}
+    cases = []
+
+    def add(name, fn, td, od):
+        (t, code), o = tables[td], outs[od]
+
+        def run():
+            rc = fn(o.data_ptr(), t.data_ptr(), idx.data_ptr(), None, args.rows, None, args.dim, code,
+                    ops.DTYPE_CODE[o.dtype], 0xFFFFFFFF, stream)
+            assert rc == 0, (name, rc)
+        cases.append((name, run, args.rows * (4 + ops.row_bytes(code, args.dim) + args.dim * o.element_size())))
+
+    fp8_name, fp8 = ("parent build", entry(args.parent_lib)) if args.parent_lib else ("this build", this)
+    for od in ("bf16", "f32"):
+        add(f"{fp8_name}: f8e4m3 -> {od}", fp8, "f8e4m3", od)
+        add(f"this build: mxfp4 -> {od}", this, "mxfp4", od)
+        if args.alt_lib:
+            add(f"{args.alt_name}: mxfp4 -> {od}", entry(args.alt_lib), "mxfp4", od)
+    add("this build: q8row -> bf16", this, "q8row", "bf16")
+    n_enc = min(args.rows, args.table_rows)
+    enc_src = src[:n_enc]
+    for name, dt in (("q8row", ops.Q8ROW), ("mxfp4", ops.MXFP4)):
+        out = ops.quantize_rows(enc_src, dt)
+        cases.append((f"this build: encode f32 -> {name} (source bytes)", lambda dt=dt, out=out: ops.quantize_rows(enc_src, dt, out=out, check=False),
+                      n_enc * args.dim * 4))
+    copy_dst = torch.empty_like(enc_src)
+    cases.append(("straight copy (torch copy_), f32 rows", lambda: copy_dst.copy_(enc_src), 2 * n_enc * args.dim * 4))
+    times = {name: [] for name, _, _ in cases}
+    for rnd in range(5):
+        for name, fn, _ in (cases if rnd % 2 == 0 else cases[::-1]):
+            times[name].append(timeit(fn, reps=30))
+    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    lines = [f"MXFP4 table A/B: {args.rows} rows x dim {args.dim} (stored row {ops.row_bytes(ops.MXFP4, args.dim)} B), tables of "
+             f"{args.table_rows} rows in HBM, one process, 5 rounds x 30 launches per case in alternating order, median of the "
+             f"rounds (min .. max; spread = (max - min) / median); fraction of the 8 TB/s HBM peak from algorithmic bytes",
+             f"device: {torch.cuda.get_device_name(0)}"]
+    for name, _, by in cases:
+        v = times[name]
+        lines.append(f"{name:52s} {med[name] * 1e3:7.4f} ms  ({min(v) * 1e3:.4f} .. {max(v) * 1e3:.4f}; spread "
+                     f"{(max(v) - min(v)) / med[name] * 100:4.1f} %)  {by / med[name] / 1e9:7.1f} GB/s = {by / med[name] / 8e12:.3f} of peak")
+    for od in ("bf16", "f32"):
+        lines.append(f"mxfp4 -> {od} / {fp8_name}'s f8e4m3 -> {od} = {med[f'this build: mxfp4 -> {od}'] / med[f'{fp8_name}: f8e4m3 -> {od}']:.3f}")
+    text = "\n".join(lines)
+    print(text, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
+if args.mxfp4_ab:
+    run_mxfp4_ab()
+    sys.exit(0)
 if args.quantize_ab:
     run_quantize_ab()
     sys.exit(0)

@@ -194,7 +194,7 @@ class SamGraphBasics(object):
     def feat_dim(self): return self.C_LIB_CTYPES.samgraph_feat_dim()
 
     def feat_row_bytes(self, delivered=False):
-        """Bytes of one feature row as stored in the table (a Q8ROW row: codes, pad, trailer) or as delivered in a batch."""
+        """Bytes of one feature row as stored in the table (a Q8ROW row: codes, pad, trailer; an MXFP4 row: code blocks, scale bytes, pad) or as delivered in a batch."""
         return self.C_LIB_CTYPES.samgraph_feat_row_bytes(1 if delivered else 0)
     def num_negative(self): return self.C_LIB_CTYPES.samgraph_num_negative()
     def get_graph_num_excluded(self, key): return self.C_LIB_CTYPES.samgraph_get_graph_num_excluded(key)

@@ -147,12 +147,13 @@ size_t ggms_dtype_bytes(int dtype) {
     case GGMS_BF16: return 2;
     case GGMS_F8E4M3: return 1;
     case GGMS_F8E5M2: return 1;
-    default: return 0; // GGMS_Q8ROW too: a row of codes with a trailer has no element size (ggms_row_bytes)
+    default: return 0; // GGMS_Q8ROW and GGMS_MXFP4 too: a row of codes with its scales has no element size (ggms_row_bytes)
   }
 }
 
 size_t ggms_row_bytes(int dtype, size_t dim) {
   if (dtype == GGMS_Q8ROW) return (size_t)q8row_stride(dim);
+  if (dtype == GGMS_MXFP4) return (size_t)mxfp4_stride(dim);
   return dim * ggms_dtype_bytes(dtype);
 }
 

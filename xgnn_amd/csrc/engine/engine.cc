@@ -85,12 +85,16 @@ static void refuse_arch6_keys(std::unordered_map<std::string, std::string> &kv, 
 static const char *const kQ8RowNeedsOutDtype =
     "FEAT_DATA_TYPE Q8ROW needs the config key feat_out_dtype (f32 | f16 | bf16): a row of 8-bit codes with its scale and "
     "bias is decoded by the feature gather, there is no element type to deliver it in as it is";
+// the same for a block-scaled 4-bit table (FEAT_DATA_TYPE MXFP4, or feat_store_dtype = MXFP4)
+static const char *const kMxfp4NeedsOutDtype =
+    "FEAT_DATA_TYPE MXFP4 needs the config key feat_out_dtype (f32 | f16 | bf16): a row of 4-bit codes with its block "
+    "scales is decoded by the feature gather, there is no element type to deliver it in as it is";
 // the dtype names of meta.txt's FEAT_DATA_TYPE; feat_store_dtype takes those of them the quantiser writes
 static const std::map<std::string, int> kFeatDtypeNames = {{"F32", GGMS_F32}, {"F64", GGMS_F64}, {"F16", GGMS_F16},
                                                            {"U8", GGMS_U8},   {"I32", GGMS_I32}, {"I8", GGMS_I8},
                                                            {"I64", GGMS_I64}, {"BF16", GGMS_BF16},
                                                            {"F8E4M3", GGMS_F8E4M3}, {"F8E5M2", GGMS_F8E5M2},
-                                                           {"Q8ROW", GGMS_Q8ROW}};
+                                                           {"Q8ROW", GGMS_Q8ROW}, {"MXFP4", GGMS_MXFP4}};
 
 void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in) {
   auto kv = kv_in;
@@ -287,7 +291,7 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
     const auto name = kFeatDtypeNames.find(v);
     if (name == kFeatDtypeNames.end() || !ggms::quantiser_writes(name->second))
       fatal(__FILE__, __LINE__, "feat_store_dtype = " + v + ": unknown store type; the GPU quantiser writes F16, BF16, "
-                                "F8E4M3, F8E5M2 or Q8ROW");
+                                "F8E4M3, F8E5M2, Q8ROW or MXFP4");
     cfg.feat_store_dtype = name->second;
     if (cfg.arch == kArch0)
       fatal(__FILE__, __LINE__, "arch0: feat_store_dtype needs a GPU: the table is encoded by a kernel, and the CPU engine "
@@ -298,6 +302,7 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
                                 "forks; quantise the dataset offline (datagen.quantize_features)");
     // the batch dtype rule of a table of that type (the table's side of it is checked in LoadDataset)
     if (cfg.feat_store_dtype == GGMS_Q8ROW && cfg.feat_out_dtype < 0) fatal(__FILE__, __LINE__, kQ8RowNeedsOutDtype);
+    if (cfg.feat_store_dtype == GGMS_MXFP4 && cfg.feat_out_dtype < 0) fatal(__FILE__, __LINE__, kMxfp4NeedsOutDtype);
   }
   if (kv.count("inline_heads")) { // extension: inline list heads for khop3 (include/ggms.h), built at graph load
     const std::string v = kv["inline_heads"];
@@ -674,14 +679,15 @@ void Engine::LoadDataset() {
       // (an FP8 table is a source of the converting gather only: without the key its rows are moved as bytes)
       if (cfg.feat_out_dtype >= 0 && !ggms::gather_converts_from(ds.feat_dtype))
         fatal(__FILE__, __LINE__, "feat_out_dtype with FEAT_DATA_TYPE " + v + ": the gather converts F16, BF16, F32, "
-                                  "F8E4M3, F8E5M2 and Q8ROW tables only");
+                                  "F8E4M3, F8E5M2, Q8ROW and MXFP4 tables only");
       // a row-scaled table has no element type to hand out raw: only the converting gather can deliver its rows
       if (ds.feat_dtype == GGMS_Q8ROW && cfg.feat_out_dtype < 0) fatal(__FILE__, __LINE__, kQ8RowNeedsOutDtype);
+      if (ds.feat_dtype == GGMS_MXFP4 && cfg.feat_out_dtype < 0) fatal(__FILE__, __LINE__, kMxfp4NeedsOutDtype);
     } else if (k == "EDGE_FEAT_DATA_TYPE") { // (read whatever the config says: the file describes the dataset)
       SAM_CHECK(kFeatDtypeNames.count(v), "unknown EDGE_FEAT_DATA_TYPE " + v);
       ds.edge_feat_dtype = kFeatDtypeNames.at(v);
-      if (cfg.edge_feat && ds.edge_feat_dtype == GGMS_Q8ROW)
-        fatal(__FILE__, __LINE__, "edge_feat with EDGE_FEAT_DATA_TYPE Q8ROW: the edge rows are moved by the plain gather, "
+      if (cfg.edge_feat && ggms::is_row_format(ds.edge_feat_dtype))
+        fatal(__FILE__, __LINE__, "edge_feat with EDGE_FEAT_DATA_TYPE " + v + ": the edge rows are moved by the plain gather, "
                                   "which takes element types only; a row-scaled edge table is not built");
     } else {
       meta[k] = std::stoull(v);
@@ -717,6 +723,10 @@ void Engine::LoadDataset() {
       fatal(__FILE__, __LINE__, key + ": needs the dataset's own feat.bin; a stand-in table (SAMGRAPH_EMPTY_FEAT, "
                                 "SAMGRAPH_FAKE_FEAT_DIM, or a dataset without feat.bin) is not quantised");
   }
+  if (!cfg.typed_feat && ds.feat_dim % 2 != 0 && (ds.feat_dtype == GGMS_MXFP4 || cfg.feat_store_dtype == GGMS_MXFP4))
+    fatal(__FILE__, __LINE__, std::string(ds.feat_dtype == GGMS_MXFP4 ? "FEAT_DATA_TYPE" : "feat_store_dtype") +
+                              " MXFP4 with FEAT_DIM " + std::to_string(ds.feat_dim) + ": an MXFP4 row has an even number of "
+                              "elements (two share a byte)");
   const size_t row_bytes = ds.feat_row_bytes();
   ds.feat_rows = ds.num_node;
   size_t empty_bits = 0; // SAMGRAPH_EMPTY_FEAT = k (run_config.cc:137-139, engine.cc:205-207): a 2^k-row stand-in table,
@@ -1809,8 +1819,8 @@ void Engine::QuantizeStore() {
   }
   (void)hipFree(d_bad);
   if (bad != ~0ull)
-    fatal(__FILE__, __LINE__, "feat_store_dtype = Q8ROW: row " + std::to_string(bad) + " of feat.bin holds NaN or inf: a "
-                              "row-scaled table has no code for either");
+    fatal(__FILE__, __LINE__, "feat_store_dtype = " + cfg.raw["feat_store_dtype"] + ": row " + std::to_string(bad) +
+                              " of feat.bin holds NaN or inf: a row-scaled table has no code for either");
   const size_t before = ds.feat.bytes;
   if (ds.feat.ptr && ds.feat.bytes) munmap(ds.feat.ptr, ds.feat.bytes); // the mapped file (arch1 / arch3 / arch4: never shared)
   ds.feat = q;

@@ -91,7 +91,7 @@ struct RunConfig {
   // extension (config key `feat_out_dtype` = f32 | f16 | bf16): the dtype the batch's feature rows are DELIVERED in; the
   // gather converts from the table's (FEAT_DATA_TYPE) in its one pass.  -1: key absent, the table's dtype
   int feat_out_dtype = -1;
-  // extension (config key `feat_store_dtype` = F16 | BF16 | F8E4M3 | F8E5M2 | Q8ROW): the F32 / F16 table on disk is
+  // extension (config key `feat_store_dtype` = F16 | BF16 | F8E4M3 | F8E5M2 | Q8ROW | MXFP4): the F32 / F16 table on disk is
   // encoded into this type by the trainer GPU before the cache is built (Engine::QuantizeStore); from then on the
   // dataset is what a meta.txt naming the type would have loaded.  -1: key absent, the table stays as it is on disk
   int feat_store_dtype = -1;
@@ -199,7 +199,8 @@ struct Dataset {
   uint32_t feat_mask = 0xffffffffu;
   size_t feat_rows = 0; // rows of ds.feat (num_node, or 2^k)
   // bytes from one STORED row of the table to the next: what sizes and strides the table, the cache, its shards and
-  // replicas and the staging buffers (feat_dim x element bytes; a Q8ROW row is its codes, pad and scale / bias trailer)
+  // replicas and the staging buffers (feat_dim x element bytes; a Q8ROW row is its codes, pad and scale / bias trailer, an MXFP4 row its
+  // code blocks, scale bytes and pad)
   size_t feat_row_bytes() const { return ggms_row_bytes(feat_dtype, feat_dim); }
   // edge_feat: edge_feat.bin, NUM_EDGE rows of EDGE_FEAT_DIM elements of EDGE_FEAT_DATA_TYPE (F32 without the key) in CSR
   // order

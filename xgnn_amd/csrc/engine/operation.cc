@@ -117,7 +117,7 @@ void samgraph_get_graph_data(uint64_t key, int l, samgraph_tensor_t *out) {
 }
 void samgraph_get_dataset_feat(samgraph_tensor_t *out) {
   auto &E = Engine::Get();
-  if (E.ds.feat_dtype == GGMS_Q8ROW) { // no element type: the stored rows as bytes, (rows, stride) of U8
+  if (E.ds.feat_dtype == GGMS_Q8ROW || E.ds.feat_dtype == GGMS_MXFP4) { // row formats, no element type: the stored rows as bytes, (rows, stride) of U8
     fill(out, E.ds.feat.ptr, (int64_t)E.ds.feat_rows, (int64_t)E.ds.feat_row_bytes(), 2, GGMS_U8, 0, 0);
     return;
   }

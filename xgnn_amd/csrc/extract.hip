@@ -202,6 +202,8 @@ __global__ __launch_bounds__(kBlock) void k_gather_rows(char *__restrict__ out, 
   // resolve one row per lane for tile `t`: source pointer (+ destination pointer; + the row's scale and bias, the
   // 8-byte trailer behind a Q8ROW row's codes)
   [[maybe_unused]] const uint64_t trailer = q8row_trailer_offset((uint64_t)rc * SB);
+  // MXFP4: where a row's scale bytes begin (rc chunks of 2 x SB elements a row)
+  [[maybe_unused]] const uint64_t mx_scales = mxfp4_scale_offset((uint64_t)rc * SB * 2);
   auto resolve = [&](uint64_t t, uint64_t &sp, uint64_t &dp, uint32_t &miss, [[maybe_unused]] u32x2_t &sb) {
     const uint64_t my_row = t * kWave + lane;
     sp = 0; dp = 0; miss = 0;
@@ -244,6 +246,7 @@ __global__ __launch_bounds__(kBlock) void k_gather_rows(char *__restrict__ out, 
     const uint64_t out_tile = (uint64_t)(out + row0 * row_bytes);
     for (uint32_t c0 = 0; c0 < total; c0 += kWave * U) {
       SV tmp[U];
+      [[maybe_unused]] uint8_t xs[Chunk::kBlockScaled ? U : 1]; // the scale byte of each chunk's block (MxChunk only)
       uint32_t cc[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -254,6 +257,8 @@ __global__ __launch_bounds__(kBlock) void k_gather_rows(char *__restrict__ out, 
         const uint32_t col = cc[u] - r * rc;
         const uint64_t p = shfl_u64(sp, (int)r);
         tmp[u] = load_chunk<SV, true>(p + (uint64_t)col * SB);
+        // (the row's other chunks read the same few bytes: left to the cache, not streamed past it)
+        if constexpr (Chunk::kBlockScaled) xs[u] = load_chunk<uint8_t, false>(p + mx_scales + col / Chunk::kChunksPerBlock);
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -271,6 +276,8 @@ __global__ __launch_bounds__(kBlock) void k_gather_rows(char *__restrict__ out, 
           const uint32_t r = __umulhi(cc[u], magic) + (rc == 1 ? cc[u] : 0u);
           const uint32_t scale = __shfl(sb.x, (int)r, 64), bias = __shfl(sb.y, (int)r, 64);
           if (c < total) store_chunk<DV, true>(q, Chunk::convert(tmp[u], scale, bias));
+        } else if constexpr (Chunk::kBlockScaled) {
+          if (c < total) store_chunk<DV, true>(q, Chunk::convert(tmp[u], xs[u]));
         } else {
           if (c < total) store_chunk<DV, true>(q, Chunk::convert(tmp[u]));
         }
@@ -314,6 +321,13 @@ __global__ __launch_bounds__(kBlock) void k_gather_long_rows(char *__restrict__ 
       const u32x2_t sb = load_chunk<u32x2_t, true>(sp + q8row_trailer_offset(rc * SB));
       for (uint64_t c = threadIdx.x; c < rc; c += kBlock)
         store_chunk<DV, true>(dp + c * DB, Chunk::convert(load_chunk<SV, true>(sp + c * SB), sb.x, sb.y));
+    } else if constexpr (Chunk::kBlockScaled) { // the chunk and its block's scale byte
+      const uint64_t scales = sp + mxfp4_scale_offset(rc * SB * 2);
+      for (uint64_t c = threadIdx.x; c < rc; c += kBlock) {
+        const SV v = load_chunk<SV, true>(sp + c * SB);
+        const uint8_t x = load_chunk<uint8_t, false>(scales + c / Chunk::kChunksPerBlock);
+        store_chunk<DV, true>(dp + c * DB, Chunk::convert(v, x));
+      }
     } else {
       for (uint64_t c = threadIdx.x; c < rc; c += kBlock)
         store_chunk<DV, true>(dp + c * DB, Chunk::convert(load_chunk<SV, true>(sp + c * SB)));
@@ -434,7 +448,7 @@ static int launch_gather(char *out, Rows rows, const uint32_t *dst_index, size_t
 // one of those or an FP8 type (decoded, never produced), and the gather converts (ConvertChunk): the same locators,
 // sweep and launch path, chunks of `epc` elements.  A Q8ROW source (row-scaled codes, a source only and never moved
 // "plain": it has no element size) goes the same way with ScaledChunk; its element is the one-byte code and its rows
-// lie ggms_row_bytes apart.
+// lie ggms_row_bytes apart.  An MXFP4 source (block-scaled 4-bit codes) stands where Q8ROW stands, with MxChunk.
 struct RowMove {
   int src_dt, dst_dt;
   size_t dim, src_es, dst_es, src_stride;
@@ -442,13 +456,17 @@ struct RowMove {
   size_t src_row_bytes() const { return src_stride; } // the distance between two stored rows
 };
 static bool row_move(int src_dt, int dst_dt, size_t dim, RowMove &m) {
-  const bool q8row = src_dt == GGMS_Q8ROW; // its element is the one-byte code
-  if ((q8row || dst_dt == GGMS_Q8ROW) && !(q8row && is_float_dtype(dst_dt))) {
-    set_error("extract: invalid argument: no conversion from dtype %d to dtype %d (Q8ROW is the source of a "
+  const bool coded = is_row_format(src_dt); // Q8ROW: its element is the one-byte code; MXFP4: half a byte, 1 stands in
+  if ((coded || is_row_format(dst_dt)) && !(coded && is_float_dtype(dst_dt))) {
+    set_error("extract: invalid argument: no conversion from dtype %d to dtype %d (Q8ROW and MXFP4 are sources of a "
               "converting gather into F16, BF16 or F32, nothing else)", src_dt, dst_dt);
     return false;
   }
-  m = RowMove{src_dt, dst_dt, dim, q8row ? 1 : ggms_dtype_bytes(src_dt), ggms_dtype_bytes(dst_dt), ggms_row_bytes(src_dt, dim)};
+  if (src_dt == GGMS_MXFP4 && dim % 2 != 0) {
+    set_error("extract: invalid argument: an MXFP4 row of dim %zu (dim must be even: two elements share a byte)", dim);
+    return false;
+  }
+  m = RowMove{src_dt, dst_dt, dim, coded ? 1 : ggms_dtype_bytes(src_dt), ggms_dtype_bytes(dst_dt), ggms_row_bytes(src_dt, dim)};
   if (m.src_es == 0 || m.dst_es == 0 || dim == 0) {
     set_error("extract: invalid argument: dtype %d -> %d, dim %zu (unknown dtype or empty rows)", src_dt, dst_dt, dim);
     return false;
@@ -472,6 +490,32 @@ template <int DST_DT> struct ScaledFamily { // Q8ROW -> DST_DT: a one-byte sourc
   static constexpr int kMaxEpc = convert_max_epc(1, sizeof(typename Elem<DST_DT>::bits));
   template <int EPC> using Chunk = ScaledChunk<EPC, DST_DT>;
 };
+
+template <int DST_DT> struct MxFamily { // MXFP4 -> DST_DT: chunks of 2, 4 or 8 elements, half a byte each
+  static constexpr int kSrcDt = GGMS_MXFP4, kDstDt = DST_DT;
+  template <int EPC> using Chunk = MxChunk<EPC, DST_DT>;
+};
+template <int DST_DT, bool SCATTER, typename Rows>
+static int launch_mx(char *out, Rows rows, const uint32_t *dst_index, size_t n_max, Count n, size_t dim, uint64_t *miss_count,
+                     hipStream_t stream) {
+  using F = MxFamily<DST_DT>;
+  constexpr size_t DES = sizeof(typename Elem<DST_DT>::bits);
+  // the widest chunk of the 16-byte rule (convert_max_epc) that divides dim with `out` aligned to it; a row's blocks are
+  // 16 code bytes each and its base a multiple of 8, so the source side of every width is aligned
+  int epc = convert_max_epc(1, DES);
+  while (epc > 2 && (dim % epc != 0 || (uintptr_t)out % (epc * DES) != 0)) epc >>= 1;
+  const uint64_t rc = dim / epc;
+  switch (epc) {
+    case 8: return launch_chunks<typename F::template Chunk<8>, Rows, SCATTER>(out, rows, dst_index, n_max, n, rc, miss_count, stream);
+    case 4: return launch_chunks<typename F::template Chunk<4>, Rows, SCATTER>(out, rows, dst_index, n_max, n, rc, miss_count, stream);
+  }
+  if ((uintptr_t)out % (2 * DES) != 0) {
+    set_error("extract: invalid argument: `out` is not aligned to two elements of dtype %d (the narrowest MXFP4 chunk is one "
+              "code byte)", DST_DT);
+    return GGMS_ERR_INVALID;
+  }
+  return launch_chunks<typename F::template Chunk<2>, Rows, SCATTER>(out, rows, dst_index, n_max, n, rc, miss_count, stream);
+}
 
 // rows of `dim` elements in the family's chunk of `epc` of them (8-element chunks exist where kMaxEpc allows them only)
 template <typename Family, bool SCATTER, typename Rows>
@@ -499,6 +543,19 @@ static int launch_move(char *out, Rows rows, const uint32_t *dst_index, size_t n
     return launch_gather(out, rows, dst_index, n_max, n, m.src_row_bytes(),
                          pick_chunk(m.src_row_bytes(), (uintptr_t)out | src_bits), miss_count, stream);
   const int epc = pick_chunk(m.dim, convert_max_epc(m.src_es, m.dst_es), m.src_es, src_bits, m.dst_es, (uintptr_t)out);
+  if (m.src_dt == GGMS_MXFP4) {
+    // rows lie a multiple of 8 bytes apart: an 8-byte aligned base keeps every chunk of up to 4 code bytes aligned
+    if (src_bits % 8 != 0) {
+      set_error("extract: invalid argument: an MXFP4 source base is not 8-byte aligned (rows are a multiple of 8 bytes, a chunk up to 4 "
+                "code bytes read by one load)");
+      return GGMS_ERR_INVALID;
+    }
+    switch (m.dst_dt) {
+      case GGMS_F32: return launch_mx<GGMS_F32, SCATTER>(out, rows, dst_index, n_max, n, m.dim, miss_count, stream);
+      case GGMS_F16: return launch_mx<GGMS_F16, SCATTER>(out, rows, dst_index, n_max, n, m.dim, miss_count, stream);
+      case GGMS_BF16: return launch_mx<GGMS_BF16, SCATTER>(out, rows, dst_index, n_max, n, m.dim, miss_count, stream);
+    }
+  }
   if (m.src_dt == GGMS_Q8ROW) {
     // rows lie a multiple of 8 bytes apart, so an 8-byte aligned base puts every row's trailer where one 8-byte load
     // reads it (the callers of a Q8ROW gather put their shard bases into src_bits too)
@@ -537,11 +594,11 @@ static int launch_move(char *out, Rows rows, const uint32_t *dst_index, size_t n
 
 using namespace ggms;
 
-// The shard bases of a Q8ROW gather, ORed (launch_move checks their alignment; every other gather leaves them out:
+// The shard bases of a Q8ROW or MXFP4 gather, ORed (launch_move checks their alignment; every other gather leaves them out:
 // shard bases come from hipMalloc / hipIpcOpenMemHandle / hipHostMalloc, and its chunk choice is unchanged by this)
 static inline uintptr_t part_align_bits(const PartPtrs &pp, uint32_t num_part, const RowMove &m) {
   uintptr_t bits = 0;
-  if (m.src_dt == GGMS_Q8ROW)
+  if (is_row_format(m.src_dt))
     for (uint32_t p = 0; p < (num_part ? num_part : 1); ++p) bits |= (uintptr_t)pp.p[p];
   return bits;
 }

@@ -1,5 +1,5 @@
 // quantize.hip -- the write side of the narrow feature tables: F32 / F16 rows encoded into F16, BF16, the two OCP
-// 8-bit floats or the row-scaled GGMS_Q8ROW format (ggms_quantize_rows, include/ggms.h).  The row gather (extract.hip)
+// 8-bit floats, the row-scaled GGMS_Q8ROW format or the block-scaled GGMS_MXFP4 (ggms_quantize_rows, include/ggms.h).  The row gather (extract.hip)
 // decodes what this file writes; the results are defined bit for bit by the CPU tools of xgnn_amd/datagen.py.
 //
 // A streaming pass: every source byte is read once (Q8ROW rows beyond kRegDim elements: twice), every output byte
@@ -13,7 +13,7 @@
 //     wave, one pass.  Rows of more than kRegDim elements take k_q8row_long: one wave per row, which reads it twice.
 //   * The encode itself is float64, as quantize_q8row computes it: one subtraction, one correctly rounded division and
 //     one round-half-even per element.
-#include "row_formats.h"
+#include "row_chunks.h"
 #include "fp8_encode.h"
 #include "ggms_device.h"
 
@@ -224,7 +224,123 @@ __global__ __launch_bounds__(kBlock) void k_q8row_long(char *__restrict__ out, c
   }
 }
 
+// ---- MXFP4 -------------------------------------------------------------------------------------------------------------
+// A block of 32 elements is one 128-byte line of f32 (64 bytes of f16) and belongs to a GROUP of G lanes that hold 16
+// source bytes each: 8 lanes x 4 f32, 4 lanes x 8 f16 -- a wave encodes BPW = 8 (16) blocks per pass.  The group
+// reduces the block's largest magnitude with lane shuffles (integer max of the |bits|; no LDS memory), every lane
+// rounds and packs its own elements (mxfp4_code, row_formats.h), and the packed nibbles travel to the group's first
+// lane, which writes the block's 16 code bytes in one store and its scale byte in another.
+// Rows are never split between waves, because a row that holds NaN or inf is zeroed as a whole by the wave that owns
+// it: rows of at most BPW blocks share a wave (BPW / nb consecutive rows per pass, so the wave's blocks are
+// consecutive in memory on both sides), a longer row takes a wave for ceil(nb / BPW) passes.
+template <int SRC_DT, int V>
+__global__ __launch_bounds__(kBlock) void k_mxfp4_rows(char *__restrict__ out, const char *__restrict__ src, uint64_t num_rows,
+                                                       uint32_t dim, uint32_t rows_per_pass, uint64_t first_row,
+                                                       unsigned long long *bad_row) {
+  using S = Elem<SRC_DT>;
+  using SV = typename VecT<typename S::bits, V>::type;
+  constexpr uint32_t ES = sizeof(typename S::bits), EPL = 16 / ES, G = kMxBlock / EPL, BPW = kWave / G, LOADS = EPL / V;
+  const uint32_t lane = lane_id(), j = lane % G, sub = lane / G;
+  const uint64_t wave = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6, num_waves = (uint64_t)gridDim.x * (kBlock / kWave);
+  const uint32_t nb = (uint32_t)mxfp4_blocks(dim);
+  const uint64_t out_stride = mxfp4_stride(dim), scales = mxfp4_scale_offset(dim);
+  // my block of a pass: row sub / nb of the wave's rows and its block sub % nb, or block pass x BPW + sub of the one row
+  const bool shared = nb <= BPW;
+  const uint32_t my_row = shared ? sub / nb : 0u, my_blk = shared ? sub - my_row * nb : sub;
+  const uint32_t passes = (nb + BPW - 1) / BPW, row_lanes = shared ? nb * G : (uint32_t)kWave, row_lane0 = my_row * row_lanes;
+  for (uint64_t r0 = wave * rows_per_pass; r0 < num_rows; r0 += num_waves * rows_per_pass) { // uniform per wave
+    const uint64_t row = r0 + my_row;
+    const bool row_live = my_row < rows_per_pass && row < num_rows;
+    const uint64_t src_row = (uint64_t)src + row * dim * ES, out_row = (uint64_t)out + row * out_stride;
+    uint32_t bad = 0u;
+    for (uint32_t p = 0; p < passes; ++p) { // uniform
+      const uint32_t blk = p * BPW + my_blk;
+      const bool live = row_live && blk < nb;
+      const uint32_t e0 = blk * kMxBlock + j * EPL; // my first element; V divides dim: a load is whole or not at all
+      float x[EPL];
+#pragma unroll
+      for (uint32_t l = 0; l < LOADS; ++l) {
+        const bool there = live && e0 + l * V < dim;
+        SV v = {};
+        if (there) v = load_chunk<SV, true>(src_row + (uint64_t)(e0 + l * V) * ES);
+#pragma unroll
+        for (int i = 0; i < V; ++i) x[l * V + i] = there ? S::to_f32(vec_get<SV, V>(v, i)) : 0.0f;
+      }
+      uint32_t amax = 0u; // |bits| order as the magnitudes do; NaN and inf are on top
+#pragma unroll
+      for (uint32_t i = 0; i < EPL; ++i) {
+        const uint32_t a = __builtin_bit_cast(uint32_t, x[i]) & 0x7fffffffu;
+        amax = a > amax ? a : amax;
+      }
+      bad |= amax >= 0x7f800000u ? 1u : 0u;
+#pragma unroll
+      for (uint32_t off = 1; off < G; off <<= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)amax, (int)off, 64);
+        amax = o > amax ? o : amax;
+      }
+      const uint32_t xb = mxfp4_scale_byte(amax);
+      uint32_t w = 0u; // my EPL nibbles, the first element lowest
+#pragma unroll
+      for (uint32_t i = 0; i < EPL; ++i) w |= mxfp4_code(x[i], xb) << (4 * i);
+      u32x4_t codes;
+      const int first = (int)(lane - j);
+      if constexpr (EPL == 8) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) codes[k] = (uint32_t)__shfl((int)w, first + k, 64);
+      } else { // 16 bits a lane: two lanes make a word
+        const uint32_t pair = w | ((uint32_t)__shfl_xor((int)w, 1, 64) << 16); // (right in the even lanes)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) codes[k] = (uint32_t)__shfl((int)pair, first + 2 * k, 64);
+      }
+      if (live && j == 0) {
+        store_chunk<u32x4_t, true>(out_row + 16u * blk, codes);
+        store_chunk<uint8_t, true>(out_row + scales + blk, (uint8_t)xb);
+        if (blk == nb - 1)
+          for (uint64_t i = 17u * (uint64_t)nb; i < out_stride; ++i) store_chunk<uint8_t, true>(out_row + i, (uint8_t)0);
+      }
+    }
+    // a row that holds NaN or inf: zero bytes, written over what its lanes stored (their stores have completed first)
+    const unsigned long long bad_lanes = __ballot(bad != 0u);
+    const unsigned long long mine = row_lanes == (uint32_t)kWave ? ~0ull : (((1ull << row_lanes) - 1ull) << (row_lane0 & 63u));
+    if (row_live && (bad_lanes & mine) != 0ull) {
+      __threadfence();
+      const uint32_t k = lane - row_lane0;
+      for (uint64_t o = 8ull * k; o < out_stride; o += 8ull * row_lanes) store_chunk<u32x2_t, false>(out_row + o, u32x2_t{0u, 0u});
+      if (k == 0 && bad_row) atomicMin(bad_row, (unsigned long long)(first_row + row));
+    }
+  }
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------
+template <int SRC_DT, int V>
+static int launch_mxfp4_v(char *out, const char *src, size_t num_rows, size_t dim, uint64_t first_row,
+                          unsigned long long *bad_row, hipStream_t stream) {
+  constexpr size_t BPW = (size_t)kWave / (kMxBlock / (16 / sizeof(typename Elem<SRC_DT>::bits)));
+  const size_t nb = mxfp4_blocks(dim), rows_per_pass = nb <= BPW ? BPW / nb : 1;
+  hipLaunchKernelGGL((k_mxfp4_rows<SRC_DT, V>), dim3(grid_for(num_rows, (size_t)(kBlock / kWave) * rows_per_pass)), dim3(kBlock), 0,
+                     stream, out, src, (uint64_t)num_rows, (uint32_t)dim, (uint32_t)rows_per_pass, first_row, bad_row);
+  GGMS_LAUNCH_CHECK();
+  return GGMS_OK;
+}
+
+template <int SRC_DT>
+static int launch_mxfp4(char *out, const char *src, size_t num_rows, size_t dim, uint64_t first_row,
+                        unsigned long long *bad_row, hipStream_t stream) {
+  constexpr size_t SES = sizeof(typename Elem<SRC_DT>::bits);
+  // the widest load (16 bytes at most) that divides a row and suits the base; dim is even and src 4-byte aligned, so an
+  // F16 source never comes down to single elements
+  switch (pick_chunk(dim, (int)(16 / SES), SES, (uintptr_t)src, 1, 0)) {
+    case 2: return launch_mxfp4_v<SRC_DT, 2>(out, src, num_rows, dim, first_row, bad_row, stream);
+    case 4: return launch_mxfp4_v<SRC_DT, 4>(out, src, num_rows, dim, first_row, bad_row, stream);
+    case 8:
+      if constexpr (SES == 2) return launch_mxfp4_v<SRC_DT, 8>(out, src, num_rows, dim, first_row, bad_row, stream);
+      break;
+    case 1:
+      if constexpr (SES == 4) return launch_mxfp4_v<SRC_DT, 1>(out, src, num_rows, dim, first_row, bad_row, stream);
+  }
+  return GGMS_ERR_INVALID;
+}
+
 template <int SRC_DT, int DST_DT>
 static int launch_encode(char *out, const char *src, uint64_t n, hipStream_t stream) {
   constexpr size_t SES = sizeof(typename Elem<SRC_DT>::bits), DES = sizeof(typename Encode<DST_DT>::bits);
@@ -287,16 +403,20 @@ extern "C" int ggms_quantize_rows(void *out, int out_dtype, const void *src, int
                                   uint64_t first_row, uint64_t *bad_row, ggms_stream_t stream) {
   if (!quantiser_reads(src_dtype) || !quantiser_writes(out_dtype) || src_dtype == out_dtype || dim == 0) {
     set_error("quantize_rows: invalid argument: dtype %d -> %d, dim %zu (the source is F32 or F16, the output another "
-              "type of F16, BF16, F8E4M3, F8E5M2 and Q8ROW; rows are not empty)", src_dtype, out_dtype, dim);
+              "type of F16, BF16, F8E4M3, F8E5M2, Q8ROW and MXFP4; rows are not empty)", src_dtype, out_dtype, dim);
+    return GGMS_ERR_INVALID;
+  }
+  if (out_dtype == GGMS_MXFP4 && dim % 2 != 0) {
+    set_error("quantize_rows: invalid argument: an MXFP4 row of dim %zu (dim must be even: two elements share a byte)", dim);
     return GGMS_ERR_INVALID;
   }
   if (num_rows == 0) return GGMS_OK;
   GGMS_CHECK_ARG(out && src);
   GGMS_CHECK_ARG(dim < (1ull << 32));
-  const size_t out_align = out_dtype == GGMS_Q8ROW ? 8 : ggms_dtype_bytes(out_dtype);
+  const size_t out_align = is_row_format(out_dtype) ? 8 : ggms_dtype_bytes(out_dtype);
   if ((uintptr_t)src % 4 != 0 || (uintptr_t)out % out_align != 0) {
     set_error("quantize_rows: invalid argument: src must be 4-byte aligned and out %zu-byte aligned for dtype %d (a Q8ROW "
-              "row ends in an 8-byte scale / bias trailer, written by one store)", out_align, out_dtype);
+              "row ends in an 8-byte scale / bias trailer, written by one store; an MXFP4 row is a multiple of 8 bytes, its blocks 16)", out_align, out_dtype);
     return GGMS_ERR_INVALID;
   }
   char *o = (char *)out;
@@ -306,6 +426,11 @@ extern "C" int ggms_quantize_rows(void *out, int out_dtype, const void *src, int
     unsigned long long *bad = (unsigned long long *)bad_row;
     return src_dtype == GGMS_F32 ? launch_q8row<GGMS_F32>(o, s, num_rows, dim, first_row, bad, st)
                                  : launch_q8row<GGMS_F16>(o, s, num_rows, dim, first_row, bad, st);
+  }
+  if (out_dtype == GGMS_MXFP4) {
+    unsigned long long *bad = (unsigned long long *)bad_row;
+    return src_dtype == GGMS_F32 ? launch_mxfp4<GGMS_F32>(o, s, num_rows, dim, first_row, bad, st)
+                                 : launch_mxfp4<GGMS_F16>(o, s, num_rows, dim, first_row, bad, st);
   }
   const uint64_t n = (uint64_t)num_rows * dim;
 #define GGMS_PAIR(S, D) \

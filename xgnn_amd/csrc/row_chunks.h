@@ -20,7 +20,7 @@ template <> struct ChunkT<1> { using type = uint8_t; };
 // out, converted at store time -- the registers a lane holds between its loads and its first store are the SOURCE
 // chunks only, whichever side is the wider one.
 template <int CB> struct CopyChunk {
-  static constexpr bool kScaled = false; // (ScaledChunk below)
+  static constexpr bool kScaled = false, kBlockScaled = false; // (ScaledChunk, MxChunk below)
   static constexpr int kSrcBytes = CB, kDstBytes = CB;
   using Src = typename ChunkT<CB>::type;
   using Dst = Src;
@@ -30,7 +30,7 @@ template <int CB> struct CopyChunk {
 template <int EPC, int SRC_DT, int DST_DT> struct ConvertChunk {
   using S = Elem<SRC_DT>;
   using D = Elem<DST_DT>;
-  static constexpr bool kScaled = false;
+  static constexpr bool kScaled = false, kBlockScaled = false;
   static constexpr int kSrcBytes = EPC * (int)sizeof(typename S::bits), kDstBytes = EPC * (int)sizeof(typename D::bits);
   using Src = typename VecT<typename S::bits, EPC>::type;
   using Dst = typename VecT<typename D::bits, EPC>::type;
@@ -61,7 +61,7 @@ template <int EPC, int SRC_DT, int DST_DT> struct ConvertChunk {
 // are plain operators in its headers; the pragma takes the licence away for these two operations).
 template <int EPC, int DST_DT> struct ScaledChunk {
   using D = Elem<DST_DT>;
-  static constexpr bool kScaled = true;
+  static constexpr bool kScaled = true, kBlockScaled = false;
   static constexpr int kSrcBytes = EPC, kDstBytes = EPC * (int)sizeof(typename D::bits);
   using Src = typename VecT<uint8_t, EPC>::type;
   using Dst = typename VecT<typename D::bits, EPC>::type;
@@ -81,6 +81,37 @@ template <int EPC, int DST_DT> struct ScaledChunk {
       for (int e = 0; e < EPC; ++e) o[e] = one(v[e], scale, bias);
       return o;
     }
+  }
+};
+
+// A block-scaled 4-bit table (GGMS_MXFP4, include/ggms.h): a row is blocks of 16 code bytes (two E2M1 nibbles a byte,
+// low nibble first), one E8M0 scale byte per block behind them.  The chunk is EPC elements = EPC / 2 code bytes of ONE
+// block (EPC divides 32), so its value needs one more byte: the block's scale, which the sweep loads beside the codes
+// -- it lies mxfp4_scale_offset(dim) + block bytes behind the row pointer the lane holds anyway, and both loads are in
+// flight together (no trailer kept by the resolving lane: a row of 768 elements has 24 scale bytes).  The decode is
+// integer (mxfp4_f32_bits: a shift and an add on the f32 exponent); into BF16 every value has at most 2 significant
+// bits, so the upper half of the f32 is the result (ConvertChunk::kTruncates does the same for FP8).
+// Width: the 16-byte rule below (8 elements into a 16-bit type, 4 into f32: a 4- or 2-byte load, one 16-byte store).
+// 16-element chunks (an 8-byte load, two or four 16-byte stores per lane) were measured against it: into f32 they take
+// twice the time, into bf16 they lose 5 % at dim 128 and win 12 % at dim 768 -- profiles/mxfp4_table_ab.txt.
+template <int EPC, int DST_DT> struct MxChunk {
+  static_assert(EPC == 2 || EPC == 4 || EPC == 8, "2, 4 or 8 elements of one block");
+  using D = Elem<DST_DT>;
+  static constexpr bool kScaled = false, kBlockScaled = true;
+  static constexpr int kSrcBytes = EPC / 2, kDstBytes = EPC * (int)sizeof(typename D::bits);
+  static constexpr uint32_t kChunksPerBlock = kMxBlock / EPC;
+  using Src = typename ChunkT<kSrcBytes>::type;
+  using Dst = typename VecT<typename D::bits, EPC>::type;
+  static __device__ __forceinline__ typename D::bits one(uint32_t code, uint32_t x) {
+    const uint32_t f = mxfp4_f32_bits(code, x);
+    if constexpr (DST_DT == GGMS_BF16) return (typename D::bits)(f >> 16);
+    else return D::from_f32(__builtin_bit_cast(float, f));
+  }
+  static __device__ __forceinline__ Dst convert(Src v, uint32_t x) {
+    Dst o;
+#pragma unroll
+    for (int e = 0; e < EPC; ++e) o[e] = one(((uint32_t)v >> (4 * e)) & 0xfu, x);
+    return o;
   }
 };
 

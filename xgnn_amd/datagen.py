@@ -150,6 +150,7 @@ def write_dataset(path, graph, feat=None, label=None, valid_frac=0.02, test_frac
     arrays: indptr/indices/train_set/test_set/valid_set/cache_by_* uint32, feat row-major, label int64;
     feat_dtype "F8E4M3" / "F8E5M2": feat is a torch.float8_e4m3fn / float8_e5m2 tensor, or its bytes as a uint8 array;
     feat_dtype "Q8ROW": feat is the packed (n, q8row_stride(feat_dim)) uint8 rows of pack_q8row;
+    feat_dtype "MXFP4": feat is the packed (n, mxfp4_stride(feat_dim)) uint8 rows of pack_mxfp4;
     weights (one float per edge) adds prob_table.bin / alias_table.bin / prob_prefix_table.bin.
     train_edges (uint32 positions in indices, each below the edge count) adds train_edge_set.bin, the set a
     link_prediction run shuffles (config key `task`); without it such a run takes every edge.
@@ -202,9 +203,13 @@ def write_dataset(path, graph, feat=None, label=None, valid_frac=0.02, test_frac
             feat = np.asarray(feat)
             assert feat.dtype == np.uint8 and feat.shape == (n, q8row_stride(meta["feat_dim"])), \
                 f"a Q8ROW table is the packed uint8 rows ({n}, {q8row_stride(meta['feat_dim'])}), not {feat.dtype} {feat.shape}"
+        if feat_dtype == "MXFP4":
+            feat = np.asarray(feat)
+            assert feat.dtype == np.uint8 and feat.shape == (n, mxfp4_stride(meta["feat_dim"])), \
+                f"an MXFP4 table is the packed uint8 rows ({n}, {mxfp4_stride(meta['feat_dim'])}), not {feat.dtype} {feat.shape}"
         np.ascontiguousarray(feat).tofile(os.path.join(path, "feat.bin"))
     if edge_feat is not None:
-        assert edge_feat_dtype != "Q8ROW", "edge_feat_dtype: an element type; a row-scaled edge table is not built"
+        assert edge_feat_dtype not in ("Q8ROW", "MXFP4"), "edge_feat_dtype: an element type; a row-scaled edge table is not built"
         if edge_feat_dtype in FP8_FORMATS:
             edge_feat = _fp8_bytes(edge_feat, edge_feat_dtype)
         edge_feat = np.ascontiguousarray(edge_feat)
@@ -480,9 +485,84 @@ def quantize_q8row(values, first_row=0):
     return codes, scale, lo.astype(np.float32)  # (the minimum of F32 / F16 values is an f32 number)
 
 
+# ---- MXFP4: block-scaled 4-bit tables (include/ggms.h: GGMS_MXFP4 = 20) ----------------------------------------------
+# OCP Microscaling FP4.  A row of `dim` elements (dim even) is nb = ceil(dim / 32) blocks of 16 code bytes -- element 2j
+# of a block in the low nibble of its byte j, element 2j + 1 in the high nibble, a partial last block padded with zero
+# nibbles -- then nb E8M0 scale bytes in block order, then zero bytes up to a multiple of 8.  An element is E2M1: sign in
+# bit 3, magnitude MXFP4_MAGNITUDES[code & 7]; value = element x 2^(scale byte - 127); scale byte 255 is NaN.
+MXFP4_BLOCK = 32
+MXFP4_MAGNITUDES = np.array([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0])
+
+
+def mxfp4_stride(dim):
+    """Bytes from one MXFP4 row of `dim` elements to the next (ggms_row_bytes)."""
+    return (17 * ((dim + 31) // 32) + 7) // 8 * 8
+
+
+def pack_mxfp4(codes, scale_bytes):
+    """(n, dim) uint8 E2M1 codes (0 .. 15) + (n, nb) uint8 scale bytes -> the (n, mxfp4_stride(dim)) uint8 rows."""
+    codes, scale_bytes = np.asarray(codes), np.asarray(scale_bytes)
+    assert codes.dtype == np.uint8 and codes.ndim == 2 and codes.shape[1] % 2 == 0, (codes.dtype, codes.shape)
+    n, dim = codes.shape
+    nb = (dim + 31) // 32
+    assert scale_bytes.dtype == np.uint8 and scale_bytes.shape == (n, nb), (scale_bytes.dtype, scale_bytes.shape)
+    padded = np.zeros((n, nb * 32), np.uint8)
+    padded[:, :dim] = codes & 0xF
+    rows = np.zeros((n, mxfp4_stride(dim)), np.uint8)
+    rows[:, :16 * nb] = padded[:, 0::2] | (padded[:, 1::2] << 4)
+    rows[:, 16 * nb:17 * nb] = scale_bytes
+    return rows
+
+
+def unpack_mxfp4(rows, dim):
+    """The inverse of pack_mxfp4: (codes, scale_bytes) of packed rows (copies; pad nibbles and bytes are not looked at)."""
+    rows = np.asarray(rows)
+    assert rows.dtype == np.uint8 and rows.ndim == 2 and rows.shape[1] == mxfp4_stride(dim) and dim % 2 == 0, (rows.dtype, rows.shape, dim)
+    nb = (dim + 31) // 32
+    codes = np.empty((rows.shape[0], nb * 32), np.uint8)
+    codes[:, 0::2] = rows[:, :16 * nb] & 0xF
+    codes[:, 1::2] = rows[:, :16 * nb] >> 4
+    return np.ascontiguousarray(codes[:, :dim]), np.ascontiguousarray(rows[:, 16 * nb:17 * nb])
+
+
+def decode_mxfp4(codes, scale_bytes):
+    """(n, dim) float32 values of unpacked rows: exact for scale bytes 2 .. 252; NaN where the block's byte is 255."""
+    codes, scale_bytes = np.asarray(codes), np.asarray(scale_bytes)
+    x = np.repeat(scale_bytes.astype(np.int64), MXFP4_BLOCK, axis=1)[:, :codes.shape[1]]
+    mag = np.ldexp(MXFP4_MAGNITUDES[codes & 7], x - 127)
+    with np.errstate(over="ignore"):  # (bytes 253 and 254 may overflow: unspecified)
+        return np.where(x == 255, np.nan, np.where(codes & 8, -mag, mag)).astype(np.float32)
+
+
+def quantize_mxfp4(values, first_row=0):
+    """(n, dim) finite F32 / F16 values, dim even -> (codes, scale_bytes), per block of 32 elements (the last one may be
+    partial): scale byte x = clamp(biased f32 exponent of max |v| - 2, 2, 252); code = v x 2^(127 - x) -- exact in
+    float64 -- rounded to the nearest E2M1 magnitude, a tie to the code with an even low bit, above 6 saturated, the sign
+    kept (-0.0 stays -0.0).  A row holding NaN or +-inf is an error that names the row (first_row + its index)."""
+    v32 = np.ascontiguousarray(np.asarray(values).astype(np.float32))
+    assert v32.ndim == 2 and v32.shape[1] % 2 == 0, f"an MXFP4 row has an even number of elements, not {v32.shape}"
+    bad = ~np.isfinite(v32).all(axis=1)
+    if bad.any():
+        raise ValueError(f"quantize_features: row {first_row + int(np.flatnonzero(bad)[0])} holds NaN or inf: a "
+                         "row-scaled table has no code for either")
+    n, dim = v32.shape
+    nb = (dim + 31) // 32
+    bits = np.zeros((n, nb * 32), np.uint32)
+    bits[:, :dim] = v32.view(np.uint32)
+    amax = (bits & 0x7FFFFFFF).reshape(n, nb, 32).max(axis=2)  # (the |bits| of finite values order as the magnitudes do)
+    x = np.clip((amax >> 23).astype(np.int64) - 2, 2, 252)
+    scaled = np.ldexp(np.abs(v32.astype(np.float64)), 127 - np.repeat(x, 32, axis=1)[:, :dim])
+    mid = (MXFP4_MAGNITUDES[:-1] + MXFP4_MAGNITUDES[1:]) / 2  # the 7 ties; the lower code of tie k is k
+    mag = (scaled[..., None] > mid).sum(axis=-1)
+    tie = scaled[..., None] == mid
+    mag = mag + (tie & (np.arange(7) % 2 == 1)).any(axis=-1)  # a tie whose lower code is odd goes up, to the even one
+    return (mag | (bits[:, :dim] >> 28 & 8)).astype(np.uint8), x.astype(np.uint8)
+
+
 def quantize_features(path_in, path_out, fmt, chunk_rows=1 << 20, device=None):
     """Rewrite the F32 / F16 dataset at path_in as the same dataset with an 8-bit feature table at path_out: fmt
-    "Q8ROW" quantises every row to 8-bit codes with the row's own scale and bias (quantize_q8row); for an FP8 feature
+    "Q8ROW" quantises every row to 8-bit codes with the row's own scale and bias (quantize_q8row), "MXFP4" every block of
+    32 elements to 4-bit codes with the block's power-of-two scale (quantize_mxfp4; FEAT_DIM must be even); for an FP8 feature
     table (fmt "F8E4M3" or "F8E5M2"): every other file is linked (or copied where a link is not possible), feat.bin is cast on the
     CPU with torch, round to nearest even, one chunk of rows at a time, and meta.txt names the new FEAT_DATA_TYPE.
     device=None: on the CPU, numpy / torch in float64, as described here.  device="cuda:0" (a torch device string): every
@@ -495,7 +575,7 @@ def quantize_features(path_in, path_out, fmt, chunk_rows=1 << 20, device=None):
     import os
     import shutil
     import torch
-    assert fmt in FP8_FORMATS or fmt == "Q8ROW" or (device is not None and fmt in ("F16", "BF16")), fmt
+    assert fmt in FP8_FORMATS or fmt in ("Q8ROW", "MXFP4") or (device is not None and fmt in ("F16", "BF16")), fmt
     with open(os.path.join(path_in, "meta.txt")) as f:
         meta = [line.split() for line in f if line.strip()]
     kv = dict(meta)
@@ -520,13 +600,16 @@ def quantize_features(path_in, path_out, fmt, chunk_rows=1 << 20, device=None):
         for r in range(0, n, chunk_rows):
             if device is not None:
                 from . import ops
-                out_dtype = ops.Q8ROW if fmt == "Q8ROW" else \
+                out_dtype = ops.Q8ROW if fmt == "Q8ROW" else ops.MXFP4 if fmt == "MXFP4" else \
                     {"F16": torch.float16, "BF16": torch.bfloat16}.get(fmt) or _fp8_torch_dtype(fmt)
                 rows = ops.quantize_rows(torch.from_numpy(np.array(table[r:r + chunk_rows])).to(device), out_dtype, first_row=r)
                 out.write(rows.view(torch.uint8).cpu().numpy().tobytes())
                 continue
             if fmt == "Q8ROW":
                 out.write(pack_q8row(*quantize_q8row(table[r:r + chunk_rows], first_row=r)).tobytes())
+                continue
+            if fmt == "MXFP4":
+                out.write(pack_mxfp4(*quantize_mxfp4(table[r:r + chunk_rows], first_row=r)).tobytes())
                 continue
             v = torch.from_numpy(np.array(table[r:r + chunk_rows])).float()
             if fmt == "F8E4M3":

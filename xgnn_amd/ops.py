@@ -29,6 +29,10 @@ DTYPE_CODE = {
 # GGMS_Q8ROW (include/ggms.h): a ROW format, 8-bit codes with a float32 scale and bias per row.  No torch dtype stands
 # for it: such a table is a torch.uint8 tensor of shape (rows, row_bytes(Q8ROW, dim)) passed with src_dtype=Q8ROW.
 Q8ROW = 18
+# GGMS_MXFP4 (include/ggms.h): a ROW format too, OCP Microscaling FP4 -- 4-bit E2M1 elements, one E8M0 scale byte per 32 of
+# them; a uint8 tensor of (rows, row_bytes(MXFP4, dim)) passed with src_dtype=MXFP4.  dim is even.
+MXFP4 = 20
+_ROW_FORMATS = {Q8ROW: "Q8ROW", MXFP4: "MXFP4"}
 
 
 def _dtype_code(dtype):
@@ -42,9 +46,10 @@ def row_bytes(dtype, dim):
 
 
 def _check_q8row(src, src_dtype, dim):
-    if _dtype_code(src_dtype) == Q8ROW and src is not None:
-        assert src.dtype == torch.uint8 and src.shape[-1] == row_bytes(Q8ROW, dim), \
-            f"a Q8ROW table of dim {dim} is a uint8 tensor of (rows, {row_bytes(Q8ROW, dim)}), not {src.dtype} {tuple(src.shape)}"
+    code = _dtype_code(src_dtype)
+    if code in _ROW_FORMATS and src is not None:
+        assert src.dtype == torch.uint8 and src.shape[-1] == row_bytes(code, dim), \
+            f"a {_ROW_FORMATS[code]} table of dim {dim} is a uint8 tensor of (rows, {row_bytes(code, dim)}), not {src.dtype} {tuple(src.shape)}"
 
 
 KHOP0, KHOP1, WEIGHTED_KHOP, RANDOM_WALK, WEIGHTED_KHOP_PREFIX, KHOP2, WEIGHTED_KHOP_HASH_DEDUP, KHOP3 = range(8)
@@ -829,7 +834,8 @@ def gather_scatter_convert(out, src, src_index, dst_index, num=None, num_dev=Non
                            src_dtype=None):
     """ggms_gather_scatter_convert: out[dst(i), :] = src[src(i) & mask, :] delivered in out's dtype (src and out each
     float16, bfloat16 or float32, src also float8_e4m3fn or float8_e5m2; the same dtype on both sides is the plain
-    gather).  src_dtype=Q8ROW: src is the uint8 (rows, row_bytes(Q8ROW, dim)) tensor of a row-scaled table, dim is out's."""
+    gather).  src_dtype=Q8ROW / MXFP4: src is the uint8 (rows, row_bytes(src_dtype, dim)) tensor of a row-scaled / block-scaled
+    table, dim is out's."""
     _require_gpu(out)
     if num is None:
         num = (src_index if src_index is not None else dst_index).numel()
@@ -868,8 +874,9 @@ def update_rows(table, nodes, grad, rule, lr, eps=1e-10, state=None, num=None, n
 
 def quantize_rows(src, out_dtype, out=None, first_row=0, check=True):
     """ggms_quantize_rows: the 2-D float32 / float16 device tensor `src` encoded into out_dtype -- torch.float16,
-    torch.bfloat16, torch.float8_e4m3fn, torch.float8_e5m2, or Q8ROW (returned as the uint8 (rows, row_bytes(Q8ROW, dim))
-    tensor of a row-scaled table) -- bit for bit what datagen.quantize_features computes on the CPU.  A Q8ROW row that
+    torch.bfloat16, torch.float8_e4m3fn, torch.float8_e5m2, or Q8ROW / MXFP4 (returned as the uint8 (rows, row_bytes(out_dtype,
+    dim)) tensor of a row-scaled / block-scaled table) -- bit for bit what datagen.quantize_features computes on the CPU.  A
+    Q8ROW or MXFP4 row that
     holds NaN or inf has no codes: with check=True the smallest such row (first_row + its index) is read back and raised
     as quantize_q8row raises it; with check=False its output row is zero bytes and nothing is said."""
     _require_gpu(src)
@@ -880,11 +887,11 @@ def quantize_rows(src, out_dtype, out=None, first_row=0, check=True):
         src = src.contiguous()
     code = _dtype_code(out_dtype)
     if out is None:
-        out = torch.empty((rows, row_bytes(Q8ROW, dim)), dtype=torch.uint8, device=src.device) if code == Q8ROW else \
+        out = torch.empty((rows, row_bytes(code, dim)), dtype=torch.uint8, device=src.device) if code in _ROW_FORMATS else \
             torch.empty((rows, dim), dtype=out_dtype, device=src.device)
     assert out.is_contiguous() and out.device == src.device
     bad = None
-    if code == Q8ROW and check:
+    if code in _ROW_FORMATS and check:
         bad = torch.full((1,), -1, dtype=torch.int64, device=src.device)  # UINT64_MAX
     _lib.check(lib().ggms_quantize_rows(_ptr(out), code, _ptr(src), DTYPE_CODE[src.dtype], rows, dim, first_row, _ptr(bad),
                                         _stream()), "ggms_quantize_rows")
@@ -942,7 +949,7 @@ def extract_cached(out, nodes, table, parts_table, num_part, host_feat, num=None
 def extract_cached_convert(out, src_dtype, nodes, table, parts_table, num_part, host_feat, num=None, num_dev=None,
                            num_miss=None):
     """extract_cached with every source (shards, host rows) in `src_dtype` and the rows delivered in out's dtype
-    (src_dtype=Q8ROW: every source is uint8 rows of row_bytes(Q8ROW, dim) bytes)."""
+    (src_dtype=Q8ROW / MXFP4: every source is uint8 rows of row_bytes(src_dtype, dim) bytes)."""
     _require_gpu(out)
     if num is None:
         num = nodes.numel()
@@ -968,8 +975,8 @@ def _feature_tiers(table, replica, parts_table, num_part, my_part, host_feat, ho
 
 def extract_tiered_convert(out, src_dtype, nodes, table, replica, parts_table, num_part, my_part, host_feat, num=None,
                            num_dev=None, tier_rows=None, host_row_mask=0):
-    """extract_tiered with every tier in `src_dtype` and the rows delivered in out's dtype (src_dtype=Q8ROW: every
-    tier is uint8 rows of row_bytes(Q8ROW, dim) bytes)."""
+    """extract_tiered with every tier in `src_dtype` and the rows delivered in out's dtype (src_dtype=Q8ROW / MXFP4: every
+    tier is uint8 rows of row_bytes(src_dtype, dim) bytes)."""
     _require_gpu(out)
     if num is None:
         num = nodes.numel()

@@ -32,7 +32,7 @@ _DT = {0: ("<f4", torch.float32), 1: ("<f8", torch.float64), 2: ("<f2", torch.fl
        7: ("<i2", torch.bfloat16),
        # GGMS_F8E4M3 / GGMS_F8E5M2 (extensions): the OCP 8-bit floats have no typestr either -- bytes, re-viewed
        16: ("|u1", torch.float8_e4m3fn), 17: ("|u1", torch.float8_e5m2)}
-# (GGMS_Q8ROW = 18 is a row format with no element type: never a batch's dtype -- the engine refuses such a table without
+# (GGMS_Q8ROW = 18 and GGMS_MXFP4 = 20 are row formats with no element type: never a batch's dtype -- the engine refuses such a table without
 # feat_out_dtype -- and get_dataset_feat reports the stored rows as uint8 of shape (rows, ggms_row_bytes), code 3)
 _FP8 = (torch.float8_e4m3fn, torch.float8_e5m2)
 
