@@ -252,7 +252,8 @@ enum ggms_sample_type {
   GGMS_KHOP_TYPED = 10, /* an extension: ggms_sample_khop_typed / ggms_sample_batch_typed below */
   GGMS_KHOP_LABOR_WEIGHTED = 11, /* an extension: ggms_sample_khop_labor_weighted / ggms_sample_batch_labor_weighted */
   GGMS_RANDOM_WALK_METAPATH = 12, /* an extension: ggms_sample_walk_metapath / ggms_sample_batch_walk_metapath below */
-  GGMS_KHOP_TYPED_TEMPORAL = 13 /* an extension: ggms_sample_khop_typed_temporal / ggms_sample_batch_typed_temporal */
+  GGMS_KHOP_TYPED_TEMPORAL = 13, /* an extension: ggms_sample_khop_typed_temporal / ggms_sample_batch_typed_temporal */
+  GGMS_PPR_TOPK = 14 /* an extension: ggms_sample_ppr / ggms_sample_batch_ppr below */
 };
 
 /* Workspace of every leaf sampler below but random walk, whose size depends on
@@ -549,6 +550,44 @@ int ggms_sample_walk_metapath(const ggms_graph_t *graph, const uint8_t *edge_typ
                               ggms_id_t *out_data, uint64_t *num_out_dev, void *workspace, size_t workspace_bytes,
                               ggms_stream_t stream);
 
+/* ppr_topk (an extension; the reference has no such sampler; PyG: utils.ppr.get_ppr on the CPU; ShaDow-GNN's PPR
+ * extractor, PPRGo, PinSAGE's importance weights): per seed, the top-K nodes of an approximate personalised PageRank
+ * vector, by a synchronous forward push (Andersen-Chung-Lang) in integer arithmetic -- the quantity that random walk's
+ * visit counts estimate.  The result is a pure function of the inputs, bit for bit.
+ *   inputs      graph: one CSR, unsharded.  input[0 .. num_input).  alpha in [0.05, 0.95], eps in [2^-20, 1], max_nodes C a
+ *               power of two in 64 .. GGMS_PPR_MAX_NODES, max_rounds in 1 .. 255, K in 1 .. 127 with K < C.
+ *   constants   on the host, in double: A = floor(alpha * 65536 + 0.5), E = floor(eps * 2^30); ONE = 2^30.
+ *   state       for seed s a map node -> (r, p) of uint32, starting as {s: (ONE, 0)}.  d(u) = the length of u's list.
+ *   round       at most max_rounds of them:
+ *               1. Act = the nodes u of the map with d(u) >= 1 and (uint64)r[u] >= (uint64)E * d(u), and those with
+ *                  d(u) == 0 and r[u] > 0.  Act empty: stop.
+ *               2. New = the distinct nodes outside the map that occur in the list of some u of Act.  |map| + |New| > C:
+ *                  stop -- the round does not happen, the seed is TRUNCATED (a count of distinct nodes: no order enters).
+ *               3. every u of Act is pushed with the values it had when the round began.  d(u) == 0: p[u] += r[u],
+ *                  r[u] = 0.  Else a = (uint32)(((uint64)A * r[u]) >> 16), q = (r[u] - a) / d(u) (integer division),
+ *                  p[u] += a, r[u] -= a + q * d(u), and r[indices[j]] += q for every position j of u's list (a node new
+ *                  to the map enters it with (0, 0) first).  Parallel edges count once per position, a self-loop is a
+ *                  position like any other.  All adds are integer and follow all reads: their order does not matter.
+ *               sum r + sum p == ONE at all times, so nothing overflows; within the ranges above q >= 51 and a > 0.
+ *   output      per seed, in input order: the nodes u != s with p[u] > 0, by p descending, ties by the smaller node id, cut
+ *               at K; (out_src = s, out_dst = u, out_data = p[u]; p[u] / 2^30 is the PPR mass), compacted over the seeds,
+ *               *num_out_dev = their number; all three hold num_input * K entries.  An input entry equal to
+ *               GGMS_EMPTY_KEY yields nothing.  Equal seeds yield equal output.
+ *   out_stat    optional (NULL: none), two uint32 per input entry: [0] = the rounds performed, bit 31 set if the seed was
+ *               truncated; [1] = sum p.  Both 0 for GGMS_EMPTY_KEY.
+ *   arguments   refused with GGMS_ERR_INVALID and a message naming the argument, before any device call: a sharded graph,
+ *               alpha, eps, max_nodes, max_rounds or K outside its range, a short workspace.  num_input == 0: GGMS_OK,
+ *               *num_out_dev = 0, no kernel is launched.
+ * A seed's whole state lives in the LDS of one workgroup (52 bytes per node of C): GGMS_PPR_MAX_NODES is the largest
+ * power of two that fits gfx950's 160 KB per workgroup.  No allocation, no synchronisation, every size stays on the
+ * device. */
+#define GGMS_PPR_MAX_NODES 2048
+size_t ggms_sample_ppr_workspace_bytes(size_t num_input, size_t K);
+int ggms_sample_ppr(const ggms_graph_t *graph, const ggms_id_t *input, size_t num_input, double alpha, double eps,
+                    size_t max_nodes, size_t max_rounds, size_t K, ggms_id_t *out_src, ggms_id_t *out_dst,
+                    ggms_id_t *out_data, uint64_t *num_out_dev, uint32_t *out_stat, void *workspace,
+                    size_t workspace_bytes, ggms_stream_t stream);
+
 /* ---------------------------------------------------------------------------
  * Ordered hash table -- OrderedHashTable, cuda/cuda_hashtable.h:103-153,
  * cuda/cuda_hashtable.cu:699-1064.  Dedup with contiguous, prefix-stable local
@@ -840,6 +879,26 @@ int ggms_sample_batch_walk_metapath(const ggms_graph_t *graph, const ggms_id_t *
                                     const uint32_t *metapath /* host, metapath_len */, uint32_t metapath_len,
                                     const ggms_sample_extra_t *extra, void *workspace, size_t workspace_bytes,
                                     ggms_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * The PPR batch (an extension): ggms_sample_batch's layers with ppr_topk as the sampler.
+ *   ppr         alpha, eps, max_nodes, max_rounds: ggms_sample_ppr's, the same for every layer.  fanouts[i] = K.
+ *   extra       required: data = HOST array of L device pointers, the scores of every layer (capacities max_edges[i]).
+ *   counts_dev, row, col, both table layouts, the numbering, seeds_distinct: ggms_sample_batch's.  rng_wait / rng_done
+ *   are ignored (stateless).  ggms_sample_batch_seed_ids(GGMS_PPR_TOPK, ...) gives the raw seeds' local ids.
+ *   ggms_sample_batch(GGMS_PPR_TOPK, ...) is GGMS_ERR_INVALID and names this call.  The push's refusals are
+ *   ggms_sample_ppr's.
+ * ------------------------------------------------------------------------- */
+typedef struct {
+  double alpha, eps;
+  uint32_t max_nodes, max_rounds;
+} ggms_ppr_t;
+size_t ggms_sample_batch_ppr_workspace_bytes(size_t num_seeds, const size_t *fanouts, uint32_t num_layer,
+                                             const ggms_sample_extra_t *extra);
+int ggms_sample_batch_ppr(const ggms_graph_t *graph, const ggms_id_t *seeds, size_t num_seeds, const size_t *fanouts,
+                          uint32_t num_layer, ggms_hashtable_t *ht, ggms_id_t *const *row, ggms_id_t *const *col,
+                          uint64_t *counts_dev, const ggms_ppr_t *ppr, const ggms_sample_extra_t *extra, void *workspace,
+                          size_t workspace_bytes, ggms_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * The weighted LABOR batch (an extension): ggms_sample_batch's chain with khop_labor_weighted as the sampler.

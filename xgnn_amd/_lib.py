@@ -37,6 +37,11 @@ class Typed(C.Structure):
     _fields_ = [("edge_type", C.c_void_p), ("num_type", C.c_uint32), ("type_fanout", C.POINTER(C.c_uint32))]
 
 
+class Ppr(C.Structure):
+    """ggms_ppr_t"""
+    _fields_ = [("alpha", C.c_double), ("eps", C.c_double), ("max_nodes", C.c_uint32), ("max_rounds", C.c_uint32)]
+
+
 class TypedTable(C.Structure):
     """ggms_typed_table_t"""
     _fields_ = [("table", C.c_void_p), ("num_rows", C.c_uint64), ("dim", C.c_uint32), ("src_dtype", C.c_int32),
@@ -193,6 +198,13 @@ SYMBOLS = {
     "ggms_sample_batch_walk_metapath": (_i, [C.POINTER(Graph), _vp, _sz, C.POINTER(_sz), _u32, C.POINTER(HashTable),
                                              C.POINTER(_vp), C.POINTER(_vp), _vp, C.POINTER(Typed),
                                              C.POINTER(C.c_uint32), _u32, C.POINTER(SampleExtra), _vp, _sz, _vp]),
+    "ggms_sample_ppr_workspace_bytes": (_sz, [_sz, _sz]),
+    "ggms_sample_ppr": (_i, [C.POINTER(Graph), _vp, _sz, C.c_double, C.c_double, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp,
+                             _vp, _sz, _vp]),
+    "ggms_sample_batch_ppr_workspace_bytes": (_sz, [_sz, C.POINTER(_sz), _u32, C.POINTER(SampleExtra)]),
+    "ggms_sample_batch_ppr": (_i, [C.POINTER(Graph), _vp, _sz, C.POINTER(_sz), _u32, C.POINTER(HashTable),
+                                   C.POINTER(_vp), C.POINTER(_vp), _vp, C.POINTER(Ppr), C.POINTER(SampleExtra), _vp, _sz,
+                                   _vp]),
     "ggms_link_seeds": (_i, [C.POINTER(Graph), _vp, _sz, _u32, _i, _u32, _vp, _vp, _vp]),
     "ggms_link_seeds_typed": (_i, [C.POINTER(Graph), _vp, _vp, _vp, _vp, _u32, _vp, _sz, _u32, _i, _u32, _vp, _vp, _vp,
                                    _vp]),

@@ -186,7 +186,15 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
       fatal(__FILE__, __LINE__, "only arch0 (CPU), arch1 (standalone), arch3 (dedicated), arch4 (dedicated with prefetch), "
                                 "arch5 (factored) and arch6 (SGNN/XGNN) are built; see DESIGN.md");
   }
-  if (!cfg.Walk()) { // operation.cc:150-163
+  if (cfg.Ppr()) { // extension: random walk's num_neighbor = K per layer; the push's own keys are read below
+    long long k = 0;
+    try { k = std::stoll(kv["num_neighbor"]); } catch (...) { k = 0; }
+    if (k < 1 || k > 127)
+      fatal(__FILE__, __LINE__, "num_neighbor = " + kv["num_neighbor"] + ": _sample_type 14 (ppr_topk) keeps the top 1 .. 127 "
+                                "nodes per seed");
+    cfg.num_neighbor = (size_t)k;
+    cfg.fanout.assign(cfg.num_layer, cfg.num_neighbor);
+  } else if (!cfg.Walk()) { // operation.cc:150-163
     SAM_CHECK(kv.count("num_fanout") && kv.count("fanout"), "khop sampling needs num_fanout/fanout");
     size_t nf = std::stoull(kv["num_fanout"]);
     std::stringstream ss(kv["fanout"]);
@@ -231,7 +239,46 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
     cfg.lookahead = 0;
     cfg.pipelines = 1;
   }
-  SAM_CHECK(cfg.sample_type >= GGMS_KHOP0 && cfg.sample_type <= GGMS_KHOP_TYPED_TEMPORAL, "unknown sample type");
+  SAM_CHECK(cfg.sample_type >= GGMS_KHOP0 && cfg.sample_type <= GGMS_PPR_TOPK, "unknown sample type");
+  if (cfg.Ppr()) { // extension: push-based personalised-PageRank neighbourhoods
+    static const char *const arch_names[] = {"arch0", "arch1", "arch2", "arch3", "arch4", "arch5", "arch6", "arch7"};
+    const std::string who = "_sample_type 14 (ppr_topk)";
+    if (cfg.arch != kArch1)
+      fatal(__FILE__, __LINE__, std::string(arch_names[cfg.arch]) + ": " + who + " is not built: the scores ride with "
+                                "arch1's batches only");
+    if (cfg.use_dist_graph)
+      fatal(__FILE__, __LINE__, who + " with use_dist_graph: a seed's push reads ONE CSR, a sharded topology is not built");
+    if (kv.count("exclude_seed_edges") && kv["exclude_seed_edges"] != "none")
+      fatal(__FILE__, __LINE__, who + " with exclude_seed_edges = " + kv["exclude_seed_edges"] + " is not built: its edges "
+                                "join a seed and a node it scored, they are not edges of the graph");
+    const auto number = [&](const char *key, double dflt) {
+      if (!kv.count(key)) return dflt;
+      double v = std::nan("");
+      try {
+        size_t used = 0;
+        v = std::stod(kv[key], &used);
+        if (used != kv[key].size()) v = std::nan("");
+      } catch (...) {}
+      return v;
+    };
+    cfg.ppr_alpha = number("ppr_alpha", 0.15);
+    if (!(cfg.ppr_alpha >= 0.05 && cfg.ppr_alpha <= 0.95))
+      fatal(__FILE__, __LINE__, "ppr_alpha = " + kv["ppr_alpha"] + ": the teleport probability, 0.05 .. 0.95");
+    cfg.ppr_eps = number("ppr_eps", 1e-4);
+    if (!(cfg.ppr_eps >= 1.0 / 1048576.0 && cfg.ppr_eps <= 1.0))
+      fatal(__FILE__, __LINE__, "ppr_eps = " + kv["ppr_eps"] + ": the residual bound per degree, 2^-20 .. 1");
+    const double c = number("ppr_max_nodes", 1024), r = number("ppr_max_rounds", 32);
+    if (!(c >= 64 && c <= GGMS_PPR_MAX_NODES) || c != std::floor(c) || ((uint32_t)c & ((uint32_t)c - 1u)) != 0)
+      fatal(__FILE__, __LINE__, "ppr_max_nodes = " + kv["ppr_max_nodes"] + ": a power of two, 64 .. " +
+                                    std::to_string(GGMS_PPR_MAX_NODES) + " (a seed's state is one workgroup's LDS)");
+    if (!(r >= 1 && r <= 255) || r != std::floor(r))
+      fatal(__FILE__, __LINE__, "ppr_max_rounds = " + kv["ppr_max_rounds"] + ": 1 .. 255 rounds");
+    cfg.ppr_max_nodes = (uint32_t)c;
+    cfg.ppr_max_rounds = (uint32_t)r;
+    if (cfg.num_neighbor >= cfg.ppr_max_nodes)
+      fatal(__FILE__, __LINE__, "num_neighbor = " + kv["num_neighbor"] + " with ppr_max_nodes = " +
+                                    std::to_string(cfg.ppr_max_nodes) + ": the top K are taken from at most ppr_max_nodes nodes");
+  }
   if (cfg.Metapath() && cfg.arch != kArch1) {
     static const char *const arch_names[] = {"arch0", "arch1", "arch2", "arch3", "arch4", "arch5", "arch6", "arch7"};
     fatal(__FILE__, __LINE__, std::string(arch_names[cfg.arch]) + ": _sample_type 12 (random_walk_metapath) is not built: "
@@ -327,6 +374,9 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
     if (cfg.arch != kArch1)
       fatal(__FILE__, __LINE__, std::string(arch_names[cfg.arch]) + ": task = link_prediction is not built: edge seeds, "
                                 "negative sampling and the pair ids run in arch1's sampling chain only");
+    if (cfg.Ppr())
+      fatal(__FILE__, __LINE__, "task = link_prediction with _sample_type 14 (ppr_topk) is not built: the pair ids are the "
+                                "k-hop batch's seed ids");
     if (cfg.Walk())
       fatal(__FILE__, __LINE__, "task = link_prediction with _sample_type " + std::to_string(cfg.sample_type) +
                                     (cfg.Metapath() ? " (random_walk_metapath)" : " (random_walk)") +
@@ -476,6 +526,12 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
     if (!(cfg.random_walk_restart_prob >= 0.0 && cfg.random_walk_restart_prob <= 1.0))
       fatal(__FILE__, __LINE__, "random_walk_restart_prob = " + kv["random_walk_restart_prob"] + ": a probability, 0 .. 1");
   }
+  if (cfg.Ppr()) { // (its keys and its other refusals: above, behind the sample type's range check)
+    if (cfg.inline_heads == 1)
+      fatal(__FILE__, __LINE__, "_sample_type 14 (ppr_topk) with inline_heads = 1: only khop3 reads the list heads; a push "
+                                "walks whole lists");
+    cfg.inline_heads = 0; // auto means off
+  }
   if (cfg.Weighted()) { // extension: weighted sampling without replacement on edge_weight.bin
     const std::string who = "_sample_type 11 (khop_labor_weighted)";
     if (cfg.use_dist_graph)
@@ -508,6 +564,9 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
     if (cfg.use_dist_graph)
       fatal(__FILE__, __LINE__, key + " with use_dist_graph: an edge id is a position in ONE CSR, a sharded topology has "
                                 "none");
+    if (cfg.Ppr())
+      fatal(__FILE__, __LINE__, key + " with _sample_type 14 (ppr_topk) is not built: its edges join a seed and a node it "
+                                "scored, they are not edges of the graph");
     if (cfg.Walk())
       fatal(__FILE__, __LINE__, key + " with _sample_type " + std::to_string(cfg.sample_type) +
                                     (cfg.Metapath() ? " (random_walk_metapath)" : " (random_walk)") +
@@ -1540,7 +1599,7 @@ void Engine::SampleInit(int worker_id, const std::string &ctx) {
   extra_.random_walk_restart_prob = cfg.random_walk_restart_prob;
   extra_.num_random_walk = cfg.num_random_walk;
   // GPURandomStates dist_engine.cc:432-433; seed = wall clock unless the "seed" key is given
-  if (cfg.sample_type == GGMS_KHOP_LABOR || cfg.Timed() || cfg.Typed() || cfg.Weighted() || cfg.Metapath()) { // stateless: their variates are hashes of (node id, salt) -- no RNG pool
+  if (cfg.sample_type == GGMS_KHOP_LABOR || cfg.Timed() || cfg.Typed() || cfg.Weighted() || cfg.Metapath() || cfg.Ppr()) { // stateless: their variates are hashes of (node id, salt), ppr_topk draws nothing -- no RNG pool
     num_states_ = 0;
     states_ = nullptr;
   } else {
@@ -1650,7 +1709,7 @@ void Engine::SampleInit(int worker_id, const std::string &ctx) {
   if (cfg.arch == kArch5) { // the sampler's own batch buffers: it samples into them and packs them into a queue slot
     sbatch_ = std::make_unique<Batch>();
     Batch *b = sbatch_.get();
-    b->sampler.Alloc(max_edges_, max_unique_, max_seeds_, cfg.Walk());
+    b->sampler.Alloc(max_edges_, max_unique_, max_seeds_, cfg.HasData());
     SAM_HIP(hipEventCreateWithFlags(&b->ev_sampled, hipEventDisableTiming));
     SAM_HIP(hipEventCreateWithFlags(&b->ev_done, hipEventDisableTiming));
     QueueMap();
@@ -1707,7 +1766,7 @@ void Engine::Presample() {
   for (uint32_t i = 0; i < row.size(); ++i) {
     SAM_HIP(hipMalloc((void **)&row[i], std::max<size_t>(max_edges_[i], 4) * 4));
     SAM_HIP(hipMalloc((void **)&col[i], std::max<size_t>(max_edges_[i], 4) * 4));
-    if (cfg.Walk()) SAM_HIP(hipMalloc((void **)&dat[i], std::max<size_t>(max_edges_[i], 4) * 4));
+    if (cfg.HasData()) SAM_HIP(hipMalloc((void **)&dat[i], std::max<size_t>(max_edges_[i], 4) * 4));
   }
   uint32_t stamp = 0; // closure k of the presample: stamp k, so `visit` is zeroed once
   for (size_t e = 0; e < cfg.presample_epoch; ++e) {
@@ -1736,6 +1795,10 @@ void Engine::Presample() {
         SAM_GGMS(ggms_sample_batch_walk_metapath(&graph_, d_train + off, size, cfg.fanout.data(), L, &pipes_[0].ht,
                                                  row.data(), col.data(), d_counts, &t, cfg.metapath.data(),
                                                  (uint32_t)cfg.metapath.size(), &extra, ws_, ws_bytes_, stream_));
+      } else if (cfg.Ppr()) {
+        const ggms_ppr_t p{cfg.ppr_alpha, cfg.ppr_eps, cfg.ppr_max_nodes, cfg.ppr_max_rounds};
+        SAM_GGMS(ggms_sample_batch_ppr(&graph_, d_train + off, size, cfg.fanout.data(), L, &pipes_[0].ht, row.data(),
+                                       col.data(), d_counts, &p, &extra, ws_, ws_bytes_, stream_));
       } else
       SAM_GGMS(ggms_sample_batch(cfg.sample_type, &graph_, d_train + off, size, cfg.fanout.data(), L, &pipes_[0].ht,
                                  states_, num_states_, row.data(), col.data(), d_counts, &extra, ws_, ws_bytes_, stream_));
@@ -2035,7 +2098,7 @@ void Engine::TrainInit(int worker_id, const std::string &ctx) {
   for (size_t s = 0; s < nslots; ++s) {
     auto b = std::make_unique<Batch>();
     b->slot = (int)s;
-    b->trainer.Alloc(max_edges_, max_unique_, max_seeds_, cfg.Walk());
+    b->trainer.Alloc(max_edges_, max_unique_, max_seeds_, cfg.HasData());
     if (cfg.typed_feat) { // per-type blocks, every one 16-byte aligned; the T + 1 offsets and their host copy
       typed_feat_bytes_ = ggms_gather_typed_out_bytes(typed_tables_.data(), ds.num_node_type, max_unique_);
       SAM_CHECK(typed_feat_bytes_ > 0, "typed_feat: the batch bound is out of ggms_gather_typed's range");
@@ -2127,7 +2190,7 @@ void Engine::TrainInit(int worker_id, const std::string &ctx) {
     if (BatchSampledElsewhere()) SAM_GGMS(ggms_launch_timer_create(&b->handoff_timer));
     if (Dedicated()) { // the sampler's side of the slot, on the sampler GPU (GetGraphFileCtx, cuda_engine.cc:437-481)
       SAM_HIP(hipSetDevice(device_));
-      b->sampler.Alloc(max_edges_, max_unique_, max_seeds_, cfg.Walk());
+      b->sampler.Alloc(max_edges_, max_unique_, max_seeds_, cfg.HasData());
     } else {
       b->sampler = b->trainer;
     }
@@ -2281,7 +2344,7 @@ void Engine::SampleInto(Batch *b, Pipe &P) {
                                     P.stream));
   }
   if (pipes_.size() > 1 && cfg.sample_type != GGMS_KHOP0 && cfg.sample_type != GGMS_KHOP_LABOR && !cfg.Timed() &&
-      !cfg.Typed() && !cfg.Weighted() && !cfg.Metapath()) {
+      !cfg.Typed() && !cfg.Weighted() && !cfg.Metapath() && !cfg.Ppr()) {
     extra.rng_wait = last_rng_done_;
     extra.rng_done = P.rng_done;
     last_rng_done_ = P.rng_done;
@@ -2330,6 +2393,11 @@ void Engine::SampleInto(Batch *b, Pipe &P) {
     SAM_GGMS(ggms_sample_batch_walk_metapath(&graph_, s.output_nodes, b->num_seeds, cfg.fanout.data(), L, &ht, s.row.data(),
                                              s.col.data(), s.counts_dev, &t, cfg.metapath.data(),
                                              (uint32_t)cfg.metapath.size(), &extra, P.ws, ws_bytes_, P.stream));
+  } else if (cfg.Ppr()) {
+    // the scores land in the batch's data buffers, like a walk's visit counts
+    const ggms_ppr_t p{cfg.ppr_alpha, cfg.ppr_eps, cfg.ppr_max_nodes, cfg.ppr_max_rounds};
+    SAM_GGMS(ggms_sample_batch_ppr(&graph_, s.output_nodes, b->num_seeds, cfg.fanout.data(), L, &ht, s.row.data(),
+                                   s.col.data(), s.counts_dev, &p, &extra, P.ws, ws_bytes_, P.stream));
   } else
     SAM_GGMS(ggms_sample_batch(cfg.sample_type, &graph_, s.output_nodes, b->num_seeds, cfg.fanout.data(), L, &ht, states_,
                                num_states_, s.row.data(), s.col.data(), s.counts_dev, &extra, P.ws, ws_bytes_, P.stream));
@@ -2677,7 +2745,7 @@ void Engine::Finish(Batch *b, Batch *prev) {
   if (BatchSampledElsewhere()) { // what the hand-off (arch5: the unpack) moved and its time
     double us_handoff = 0;       // (DoGraphCopy / DoIdCopy, cuda/cuda_loops.cc:629,653)
     SAM_GGMS(ggms_launch_timer_elapsed_us(b->handoff_timer, &us_handoff));
-    const double per_edge = cfg.Walk() ? 12.0 : 8.0; // row + col (+ data)
+    const double per_edge = cfg.HasData() ? 12.0 : 8.0; // row + col (+ data)
     prof.LogStep(b->key, 12 /*kLogL1GraphBytes*/, edges * per_edge);
     prof.LogStep(b->key, 11 /*kLogL1IdBytes*/, (b->num_input + b->num_seeds) * 4.0);
     prof.LogStep(b->key, 22 /*kLogL2GraphCopyTime*/, us_handoff * 1e-6);

@@ -151,6 +151,14 @@ struct RunConfig {
   std::vector<uint32_t> metapath;
   bool Metapath() const { return sample_type == GGMS_RANDOM_WALK_METAPATH; }
   bool Walk() const { return sample_type == GGMS_RANDOM_WALK || Metapath(); }
+  // extension (`_sample_type` 14 = ppr_topk, config keys `ppr_alpha`, `ppr_eps`, `ppr_max_nodes`, `ppr_max_rounds`; arch1,
+  // one CSR, node_classification): every layer is the top num_neighbor nodes of each seed's pushed PPR vector
+  // (ggms_sample_batch_ppr); num_neighbor and num_layer as for random walk.  HasData(): a uint32 per edge rides with the
+  // batch (visit counts or PPR scores), handed out by samgraph_get_graph_data
+  double ppr_alpha = 0.15, ppr_eps = 1e-4;
+  uint32_t ppr_max_nodes = 1024, ppr_max_rounds = 32;
+  bool Ppr() const { return sample_type == GGMS_PPR_TOPK; }
+  bool HasData() const { return Walk() || Ppr(); }
   // extension (config keys `induced_subgraph` = on, `induced_max_edges`; arch1, one CSR, not khop2 / khop_temporal, no
   // exclude_seed_edges): every batch also carries the subgraph its input nodes induce -- every edge of the graph with
   // both ends among them, one COO over the batch's local ids with the edges' CSR positions (ggms_induced_edges behind

@@ -104,6 +104,10 @@ struct SampleLayer {
   // num_type with khop_typed, walk_length (the traversals) / num_walk / restart_prob / out_data with random walk, salt
   const uint32_t *metapath = nullptr;
   uint32_t metapath_len = 0;
+  // ppr_topk: A, E, max_nodes, max_rounds (ppr_set); the per-seed stats (leaf, may be NULL).  `fanout` is K; shares out_data
+  // with random walk
+  uint32_t ppr_a = 0, ppr_e = 0, ppr_nodes = 0, ppr_rounds = 0;
+  uint32_t *out_stat = nullptr;
 };
 
 // sample_khop.hip
@@ -126,6 +130,12 @@ int walk_topk_impl(const SampleLayer &l, uint32_t *tmp_src, uint32_t *tmp_dst, u
 int walk_metapath_check(uint32_t num_type, const uint32_t *metapath, uint32_t metapath_len, size_t num_traversal,
                         double restart_prob, size_t num_walk, size_t K, const char *who); // the refusals of include/ggms.h
 int sample_walk_metapath_impl(const SampleLayer &l);
+
+// sample_ppr.hip
+size_t ppr_ws_words(size_t num_input, size_t K);
+int ppr_check(double alpha, double eps, size_t max_nodes, size_t max_rounds, size_t K, const char *who); // the refusals of include/ggms.h
+void ppr_set(SampleLayer &l, double alpha, double eps, size_t max_nodes, size_t max_rounds);            // A, E, C, rounds
+int sample_ppr_impl(const SampleLayer &l);
 
 // sample_labor.hip
 size_t labor_ws_words(size_t num_input);

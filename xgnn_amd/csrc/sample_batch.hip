@@ -81,6 +81,7 @@ size_t layer_ws_words(int type, size_t n, size_t fanout, size_t walk_length, siz
   case GGMS_KHOP_LABOR:
   case GGMS_KHOP_LABOR_WEIGHTED: return labor_ws_words(n);
   case GGMS_KHOP_TEMPORAL: return temporal_ws_words(n);
+  case GGMS_PPR_TOPK: return ppr_ws_words(n, fanout);
   default: return sample_ws_words(n); // khop3, khop2, weighted_khop_hash_dedup
   }
 }
@@ -106,6 +107,7 @@ static int layer_shape_check(int type, const SampleLayer &l) {
                                        l.fanout, "random_walk_metapath");
     if (rc != GGMS_OK) return rc;
   }
+  if (type == GGMS_PPR_TOPK) GGMS_CHECK_ARG(l.fanout <= 127 && l.ppr_nodes >= 64 && l.fanout < l.ppr_nodes); // ppr_check's
   // "this algorithm not support DistGraph engine", dist_loops.cc:167-228
   if (type != GGMS_KHOP3 && type != GGMS_KHOP0 && type != GGMS_RANDOM_WALK && type != GGMS_KHOP_LABOR)
     GGMS_CHECK_ARG(l.graph->num_part == 0);
@@ -118,8 +120,10 @@ static int layer_check(int type, const SampleLayer &l, size_t num_states) {
   if (rc != GGMS_OK) return rc;
   const uint64_t n = l.n_max;
   if (type == GGMS_KHOP1 || type == GGMS_KHOP2 || type == GGMS_KHOP_TEMPORAL || type == GGMS_KHOP_TYPED ||
-      type == GGMS_KHOP_LABOR_WEIGHTED || type == GGMS_RANDOM_WALK_METAPATH || type == GGMS_KHOP_TYPED_TEMPORAL)
+      type == GGMS_KHOP_LABOR_WEIGHTED || type == GGMS_RANDOM_WALK_METAPATH || type == GGMS_KHOP_TYPED_TEMPORAL ||
+      type == GGMS_PPR_TOPK)
     GGMS_CHECK_ARG(l.graph->indptr && l.graph->indices);
+  if (type == GGMS_PPR_TOPK) GGMS_CHECK_ARG(l.out_data);
   if (type == GGMS_RANDOM_WALK_METAPATH) GGMS_CHECK_ARG(l.edge_type && l.out_data);
   if (type == GGMS_KHOP_TYPED || type == GGMS_KHOP_TYPED_TEMPORAL) GGMS_CHECK_ARG(l.edge_type && l.out_pos && l.out_type);
   if (type == GGMS_KHOP_TEMPORAL || type == GGMS_KHOP_TYPED_TEMPORAL)
@@ -135,7 +139,8 @@ static int layer_check(int type, const SampleLayer &l, size_t num_states) {
   case GGMS_KHOP_TYPED:
   case GGMS_KHOP_TYPED_TEMPORAL:
   case GGMS_KHOP_LABOR_WEIGHTED:
-  case GGMS_RANDOM_WALK_METAPATH: return GGMS_OK; // stateless
+  case GGMS_RANDOM_WALK_METAPATH:
+  case GGMS_PPR_TOPK: return GGMS_OK; // stateless
   case GGMS_KHOP3: GGMS_CHECK_ARG(l.states && (n + 127) / 128 * 8 <= num_states); return GGMS_OK; // khop3.cu:89
   case GGMS_KHOP2:                                                                                   // khop2.cu:57
   case GGMS_WEIGHTED_KHOP_HASH_DEDUP: // hash_dedup.cu:70
@@ -163,6 +168,7 @@ static int sample_layer(int type, const SampleLayer &l) {
   case GGMS_RANDOM_WALK: return sample_random_walk_impl(l);
   case GGMS_RANDOM_WALK_METAPATH: return sample_walk_metapath_impl(l);
   case GGMS_KHOP_LABOR: return sample_khop_labor_impl(l);
+  case GGMS_PPR_TOPK: return sample_ppr_impl(l);
   case GGMS_KHOP_TEMPORAL: return sample_khop_temporal_impl(l);
   case GGMS_KHOP_TYPED: return sample_khop_typed_impl(l);
   case GGMS_KHOP_TYPED_TEMPORAL: return sample_khop_typed_temporal_impl(l);
@@ -179,9 +185,10 @@ static int sample_layer(int type, const SampleLayer &l) {
 // the lane that held the key, after a search that is all ballots -- a returning atomic per edge there would serialise
 // behind the search of the seed's whole wave, and the sampler stays a pure function of its inputs.
 // khop_temporal, khop_typed, khop_typed_temporal and khop_labor_weighted are khop_labor's selection: the same holds.
+// ppr_topk's output leaves through a tile scan's emit, one lane per seed: K dependent atomics per lane there, not tried.
 static bool layer_enters_output(int type) {
   return type != GGMS_KHOP2 && type != GGMS_KHOP_LABOR && type != GGMS_KHOP_TEMPORAL && type != GGMS_KHOP_TYPED &&
-         type != GGMS_KHOP_LABOR_WEIGHTED && type != GGMS_KHOP_TYPED_TEMPORAL;
+         type != GGMS_KHOP_LABOR_WEIGHTED && type != GGMS_KHOP_TYPED_TEMPORAL && type != GGMS_PPR_TOPK;
 }
 
 // a leaf entry point: shape checks; nothing to sample -> a zero count (null pointers allowed); pointers, workspace and
@@ -195,7 +202,7 @@ int sample_leaf(int type, SampleLayer l, size_t num_states, size_t workspace_byt
     return GGMS_OK;
   }
   const bool walk = type == GGMS_RANDOM_WALK || type == GGMS_RANDOM_WALK_METAPATH;
-  GGMS_CHECK_ARG(l.input && l.out_src && l.out_dst && l.workspace && (!walk || l.out_data));
+  GGMS_CHECK_ARG(l.input && l.out_src && l.out_dst && l.workspace && ((!walk && type != GGMS_PPR_TOPK) || l.out_data));
   GGMS_CHECK_ARG(workspace_bytes >=
                  layer_ws_words(type, l.n_max, l.fanout, l.walk_length, l.num_walk, l.num_type) * sizeof(uint32_t));
   // 32-bit output positions; a random walk's are bounded by walk_length * num_walk < 2^31 instead
@@ -339,14 +346,15 @@ struct MetapathBatch {
 };
 
 // the body of ggms_sample_batch, ggms_sample_batch_prefetch, ggms_sample_batch_temporal, ggms_sample_batch_typed,
-// ggms_sample_batch_labor_weighted, ggms_sample_batch_walk_metapath and ggms_sample_batch_typed_temporal (tb and yb
-// together); every argument check is the caller's
+// ggms_sample_batch_labor_weighted, ggms_sample_batch_walk_metapath, ggms_sample_batch_typed_temporal (tb and yb
+// together) and ggms_sample_batch_ppr (pb); every argument check is the caller's
 static int sample_batch_impl(int sample_type, const ggms_graph_t *graph, const ggms_id_t *seeds, size_t num_seeds,
                              const size_t *fanouts, uint32_t num_layer, ggms_hashtable_t *ht, void *states,
                              size_t num_states, ggms_id_t *const *row, ggms_id_t *const *col, uint64_t *counts_dev,
                              const ggms_sample_extra_t *extra, void *workspace, const Prefetch *pf, hipStream_t s,
                              const TemporalBatch *tb = nullptr, const TypedBatch *yb = nullptr,
-                             const WeightedBatch *wb = nullptr, const MetapathBatch *mb = nullptr) {
+                             const WeightedBatch *wb = nullptr, const MetapathBatch *mb = nullptr,
+                             const ggms_ppr_t *pb = nullptr) {
   const BatchCaps c = caps_of(num_seeds, fanouts, num_layer);
   // what every layer's sampler call shares; the loop below fills in the rest
   SampleLayer L{graph, nullptr, 0, 0, nullptr, nullptr, nullptr, (uint32_t *)states, nullptr, s};
@@ -360,8 +368,13 @@ static int sample_batch_impl(int sample_type, const ggms_graph_t *graph, const g
   // a stateless sampler has nothing to order between batches
   const bool ordered_rng = sample_type != GGMS_KHOP_LABOR && sample_type != GGMS_KHOP_TEMPORAL &&
                            sample_type != GGMS_KHOP_TYPED && sample_type != GGMS_KHOP_LABOR_WEIGHTED &&
-                           sample_type != GGMS_RANDOM_WALK_METAPATH && sample_type != GGMS_KHOP_TYPED_TEMPORAL;
+                           sample_type != GGMS_RANDOM_WALK_METAPATH && sample_type != GGMS_KHOP_TYPED_TEMPORAL &&
+                           sample_type != GGMS_PPR_TOPK;
   const bool walk = sample_type == GGMS_RANDOM_WALK || sample_type == GGMS_RANDOM_WALK_METAPATH;
+  if (pb) {
+    ppr_set(L, pb->alpha, pb->eps, pb->max_nodes, pb->max_rounds);
+    L.out_data = extra->data[0]; // layer_check's non-null test; every layer sets its own below
+  }
   if (mb) {
     L.edge_type = mb->t->edge_type;
     L.num_type = mb->t->num_type;
@@ -544,7 +557,7 @@ static int sample_batch_impl(int sample_type, const ggms_graph_t *graph, const g
       L.insert = inserted ? &di : nullptr;
       L.first = first && fuse_seeds ? &first_layer : nullptr;
       L.enter = first && khop0_enters ? &seed_enter : nullptr;
-      if (walk) L.out_data = extra->data[i];
+      if (walk || pb) L.out_data = extra->data[i];
       if (tb) L.out_pos = tb->eid[i];
       if (wb) L.out_pos = wb->eid[i];
       if (yb) {
@@ -627,6 +640,11 @@ int ggms_sample_batch(int sample_type, const ggms_graph_t *graph, const ggms_id_
               "ggms_sample_batch_walk_metapath", sample_type);
     return GGMS_ERR_INVALID;
   }
+  if (sample_type == GGMS_PPR_TOPK) {
+    set_error("ggms_sample_batch: sample type %d (ppr_topk) takes the push's parameters (ggms_ppr_t): call "
+              "ggms_sample_batch_ppr", sample_type);
+    return GGMS_ERR_INVALID;
+  }
   if (sample_type == GGMS_KHOP_TYPED_TEMPORAL) {
     set_error("ggms_sample_batch: sample type %d (khop_typed_temporal) takes edge types, edge times, seed times, a cut "
               "table and a fanout per type and layer: call ggms_sample_batch_typed_temporal", sample_type);
@@ -650,7 +668,7 @@ int ggms_sample_batch_seed_ids(int sample_type, size_t num_seeds, const size_t *
                                const ggms_sample_extra_t *extra, const void *workspace, const ggms_id_t **seed_ids_dev) {
   GGMS_CHECK_ARG(fanouts && workspace && seed_ids_dev);
   GGMS_CHECK_ARG(num_layer >= 1 && num_layer <= 16);
-  GGMS_CHECK_ARG(sample_type >= GGMS_KHOP0 && sample_type <= GGMS_KHOP_TYPED_TEMPORAL);
+  GGMS_CHECK_ARG(sample_type >= GGMS_KHOP0 && sample_type <= GGMS_PPR_TOPK);
   const BatchCaps c = caps_of(num_seeds, fanouts, num_layer);
   const BatchLayout lay = layout_of(sample_type, num_seeds, fanouts, num_layer, c, extra);
   const uint32_t *w = (const uint32_t *)(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
@@ -842,6 +860,45 @@ int ggms_sample_batch_walk_metapath(const ggms_graph_t *graph, const ggms_id_t *
   const MetapathBatch mb{t, metapath, metapath_len};
   return sample_batch_impl(GGMS_RANDOM_WALK_METAPATH, graph, seeds, num_seeds, fanouts, num_layer, ht, nullptr, 0, row, col,
                            counts_dev, extra, workspace, nullptr, to_stream(stream), nullptr, nullptr, nullptr, &mb);
+}
+
+// ---- ppr_topk: the batch with the push's parameters ------------------------------------------------------------------
+size_t ggms_sample_batch_ppr_workspace_bytes(size_t num_seeds, const size_t *fanouts, uint32_t num_layer,
+                                             const ggms_sample_extra_t *extra) {
+  return ggms_sample_batch_workspace_bytes(GGMS_PPR_TOPK, num_seeds, fanouts, num_layer, extra);
+}
+
+int ggms_sample_batch_ppr(const ggms_graph_t *graph, const ggms_id_t *seeds, size_t num_seeds, const size_t *fanouts,
+                          uint32_t num_layer, ggms_hashtable_t *ht, ggms_id_t *const *row, ggms_id_t *const *col,
+                          uint64_t *counts_dev, const ggms_ppr_t *ppr, const ggms_sample_extra_t *extra, void *workspace,
+                          size_t workspace_bytes, ggms_stream_t stream) {
+  static const char *const who = "ggms_sample_batch_ppr";
+  GGMS_CHECK_ARG(graph && fanouts && ht && row && col && counts_dev && ppr);
+  GGMS_CHECK_ARG(num_layer >= 1 && num_layer <= 16);
+  if (graph->num_part != 0) {
+    set_error("%s: num_part %u: a seed's push reads ONE CSR, the call takes unsharded graphs only", who, graph->num_part);
+    return GGMS_ERR_INVALID;
+  }
+  if (!extra || !extra->data) {
+    set_error("%s: extra is required: data, the scores of every layer", who);
+    return GGMS_ERR_INVALID;
+  }
+  for (uint32_t i = 0; i < num_layer; ++i) { // fanouts[i] = K of layer i
+    const int rc = ppr_check(ppr->alpha, ppr->eps, ppr->max_nodes, ppr->max_rounds, fanouts[i], who);
+    if (rc != GGMS_OK) return rc;
+  }
+  GGMS_CHECK_ARG(num_seeds == 0 || seeds);
+  for (uint32_t i = 0; i < num_layer; ++i) GGMS_CHECK_ARG(row[i] && col[i] && extra->data[i]);
+  if (!workspace || workspace_bytes < ggms_sample_batch_ppr_workspace_bytes(num_seeds, fanouts, num_layer, extra)) {
+    set_error("%s: workspace_bytes %zu, ggms_sample_batch_ppr_workspace_bytes gives %zu", who, workspace_bytes,
+              ggms_sample_batch_ppr_workspace_bytes(num_seeds, fanouts, num_layer, extra));
+    return GGMS_ERR_INVALID;
+  }
+  const BatchCaps c = caps_of(num_seeds, fanouts, num_layer);
+  GGMS_CHECK_ARG(c.max_input[0] + c.max_edges[0] <= ht->n2o_size);
+  GGMS_CHECK_ARG(c.max_input[0] + c.max_edges[0] < (1ull << 32) - 4); // indices and 2 + local id fit 32 bits
+  return sample_batch_impl(GGMS_PPR_TOPK, graph, seeds, num_seeds, fanouts, num_layer, ht, nullptr, 0, row, col, counts_dev,
+                           extra, workspace, nullptr, to_stream(stream), nullptr, nullptr, nullptr, nullptr, ppr);
 }
 
 // ---- arch4: the prefetching batch ----------------------------------------------------------------------------------

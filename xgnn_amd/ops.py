@@ -62,9 +62,11 @@ KHOP_LABOR_WEIGHTED = 11  # an extension: weighted sampling without replacement,
 RANDOM_WALK_METAPATH = 12  # an extension: PinSAGE's walks along a relation path (include/ggms.h)
 MAX_METAPATH = 8  # GGMS_MAX_METAPATH
 KHOP_TYPED_TEMPORAL = 13  # an extension: a fanout per edge type before a per-seed cut-off time (include/ggms.h)
+PPR_TOPK = 14  # an extension: the top-K of a pushed personalised-PageRank vector per seed (include/ggms.h)
+PPR_MAX_NODES = 2048  # GGMS_PPR_MAX_NODES
 # samplers without an RNG pool
 _STATELESS = (KHOP0, KHOP_LABOR, KHOP_TEMPORAL, KHOP_TYPED, KHOP_LABOR_WEIGHTED, RANDOM_WALK_METAPATH,
-              KHOP_TYPED_TEMPORAL)
+              KHOP_TYPED_TEMPORAL, PPR_TOPK)
 
 
 def _require_gpu(t):
@@ -687,6 +689,25 @@ def sample_walk_metapath(graph, edge_type, num_type, metapath, inp, num_traversa
                                           _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), _ptr(num_out), _ptr(ws),
                                           ws.numel() * 4, _stream()), "ggms_sample_walk_metapath")
     return outs[0], outs[1], outs[2], num_out
+
+
+def sample_ppr(graph, inp, alpha, eps, max_nodes, max_rounds, K):
+    """ggms_sample_ppr: per seed, a forward push of its personalised-PageRank vector in integer arithmetic (teleport
+    `alpha`, residual bound `eps` per degree, at most `max_nodes` nodes and `max_rounds` rounds); the K highest-scored
+    nodes per seed.  Returns (out_src, out_dst, out_data = scores, a score / 2^30 is the PPR mass, num_out[1] on device,
+    stat (n, 2): rounds with the truncated flag in bit 31, and sum p)."""
+    _require_gpu(inp)
+    _i32(inp)
+    n = inp.numel()
+    dev = inp.device
+    outs = [torch.empty(max(1, n * K), dtype=torch.int32, device=dev) for _ in range(3)]
+    num_out = torch.zeros(1, dtype=torch.int64, device=dev)
+    stat = torch.zeros((n, 2), dtype=torch.int32, device=dev)
+    ws = _workspace(lib().ggms_sample_ppr_workspace_bytes(n, K), dev)
+    check(lib().ggms_sample_ppr(C.byref(graph.c), _ptr(inp), n, alpha, eps, max_nodes, max_rounds, K, _ptr(outs[0]),
+                                _ptr(outs[1]), _ptr(outs[2]), _ptr(num_out), _ptr(stat), _ptr(ws), ws.numel() * 4,
+                                _stream()), "ggms_sample_ppr")
+    return outs[0], outs[1], outs[2], num_out, stat
 
 
 class OrderedHashTable:
@@ -1649,6 +1670,43 @@ class WalkMetapathBatchSampler(_BatchBuffers):
     def result(self):
         """Sync and slice the outputs: BatchSampler.result()'s, each layer with its visit counts `data`."""
         c, layers = self._sliced("ggms_sample_batch_walk_metapath")
+        for i, lay in enumerate(layers):
+            lay["data"] = self.data[i][:c[COUNT_EDGES(i)]]
+        return dict(layers=layers, input_nodes=self.ht.n2o[:c[COUNT_INPUT(self.L)]])
+
+
+class PprBatchSampler(_BatchBuffers):
+    """ggms_sample_batch_ppr: BatchSampler's layers with ppr_topk as the sampler: every layer keeps the K highest-scored
+    nodes of each frontier node's pushed PPR vector.  One slot, one pipeline."""
+
+    def __init__(self, graph, num_layer, K, alpha, eps, max_nodes, max_rounds, batch_size, device="cuda",
+                 direct_table=True, max_seeds=None):
+        self._init_capacity(graph, [int(K)] * num_layer, PPR_TOPK,
+                            int(batch_size * 1.25) + 1 if max_seeds is None else int(max_seeds), None, None)
+        self._ppr = _lib.Ppr(alpha, eps, max_nodes, max_rounds)
+        self.ht = OrderedHashTable(self.max_unique, device, num_node=graph.c.num_node if direct_table else None)
+        self.states = None
+        (self.row, self._rows), (self.col, self._cols) = self._layer_buffers(1, device), self._layer_buffers(1, device)
+        self.data, self._datas = self._layer_buffers(1, device)
+        self.counts = torch.zeros(COUNTS_SAMPLE_WORDS(self.L), dtype=torch.int64, device=device)
+        self._extra.data = C.cast(self._datas, C.c_void_p)
+        self.ws = _workspace(lib().ggms_sample_batch_ppr_workspace_bytes(self.max_seeds, self._f, self.L,
+                                                                         C.byref(self._extra)), device)
+
+    def sample(self, seeds, distinct=False):
+        """Enqueue one batch; distinct: the caller promises pairwise distinct seeds (ggms_sample_extra_t.seeds_distinct)."""
+        _i32(seeds)
+        n = seeds.numel()
+        assert n <= self.max_seeds
+        self._extra.seeds_distinct = 1 if distinct else 0
+        check(lib().ggms_sample_batch_ppr(C.byref(self.graph.c), _ptr(seeds), n, self._f, self.L, C.byref(self.ht.c),
+                                          self._rows, self._cols, _ptr(self.counts), C.byref(self._ppr),
+                                          C.byref(self._extra), _ptr(self.ws), self.ws.numel() * 4, _stream()),
+              "ggms_sample_batch_ppr")
+
+    def result(self):
+        """Sync and slice the outputs: BatchSampler.result()'s, each layer with its scores `data`."""
+        c, layers = self._sliced("ggms_sample_batch_ppr")
         for i, lay in enumerate(layers):
             lay["data"] = self.data[i][:c[COUNT_EDGES(i)]]
         return dict(layers=layers, input_nodes=self.ht.n2o[:c[COUNT_INPUT(self.L)]])
