@@ -253,7 +253,8 @@ enum ggms_sample_type {
   GGMS_KHOP_LABOR_WEIGHTED = 11, /* an extension: ggms_sample_khop_labor_weighted / ggms_sample_batch_labor_weighted */
   GGMS_RANDOM_WALK_METAPATH = 12, /* an extension: ggms_sample_walk_metapath / ggms_sample_batch_walk_metapath below */
   GGMS_KHOP_TYPED_TEMPORAL = 13, /* an extension: ggms_sample_khop_typed_temporal / ggms_sample_batch_typed_temporal */
-  GGMS_PPR_TOPK = 14 /* an extension: ggms_sample_ppr / ggms_sample_batch_ppr below */
+  GGMS_PPR_TOPK = 14, /* an extension: ggms_sample_ppr / ggms_sample_batch_ppr below */
+  GGMS_KHOP_BUDGET = 15 /* an extension: ggms_sample_khop_budget / ggms_sample_batch_budget below */
 };
 
 /* Workspace of every leaf sampler below but random walk, whose size depends on
@@ -430,6 +431,51 @@ int ggms_sample_khop_labor_weighted(const ggms_graph_t *graph, const float *edge
                                     size_t num_input, size_t fanout, uint32_t layer_salt, ggms_id_t *out_src,
                                     ggms_id_t *out_dst, ggms_id_t *out_pos, uint64_t *num_out_dev, void *workspace,
                                     size_t workspace_bytes, ggms_stream_t stream);
+
+/* khop_budget (an extension; the reference has no such sampler; FastGCN, LADIES -- DGL ships a LADIES example --, PyG's
+ * HGTLoader / HGSampling): LAYER-wise importance sampling.  A layer draws at most `budget` nodes for the whole
+ * frontier, a candidate's chance grows with how much of the frontier points at it, and the frontier keeps its edges
+ * into the chosen set -- a seed at most `fanout` of them, so a layer has at most num_input * fanout edges like every
+ * other sampler here and at most `budget` new nodes.  With fanout >= the largest degree the result is exactly LADIES.
+ *   seeds       u_0 .. u_{n-1} with degrees d_i; a seed that repeats is an independent seed and contributes again
+ *   contribution of seed i to every entry of its list: GGMS_BUDGET_UNIFORM c_i = 1; GGMS_BUDGET_LADIES (the squared
+ *               row-normalised adjacency, sum of 1 / d^2) c_i = max(1, floor(2^40 / d_i^2)) for d_i < 2^20, else 1
+ *   weight      W_t = the uint64 sum of c_i over every list entry (i, p) with indices[p] == t (parallel edges count
+ *               each time; integer adds: the sum does not depend on the order).  The candidates are the M distinct t
+ *               with W_t >= 1.  n < 2^22 keeps every sum below 2^62
+ *   key         E(t) = khop_labor_weighted's variate E of fmix32(t ^ layer_salt) (the same 257-entry table);
+ *               key32 = the bits of float32(E) / float32(W_t), both conversions round-to-nearest-even from uint64, ONE
+ *               correctly rounded binary32 division; key = (key32 << 32) | t -- distinct because the t are
+ *   chosen      every candidate if M <= budget, else the `budget` candidates with the smallest keys (Efraimidis-Spirakis:
+ *               with budget 1, t is chosen with probability W_t / sum of W)
+ *   edges       of seed i: among its list positions p whose neighbour is chosen, the min(fanout, eligible) with the
+ *               smallest (key32(indices[p]) << 32) | p (parallel edges tie on key32 and break by position)
+ *   output      seeds in input order, within a seed ascending position; out_src / out_dst as khop_labor writes them,
+ *               out_pos[k] = the edge's position in graph->indices; *num_out_dev = the edge count; stat_dev (may be
+ *               NULL) = {M, number chosen}, two device uint64.  All three arrays hold num_input * fanout entries.
+ *   map         caller-owned, one uint64 per node id, ZERO between calls (ggms_budget_map_init once); the call sums
+ *               the weights there, marks the chosen and puts every word it touched back to zero
+ *   workspace   ggms_sample_khop_budget_workspace_bytes(num_input, fanout, num_edge): the layer's own part and a
+ *               candidate list of 8 bytes per distinct neighbour.  num_edge = indptr[num_node] always bounds their
+ *               number; any smaller bound a caller knows (num_node) may be passed instead.  A list that still
+ *               overflows sets GGMS_STATUS_TABLE_FULL (the result is invalid and the map must be initialised again)
+ *   arguments   refused by name with GGMS_ERR_INVALID before any device call: a sharded graph, budget 0, fanout 0 or
+ *               >= 128, an unknown mode, num_input >= 2^22, a null array, a short workspace; num_edge >= 2^32 - 1 makes
+ *               the workspace size 0.  What the host cannot see is caught on the device: a frontier whose list entries
+ *               total 2^32 or more (only repeated seeds can exceed the graph's own edge count) is not walked -- the
+ *               call sets GGMS_STATUS_TABLE_FULL and delivers zero edges, M = chosen = 0, the map untouched.
+ * Stateless: a pure function of (graph, input, budget, fanout, mode, layer_salt).  No allocation, no synchronisation,
+ * every size -- M and the selection's ranks among them -- stays on the device; the number of launches depends on
+ * num_node alone. */
+#define GGMS_BUDGET_UNIFORM 0
+#define GGMS_BUDGET_LADIES 1
+int ggms_budget_map_init(uint64_t *map, size_t num_node, ggms_stream_t stream);
+size_t ggms_sample_khop_budget_workspace_bytes(size_t num_input, size_t fanout, uint64_t num_edge);
+int ggms_sample_khop_budget(const ggms_graph_t *graph, const ggms_id_t *input, size_t num_input, size_t budget,
+                            size_t fanout, int mode, uint32_t layer_salt, uint64_t *map, ggms_id_t *out_src,
+                            ggms_id_t *out_dst, ggms_id_t *out_pos, uint64_t *num_out_dev,
+                            uint64_t *stat_dev /* M, chosen; may be NULL */, void *workspace, size_t workspace_bytes,
+                            ggms_stream_t stream);
 
 /* GPUSampleWeightedKHopPrefix, cuda/cuda_sampling_weighted_khop_prefix.cu:145-246:
  * prob_prefix_table = per-list inclusive prefix sums of the edge weights; one
@@ -899,6 +945,27 @@ int ggms_sample_batch_ppr(const ggms_graph_t *graph, const ggms_id_t *seeds, siz
                           uint32_t num_layer, ggms_hashtable_t *ht, ggms_id_t *const *row, ggms_id_t *const *col,
                           uint64_t *counts_dev, const ggms_ppr_t *ppr, const ggms_sample_extra_t *extra, void *workspace,
                           size_t workspace_bytes, ggms_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * The budget batch (an extension): ggms_sample_batch's chain with khop_budget as the sampler.
+ *   fanouts     fanouts[i] = the per-seed cap of layer i: capacities are ggms_sample_batch_capacity's, untouched.
+ *   layer_nodes HOST array of L node budgets, each >= 1: layer i adds at most layer_nodes[i] nodes to the batch.
+ *   mode, map   ggms_sample_khop_budget's.  Layer i runs with layer_salt = fmix32(labor_salt + 0x9e3779b9 * (i + 1)).
+ *   eid         HOST array of L device pointers, capacities max_edges[i]: the CSR position of every edge.
+ *   counts_dev, row, col, both table layouts, the numbering, seeds_distinct: ggms_sample_batch's; M and the number
+ *   chosen are not reported.  rng_wait / rng_done are ignored (stateless).  The workspace is
+ *   ggms_sample_batch_budget_workspace_bytes(..., num_edge, extra): the batch's and the leaf's candidate list.
+ *   ggms_sample_batch_seed_ids(GGMS_KHOP_BUDGET, ...) gives the raw seeds' local ids.
+ *   ggms_sample_batch(GGMS_KHOP_BUDGET, ...) is GGMS_ERR_INVALID and names this call.  The leaf's refusals hold, with
+ *   the largest frontier capacity in place of num_input.
+ * ------------------------------------------------------------------------- */
+size_t ggms_sample_batch_budget_workspace_bytes(size_t num_seeds, const size_t *fanouts, uint32_t num_layer,
+                                                uint64_t num_edge, const ggms_sample_extra_t *extra);
+int ggms_sample_batch_budget(const ggms_graph_t *graph, const ggms_id_t *seeds, size_t num_seeds, const size_t *fanouts,
+                             const size_t *layer_nodes, uint32_t num_layer, int mode, uint64_t *map, ggms_hashtable_t *ht,
+                             ggms_id_t *const *row, ggms_id_t *const *col, ggms_id_t *const *eid, uint64_t *counts_dev,
+                             const ggms_sample_extra_t *extra, void *workspace, size_t workspace_bytes,
+                             ggms_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * The weighted LABOR batch (an extension): ggms_sample_batch's chain with khop_labor_weighted as the sampler.

@@ -205,6 +205,14 @@ SYMBOLS = {
     "ggms_sample_batch_ppr": (_i, [C.POINTER(Graph), _vp, _sz, C.POINTER(_sz), _u32, C.POINTER(HashTable),
                                    C.POINTER(_vp), C.POINTER(_vp), _vp, C.POINTER(Ppr), C.POINTER(SampleExtra), _vp, _sz,
                                    _vp]),
+    "ggms_budget_map_init": (_i, [_vp, _sz, _vp]),
+    "ggms_sample_khop_budget_workspace_bytes": (_sz, [_sz, _sz, _u64]),
+    "ggms_sample_khop_budget": (_i, [C.POINTER(Graph), _vp, _sz, _sz, _sz, _i, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                     _vp, _sz, _vp]),
+    "ggms_sample_batch_budget_workspace_bytes": (_sz, [_sz, C.POINTER(_sz), _u32, _u64, C.POINTER(SampleExtra)]),
+    "ggms_sample_batch_budget": (_i, [C.POINTER(Graph), _vp, _sz, C.POINTER(_sz), C.POINTER(_sz), _u32, _i, _vp,
+                                      C.POINTER(HashTable), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp,
+                                      C.POINTER(SampleExtra), _vp, _sz, _vp]),
     "ggms_link_seeds": (_i, [C.POINTER(Graph), _vp, _sz, _u32, _i, _u32, _vp, _vp, _vp]),
     "ggms_link_seeds_typed": (_i, [C.POINTER(Graph), _vp, _vp, _vp, _vp, _u32, _vp, _sz, _u32, _i, _u32, _vp, _vp, _vp,
                                    _vp]),

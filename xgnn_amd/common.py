@@ -17,6 +17,7 @@ kKHopLaborWeighted = 11  # an extension: weighted sampling without replacement (
 kRandomWalkMetapath = 12  # an extension: PinSAGE's walks along a relation path (include/ggms.h, GGMS_RANDOM_WALK_METAPATH)
 kKHopTypedTemporal = 13  # an extension: a fanout per edge type before the seed's time (include/ggms.h, GGMS_KHOP_TYPED_TEMPORAL)
 kPPRTopK = 14  # an extension: push-based personalised-PageRank neighbourhoods (include/ggms.h, GGMS_PPR_TOPK)
+kKHopBudget = 15  # an extension: layer-wise sampling under a node budget per layer (include/ggms.h, GGMS_KHOP_BUDGET)
 kArch0, kArch1, kArch2, kArch3, kArch4, kArch5, kArch6, kArch7 = range(8)
 (kCacheByDegree, kCacheByHeuristic, kCacheByPreSample, kCacheByDegreeHop, kCacheByPreSampleStatic,
  kCacheByFakeOptimal, kDynamicCache, kCacheByRandom) = range(8)
@@ -35,7 +36,7 @@ sample_types = {
     'weighted_khop': kWeightedKHop, 'weighted_khop_prefix': kWeightedKHopPrefix,
     'weighted_khop_hash_dedup': kWeightedKHopHashDedup, 'khop_labor': kKHopLabor, 'khop_temporal': kKHopTemporal,
     'khop_typed': kKHopTyped, 'khop_labor_weighted': kKHopLaborWeighted, 'random_walk_metapath': kRandomWalkMetapath,
-    'khop_typed_temporal': kKHopTypedTemporal, 'ppr_topk': kPPRTopK,
+    'khop_typed_temporal': kKHopTypedTemporal, 'ppr_topk': kPPRTopK, 'khop_budget': kKHopBudget,
 }
 builtin_archs = {
     'arch0': {'arch': kArch0, 'sampler_ctx': cpu(), 'trainer_ctx': gpu(0)},

@@ -239,7 +239,36 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
     cfg.lookahead = 0;
     cfg.pipelines = 1;
   }
-  SAM_CHECK(cfg.sample_type >= GGMS_KHOP0 && cfg.sample_type <= GGMS_PPR_TOPK, "unknown sample type");
+  SAM_CHECK(cfg.sample_type >= GGMS_KHOP0 && cfg.sample_type <= GGMS_KHOP_BUDGET, "unknown sample type");
+  if (cfg.Budget()) { // extension: layer-wise sampling under a node budget per layer
+    static const char *const arch_names[] = {"arch0", "arch1", "arch2", "arch3", "arch4", "arch5", "arch6", "arch7"};
+    const std::string who = "_sample_type 15 (khop_budget)";
+    if (cfg.arch != kArch1)
+      fatal(__FILE__, __LINE__, std::string(arch_names[cfg.arch]) + ": " + who + " is not built: the weight map and the "
+                                "edge positions run in arch1's sampling chain only");
+    if (cfg.use_dist_graph)
+      fatal(__FILE__, __LINE__, who + " with use_dist_graph: the weights are summed over the lists of ONE CSR, a sharded "
+                                "topology is not built");
+    if (kv.count("hetero_batch") && kv["hetero_batch"] == "on")
+      fatal(__FILE__, __LINE__, who + " with hetero_batch is not built: the typed view needs the edge types the typed "
+                                "samplers write");
+    if (!kv.count("layer_nodes"))
+      fatal(__FILE__, __LINE__, who + " needs layer_nodes: one node budget per layer (fanout holds the per-seed caps)");
+    std::stringstream ss(kv["layer_nodes"]);
+    long long v = 0;
+    while (ss >> v) {
+      if (v < 1) fatal(__FILE__, __LINE__, "layer_nodes = " + kv["layer_nodes"] + ": every layer draws at least one node");
+      cfg.layer_nodes.push_back((size_t)v);
+    }
+    if (cfg.layer_nodes.size() != cfg.fanout.size())
+      fatal(__FILE__, __LINE__, "layer_nodes = " + kv["layer_nodes"] + ": " + std::to_string(cfg.layer_nodes.size()) +
+                                    " budgets for " + std::to_string(cfg.fanout.size()) + " layers (one per fanout)");
+    for (size_t f : cfg.fanout)
+      if (f > 127) fatal(__FILE__, __LINE__, "fanout = " + kv["fanout"] + ": " + who + " keeps 1 .. 127 edges per seed");
+    const std::string w = kv.count("budget_weight") ? kv["budget_weight"] : "ladies";
+    if (w != "uniform" && w != "ladies") fatal(__FILE__, __LINE__, "budget_weight = " + w + ": uniform or ladies (the default)");
+    cfg.budget_mode = w == "uniform" ? GGMS_BUDGET_UNIFORM : GGMS_BUDGET_LADIES;
+  }
   if (cfg.Ppr()) { // extension: push-based personalised-PageRank neighbourhoods
     static const char *const arch_names[] = {"arch0", "arch1", "arch2", "arch3", "arch4", "arch5", "arch6", "arch7"};
     const std::string who = "_sample_type 14 (ppr_topk)";
@@ -532,6 +561,12 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
                                 "walks whole lists");
     cfg.inline_heads = 0; // auto means off
   }
+  if (cfg.Budget()) { // (its keys and its other refusals: above, behind the sample type's range check)
+    if (cfg.inline_heads == 1)
+      fatal(__FILE__, __LINE__, "_sample_type 15 (khop_budget) with inline_heads = 1: only khop3 reads the list heads; the "
+                                "budget sampler walks whole lists");
+    cfg.inline_heads = 0; // auto means off
+  }
   if (cfg.Weighted()) { // extension: weighted sampling without replacement on edge_weight.bin
     const std::string who = "_sample_type 11 (khop_labor_weighted)";
     if (cfg.use_dist_graph)
@@ -554,7 +589,7 @@ void Engine::Configure(const std::unordered_map<std::string, std::string> &kv_in
     cfg.edge_feat = kv.count("edge_feat") && kv["edge_feat"] == "on";
     cfg.edge_ids = cfg.edge_feat || (kv.count("edge_ids") && kv["edge_ids"] == "on");
   }
-  if (cfg.SamplerEmitsEdgeIds()) cfg.edge_ids = true; // implied: the sampler emits the positions itself
+  if (cfg.SamplerEmitsEdgeIds() || cfg.Budget()) cfg.edge_ids = true; // implied: the sampler emits the positions itself
   if (cfg.edge_ids) {
     static const char *const arch_names[] = {"arch0", "arch1", "arch2", "arch3", "arch4", "arch5", "arch6", "arch7"};
     const std::string key = cfg.edge_feat ? "edge_feat" : "edge_ids";
@@ -1599,7 +1634,7 @@ void Engine::SampleInit(int worker_id, const std::string &ctx) {
   extra_.random_walk_restart_prob = cfg.random_walk_restart_prob;
   extra_.num_random_walk = cfg.num_random_walk;
   // GPURandomStates dist_engine.cc:432-433; seed = wall clock unless the "seed" key is given
-  if (cfg.sample_type == GGMS_KHOP_LABOR || cfg.Timed() || cfg.Typed() || cfg.Weighted() || cfg.Metapath() || cfg.Ppr()) { // stateless: their variates are hashes of (node id, salt), ppr_topk draws nothing -- no RNG pool
+  if (cfg.sample_type == GGMS_KHOP_LABOR || cfg.Timed() || cfg.Typed() || cfg.Weighted() || cfg.Metapath() || cfg.Ppr() || cfg.Budget()) { // stateless: their variates are hashes of (node id, salt), ppr_topk draws nothing -- no RNG pool
     num_states_ = 0;
     states_ = nullptr;
   } else {
@@ -1622,6 +1657,11 @@ void Engine::SampleInit(int worker_id, const std::string &ctx) {
     ws_bytes_ = ggms_sample_batch_typed_workspace_bytes(max_seeds_, cfg.fanout.data(), L, cfg.num_edge_type, &extra_);
   if (cfg.TypedTemporal()) // likewise its records
     ws_bytes_ = ggms_sample_batch_typed_temporal_workspace_bytes(max_seeds_, cfg.fanout.data(), L, cfg.num_edge_type, &extra_);
+  if (cfg.Budget()) { // + the candidate list: no more distinct neighbours than nodes or edges
+    ws_bytes_ = ggms_sample_batch_budget_workspace_bytes(max_seeds_, cfg.fanout.data(), L,
+                                                         std::min<uint64_t>(ds.num_edge, ds.num_node), &extra_);
+    SAM_CHECK(ws_bytes_ > 0, "khop_budget: the batch bounds are out of ggms_sample_batch_budget's range");
+  }
   SAM_HIP(hipMalloc(&ws_, ws_bytes_));
   // pipeline 0 = {stream_, ht_, ws_}; the others get their own stream, table and workspace
   pipes_.assign(cfg.pipelines, Pipe{});
@@ -1651,6 +1691,12 @@ void Engine::SampleInit(int worker_id, const std::string &ctx) {
     for (Pipe &P : pipes_) {
       SAM_HIP(hipMalloc((void **)&P.cut_table, std::max<size_t>(ds.num_node, 1) * 8));
       SAM_HIP(hipMemsetAsync(P.cut_table, 0, std::max<size_t>(ds.num_node, 1) * 8, stream_));
+    }
+  }
+  if (cfg.Budget()) { // one weight map per pipeline: 8 B x num_node, zeroed once (every batch restores it)
+    for (Pipe &P : pipes_) {
+      SAM_HIP(hipMalloc((void **)&P.budget_map, std::max<size_t>(ds.num_node, 1) * 8));
+      SAM_GGMS(ggms_budget_map_init(P.budget_map, ds.num_node, stream_));
     }
   }
   if (cfg.Relational() || cfg.Metapath()) { // the edge types in HBM, beside the topology the sampler reads
@@ -1763,6 +1809,8 @@ void Engine::Presample() {
     SAM_HIP(hipMemsetAsync(d_visit, 0, ds.num_node * 4, stream_));
   }
   std::vector<uint32_t *> row(closure ? 0 : L), col(closure ? 0 : L), dat(closure ? 0 : L, nullptr);
+  std::vector<uint32_t *> pos(closure || !cfg.Budget() ? 0 : L, nullptr); // khop_budget writes its positions
+  for (uint32_t i = 0; i < pos.size(); ++i) SAM_HIP(hipMalloc((void **)&pos[i], std::max<size_t>(max_edges_[i], 4) * 4));
   for (uint32_t i = 0; i < row.size(); ++i) {
     SAM_HIP(hipMalloc((void **)&row[i], std::max<size_t>(max_edges_[i], 4) * 4));
     SAM_HIP(hipMalloc((void **)&col[i], std::max<size_t>(max_edges_[i], 4) * 4));
@@ -1799,6 +1847,10 @@ void Engine::Presample() {
         const ggms_ppr_t p{cfg.ppr_alpha, cfg.ppr_eps, cfg.ppr_max_nodes, cfg.ppr_max_rounds};
         SAM_GGMS(ggms_sample_batch_ppr(&graph_, d_train + off, size, cfg.fanout.data(), L, &pipes_[0].ht, row.data(),
                                        col.data(), d_counts, &p, &extra, ws_, ws_bytes_, stream_));
+      } else if (cfg.Budget()) {
+        SAM_GGMS(ggms_sample_batch_budget(&graph_, d_train + off, size, cfg.fanout.data(), cfg.layer_nodes.data(), L,
+                                          cfg.budget_mode, pipes_[0].budget_map, &pipes_[0].ht, row.data(), col.data(),
+                                          pos.data(), d_counts, &extra, ws_, ws_bytes_, stream_));
       } else
       SAM_GGMS(ggms_sample_batch(cfg.sample_type, &graph_, d_train + off, size, cfg.fanout.data(), L, &pipes_[0].ht,
                                  states_, num_states_, row.data(), col.data(), d_counts, &extra, ws_, ws_bytes_, stream_));
@@ -1820,6 +1872,7 @@ void Engine::Presample() {
   uint32_t *rank = (uint32_t *)ds.ranking_nodes.ptr;
   for (size_t i = 0; i < ds.num_node; ++i) rank[i] = (uint32_t)keys[i]; // GetRankNode :141-151
   for (size_t i = 0; i < row.size(); ++i) { (void)hipFree(row[i]); (void)hipFree(col[i]); if (dat[i]) (void)hipFree(dat[i]); }
+  for (uint32_t *p : pos) (void)hipFree(p);
   (void)hipFree(d_train); (void)hipFree(d_freq); (void)hipFree(d_counts);
 }
 
@@ -2344,7 +2397,7 @@ void Engine::SampleInto(Batch *b, Pipe &P) {
                                     P.stream));
   }
   if (pipes_.size() > 1 && cfg.sample_type != GGMS_KHOP0 && cfg.sample_type != GGMS_KHOP_LABOR && !cfg.Timed() &&
-      !cfg.Typed() && !cfg.Weighted() && !cfg.Metapath() && !cfg.Ppr()) {
+      !cfg.Typed() && !cfg.Weighted() && !cfg.Metapath() && !cfg.Ppr() && !cfg.Budget()) {
     extra.rng_wait = last_rng_done_;
     extra.rng_done = P.rng_done;
     last_rng_done_ = P.rng_done;
@@ -2387,6 +2440,11 @@ void Engine::SampleInto(Batch *b, Pipe &P) {
     SAM_GGMS(ggms_sample_batch_labor_weighted(&graph_, s.output_nodes, b->num_seeds, cfg.fanout.data(), L, &ht, s.row.data(),
                                               s.col.data(), b->eid.data(), s.counts_dev, d_edge_weight_, &extra, P.ws,
                                               ws_bytes_, P.stream));
+  } else if (cfg.Budget()) {
+    // the sampler fills the batch's eid buffers itself, on the pipeline's own map
+    SAM_GGMS(ggms_sample_batch_budget(&graph_, s.output_nodes, b->num_seeds, cfg.fanout.data(), cfg.layer_nodes.data(), L,
+                                      cfg.budget_mode, P.budget_map, &ht, s.row.data(), s.col.data(), b->eid.data(),
+                                      s.counts_dev, &extra, P.ws, ws_bytes_, P.stream));
   } else if (cfg.Metapath()) {
     // random walk's batch with the edge types and the path; the visit counts land in the batch's data buffers
     const ggms_typed_t t{d_edge_type_, cfg.num_edge_type, nullptr};

@@ -144,7 +144,16 @@ struct RunConfig {
   bool TypedTemporal() const { return sample_type == GGMS_KHOP_TYPED_TEMPORAL; }
   bool Timed() const { return Temporal() || TypedTemporal(); }
   bool Relational() const { return Typed() || TypedTemporal(); }
-  bool SamplerEmitsEdgeIds() const { return Timed() || Typed() || Weighted(); } // ggms_edge_positions is not enqueued
+  // extension (`_sample_type` 15 = khop_budget, config keys `layer_nodes` = one node budget per layer and `budget_weight`
+  // = uniform | ladies; arch1, one CSR, both tasks): layer-wise sampling under a node budget (ggms_sample_batch_budget);
+  // `fanout` holds the per-seed caps.  Implies edge_ids: the sampler writes the positions.  Behind exclude_seed_edges the
+  // filter compacts row / col only, so there the positions are computed again from the filtered layers
+  std::vector<size_t> layer_nodes;
+  int budget_mode = GGMS_BUDGET_LADIES;
+  bool Budget() const { return sample_type == GGMS_KHOP_BUDGET; }
+  bool SamplerEmitsEdgeIds() const { // ggms_edge_positions is not enqueued
+    return Timed() || Typed() || Weighted() || (Budget() && exclude_seed_edges == 0);
+  }
   // extension (`_sample_type` 12 = random_walk_metapath, config key `metapath` = relation ids; arch1, one CSR): random
   // walk's keys with random_walk_length as the number of traversals of the path (ggms_sample_batch_walk_metapath);
   // num_edge_type is meta.txt's NUM_EDGE_TYPE.  Walk(): either walk sampler -- visit counts ride with the batch
@@ -524,6 +533,7 @@ class Engine {
     void *eid_ws = nullptr;  // edge_ids: ggms_edge_positions' workspace
     uint64_t *cut_table = nullptr; // khop_temporal: the pipeline's cut table (8 B x num_node, zeroed once) and the stamp of
     uint32_t stamp = 0;            // its last batch
+    uint64_t *budget_map = nullptr;  // khop_budget: the pipeline's weight map (8 B x num_node, zero between batches)
     uint32_t *induced_map = nullptr; // induced_subgraph: the pipeline's membership map (4 B x num_node, all EMPTY between
     void *induced_ws = nullptr;      // batches) and ggms_induced_edges' workspace
     void *hetero_ws = nullptr;       // hetero_batch: the one workspace of ggms_hetero_nodes and ggms_hetero_edges

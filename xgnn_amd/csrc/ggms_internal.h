@@ -108,6 +108,14 @@ struct SampleLayer {
   // with random walk
   uint32_t ppr_a = 0, ppr_e = 0, ppr_nodes = 0, ppr_rounds = 0;
   uint32_t *out_stat = nullptr;
+  // khop_budget: the per-node map (8 bytes per node, zero between calls), the candidate ids + keys (2 x budget_cap
+  // words), the layer's node budget S, the mode, M and the number chosen (may be NULL).  Shares out_pos and salt
+  unsigned long long *budget_map = nullptr;
+  uint32_t *budget_cand = nullptr;
+  size_t budget_cap = 0;
+  uint64_t budget_nodes = 0;
+  int budget_mode = 0;
+  uint64_t *budget_stat = nullptr;
 };
 
 // sample_khop.hip
@@ -136,6 +144,15 @@ size_t ppr_ws_words(size_t num_input, size_t K);
 int ppr_check(double alpha, double eps, size_t max_nodes, size_t max_rounds, size_t K, const char *who); // the refusals of include/ggms.h
 void ppr_set(SampleLayer &l, double alpha, double eps, size_t max_nodes, size_t max_rounds);            // A, E, C, rounds
 int sample_ppr_impl(const SampleLayer &l);
+
+// sample_budget.hip.  The candidate list lives BEHIND a workspace's layer / batch part: budget_cand_bytes(num_edge) more
+// bytes, which budget_set_cand turns into budget_cand / budget_cap (false + an error message: no room)
+size_t budget_ws_words(size_t num_input);
+int budget_check(const ggms_graph_t *graph, size_t n_max, const size_t *budgets, const size_t *fanouts, uint32_t num,
+                 int mode, const void *map, const char *who); // the refusals of include/ggms.h
+size_t budget_cand_bytes(uint64_t num_edge);
+bool budget_set_cand(SampleLayer &l, void *workspace, size_t workspace_bytes, size_t fixed_bytes, const char *who);
+int sample_khop_budget_impl(const SampleLayer &l);
 
 // sample_labor.hip
 size_t labor_ws_words(size_t num_input);

@@ -82,6 +82,7 @@ size_t layer_ws_words(int type, size_t n, size_t fanout, size_t walk_length, siz
   case GGMS_KHOP_LABOR_WEIGHTED: return labor_ws_words(n);
   case GGMS_KHOP_TEMPORAL: return temporal_ws_words(n);
   case GGMS_PPR_TOPK: return ppr_ws_words(n, fanout);
+  case GGMS_KHOP_BUDGET: return budget_ws_words(n);
   default: return sample_ws_words(n); // khop3, khop2, weighted_khop_hash_dedup
   }
 }
@@ -107,6 +108,9 @@ static int layer_shape_check(int type, const SampleLayer &l) {
                                        l.fanout, "random_walk_metapath");
     if (rc != GGMS_OK) return rc;
   }
+  if (type == GGMS_KHOP_BUDGET) // budget_check's; the per-seed cap is khop_labor's selection over the chosen set
+    GGMS_CHECK_ARG(l.fanout < 128 && l.budget_nodes >= 1 &&
+                   (l.budget_mode == GGMS_BUDGET_UNIFORM || l.budget_mode == GGMS_BUDGET_LADIES));
   if (type == GGMS_PPR_TOPK) GGMS_CHECK_ARG(l.fanout <= 127 && l.ppr_nodes >= 64 && l.fanout < l.ppr_nodes); // ppr_check's
   // "this algorithm not support DistGraph engine", dist_loops.cc:167-228
   if (type != GGMS_KHOP3 && type != GGMS_KHOP0 && type != GGMS_RANDOM_WALK && type != GGMS_KHOP_LABOR)
@@ -121,8 +125,9 @@ static int layer_check(int type, const SampleLayer &l, size_t num_states) {
   const uint64_t n = l.n_max;
   if (type == GGMS_KHOP1 || type == GGMS_KHOP2 || type == GGMS_KHOP_TEMPORAL || type == GGMS_KHOP_TYPED ||
       type == GGMS_KHOP_LABOR_WEIGHTED || type == GGMS_RANDOM_WALK_METAPATH || type == GGMS_KHOP_TYPED_TEMPORAL ||
-      type == GGMS_PPR_TOPK)
+      type == GGMS_PPR_TOPK || type == GGMS_KHOP_BUDGET)
     GGMS_CHECK_ARG(l.graph->indptr && l.graph->indices);
+  if (type == GGMS_KHOP_BUDGET) GGMS_CHECK_ARG(l.out_pos && l.budget_map && l.budget_cand && n < (1ull << 22));
   if (type == GGMS_PPR_TOPK) GGMS_CHECK_ARG(l.out_data);
   if (type == GGMS_RANDOM_WALK_METAPATH) GGMS_CHECK_ARG(l.edge_type && l.out_data);
   if (type == GGMS_KHOP_TYPED || type == GGMS_KHOP_TYPED_TEMPORAL) GGMS_CHECK_ARG(l.edge_type && l.out_pos && l.out_type);
@@ -140,7 +145,8 @@ static int layer_check(int type, const SampleLayer &l, size_t num_states) {
   case GGMS_KHOP_TYPED_TEMPORAL:
   case GGMS_KHOP_LABOR_WEIGHTED:
   case GGMS_RANDOM_WALK_METAPATH:
-  case GGMS_PPR_TOPK: return GGMS_OK; // stateless
+  case GGMS_PPR_TOPK:
+  case GGMS_KHOP_BUDGET: return GGMS_OK; // stateless
   case GGMS_KHOP3: GGMS_CHECK_ARG(l.states && (n + 127) / 128 * 8 <= num_states); return GGMS_OK; // khop3.cu:89
   case GGMS_KHOP2:                                                                                   // khop2.cu:57
   case GGMS_WEIGHTED_KHOP_HASH_DEDUP: // hash_dedup.cu:70
@@ -169,6 +175,7 @@ static int sample_layer(int type, const SampleLayer &l) {
   case GGMS_RANDOM_WALK_METAPATH: return sample_walk_metapath_impl(l);
   case GGMS_KHOP_LABOR: return sample_khop_labor_impl(l);
   case GGMS_PPR_TOPK: return sample_ppr_impl(l);
+  case GGMS_KHOP_BUDGET: return sample_khop_budget_impl(l);
   case GGMS_KHOP_TEMPORAL: return sample_khop_temporal_impl(l);
   case GGMS_KHOP_TYPED: return sample_khop_typed_impl(l);
   case GGMS_KHOP_TYPED_TEMPORAL: return sample_khop_typed_temporal_impl(l);
@@ -186,9 +193,11 @@ static int sample_layer(int type, const SampleLayer &l) {
 // behind the search of the seed's whole wave, and the sampler stays a pure function of its inputs.
 // khop_temporal, khop_typed, khop_typed_temporal and khop_labor_weighted are khop_labor's selection: the same holds.
 // ppr_topk's output leaves through a tile scan's emit, one lane per seed: K dependent atomics per lane there, not tried.
+// khop_budget's per-seed stage is khop_labor's selection again.
 static bool layer_enters_output(int type) {
   return type != GGMS_KHOP2 && type != GGMS_KHOP_LABOR && type != GGMS_KHOP_TEMPORAL && type != GGMS_KHOP_TYPED &&
-         type != GGMS_KHOP_LABOR_WEIGHTED && type != GGMS_KHOP_TYPED_TEMPORAL && type != GGMS_PPR_TOPK;
+         type != GGMS_KHOP_LABOR_WEIGHTED && type != GGMS_KHOP_TYPED_TEMPORAL && type != GGMS_PPR_TOPK &&
+         type != GGMS_KHOP_BUDGET;
 }
 
 // a leaf entry point: shape checks; nothing to sample -> a zero count (null pointers allowed); pointers, workspace and
@@ -338,6 +347,16 @@ struct WeightedBatch {
   ggms_id_t *const *eid;
 };
 
+// ggms_sample_batch_budget's part of a batch (NULL: any other batch); cand / cap: budget_set_cand's
+struct BudgetBatch {
+  const size_t *layer_nodes;
+  int mode;
+  unsigned long long *map;
+  ggms_id_t *const *eid;
+  uint32_t *cand;
+  size_t cap;
+};
+
 // ggms_sample_batch_walk_metapath's part of a batch (NULL: any other batch)
 struct MetapathBatch {
   const ggms_typed_t *t;
@@ -347,14 +366,14 @@ struct MetapathBatch {
 
 // the body of ggms_sample_batch, ggms_sample_batch_prefetch, ggms_sample_batch_temporal, ggms_sample_batch_typed,
 // ggms_sample_batch_labor_weighted, ggms_sample_batch_walk_metapath, ggms_sample_batch_typed_temporal (tb and yb
-// together) and ggms_sample_batch_ppr (pb); every argument check is the caller's
+// together), ggms_sample_batch_ppr (pb) and ggms_sample_batch_budget (bb); every argument check is the caller's
 static int sample_batch_impl(int sample_type, const ggms_graph_t *graph, const ggms_id_t *seeds, size_t num_seeds,
                              const size_t *fanouts, uint32_t num_layer, ggms_hashtable_t *ht, void *states,
                              size_t num_states, ggms_id_t *const *row, ggms_id_t *const *col, uint64_t *counts_dev,
                              const ggms_sample_extra_t *extra, void *workspace, const Prefetch *pf, hipStream_t s,
                              const TemporalBatch *tb = nullptr, const TypedBatch *yb = nullptr,
                              const WeightedBatch *wb = nullptr, const MetapathBatch *mb = nullptr,
-                             const ggms_ppr_t *pb = nullptr) {
+                             const ggms_ppr_t *pb = nullptr, const BudgetBatch *bb = nullptr) {
   const BatchCaps c = caps_of(num_seeds, fanouts, num_layer);
   // what every layer's sampler call shares; the loop below fills in the rest
   SampleLayer L{graph, nullptr, 0, 0, nullptr, nullptr, nullptr, (uint32_t *)states, nullptr, s};
@@ -369,7 +388,7 @@ static int sample_batch_impl(int sample_type, const ggms_graph_t *graph, const g
   const bool ordered_rng = sample_type != GGMS_KHOP_LABOR && sample_type != GGMS_KHOP_TEMPORAL &&
                            sample_type != GGMS_KHOP_TYPED && sample_type != GGMS_KHOP_LABOR_WEIGHTED &&
                            sample_type != GGMS_RANDOM_WALK_METAPATH && sample_type != GGMS_KHOP_TYPED_TEMPORAL &&
-                           sample_type != GGMS_PPR_TOPK;
+                           sample_type != GGMS_PPR_TOPK && sample_type != GGMS_KHOP_BUDGET;
   const bool walk = sample_type == GGMS_RANDOM_WALK || sample_type == GGMS_RANDOM_WALK_METAPATH;
   if (pb) {
     ppr_set(L, pb->alpha, pb->eps, pb->max_nodes, pb->max_rounds);
@@ -399,9 +418,17 @@ static int sample_batch_impl(int sample_type, const ggms_graph_t *graph, const g
     L.edge_weight = wb->edge_weight;
     L.out_pos = wb->eid[0]; // layer_check's non-null test; every layer sets its own below
   }
+  if (bb) {
+    L.budget_mode = bb->mode;
+    L.budget_map = bb->map;
+    L.budget_cand = bb->cand;
+    L.budget_cap = bb->cap;
+    L.out_pos = bb->eid[0]; // layer_check's non-null test; every layer sets its own below
+  }
   for (uint32_t i = 0; i < num_layer; ++i) {
     L.n_max = c.max_input[i];
     L.fanout = fanouts[i];
+    if (bb) L.budget_nodes = bb->layer_nodes[i];
     if (yb) L.type_fanout = yb->t->type_fanout + (size_t)i * L.num_type; // fanouts[i] must be this row's sum
     const int rc = layer_check(sample_type, L, num_states);
     if (rc != GGMS_OK) return rc;
@@ -560,6 +587,10 @@ static int sample_batch_impl(int sample_type, const ggms_graph_t *graph, const g
       if (walk || pb) L.out_data = extra->data[i];
       if (tb) L.out_pos = tb->eid[i];
       if (wb) L.out_pos = wb->eid[i];
+      if (bb) {
+        L.out_pos = bb->eid[i];
+        L.budget_nodes = bb->layer_nodes[i];
+      }
       if (yb) {
         L.type_fanout = yb->t->type_fanout + (size_t)i * L.num_type;
         L.out_pos = yb->eid[i];
@@ -645,6 +676,11 @@ int ggms_sample_batch(int sample_type, const ggms_graph_t *graph, const ggms_id_
               "ggms_sample_batch_ppr", sample_type);
     return GGMS_ERR_INVALID;
   }
+  if (sample_type == GGMS_KHOP_BUDGET) {
+    set_error("ggms_sample_batch: sample type %d (khop_budget) takes a node budget per layer, a mode and the per-node "
+              "map: call ggms_sample_batch_budget", sample_type);
+    return GGMS_ERR_INVALID;
+  }
   if (sample_type == GGMS_KHOP_TYPED_TEMPORAL) {
     set_error("ggms_sample_batch: sample type %d (khop_typed_temporal) takes edge types, edge times, seed times, a cut "
               "table and a fanout per type and layer: call ggms_sample_batch_typed_temporal", sample_type);
@@ -668,7 +704,7 @@ int ggms_sample_batch_seed_ids(int sample_type, size_t num_seeds, const size_t *
                                const ggms_sample_extra_t *extra, const void *workspace, const ggms_id_t **seed_ids_dev) {
   GGMS_CHECK_ARG(fanouts && workspace && seed_ids_dev);
   GGMS_CHECK_ARG(num_layer >= 1 && num_layer <= 16);
-  GGMS_CHECK_ARG(sample_type >= GGMS_KHOP0 && sample_type <= GGMS_PPR_TOPK);
+  GGMS_CHECK_ARG(sample_type >= GGMS_KHOP0 && sample_type <= GGMS_KHOP_BUDGET);
   const BatchCaps c = caps_of(num_seeds, fanouts, num_layer);
   const BatchLayout lay = layout_of(sample_type, num_seeds, fanouts, num_layer, c, extra);
   const uint32_t *w = (const uint32_t *)(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
@@ -899,6 +935,45 @@ int ggms_sample_batch_ppr(const ggms_graph_t *graph, const ggms_id_t *seeds, siz
   GGMS_CHECK_ARG(c.max_input[0] + c.max_edges[0] < (1ull << 32) - 4); // indices and 2 + local id fit 32 bits
   return sample_batch_impl(GGMS_PPR_TOPK, graph, seeds, num_seeds, fanouts, num_layer, ht, nullptr, 0, row, col, counts_dev,
                            extra, workspace, nullptr, to_stream(stream), nullptr, nullptr, nullptr, nullptr, ppr);
+}
+
+// ---- khop_budget: the batch with a node budget per layer -------------------------------------------------------------
+size_t ggms_sample_batch_budget_workspace_bytes(size_t num_seeds, const size_t *fanouts, uint32_t num_layer,
+                                                uint64_t num_edge, const ggms_sample_extra_t *extra) {
+  const size_t base = ggms_sample_batch_workspace_bytes(GGMS_KHOP_BUDGET, num_seeds, fanouts, num_layer, extra);
+  if (base == 0) return 0;
+  if (num_edge >= 0xffffffffull) {
+    set_error("ggms_sample_batch_budget_workspace_bytes: %llu edges: positions are 32-bit (at most 2^32 - 2)",
+              (unsigned long long)num_edge);
+    return 0;
+  }
+  return base + budget_cand_bytes(num_edge);
+}
+
+int ggms_sample_batch_budget(const ggms_graph_t *graph, const ggms_id_t *seeds, size_t num_seeds, const size_t *fanouts,
+                             const size_t *layer_nodes, uint32_t num_layer, int mode, uint64_t *map, ggms_hashtable_t *ht,
+                             ggms_id_t *const *row, ggms_id_t *const *col, ggms_id_t *const *eid, uint64_t *counts_dev,
+                             const ggms_sample_extra_t *extra, void *workspace, size_t workspace_bytes,
+                             ggms_stream_t stream) {
+  static const char *const who = "ggms_sample_batch_budget";
+  GGMS_CHECK_ARG(graph && fanouts && layer_nodes && ht && row && col && eid && counts_dev);
+  GGMS_CHECK_ARG(num_layer >= 1 && num_layer <= 16);
+  const BatchCaps c = caps_of(num_seeds, fanouts, num_layer);
+  const int rc = budget_check(graph, c.max_in_all, layer_nodes, fanouts, num_layer, mode, map, who);
+  if (rc != GGMS_OK) return rc;
+  GGMS_CHECK_ARG(map && (num_seeds == 0 || seeds));
+  for (uint32_t i = 0; i < num_layer; ++i) GGMS_CHECK_ARG(row[i] && col[i] && eid[i]);
+  const size_t base = ggms_sample_batch_workspace_bytes(GGMS_KHOP_BUDGET, num_seeds, fanouts, num_layer, extra);
+  GGMS_CHECK_ARG(workspace && workspace_bytes >= base);
+  GGMS_CHECK_ARG(c.max_input[0] + c.max_edges[0] <= ht->n2o_size);
+  GGMS_CHECK_ARG(c.max_input[0] + c.max_edges[0] < (1ull << 32) - 4); // indices and 2 + local id fit 32 bits
+  SampleLayer probe{};
+  probe.graph = graph;
+  if (!budget_set_cand(probe, workspace, workspace_bytes, base, who)) return GGMS_ERR_INVALID;
+  const BudgetBatch bb{layer_nodes, mode, (unsigned long long *)map, eid, probe.budget_cand, probe.budget_cap};
+  return sample_batch_impl(GGMS_KHOP_BUDGET, graph, seeds, num_seeds, fanouts, num_layer, ht, nullptr, 0, row, col,
+                           counts_dev, extra, workspace, nullptr, to_stream(stream), nullptr, nullptr, nullptr, nullptr,
+                           nullptr, &bb);
 }
 
 // ---- arch4: the prefetching batch ----------------------------------------------------------------------------------

@@ -46,18 +46,7 @@ __device__ __forceinline__ float weight_clamp(float w) {
 
 // key32 of (neighbour id, weight); T = the log table in LDS
 __device__ __forceinline__ uint32_t weighted_key32(uint32_t t, float w, uint32_t salt, const uint64_t *T) {
-  const uint64_t v = 2ull * fmix32(t ^ salt) + 1ull;
-  const uint32_t e = 63u - (uint32_t)__clzll((long long)v);
-  const uint32_t f = (uint32_t)((v << (63u - e)) >> 31);
-  const uint32_t i = f >> 24, r = f & 0xffffffu;
-  const uint64_t t0 = T[i], t1 = T[i + 1];
-  const uint64_t E = (33ull << 32) - (((uint64_t)e << 32) + t0 + (((t1 - t0) * r) >> 24));
-  return __float_as_uint((float)E / weight_clamp(w));
-}
-
-__device__ __forceinline__ void load_log_table(uint64_t *T) { // by the whole workgroup; ends with a barrier
-  for (uint32_t j = threadIdx.x; j < kLaborLogEntries; j += kBlock) T[j] = kLaborLog2[j];
-  __syncthreads();
+  return __float_as_uint((float)labor_exp_units(t, salt, T) / weight_clamp(w));
 }
 
 // an edge of khop_labor_weighted: khop_labor's (seed's value, neighbour id) and the edge's CSR position

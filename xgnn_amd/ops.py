@@ -64,9 +64,11 @@ MAX_METAPATH = 8  # GGMS_MAX_METAPATH
 KHOP_TYPED_TEMPORAL = 13  # an extension: a fanout per edge type before a per-seed cut-off time (include/ggms.h)
 PPR_TOPK = 14  # an extension: the top-K of a pushed personalised-PageRank vector per seed (include/ggms.h)
 PPR_MAX_NODES = 2048  # GGMS_PPR_MAX_NODES
+KHOP_BUDGET = 15  # an extension: layer-wise importance sampling under a node budget per layer (include/ggms.h)
+BUDGET_UNIFORM, BUDGET_LADIES = 0, 1  # khop_budget's candidate weights
 # samplers without an RNG pool
 _STATELESS = (KHOP0, KHOP_LABOR, KHOP_TEMPORAL, KHOP_TYPED, KHOP_LABOR_WEIGHTED, RANDOM_WALK_METAPATH,
-              KHOP_TYPED_TEMPORAL, PPR_TOPK)
+              KHOP_TYPED_TEMPORAL, PPR_TOPK, KHOP_BUDGET)
 
 
 def _require_gpu(t):
@@ -257,6 +259,37 @@ def sample_khop_labor_weighted(graph, edge_weight, inp, fanout, layer_salt):
                                                 _ptr(num_out), _ptr(ws), ws.numel() * 4, _stream()),
           "ggms_sample_khop_labor_weighted")
     return out[0], out[1], out[2], num_out
+
+
+def budget_map(num_node, device):
+    """khop_budget's per-node map: one int64 per node id, zero between calls (ggms_budget_map_init)."""
+    m = torch.empty(max(1, num_node), dtype=torch.int64, device=device)
+    check(lib().ggms_budget_map_init(_ptr(m), num_node, _stream()), "ggms_budget_map_init")
+    return m
+
+
+def sample_khop_budget(graph, inp, budget, fanout, layer_salt, mode=BUDGET_LADIES, map=None, num_edge=None):
+    """ggms_sample_khop_budget: the layer draws at most `budget` nodes for the whole frontier (a candidate's chance grows
+    with the frontier's weight on it), each seed keeps at most `fanout` edges into the chosen set.  map: budget_map()'s
+    tensor (made here if None); num_edge: the graph's edge count (read from graph.indices if None).
+    Returns (out_src, out_dst, out_pos, num_out[1], stat[2] = {M, chosen}), the last two on the device."""
+    _require_gpu(inp)
+    _i32(inp)
+    n = inp.numel()
+    dev = inp.device
+    if map is None:
+        map = budget_map(graph.c.num_node, dev)
+    if num_edge is None:
+        num_edge = graph.indices.numel()
+    out = [torch.empty(max(1, n * fanout), dtype=torch.int32, device=dev) for _ in range(3)]
+    num_out = torch.zeros(1, dtype=torch.int64, device=dev)
+    stat = torch.zeros(2, dtype=torch.int64, device=dev)
+    ws = _workspace(lib().ggms_sample_khop_budget_workspace_bytes(n, fanout, num_edge), dev)
+    check(lib().ggms_sample_khop_budget(C.byref(graph.c), _ptr(inp), n, budget, fanout, mode, layer_salt & 0xFFFFFFFF,
+                                        _ptr(map), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(num_out), _ptr(stat),
+                                        _ptr(ws), ws.numel() * 4, _stream()),
+          "ggms_sample_khop_budget")
+    return out[0], out[1], out[2], num_out, stat
 
 
 def _u8(t):
@@ -1747,6 +1780,50 @@ class LaborWeightedBatchSampler(_BatchBuffers):
     def result(self):
         """Sync and slice the outputs: BatchSampler.result()'s, each layer with its `eid`."""
         c, layers = self._sliced("ggms_sample_batch_labor_weighted")
+        for i, lay in enumerate(layers):
+            lay["eid"] = self.eid[i][:c[COUNT_EDGES(i)]]
+        return dict(layers=layers, input_nodes=self.ht.n2o[:c[COUNT_INPUT(self.L)]])
+
+
+class BudgetBatchSampler(_BatchBuffers):
+    """ggms_sample_batch_budget: BatchSampler's layers with khop_budget as the sampler -- fanouts[i] the per-seed cap,
+    layer_nodes[i] the node budget of layer i.  One slot, one pipeline."""
+
+    def __init__(self, graph, fanouts, layer_nodes, batch_size, mode=BUDGET_LADIES, device="cuda", direct_table=True,
+                 max_seeds=None, num_edge=None):
+        assert len(layer_nodes) == len(fanouts), "one node budget per layer"
+        self._init_capacity(graph, fanouts, KHOP_BUDGET,
+                            int(batch_size * 1.25) + 1 if max_seeds is None else int(max_seeds), None, None)
+        self.mode = mode
+        self._nodes = (C.c_size_t * self.L)(*[int(s) for s in layer_nodes])
+        self.map = budget_map(graph.c.num_node, device)
+        self.ht = OrderedHashTable(self.max_unique, device, num_node=graph.c.num_node if direct_table else None)
+        self.states = None
+        (self.row, self._rows), (self.col, self._cols) = self._layer_buffers(1, device), self._layer_buffers(1, device)
+        self.eid, self._eids = self._layer_buffers(1, device)
+        self.counts = torch.zeros(COUNTS_SAMPLE_WORDS(self.L), dtype=torch.int64, device=device)
+        wsb = lib().ggms_sample_batch_budget_workspace_bytes(self.max_seeds, self._f, self.L,
+                                                             graph.indices.numel() if num_edge is None else num_edge,
+                                                             C.byref(self._extra))
+        self.ws = _workspace(wsb, device)
+
+    def sample(self, seeds, salt=0, distinct=False):
+        """Enqueue one batch; salt: the batch salt (layer i samples under fmix32(salt + 0x9e3779b9 * (i + 1)));
+        distinct: the caller promises pairwise distinct seeds (ggms_sample_extra_t.seeds_distinct)."""
+        _i32(seeds)
+        n = seeds.numel()
+        assert n <= self.max_seeds
+        self._extra.labor_salt = salt & 0xFFFFFFFF
+        self._extra.seeds_distinct = 1 if distinct else 0
+        check(lib().ggms_sample_batch_budget(C.byref(self.graph.c), _ptr(seeds), n, self._f, self._nodes, self.L,
+                                             self.mode, _ptr(self.map), C.byref(self.ht.c), self._rows, self._cols,
+                                             self._eids, _ptr(self.counts), C.byref(self._extra), _ptr(self.ws),
+                                             self.ws.numel() * 4, _stream()),
+              "ggms_sample_batch_budget")
+
+    def result(self):
+        """Sync and slice the outputs: BatchSampler.result()'s, each layer with its `eid`."""
+        c, layers = self._sliced("ggms_sample_batch_budget")
         for i, lay in enumerate(layers):
             lay["eid"] = self.eid[i][:c[COUNT_EDGES(i)]]
         return dict(layers=layers, input_nodes=self.ht.n2o[:c[COUNT_INPUT(self.L)]])
